@@ -25,7 +25,9 @@ sharded over the ranks (strong scaling, 10 000 segments = 1250 per GPU at 8 GPUs
 Launch:  python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: spawns N ranks itself)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline line; the
+roofline, the `extra` blocks and the CPU baseline (with its parity check) run only with `--full`.
+`--dump-outputs DIR` writes what the last timed step handed its caller (token rows, notes) as .npy files.
 """
 import argparse
 import hashlib
@@ -88,7 +90,12 @@ def cpu_baseline(n_segments: int, decode_steps: int, enc_segments: int, small_se
     import torch
     from mt3_amd import network
     from oracle import frontend as OF, network as ON, symbolic as OS
-    nproc = os.cpu_count() or 1
+    # the CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS when set (a shared host shows all of
+    # its cores to os.cpu_count() while a job gets a share of them; threads beyond that share only slow the sample down)
+    nproc = len(os.sched_getaffinity(0)) or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        nproc = min(nproc, int(omp))
     cfg = network.T5Config(dtype="float32")
     params = network.init_random_params(cfg, seed=0)
     audio = OF.synth_audio(max(n_segments, enc_segments), seed=0)
@@ -244,6 +251,37 @@ def parity_rows(batch: int, n: int, groups: int):
     return sorted(set(rows))[:n]
 
 
+# ----------------------------------------------------------------------------------------- --dump-outputs
+DUMP_TOKEN_BYTES = 48 << 20          # with DUMP_NOTE_BYTES: at most 64 MB per dump, index arrays included
+DUMP_NOTE_BYTES = 15 << 20
+
+
+def dump_outputs(out_dir: str, last):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, on rank 0.  `last`: the host stage's
+    (token rows, note records) of every file of that step, in file order (= global segment order).  Writes
+      tokens.npy  float32 [segments, decode steps]: the decode_tf token rows (-1 from EOS on; ids are exact in float32)
+      notes.npy   float64 [notes, 7]: start_time, end_time, pitch, velocity, program, is_drum, instrument
+    Past their byte budget a fixed sample (seed 0) of rows is written instead, its row indices in tokens_rows.npy /
+    notes_rows.npy.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    tokens = np.concatenate([rows for rows, _ in last]).astype(np.float32)
+    rec = np.concatenate([r for _, r in last])
+    notes = np.stack([rec[f].astype(np.float64) for f in ("start_time", "end_time", "pitch", "velocity", "program",
+                                                          "is_drum", "instrument")], axis=1).reshape(-1, 7)
+    out = {}
+    for name, arr, budget in (("tokens", tokens, DUMP_TOKEN_BYTES), ("notes", notes, DUMP_NOTE_BYTES)):
+        if arr.nbytes > budget:
+            keep = budget // max(1, arr.itemsize * arr.shape[1])
+            idx = np.sort(np.random.default_rng(0).choice(arr.shape[0], keep, replace=False))
+            arr = arr[idx]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+            out[name + "_rows"] = list(idx.shape)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        out[name] = list(arr.shape)
+    return out
+
+
 # ----------------------------------------------------------------------------------------- rank spawning
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: run N ranks (one per GPU) under torch.distributed.run."""
@@ -295,8 +333,13 @@ def main():
     ap.add_argument("--file-segments", type=int, default=256,
                     help="the corpus is a list of files of this many consecutive segments (256 x 2.048 s = 8.7 min of "
                          "audio); host note decoding is sequential inside a file and parallel across files")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other-precision blocks and the stage (frontend/encoder) extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, the extras (other precisions, stages, EOS "
+                         "schedule, single file, noise) and the CPU baseline with its parity check; off: the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/tokens.npy and DIR/notes.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other-precision blocks and the stage (frontend/encoder) extras")
     ap.add_argument("--eos-mean", type=float, default=300.0, help="synthetic EOS schedule: mean output length (SURVEY 8d)")
     ap.add_argument("--eos-sd", type=float, default=100.0)
     ap.add_argument("--cpu-segments", type=int, default=8)
@@ -379,10 +422,10 @@ def main():
 
     def notes_of_file(rows, first):
         """EOS trim + run-length / note decoding of one file's token rows (C++ in libmt3hip.so; notes as a record array:
-        no Python object per note on the job's host stage)"""
+        no Python object per note on the job's host stage) -> (the rows, the notes): what a caller of the path receives"""
         rec, inv, drop, total = metrics_utils.decode_token_rows(codec, note_sequences.NoteEncodingWithTiesSpec, rows,
                                                                 start_times[first: first + len(rows)])
-        return len(rec)
+        return rows, rec
 
     def transcribe(first, count, engine=None):
         """frontend -> encode -> decode -> ids -> tokens for global segments [first, first + count): CUDA int32 [count, L]"""
@@ -426,7 +469,8 @@ def main():
             job.step()
 
     def drain():
-        return sum(job.drain())
+        """join the host stage: (token rows, notes) of every file of the last pass, in file order (rank 0; [] elsewhere)"""
+        return job.drain()
 
     def device_sync():
         if not dry:
@@ -446,7 +490,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
-    n_notes = drain()
+    last = drain()
     device_sync()
     dt_own = time.perf_counter() - t0                 # this rank's own time to finish its K steps
     sync_all()
@@ -461,6 +505,8 @@ def main():
         dist.all_gather(allr, mine)
         per_rank_ms = [float(t.item()) for t in allr]
         gather_ms = sum(a.elapsed_time(b) for a, b in gather_events) / max(1, len(gather_events))
+    n_notes = sum(len(rec) for _, rec in last)
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
     graph_fallbacks = used_graph = decode_groups = partition_fallbacks = 0
     if not dry:
         graph_fallbacks = eng.status(_lib.STATUS_GRAPH_FALLBACKS)
@@ -472,9 +518,9 @@ def main():
     # In-situ and live: HIP events (recorded on the stream the graphs are launched on) around the whole
     # graph-replayed decode, once as it ships and once with that kernel's launches left out of the step
     # graph (mt3_debug_engine_decode, include/mt3_hip_debug.h); the difference / launches = the kernel's average
-    # duration inside the real decode loop.
+    # duration inside the real decode loop.  Everything from here to the result line runs only with --full.
     roof, extras = None, {}
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         Br = min(B, n_local)
 
         def timed(fn, reps=1):
@@ -1075,7 +1121,7 @@ def main():
             "dtype": ("bf16" if args.dtype == "bfloat16" else "f32") + ("+fp8kv" if args.kv_dtype else "") +
                      ("+mxfp8 encoder" if args.dense_dtype else ""),
             "data": "synthetic" if not dry else "stub token rows (DRY RUN: no GPU work, the value measures nothing)",
-            "dry_run": bool(dry),
+            "dry_run": bool(dry), "full": bool(args.full), "dumped_outputs": dumped,
             "config": {"workload": workload,
                        "segments_per_gpu": n_local, "segments_total": n_global, "decode_steps": args.decode_steps,
                        "segment_seconds": SEG_SECONDS, "decode_chains": args.chains, "decoding": args.decoding,
@@ -1099,7 +1145,7 @@ def main():
             "roofline": roof,
             "extra": extras,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             parity_args = []
             if args.dtype == "float32" and args.model == "mt3" and not args.kv_dtype and not args.dense_dtype and not corpus:
                 # the rows the oracle will be compared on: the first cpu_segments rows of the headline batch, decoded once

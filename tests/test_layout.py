@@ -116,3 +116,29 @@ def test_bench_cpu_baseline_leg_runs_and_reports_the_contract_fields():
     d = json.loads(line[-1][len("CPU_BASELINE "):])
     assert d["unit"] == "audio-s/s" and d["kind"] == "port" and d["value"] > 0 and 1 <= d["cores"] <= 16
     assert "segments" in d["sample"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` line is the headline alone (no roofline, extras or CPU leg: those need --full), `--steps` is the
+    number of timed steps, and `--dump-outputs` writes the last step's token rows / notes as float .npy files that are
+    the same from run to run (dry run: the real host stage on stub token rows)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    lines = {}
+    for name, steps, warmup in (("a", 2, 1), ("b", 1, 0)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", str(steps), "--warmup",
+                            str(warmup), "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True,
+                           timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-500:]
+        lines[name] = d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["full"] is False
+        assert d["roofline"] is None and d["extra"] == {} and "cpu_baseline" not in d
+    tok = np.load(tmp_path / "a" / "tokens.npy")
+    notes = np.load(tmp_path / "a" / "notes.npy")
+    assert tok.dtype == np.float32 and tok.shape == (256, 1024) and notes.dtype == np.float64 and notes.shape[1] == 7
+    assert len(notes) == lines["a"]["config"]["notes_decoded_last_step"] > 0
+    assert lines["a"]["dumped_outputs"] == {"tokens": [256, 1024], "notes": list(notes.shape)}
+    for f in ("tokens.npy", "notes.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

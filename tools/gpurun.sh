@@ -3,8 +3,8 @@
 # gpurun_out/ with the round tag $TAG (default r6).  Stages:
 #   test [pytest args]   pytest -m gpu (TESTS = files / -k expression, default the whole suite)
 #   smoke                __graft_entry__.smoke()
-#   bench                the driver's bench command (BENCH_ARGS, default --gpus 1 --steps 20 --warmup 5) + digest
-#   prof                 rocprofv3 --kernel-trace --stats of the f32 bench command + trace digest
+#   bench                bench.py --full (BENCH_ARGS, default --gpus 1 --steps 20 --warmup 5) + digest
+#   prof                 rocprofv3 --kernel-trace --stats of the f32 bench.py --full command (roofline passes included) + trace digest
 #   tol                  tools/note_tolerance.py (TOL_ARGS)
 #   pmcdec               rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over tools/pmc_decode.py -> per-kernel HBM bytes (PMC_STEPS)
 #   pmcattn              the same two passes over tools/pmc_attn.py -> <TAG>_pmc_summary.json (roofline.traffic)
@@ -17,6 +17,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 R="$PWD"
 TAG="${TAG:-r6}"
 mkdir -p gpurun_out
+OUT="$R/$(basename "$0" .sh)_out"       # the folder every stage writes under
 export TMPDIR=/tmp
 for stage in "$@"; do
   t0=$(date +%s)
@@ -27,14 +28,14 @@ for stage in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
     bench)
-      timeout 1500 python bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} > "gpurun_out/${TAG}_bench.log" 2>&1
+      timeout 1500 python bench.py --full ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} > "$OUT/${TAG}_bench.log" 2>&1
       echo "exit $? : bench after $(( $(date +%s) - t0 )) s"
       grep '^{' "gpurun_out/${TAG}_bench.log" | tail -1 > "gpurun_out/${TAG}_bench.json"
       python tools/bench_digest.py < "gpurun_out/${TAG}_bench.json" 2>&1 | tail -40 ;;
     prof)
       rm -rf gpurun_out/prof; mkdir -p gpurun_out/prof
       ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof" -o "${TAG}_f32" -- \
-          python "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-extras > "$R/gpurun_out/${TAG}_bench_prof.log" 2>&1 )
+          python "$R/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/${TAG}_bench_prof.log" 2>&1 )
       echo "exit $? : rocprof bench after $(( $(date +%s) - t0 )) s"
       f=$(find gpurun_out/prof -name "${TAG}_f32_kernel_stats.csv" | head -1)
       [ -n "$f" ] && cp "$f" "gpurun_out/${TAG}_f32_kernel_stats.csv" && head -8 "$f" | cut -c1-180
