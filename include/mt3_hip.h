@@ -247,6 +247,41 @@ int mt3_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t f
  * finalisation before it) and reports errors of the decode loop.  MT3_ERR_INVALID when no decode is in flight. */
 int mt3_engine_decode_wait(mt3_engine* e, int32_t* h_steps_run);
 
+/* k-beam search: t5x decoding.beam_search(alpha = 0.6) with num_decodes = num_beams = k, 1 <= k <= 8 -- the reference's
+ * decode_fn (mt3/models.py:126-127), reached in t5x through predict_batch_with_aux(..., num_decodes=k,
+ * return_all_decodes=...).  The rule, written down from memory [from memory: t5x is not at hand; SURVEY.md A.5 has
+ * the same status], with NEG_INF = -1e7 and bp(n) = ((5 + n) / 6) ^ 0.6:
+ *   start       the k live beams of an element have log-probs [0, NEG_INF, ...] (step 0 expands beam 0 only); the k
+ *               finished entries have score NEG_INF (unfilled).
+ *   candidates  per step, log_softmax of each live beam's logits plus the beam's log-prob; the top 2k of the k*V
+ *               candidates, ties to the lower flattened index beam*V + token (lax.top_k).
+ *   finished    a candidate ending in EOS scores logp / bp(t + 1); the k old entries and the new ones are merged and the
+ *               k best kept (the old entry on equal scores).
+ *   live        the k best candidates not ending in EOS are the new live beams (parent beam + token each).
+ *   retirement  an element is retired once its k-th best finished score exceeds its best live log-prob / bp(num_steps + 1):
+ *               no later candidate can enter its finished set, so its state is final.  The decode runs num_steps steps, or
+ *               with MT3_DECODE_EARLY_EXIT until every element is retired.
+ *   result      an element with no finished entry returns its k live beams and their log-probs; one with at least one
+ *               returns its finished set only (unfilled entries: score NEG_INF, all-zero ids).  The k decodes come back
+ *               in INCREASING order of score, the best last (as t5x returns them); every decode is padded with 0 after
+ *               its EOS.  At k = 1 this is MT3_DECODE_BEAM1, and the ids are bit-identical to it.
+ * The candidates' log-softmax is computed per beam in the order MT3_DECODE_BEAM1 uses; within a beam the candidates are
+ * ranked by logit (lower id on ties), so an exact tie of two rounded scores in one beam goes to the larger logit.
+ * Input: the preceding mt3_engine_encode must have encoded batch * num_beams rows, rows b*k .. b*k + k - 1 all holding
+ * segment b (each segment encoded k times in a row: its cross-attention K/V then sit in the cache rows of its k beams).
+ * d_ids [batch, L] int32: the best decode.  d_all_ids [batch, k, L] int32 or NULL: all k decodes.  d_scores [batch, k]
+ * f32 or NULL: their scores (finished: logp / bp(length incl. EOS); live: logp).  h_steps_run (may be NULL): the steps run.
+ * flags: MT3_DECODE_NO_GRAPH, MT3_DECODE_EARLY_EXIT, MT3_DECODE_SINGLE_STREAM; any other bit, num_beams outside 1 .. 8,
+ * batch * num_beams > max_batch, or a vocabulary larger than 2048 returns MT3_ERR_INVALID.  The step is one captured
+ * graph per row group (the schedule of mt3_engine_decode on batch * k rows; every group boundary is a multiple of k).
+ * Each step ends with the beam step and a cache-row pass: a beam whose parent has one child takes over the parent's
+ * self-attention cache row (only the slot -> row map changes); the further children of a parent take the rows of
+ * parents nobody chose and get positions [0, t] of the parent's K/V copied into them, for every layer and head (with
+ * e4m3 caches the scale rows as well) -- MT3_STATUS_LAST_DECODE_FORKS counts those copies.  The call returns when the
+ * decode is complete on the device. */
+int mt3_engine_decode_beams(mt3_engine* e, int32_t batch, int32_t num_beams, int32_t num_steps, int32_t flags,
+                            int32_t* d_ids, int32_t* d_all_ids, float* d_scores, int32_t* h_steps_run, void* stream);
+
 /* Streaming transcription with IN-FLIGHT BATCHING: encode + decode of n_segments independent segments (any number;
  * the reference's loop over `.batch(8)` calls of predict_batch_with_aux, NB:295-301, mt3/models.py:121-152) through the
  * engine's max_batch decode SLOTS.  The reference's decode is batch-synchronous -- a batch ends when its LAST row has
@@ -300,7 +335,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_QKV_FOLD = 6 /* the decoder layers' q/k/v projections folded into the preceding launches */,
        MT3_STATUS_LAST_DECODE_GROUPS = 7 /* row groups of the most recent decode (2 or 4: the row-group schedule); 1: on the caller's stream */,
        MT3_STATUS_PARTITION_FALLBACKS = 8 /* decodes that wanted the row-group schedule but could not set it up */,
-       MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */ };
+       MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */,
+       MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the

@@ -25,7 +25,8 @@ OPT_SPIN_WAITS = 64
 DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
- STATUS_LAST_DECODE_COMPACTIONS) = range(10)
+ STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS) = range(11)
+MAX_BEAMS = 8                                  # mt3_engine_decode_beams: 1 <= num_beams <= 8
 EV_SHIFT, EV_PITCH, EV_VELOCITY, EV_TIE, EV_PROGRAM, EV_DRUM = range(6)
 EVENT_TYPE_NAMES = ("shift", "pitch", "velocity", "tie", "program", "drum")
 SPEC_ONSETS, SPEC_NOTES, SPEC_TIES = range(3)
@@ -86,6 +87,8 @@ SIGNATURES = {
     "mt3_engine_encode": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "mt3_engine_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32), _P]),
     "mt3_engine_decode_wait": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "mt3_engine_decode_beams": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                          C.POINTER(C.c_int32), _P]),
     "mt3_engine_transcribe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(TranscribeStats), _P]),
     "mt3_engine_decode_forced": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_engine_status": (C.c_int, [_P, C.c_int32]),

@@ -10,6 +10,9 @@
 //                       of t5x beam_search with num_decodes=1 (top-2 of log_softmax, live/finished sets).
 //                       Positions are PER-ROW device counters (no cross-row sync), so ONE captured
 //                       hipGraph serves every step; the block also writes the next step's embedding row.
+//   beam_step_kernel    one step of t5x beam_search with num_decodes = k (mt3_engine_decode_beams): one wave per live
+//                       beam, the k * 2k candidates merged in LDS, the slot -> cache-row map rewritten; with
+//                       beam_reorder_kernel (K/V copies of forked rows) and beam_finalize_kernel (history backtrack).
 //   ids_to_tokens_kernel GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271), bit-exact.
 #include <hip/hip_runtime.h>
 
@@ -578,6 +581,358 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(refill_cross_kernel, dim3(a.n_new, a.n_layers * 3, parts), dim3(256), 0, s, a, parts);
   }
   hipLaunchKernelGGL(refill_slot_kernel, dim3(a.rows), dim3(128), 0, s, a);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- k-beam search
+// One step of t5x beam_search with k = num_decodes (the rule: include/mt3_hip.h, mt3_engine_decode_beams).  One block of
+// k waves per batch element, wave w = the live beam in slot b*k + w.
+//   1. each wave holds its logits row in registers and computes log-sum-exp in EXACTLY the order of
+//      argmax_step_kernel<true> (four "virtual threads" per lane stand for that kernel's 256 threads), so that k = 1
+//      reproduces MT3_DECODE_BEAM1 bit for bit;
+//   2. each wave takes its own top 2k by logit (lower id on ties) and scores them live + logp;
+//   3. wave 0 merges the k * 2k scored candidates in LDS (higher score first; on equal scores the lower flattened index
+//      beam * V + token, taken in the order of step 2 inside a beam), then lane 0 updates the live and finished sets,
+//      the history, the slot -> cache-row map (a beam takes over its parent's row; the extra children of a parent take
+//      the rows of parents nobody chose and are marked for beam_reorder_kernel) and the retirement;
+//   4. each wave writes its slot's next input row, as the greedy / beam-1 kernel does.
+__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, RowProj rp, LogitScale ls) {
+  constexpr int kPerLane = 32;                         // vocab <= 2048: lane l holds i = l + 64 * vt + 256 * u
+  __shared__ float c_score[2 * kBeamMaxK * kBeamMaxK];
+  __shared__ int c_tok[2 * kBeamMaxK * kBeamMaxK];
+  __shared__ int s_sel[2 * kBeamMaxK];
+  __shared__ int s_tok[kBeamMaxK];
+  const int k = a.k, k2 = 2 * k, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int s0 = blockIdx.x * k, slot = s0 + w;
+  if (a.done[s0]) return;                              // retired element: its state is final
+  const int t = a.step[s0];
+  const float* row = a.logits + static_cast<size_t>(slot) * a.vocab;
+  float xv[kPerLane];
+#pragma unroll
+  for (int j = 0; j < kPerLane; ++j) {
+    const int i = lane + 64 * (j >> 3) + 256 * (j & 7);
+    xv[j] = row[i < a.vocab ? i : a.vocab - 1];
+  }
+  const float live = a.live[slot];
+  if (ls.ss) {                                         // folded logits projection (LogitScale)
+    float p = lane < ls.n_ss ? ls.ss[static_cast<size_t>(slot) * ls.n_ss + lane] : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
+    const float rs = rsqrtf(p / static_cast<float>(ls.dim) + 1e-6f);
+#pragma unroll
+    for (int j = 0; j < kPerLane; ++j) xv[j] *= rs;
+  }
+  // log-sum-exp of the row, in argmax_step_kernel<true>'s order: per thread, per wave, then over the four waves
+  float vmax[4], vsum[4];
+#pragma unroll
+  for (int vt = 0; vt < 4; ++vt) {
+    float m = -3.0e38f, acc = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (lane + 64 * vt + 256 * u < a.vocab && xv[vt * 8 + u] > m) m = xv[vt * 8 + u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (lane + 64 * vt + 256 * u < a.vocab) acc += __expf(xv[vt * 8 + u] - m);
+    float wm = m;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o));
+    acc *= __expf(m - wm);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    vmax[vt] = wm;
+    vsum[vt] = acc;
+  }
+  float bm = vmax[0];
+#pragma unroll
+  for (int vt = 1; vt < 4; ++vt)
+    if (vmax[vt] > bm) bm = vmax[vt];
+  float sum = 0.f;
+#pragma unroll
+  for (int vt = 0; vt < 4; ++vt) sum += vsum[vt] * __expf(vmax[vt] - bm);
+  const float lse = bm + __logf(sum);
+  // this beam's top 2k by logit: 2k rounds of a wave arg-max over the values not yet taken
+  unsigned taken = 0u;
+  for (int r = 0; r < k2; ++r) {
+    float bv = -3.0e38f;
+    int bi = 0x7fffffff, bj = -1;
+#pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+      const int i = lane + 64 * (j >> 3) + 256 * (j & 7);
+      if (i < a.vocab && !((taken >> j) & 1u) && cand_better(xv[j], i, bv, bi)) {
+        bv = xv[j];
+        bi = i;
+        bj = j;
+      }
+    }
+    float wv = bv;
+    int wi = bi;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(wv, o);
+      const int oi = __shfl_xor(wi, o);
+      if (cand_better(ov, oi, wv, wi)) {
+        wv = ov;
+        wi = oi;
+      }
+    }
+    if (bj >= 0 && bi == wi) taken |= 1u << bj;       // the lane that owns the winner
+    if (lane == 0) {
+      c_score[w * k2 + r] = live + (wv - lse);
+      c_tok[w * k2 + r] = wi;
+    }
+  }
+  __syncthreads();
+  if (w == 0) {
+    // the 2k best of the k * 2k candidates; candidate index e = beam * 2k + rank orders ties as the flattened index does
+    const int n = k * k2;
+    unsigned sel = 0u;
+    for (int r = 0; r < k2; ++r) {
+      float bv = -3.0e38f;
+      int be = 0x7fffffff;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int e = lane + 64 * h;
+        if (e < n && !((sel >> h) & 1u) && cand_better(c_score[e], e, bv, be)) {
+          bv = c_score[e];
+          be = e;
+        }
+      }
+      float wv = bv;
+      int we = be;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(wv, o);
+        const int oe = __shfl_xor(we, o);
+        if (cand_better(ov, oe, wv, we)) {
+          wv = ov;
+          we = oe;
+        }
+      }
+      if (be == we && be != 0x7fffffff) sel |= 1u << ((we - lane) >> 6);
+      if (lane == 0) s_sel[r] = we;
+    }
+    if (lane == 0) {
+      const float bp_t = a.bp[1 + t + 1], bp_max = a.bp[0];
+      // the new live beams: the k best candidates that do not end in EOS (at most k of the 2k do)
+      float nl_score[kBeamMaxK];
+      int nl_par[kBeamMaxK];
+      float nf_score[2 * kBeamMaxK];
+      int nf_par[2 * kBeamMaxK];
+      int nlive = 0;
+      for (int r = 0; r < k2; ++r) {
+        const int e = s_sel[r], tok = c_tok[e], par = e / k2;
+        const float sc = c_score[e];
+        if (tok == 1) {
+          nf_score[r] = sc / bp_t;
+          nf_par[r] = par;
+        } else {
+          nf_score[r] = kBeamNegInf;
+          nf_par[r] = -1;
+          if (nlive < k) {
+            nl_score[nlive] = sc;
+            nl_par[nlive] = par;
+            s_tok[nlive] = tok;
+            ++nlive;
+          }
+        }
+      }
+      // finished set: the k best of [old k entries | this step's 2k], the lower index on equal scores
+      float of_score[kBeamMaxK];
+      int of_step[kBeamMaxK], of_beam[kBeamMaxK];
+      for (int j = 0; j < k; ++j) {
+        of_score[j] = a.fin_score[s0 + j];
+        of_step[j] = a.fin_step[s0 + j];
+        of_beam[j] = a.fin_beam[s0 + j];
+      }
+      unsigned used = 0u;
+      float kth = kBeamNegInf;
+      int kth_step = -1;
+      for (int q = 0; q < k; ++q) {
+        int best = -1;
+        float bs = 0.f;
+        for (int x = 0; x < k + k2; ++x) {
+          if ((used >> x) & 1u) continue;
+          const float sc = x < k ? of_score[x] : nf_score[x - k];
+          if (best < 0 || sc > bs) {
+            best = x;
+            bs = sc;
+          }
+        }
+        used |= 1u << best;
+        const int st = best < k ? of_step[best] : (nf_par[best - k] >= 0 ? t : -1);
+        const int bb = best < k ? of_beam[best] : nf_par[best - k];
+        a.fin_score[s0 + q] = bs;
+        a.fin_step[s0 + q] = st;
+        a.fin_beam[s0 + q] = st >= 0 ? bb : -1;
+        kth = bs;
+        kth_step = st;
+      }
+      // cache rows: the first child of a parent takes the parent's row, every further child a row nobody chose
+      int orow[kBeamMaxK], nchild[kBeamMaxK];
+      for (int j = 0; j < k; ++j) {
+        orow[j] = a.slot_row[s0 + j];
+        nchild[j] = 0;
+      }
+      for (int j = 0; j < k; ++j) ++nchild[nl_par[j]];
+      int free_row[kBeamMaxK], nfree = 0, forks = 0;
+      for (int j = 0; j < k; ++j)
+        if (nchild[j] == 0) free_row[nfree++] = orow[j];
+      unsigned claimed = 0u;
+      int nfree_used = 0;
+      int* par_out = a.hist_par + static_cast<size_t>(t) * a.hist_stride + s0;
+      int* tok_out = a.hist_tok + static_cast<size_t>(t) * a.hist_stride + s0;
+      const bool retired = kth_step >= 0 && kth > nl_score[0] / bp_max;
+      for (int j = 0; j < k; ++j) {
+        const int p = nl_par[j];
+        int nrow, src = -1;
+        if (!((claimed >> p) & 1u)) {
+          claimed |= 1u << p;
+          nrow = orow[p];
+        } else {
+          nrow = free_row[nfree_used++];
+          src = orow[p];
+          ++forks;
+        }
+        a.slot_row[s0 + j] = nrow;
+        a.fork_src[s0 + j] = src;
+        par_out[j] = p;
+        tok_out[j] = s_tok[j];
+        a.live[s0 + j] = nl_score[j];
+        a.cur_tok[s0 + j] = s_tok[j];
+        a.step[s0 + j] = t + 1;
+        if (retired) a.done[s0 + j] = 1;
+      }
+      if (forks && !retired) atomicAdd(a.fork_count, forks);   // a retired element's forks are never copied
+      if (retired) atomicAdd(a.n_done, k);
+    }
+  }
+  __syncthreads();
+  // the next step's input row of this wave's slot: Embed(tok) + FixedEmbed[t+1]
+  if (a.y_next) {
+    const int tok = s_tok[w], tp = t + 1 < a.max_pos ? t + 1 : a.max_pos - 1;
+    const float* e = a.table + static_cast<size_t>(tok) * a.dim;
+    const float* p = a.pos_table + static_cast<size_t>(tp) * a.dim;
+    for (int i = lane * 4; i < a.dim; i += 256) {
+      const float4 x = *reinterpret_cast<const float4*>(e + i), c = *reinterpret_cast<const float4*>(p + i);
+      put_row_piece(make_float4(x.x + c.x, x.y + c.y, x.z + c.z, x.w + c.w), a.y_next, a.y_ct, a.y_ss, slot, a.dim, i);
+    }
+    if (rp.q_out) put_row_projection(rp, slot, tok, tp, lane, 64);
+  }
+}
+
+int launch_beam_step(const BeamKArgs& a, const RowProj& rp, const LogitScale& ls, hipStream_t s) {
+  if (a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || a.vocab < 2 * a.k || a.vocab > 2048)
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: k must be 1 .. 8 and 2k <= vocab <= 2048");
+  if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.slot_row ||
+      !a.fork_src || !a.fork_count || !a.done || !a.n_done || !a.step || !a.cur_tok || !a.bp)
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: missing state");
+  if (ls.ss && (ls.n_ss <= 0 || ls.n_ss > 64 || ls.dim <= 0))
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: the row scale needs 1 .. 64 partial sums");
+  if (a.y_next && (a.dim % 16 || ((a.y_ct || a.y_ss) && !a.y_ss)))
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: the next input row needs dim % 16 == 0 and y_ss with the split form");
+  if (rp.q_out && (!a.y_next || !rp.ew || !rp.pw || rp.q_n % 4))
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: row projection needs the next-row output and its tables");
+  hipLaunchKernelGGL(beam_step_kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, rp, ls);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
+// block (slot, layer * H + head): a slot that did not fork this step returns at once
+__global__ __launch_bounds__(256) void beam_reorder_kernel(BeamReorderArgs a) {
+  const int slot = blockIdx.x, l = blockIdx.y / a.H, h = blockIdx.y % a.H;
+  const int src = a.fork_src[slot];
+  if (src < 0 || a.done[slot]) return;
+  const int dst = a.slot_row[slot], n = a.step[slot];     // positions [0, t] = [0, step)
+  const size_t pos_bytes = static_cast<size_t>(64) * a.kv_esize;
+  const size_t so = (static_cast<size_t>(src) * a.H + h) * a.cap, dof = (static_cast<size_t>(dst) * a.H + h) * a.cap;
+  const size_t n16 = static_cast<size_t>(n) * pos_bytes / 16;
+  const uint4* ks = reinterpret_cast<const uint4*>(a.k[l] + so * pos_bytes);
+  const uint4* vs = reinterpret_cast<const uint4*>(a.v[l] + so * pos_bytes);
+  uint4* kd = reinterpret_cast<uint4*>(a.k[l] + dof * pos_bytes);
+  uint4* vd = reinterpret_cast<uint4*>(a.v[l] + dof * pos_bytes);
+  for (size_t i = threadIdx.x; i < n16; i += 256) {
+    const uint4 x = ks[i], y = vs[i];
+    kd[i] = x;
+    vd[i] = y;
+  }
+  if (a.scale[l])
+    for (int i = threadIdx.x; i < n; i += 256) a.scale[l][dof + i] = a.scale[l][so + i];
+}
+
+int launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s) {
+  if (a.n_layers <= 0 || a.n_layers > kRefillMaxLayers || a.H <= 0 || a.cap <= 0 || a.slots <= 0 ||
+      (a.kv_esize != 1 && a.kv_esize != 2 && a.kv_esize != 4) || !a.fork_src || !a.slot_row || !a.step || !a.done)
+    return mt3::fail(MT3_ERR_INVALID, "beam_reorder: bad arguments");
+  for (int l = 0; l < a.n_layers; ++l)
+    if (!a.k[l] || !a.v[l]) return mt3::fail(MT3_ERR_INVALID, "beam_reorder: missing cache");
+  hipLaunchKernelGGL(beam_reorder_kernel, dim3(a.slots, a.n_layers * a.H), dim3(256), 0, s, a);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
+__global__ void beam_init_kernel(float* live, float* fin_score, int* fin_step, int* fin_beam, int slots, int k) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= slots) return;
+  live[i] = i % k == 0 ? 0.f : kBeamNegInf;
+  fin_score[i] = kBeamNegInf;
+  fin_step[i] = -1;
+  fin_beam[i] = -1;
+}
+
+int launch_beam_init(float* live, float* fin_score, int* fin_step, int* fin_beam, int slots, int k, hipStream_t s) {
+  if (!live || !fin_score || !fin_step || !fin_beam || slots <= 0 || k < 1 || slots % k)
+    return mt3::fail(MT3_ERR_INVALID, "beam_init: bad arguments");
+  hipLaunchKernelGGL(beam_init_kernel, dim3((slots + 255) / 256), dim3(256), 0, s, live, fin_score, fin_step, fin_beam,
+                     slots, k);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
+// block (element b, output decode i): decode i of the result is state entry k - 1 - i (the state is best first, the
+// result in increasing order of score).  The history is walked back from the entry's last step by one thread.
+__global__ __launch_bounds__(256) void beam_finalize_kernel(BeamKArgs a, int L, int num_steps, int* ids, int* all_ids,
+                                                           float* scores) {
+  const int b = blockIdx.x, i = blockIdx.y, k = a.k, s0 = b * k, e = k - 1 - i;
+  int* out_all = all_ids ? all_ids + (static_cast<size_t>(b) * k + i) * L : nullptr;
+  int* out_best = i == k - 1 ? ids + static_cast<size_t>(b) * L : nullptr;
+  for (int u = threadIdx.x; u < L; u += 256) {
+    if (out_all) out_all[u] = 0;
+    if (out_best) out_best[u] = 0;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const bool any_finished = a.fin_step[s0] >= 0;
+  float score;
+  int u, j;
+  if (any_finished) {
+    score = a.fin_score[s0 + e];
+    u = a.fin_step[s0 + e];
+    j = a.fin_beam[s0 + e];
+    if (u >= 0) {
+      if (out_all) out_all[u] = 1;
+      if (out_best) out_best[u] = 1;
+    }
+    --u;                                                // u = -2 for an unfilled entry: nothing to walk
+  } else {
+    score = a.live[s0 + e];
+    u = num_steps - 1;
+    j = e;
+  }
+  for (; u >= 0; --u) {
+    const size_t x = static_cast<size_t>(u) * a.hist_stride + s0 + j;
+    const int tok = a.hist_tok[x];
+    j = a.hist_par[x];
+    if (out_all) out_all[u] = tok;
+    if (out_best) out_best[u] = tok;
+  }
+  if (scores) scores[static_cast<size_t>(b) * k + i] = score;
+}
+
+int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int* all_ids, float* scores, hipStream_t s) {
+  if (!ids || a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || L <= 0 || num_steps <= 0 || num_steps > L)
+    return mt3::fail(MT3_ERR_INVALID, "beam_finalize: bad arguments");
+  hipLaunchKernelGGL(beam_finalize_kernel, dim3(a.elems, a.k), dim3(256), 0, s, a, L, num_steps, ids, all_ids, scores);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }

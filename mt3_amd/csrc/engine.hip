@@ -56,6 +56,7 @@ namespace {
 
 constexpr int kMaxPos = 2048;   // FixedEmbed.max_length, layers.py:565
 constexpr int kMaxChains = 8;
+constexpr int kForksPinned = 15;  // h_pinned[15]: fork count of the last beam decode (h_pinned[0 .. kMaxGroups): polls)
 
 uint16_t f32_to_bf16_bits(float f) {
   uint32_t u;
@@ -106,6 +107,9 @@ constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarS
 // row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
 // keeps such steps apart from a lone stream's steps of the same shape
 constexpr int kVarBeside = 128;
+// not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
+// number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
+constexpr int kVarBeams = 256, kVarBeamsShift = 9;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
 // to kStageChunkCap segments each (one encoder pass per chunk)
@@ -145,6 +149,10 @@ struct PendingDecode {
   int batch = 0;
   int32_t* d_ids = nullptr;
   hipStream_t s = nullptr;
+  int beams = 0;                // mt3_engine_decode_beams: k (0: mt3_engine_decode)
+  int num_steps = 0;
+  int32_t* d_all_ids = nullptr;
+  float* d_scores = nullptr;
   int rcs[kMaxGroups] = {};
   int ran[kMaxGroups] = {};
   std::string errs[kMaxGroups];
@@ -265,6 +273,15 @@ struct mt3_engine {
   int* beam_len = nullptr;       // [max_batch] per slot
   int* beam_len_row = nullptr;   // [max_batch] per row (read by the finalisation)
   float* beam_cfg = nullptr;     // [0] brevity penalty of the loop bound, [1 + n] brevity_penalty(n)
+  // k-beam search (mt3_engine_decode_beams; allocated by its first call): slot-indexed state and the per-step history
+  float* bk_live = nullptr;      // [max_batch]
+  float* bk_fin_score = nullptr; // [max_batch]: k entries per element
+  int* bk_fin_step = nullptr;
+  int* bk_fin_beam = nullptr;
+  int* bk_fork_src = nullptr;    // [max_batch]
+  int* bk_forks = nullptr;       // [1] forks of the decode in flight
+  int* bk_par = nullptr;         // [L][max_batch]
+  int* bk_tok = nullptr;         // [L][max_batch]
 
   // Row-group decode schedule (round 3): the batch as 2 or 4 row groups (row_groups_for), each on an engine-owned stream
   // with a hardware queue of its own, each driven by its own host thread with direct launches -- one group's HBM-bound
@@ -630,6 +647,29 @@ inline bool chain_op_is_heavy(const mt3_engine* e, int op) {
   return op < 8 * e->cfg.num_decoder_layers && ((op & 7) == 1 || (op & 7) == 4);
 }
 
+// the k-beam state of slots [row0, row0 + rows) (the kernel-side pointers are those of the first slot)
+mt3k::BeamKArgs beam_args(mt3_engine* e, int row0, int rows, int k) {
+  mt3k::BeamKArgs b{};
+  b.vocab = e->cfg.vocab_size;
+  b.k = k;
+  b.elems = rows / k;
+  b.live = e->bk_live + row0;
+  b.fin_score = e->bk_fin_score + row0;
+  b.fin_step = e->bk_fin_step + row0;
+  b.fin_beam = e->bk_fin_beam + row0;
+  b.hist_par = e->bk_par + row0;
+  b.hist_tok = e->bk_tok + row0;
+  b.hist_stride = e->cfg.max_batch;
+  b.slot_row = e->slot_row + row0;
+  b.fork_src = e->bk_fork_src + row0;
+  b.fork_count = e->bk_forks;
+  b.done = e->done + row0;
+  b.step = e->step + row0;
+  b.cur_tok = e->cur_tok + row0;
+  b.bp = e->beam_cfg;
+  return b;
+}
+
 int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, int op, hipStream_t s, int done_slot = 0) {
   const mt3_engine_config& c = e->cfg;
   const int dt = c.compute_dtype, emb = c.emb_dim, hd = e->HD(), H = c.num_heads, T = c.input_length;
@@ -692,6 +732,38 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     if (fold) return MT3_OK;                  // the logits projection rode in the last layer's MLP out-projection launch
     return mt3k::launch_gemm(dt, normed(e->logits_w, logits, c.vocab_size, c.vocab_size), !split, nrm, MT3_EPI_F32,
                              small, s);
+  }
+  if (op == 8 * nl + 1 && (skip & kVarBeams)) {
+    // k-beam search: the beam step, then the cache-row copies of the beams that forked
+    mt3k::BeamKArgs b = beam_args(e, row0, rows, (skip >> kVarBeamsShift) & 15);
+    b.logits = logits;
+    b.n_done = e->n_done + done_slot;
+    b.table = e->embedding;
+    b.pos_table = e->pos_table;
+    b.max_pos = kMaxPos;
+    b.y_next = y_buf(0);
+    b.y_ct = split && !f32 ? yct_buf(0) : nullptr;
+    b.y_ss = y_ss;
+    b.dim = emb;
+    const mt3k::RowProj rp{e->ew0, e->pw0, qkvf, 4 * hd};
+    const mt3k::LogitScale ls{fold ? y_ss : nullptr, emb / 16, emb};
+    MT3_TRY(mt3k::launch_beam_step(b, rp, ls, s));
+    mt3k::BeamReorderArgs r{};
+    r.n_layers = nl;
+    r.H = H;
+    r.cap = Lmax;
+    r.kv_esize = static_cast<int>(kes);
+    r.slots = rows;
+    for (int l = 0; l < nl; ++l) {                   // cache bases of the whole batch: slot_row holds batch rows
+      r.k[l] = static_cast<char*>(e->dec[l].self_k);
+      r.v[l] = static_cast<char*>(e->dec[l].self_v);
+      r.scale[l] = e->kv_fp8 ? e->dec[l].self_scale : nullptr;
+    }
+    r.fork_src = e->bk_fork_src + row0;
+    r.slot_row = e->slot_row + row0;
+    r.step = step;
+    r.done = e->done + row0;
+    return mt3k::launch_beam_reorder(r, s);
   }
   if (op == 8 * nl + 1) {
     const mt3k::BeamState beam{e->beam_f + row0, e->beam_len + row0, e->beam_cfg, c.max_batch, e->beam_len_row + crow0};
@@ -1173,6 +1245,7 @@ int mt3_engine_finalize(mt3_engine* e) {
     MT3_HIP_CHECK(hipMemcpy(e->beam_cfg, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
   }
   MT3_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_pinned), 64, hipHostMallocDefault));
+  e->h_pinned[kForksPinned] = 0;
   e->raw.clear();
   e->finalized = true;
   return MT3_OK;
@@ -1607,7 +1680,7 @@ static int run_group(mt3_engine* e, GroupRun& r) {
       MT3_HIP_CHECK(wait_stream(e, wslot, r.s));
       const int live = r.rows - e->h_pinned[r.slot];
       if (live <= 0) break;
-      if (retire) {
+      if (retire && !(r.variant & kVarBeams)) {    // beam groups stay where they are (their rows are k-slot units)
         int want = (live + 31) & ~31;
         if (want > r.rows) want = r.rows;
         if (want < cur) {                        // the live rows fit fewer GEMM row tiles: move them to the front
@@ -1658,8 +1731,15 @@ static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
     most = p.ran[g] > most ? p.ran[g] : most;
   }
   const int L = e->cfg.max_decode_len;
-  if (p.beam1) MT3_TRY(mt3k::launch_beam1_finalize(e->ids, L, e->beam_len_row, p.batch, p.s));
-  MT3_HIP_CHECK(hipMemcpyAsync(p.d_ids, e->ids, static_cast<size_t>(p.batch) * L * 4, hipMemcpyDeviceToDevice, p.s));
+  if (p.beams) {
+    // k-beam search: the results are walked back from the history straight into the caller's buffers
+    mt3k::BeamKArgs b = beam_args(e, 0, p.batch * p.beams, p.beams);
+    MT3_TRY(mt3k::launch_beam_finalize(b, L, p.num_steps, p.d_ids, p.d_all_ids, p.d_scores, p.s));
+    MT3_HIP_CHECK(hipMemcpyAsync(e->h_pinned + kForksPinned, e->bk_forks, 4, hipMemcpyDeviceToHost, p.s));
+  } else {
+    if (p.beam1) MT3_TRY(mt3k::launch_beam1_finalize(e->ids, L, e->beam_len_row, p.batch, p.s));
+    MT3_HIP_CHECK(hipMemcpyAsync(p.d_ids, e->ids, static_cast<size_t>(p.batch) * L * 4, hipMemcpyDeviceToDevice, p.s));
+  }
   e->last_groups = p.groups;
   e->last_used_graph = 1;
   for (int g = 0; g < p.groups; ++g)
@@ -1838,6 +1918,138 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   body();
   if (async) return MT3_OK;
   return decode_finish(e, h_steps_run);
+}
+
+// ----------------------------------------------------------------------------------------------- k-beam search
+// mt3_engine_decode_beams: the decode loop of mt3_engine_decode with the beam step (decode_ops.hip: beam_step_kernel +
+// beam_reorder_kernel) as the last launches of every step.  Slots b*k .. b*k + k - 1 are the beams of element b; the
+// slot -> cache-row map of row retirement is always in use (a beam takes over its parent's cache row), compaction
+// never is (beam groups stay in place), and a retired element's k slots are `done` from the step after it retired.
+static int ensure_beam_state(mt3_engine* e) {
+  if (e->bk_live) return MT3_OK;
+  const size_t Bm = static_cast<size_t>(e->cfg.max_batch), L = static_cast<size_t>(e->cfg.max_decode_len);
+  int rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_fin_score), Bm * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_fin_step), Bm * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_fin_beam), Bm * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_fork_src), Bm * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_forks), 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_par), L * Bm * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->bk_tok), L * Bm * 4))) return rc;
+  return dmalloc(e, reinterpret_cast<void**>(&e->bk_live), Bm * 4);     // last: it marks the set as complete
+}
+
+static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t num_steps, int32_t flags, int32_t* d_ids,
+                             int32_t* d_all_ids, float* d_scores, int32_t* h_steps_run, hipStream_t s) {
+  if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: engine not finalized");
+  if (e->pending.active)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+  const mt3_engine_config& c = e->cfg;
+  if (k < 1 || k > mt3k::kBeamMaxK) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: num_beams must be 1 .. 8");
+  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_EARLY_EXIT | MT3_DECODE_SINGLE_STREAM))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: flags other than NO_GRAPH / EARLY_EXIT / SINGLE_STREAM");
+  if (batch <= 0 || static_cast<int64_t>(batch) * k > c.max_batch)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: batch * num_beams must be 1 .. max_batch");
+  if (batch * k != e->cur_batch)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: the preceding encode must hold each of the batch's "
+                                      "segments num_beams times in a row (batch * num_beams rows)");
+  if (num_steps <= 0 || num_steps > c.max_decode_len || !d_ids)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: num_steps out of range or null ids");
+  if (c.vocab_size > 2048 || c.vocab_size < 2 * k)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: the beam step needs 2 * num_beams <= vocab <= 2048");
+  if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: more than 16 decoder layers");
+  MT3_TRY(ensure_beam_state(e));
+  const int slots = batch * k;
+  const bool early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
+  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(slots) * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->done, 0, static_cast<size_t>(slots) * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(slots) * 4, s));     // BOS = 0
+  MT3_HIP_CHECK(hipMemsetAsync(e->bk_forks, 0, 4, s));
+  {
+    const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
+    MT3_TRY(mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
+                               c.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, slots, c.emb_dim, rp, s));
+  }
+  MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
+  MT3_TRY(mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s));
+  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // as MT3_DECODE_BEAM1
+  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift);
+  if (e->group_graphs.size() > 96) drop_group_graphs(e);
+  PendingDecode& p = e->pending;
+  p = PendingDecode();
+  p.beams = k;
+  p.num_steps = num_steps;
+  p.batch = batch;
+  p.d_ids = d_ids;
+  p.d_all_ids = d_all_ids;
+  p.d_scores = d_scores;
+  p.s = s;
+  const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
+  // the row-group schedule of mt3_engine_decode, on B * k rows, with every group boundary on a beam-group boundary
+  int groups = row_groups_for(c, slots, early);
+  if (groups > batch) groups = 1;
+  if (groups > 1 && !(flags & MT3_DECODE_SINGLE_STREAM) && c.decode_chains <= 1 && !(c.options & MT3_OPT_NO_ROW_GROUPS)) {
+    if (ensure_group_streams(e, groups) == MT3_OK) {
+      MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
+      p.groups = groups;
+      p.active = true;
+      for (int g = 0; g < groups; ++g) {
+        auto body = [e, g, groups, batch, k, slots, variant, num_steps, early, use_graph]() {
+          PendingDecode& q = e->pending;
+          GroupRun r{};
+          int e0, en;
+          chain_rows(batch, groups, g, &e0, &en);
+          r.row0 = e0 * k;
+          r.rows = en * k;
+          r.batch = slots;
+          r.variant = variant | kVarBeside;
+          r.num_steps = num_steps;
+          r.slot = g;
+          r.early = early;
+          r.use_graph = use_graph;
+          r.s = e->part_stream[g];
+          hipError_t he = hipStreamWaitEvent(r.s, e->part_begin, 0);
+          if (he == hipSuccess) {
+            q.rcs[g] = run_group(e, r);
+            if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
+          }
+          q.ran[g] = r.ran;
+          q.used_graph[g] = r.used_graph;
+          if (he == hipSuccess) he = wait_stream(e, g, r.s);
+          if (q.rcs[g] == MT3_OK && he != hipSuccess) {
+            q.rcs[g] = MT3_ERR_HIP;
+            q.errs[g] = hipGetErrorString(he);
+          }
+        };
+        if (worker_post(e, g, body)) p.posted = g + 1;
+        else body();
+      }
+      MT3_TRY(decode_finish(e, h_steps_run));
+      MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));    // complete on return: the fork count is in host memory
+      return MT3_OK;
+    }
+    ++e->part_failed;
+  }
+  p.groups = 1;
+  p.active = true;
+  GroupRun r{};
+  r.row0 = 0;
+  r.rows = r.batch = slots;
+  r.variant = variant;
+  r.num_steps = num_steps;
+  r.slot = 0;
+  r.early = early;
+  r.use_graph = use_graph;
+  r.s = s;
+  p.rcs[0] = run_group(e, r);
+  if (p.rcs[0] != MT3_OK) p.errs[0] = mt3_last_error();
+  p.ran[0] = r.ran;
+  p.used_graph[0] = r.used_graph;
+  MT3_TRY(decode_finish(e, h_steps_run));
+  MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
+  return MT3_OK;
 }
 
 // ------------------------------------------------------------------------------------------- in-flight batching
@@ -2195,6 +2407,12 @@ int mt3_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t f
   return decode_impl(e, batch, num_steps, flags, 0, nullptr, nullptr, d_ids, d_first_logits, h_steps_run, stream);
 }
 
+int mt3_engine_decode_beams(mt3_engine* e, int32_t batch, int32_t num_beams, int32_t num_steps, int32_t flags,
+                            int32_t* d_ids, int32_t* d_all_ids, float* d_scores, int32_t* h_steps_run, void* stream) {
+  return decode_beams_impl(e, batch, num_beams, num_steps, flags, d_ids, d_all_ids, d_scores, h_steps_run,
+                           static_cast<hipStream_t>(stream));
+}
+
 int mt3_engine_decode_wait(mt3_engine* e, int32_t* h_steps_run) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_wait: engine not finalized");
   return decode_finish(e, h_steps_run);
@@ -2275,6 +2493,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_LAST_DECODE_GROUPS: return e->last_groups;
     case MT3_STATUS_PARTITION_FALLBACKS: return e->part_failed;
     case MT3_STATUS_LAST_DECODE_COMPACTIONS: return e->compactions;
+    case MT3_STATUS_LAST_DECODE_FORKS: return e->h_pinned ? e->h_pinned[kForksPinned] : 0;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

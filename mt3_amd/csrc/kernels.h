@@ -230,6 +230,56 @@ struct RefillArgs {
   size_t row_bytes, sc_bytes;
 };
 int launch_refill(const RefillArgs& a, hipStream_t s);
+// ---- k-beam search (mt3_engine_decode_beams; the rule is stated in include/mt3_hip.h)
+// Slots b*k .. b*k + k - 1 hold the k live beams of batch element b.  All slot-indexed pointers are those of the step's
+// first slot; `hist_*` are [L][hist_stride] with the step's first slot as column 0.
+constexpr int kBeamMaxK = 8;
+constexpr float kBeamNegInf = -1.0e7f;       // t5x decoding.NEG_INF
+struct BeamKArgs {
+  float* logits;
+  int vocab, k, elems;
+  float* live;          // [slots] running log-prob of each live beam, best first within an element
+  float* fin_score;     // [slots] the element's k finished entries, best first (kBeamNegInf: unfilled)
+  int* fin_step;        // [slots] step of the entry's EOS (-1: unfilled)
+  int* fin_beam;        // [slots] beam (0 .. k-1) whose prefix the EOS ends
+  int* hist_par;        // [L][hist_stride] parent beam of the new beam in each slot
+  int* hist_tok;        // [L][hist_stride] its token
+  int hist_stride;
+  int* slot_row;        // [slots] slot -> self-attention cache row (rewritten: a beam takes over its parent's row)
+  int* fork_src;        // [slots] row to copy positions [0, t] from into the slot's new row (-1: no copy)
+  int* fork_count;      // running count of forks (copies)
+  int* done;            // [slots] set for all k slots once the element is retired
+  int* n_done;          // finished slots of the row group (+k per retired element)
+  int* step;
+  int* cur_tok;
+  const float* bp;      // BeamState::cfg
+  const float* table;
+  const float* pos_table;
+  int max_pos;
+  float* y_next;
+  void* y_ct;
+  float* y_ss;
+  int dim;
+};
+int launch_beam_step(const BeamKArgs& a, const RowProj& rp, const LogitScale& ls, hipStream_t s);
+// copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
+// (and e4m3 scale rows), for every slot that forked this step; the grid covers every slot x layer x head
+struct BeamReorderArgs {
+  int n_layers, H, cap, kv_esize, slots;
+  char* k[kRefillMaxLayers];
+  char* v[kRefillMaxLayers];
+  float2* scale[kRefillMaxLayers];   // nullptr: no e4m3 side array
+  const int* fork_src;
+  const int* slot_row;
+  const int* step;
+  const int* done;
+};
+int launch_beam_reorder(const BeamReorderArgs& a, hipStream_t s);
+// state of a new search: live = [0, NEG_INF, ...] per element, nothing finished
+int launch_beam_init(float* live, float* fin_score, int* fin_step, int* fin_beam, int slots, int k, hipStream_t s);
+// backtracks the result of every element: ids [elems][L] (the best decode), all_ids [elems][k][L] and scores
+// [elems][k] in increasing order of score (either may be nullptr)
+int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int* all_ids, float* scores, hipStream_t s);
 int launch_iota(int* dst, int n, hipStream_t s);
 int launch_set_float(float* dst, float v, hipStream_t s);
 int launch_beam1_finalize(int* ids, int L, const int* beam_len, int B, hipStream_t s);

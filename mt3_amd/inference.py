@@ -54,7 +54,7 @@ class InferenceModel(object):
 
     def __init__(self, checkpoint_path, model_type="mt3", *, config: Optional[network.T5Config] = None,
                  dtype: str = "float32", batch_size: int = 8, early_exit: bool = True,
-                 decoding: str = "beam1", max_slots: int = 256, schedule: str = "refill"):
+                 decoding: str = "beam1", max_slots: int = 256, schedule: str = "refill", num_beams: int = 4):
         """dtype: 'float32' (default) = the reference's own precision (gin/model.gin:50 restores and runs
         float32): f32 MFMA operands, f32 K/V cache, token-exact against the oracle.  'bfloat16' is the explicit
         opt-in fast path (bf16 operands and caches, f32 accumulation / residual / softmax; what bench.py times;
@@ -63,7 +63,11 @@ class InferenceModel(object):
         that many rows: 3.2 GB per 64 slots in f32 at the MT3 shape); the engine starts at `batch_size` slots and is rebuilt
         with more (next power of two) when a job has more segments.  schedule: 'refill' = one mt3_engine_transcribe call
         per job (in-flight batching; needs early_exit); 'batch' = the reference's loop, one batch-synchronous engine call
-        per `batch_size` segments (NB:295-301)."""
+        per `batch_size` segments (NB:295-301).
+        decoding: 'beam1' (default) / 'greedy' as above; 'beam' = t5x beam_search with num_decodes = `num_beams` (1 .. 8,
+        Transformer.decode_beams): segments are encoded and beam-decoded in batch-synchronous chunks of
+        max_slots // num_beams segments (each beam is a decode slot), and `schedule='refill'` is ignored (in-flight
+        refill of beam groups is not implemented)."""
         if model_type == "ismir2021":
             num_velocity_bins = 127
             self.encoding_spec = note_sequences.NoteEncodingSpec
@@ -83,9 +87,12 @@ class InferenceModel(object):
         self.outputs_length = 1024
         self.sequence_length = {"inputs": self.inputs_length, "targets": self.outputs_length}
         self.early_exit = early_exit
-        if decoding not in ("beam1", "greedy"):
-            raise ValueError("decoding must be 'beam1' or 'greedy', got %r" % (decoding,))
+        if decoding not in ("beam1", "greedy", "beam"):
+            raise ValueError("decoding must be 'beam1', 'greedy' or 'beam', got %r" % (decoding,))
+        if decoding == "beam" and not 1 <= int(num_beams) <= min(8, self.max_slots):
+            raise ValueError("num_beams must be 1 .. 8 (and <= max_slots), got %r" % (num_beams,))
         self.decoding = decoding
+        self.num_beams = int(num_beams) if decoding == "beam" else 1
 
         self.spectrogram_config = spectrograms.SpectrogramConfig()
         self.codec = vocabularies.build_codec(
@@ -168,6 +175,8 @@ class InferenceModel(object):
         x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, np.float32))
         x = x.cuda()
         beam1 = self.decoding == "beam1"
+        if self.decoding == "beam":
+            return self._predict_tokens_beam(x)
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: finished rows restart on the job's next segments
             self._ensure_slots(x.shape[0])
@@ -181,6 +190,22 @@ class InferenceModel(object):
             ids = self.model.decode(early_exit=self.early_exit, beam1=beam1)
             out.append(self.vocabulary.decode_tf(ids))
             self.rows_per_engine_call.append(int(min(step, x.shape[0] - s)))
+        return torch.cat(out, 0).cpu().numpy()
+
+    def _predict_tokens_beam(self, x):
+        """decoding='beam': batch-synchronous chunks of max_slots // k segments, k engine rows (beams) per segment"""
+        import torch
+        k = self.num_beams
+        chunk = max(1, self.max_slots // k)
+        self._ensure_slots(min(x.shape[0], chunk) * k)
+        chunk = max(1, min(chunk, self.model.max_batch // k))
+        out = []
+        self.rows_per_engine_call = []
+        for s in range(0, x.shape[0], chunk):
+            self.model.encode(x[s:s + chunk], num_beams=k)
+            ids, _ = self.model.decode_beams(k, early_exit=self.early_exit)
+            out.append(self.vocabulary.decode_tf(ids))
+            self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
         return torch.cat(out, 0).cpu().numpy()
 
     def __call__(self, audio):

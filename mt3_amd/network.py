@@ -187,18 +187,24 @@ class Transformer:
     def device_bytes(self) -> int:
         return int(self._lib.mt3_engine_device_bytes(self._h))
 
-    def encode(self, encoder_input_tokens, return_encoded: bool = False):
-        """encoder_input_tokens: CUDA f32 tensor [B, T, input_depth]."""
+    def encode(self, encoder_input_tokens, return_encoded: bool = False, num_beams: int = 1):
+        """encoder_input_tokens: CUDA f32 tensor [B, T, input_depth].  num_beams = k > 1: each segment is encoded k times
+        in a row (B * k engine rows, the input `decode_beams(k)` expects; `decode()` would then decode every copy)."""
         import torch
         x = encoder_input_tokens
         if x.dim() != 3 or x.shape[1] != self.input_length or x.shape[2] != self.config.input_depth:
             raise ValueError(f"expected [B, {self.input_length}, {self.config.input_depth}], got {tuple(x.shape)}")
         x = x.to(device="cuda", dtype=torch.float32).contiguous()
+        if num_beams < 1:
+            raise ValueError(f"num_beams must be >= 1, got {num_beams}")
+        if num_beams > 1:
+            x = x.repeat_interleave(num_beams, 0).contiguous()
         enc = torch.empty((x.shape[0], x.shape[1], self.config.emb_dim), device="cuda", dtype=torch.float32) \
             if return_encoded else None
         _lib.check(self._lib.mt3_engine_encode(self._h, x.data_ptr(), x.shape[0], enc.data_ptr() if enc is not None
                                                else None, torch.cuda.current_stream().cuda_stream))
         self._batch = x.shape[0]
+        self._encoded_beams = num_beams
         return enc
 
     def decode(self, num_steps: Optional[int] = None, use_graph: bool = True, early_exit: bool = False,
@@ -228,6 +234,35 @@ class Transformer:
             return None
         self.steps_run = ran.value
         return (ids, logits) if return_first_logits else ids
+
+    def decode_beams(self, num_beams: int, num_steps: Optional[int] = None, use_graph: bool = True,
+                     early_exit: bool = False, single_stream: bool = False, return_all: bool = False):
+        """mt3_engine_decode_beams: t5x beam_search(alpha=0.6) with num_decodes = num_beams (1 .. 8) for the segments of
+        the last `encode(x, num_beams=num_beams)` (include/mt3_hip.h states the rule).  Returns int32 CUDA ids [B, L] of
+        the best decode and f32 scores [B]; with `return_all` all k decodes [B, k, L] and their scores [B, k] in
+        increasing order of score (the best last, as t5x returns them).  early_exit: stop once every segment's search is
+        closed (a closed segment's beams cost no attention meanwhile); `self.steps_run` says how many steps ran."""
+        import torch
+        k = int(num_beams)
+        if k < 1 or k > _lib.MAX_BEAMS:
+            raise ValueError(f"num_beams must be 1 .. {_lib.MAX_BEAMS}, got {num_beams}")
+        if getattr(self, "_encoded_beams", 1) != k or self._batch % k:
+            raise ValueError(f"decode_beams({k}) needs the segments encoded with encode(x, num_beams={k}) first")
+        B, L = self._batch // k, self.max_decode_length
+        ids = torch.empty((B, L), device="cuda", dtype=torch.int32)
+        all_ids = torch.empty((B, k, L), device="cuda", dtype=torch.int32) if return_all else None
+        scores = torch.empty((B, k), device="cuda", dtype=torch.float32)
+        flags = (0 if use_graph else _lib.DECODE_NO_GRAPH) | (_lib.DECODE_EARLY_EXIT if early_exit else 0) | \
+            (_lib.DECODE_SINGLE_STREAM if single_stream else 0)
+        ran = C.c_int32()
+        _lib.check(self._lib.mt3_engine_decode_beams(self._h, B, k, num_steps or L, flags, ids.data_ptr(),
+                                                     all_ids.data_ptr() if all_ids is not None else None,
+                                                     scores.data_ptr(), C.byref(ran),
+                                                     torch.cuda.current_stream().cuda_stream))
+        self.steps_run = ran.value
+        if return_all:
+            return all_ids, scores
+        return ids, scores[:, -1].contiguous()
 
     def transcribe(self, encoder_input_tokens, num_steps: Optional[int] = None, beam1: bool = False,
                    use_graph: bool = True, single_stream: bool = False, debug_poll_steps: int = 0,
