@@ -324,6 +324,44 @@ int mt3_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_segmen
 int mt3_engine_decode_forced(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags,
                              const int32_t* d_forced_ids, float* d_step_logits, int32_t* d_ids, void* stream);
 
+/* Teacher-forced sequence scoring: t5x EncoderDecoderModel.score_batch, which ContinuousInputsEncoderDecoderModel
+ * (mt3/models.py:121-152) inherits and t5x's infer reaches with mode='score'.  The rule, written down from memory
+ * [from memory: t5x is not at hand, as for the beam search above]:
+ *   logits         Transformer.decode(..., decode=False, enable_dropout=False) (mt3/network.py:303-361) on the encoder
+ *                  output of the segment: every position at once, positions 0 .. length-1 on the sinusoidal table the
+ *                  cached step uses.
+ *   decoder inputs d_decoder_inputs, or (NULL) shift_right(targets) with BOS = 0 -- seqio autoregressive_inputs, what
+ *                  mt3_amd.models.convert_features builds.
+ *   masks          make_decoder_mask(decoder_target_tokens) (network.py:333-340): a query attends key j <= itself whose
+ *                  target is > 0.  Keys with target 0 contribute nothing, wherever they sit in the row.  The query-side
+ *                  mask of t5x only touches positions whose target is 0, and those are padding: their token score is 0
+ *                  whatever their weight, and (masked as keys) their hidden state never reaches another position.  So
+ *                  the scores equal t5x's wherever t5x's own converter sets the weights (target > 0).
+ *   token scores   token_scores[b, t] = (logits[b, t, target[b, t]] - logsumexp(logits[b, t, :])) * weights[b, t]
+ *                  (0 where target == 0; weights NULL: 1) -- -cross_entropy_with_logits(logits, onehot(targets),
+ *                  z_loss = 0)[0] * decoder_loss_weights; t5x returns them with return_intermediates.
+ *   sequence score sequence_scores[b] = sum over t of token_scores[b, t], summed in a fixed order (in double), so a
+ *                  segment's score has the same bits on every run.
+ * Rows: segments 0 .. batch-1 of the preceding mt3_engine_encode (batch <= its batch), as for mt3_engine_decode.
+ * d_targets [batch, length] int32 (vocabulary ids, 0 = padding); d_decoder_inputs [batch, length] int32 or NULL;
+ * d_weights [batch, length] f32 or NULL; d_sequence_scores [batch] f32; d_token_scores [batch, length] f32 or NULL;
+ * d_logits [batch, length, vocab] f32 or NULL.  1 <= length <= max_decode_len, any value (padded internally to 64).
+ * Work: the decoder as a PREFILL over chunks of segments x length rows (DESIGN.md "Scoring"): the dense layers on the
+ * encoder's large-M tiles (f32: the three-plane tile, whose plane copies of the decoder matrices are built by the first
+ * call; bf16: the LDS-DMA tile on the split residual rows), a causal self-attention and a cross-attention against the
+ * cached cross-K/V of the encode, a log-softmax / gather reduction.  The chunk comes from a score workspace allocated by
+ * the first call (32 segments at L = 1024, at most max_batch; MT3_STATUS_SCORE_CHUNKS reports the chunks of the last
+ * call); the tiles do not depend on the batch or the chunk, so a segment gets the same bits in any batch wherever the
+ * encoder gives it the same bits (f32: always; bf16: passes of 8 or more segments, see mt3_engine_encode).
+ * Everything is enqueued on `stream` (no graph, no row groups); the call does not touch the decode state, so a decode
+ * of the same encoded rows after it returns the same ids.
+ * MT3_ERR_INVALID: a decode in flight (MT3_DECODE_ASYNC), e4m3 K/V caches (kv_cache_dtype MT3_FP8_E4M3: out of scope),
+ * length outside 1 .. max_decode_len, batch outside 1 .. the encoded batch, null targets or sequence scores.  Ids
+ * outside [0, vocab) are the caller's error (they are clamped, the scores are then meaningless). */
+int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t* d_targets,
+                     const int32_t* d_decoder_inputs /* NULL: shift right */, const float* d_weights /* NULL: target > 0 */,
+                     float* d_sequence_scores, float* d_token_scores, float* d_logits, void* stream);
+
 /* Engine facts a caller cannot see from results alone (a negative return is an mt3_status).
  * GRAPH_FALLBACKS: decode calls so far whose step graph could not be captured/instantiated and that therefore
  * ran as direct launches (same ids, slower) -- the fallback is counted, never silent;
@@ -336,7 +374,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_LAST_DECODE_GROUPS = 7 /* row groups of the most recent decode (2 or 4: the row-group schedule); 1: on the caller's stream */,
        MT3_STATUS_PARTITION_FALLBACKS = 8 /* decodes that wanted the row-group schedule but could not set it up */,
        MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */,
-       MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams */ };
+       MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams */,
+       MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the

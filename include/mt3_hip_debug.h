@@ -52,6 +52,11 @@ int mt3_debug_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_
  * return exactly the ids it returns over zero-filled caches. */
 int mt3_debug_engine_poison_caches(mt3_engine* e, int32_t pattern, int32_t cross, void* stream);
 
+/* Segments per chunk of mt3_engine_score (1 .. max_batch; 0: the default the score workspace sets), so that tests can make a
+ * small batch run in several chunks.  The workspace grows on the next score call if it holds fewer segments.  The
+ * scores do not depend on the chunk (include/mt3_hip.h, mt3_engine_score). */
+int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments);
+
 /* (Rounds 2-3 had thirteen process-wide launch-shape knobs here -- mt3_debug_set_knob -- and a row-group experiment
  * entry, mt3_debug_engine_decode_split.  What they measured is recorded in DESIGN.md sections 3 and 5 and under
  * profiles/r3_ab_*; the variants that lost are no longer compiled into the library, the ones that won are the code.) */

@@ -93,6 +93,9 @@ struct LayerDev {
           *wo_mlp_q = nullptr, *wo_mlp_sc = nullptr, *wkv_x_q = nullptr, *wkv_x_sc = nullptr;
   // f32 engine, encoder-sized launches (gemm_x6_kernel): the same matrices as three bf16 planes (hi / mid / lo) [N][K]
   void *wqkv_p[3] = {}, *wo_p[3] = {}, *wi_p[3] = {}, *wo_mlp_p[3] = {}, *wkv_x_p[3] = {};
+  // ... and, for DECODER layers, built by the first mt3_engine_score call (the decode step never reads them): the planes of
+  // wqkv / wo / wi / wo_mlp above plus the cross-attention query and out-projection
+  void *wq_x_p[3] = {}, *wo_x_p[3] = {};
   // fp8 (e4m3) K/V caches only: {k_scale, v_scale} per cached row
   float2* self_scale = nullptr;    // [Bm][H][L]
   float2* cross_scale = nullptr;   // [B][H][T]
@@ -309,6 +312,25 @@ struct mt3_engine {
   hipGraphExec_t graph_exec[kNumVariants][9] = {};   // [variant][chains]: the step graph with `chains` parallel branches
   hipGraph_t graph[kNumVariants][9] = {};
   int graph_batch = 0;
+
+  // Teacher-forced scoring (mt3_engine_score): a workspace of score_cap segments x score_Lp rows, allocated by the first
+  // call (and grown by mt3_debug_engine_set_score_chunk); an engine that never scores keeps its device bytes
+  int score_cap = 0;             // segments the workspace holds (0: not allocated)
+  int score_Lp = 0;              // rows per segment: max_decode_len rounded up to 64
+  int score_chunk_req = 0;       // mt3_debug_engine_set_score_chunk (0: the workspace default)
+  int score_chunks = 0;          // chunks of the most recent score call
+  bool score_planes = false;     // f32 engine (x6): the decoder's plane copies exist
+  void* logits_p[3] = {};        // f32 engine (x6): planes of logits_w
+  float* sc_y = nullptr;         // [rows][emb] f32 residual rows
+  void* sc_y_ct = nullptr;       // bf16: compute-type copy [rows][emb] ...
+  float* sc_y_ss = nullptr;      // ... and per-16-column sums of squares [rows][emb / 16]
+  void* sc_qkv = nullptr;        // [rows][3HD]
+  void* sc_attn = nullptr;       // [rows][HD]
+  void* sc_q = nullptr;          // [rows][HD] cross-attention queries
+  void* sc_h = nullptr;          // [rows][mlp]
+  float* sc_logits = nullptr;    // [rows][vocab]
+  int* sc_tgt = nullptr;         // [rows] padded targets
+  float* sc_tok = nullptr;       // [rows] token scores
 
   int HD() const { return cfg.num_heads * cfg.head_dim; }
 };
@@ -2424,6 +2446,189 @@ int mt3_engine_decode_forced(mt3_engine* e, int32_t batch, int32_t num_steps, in
   return decode_impl(e, batch, num_steps, flags, 0, d_forced_ids, d_step_logits, d_ids, nullptr, nullptr, stream);
 }
 
+// ---------------------------------------------------------------------------------------------- teacher-forced scoring
+// Rows of the score workspace by default: 32 segments at L = 1024 (about 0.7 GB in f32); a chunk is that many segments.
+constexpr int kScoreRows = 32768;
+
+static int score_default_chunk(const mt3_engine* e) {
+  const int Lp = (e->cfg.max_decode_len + 63) / 64 * 64;
+  return std::max(1, std::min(e->cfg.max_batch, kScoreRows / Lp));
+}
+
+static bool score_split(const mt3_engine* e) {
+  const int emb = e->cfg.emb_dim;
+  return e->cfg.compute_dtype == MT3_BF16 && emb % 64 == 0 && emb <= 1024;
+}
+
+static int ensure_score_workspace(mt3_engine* e, int segs) {
+  if (e->score_cap >= segs) return MT3_OK;
+  const mt3_engine_config& c = e->cfg;
+  const int Lp = (c.max_decode_len + 63) / 64 * 64;
+  const size_t R = static_cast<size_t>(segs) * Lp, es = e->esize, hd = e->HD(), emb = c.emb_dim;
+  // (a grown workspace replaces the old one; the old buffers stay in the engine's allocation list until destroy)
+  MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->sc_y), R * emb * 4));
+  if (score_split(e)) {
+    MT3_TRY(dmalloc(e, &e->sc_y_ct, R * emb * 2));
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->sc_y_ss), R * (emb / 16) * 4));
+  }
+  MT3_TRY(dmalloc(e, &e->sc_qkv, R * 3 * hd * es));
+  MT3_TRY(dmalloc(e, &e->sc_attn, R * hd * es));
+  MT3_TRY(dmalloc(e, &e->sc_q, R * hd * es));
+  MT3_TRY(dmalloc(e, &e->sc_h, R * c.mlp_dim * es));
+  MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->sc_logits), R * c.vocab_size * 4));
+  MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->sc_tgt), R * 4));
+  MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->sc_tok), R * 4));
+  e->score_cap = segs;
+  e->score_Lp = Lp;
+  return MT3_OK;
+}
+
+// f32 engine on the three-plane tile: plane copies of the decoder matrices it scores with (built once, on the device,
+// from the f32 matrices finalize uploaded -- the same split upload_planes makes on the host)
+static int ensure_score_planes(mt3_engine* e, hipStream_t s) {
+  if (!e->x6 || e->score_planes) return MT3_OK;
+  const mt3_engine_config& c = e->cfg;
+  const size_t hd = e->HD(), emb = c.emb_dim, mlp = c.mlp_dim;
+  auto planes = [&](const void* w, size_t n, void* (&p)[3]) -> int {
+    for (int k = 0; k < 3; ++k) MT3_TRY(dmalloc(e, &p[k], n * 2));
+    return mt3k::launch_planes(static_cast<const float*>(w), p[0], p[1], p[2], n, s);
+  };
+  for (LayerDev& L : e->dec) {
+    MT3_TRY(planes(L.wqkv, 3 * hd * emb, L.wqkv_p));
+    MT3_TRY(planes(L.wo, emb * hd, L.wo_p));
+    MT3_TRY(planes(L.wq_x, hd * emb, L.wq_x_p));
+    MT3_TRY(planes(L.wo_x, emb * hd, L.wo_x_p));
+    MT3_TRY(planes(L.wi, 2 * mlp * emb, L.wi_p));
+    MT3_TRY(planes(L.wo_mlp, emb * mlp, L.wo_mlp_p));
+  }
+  MT3_TRY(planes(e->logits_w, static_cast<size_t>(c.vocab_size) * emb, e->logits_p));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));     // later calls may come on other streams
+  e->score_planes = true;
+  return MT3_OK;
+}
+
+static int score_impl(mt3_engine* e, int32_t batch, int32_t length, const int32_t* d_targets,
+                      const int32_t* d_decoder_inputs, const float* d_weights, float* d_sequence_scores,
+                      float* d_token_scores, float* d_logits, hipStream_t s) {
+  const mt3_engine_config& c = e->cfg;
+  const int dt = c.compute_dtype, emb = c.emb_dim, hd = e->HD(), H = c.num_heads, T = c.input_length, V = c.vocab_size;
+  const int Lp = (length + 63) / 64 * 64;
+  const int chunk = e->score_chunk_req > 0 ? e->score_chunk_req : score_default_chunk(e);
+  MT3_TRY(ensure_score_workspace(e, chunk));
+  MT3_TRY(ensure_score_planes(e, s));
+  const bool split = score_split(e), x6 = e->x6;
+  const size_t es = e->esize;
+  int chunks = 0;
+  for (int seg0 = 0; seg0 < batch; seg0 += chunk, ++chunks) {
+    const int C = std::min(chunk, batch - seg0), M = C * Lp;
+    {
+      mt3k::ScoreEmbedArgs a{e->embedding, e->pos_table, d_targets, d_decoder_inputs, e->sc_tgt, e->sc_y,
+                             M, Lp, length, seg0, emb, V};
+      MT3_TRY(mt3k::launch_score_embed(a, s));
+    }
+    if (split) MT3_TRY(mt3k::launch_residual_split(e->sc_y, e->sc_y_ct, e->sc_y_ss, M, emb, s));
+    // the residual rows normalised into a projection (the norm scale is folded into W's rows): three planes (f32
+    // engine), the bf16 LDS-DMA tile from the split rows, or the encoder-sized tile with in-kernel statistics
+    auto normed = [&](const void* W, void* (&P)[3], void* out, int N, int ldo, int epi) -> int {
+      if (x6) {
+        mt3k::GemmArgs g = gemm_args(e->sc_y, P[0], out, M, N, emb, ldo);
+        return mt3k::launch_gemm_x6(g, P[1], P[2], true, epi == MT3_EPI_F32 ? MT3_EPI_STORE : epi, s);
+      }
+      mt3k::GemmArgs g = gemm_args(split ? static_cast<const void*>(e->sc_y_ct) : static_cast<const void*>(e->sc_y), W,
+                                   out, M, N, emb, ldo);
+      g.a_ss = split ? e->sc_y_ss : nullptr;
+      return mt3k::launch_gemm(dt, g, !split, split ? 2 : 1, epi, false, s);
+    };
+    auto resid = [&](const void* A, const void* W, void* (&P)[3], int K) -> int {
+      mt3k::GemmArgs g = gemm_args(A, x6 ? P[0] : W, e->sc_y, M, emb, K, emb);
+      if (x6) return mt3k::launch_gemm_x6(g, P[1], P[2], false, MT3_EPI_RESID, s);
+      g.out_ct = split ? e->sc_y_ct : nullptr;
+      g.out_ss = split ? e->sc_y_ss : nullptr;
+      return mt3k::launch_gemm(dt, g, false, 0, MT3_EPI_RESID, false, s);
+    };
+    for (int l = 0; l < c.num_decoder_layers; ++l) {
+      LayerDev& L = e->dec[l];
+      MT3_TRY(normed(L.wqkv, L.wqkv_p, e->sc_qkv, 3 * hd, 3 * hd, MT3_EPI_STORE));
+      {
+        mt3k::ScoreAttnArgs a{};
+        a.q = e->sc_qkv;
+        a.q_stride = 3 * hd;
+        a.k = static_cast<const char*>(e->sc_qkv) + static_cast<size_t>(hd) * es;
+        a.v = static_cast<const char*>(e->sc_qkv) + static_cast<size_t>(2 * hd) * es;
+        a.kv_stride = 3 * hd;
+        a.kv_bstride = static_cast<long long>(Lp) * 3 * hd;
+        a.kv_hstride = 64;
+        a.key_tgt = e->sc_tgt;
+        a.out = e->sc_attn;
+        a.out_stride = hd;
+        a.B = C;
+        a.H = H;
+        a.Lq = Lp;
+        a.n_keys = Lp;
+        a.causal = 1;
+        MT3_TRY(mt3k::launch_score_attention(dt, a, s));
+      }
+      MT3_TRY(resid(e->sc_attn, L.wo, L.wo_p, hd));
+      MT3_TRY(normed(L.wq_x, L.wq_x_p, e->sc_q, hd, hd, MT3_EPI_STORE));
+      {
+        // the cross K/V cache of the encoded batch: [2][cur_batch][H][T][64]; the chunk's segments start at row seg0
+        const size_t head = static_cast<size_t>(T) * 64;
+        mt3k::ScoreAttnArgs a{};
+        a.q = e->sc_q;
+        a.q_stride = hd;
+        a.k = static_cast<const char*>(L.cross_kv) + static_cast<size_t>(seg0) * H * head * es;
+        a.v = static_cast<const char*>(L.cross_kv) + (static_cast<size_t>(e->cur_batch) + seg0) * H * head * es;
+        a.kv_stride = 64;
+        a.kv_bstride = static_cast<long long>(H) * head;
+        a.kv_hstride = static_cast<long long>(head);
+        a.out = e->sc_attn;
+        a.out_stride = hd;
+        a.B = C;
+        a.H = H;
+        a.Lq = Lp;
+        a.n_keys = T;
+        a.causal = 0;
+        MT3_TRY(mt3k::launch_score_attention(dt, a, s));
+      }
+      MT3_TRY(resid(e->sc_attn, L.wo_x, L.wo_x_p, hd));
+      MT3_TRY(normed(L.wi, L.wi_p, e->sc_h, 2 * c.mlp_dim, c.mlp_dim, MT3_EPI_GEGLU));
+      MT3_TRY(resid(e->sc_h, L.wo_mlp, L.wo_mlp_p, c.mlp_dim));
+    }
+    MT3_TRY(normed(e->logits_w, e->logits_p, e->sc_logits, V, V, MT3_EPI_F32));     // decoder_norm folded
+    {
+      mt3k::ScoreReduceArgs a{e->sc_logits, e->sc_tgt, d_weights, e->sc_tok, d_token_scores, d_sequence_scores,
+                              M, Lp, length, seg0, V};
+      MT3_TRY(mt3k::launch_score_reduce(a, s));
+    }
+    if (d_logits) {
+      const size_t row = static_cast<size_t>(length) * V * 4;
+      MT3_HIP_CHECK(hipMemcpy2DAsync(d_logits + static_cast<size_t>(seg0) * length * V, row, e->sc_logits,
+                                     static_cast<size_t>(Lp) * V * 4, row, C, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  e->score_chunks = chunks;
+  return MT3_OK;
+}
+
+int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t* d_targets,
+                     const int32_t* d_decoder_inputs, const float* d_weights, float* d_sequence_scores,
+                     float* d_token_scores, float* d_logits, void* stream) {
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: null engine");
+  if (length < 1 || length > e->cfg.max_decode_len)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: length must be in 1 .. max_decode_len");
+  if (!d_targets || !d_sequence_scores)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: null targets or sequence scores");
+  if (e->kv_fp8)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: engines with e4m3 K/V caches (kv_cache_dtype MT3_FP8_E4M3) cannot score");
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: engine not finalized");
+  if (e->pending.active)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+  if (batch <= 0 || batch > e->cur_batch)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: batch must be in 1 .. the batch of the preceding encode");
+  return score_impl(e, batch, length, d_targets, d_decoder_inputs, d_weights, d_sequence_scores, d_token_scores, d_logits,
+                    static_cast<hipStream_t>(stream));
+}
+
 // ---- mt3_hip_debug.h
 int mt3_debug_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t skip,
                             int32_t* d_ids, void* stream) {
@@ -2461,6 +2666,14 @@ int mt3_debug_engine_set_eos_schedule(mt3_engine* e, const int32_t* h_lengths, i
   return MT3_OK;
 }
 
+int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments) {
+  if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_score_chunk: engine not finalized");
+  if (segments < 0 || segments > e->cfg.max_batch)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_score_chunk: segments must be in 0 .. max_batch");
+  e->score_chunk_req = segments;
+  return MT3_OK;
+}
+
 int mt3_debug_engine_poison_caches(mt3_engine* e, int32_t pattern, int32_t cross, void* stream) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_poison_caches: engine not finalized");
   if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_poison_caches: a decode is in flight");
@@ -2494,6 +2707,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_PARTITION_FALLBACKS: return e->part_failed;
     case MT3_STATUS_LAST_DECODE_COMPACTIONS: return e->compactions;
     case MT3_STATUS_LAST_DECODE_FORKS: return e->h_pinned ? e->h_pinned[kForksPinned] : 0;
+    case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

@@ -285,5 +285,44 @@ int launch_set_float(float* dst, float v, hipStream_t s);
 int launch_beam1_finalize(int* ids, int L, const int* beam_len, int B, hipStream_t s);
 int launch_ids_to_tokens(const int* ids, int B, int L, int num_regular, int* out, hipStream_t s);
 
+// ---- teacher-forced scoring (mt3_engine_score, score.hip).  A chunk holds `rows` = segments * Lp rows, row = seg * Lp + t;
+// caller arrays are [batch][length], the chunk's first segment is seg0
+struct ScoreEmbedArgs {
+  const float* table;     // token embedding [vocab][dim]
+  const float* pos;       // position table
+  const int* targets;     // caller [batch][length]
+  const int* dec_in;      // caller [batch][length] or nullptr: shift_right(targets), BOS = 0
+  int* tgt_pad;           // [rows] targets, 0 past `length`
+  float* y;               // [rows][dim] f32 decoder input rows
+  int rows, Lp, length, seg0, dim, vocab;
+};
+int launch_score_embed(const ScoreEmbedArgs& a, hipStream_t s);
+struct ScoreAttnArgs {
+  const void* q;          // [B][Lq] query rows, row stride q_stride elements; head h at +h*64
+  int q_stride;
+  const void* k;          // key j of (batch b, head h) at k + b*kv_bstride + h*kv_hstride + j*kv_stride
+  const void* v;
+  int kv_stride;
+  long long kv_bstride, kv_hstride;
+  const int* key_tgt;     // [B][Lq] (causal only): key j is visible iff key_tgt[b][j] != 0 (nullptr: every key)
+  void* out;              // [B][Lq] rows of out_stride elements; head h at +h*64
+  int out_stride;
+  int B, H, Lq, n_keys;   // Lq % 64 == 0; causal: n_keys = Lq; cross: n_keys = T (a multiple of 64)
+  int causal;
+};
+int launch_score_attention(int dtype, const ScoreAttnArgs& a, hipStream_t s);
+struct ScoreReduceArgs {
+  const float* logits;    // [rows][vocab]
+  const int* tgt_pad;     // [rows]
+  const float* weights;   // caller [batch][length] or nullptr (1)
+  float* tok_pad;         // [rows] token scores of the chunk
+  float* token_scores;    // caller [batch][length] or nullptr
+  float* seq_scores;      // caller [batch]
+  int rows, Lp, length, seg0, vocab;
+};
+int launch_score_reduce(const ScoreReduceArgs& a, hipStream_t s);
+// f32 [n] -> three bf16 planes (gemm_x6_kernel's weight operand)
+int launch_planes(const float* w, void* hi, void* mid, void* lo, size_t n, hipStream_t s);
+
 }  // namespace mt3k
 #endif  // MT3_KERNELS_H_

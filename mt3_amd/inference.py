@@ -222,6 +222,38 @@ class InferenceModel(object):
                                                        encoding_spec=self.encoding_spec)
         return result["est_ns"]
 
+    def score(self, audio, targets, return_token_scores: bool = False):
+        """Teacher-forced scores of token rows for this audio (t5x score_batch; the reference's infer(mode='score')
+        path, which its write_inferences_to_file refuses to write).  The audio goes through the frontend and segmenting
+        of `__call__`; targets[i] are the vocabulary ids of segment i in decoder_target_tokens form (EOS included, at
+        most 1024).  Returns float64 [n_segments] sequence scores, with return_token_scores also a list of float64
+        per-token scores (one array of len(targets[i]) per segment)."""
+        import torch
+        if self.model_config.kv_dtype:
+            raise ValueError("score() is not available with kv_dtype=%r: e4m3 K/V caches cannot score"
+                             % (self.model_config.kv_dtype,))
+        examples = self.preprocess(self.audio_to_dataset(audio), host_inputs=False)
+        x, self._logmel_dev = self._logmel_dev, None
+        if len(targets) != len(examples):
+            raise ValueError("targets has %d rows; the audio has %d segments" % (len(targets), len(examples)))
+        rows = [np.asarray(t, np.int32).reshape(-1)[: self.outputs_length] for t in targets]
+        n = max([len(r) for r in rows] + [1])
+        tgt = np.zeros((len(rows), n), np.int32)
+        for i, r in enumerate(rows):
+            tgt[i, : len(r)] = r
+        seq, tok = [], []
+        step = self.model.max_batch
+        for s in range(0, len(rows), step):
+            self.model.encode(x[s:s + step])
+            sc, ts = self.model.score(torch.from_numpy(tgt[s:s + step]), return_token_scores=True)
+            seq.append(sc.cpu().numpy().astype(np.float64))
+            tok.append(ts.cpu().numpy().astype(np.float64))
+        scores = np.concatenate(seq) if seq else np.zeros((0,), np.float64)
+        if not return_token_scores:
+            return scores
+        tok = np.concatenate(tok) if tok else np.zeros((0, n), np.float64)
+        return scores, [tok[i, : len(r)] for i, r in enumerate(rows)]
+
     def transcribe_many(self, audios: Sequence[Any]) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next

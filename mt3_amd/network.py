@@ -355,6 +355,56 @@ class Transformer:
         torch.cuda.current_stream().synchronize()          # `f` must outlive the copy the call enqueued
         return ids, logits
 
+    def score(self, targets, decoder_inputs=None, weights=None, return_token_scores: bool = False,
+              return_logits: bool = False):
+        """mt3_engine_score: t5x score_batch on the segments of the last `encode` (include/mt3_hip.h states the rule).
+        targets: int32 [B, <= L] vocabulary ids (0 = padding; B <= the encoded batch), CUDA or host; decoder_inputs (same
+        shape, default shift_right(targets) with BOS = 0) and weights (f32, default target > 0) likewise.  Narrower
+        arrays are padded with 0 to the width of `targets`, the call's length.  Returns the f32 CUDA sequence scores [B],
+        or a tuple (scores, token_scores [B, length] if asked, logits [B, length, V] if asked)."""
+        import torch
+        if self.config.kv_dtype:
+            raise ValueError("scoring is not available with kv_dtype=%r (e4m3 cross caches are out of scope)"
+                             % (self.config.kv_dtype,))
+        tgt = torch.as_tensor(targets)
+        if tgt.dim() != 2 or tgt.shape[1] < 1 or tgt.shape[1] > self.max_decode_length:
+            raise ValueError(f"targets must be [B, 1 .. {self.max_decode_length}], got {tuple(tgt.shape)}")
+        B, n = int(tgt.shape[0]), int(tgt.shape[1])
+        if not 1 <= B <= getattr(self, "_batch", 0):
+            raise ValueError(f"targets has {B} rows; the last encode holds {getattr(self, '_batch', 0)}")
+
+        def padded(a, dtype):
+            if a is None:
+                return None
+            a = torch.as_tensor(a).to(device="cuda", dtype=dtype)
+            if a.dim() != 2 or a.shape[0] != B or a.shape[1] > n:
+                raise ValueError(f"expected [B={B}, <= {n}], got {tuple(a.shape)}")
+            out = torch.zeros((B, n), device="cuda", dtype=dtype)
+            out[:, : a.shape[1]] = a
+            return out
+
+        tgt = padded(tgt, torch.int32)
+        if int(tgt.min()) < 0 or int(tgt.max()) >= self.config.vocab_size:
+            raise ValueError("target ids must lie in [0, vocab_size)")
+        din = padded(decoder_inputs, torch.int32)
+        if din is not None and (int(din.min()) < 0 or int(din.max()) >= self.config.vocab_size):
+            raise ValueError("decoder input ids must lie in [0, vocab_size)")
+        w = padded(weights, torch.float32)
+        seq = torch.empty((B,), device="cuda", dtype=torch.float32)
+        tok = torch.empty((B, n), device="cuda", dtype=torch.float32) if return_token_scores else None
+        logits = torch.empty((B, n, self.config.vocab_size), device="cuda", dtype=torch.float32) if return_logits else None
+        ptr = (lambda t: t.data_ptr() if t is not None else None)
+        _lib.check(self._lib.mt3_engine_score(self._h, B, n, ptr(tgt), ptr(din), ptr(w), ptr(seq), ptr(tok), ptr(logits),
+                                              torch.cuda.current_stream().cuda_stream))
+        torch.cuda.current_stream().synchronize()          # the padded inputs must outlive the work the call enqueued
+        if not (return_token_scores or return_logits):
+            return seq
+        return (seq,) + ((tok,) if return_token_scores else ()) + ((logits,) if return_logits else ())
+
+    def debug_set_score_chunk(self, segments: int = 0):
+        """mt3_debug_engine_set_score_chunk: segments per chunk of `score` (0: the workspace default)."""
+        _lib.check(self._lib.mt3_debug_engine_set_score_chunk(self._h, int(segments)))
+
     def status(self, what: int) -> int:
         """mt3_engine_status: _lib.STATUS_* (graph fallbacks, row groups / compactions of the last decode, ...)."""
         rc = int(self._lib.mt3_engine_status(self._h, what))
