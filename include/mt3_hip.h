@@ -99,6 +99,36 @@ int mt3_frontend_logmel_dev(mt3_frontend* fe, const float* d_audio, int32_t n_se
                             int32_t frames_per_segment, const int32_t* d_n_frames /* may be NULL */,
                             float* d_logmel, void* stream);
 
+/* ---------------------------------------------------------------- resampler
+ * Replaces the host resample inside note_seq.audio_io.wav_data_to_samples_librosa (NB cell 2,
+ * `wav_data_to_samples_librosa(wav, sample_rate=16000)` before `inference_model(audio)`), which the Python mirror
+ * evaluates as mt3_amd/audio_io.resample: scipy.signal.resample_poly(x, up, down, window=w) with the default padtype
+ * (zeros outside x) and resampy's kaiser_best filter.  The device computes exactly
+ *   n_out = ceil(n_in * up / down)
+ *   y[n]  = float32( sum_k x[k] * h_taps[n*down + half - k*up] ),  n < n_out,  half = (n_taps - 1) / 2
+ * (taps whose index falls outside [0, n_taps) and inputs outside [0, n_in) contribute nothing), every product and the
+ * sum in float64: the same samples as resample_poly on the host, to the last bit or within one f32 ulp where
+ * the two summation orders round differently.
+ * mt3_resample_output_length: n_out in int64 (-1 for n_in < 0, up < 1 or down < 1).
+ * mt3_resampler_create: h_taps = resample_poly's window ALREADY multiplied by `up` (resample_poly applies w * up), odd
+ *   n_taps <= 2^20, up/down in lowest terms; the table is reordered phase-major and uploaded once (setup call,
+ *   synchronous).  MT3_ERR_INVALID for a NULL pointer, an even or non-positive n_taps, more than 2^20 taps, up < 1,
+ *   down < 1 or gcd(up, down) != 1.
+ * mt3_resampler_run: d_in [n_in] f32 -> d_out [out_capacity] f32: y[0 .. n_out) and 0.0 in [n_out, out_capacity),
+ *   nothing written at or past out_capacity (so d_out may be the frontend's zero-padded [n_segments, T*hop] buffer).
+ *   MT3_ERR_INVALID for a NULL pointer, n_in < 1 or out_capacity < n_out.  Same contract as mt3_frontend_logmel:
+ *   one launch enqueued on `stream`, nothing allocated, copied or waited for; a resampler is read-only after create,
+ *   so any number of threads and streams may run it.
+ */
+typedef struct mt3_resampler mt3_resampler;
+
+int64_t mt3_resample_output_length(int64_t n_in, int32_t up, int32_t down);
+int mt3_resampler_create(const double* h_taps /* w * up, [n_taps] */, int64_t n_taps, int32_t up, int32_t down,
+                         mt3_resampler** out);
+void mt3_resampler_destroy(mt3_resampler* r);
+int mt3_resampler_run(mt3_resampler* r, const float* d_in, int64_t n_in, float* d_out, int64_t out_capacity,
+                      void* stream);
+
 /* -------------------------------------------------------------------- engine
  * Replaces network.Transformer (mt3/network.py:265-409, layers in mt3/layers.py)
  * as driven by t5x predict_batch_with_aux through

@@ -79,6 +79,10 @@ SIGNATURES = {
     "mt3_frontend_mel_matrix": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
     "mt3_frontend_logmel": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "mt3_frontend_logmel_dev": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mt3_resample_output_length": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "mt3_resampler_create": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "mt3_resampler_destroy": (None, [_P]),
+    "mt3_resampler_run": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),
     "mt3_engine_create": (C.c_int, [C.POINTER(EngineConfig), C.POINTER(_P)]),
     "mt3_engine_destroy": (None, [_P]),
     "mt3_engine_load_weight": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),

@@ -31,8 +31,9 @@ import numpy as np
 SAMPLE_RATE = 16000
 
 
-def wav_data_to_samples(wav_data, sample_rate: int = SAMPLE_RATE) -> np.ndarray:
-    """bytes or path -> float32 mono in [-1, 1] at `sample_rate`."""
+def read_wav(wav_data):
+    """bytes or path -> (float32 mono in [-1, 1], native sample rate): the PCM decode and stereo mixdown of
+    `wav_data_to_samples`, without the resample."""
     from scipy.io import wavfile
     src = io.BytesIO(wav_data) if isinstance(wav_data, (bytes, bytearray)) else wav_data
     native_sr, y = wavfile.read(src)
@@ -44,6 +45,12 @@ def wav_data_to_samples(wav_data, sample_rate: int = SAMPLE_RATE) -> np.ndarray:
         y = y.astype(np.float32)
     if y.ndim == 2:
         y = y.mean(axis=1)
+    return y, int(native_sr)
+
+
+def wav_data_to_samples(wav_data, sample_rate: int = SAMPLE_RATE) -> np.ndarray:
+    """bytes or path -> float32 mono in [-1, 1] at `sample_rate` (`read_wav` + host `resample`)."""
+    y, native_sr = read_wav(wav_data)
     return resample(y, native_sr, sample_rate)
 
 
@@ -62,26 +69,114 @@ def kaiser_sinc_kernel(tau: np.ndarray, scale: float, num_zeros: int, beta: floa
     return np.where(inside, scale * rolloff * np.sinc(rolloff * t) * taper, 0.0)
 
 
+def rate_ratio(orig_sr: int, target_sr: int = SAMPLE_RATE):
+    """(up, down) in lowest terms: target_sr / orig_sr."""
+    frac = Fraction(int(target_sr), int(orig_sr))
+    return frac.numerator, frac.denominator
+
+
+def kaiser_best_num_taps(orig_sr: int, target_sr: int = SAMPLE_RATE) -> int:
+    """Length 2*half + 1 of the kaiser_best table for this rate pair (without building it)."""
+    up, down = rate_ratio(orig_sr, target_sr)
+    return 2 * int(np.ceil(KAISER_BEST["num_zeros"] / min(1.0, up / down) * up)) + 1
+
+
+def kaiser_best_window(orig_sr: int, target_sr: int = SAMPLE_RATE):
+    """(w, up, down): the FIR `resample(..., "kaiser_best")` hands to scipy.signal.resample_poly as `window`."""
+    up, down = rate_ratio(orig_sr, target_sr)
+    scale = min(1.0, up / down)
+    half = int(np.ceil(KAISER_BEST["num_zeros"] / scale * up))              # taps each side at the up-sampled rate
+    k = np.arange(-half, half + 1)
+    return kaiser_sinc_kernel(k / up, scale, **KAISER_BEST) / up, up, down    # (resample_poly multiplies the filter by `up`)
+
+
+def kaiser_best_taps(orig_sr: int, target_sr: int = SAMPLE_RATE):
+    """(H, up, down): H = w * up in float64, the table resample_poly actually applies (and mt3_resampler_create takes):
+    y[n] = sum_k x[k] H[n*down + half - k*up], n < ceil(len(x) * up / down)."""
+    w, up, down = kaiser_best_window(orig_sr, target_sr)
+    return w * up, up, down
+
+
 def resample(y: np.ndarray, orig_sr: int, target_sr: int = SAMPLE_RATE, res_type: str = "kaiser_best") -> np.ndarray:
     """res_type: "polyphase" = scipy.signal.resample_poly's own Kaiser(5.0) low-pass of 20 x max(up, down) + 1
     taps; "kaiser_best" (default) = the band-limited sinc interpolation of resampy's kaiser_best filter (see KAISER_BEST), evaluated
     EXACTLY on the polyphase grid (resampy itself interpolates a 512-per-zero-crossing table linearly: ~1e-6 relative).
     Measured difference between the two on a 44.1 kHz fixture and its effect on the log-mel: module docstring,
-    tests/test_io_and_metrics.py::test_resampling_filters_measured."""
+    tests/test_io_and_metrics.py::test_resampling_filters_measured.  The device counterpart is `resample_device`."""
     if orig_sr == target_sr:
         return np.ascontiguousarray(y, np.float32)
     from scipy.signal import resample_poly
-    frac = Fraction(int(target_sr), int(orig_sr))
-    up, down = frac.numerator, frac.denominator
     if res_type == "polyphase":
+        up, down = rate_ratio(orig_sr, target_sr)
         return resample_poly(y.astype(np.float64), up, down).astype(np.float32)
     if res_type != "kaiser_best":
         raise ValueError("res_type must be 'polyphase' or 'kaiser_best'")
-    scale = min(1.0, up / down)
-    half = int(np.ceil(KAISER_BEST["num_zeros"] / scale * up))              # taps each side at the up-sampled rate
-    k = np.arange(-half, half + 1)
-    h = kaiser_sinc_kernel(k / up, scale, **KAISER_BEST) / up                 # (resample_poly multiplies the filter by `up`)
-    return resample_poly(y.astype(np.float64), up, down, window=h).astype(np.float32)
+    w, up, down = kaiser_best_window(orig_sr, target_sr)
+    return resample_poly(y.astype(np.float64), up, down, window=w).astype(np.float32)
+
+
+# ------------------------------------------------------------------ device resample (mt3_resampler_*)
+MAX_DEVICE_TAPS = 1 << 20                    # mt3_resampler_create's limit
+_resamplers = {}
+
+
+def resampled_length(n_in: int, orig_sr: int, target_sr: int = SAMPLE_RATE) -> int:
+    """ceil(n_in * up / down): the number of samples `resample` / `resample_device` produce."""
+    if orig_sr == target_sr:
+        return int(n_in)
+    up, down = rate_ratio(orig_sr, target_sr)
+    return -(-int(n_in) * up // down)
+
+
+def _resampler(orig_sr: int, target_sr: int):
+    """one mt3_resampler per rate pair (kaiser_best taps), created on first use"""
+    key = (int(orig_sr), int(target_sr))
+    if key not in _resamplers:
+        import ctypes as C
+        from . import _lib
+        n_taps = kaiser_best_num_taps(orig_sr, target_sr)
+        if n_taps > MAX_DEVICE_TAPS:
+            raise ValueError("resample_device: %d Hz -> %d Hz needs a %d-tap filter; the device resampler takes at most "
+                             "2^20 taps" % (orig_sr, target_sr, n_taps))
+        h, up, down = kaiser_best_taps(orig_sr, target_sr)
+        h = np.ascontiguousarray(h, np.float64)
+        r = C.c_void_p()
+        lib = _lib.load()
+        rc = lib.mt3_resampler_create(h.ctypes.data, len(h), up, down, C.byref(r))
+        if rc == _lib.MT3_ERR_INVALID:
+            raise ValueError(lib.mt3_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+        _resamplers[key] = r
+    return _resamplers[key]
+
+
+def resample_device(x, orig_sr: int, target_sr: int = SAMPLE_RATE, capacity: int = None):
+    """`resample(x, orig_sr, target_sr)` on the GPU (mt3_resampler_run: the same kaiser_best table, summed in float64).
+    x: float32 1-d torch tensor (CUDA or host) or numpy array.  Returns a CUDA float32 tensor of `capacity` samples
+    (default: the resampled length) with zeros after the resampled length.  The work is stream-ordered on torch's
+    current stream; equal rates copy x without running a kernel.  A rate pair whose table exceeds 2^20 taps raises
+    ValueError."""
+    import torch
+    from . import _lib
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float32))
+    if t.dim() != 1 or t.dtype != torch.float32:
+        raise ValueError("resample_device: x must be a 1-d float32 tensor or array")
+    n_out = resampled_length(t.shape[0], orig_sr, target_sr)
+    capacity = n_out if capacity is None else int(capacity)
+    if capacity < n_out:
+        raise ValueError("resample_device: capacity %d < %d output samples" % (capacity, n_out))
+    if orig_sr == target_sr:
+        out = torch.zeros(capacity, device="cuda", dtype=torch.float32)
+        out[:n_out].copy_(t)
+        return out
+    if t.shape[0] < 1:
+        raise ValueError("resample_device: empty input")
+    r = _resampler(orig_sr, target_sr)
+    t = t.to(device="cuda").contiguous()
+    out = torch.empty(capacity, device="cuda", dtype=torch.float32)
+    _lib.check(_lib.load().mt3_resampler_run(r, t.data_ptr(), t.shape[0], out.data_ptr(), capacity,
+                                             torch.cuda.current_stream().cuda_stream))
+    return out
 
 
 def samples_to_wav_data(samples: np.ndarray, sample_rate: int = SAMPLE_RATE) -> bytes:

@@ -32,6 +32,7 @@ from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import audio_io
 from . import metrics_utils
 from . import network
 from . import note_sequences
@@ -208,10 +209,11 @@ class InferenceModel(object):
             self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
         return torch.cat(out, 0).cpu().numpy()
 
-    def __call__(self, audio):
-        """1-d numpy array of 16 kHz samples -> NoteSequence."""
-        ds = self.audio_to_dataset(audio)
-        examples = self.preprocess(ds, host_inputs=False)
+    def __call__(self, audio, sample_rate: int = SAMPLE_RATE):
+        """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
+        frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
+        notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`."""
+        examples = self._examples(audio, sample_rate)
         # the frontend kernel has already written the feature converter's form of every segment -- [T, 512] rows, 0.0
         # after a short last segment's frames (mt3/models.py:48-98 via models.convert_features) -- and it is still on the
         # device: no host round trip between preprocess and predict_tokens
@@ -222,17 +224,17 @@ class InferenceModel(object):
                                                        encoding_spec=self.encoding_spec)
         return result["est_ns"]
 
-    def score(self, audio, targets, return_token_scores: bool = False):
+    def score(self, audio, targets, return_token_scores: bool = False, *, sample_rate: int = SAMPLE_RATE):
         """Teacher-forced scores of token rows for this audio (t5x score_batch; the reference's infer(mode='score')
         path, which its write_inferences_to_file refuses to write).  The audio goes through the frontend and segmenting
         of `__call__`; targets[i] are the vocabulary ids of segment i in decoder_target_tokens form (EOS included, at
         most 1024).  Returns float64 [n_segments] sequence scores, with return_token_scores also a list of float64
-        per-token scores (one array of len(targets[i]) per segment)."""
+        per-token scores (one array of len(targets[i]) per segment).  sample_rate: as for `__call__`."""
         import torch
         if self.model_config.kv_dtype:
             raise ValueError("score() is not available with kv_dtype=%r: e4m3 K/V caches cannot score"
                              % (self.model_config.kv_dtype,))
-        examples = self.preprocess(self.audio_to_dataset(audio), host_inputs=False)
+        examples = self._examples(audio, sample_rate)
         x, self._logmel_dev = self._logmel_dev, None
         if len(targets) != len(examples):
             raise ValueError("targets has %d rows; the audio has %d segments" % (len(targets), len(examples)))
@@ -254,16 +256,21 @@ class InferenceModel(object):
         tok = np.concatenate(tok) if tok else np.zeros((0, n), np.float64)
         return scores, [tok[i, : len(r)] for i, r in enumerate(rows)]
 
-    def transcribe_many(self, audios: Sequence[Any]) -> List[Any]:
+    def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
         machine is sequential within a file and independent across files, mt3/metrics_utils.py:92-116).  Returns one
-        NoteSequence per file, each identical to `self(audio)`."""
+        NoteSequence per file, each identical to `self(audio)`.  sample_rates: one rate per file (default: all 16 kHz),
+        as for `__call__`."""
         import torch
+        if sample_rates is None:
+            sample_rates = [SAMPLE_RATE] * len(audios)
+        if len(sample_rates) != len(audios):
+            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
         per_file, feats = [], []
-        for audio in audios:
-            examples = self.preprocess(self.audio_to_dataset(audio), host_inputs=False)
+        for audio, sr in zip(audios, sample_rates):
+            examples = self._examples(audio, sr)
             per_file.append(examples)
             feats.append(self._logmel_dev)
         self._logmel_dev = None
@@ -279,6 +286,29 @@ class InferenceModel(object):
         return out
 
     # ------------------------------------------------------------------ host preprocessing
+    def _examples(self, audio, sample_rate: int):
+        """audio at `sample_rate` -> the examples of `preprocess(..., host_inputs=False)`, log-mel left in _logmel_dev"""
+        if int(sample_rate) == SAMPLE_RATE:
+            return self.preprocess(self.audio_to_dataset(audio), host_inputs=False)
+        if int(sample_rate) != sample_rate or sample_rate < 1:
+            raise ValueError("sample_rate must be a positive integer, got %r" % (sample_rate,))
+        return self._device_examples(audio, int(sample_rate))
+
+    def _device_examples(self, audio, sample_rate: int):
+        """Native-rate samples: uploaded as float32 and resampled to 16 kHz on the device (audio_io.resample_device, the
+        kaiser_best filter of audio_io.resample) straight into the zeroed [n_segments, T*hop] buffer the frontend reads.
+        Frames, segment counts and input_times are those `_audio_to_frames` + `preprocess` derive from the 16 kHz samples
+        of length n_out (it always pads: n_out // hop + 1 frames).  The examples' 'raw_inputs' are None: the 16 kHz samples
+        stay on the device."""
+        hop, T = self.spectrogram_config.hop_width, self.inputs_length
+        x = audio if hasattr(audio, "data_ptr") else np.ascontiguousarray(np.asarray(audio).reshape(-1), np.float32)
+        n_out = audio_io.resampled_length(x.shape[0], sample_rate, SAMPLE_RATE)
+        n_frames = n_out // hop + 1
+        times = np.arange(n_frames) / self.spectrogram_config.frames_per_second
+        counts = self._segment_counts(n_frames)
+        audio_dev = audio_io.resample_device(x, sample_rate, SAMPLE_RATE, capacity=len(counts) * T * hop)
+        return self._spectrogram_examples(audio_dev.view(len(counts), T * hop), counts, times, False, None)
+
     def audio_to_dataset(self, audio):
         frames, frame_times = self._audio_to_frames(audio)
         return {"inputs": frames, "input_times": frame_times}
@@ -301,20 +331,31 @@ class InferenceModel(object):
         import torch
         frames, times = ds["inputs"], ds["input_times"]
         T, hop = self.inputs_length, self.spectrogram_config.hop_width
-        n_seg = -(-len(frames) // T)
-        audio = np.zeros((n_seg, T * hop), np.float32)
-        counts = []
-        for s in range(n_seg):
+        counts = self._segment_counts(len(frames))
+        audio = np.zeros((len(counts), T * hop), np.float32)
+        for s in range(len(counts)):
             chunk = frames[s * T:(s + 1) * T]
             audio[s, : chunk.size] = chunk.reshape(-1)
-            counts.append(len(chunk))
-        logmel_dev = spectrograms.compute_spectrogram_batch(torch.from_numpy(audio).cuda(), counts, self.spectrogram_config)
+        return self._spectrogram_examples(torch.from_numpy(audio).cuda(), counts, times, host_inputs, audio)
+
+    def _segment_counts(self, n_frames: int) -> List[int]:
+        """frames of each `inputs_length`-frame segment (split_tokens_to_inputs_length; the last one may be short)"""
+        T = self.inputs_length
+        return [min(T, n_frames - s) for s in range(0, n_frames, T)]
+
+    def _spectrogram_examples(self, audio_dev, counts, times, host_inputs: bool, audio_host):
+        """The tail of `preprocess`: one frontend launch over the [n_segments, T*hop] device samples, then the examples.
+        audio_host: the same samples on the host for 'raw_inputs' (None: not kept)."""
+        T, hop = self.inputs_length, self.spectrogram_config.hop_width
+        n_seg = len(counts)
+        logmel_dev = spectrograms.compute_spectrogram_batch(audio_dev, counts, self.spectrogram_config)
         # host_inputs=False: the device tensor is kept for the predict_tokens call that follows (and dropped by it);
         # otherwise the examples carry host arrays, as the reference's preprocess returns them, and nothing stays pinned
         self._logmel_dev = None if host_inputs else logmel_dev
         logmel = logmel_dev.cpu().numpy() if host_inputs else None
         return [{"inputs": logmel[s, : counts[s]] if host_inputs else None, "input_times": times[s * T:(s + 1) * T],
-                 "raw_inputs": audio[s, : counts[s] * hop], "targets": np.zeros((0,), np.int32)}
+                 "raw_inputs": None if audio_host is None else audio_host[s, : counts[s] * hop],
+                 "targets": np.zeros((0,), np.int32)}
                 for s in range(n_seg)]
 
     def postprocess(self, tokens, example):
