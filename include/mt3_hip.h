@@ -129,6 +129,39 @@ void mt3_resampler_destroy(mt3_resampler* r);
 int mt3_resampler_run(mt3_resampler* r, const float* d_in, int64_t n_in, float* d_out, int64_t out_capacity,
                       void* stream);
 
+/* --------------------------------------------------------------- PCM decode
+ * Replaces the sample decode and the channel mixdown inside note_seq.audio_io.wav_data_to_samples_librosa (NB cell 2),
+ * which the Python mirror evaluates as mt3_amd/audio_io.read_wav: scipy.io.wavfile.read, the integer types scaled to
+ * [-1, 1) in float32, `mean(axis=1)` over the channels.  The caller uploads the WAV file's data chunk as it is
+ * (interleaved little-endian frames, `channels` samples each) and the device computes, per sample,
+ *   MT3_PCM_U8   1 byte unsigned            (float(v) - 128) / 128
+ *   MT3_PCM_S16  2 bytes                    float(v) / 2^15
+ *   MT3_PCM_S24  3 bytes packed             float(int32(b0 << 8 | b1 << 16 | b2 << 24)) / 2^31   (left-justified)
+ *   MT3_PCM_S32  4 bytes                    float(v) (round to nearest even) / 2^31
+ *   MT3_PCM_F32  4 bytes IEEE               v  (NaN, infinities and -0.0 pass through)
+ *   MT3_PCM_F64  8 bytes IEEE               float(v) (round to nearest even)
+ * and per frame of C = `channels` samples
+ *   C = 1        the sample itself
+ *   2 <= C <= 7  acc = +0.0f; acc = acc + s_c for c = 0 .. C-1 in float32; acc / float(C), correctly rounded
+ * which is numpy's mean over fewer than 8 addends: the same bits as read_wav on the host.  8 or more channels are not
+ * covered (numpy sums those with eight partial accumulators); the Python mirror decodes such files on the host.
+ * d_pcm is aligned to the size of one sample; MT3_PCM_S24 needs byte alignment only.
+ * mt3_pcm_decode: d_out[0 .. n_frames) = the mono samples, +0.0 in [n_frames, out_capacity), nothing written at or
+ *   past out_capacity (d_out may be the frontend's [n_segments, T*hop] buffer: the path of a 16 kHz file).
+ * mt3_resampler_run_pcm: what mt3_resampler_run gives on those mono samples, bit for bit; the frames are decoded as
+ *   the kernel stages its input, so the mono float32 array never exists in device memory.
+ * Both: one launch enqueued on `stream`, nothing allocated, copied or waited for.  MT3_ERR_INVALID, before any HIP
+ * call, for a NULL pointer, n_frames < 1, channels outside 1 .. 7, an unknown format, out_capacity below the output
+ * length, or sizes whose index arithmetic would leave int64.
+ */
+enum { MT3_PCM_U8 = 0, MT3_PCM_S16 = 1, MT3_PCM_S24 = 2, MT3_PCM_S32 = 3, MT3_PCM_F32 = 4, MT3_PCM_F64 = 5 };
+#define MT3_PCM_MAX_CHANNELS 7
+
+int mt3_pcm_decode(const void* d_pcm, int64_t n_frames, int32_t channels, int32_t format, float* d_out,
+                   int64_t out_capacity, void* stream);
+int mt3_resampler_run_pcm(mt3_resampler* r, const void* d_pcm, int64_t n_frames, int32_t channels, int32_t format,
+                          float* d_out, int64_t out_capacity, void* stream);
+
 /* -------------------------------------------------------------------- engine
  * Replaces network.Transformer (mt3/network.py:265-409, layers in mt3/layers.py)
  * as driven by t5x predict_batch_with_aux through

@@ -26,6 +26,8 @@ DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
  STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS) = range(12)
+(MT3_PCM_U8, MT3_PCM_S16, MT3_PCM_S24, MT3_PCM_S32, MT3_PCM_F32, MT3_PCM_F64) = range(6)     # mt3_pcm_decode formats
+PCM_MAX_CHANNELS = 7
 MAX_BEAMS = 8                                  # mt3_engine_decode_beams: 1 <= num_beams <= 8
 EV_SHIFT, EV_PITCH, EV_VELOCITY, EV_TIE, EV_PROGRAM, EV_DRUM = range(6)
 EVENT_TYPE_NAMES = ("shift", "pitch", "velocity", "tie", "program", "drum")
@@ -83,6 +85,8 @@ SIGNATURES = {
     "mt3_resampler_create": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "mt3_resampler_destroy": (None, [_P]),
     "mt3_resampler_run": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "mt3_pcm_decode": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "mt3_resampler_run_pcm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "mt3_engine_create": (C.c_int, [C.POINTER(EngineConfig), C.POINTER(_P)]),
     "mt3_engine_destroy": (None, [_P]),
     "mt3_engine_load_weight": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),

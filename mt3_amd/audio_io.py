@@ -23,7 +23,10 @@ polyphase filter's -66 dB stop band, not a property of the material.
 """
 from __future__ import annotations
 
+import collections
 import io
+import struct
+import warnings
 from fractions import Fraction
 
 import numpy as np
@@ -177,6 +180,129 @@ def resample_device(x, orig_sr: int, target_sr: int = SAMPLE_RATE, capacity: int
     _lib.check(_lib.load().mt3_resampler_run(r, t.data_ptr(), t.shape[0], out.data_ptr(), capacity,
                                              torch.cuda.current_stream().cuda_stream))
     return out
+
+
+# ------------------------------------------------------------------ device decode (mt3_pcm_decode, mt3_resampler_run_pcm)
+WavInfo = collections.namedtuple("WavInfo", "sample_rate channels format data_offset data_bytes frames")
+_SILENT_CHUNKS = (b"fact", b"LIST", b"JUNK", b"Fake")        # what scipy.io.wavfile.read skips without a warning
+_GUID_TAIL = b"\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71"      # {XXXXXXXX-0000-0010-8000-00AA00389B71}
+
+
+def _open_wav(wav_data):
+    return io.BytesIO(wav_data) if isinstance(wav_data, (bytes, bytearray, memoryview)) else open(wav_data, "rb")
+
+
+def wav_info(wav_data):
+    """bytes or path -> WavInfo(sample_rate, channels, MT3_PCM_* format, data_offset, data_bytes, frames) when the
+    device decode gives `read_wav`'s samples for this file, else None (the caller then calls `read_wav`, with scipy's
+    errors and warnings).  Standard library only; reads the chunk headers, not the samples.
+
+    Accepted: little-endian RIFF/WAVE whose chunks up to the RIFF size are one `fmt `, one `data` after it, and
+    `fact` / `LIST` / `JUNK` / `Fake` chunks (scipy skips those silently; any other chunk makes it warn), all of them
+    wholly inside the file; format tag 1 (PCM: 8, 16, 24 or 32 bits), 3 (IEEE float: 32 or 64 bits) or 0xFFFE with one
+    of those as sub-format; block_align == channels * bits / 8; 1 .. 7 channels; a data chunk of a whole number of
+    frames, at least one.  Rejected, among others: RIFX, RF64, 12- and 20-bit samples, 64-bit integers, 8 or more
+    channels, truncated files, a PCM header whose byte rate is not rate * block_align (scipy raises on it)."""
+    from . import _lib
+    if hasattr(wav_data, "read"):                     # an open file object: scipy's business
+        return None
+    with _open_wav(wav_data) as f:
+        size = f.seek(0, 2)
+        f.seek(0)
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:] != b"WAVE":
+            return None
+        riff_end = struct.unpack("<I", head[4:8])[0] + 8
+        fmt = data = None
+        pos = 12
+        while pos < riff_end:                         # scipy's loop: `while fid.tell() < file_size`
+            f.seek(pos)
+            ck = f.read(8)
+            if len(ck) < 8:
+                return None                           # scipy: raises, or warns once it has the data
+            n = struct.unpack("<I", ck[4:])[0]
+            if pos + 8 + n > size:
+                return None
+            if ck[:4] == b"fmt ":
+                if fmt is not None or data is not None or n < 16:
+                    return None
+                fmt = f.read(min(n, 40))
+            elif ck[:4] == b"data":
+                if fmt is None or data is not None:
+                    return None
+                data = (pos + 8, n)
+            elif ck[:4] not in _SILENT_CHUNKS:
+                return None
+            pos += 8 + n + (n & 1)                    # chunks are padded to an even size
+    if fmt is None or data is None:
+        return None
+    tag, channels, rate, byte_rate, block_align, bits = struct.unpack("<HHIIHH", fmt[:16])
+    if tag == 0xFFFE:                                 # WAVE_FORMAT_EXTENSIBLE: cbSize, valid bits, mask, sub-format GUID
+        if len(fmt) < 40 or struct.unpack("<H", fmt[16:18])[0] < 22 or fmt[28:40] != _GUID_TAIL:
+            return None
+        tag = struct.unpack("<I", fmt[24:28])[0]
+    if tag == 1:
+        if byte_rate != rate * block_align:
+            return None
+        pcm = {8: _lib.MT3_PCM_U8, 16: _lib.MT3_PCM_S16, 24: _lib.MT3_PCM_S24, 32: _lib.MT3_PCM_S32}.get(bits)
+    elif tag == 3:
+        pcm = {32: _lib.MT3_PCM_F32, 64: _lib.MT3_PCM_F64}.get(bits)
+    else:
+        return None
+    if pcm is None or rate < 1 or not 1 <= channels <= _lib.PCM_MAX_CHANNELS or block_align != channels * bits // 8:
+        return None
+    offset, nbytes = data
+    if nbytes < block_align or nbytes % block_align:
+        return None
+    return WavInfo(int(rate), int(channels), pcm, offset, nbytes, nbytes // block_align)
+
+
+def _upload_chunk(wav_data, info):
+    """the data chunk's bytes as a CUDA uint8 tensor: one copy out of the caller's buffer, or one read of that part of
+    the file, then the upload"""
+    import torch
+    if isinstance(wav_data, (bytes, bytearray, memoryview)):
+        raw = np.frombuffer(wav_data, np.uint8, info.data_bytes, info.data_offset)
+        with warnings.catch_warnings():               # torch warns that a view of `bytes` is read-only; it is only read
+            warnings.simplefilter("ignore", UserWarning)
+            host = torch.from_numpy(raw)
+    else:
+        host = torch.from_numpy(np.fromfile(wav_data, np.uint8, info.data_bytes, offset=info.data_offset))
+    if host.numel() != info.data_bytes:
+        raise ValueError("read_wav_device: the file changed while it was read")
+    return host.to(device="cuda")
+
+
+def read_wav_device(wav_data, target_sr: int = SAMPLE_RATE, capacity: int = None):
+    """bytes or path -> (CUDA float32 tensor of `capacity` samples at `target_sr`, zeros after the resampled length;
+    native sample rate; resampled length): `read_wav` + `resample_device` with the PCM decode and the channel mixdown
+    on the GPU as well.  Only the file's data chunk is uploaded, as it is, and ONE kernel runs on torch's current
+    stream: mt3_pcm_decode at equal rates, mt3_resampler_run_pcm otherwise (the same bits as the host decode followed
+    by `resample_device`).  A file `wav_info` does not take (RIFX, 20-bit samples, 8 or more channels, a truncated
+    chunk, ...) goes through `read_wav` on the host instead, with its errors and warnings.  capacity defaults to the
+    resampled length.  A rate pair whose filter exceeds 2^20 taps raises ValueError."""
+    import torch
+    from . import _lib
+    info = wav_info(wav_data)
+    if info is None:
+        y, native_sr = read_wav(wav_data)
+        n_out = resampled_length(len(y), native_sr, target_sr)
+        return resample_device(y, native_sr, target_sr, capacity=capacity), native_sr, n_out
+    n_out = resampled_length(info.frames, info.sample_rate, target_sr)
+    capacity = n_out if capacity is None else int(capacity)
+    if capacity < n_out:
+        raise ValueError("read_wav_device: capacity %d < %d output samples" % (capacity, n_out))
+    r = None if info.sample_rate == target_sr else _resampler(info.sample_rate, target_sr)     # ValueError before the upload
+    pcm = _upload_chunk(wav_data, info)
+    out = torch.empty(capacity, device="cuda", dtype=torch.float32)
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    if r is None:
+        _lib.check(lib.mt3_pcm_decode(pcm.data_ptr(), info.frames, info.channels, info.format, out.data_ptr(), capacity,
+                                      stream))
+    else:
+        _lib.check(lib.mt3_resampler_run_pcm(r, pcm.data_ptr(), info.frames, info.channels, info.format, out.data_ptr(),
+                                             capacity, stream))
+    return out, info.sample_rate, n_out
 
 
 def samples_to_wav_data(samples: np.ndarray, sample_rate: int = SAMPLE_RATE) -> bytes:

@@ -21,6 +21,11 @@
 //     (n*down reaches 4.2e9 on a 10-minute 44.1 kHz file).
 //   * outputs n_out <= n < out_capacity are written as 0.0 (the frontend's zero-padded [n_segments, T*hop] layout);
 //     nothing at or past out_capacity is touched.
+//   * the input is a sample source (pcm.h), read only by the LDS staging line: a float32 array (mt3_resampler_run) or
+//     a WAV file's PCM frames, decoded and mixed down to mono as they are staged (mt3_resampler_run_pcm: the decode
+//     inside wav_data_to_samples_librosa, NB cell 2, fused in).  A frame is decoded once per workgroup whose span
+//     holds it, about 1.5 times at 44.1 kHz, against 353 f64 multiply-adds per output.  From LDS on both paths are
+//     the same code, so the PCM path gives mt3_resampler_run's bits on read_wav's samples.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -30,6 +35,7 @@
 
 #include "common.h"
 #include "mt3_hip.h"
+#include "pcm.h"
 
 struct mt3_resampler {
   int32_t up = 0, down = 0;
@@ -44,7 +50,8 @@ constexpr int kThreads = 256;          // outputs per workgroup
 constexpr int kSpan = 4096;            // input samples staged in LDS per pass (16 KB)
 constexpr int64_t kMaxTaps = 1 << 20;
 
-__global__ __launch_bounds__(kThreads) void resample_poly_kernel(const float* __restrict__ x, int64_t n_in,
+template <class Src>
+__global__ __launch_bounds__(kThreads) void resample_poly_kernel(Src x, int64_t n_in,
                                                                  const double* __restrict__ taps, int32_t up,
                                                                  int32_t down, int64_t half, int32_t tpp,
                                                                  int64_t n_out, float* __restrict__ y, int64_t cap) {
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void resample_poly_kernel(const float* __
   for (int64_t c0 = lo; c0 <= hi; c0 += kSpan) {
     const int len = static_cast<int>(hi + 1 - c0 < kSpan ? hi + 1 - c0 : kSpan);
     __syncthreads();                                   // the previous pass has been read
-    for (int i = threadIdx.x; i < len; i += kThreads) xs[i] = x[c0 + i];
+    for (int i = threadIdx.x; i < len; i += kThreads) xs[i] = x(c0 + i);
     __syncthreads();
     if (n <= n_last) {
       // taps t with kmax - t in [c0, c0 + len) and 0 <= t < tpp
@@ -90,6 +97,27 @@ int64_t gcd64(int64_t a, int64_t b) {
     b = t;
   }
   return a;
+}
+
+// the size checks and the one launch mt3_resampler_run and mt3_resampler_run_pcm share (n_in >= 1 samples of `src`)
+template <class Src>
+int launch(const char* who, const mt3_resampler* r, Src src, int64_t n_in, float* d_out, int64_t out_capacity,
+           void* stream) {
+  const std::string w(who);
+  const int64_t n_out = mt3_resample_output_length(n_in, r->up, r->down);
+  if (n_out < 0) return mt3::fail(MT3_ERR_INVALID, w + ": n_in too large");
+  if (out_capacity < n_out)
+    return mt3::fail(MT3_ERR_INVALID, w + ": out_capacity " + std::to_string(out_capacity) + " is less than the " +
+                                          std::to_string(n_out) + " output samples");
+  const int64_t blocks = (out_capacity + kThreads - 1) / kThreads;
+  // n*down + half must stay in int64 for every n of the grid
+  if (blocks > INT32_MAX || blocks * kThreads > (INT64_MAX / 2 - r->half) / r->down)
+    return mt3::fail(MT3_ERR_INVALID, w + ": out_capacity too large");
+  hipLaunchKernelGGL(resample_poly_kernel<Src>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), src, n_in, r->d_taps, r->up, r->down, r->half, r->tpp, n_out,
+                     d_out, out_capacity);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
 }
 
 }  // namespace
@@ -144,20 +172,17 @@ int mt3_resampler_run(mt3_resampler* r, const float* d_in, int64_t n_in, float* 
                       void* stream) {
   if (!r || !d_in || !d_out) return mt3::fail(MT3_ERR_INVALID, "mt3_resampler_run: null argument");
   if (n_in < 1) return mt3::fail(MT3_ERR_INVALID, "mt3_resampler_run: n_in must be >= 1");
-  const int64_t n_out = mt3_resample_output_length(n_in, r->up, r->down);
-  if (n_out < 0) return mt3::fail(MT3_ERR_INVALID, "mt3_resampler_run: n_in too large");
-  if (out_capacity < n_out)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_resampler_run: out_capacity " + std::to_string(out_capacity) +
-                                          " is less than the " + std::to_string(n_out) + " output samples");
-  const int64_t blocks = (out_capacity + kThreads - 1) / kThreads;
-  // n*down + half must stay in int64 for every n of the grid
-  if (blocks > INT32_MAX || blocks * kThreads > (INT64_MAX / 2 - r->half) / r->down)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_resampler_run: out_capacity too large");
-  hipLaunchKernelGGL(resample_poly_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream), d_in, n_in, r->d_taps, r->up, r->down, r->half, r->tpp, n_out,
-                     d_out, out_capacity);
-  MT3_HIP_CHECK(hipGetLastError());
-  return MT3_OK;
+  return launch("mt3_resampler_run", r, mt3::F32Samples{d_in}, n_in, d_out, out_capacity, stream);
+}
+
+int mt3_resampler_run_pcm(mt3_resampler* r, const void* d_pcm, int64_t n_frames, int32_t channels, int32_t format,
+                          float* d_out, int64_t out_capacity, void* stream) {
+  const int rc = mt3::pcm_check("mt3_resampler_run_pcm", d_pcm, d_out, n_frames, channels, format);
+  if (rc != MT3_OK) return rc;
+  if (!r) return mt3::fail(MT3_ERR_INVALID, "mt3_resampler_run_pcm: null resampler");
+  return mt3::pcm_dispatch(format, d_pcm, channels, [&](auto src) {
+    return launch("mt3_resampler_run_pcm", r, src, n_frames, d_out, out_capacity, stream);
+  });
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ alpha 0.6, which is what the reference's predict_batch_with_aux runs (SURVEY.md 
 """
 from __future__ import annotations
 
+import functools
 import json
 import os
 import re
@@ -213,7 +214,16 @@ class InferenceModel(object):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
         notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`."""
-        examples = self._examples(audio, sample_rate)
+        return self._transcribe_examples(self._examples(audio, sample_rate))
+
+    def transcribe_wav(self, wav_data):
+        """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
+        note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
+        to 16 kHz run on the device in one launch (`_wav_examples`)."""
+        return self._transcribe_examples(self._wav_examples(wav_data))
+
+    def _transcribe_examples(self, examples):
+        """the examples of one file, their log-mel in _logmel_dev -> NoteSequence"""
         # the frontend kernel has already written the feature converter's form of every segment -- [T, 512] rows, 0.0
         # after a short last segment's frames (mt3/models.py:48-98 via models.convert_features) -- and it is still on the
         # device: no host round trip between preprocess and predict_tokens
@@ -263,15 +273,25 @@ class InferenceModel(object):
         machine is sequential within a file and independent across files, mt3/metrics_utils.py:92-116).  Returns one
         NoteSequence per file, each identical to `self(audio)`.  sample_rates: one rate per file (default: all 16 kHz),
         as for `__call__`."""
-        import torch
         if sample_rates is None:
             sample_rates = [SAMPLE_RATE] * len(audios)
         if len(sample_rates) != len(audios):
             raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
+        return self._transcribe_files([functools.partial(self._examples, audio, sr)
+                                       for audio, sr in zip(audios, sample_rates)])
+
+    def transcribe_wavs(self, wavs: Sequence[Any]) -> List[Any]:
+        """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
+        `self.transcribe_wav(wav)`."""
+        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs])
+
+    def _transcribe_files(self, make_examples):
+        """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
+        NoteSequence per file, all segments through the engine as one job"""
+        import torch
         per_file, feats = [], []
-        for audio, sr in zip(audios, sample_rates):
-            examples = self._examples(audio, sr)
-            per_file.append(examples)
+        for make in make_examples:
+            per_file.append(make())
             feats.append(self._logmel_dev)
         self._logmel_dev = None
         if not per_file:
@@ -300,13 +320,31 @@ class InferenceModel(object):
         Frames, segment counts and input_times are those `_audio_to_frames` + `preprocess` derive from the 16 kHz samples
         of length n_out (it always pads: n_out // hop + 1 frames).  The examples' 'raw_inputs' are None: the 16 kHz samples
         stay on the device."""
-        hop, T = self.spectrogram_config.hop_width, self.inputs_length
         x = audio if hasattr(audio, "data_ptr") else np.ascontiguousarray(np.asarray(audio).reshape(-1), np.float32)
         n_out = audio_io.resampled_length(x.shape[0], sample_rate, SAMPLE_RATE)
+        return self._segment_device_audio(
+            n_out, lambda capacity: audio_io.resample_device(x, sample_rate, SAMPLE_RATE, capacity=capacity))
+
+    def _wav_examples(self, wav_data):
+        """A WAV file (bytes or path): its data chunk is uploaded as it is and decoded, mixed down and resampled on the
+        device (audio_io.read_wav_device) into the buffer `_device_examples` fills, with the same frames, segment counts
+        and input_times.  A file audio_io.wav_info does not take is decoded by `read_wav` on the host and goes the way of
+        `__call__`."""
+        info = audio_io.wav_info(wav_data)
+        if info is None:
+            return self._examples(*audio_io.read_wav(wav_data))
+        n_out = audio_io.resampled_length(info.frames, info.sample_rate, SAMPLE_RATE)
+        return self._segment_device_audio(
+            n_out, lambda capacity: audio_io.read_wav_device(wav_data, SAMPLE_RATE, capacity)[0])
+
+    def _segment_device_audio(self, n_out: int, fill):
+        """n_out 16 kHz samples that fill(capacity) puts at the head of a zero-padded device buffer of `capacity` samples
+        -> examples: the buffer is the frontend's [n_segments, T*hop] layout"""
+        hop, T = self.spectrogram_config.hop_width, self.inputs_length
         n_frames = n_out // hop + 1
         times = np.arange(n_frames) / self.spectrogram_config.frames_per_second
         counts = self._segment_counts(n_frames)
-        audio_dev = audio_io.resample_device(x, sample_rate, SAMPLE_RATE, capacity=len(counts) * T * hop)
+        audio_dev = fill(len(counts) * T * hop)
         return self._spectrogram_examples(audio_dev.view(len(counts), T * hop), counts, times, False, None)
 
     def audio_to_dataset(self, audio):

@@ -1,0 +1,61 @@
+"""Command line: WAV files -> MIDI files (the notebook's upload / transcribe / download cells in one call).
+
+    python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
+                                 IN.wav [IN2.wav ...] [-o OUT]
+
+Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
+engine as one job (`InferenceModel.transcribe_wavs`).  --checkpoint is handed to `InferenceModel` as it is: a t5x
+checkpoint directory, a flat or compact `.npz`, or `random:<seed>`.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+
+def plan(argv=None):
+    """parse the arguments and decide every output path; nothing is loaded or built.  Exits (status 2, message on
+    stderr) on a missing input or an -o that cannot hold the outputs."""
+    ap = argparse.ArgumentParser(prog="python -m mt3_amd.transcribe", description="Transcribe WAV files to MIDI.")
+    ap.add_argument("--checkpoint", required=True, help="t5x checkpoint directory, .npz, or random:<seed>")
+    ap.add_argument("--model", default="mt3", choices=("mt3", "ismir2021"))
+    ap.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
+    ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
+    ap.add_argument("inputs", nargs="+", metavar="IN.wav")
+    args = ap.parse_args(argv)
+    for path in args.inputs:
+        if not os.path.isfile(path):
+            ap.error("no such file: %s" % path)
+    out = args.output
+    if out is None:
+        outputs = [os.path.splitext(p)[0] + ".mid" for p in args.inputs]
+    elif len(args.inputs) == 1 and not os.path.isdir(out):
+        outputs = [out]
+    else:
+        if os.path.exists(out) and not os.path.isdir(out):
+            ap.error("-o %s is a file; %d inputs need a directory" % (out, len(args.inputs)))
+        outputs = [os.path.join(out, os.path.splitext(os.path.basename(p))[0] + ".mid") for p in args.inputs]
+    if len(set(os.path.abspath(p) for p in outputs)) != len(outputs):
+        ap.error("two inputs would be written to the same output file")
+    return args, outputs
+
+
+def main(argv=None) -> int:
+    args, outputs = plan(argv)
+    from . import inference, midi_io
+    try:
+        model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype)
+        sequences = model.transcribe_wavs(args.inputs)
+    except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
+        print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
+        return 1
+    for ns, path in zip(sequences, outputs):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        midi_io.note_sequence_to_midi_file(ns, path)
+        print("%s: %d notes" % (path, len(ns.notes)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -9,10 +9,20 @@ host-resampled up to 44.1 kHz and written as a stereo int16 WAV (both channels e
   c_16k_file        model(y16) on the 16 kHz file itself: bench.py's single_file.file_sized_engine_refill on this box
   d_16k_resampled   model(y16) on the 16 kHz samples (a) resamples from the WAV: the model call of (a) and (b) alone (the
                     round trip through 44.1 kHz int16 changes the audio, so (a), (b) and (d) decode other notes than (c))
+  e_wav_device      model.transcribe_wav(wav_bytes): the data chunk uploaded as it is, PCM decode + mixdown + resample in
+                    one launch (mt3_resampler_run_pcm), frontend, engine
+  e_wav_device_path the same from a path on disk (the chunk is read from the file inside the timed call)
 Each wall time is the median of --runs timed calls after one warm-up call, clocked on the host around work that ends
-in a device synchronise.  notes_identical: (a) and (b) give the same notes.
+in a device synchronise; min_s / max_s are the spread of those calls.  notes_identical: (a), (b) and both (e) give the
+same notes.
   resample_kernel_ms  device time of mt3_resampler_run on the 10-minute file (events; median of 20)
   h2d_ms              the upload of the native f32 samples (events; pageable host memory, as the model call does it)
+  pcm_kernel_ms       device time of mt3_resampler_run_pcm on the file's raw frames (events; median of 20; _min / _max
+                      next to it, as for resample_kernel_ms)
+  pcm_decode_ms       device time of mt3_pcm_decode on the same bytes (the path of a 16 kHz file), with the bytes it moves
+                      per second (4 in and 4 out per stereo int16 frame) against the 8 TB/s HBM peak
+  h2d_pcm_ms          the upload of the raw data chunk (events; out of the caller's bytes object)
+  file_read_s         reading the data chunk from the file on disk (page cache warm; median of --runs)
   host_resample_s     audio_io.resample alone (median of --runs)
   read_wav_s          audio_io.read_wav alone: PCM decode and stereo mixdown on the host (median of --runs)
 Prints one JSON line and writes it to --out.
@@ -23,6 +33,7 @@ import json
 import os
 import statistics
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,6 +80,17 @@ def main():
     def path_c():
         return m(wav16)
 
+    wav_dir = tempfile.TemporaryDirectory()
+    wav_path = os.path.join(wav_dir.name, "ten_minutes.wav")
+    with open(wav_path, "wb") as f:
+        f.write(wav_bytes)
+
+    def path_e():
+        return m.transcribe_wav(wav_bytes)
+
+    def path_e_path():
+        return m.transcribe_wav(wav_path)
+
     y16_wav = audio_io.resample(*audio_io.read_wav(wav_bytes))
 
     def path_d():
@@ -90,11 +112,14 @@ def main():
            "runs": args.runs, "wav_bytes": len(wav_bytes)}
     res = {}
     for key, fn in (("c_16k_file", path_c), ("a_host_resample", path_a), ("b_device_resample", path_b),
-                     ("d_16k_resampled", path_d)):
+                     ("d_16k_resampled", path_d), ("e_wav_device", path_e), ("e_wav_device_path", path_e_path)):
         wall, walls, ns = timed(fn)
         res[key] = notes(ns)
-        rec[key] = {"wall_s": wall, "walls_s": walls, "notes": len(ns.notes)}
-    rec["notes_identical"] = res["a_host_resample"] == res["b_device_resample"]
+        rec[key] = {"wall_s": wall, "min_s": min(walls), "max_s": max(walls), "walls_s": walls, "notes": len(ns.notes)}
+    rec["notes_identical"] = (res["a_host_resample"] == res["b_device_resample"] == res["e_wav_device"]
+                              == res["e_wav_device_path"])
+    rec["e_over_b"] = rec["e_wav_device"]["wall_s"] / rec["b_device_resample"]["wall_s"]
+    rec["b_minus_e_s"] = rec["b_device_resample"]["wall_s"] - rec["e_wav_device"]["wall_s"]
     rec["b_over_c"] = rec["b_device_resample"]["wall_s"] / rec["c_16k_file"]["wall_s"]
     rec["a_over_c"] = rec["a_host_resample"]["wall_s"] / rec["c_16k_file"]["wall_s"]
     rec["b_over_d"] = rec["b_device_resample"]["wall_s"] / rec["d_16k_resampled"]["wall_s"]
@@ -126,6 +151,48 @@ def main():
     rec["h2d_ms"] = statistics.median(h2d)
     rec["resample_kernel_ms"] = statistics.median(kern)
     rec["resample_kernel_ms_min"] = min(kern)
+    rec["resample_kernel_ms_max"] = max(kern)
+    # the same file through the PCM entries: raw chunk upload, fused decode + resample, decode alone
+    from mt3_amd import _lib
+    info = audio_io.wav_info(wav_bytes)
+    lib, rs = _lib.load(), audio_io._resampler(r, 16000)
+    stream = torch.cuda.current_stream().cuda_stream
+    out_pcm = torch.empty(len(y16h), device="cuda", dtype=torch.float32)
+    mono = torch.empty(info.frames, device="cuda", dtype=torch.float32)
+    e3 = torch.cuda.Event(enable_timing=True)
+    h2d_pcm, kern_pcm, dec = [], [], []
+    for i in range(21):                           # the first pass warms the new kernels up and is not kept
+        e0.record()
+        pd = audio_io._upload_chunk(wav_bytes, info)
+        e1.record()
+        _lib.check(lib.mt3_resampler_run_pcm(rs, pd.data_ptr(), info.frames, info.channels, info.format,
+                                             out_pcm.data_ptr(), out_pcm.shape[0], stream))
+        e2.record()
+        _lib.check(lib.mt3_pcm_decode(pd.data_ptr(), info.frames, info.channels, info.format, mono.data_ptr(),
+                                      mono.shape[0], stream))
+        e3.record()
+        torch.cuda.synchronize()
+        if i:
+            h2d_pcm.append(e0.elapsed_time(e1))
+            kern_pcm.append(e1.elapsed_time(e2))
+            dec.append(e2.elapsed_time(e3))
+    rec["h2d_pcm_ms"] = statistics.median(h2d_pcm)
+    rec["pcm_kernel_ms"] = statistics.median(kern_pcm)
+    rec["pcm_kernel_ms_min"] = min(kern_pcm)
+    rec["pcm_kernel_ms_max"] = max(kern_pcm)
+    rec["pcm_decode_ms"] = statistics.median(dec)
+    rec["pcm_decode_bytes"] = info.data_bytes + 4 * info.frames
+    rec["pcm_decode_tb_per_s"] = rec["pcm_decode_bytes"] / (rec["pcm_decode_ms"] * 1e-3) / 1e12
+    rec["pcm_decode_share_of_hbm_peak"] = rec["pcm_decode_tb_per_s"] / 8.0
+    rec["pcm_vs_float_path_samples_differing"] = int((out_pcm != out).sum().item())
+    rec["pcm_decode_vs_read_wav_samples_differing"] = int((mono.cpu().numpy().view(np.int32) != y.view(np.int32)).sum())
+    fr = []
+    for _ in range(args.runs):
+        t0 = time.perf_counter()
+        np.fromfile(wav_path, np.uint8, info.data_bytes, offset=info.data_offset)
+        fr.append(time.perf_counter() - t0)
+    rec["file_read_s"] = statistics.median(fr)
+    wav_dir.cleanup()
     taps = audio_io.kaiser_best_num_taps(r)
     up, down = audio_io.rate_ratio(r)
     rec["multiply_adds"] = int(len(y16h)) * (-(-taps // up))
