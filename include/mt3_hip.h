@@ -465,6 +465,18 @@ int mt3_op_gemm_ex(int32_t dtype, const void* d_A, int32_t a_is_f32, int32_t nor
                    void* d_out, int32_t M, int32_t N, int32_t K, int32_t epilogue, const float* d_aux,
                    int32_t seq_len, int32_t small, const float* d_a_ss, void* d_out_ct, float* d_out_ss,
                    void* stream);
+/* The two decode-sized launches that carry a SECOND product in extra column tiles (the qkv-fold):
+ * columns [0, n_split) behave as mt3_op_gemm_ex with small = 1, columns [n_split, n_split + n_side) are the plain f32
+ * product of the same rows with the weight rows that follow -- no row scale, no activation -- in d_side [M][n_side].
+ *   MT3_EPI_GEGLU: norm 2 (d_A compute type + d_a_ss), d_out [M][n_split / 2]; d_side is STORED.  d_Wt holds
+ *                  n_split + 64 * ceil(n_side / 64) rows (whole tiles; what the padding rows hold is never stored).
+ *   MT3_EPI_RESID: no norm, f32 d_out [M][n_split] += product (d_out_ct / d_out_ss as for mt3_op_gemm_ex); d_side is
+ *                  ACCUMULATED into: side = side + product.  n_side a multiple of 32.
+ * n_split a multiple of 64.  concurrent != 0 with f32 operands and M >= 256 selects the 64 x 32 x 128 tile of large
+ * row groups that run side by side (same bits). */
+int mt3_op_gemm_side(int32_t dtype, const void* d_A, const void* d_Wt, void* d_out, int32_t M, int32_t n_split,
+                     int32_t n_side, int32_t K, int32_t epilogue, const float* d_a_ss, void* d_out_ct, float* d_out_ss,
+                     float* d_side, int32_t concurrent, void* stream);
 /* x f32 [rows][dim] -> compute-type copy [rows][dim] + per-16-column sums of squares [rows][dim/16] */
 int mt3_op_residual_split(int32_t dtype, const float* d_x, void* d_x_ct, float* d_x_ss, int32_t rows, int32_t dim,
                           void* stream);

@@ -112,6 +112,8 @@ SIGNATURES = {
                               C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_gemm_ex": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mt3_op_gemm_side": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                   _P, C.c_int32, _P]),
     "mt3_op_residual_split": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_encoder_attention": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mt3_op_decode_attention": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,

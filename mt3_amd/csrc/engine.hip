@@ -80,10 +80,11 @@ struct LayerDev {
   // q-fold (bf16 decode): the cross-attention q-projection rides in the two neighbouring launches
   void* wqkv_ext = nullptr;  // decoder [3HD + HD][emb]: wqkv rows, then the cross query rows (pre_cross norm scale folded)
   void* wo_ext = nullptr;    // decoder [emb + HD][HD]: self out-projection rows, then (Wo . (s2 * Wq_x))^T
-  // qkv-fold (round 3): the NEXT layer's q | k | v | cross-q projections ride in this layer's MLP out-projection launch
-  void* w_fold = nullptr;    // decoder [emb + 4HD][mlp + emb]: rows < emb = [Wo_mlp^T | 0]; rows >= emb =
-                             // [(Wo_mlp . Wext)^T | Wext^T] with Wext = the next layer's scaled [q | k | v | cross-q]
-  void* wi = nullptr;        // [2*mlp][emb] interleaved gate/linear
+  // qkv-fold (round 3): the NEXT layer's q | k | v | cross-q projections ride in this layer's GEGLU and MLP
+  // out-projection launches.  Wext = the next layer's scaled [q | k | v | cross-q] (last layer: the scaled logits matrix)
+  void* w_fold = nullptr;    // decoder [emb + nx][mlp]: rows < emb = Wo_mlp^T; rows >= emb = (Wo_mlp . Wext)^T
+  void* wi = nullptr;        // [2*mlp][emb] interleaved gate/linear; qkv-fold decoder layers: + Wext^T [nx][emb], zero
+                             // rows up to a multiple of 64
   void* wo_mlp = nullptr;    // [emb][mlp]
   void* self_k = nullptr;    // decoder [Bm][H][L][64]
   void* self_v = nullptr;
@@ -214,18 +215,15 @@ struct mt3_engine {
   float* qf = nullptr;           // [max_batch][HD] f32, unnormalised cross-attention query
   bool q_fold = false;
   // qkv-fold: y_in(l+1) . W = y2(l) . W + h(l) . (Wo_mlp . W) by the same linearity, W = the next layer's
-  // [q | k | v | cross-q]: a two-source K = mlp + emb product that rides as 4HD extra output columns in layer l's MLP
-  // out-projection launch (kEpiResidS); layer 0's row comes from two table rows (embedding . W, position table . W)
-  // written by the kernel that creates the decoder input row.  The self-attention kernel applies 1/rms and rounds
-  // q / k / v itself.  8 more launches per step gone.
+  // [q | k | v | cross-q].  The first term needs only the row the GEGLU launch reads anyway: it is that launch's side
+  // product (4HD extra output columns, kEpiGegluP, stored to qkvf); the second rides as 4HD extra output columns in
+  // layer l's MLP out-projection launch and is added to it (kEpiResidQ).  Layer 0's row comes from two table rows
+  // (embedding . W, position table . W) written by the kernel that creates the decoder input row.  The self-attention
+  // kernel applies 1/rms and rounds q / k / v itself.  8 more launches per step gone.
   bool qkv_fold = false;
   float* qkvf = nullptr;         // [max_batch][4HD] f32 unnormalised q | k | v | cross-q of the current layer's input row
   float* ew0 = nullptr;          // [vocab][4HD] f32: embedding . Wext(layer 0)
   float* pw0 = nullptr;          // [kMaxPos][4HD] f32: position table . Wext(layer 0)
-  // the two-source launch reads the compute-type residual rows as an operand while its RESID tiles replace them: the
-  // rows alternate between two buffers from layer to layer (bf16: the bf16 copy; f32: the f32 rows themselves)
-  void* y_ct_alt = nullptr;
-  float* y_alt = nullptr;
   void* qkv_d = nullptr;
   void* attn_d = nullptr;
   void* q_d = nullptr;
@@ -507,10 +505,11 @@ int build_q_fold(mt3_engine* e, const std::string& P, const float* s1, const flo
 mt3k::GemmArgs gemm_args(const void* A, const void* Wt, void* out, int M, int N, int K, int ldo);
 const float* scale_of(mt3_engine* e, const std::string& name);
 
-// qkv-fold matrices and tables (see mt3_engine::qkv_fold).  The matrix products (Wo_mlp . Wext per layer: 0.8 GFLOP;
+// qkv-fold matrices and tables (see mt3_engine::qkv_fold); wi_host[l] = layer l's GEGLU matrix as build_mlp laid it
+// out, which leaves here with the layer's Wext^T rows appended.  The matrix products (Wo_mlp . Wext per layer: 0.8 GFLOP;
 // embedding / position table . Wext of layer 0) run on the device with the engine's own f32 GEMM (exact f32 products,
 // f32 accumulation: ~1e-6 of an entry, far below what the operand formats keep) instead of seconds of host loops.
-int build_qkv_fold(mt3_engine* e) {
+int build_qkv_fold(mt3_engine* e, const std::vector<std::vector<float>>& wi_host) {
   const mt3_engine_config& c = e->cfg;
   const int emb = c.emb_dim, hd = e->HD(), mlp = c.mlp_dim, n4 = 4 * hd, nl = c.num_decoder_layers;
   // Wext^T of layer l: output-major [4HD][emb] = scaled q | k | v of the self-attention, scaled cross-attention query
@@ -570,16 +569,23 @@ int build_qkv_fold(mt3_engine* e) {
     prod.resize(static_cast<size_t>(nx) * mlp);
     he = hipMemcpy(prod.data(), d_prod, prod.size() * 4, hipMemcpyDeviceToHost);
     if (he != hipSuccess) break;
-    const size_t K = static_cast<size_t>(mlp) + emb;
-    w.assign((static_cast<size_t>(emb) + nx) * K, 0.f);
+    // MLP out-projection launch: [Wo_mlp^T ; (Wo_mlp . Wext)^T], K = mlp
+    w.assign((static_cast<size_t>(emb) + nx) * mlp, 0.f);
     for (int k = 0; k < mlp; ++k)
-      for (int n = 0; n < emb; ++n) w[static_cast<size_t>(n) * K + k] = wo->data[static_cast<size_t>(k) * emb + n];
-    for (int n = 0; n < nx; ++n) {
-      float* row = w.data() + (static_cast<size_t>(emb) + n) * K;
-      std::memcpy(row, prod.data() + static_cast<size_t>(n) * mlp, static_cast<size_t>(mlp) * 4);
-      std::memcpy(row + mlp, wt.data() + static_cast<size_t>(n) * emb, static_cast<size_t>(emb) * 4);
-    }
+      for (int n = 0; n < emb; ++n) w[static_cast<size_t>(n) * mlp + k] = wo->data[static_cast<size_t>(k) * emb + n];
+    std::memcpy(w.data() + static_cast<size_t>(emb) * mlp, prod.data(), static_cast<size_t>(nx) * mlp * 4);
     rc = upload_ct(e, w, &e->dec[l].w_fold);
+    if (rc != MT3_OK) break;
+    // GEGLU launch: [wi_0 | wi_1 interleaved ; Wext^T ; zero rows up to whole 64-column tiles], K = emb
+    const size_t n_wi = static_cast<size_t>(2) * mlp * emb, nx64 = (static_cast<size_t>(nx) + 63) / 64 * 64;
+    if (wi_host[l].size() != n_wi) {
+      rc = mt3::fail(MT3_ERR_INVALID, "qkv-fold: GEGLU matrix of the layer missing");
+      break;
+    }
+    w.assign(n_wi + nx64 * emb, 0.f);
+    std::memcpy(w.data(), wi_host[l].data(), n_wi * 4);
+    std::memcpy(w.data() + n_wi, wt.data(), static_cast<size_t>(nx) * emb * 4);
+    rc = upload_ct(e, w, &e->dec[l].wi);
   }
   // layer 0: its input row is Embed(tok) + FixedEmbed[t], so its projection is the sum of two table rows
   if (he == hipSuccess && rc == MT3_OK) rc = wext_t(0, &wt);
@@ -602,7 +608,9 @@ int build_qkv_fold(mt3_engine* e) {
   return MT3_OK;
 }
 
-int build_mlp(mt3_engine* e, const std::string& prefix, const float* scale, LayerDev* L, bool encoder = false) {
+// keep_wi != nullptr: the GEGLU matrix is not uploaded but handed back (build_qkv_fold uploads it with more rows)
+int build_mlp(mt3_engine* e, const std::string& prefix, const float* scale, LayerDev* L, bool encoder = false,
+              std::vector<float>* keep_wi = nullptr) {
   const int emb = e->cfg.emb_dim, mlp = e->cfg.mlp_dim;
   const HostWeight *w0 = find(e, prefix + "/wi_0/kernel", emb, mlp), *w1 = find(e, prefix + "/wi_1/kernel", emb, mlp),
                    *wo = find(e, prefix + "/wo/kernel", mlp, emb);
@@ -620,6 +628,11 @@ int build_mlp(mt3_engine* e, const std::string& prefix, const float* scale, Laye
   std::vector<float> ot(static_cast<size_t>(emb) * mlp);
   put_transposed(ot, mlp, 0, *wo, nullptr);
   int rc;
+  if (keep_wi) {
+    if ((rc = upload_ct(e, ot, &L->wo_mlp))) return rc;
+    keep_wi->swap(t);
+    return MT3_OK;
+  }
   if ((rc = upload_ct(e, t, &L->wi))) return rc;
   if (encoder) {
     if ((rc = upload_planes(e, t, L->wi_p))) return rc;
@@ -704,26 +717,13 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   // cache and id base pointers stay those of the whole batch
   const bool retire = (skip & kVarRetire) != 0;
   const size_t crow0 = retire ? 0 : static_cast<size_t>(row0);
-  // Which of the two residual buffers is current (qkv-fold only: the two-source launch at the end of layer l reads the
-  // rows it replaces, so the rows move to the other buffer there): layer l works on buffer l & 1; the logits and the
-  // arg-max read the last layer's, the arg-max writes the next step's input row into buffer 0.
-  const int layer = op < 8 * nl ? (op >> 3) : nl - 1;
-  const int cur = fold ? (layer & 1) : 0;
   const bool f32 = dt == MT3_F32;
-  auto y_buf = [&](int which) -> float* {            // f32 residual rows
-    return ((fold && f32 && which) ? e->y_alt : e->y) + static_cast<size_t>(row0) * emb;
-  };
-  auto yct_buf = [&](int which) -> char* {           // compute-type rows the norm-fused GEMMs read (f32: the rows themselves)
-    if (!split) return nullptr;
-    if (f32) return reinterpret_cast<char*>(y_buf(which));
-    return static_cast<char*>((fold && which) ? e->y_ct_alt : e->y_ct) + static_cast<size_t>(row0) * emb * es;
-  };
   // the decoder input row of this step (Embed(tok) + FixedEmbed[t]) is already in `y`: written by the
   // embed launch before the first step and by the previous step's argmax kernel afterwards
-  float* y = y_buf(cur);
+  float* y = e->y + static_cast<size_t>(row0) * emb;
   // residual rows as the norm-fused GEMMs see them: f32 with in-kernel statistics, or (split form) the
-  // compute-type rows with the producer's partial sums
-  char* y_ct = yct_buf(cur);
+  // compute-type rows with the producer's partial sums (f32: the rows themselves)
+  char* y_ct = !split ? nullptr : f32 ? reinterpret_cast<char*>(y) : static_cast<char*>(e->y_ct) + static_cast<size_t>(row0) * emb * es;
   char* y_copy = split && !f32 ? y_ct : nullptr;     // where producers of a residual row leave its bf16 copy
   float* y_ss = split ? e->y_ss + static_cast<size_t>(row0) * (emb / 16) : nullptr;
   auto normed = [&](const void* Wt, void* out, int N, int ldo) {
@@ -763,8 +763,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     b.table = e->embedding;
     b.pos_table = e->pos_table;
     b.max_pos = kMaxPos;
-    b.y_next = y_buf(0);
-    b.y_ct = split && !f32 ? yct_buf(0) : nullptr;
+    b.y_next = y;
+    b.y_ct = y_copy;
     b.y_ss = y_ss;
     b.dim = emb;
     const mt3k::RowProj rp{e->ew0, e->pw0, qkvf, 4 * hd};
@@ -798,7 +798,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
                               streaming ? e->stream_max_len : 0};
     return mt3k::launch_argmax_step(logits, c.vocab_size, e->ids + crow0 * Lmax, Lmax,
                                     e->cur_tok + row0, e->done + row0, e->n_done + done_slot, step, e->embedding, e->pos_table,
-                                    kMaxPos, y_buf(0), split && !f32 ? yct_buf(0) : nullptr, y_ss, emb, rows,
+                                    kMaxPos, y, y_copy, y_ss, emb, rows,
                                     (skip & kVarBeam) ? &beam : nullptr,
                                     (skip & kVarForced) ? e->forced + static_cast<size_t>(row0) * Lmax : nullptr, Lmax, rp, ls,
                                     rt, s);
@@ -888,28 +888,34 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     case 6: {
       mt3k::GemmArgs g = normed(L.wi, h_d, 2 * c.mlp_dim, c.mlp_dim);
       g.concurrent = beside;
+      if (fold) {
+        // what consumes the row this layer is about to finish, unnormalised -- the NEXT layer's q | k | v | cross-q (4HD
+        // columns of qkvf), after the last layer the logits -- is y2 . Wext + h . (Wo_mlp . Wext).  The first term needs
+        // only the row this launch reads: it is computed here, in extra column tiles, on CUs the GEGLU tiles of this
+        // row group leave idle (this layer's qkvf is dead: q | k | v went into op 1, the cross query into op 4; the
+        // previous step's logits into its arg-max), and op 7 adds the second term.
+        const bool last = (op >> 3) + 1 == nl;
+        const int nx = last ? c.vocab_size : 4 * hd;
+        g.N = 2 * c.mlp_dim + (nx + 63) / 64 * 64;
+        g.out2 = last ? logits : qkvf;
+        g.ld2 = nx;
+        g.n_split = 2 * c.mlp_dim;
+        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiGegluP, small, s);
+      }
       return mt3k::launch_gemm(dt, g, !split, nrm, MT3_EPI_GEGLU, small, s);
     }
     default:
       if (fold) {
-        // MLP out-projection + residual, and -- as extra output columns with a two-source K = mlp + emb -- what consumes
-        // the updated row next, unnormalised: the NEXT layer's q | k | v | cross-q (4HD columns into qkvf), or after
-        // the last layer the logits (vocab columns).  The residual rows move to the other buffer (see `cur`).
+        // MLP out-projection + residual, and -- as extra output columns over the same K = mlp -- h . (Wo_mlp . Wext),
+        // added to the part of the next consumer's row that op 6 left in qkvf / logits
         const bool last = (op >> 3) + 1 == nl;
         const int nx = last ? c.vocab_size : 4 * hd;
-        mt3k::GemmArgs g = gemm_args(h_d, L.w_fold, y_buf(cur ^ 1), rows, emb + nx, c.mlp_dim + emb, emb);
-        g.lda = c.mlp_dim;
-        g.resid_src = y;
-        g.out_ct = f32 ? nullptr : yct_buf(cur ^ 1);
-        g.out_ss = y_ss;
+        mt3k::GemmArgs g = resid(h_d, L.w_fold, c.mlp_dim);
+        g.N = emb + nx;
         g.out2 = last ? logits : qkvf;
         g.ld2 = nx;
         g.n_split = emb;
-        g.A2 = y_ct;
-        g.lda2 = emb;
-        g.k_split = c.mlp_dim;
-        g.concurrent = beside;
-        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidS, small, s);
+        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, small, s);
       }
       return mt3k::launch_gemm(dt, resid(h_d, L.wo_mlp, c.mlp_dim), false, 0, MT3_EPI_RESID, small, s);
   }
@@ -1129,6 +1135,10 @@ int mt3_engine_finalize(mt3_engine* e) {
   const bool q_fold = emb % 64 == 0 && (emb <= 512 || (emb == 768 && c.compute_dtype == MT3_BF16)) && !single_stream &&
                       !(c.options & MT3_OPT_SEPARATE_PROJECTIONS);
   e->q_fold = q_fold;
+  // qkv-fold (the fold launch's 32-column tiles need whole tiles of logits columns)
+  e->qkv_fold = q_fold && !(c.options & MT3_OPT_SEPARATE_QKV_PROJECTION) && emb % 512 == 0 && c.mlp_dim % 512 == 0 &&
+                c.vocab_size % 32 == 0;
+  std::vector<std::vector<float>> dec_wi(e->qkv_fold ? c.num_decoder_layers : 0);
   for (int l = 0; l < c.num_decoder_layers; ++l) {
     const std::string P = "decoder/layers_" + std::to_string(l);
     const float* s1 = scale_of(e, P + "/pre_self_attention_layer_norm/scale");
@@ -1138,7 +1148,7 @@ int mt3_engine_finalize(mt3_engine* e) {
     if ((rc = build_attention(e, P + "/self_attention", s1, false, &e->dec[l]))) return rc;
     if ((rc = build_attention(e, P + "/encoder_decoder_attention", s2, true, &e->dec[l]))) return rc;
     if (q_fold && (rc = build_q_fold(e, P, s1, s2, &e->dec[l]))) return rc;
-    if ((rc = build_mlp(e, P + "/mlp", s3, &e->dec[l]))) return rc;
+    if ((rc = build_mlp(e, P + "/mlp", s3, &e->dec[l], false, e->qkv_fold ? &dec_wi[l] : nullptr))) return rc;
     const size_t kvb = static_cast<size_t>(Bm) * c.num_heads * L * 64 * e->kv_esize;
     if ((rc = dmalloc(e, &e->dec[l].self_k, kvb))) return rc;
     if ((rc = dmalloc(e, &e->dec[l].self_v, kvb))) return rc;
@@ -1181,8 +1191,8 @@ int mt3_engine_finalize(mt3_engine* e) {
     if ((rc = upload_f32(e, pe, &e->pos_table))) return rc;
   }
   // ---- qkv-fold (needs the embedding and the position table on the device, and the raw weights still on the host)
-  e->qkv_fold = q_fold && !(c.options & MT3_OPT_SEPARATE_QKV_PROJECTION) && emb % 512 == 0 && c.mlp_dim % 512 == 0;
-  if (e->qkv_fold && (rc = build_qkv_fold(e))) return rc;
+  if (e->qkv_fold && (rc = build_qkv_fold(e, dec_wi))) return rc;
+  dec_wi.clear();
   // ---- workspaces
   const size_t M = static_cast<size_t>(Bm) * T;
   if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->x), M * emb * 4))) return rc;
@@ -1223,14 +1233,7 @@ int mt3_engine_finalize(mt3_engine* e) {
   if (e->q_fold && !e->y_split) e->q_fold = false;
   if (!e->q_fold) e->qkv_fold = false;
   if (e->q_fold && (rc = dmalloc(e, reinterpret_cast<void**>(&e->qf), static_cast<size_t>(Bm) * hd * 4))) return rc;
-  if (e->qkv_fold) {
-    if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->qkvf), static_cast<size_t>(Bm) * 4 * hd * 4))) return rc;
-    if (c.compute_dtype == MT3_BF16) {
-      if ((rc = dmalloc(e, &e->y_ct_alt, static_cast<size_t>(Bm) * emb * 2))) return rc;
-    } else if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->y_alt), static_cast<size_t>(Bm) * emb * 4))) {
-      return rc;
-    }
-  }
+  if (e->qkv_fold && (rc = dmalloc(e, reinterpret_cast<void**>(&e->qkvf), static_cast<size_t>(Bm) * 4 * hd * 4))) return rc;
   if ((rc = dmalloc(e, &e->qkv_d, static_cast<size_t>(Bm) * 3 * hd * e->esize))) return rc;
   if ((rc = dmalloc(e, &e->attn_d, static_cast<size_t>(Bm) * hd * e->esize))) return rc;
   if ((rc = dmalloc(e, &e->q_d, static_cast<size_t>(Bm) * hd * e->esize))) return rc;

@@ -117,23 +117,15 @@ __device__ __forceinline__ void tile_chunk(int tid, int p, int* row, int* chunk)
 template <typename CT, bool A_F32, bool NORM, int A_PASSES, int B_PASSES, int CPR, int NT>
 __device__ __forceinline__ void gemm_load_tiles(u32x4 (&a_reg)[A_PASSES], u32x4 (&b_reg)[B_PASSES],
                                                 float (&ss)[A_PASSES], const void* gA, const void* gW, int m0,
-                                                int n0, int tid, int gM, int gLda, int gK, int k0,
-                                                const void* gA2 = nullptr, int gLda2 = 0, int k1 = 0) {
+                                                int n0, int tid, int gM, int gLda, int gK, int k0) {
   constexpr int KPL = CTraits<CT>::KPL;
-  // two-source rows (kEpiResidS): weight columns [k1, K) multiply the rows of A2 (slice-uniform)
-  int ka = k0;
-  if (gA2 != nullptr && k0 >= k1) {
-    gA = gA2;
-    gLda = gLda2;
-    ka = k0 - k1;
-  }
 #pragma unroll
   for (int p = 0; p < A_PASSES; ++p) {
     int ld_row, ld_chunk;
     tile_chunk<CPR, NT>(tid, p, &ld_row, &ld_chunk);
     int row = m0 + ld_row;
     row = row < gM ? row : gM - 1;                       // clamp: out-of-range rows are never stored
-    const size_t e = static_cast<size_t>(row) * gLda + ka + ld_chunk * KPL;
+    const size_t e = static_cast<size_t>(row) * gLda + k0 + ld_chunk * KPL;
     if constexpr (A_F32) {
       const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(gA) + e);
       if constexpr (KPL == 8) {
@@ -176,7 +168,6 @@ struct EpiCtx {
   float* out_ss;
   float* out2;              // *Q epilogues: f32 [M][ld2] for tile columns >= n_split
   int n_split, ld2;
-  const float* resid_src;   // RESID: old values of the f32 output region (== out unless the update is out of place)
 };
 
 // acc[i][j]: the wave's (wm, wn) sub-tile as FM x FN 16x16 C fragments of the workgroup tile at (m0, n0);
@@ -188,8 +179,8 @@ template <typename CT, int EPI_, int FM, int FN, bool PRE, typename RowRs>
 __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[FM][FN], int wm, int wn, int lane, int m0, int n0,
                                               const EpiCtx& c, RowRs row_rs, const float (&pre)[FM][FN][4]) {
   const int frag_row = lane & 15, frag_g = lane >> 4;
-  if constexpr (EPI_ == kEpiStoreQ || EPI_ == kEpiResidQ || EPI_ == kEpiResidS) {
-    if (n0 >= c.n_split) {       // (tile-uniform) the second product: plain f32, no row scale
+  if constexpr (EPI_ == kEpiStoreQ || EPI_ == kEpiResidQ || EPI_ == kEpiGegluP) {
+    if (n0 >= c.n_split) {       // (tile-uniform) the second product: plain f32, no row scale, no activation
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -198,15 +189,18 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[FM][FN], int wm
           if (row >= c.M) continue;
 #pragma unroll
           for (int j = 0; j < FN; ++j) {
-            float* o = c.out2 + static_cast<size_t>(row) * c.ld2 + (n0 - c.n_split) + wn * FN * 16 + j * 16 + frag_row;
+            const int col2 = (n0 - c.n_split) + wn * FN * 16 + j * 16 + frag_row;
+            float* o = c.out2 + static_cast<size_t>(row) * c.ld2 + col2;
             if constexpr (EPI_ == kEpiResidQ) *o = (PRE ? pre[i][j][r] : *o) + acc[i][j][r];
-            else *o = acc[i][j][r];
+            else if constexpr (EPI_ == kEpiGegluP) {       // the weight rows are padded to whole tiles, the output is not
+              if (col2 < c.ld2) *o = acc[i][j][r];
+            } else *o = acc[i][j][r];
           }
         }
       return;
     }
   }
-  constexpr int EPI = EPI_ == kEpiStoreQ ? MT3_EPI_STORE : (EPI_ == kEpiResidQ || EPI_ == kEpiResidS) ? MT3_EPI_RESID : EPI_;
+  constexpr int EPI = EPI_ == kEpiStoreQ ? MT3_EPI_STORE : EPI_ == kEpiResidQ ? MT3_EPI_RESID : EPI_ == kEpiGegluP ? MT3_EPI_GEGLU : EPI_;
   // ---- epilogue: C fragment (i, j): rows (lane>>4)*4 + r, col lane & 15
   // 2-byte outputs are never stored one element at a time (a sub-dword store costs a read-modify-write in the
   // cache: the bf16 STORE epilogue of a decode GEMM took 2.5 us against 0.7 us for the f32 RESID one): lanes l
@@ -268,7 +262,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[FM][FN], int wm
         for (int r = 0; r < 4; ++r) {
           const int row = m0 + lrow0 + r;
           const size_t at = static_cast<size_t>(row < c.M ? row : c.M - 1) * c.ldo + col;
-          vnew[r] = (PRE ? pre[i][j][r] : c.resid_src[at]) + acc[i][j][r];
+          vnew[r] = (PRE ? pre[i][j][r] : static_cast<const float*>(c.out)[at]) + acc[i][j][r];
           if (row < c.M) static_cast<float*>(c.out)[at] = vnew[r];
         }
         if (c.out_ss) {
@@ -365,7 +359,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
                 "fused norm: CPR a power of two, <= one wave, dividing NT");
   static_assert(BK % KG == 0, "BK must be a multiple of the MFMA K-group");
   static_assert(!NORM || A_F32, "NORM needs the f32 A operand");
-  static_assert(EPI != MT3_EPI_GEGLU || (FN % 2 == 0), "GEGLU pairs fragments");
+  static_assert((EPI != MT3_EPI_GEGLU && EPI != kEpiGegluP) || (FN % 2 == 0), "GEGLU pairs fragments");
 
   __shared__ __attribute__((aligned(16))) CT As[BM * ROWE];
   __shared__ __attribute__((aligned(16))) CT Bs[BN * ROWE];
@@ -382,7 +376,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
 #if !(MT3_EXP & 64)
   asm volatile("" ::"s"(g.A), "s"(g.Wt), "s"(g.out), "s"(g.aux), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.lda), "s"(g.ldo),
                "s"(g.seq_len), "s"(g.a_ss), "s"(g.out_ct), "s"(g.out_ss), "s"(g.out2), "s"(g.n_split), "s"(g.ld2),
-               "s"(g.A2), "s"(g.lda2), "s"(g.k_split), "s"(g.resid_src), "s"(g.n_major), "s"(gridDim.x));
+               "s"(g.n_major), "s"(gridDim.x));
 #endif
   // scalars out of the by-value argument struct (never take its address: that forces a private copy)
   const void* const gA = g.A;
@@ -430,18 +424,14 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
     for (int u = 0; u < NPV; ++u) pv[u] = p4[u < npv ? u : npv - 1];
   }
   // decode-sized RESID tiles (bf16): this lane's elements of the residual rows, requested before anything else
-  constexpr bool kPre = (EPI == MT3_EPI_RESID || EPI == kEpiResidQ || EPI == kEpiResidS) && FM * FN <= 2;
-  constexpr bool kSplitEpi = EPI == kEpiStoreQ || EPI == kEpiResidQ || EPI == kEpiResidS;
+  constexpr bool kPre = (EPI == MT3_EPI_RESID || EPI == kEpiResidQ) && FM * FN <= 2;
+  constexpr bool kSplitEpi = EPI == kEpiStoreQ || EPI == kEpiResidQ || EPI == kEpiGegluP;
   const int ld2 = kSplitEpi ? (g.ld2 ? g.ld2 : gN - g.n_split) : 0;
   const bool second = kSplitEpi && n0 >= g.n_split;        // (tile-uniform) this tile belongs to the second product
-  // kEpiResidS: second-product tiles run over the whole two-source K, the RESID tiles over its first k_split columns
-  const int kend = EPI == kEpiResidS ? (second ? gK : g.k_split) : gK;
-  const void* const gA2 = EPI == kEpiResidS && second ? g.A2 : nullptr;
-  const int gLda2 = g.lda2, k1 = g.k_split;
+  const int kend = gK;
   float xpre[FM][FN][4];
-  const float* const gResidSrc = g.resid_src ? g.resid_src : static_cast<const float*>(gO);
-  if constexpr (kPre) if (!(EPI == kEpiResidS && second)) {
-    const float* src = gResidSrc;
+  if constexpr (kPre) {
+    const float* src = static_cast<const float*>(gO);
     int ld = gLdo, c0 = n0;
     if constexpr (EPI == kEpiResidQ) {
       if (second) {                      // the second product's f32 region
@@ -475,8 +465,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
   const CT* a_base = &As[(wm * FM * 16 + frag_row) * ROWE + frag_g * KPL];
   const CT* b_base = &Bs[(wn * FN * 16 + frag_row) * ROWE + frag_g * KPL];
 
-  gemm_load_tiles<CT, A_F32, NORM, A_PASSES, B_PASSES, CPR, NT>(a_reg, b_reg, ss, gA, gW, m0, n0, tid, gM, gLda, gK, 0,
-                                                                gA2, gLda2, k1);
+  gemm_load_tiles<CT, A_F32, NORM, A_PASSES, B_PASSES, CPR, NT>(a_reg, b_reg, ss, gA, gW, m0, n0, tid, gM, gLda, gK, 0);
   if constexpr (!NORM) {
     if (scale_rows) {
       float t = 0.f;
@@ -508,7 +497,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
     MT3_PROF_MARK(2);
     if (k0 + BK < kend)                 // the next slice in flight while the MFMAs below run
       gemm_load_tiles<CT, A_F32, NORM, A_PASSES, B_PASSES, CPR, NT>(a_reg, b_reg, ss, gA, gW, m0, n0, tid, gM, gLda, gK,
-                                                                    k0 + BK, gA2, gLda2, k1);
+                                                                    k0 + BK);
 #pragma unroll
     for (int kk = 0; kk < BK / KG; ++kk) {
       u32x4 af[FM], bf[FN];
@@ -550,7 +539,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
     return rsqrtf(t / static_cast<float>(gK) + 1e-6f);
   };
   MT3_PROF_MARK(5);
-  const EpiCtx ec{gO, gAux, gM, kSplitEpi ? g.n_split : gN, gLdo, gSeq, gOutCt, gOutSs, g.out2, g.n_split, ld2, gResidSrc};
+  const EpiCtx ec{gO, gAux, gM, kSplitEpi ? g.n_split : gN, gLdo, gSeq, gOutCt, gOutSs, g.out2, g.n_split, ld2};
   gemm_epilogue<CT, EPI, FM, FN, kPre>(acc, wm, wn, lane, m0, n0, ec, row_rs, xpre);
   MT3_PROF_MARK(4);
 }
@@ -793,7 +782,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(GemmArgs g, const __bf1
     if constexpr (!NORM) return 1.f;
     return rsqrtf(ss_part[lrow] / static_cast<float>(gK) + 1e-6f);
   };
-  const EpiCtx ec{g.out, g.aux, gM, gN, g.ldo, g.seq_len, nullptr, nullptr, nullptr, 0, 0, static_cast<const float*>(g.out)};
+  const EpiCtx ec{g.out, g.aux, gM, gN, g.ldo, g.seq_len, nullptr, nullptr, nullptr, 0, 0};
   const float nopre[FM][FN][4] = {};
   gemm_epilogue<float, EPI, FM, FN, false>(acc, wm, wn, lane, m0, n0, ec, row_rs, nopre);
 }
@@ -1121,6 +1110,8 @@ template <typename CT, int BM, int BN, int BK, int WM, int WN, bool A_F32, bool 
 static int launch_cfg(const GemmArgs& g, hipStream_t s) {
   if (g.N % BN != 0 || g.K % BK != 0) return mt3::fail(MT3_ERR_INVALID, "gemm: N/K not a multiple of the tile");
   if (g.a_ss && g.K > 64 * NPV) return mt3::fail(MT3_ERR_INVALID, "gemm: K too large for this tile's partial-sum registers");
+  // (the kernel reads the row's K/16 partial sums as K/64 float4: with none it would index p4[-1])
+  if (g.a_ss && (g.K < 64 || g.K % 64)) return mt3::fail(MT3_ERR_INVALID, "gemm: a_ss needs K = 64n >= 64");
   const int grid = ((g.M + BM - 1) / BM) * (g.N / BN);
   hipLaunchKernelGGL((gemm_kernel<CT, BM, BN, BK, WM, WN, A_F32, NORM, EPI, NPV>), dim3(grid), dim3(WM * WN * 64), 0, s, g);
   MT3_HIP_CHECK(hipGetLastError());
@@ -1134,6 +1125,12 @@ static int launch_cfg(const GemmArgs& g, hipStream_t s) {
 //         >= 100 workgroups on the chip, and the K step is as deep as LDS allows (16 K-groups = 512 bf16
 //         elements: K = 512 in ONE slice) so that every global load of the block is in flight at once
 //         instead of 8-16 dependent load->barrier->MFMA rounds.
+//   second products (kEpiStoreQ / kEpiResidQ / kEpiGegluP): column tiles past GemmArgs::n_split belong to another
+//         product of the same rows (plain f32 into out2; ResidQ adds to what is there).  They take the SAME tile as the
+//         launch's own columns, so every workgroup of a launch runs the same K slices.  The qkv-fold uses two of them per
+//         layer: the GEGLU launch carries y2 . Wext (K = emb, its A operand anyway), the MLP out-projection launch adds
+//         h . (Wo_mlp . Wext) (K = mlp).  Both tile shapes below (32-row and, for large concurrent groups, 64 x 32 x 128)
+//         treat them alike; the base.gin shape (q-fold without qkv-fold) never launches kEpiGegluP.
 // decode-sized tile BMxBN with K slice BK
 template <typename CT, int BM, int BN, int BK, bool A_F32, bool NORM, int EPI, int NPV = 8>
 static int launch_small(const GemmArgs& g, hipStream_t s) {
@@ -1143,10 +1140,15 @@ static int launch_small(const GemmArgs& g, hipStream_t s) {
 template <typename CT, bool A_F32, bool NORM, int EPI>
 static int launch_tile(const GemmArgs& g, bool small, hipStream_t s) {
   constexpr int KG = CTraits<CT>::KGROUP;
+  // GEGLU column tiles pair fragments inside a wave; kEpiGegluP's side-product tiles (columns past n_split: plain f32
+  // products of the same rows, stored unscaled to out2) ride on the same tile shape, so a launch has ONE kind of
+  // workgroup: same operand bytes, same K slices, same duration whichever class a tile belongs to
+  constexpr bool kGeglu = EPI == MT3_EPI_GEGLU || EPI == kEpiGegluP;
   if (small) {
     const bool deep = g.K % (16 * KG) == 0;
-    // (measured and removed, DESIGN.md section 3: the two-source fold launch on 32 x 64 tiles -- 25 % fewer operand
-    // bytes through a CU's L1 but one workgroup per CU, slower; eight-wave split-K f32 tiles, slower)
+    // (measured and removed, DESIGN.md section 3: the fold launch as ONE two-source product over K = mlp + emb, six
+    // slices -- since round 7 its K = emb part is the GEGLU launch's side product; the fold launch on 32 x 64 tiles -- 25 %
+    // fewer operand bytes through a CU's L1 but one workgroup per CU, slower; eight-wave split-K f32 tiles, slower)
     if constexpr (!NORM && !A_F32 && KG == 32 && EPI != MT3_EPI_HEADS && EPI != MT3_EPI_POS) {
       // ismir2022/base.gin shape (emb = heads * 64 = 768): K = 768 as ONE slice too, with room for its 48 partial
       // sums of squares when the rows arrive as the bf16 residual copy (norm 2)
@@ -1154,7 +1156,7 @@ static int launch_tile(const GemmArgs& g, bool small, hipStream_t s) {
         // (the one-slice tiles hold 100 / 150 KB of LDS = ONE workgroup per CU: a launch with more workgroups than CUs
         // -- QKV N = 3072: 768, GEGLU N = 4096: 512 -- would run in rounds; those take K in two slices of 384 instead,
         // 51 / 75 KB, three / two workgroups per CU, one round)
-        if constexpr (EPI == MT3_EPI_GEGLU) {
+        if constexpr (kGeglu) {
           if (((g.M + 31) / 32) * (g.N / 64) > 256)
             return launch_cfg<CT, 32, 64, 12 * KG, 2, 2, A_F32, NORM, EPI, 16>(g, s);
           return launch_cfg<CT, 32, 64, 24 * KG, 2, 2, A_F32, NORM, EPI, 16>(g, s);
@@ -1166,7 +1168,7 @@ static int launch_tile(const GemmArgs& g, bool small, hipStream_t s) {
       }
     }
     if constexpr (KG == 16 && !NORM && !A_F32 &&
-                  (EPI == kEpiResidS || EPI == MT3_EPI_GEGLU || EPI == kEpiResidQ || EPI == MT3_EPI_RESID)) {
+                  (kGeglu || EPI == kEpiResidQ || EPI == MT3_EPI_RESID)) {
       // f32 operands, the four dense launches of a decoder layer for a LARGE row group (>= 256 rows per group: engines of
       // 1024+ slots) that runs BESIDE other groups (GemmArgs::concurrent): 64 x 32 tiles with K slices of 128 -- half the
       // workgroups of the 32-row tiles, a 64-row block fetches each weight byte once, and 51 KB of LDS let three
@@ -1180,7 +1182,7 @@ static int launch_tile(const GemmArgs& g, bool small, hipStream_t s) {
       // bytes through the L1s decide, alone the latency of a workgroup does)
       if (g.concurrent && g.M >= 256 && g.K % (8 * KG) == 0) return launch_cfg<CT, 64, 32, 8 * KG, 4, 1, A_F32, NORM, EPI>(g, s);
     }
-    if constexpr (EPI == MT3_EPI_GEGLU) {
+    if constexpr (kGeglu) {
       if (deep) return launch_small<CT, 32, 64, 16 * KG, A_F32, NORM, EPI>(g, s);
       return launch_cfg<CT, 32, 64, 4 * KG, 2, 2, A_F32, NORM, EPI>(g, s);
     } else {
@@ -1222,6 +1224,9 @@ static int launch_typed(const GemmArgs& g, bool a_f32, int norm, int epi, bool s
       case kEpiStoreQ:
         if (small) return launch_tile<CT, false, false, kEpiStoreQ>(g, small, s);
         break;
+      case kEpiGegluP:
+        if (small) return launch_tile<CT, false, false, kEpiGegluP>(g, small, s);
+        break;
       default: break;
     }
     return mt3::fail(MT3_ERR_INVALID, "gemm: unsupported epilogue for norm 2");
@@ -1248,9 +1253,6 @@ static int launch_typed(const GemmArgs& g, bool a_f32, int norm, int epi, bool s
       case kEpiResidQ:
         if (small) return launch_tile<CT, false, false, kEpiResidQ>(g, small, s);
         break;
-      case kEpiResidS:
-        if (small) return launch_tile<CT, false, false, kEpiResidS>(g, small, s);
-        break;
       case MT3_EPI_HEADS: return launch_tile<CT, false, false, MT3_EPI_HEADS>(g, small, s);
       case MT3_EPI_STORE: return launch_tile<CT, false, false, MT3_EPI_STORE>(g, small, s);
       case MT3_EPI_F32: return launch_tile<CT, false, false, MT3_EPI_F32>(g, small, s);
@@ -1264,11 +1266,12 @@ int launch_gemm(int dtype, const GemmArgs& g, bool a_f32, int norm, int epi, boo
   if (g.M <= 0 || g.N <= 0 || g.K <= 0 || !g.A || !g.Wt || !g.out)
     return mt3::fail(MT3_ERR_INVALID, "gemm: bad shape or null pointer");
   if (epi == MT3_EPI_POS && (!g.aux || g.seq_len <= 0)) return mt3::fail(MT3_ERR_INVALID, "gemm: POS needs aux/seq_len");
-  if ((epi == kEpiStoreQ || epi == kEpiResidQ || epi == kEpiResidS) &&
+  if ((epi == kEpiStoreQ || epi == kEpiResidQ || epi == kEpiGegluP) &&
       (!g.out2 || g.n_split <= 0 || g.n_split >= g.N || g.n_split % 64))
     return mt3::fail(MT3_ERR_INVALID, "gemm: split epilogue needs out2 and 0 < n_split < N, n_split a multiple of 64");
-  if (epi == kEpiResidS && (!g.A2 || g.k_split <= 0 || g.k_split >= g.K || g.k_split % 512 || (g.K - g.k_split) % 512))
-    return mt3::fail(MT3_ERR_INVALID, "gemm: the two-source epilogue needs A2 and slice-aligned 0 < k_split < K");
+  // kEpiGegluP: Wt holds N rows (whole tiles), out2 rows hold ld2 <= N - n_split columns (the rest is never written)
+  if (epi == kEpiGegluP && (g.ld2 < 0 || g.ld2 > g.N - g.n_split || (g.N - g.n_split) % 64))
+    return mt3::fail(MT3_ERR_INVALID, "gemm: the GEGLU side product needs N - n_split = 64n >= ld2");
   if (epi == MT3_EPI_HEADS && (g.seq_len <= 0 || g.M % g.seq_len != 0 || g.N % 128 != 0))
     return mt3::fail(MT3_ERR_INVALID, "gemm: HEADS needs M = B*T and N = 2*H*64");
   if (dtype == MT3_BF16 && !small && glds_eligible(g, a_f32, norm, epi)) {
@@ -1333,6 +1336,37 @@ extern "C" int mt3_op_gemm(int32_t dtype, const void* d_A, int32_t a_is_f32, int
   g.ldo = epilogue == MT3_EPI_GEGLU ? N / 2 : N;
   g.seq_len = seq_len;
   return mt3k::launch_gemm(dtype, g, a_is_f32 != 0, norm != 0 ? 1 : 0, epilogue, small != 0, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mt3_op_gemm_side(int32_t dtype, const void* d_A, const void* d_Wt, void* d_out, int32_t M, int32_t n_split,
+                                int32_t n_side, int32_t K, int32_t epilogue, const float* d_a_ss, void* d_out_ct,
+                                float* d_out_ss, float* d_side, int32_t concurrent, void* stream) {
+  if (epilogue != MT3_EPI_GEGLU && epilogue != MT3_EPI_RESID)
+    return mt3::fail(MT3_ERR_INVALID, "gemm_side: epilogue must be MT3_EPI_GEGLU or MT3_EPI_RESID");
+  if (n_side <= 0) return mt3::fail(MT3_ERR_INVALID, "gemm_side: n_side must be positive");
+  const bool geglu = epilogue == MT3_EPI_GEGLU;
+  if (geglu ? (d_a_ss == nullptr || d_out_ct != nullptr || d_out_ss != nullptr)
+            : (d_a_ss != nullptr || (dtype == MT3_BF16 ? (d_out_ct != nullptr) != (d_out_ss != nullptr) : d_out_ct != nullptr)))
+    return mt3::fail(MT3_ERR_INVALID, "gemm_side: GEGLU takes a_ss and no out_ct / out_ss; RESID takes no a_ss (bf16: out_ct "
+                                      "and out_ss together, f32: out_ss alone)");
+  mt3k::GemmArgs g{};
+  g.A = d_A;
+  g.Wt = d_Wt;
+  g.out = d_out;
+  g.M = M;
+  g.N = n_split + (geglu ? (n_side + 63) / 64 * 64 : n_side);
+  g.K = K;
+  g.lda = K;
+  g.ldo = geglu ? n_split / 2 : n_split;
+  g.a_ss = d_a_ss;
+  g.out_ct = d_out_ct;
+  g.out_ss = d_out_ss;
+  g.out2 = d_side;
+  g.n_split = n_split;
+  g.ld2 = n_side;
+  g.concurrent = concurrent != 0;
+  return mt3k::launch_gemm(dtype, g, false, geglu ? 2 : 0, geglu ? mt3k::kEpiGegluP : mt3k::kEpiResidQ, true,
+                           static_cast<hipStream_t>(stream));
 }
 
 #if MT3_EXP & 32

@@ -23,21 +23,13 @@ struct GemmArgs {
   const float* a_ss;  // norm == 2: [M][K/16] partial sums of squares of the rows whose compute-type copy is A
   void* out_ct;       // EPI_RESID: also write the updated rows in the compute type here [M][ldo] (nullptr: no)
   float* out_ss;      // EPI_RESID with out_ct: [M][N/16] partial sums of squares of the updated rows
-  // kEpiStoreQ / kEpiResidQ: output columns [n_split, N) are a SECOND product riding in the same launch -- they go to
-  // out2 (f32 [M][N - n_split], unscaled; ResidQ accumulates into it), columns [0, n_split) take the STORE / RESID path
+  // kEpiStoreQ / kEpiResidQ / kEpiGegluP: output columns [n_split, N) are a SECOND product riding in the same launch --
+  // they go to out2 (f32, unscaled, no activation; ResidQ accumulates into it), columns [0, n_split) take the STORE /
+  // RESID / GEGLU path.  kEpiGegluP: Wt's N rows are padded to whole 64-column tiles, out2 rows are ld2 columns wide
+  // and only those are written
   float* out2;
   int n_split;
   int ld2;            // row stride of out2 in floats (0: N - n_split)
-  // kEpiResidS: the tiles past n_split multiply a TWO-SOURCE row [A (K = k_split columns) | A2 (K - k_split columns)]
-  // with their K-wide weight rows and STORE the product to out2; the tiles before n_split are a plain RESID over
-  // the first k_split columns of their weight rows (the rest of those rows is never read)
-  const void* A2;     // [M, lda2] compute type
-  int lda2;
-  int k_split;
-  // RESID family: where the OLD value of the f32 output region is read from (nullptr: `out` itself, the update in
-  // place).  The two-source launch of the f32 engine reads the rows it updates as an operand of its other tiles, so
-  // there the update goes out of place
-  const float* resid_src;
   // tile -> XCD dealing: 0 = an XCD owns a run of row blocks (all weight columns pass through its L2), 1 = an XCD
   // owns a run of weight-column tiles for ALL row blocks (its L2 sees 1/8 of the weights; set by launch_gemm)
   int n_major;
@@ -45,8 +37,9 @@ struct GemmArgs {
   // a row block of >= 256 rows takes the 64 x 32 tiles (gemm.hip: launch_tile); alone on the chip the 32-row tiles win
   int concurrent;
 };
-// internal epilogues (not part of the C ABI): STORE / RESID with a second f32 output region, see GemmArgs::out2
-constexpr int kEpiStoreQ = 6, kEpiResidQ = 7, kEpiResidS = 8;
+// internal epilogues (not part of the C ABI): STORE / RESID / GEGLU with a second f32 output region, see GemmArgs::out2
+// (8 was the two-source fold launch of rounds 3-6)
+constexpr int kEpiStoreQ = 6, kEpiResidQ = 7, kEpiGegluP = 9;
 
 // norm: 0 none, 1 fused RMSNorm with statistics from the f32 A stream, 2 fused RMSNorm from g.a_ss (A = compute type)
 int launch_gemm(int dtype, const GemmArgs& g, bool a_f32, int norm, int epi, bool small, hipStream_t s);
