@@ -377,6 +377,33 @@ typedef struct mt3_transcribe_stats {
 int mt3_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_steps, int32_t flags,
                           int32_t* d_ids, mt3_transcribe_stats* h_stats, void* stream);
 
+/* In-flight batching of the k-beam search: mt3_engine_transcribe with the token rule of mt3_engine_decode_beams
+ * (num_beams = k, 1 <= k <= 8).  An engine of max_batch rows gives E = min(n_segments, max_batch / k) ELEMENTS of k slots
+ * each; an element whose search has closed -- retired by the rule above, or out of positions after num_steps steps --
+ * hands its k decodes to the caller and restarts at position 0 on the next segment, while the other elements go on.
+ * d_inputs [n_segments, T, input_depth] f32: every segment ONCE (the engine puts a segment's cross-attention K/V into the
+ * k cache rows of the element that takes it; every segment, the first E included, comes through the staging ring of
+ * encoder passes that run ahead on the caller's stream).  d_ids [n_segments, L] int32: the best decode of each segment.
+ * d_all_ids [n_segments, k, L] int32 or NULL and d_scores [n_segments, k] f32 or NULL: all k decodes and their scores in
+ * INCREASING order of score, exactly as mt3_engine_decode_beams returns them.
+ * Contract: segment i's rows of d_ids, d_all_ids and d_scores are BIT-IDENTICAL to what mt3_engine_encode (the segment k
+ * times in a row) + mt3_engine_decode_beams(..., MT3_DECODE_EARLY_EXIT) return for it, under the encoder-reproducibility
+ * condition mt3_engine_encode documents (f32: always; bf16: every encoder pass of 8 or more segments -- the staging
+ * passes are padded to 8 as in mt3_engine_transcribe).  At k = 1 the ids equal mt3_engine_transcribe(MT3_DECODE_BEAM1).
+ * Schedule: the row groups of mt3_engine_transcribe on E * k slots, every group boundary on an element boundary; one
+ * captured step graph per group for the whole job; beam groups are never compacted -- a closed element costs no
+ * attention, and once the queue of segments is empty a group ends when its last element has closed.
+ * flags: MT3_DECODE_NO_GRAPH, MT3_DECODE_SINGLE_STREAM.  MT3_ERR_INVALID, before any device work: any other flag bit,
+ * num_beams outside 1 .. 8 or above max_batch, a vocabulary outside [2k, 2048], more than 16 decoder layers, NULL d_inputs
+ * or d_ids, n_segments < 1, num_steps outside 1 .. L, a decode in flight, or a synthetic EOS schedule being set
+ * (mt3_hip_debug.h: that hook drives the greedy / beam-1 token kernel only).
+ * h_stats (may be NULL; written only when the call succeeds) as for mt3_engine_transcribe, in slots: slots = E * k,
+ * refills = (n_segments - E) * k, encoder_chunks = all encoder passes, compactions = 0.  MT3_STATUS_LAST_DECODE_FORKS
+ * reports the cache-row copies of the whole job.  The call BLOCKS until every segment is done. */
+int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_beams,
+                                int32_t num_steps, int32_t flags, int32_t* d_ids, int32_t* d_all_ids /* NULL ok */,
+                                float* d_scores /* NULL ok */, mt3_transcribe_stats* h_stats, void* stream);
+
 /* Teacher-forced cached decode: Transformer.decode (mt3/network.py:303-361) on GIVEN decoder inputs, driven one
  * token per call through the same cached step (layers.py:246-314) the autoregressive loop uses -- the input of
  * step 0 is BOS, the input of step t+1 is d_forced_ids[b][t] (i.e. decoder_input_tokens = shift_right(forced),
@@ -437,7 +464,7 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_LAST_DECODE_GROUPS = 7 /* row groups of the most recent decode (2 or 4: the row-group schedule); 1: on the caller's stream */,
        MT3_STATUS_PARTITION_FALLBACKS = 8 /* decodes that wanted the row-group schedule but could not set it up */,
        MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */,
-       MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams */,
+       MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams / mt3_engine_transcribe_beams */,
        MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 

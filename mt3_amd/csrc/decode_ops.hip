@@ -480,20 +480,21 @@ int launch_compact(const CompactArgs& c, hipStream_t s) {
 //          into the cache rows of slot plan[i]  (16-byte pieces, 256 lanes, a row of H*T*64 elements in `parts` pieces)
 //   slot   block i: id row of slot plan[i] -> the caller's row of the segment it decoded (beam-1: the finished
 //          hypothesis, as beam1_finalize_kernel would leave it); i < n_new: restart on segment first_seg + i
+// (unit > 1: the plan is over ELEMENTS of `unit` slots each -- beam groups, keyed on the element's first slot)
 __global__ __launch_bounds__(64) void refill_plan_kernel(const int* __restrict__ done, int* __restrict__ plan,
-                                                          int* __restrict__ n_done, int rows, int n_new) {
+                                                          int* __restrict__ n_done, int rows, int n_new, int unit) {
   const int lane = threadIdx.x;
   int n = 0;
   for (int base = 0; base < rows; base += 64) {
     const int i = base + lane;
-    const bool fin = i < rows && done[i] != 0;
+    const bool fin = i < rows && done[i * unit] != 0;
     const unsigned long long m = __ballot(fin);
     if (fin) plan[n + __popcll(m & ((1ull << lane) - 1ull))] = i;
     n += __popcll(m);
   }
   if (lane == 0) {
     plan[rows] = n;
-    *n_done -= n_new < n ? n_new : n;
+    *n_done -= (n_new < n ? n_new : n) * unit;
   }
 }
 
@@ -573,7 +574,7 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
   if (a.n_new > 0 && (a.n_layers <= 0 || a.n_layers > kRefillMaxLayers || a.row_bytes % 16 || a.sc_bytes % 16 ||
                       a.src_batch <= 0 || a.dst_batch <= 0 || a.src_entry0 < 0 || a.src_entry0 + a.n_new > a.src_batch))
     return mt3::fail(MT3_ERR_INVALID, "refill: bad staging chunk");
-  hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, a.done, a.plan, a.n_done, a.rows, a.n_new);
+  hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, a.done, a.plan, a.n_done, a.rows, a.n_new, 1);
   if (a.n_new > 0) {
     // a K or V row of one layer is H*T*64 elements (98 KB ... 393 KB): 8 blocks of 256 lanes per row keep >= 1000
     // workgroups in flight for a handful of segments
@@ -783,6 +784,8 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
       int* par_out = a.hist_par + static_cast<size_t>(t) * a.hist_stride + s0;
       int* tok_out = a.hist_tok + static_cast<size_t>(t) * a.hist_stride + s0;
       const bool retired = kth_step >= 0 && kth > nl_score[0] / bp_max;
+      // in-flight batching: an element that has run max_len steps is closed as well (the row ran out of positions)
+      const bool closed = retired || (a.max_len > 0 && t + 1 >= a.max_len);
       for (int j = 0; j < k; ++j) {
         const int p = nl_par[j];
         int nrow, src = -1;
@@ -801,10 +804,10 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
         a.live[s0 + j] = nl_score[j];
         a.cur_tok[s0 + j] = s_tok[j];
         a.step[s0 + j] = t + 1;
-        if (retired) a.done[s0 + j] = 1;
+        if (closed) a.done[s0 + j] = 1;
       }
-      if (forks && !retired) atomicAdd(a.fork_count, forks);   // a retired element's forks are never copied
-      if (retired) atomicAdd(a.n_done, k);
+      if (forks && !closed) atomicAdd(a.fork_count, forks);    // a closed element's forks are never copied
+      if (closed) atomicAdd(a.n_done, k);
     }
   }
   __syncthreads();
@@ -933,6 +936,166 @@ int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int
   if (!ids || a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || L <= 0 || num_steps <= 0 || num_steps > L)
     return mt3::fail(MT3_ERR_INVALID, "beam_finalize: bad arguments");
   hipLaunchKernelGGL(beam_finalize_kernel, dim3(a.elems, a.k), dim3(256), 0, s, a, L, num_steps, ids, all_ids, scores);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
+// ------------------------------------------------------------------------------- refill of beam elements
+// (BeamRefillArgs, kernels.h)
+__global__ __launch_bounds__(256) void beam_refill_cross_kernel(BeamRefillArgs a, int parts) {
+  const int i = blockIdx.x, k = a.b.k;
+  const int n_fin = a.plan[a.b.elems];
+  if (i >= a.n_new || i >= n_fin) return;
+  const int s0 = a.plan[i] * k;
+  const int l = blockIdx.y / 3, what = blockIdx.y % 3;          // 0: K rows, 1: V rows, 2: scale rows (e4m3 caches)
+  const char* src;
+  char* dst;
+  size_t bytes;
+  if (what < 2) {
+    bytes = a.row_bytes;
+    src = a.src[l] + (static_cast<size_t>(what) * a.src_batch + a.src_entry0 + i) * bytes;
+    dst = a.dst[l] + static_cast<size_t>(what) * a.dst_batch * bytes;
+  } else {
+    if (!a.src_sc[l]) return;
+    bytes = a.sc_bytes;
+    src = a.src_sc[l] + static_cast<size_t>(a.src_entry0 + i) * bytes;
+    dst = a.dst_sc[l];
+  }
+  u32x4* d4[kBeamMaxK];
+#pragma unroll
+  for (int j = 0; j < kBeamMaxK; ++j)       // (entries past k repeat beam 0's row and are never stored to)
+    d4[j] = reinterpret_cast<u32x4*>(dst + static_cast<size_t>(a.b.slot_row[s0 + (j < k ? j : 0)]) * bytes);
+  const size_t n16 = bytes >> 4;
+  const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+  for (size_t x = static_cast<size_t>(blockIdx.z) * 256 + threadIdx.x; x < n16; x += static_cast<size_t>(parts) * 256) {
+    const u32x4 v = __builtin_nontemporal_load(s4 + x);
+#pragma unroll
+    for (int j = 0; j < kBeamMaxK; ++j)
+      if (j < k) d4[j][x] = v;
+  }
+}
+
+// dynamic LDS: the element's history columns [n_hist][k] (token | parent << 11: vocab <= 2048, k <= 8), then the k
+// decodes [k][L], both as 16-bit values
+__global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a) {
+  extern __shared__ unsigned short s_mem[];
+  const int i = blockIdx.x, tid = threadIdx.x, k = a.b.k, L = a.L;
+  if (i >= a.plan[a.b.elems]) return;
+  const int s0 = a.plan[i] * k;
+  const int seg_old = a.slot_seg[s0];
+  if (seg_old >= 0) {
+    unsigned short* s_hist = s_mem;
+    unsigned short* s_out = s_mem + static_cast<size_t>(a.num_steps) * k;
+    const int ran = a.b.step[s0];
+    const int n_hist = ran < a.num_steps ? ran : a.num_steps;   // steps the element ran (its history rows)
+    for (int x = tid; x < n_hist * k; x += 256) {
+      const int u = x / k, j = x - u * k;
+      const size_t h = static_cast<size_t>(u) * a.b.hist_stride + s0 + j;
+      s_hist[x] = static_cast<unsigned short>(a.b.hist_tok[h] | (a.b.hist_par[h] << 11));
+    }
+    for (int x = tid; x < k * L; x += 256) s_out[x] = 0;
+    __syncthreads();
+    float score = 0.f;
+    if (tid < k) {
+      // decode tid of the result = state entry k - 1 - tid (beam_finalize_kernel)
+      const int e = k - 1 - tid;
+      unsigned short* out = s_out + static_cast<size_t>(tid) * L;
+      int u, j;
+      if (a.b.fin_step[s0] >= 0) {
+        score = a.b.fin_score[s0 + e];
+        u = a.b.fin_step[s0 + e];
+        j = a.b.fin_beam[s0 + e];
+        if (u >= 0 && u < L) out[u] = 1;
+        --u;                                              // u = -2 for an unfilled entry: nothing to walk
+      } else {
+        score = a.b.live[s0 + e];                         // nothing finished: the live beams at the last step
+        u = n_hist - 1;
+        j = e;
+      }
+      if (u >= n_hist) u = n_hist - 1;
+      for (; u >= 0; --u) {
+        const unsigned short hv = s_hist[u * k + j];
+        out[u] = hv & 0x7ff;
+        j = hv >> 11;
+      }
+    }
+    __syncthreads();
+    int* o_best = a.out_ids + static_cast<size_t>(seg_old) * L;
+    int* o_all = a.out_all ? a.out_all + static_cast<size_t>(seg_old) * k * L : nullptr;
+    for (int x = tid; x < k * L; x += 256) {
+      const int v = s_out[x];
+      if (o_all) o_all[x] = v;
+      if (x >= (k - 1) * L) o_best[x - (k - 1) * L] = v;
+    }
+    if (tid < k && a.out_scores) a.out_scores[static_cast<size_t>(seg_old) * k + tid] = score;
+  }
+  const bool restart = i < a.n_new;
+  if (tid < k) {
+    const int slot = s0 + tid;
+    a.slot_seg[slot] = restart ? a.first_seg + i : -1;
+    if (restart) {
+      a.b.live[slot] = tid == 0 ? 0.f : kBeamNegInf;
+      a.b.fin_score[slot] = kBeamNegInf;
+      a.b.fin_step[slot] = -1;
+      a.b.fin_beam[slot] = -1;
+      a.b.fork_src[slot] = -1;
+      a.b.step[slot] = 0;
+      a.b.cur_tok[slot] = 0;                               // BOS
+      a.b.done[slot] = 0;
+    }
+  }
+  if (!restart) return;
+  // decoder input of position 0 for all k slots: Embed(BOS) + FixedEmbed[0], in the forms the step reads (embed_kernel)
+  for (int c = tid * 4; c < a.b.dim; c += 1024) {
+    const float4 e4 = *reinterpret_cast<const float4*>(a.b.table + c), p4 = *reinterpret_cast<const float4*>(a.b.pos_table + c);
+    const float4 v = make_float4(e4.x + p4.x, e4.y + p4.y, e4.z + p4.z, e4.w + p4.w);
+    for (int j = 0; j < k; ++j) put_row_piece(v, a.b.y_next, a.b.y_ct, a.b.y_ss, s0 + j, a.b.dim, c);
+  }
+  if (a.rp.q_out)
+    for (int j = 0; j < k; ++j) put_row_projection(a.rp, s0 + j, 0, 0, tid, 256);
+}
+
+int launch_beam_refill(const BeamRefillArgs& a, hipStream_t s) {
+  const BeamKArgs& b = a.b;
+  if (b.k < 1 || b.k > kBeamMaxK || b.elems <= 0 || b.vocab > 2048 || !b.live || !b.fin_score || !b.fin_step || !b.fin_beam ||
+      !b.hist_par || !b.hist_tok || !b.slot_row || !b.fork_src || !b.done || !b.n_done || !b.step || !b.cur_tok ||
+      !b.table || !b.pos_table || !b.y_next || b.dim % 16 || (b.y_ct && !b.y_ss) || !a.slot_seg || !a.plan || !a.out_ids ||
+      a.L <= 0 || a.num_steps <= 0 || a.num_steps > a.L || a.n_new < 0 || a.n_new > b.elems ||
+      (a.rp.q_out && (!a.rp.ew || !a.rp.pw || a.rp.q_n % 4)))
+    return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad arguments");
+  if (a.n_new > 0 && (a.n_layers <= 0 || a.n_layers > kRefillMaxLayers || a.row_bytes % 16 || a.sc_bytes % 16 ||
+                      a.src_batch <= 0 || a.dst_batch <= 0 || a.src_entry0 < 0 || a.src_entry0 + a.n_new > a.src_batch))
+    return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad staging chunk");
+  const size_t lds = (static_cast<size_t>(a.num_steps) + a.L) * b.k * sizeof(unsigned short);
+  if (lds > 65536) return mt3::fail(MT3_ERR_INVALID, "beam_refill: history and decodes of an element exceed 64 KB of LDS");
+  hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, b.done, a.plan, b.n_done, b.elems, a.n_new, b.k);
+  if (a.n_new > 0) {
+    // as refill_cross_kernel, with twice the parts: a block stores every piece it loads k times
+    const int parts = 16;
+    hipLaunchKernelGGL(beam_refill_cross_kernel, dim3(a.n_new, a.n_layers * 3, parts), dim3(256), 0, s, a, parts);
+  }
+  hipLaunchKernelGGL(beam_refill_elem_kernel, dim3(b.elems), dim3(256), lds, s, a);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
+__global__ void beam_stream_init_kernel(int* done, int* slot_seg, int* fork_src, int* slot_row, int* n_done, int slots,
+                                        int groups, GroupSlots gs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < groups) n_done[i] = gs.n[i];
+  if (i >= slots) return;
+  done[i] = 1;
+  slot_seg[i] = -1;
+  fork_src[i] = -1;
+  slot_row[i] = i;
+}
+
+int launch_beam_stream_init(int* done, int* slot_seg, int* fork_src, int* slot_row, int* n_done, int slots, int groups,
+                            const GroupSlots& group_slots, hipStream_t s) {
+  if (!done || !slot_seg || !fork_src || !slot_row || !n_done || slots <= 0 || groups < 1 || groups > 4)
+    return mt3::fail(MT3_ERR_INVALID, "beam_stream_init: bad arguments");
+  hipLaunchKernelGGL(beam_stream_init_kernel, dim3((slots + 255) / 256), dim3(256), 0, s, done, slot_seg, fork_src,
+                     slot_row, n_done, slots, groups, group_slots);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }

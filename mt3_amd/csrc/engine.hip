@@ -767,6 +767,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     b.y_ct = y_copy;
     b.y_ss = y_ss;
     b.dim = emb;
+    b.max_len = (skip & kVarStream) ? e->stream_max_len : 0;
     const mt3k::RowProj rp{e->ew0, e->pw0, qkvf, 4 * hd};
     const mt3k::LogitScale ls{fold ? y_ss : nullptr, emb / 16, emb};
     MT3_TRY(mt3k::launch_beam_step(b, rp, ls, s));
@@ -2157,9 +2158,69 @@ static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRan
   return mt3k::launch_refill(a, r.s);
 }
 
+// where the decodes of mt3_engine_transcribe_beams go (the caller's buffers, rows by segment)
+struct BeamOut {
+  int k;
+  int32_t* all_ids;
+  float* scores;
+};
+
+// the beam counterpart of refill_group: finished ELEMENTS of row group `r` hand their k decodes over and restart on the
+// run `rg` of staged segments (rg == nullptr: hand-over only)
+static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* rg, int32_t* d_out, const BeamOut& bo) {
+  const mt3_engine_config& c = e->cfg;
+  const size_t r0 = static_cast<size_t>(r.row0);
+  const int emb = c.emb_dim, n4 = 4 * e->HD();
+  mt3k::BeamRefillArgs a{};
+  a.b = beam_args(e, r.row0, r.rows, bo.k);
+  a.b.n_done = e->n_done + r.slot;
+  a.b.table = e->embedding;
+  a.b.pos_table = e->pos_table;
+  a.b.max_pos = kMaxPos;
+  a.b.y_next = e->y + r0 * emb;
+  if (e->y_split && c.compute_dtype == MT3_BF16) a.b.y_ct = static_cast<char*>(e->y_ct) + r0 * emb * 2;
+  if (e->y_split) a.b.y_ss = e->y_ss + r0 * (emb / 16);
+  a.b.dim = emb;
+  a.rp = mt3k::RowProj{e->ew0, e->pw0, e->qkv_fold ? e->qkvf + r0 * n4 : nullptr, n4};
+  a.slot_seg = e->slot_seg + r0;
+  a.plan = e->refill_plan + r0 + r.slot;
+  a.L = c.max_decode_len;
+  a.num_steps = r.num_steps;
+  a.out_ids = d_out;
+  a.out_all = bo.all_ids;
+  a.out_scores = bo.scores;
+  if (rg) {
+    a.n_new = rg->n;
+    a.first_seg = rg->first_seg;
+    a.n_layers = c.num_decoder_layers;
+    a.row_bytes = static_cast<size_t>(c.num_heads) * c.input_length * 64 * e->kv_esize;
+    a.sc_bytes = static_cast<size_t>(c.num_heads) * c.input_length * sizeof(float2);
+    const size_t chunk = static_cast<size_t>(rg->seq % kStageChunks);
+    for (int l = 0; l < c.num_decoder_layers; ++l) {
+      a.src[l] = static_cast<const char*>(e->stage_kv[l]) + chunk * 2 * e->stage_cap * a.row_bytes;
+      a.dst[l] = static_cast<char*>(e->dec[l].cross_kv);
+      if (e->kv_fp8) {
+        a.src_sc[l] = reinterpret_cast<const char*>(e->stage_scale[l]) + chunk * e->stage_cap * a.sc_bytes;
+        a.dst_sc[l] = reinterpret_cast<char*>(e->dec[l].cross_scale);
+      }
+    }
+    a.src_batch = rg->batch;
+    a.src_entry0 = rg->entry0;
+    a.dst_batch = r.batch;
+  }
+  return mt3k::launch_beam_refill(a, r.s);
+}
+
 // One row group's loop of mt3_engine_transcribe: as run_group, but a finished slot restarts on the next staged segment
 // at the poll, and the loop ends when the queue is empty for good and every slot of the group has finished.
-static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out, int kPoll) {
+// bo != nullptr (mt3_engine_transcribe_beams): the unit of refill is an ELEMENT of bo->k slots -- the snapshot, the
+// watchdog and `refillable` count slots, the feed counts segments = elements -- the group starts with every element
+// finished and takes its first segments off the feed before its first step, and it is never compacted.
+static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out, int kPoll, const BeamOut* bo = nullptr) {
+  const int unit = bo ? bo->k : 1;
+  auto refill = [&](int cur_rows, const FeedRange* rg) {
+    return bo ? refill_beam_group(e, r, rg, d_out, *bo) : refill_group(e, r, cur_rows, rg, d_out);
+  };
   int cur = r.rows;
   hipGraphExec_t exec = nullptr;
   int exec_rows = -1, flushed_at = -1;
@@ -2183,6 +2244,26 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
   const long stall_limit = static_cast<long>(r.num_steps) + 4L * kPoll + 64;
   long last_progress = 0;
   int seen_fin = 0;
+  if (bo) {
+    // every element is finished and empty: the first refill comes before the first step interval
+    int n_fin = r.rows;
+    bool dry = false;
+    while (!dry && n_fin == r.rows) {
+      feed_wait(f);                              // (sleeps until the first encoder pass is on offer)
+      if (mt3feed::feed_failed(f)) return MT3_OK;
+      const int nr = feed_pop(f, n_fin / unit, got.data(), static_cast<int>(got.size()), &dry);
+      for (int i = 0; i < nr; ++i) {
+        MT3_TRY(refill(cur, &got[i]));
+        held.push_back(got[i]);
+        n_fin -= got[i].n * unit;
+      }
+    }
+    if (n_fin == r.rows) {                       // the other groups took every segment: nothing to decode here
+      r.used_graph = r.use_graph;
+      return MT3_OK;
+    }
+    seen_fin = n_fin;
+  }
   for (long t = 0;; ++t) {
     if (t - last_progress > stall_limit)
       return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: a row group made no progress for num_steps + 4 polls");
@@ -2209,12 +2290,12 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
       bool dry = false;
       for (;;) {
         if (mt3feed::feed_failed(f)) return MT3_OK;           // somebody else reports the error
-        const int refillable = n_fin - (r.rows - cur);
+        const int refillable = (n_fin - (r.rows - cur)) / unit;
         const int nr = feed_pop(f, refillable, got.data(), static_cast<int>(got.size()), &dry);
         for (int i = 0; i < nr; ++i) {
-          MT3_TRY(refill_group(e, r, cur, &got[i], d_out));
+          MT3_TRY(refill(cur, &got[i]));
           held.push_back(got[i]);
-          n_fin -= got[i].n;
+          n_fin -= got[i].n * unit;
           last_progress = t;
         }
         if (dry || n_fin < r.rows) break;
@@ -2225,11 +2306,11 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
         const int live = r.rows - n_fin;
         int want = (live + 31) & ~31;
         if (want > r.rows) want = r.rows;
-        const bool compact = live > 0 && want < cur;
+        const bool compact = !bo && live > 0 && want < cur;    // beam groups stay where they are (run_group)
         // (the hand-over runs on the device's own done flags, directly in front of a compaction or of the exit: no slot
         // that finished after the snapshot can be dropped with its ids still in the engine)
         if ((n_fin - (r.rows - cur) > 0 && n_fin != flushed_at) || compact || live <= 0) {
-          MT3_TRY(refill_group(e, r, cur, nullptr, d_out));
+          MT3_TRY(refill(cur, nullptr));
           flushed_at = n_fin;
         }
         if (live <= 0) break;
@@ -2425,6 +2506,147 @@ int mt3_debug_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_
     return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_transcribe: poll_steps in [0, 1024], row_groups in [0, 4]");
   return transcribe_impl(e, d_inputs, n_segments, num_steps, flags, d_ids, h_stats, stream, poll_steps, row_groups,
                          skip_encoder_passes != 0);
+}
+
+// mt3_engine_transcribe_beams: in-flight batching of the k-beam search.  E = min(n_segments, max_batch / k) elements of k
+// slots each; EVERY segment, the first E included, reaches its element through the staging ring (one code path, and no
+// k-fold copy of the inputs for a direct first encode): the groups start with every element finished and empty, and the
+// feed starts at segment 0.
+int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_beams,
+                                int32_t num_steps, int32_t flags, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
+                                mt3_transcribe_stats* h_stats, void* stream) {
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: null engine");
+  const mt3_engine_config& c = e->cfg;
+  const int k = num_beams;
+  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM");
+  if (k < 1 || k > mt3k::kBeamMaxK) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: num_beams must be 1 .. 8");
+  if (k > c.max_batch) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: num_beams exceeds max_batch");
+  if (c.vocab_size > 2048 || c.vocab_size < 2 * k)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the beam step needs 2 * num_beams <= vocab <= 2048");
+  if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: more than 16 decoder layers");
+  if (!d_inputs || !d_ids || n_segments < 1)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: null buffer or no segments");
+  if (num_steps < 1 || num_steps > c.max_decode_len)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: num_steps out of range");
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: engine not finalized");
+  if (e->pending.active)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+  if (e->eos_on)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the synthetic EOS schedule drives the greedy / beam-1 token kernel only");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MT3_TRY(ensure_beam_state(e));
+  MT3_TRY(ensure_stage(e));
+  const int E = n_segments < c.max_batch / k ? n_segments : c.max_batch / k, slots = E * k;
+  // transcribe_impl's group rule on E * k slots, group boundaries on element boundaries
+  int groups = ((flags & MT3_DECODE_SINGLE_STREAM) || (c.options & MT3_OPT_NO_ROW_GROUPS)) ? 1 : stream_row_groups_for(c, slots);
+  while (groups > 1 && (E / groups) * k < 16) --groups;
+  if (ensure_group_streams(e, groups) != MT3_OK)
+    return mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe_beams: could not create the row groups' streams");
+
+  // ---- every slot finished and empty; valid (BOS) input rows so that the dense launches of empty slots read numbers
+  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(slots) * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(slots) * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->bk_forks, 0, 4, s));
+  {
+    const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
+    MT3_TRY(mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
+                               c.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, slots, c.emb_dim, rp, s));
+  }
+  {
+    mt3k::GroupSlots gs{};
+    for (int g = 0; g < groups; ++g) {
+      int e0, en;
+      chain_rows(E, groups, g, &e0, &en);
+      gs.n[g] = en * k;
+    }
+    MT3_TRY(mt3k::launch_beam_stream_init(e->done, e->slot_seg, e->bk_fork_src, e->slot_row, e->n_done, slots, groups, gs, s));
+  }
+  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // as mt3_engine_decode_beams
+  if (e->group_graphs.size() > 96) drop_group_graphs(e);
+  e->cur_batch = slots;
+  e->stream_max_len = num_steps;
+  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift);
+  const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
+  MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
+
+  Feed feed;
+  feed.n_total = n_segments;
+  PendingDecode& p = e->pending;
+  p = PendingDecode();
+  p.groups = groups;
+  p.active = true;
+  const BeamOut bo{k, d_all_ids, d_scores};
+  bool posted_all = true;
+  for (int g = 0; g < groups && posted_all; ++g) {
+    auto body = [e, g, groups, E, k, slots, variant, num_steps, use_graph, &feed, d_ids, &bo]() {
+      PendingDecode& q = e->pending;
+      GroupRun r{};
+      int e0, en;
+      chain_rows(E, groups, g, &e0, &en);
+      r.row0 = e0 * k;
+      r.rows = en * k;
+      r.batch = slots;
+      r.variant = variant | (groups > 1 ? kVarBeside : 0);
+      r.num_steps = num_steps;
+      r.slot = g;
+      r.early = true;
+      r.use_graph = use_graph;
+      r.s = e->part_stream[g];
+      hipError_t he = hipStreamWaitEvent(r.s, e->part_begin, 0);
+      if (he == hipSuccess) {
+        q.rcs[g] = run_group_stream(e, r, feed, d_ids, kStreamPollSteps, &bo);
+        if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
+        he = wait_stream(e, g, r.s);
+      }
+      if (q.rcs[g] == MT3_OK && he != hipSuccess) {
+        q.rcs[g] = MT3_ERR_HIP;
+        q.errs[g] = hipGetErrorString(he);
+      }
+      q.ran[g] = r.ran;
+      q.used_graph[g] = r.used_graph;
+      if (q.rcs[g] != MT3_OK) feed_fail(feed);
+    };
+    if (worker_post(e, g, body)) p.posted = g + 1;
+    else posted_all = false;
+  }
+  int rc = MT3_OK;
+  if (!posted_all) {
+    feed_fail(feed);
+    rc = mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe_beams: could not start a row group's worker thread");
+  } else {
+    rc = produce_chunks(e, feed, d_inputs, s, false);
+  }
+  const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
+  for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
+  p.active = false;
+  e->compactions = e->compactions_now.exchange(0);
+  e->last_groups = groups;
+  int most = 0;
+  e->last_used_graph = 1;
+  for (int g = 0; g < p.posted; ++g) {
+    if (rc == MT3_OK && p.rcs[g] != MT3_OK)
+      rc = mt3::fail(p.rcs[g], "mt3_engine_transcribe_beams (row group " + std::to_string(g) + "): " + p.errs[g]);
+    most = p.ran[g] > most ? p.ran[g] : most;
+    if (!p.used_graph[g]) e->last_used_graph = 0;
+  }
+  if (rc != MT3_OK) return producer_err.empty() ? rc : mt3::fail(rc, producer_err);
+  // every group thread has waited for its stream: the fork count of the job is final
+  MT3_HIP_CHECK(hipMemcpyAsync(e->h_pinned + kForksPinned, e->bk_forks, 4, hipMemcpyDeviceToHost, s));
+  MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
+  mt3_transcribe_stats st{};
+  st.slots = slots;
+  st.groups = groups;
+  st.steps_run = most;
+  st.polls = feed.polls;
+  st.refills = (feed.refills - E) * k;
+  st.starved_polls = feed.starved;
+  st.encoder_chunks = feed.produced;
+  st.compactions = 0;
+  st.used_graph = e->last_used_graph;
+  if (h_stats) *h_stats = st;
+  return MT3_OK;
 }
 
 int mt3_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t* d_ids,

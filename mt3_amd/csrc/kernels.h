@@ -253,6 +253,10 @@ struct BeamKArgs {
   void* y_ct;
   float* y_ss;
   int dim;
+  // > 0 (mt3_engine_transcribe_beams): an element whose position counter reaches max_len is closed whether or not its
+  // search has -- its k slots are marked done and counted, its live and finished sets stay as the step left them (in
+  // mt3_engine_decode_beams the host loop's bound does that: it passes 0)
+  int max_len;
 };
 int launch_beam_step(const BeamKArgs& a, const RowProj& rp, const LogitScale& ls, hipStream_t s);
 // copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
@@ -273,6 +277,45 @@ int launch_beam_init(float* live, float* fin_score, int* fin_step, int* fin_beam
 // backtracks the result of every element: ids [elems][L] (the best decode), all_ids [elems][k][L] and scores
 // [elems][k] in increasing order of score (either may be nullptr)
 int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int* all_ids, float* scores, hipStream_t s);
+// Refill of finished beam ELEMENTS (in-flight batching of the k-beam search, mt3_engine_transcribe_beams): the beam
+// counterpart of launch_refill, three launches on the group's stream at a poll of the group's loop.
+//   plan   refill_plan_kernel over elements (an element is finished when its first slot is done): plan[i] = i-th finished
+//          element, plan[elems] = how many; the group's counter of finished slots drops by k per restarted element
+//   cross  the cross-attention K/V (and e4m3 scale rows) of segment first_seg + i from the staging chunk into EACH of the k
+//          cache rows slot_row[s0 .. s0 + k) of element plan[i]: every 16-byte piece is loaded once and stored k times
+//   elem   block i: the k decodes of element plan[i] are walked back from the history (beam_finalize_kernel's walk, on a
+//          copy of the element's history columns in LDS) straight into the caller's rows of the segment it held; then,
+//          i < n_new: the element restarts on segment first_seg + i (live = [0, NEG_INF, ...], nothing finished, position 0,
+//          BOS input rows in their three forms and layer 0's projected rows for all k slots); the others keep done = 1 and
+//          get slot_seg = -1 -- they decode nothing until a later refill.
+// b: the group's beam state (pointers of the group's first slot, b.elems = elements of the group); the self-attention
+// caches need nothing: an element's slot_row entries stay a permutation of its own k rows.
+struct BeamRefillArgs {
+  BeamKArgs b;
+  RowProj rp;           // q_out = the group's qkvf rows (nullptr: no qkv-fold)
+  int* slot_seg;        // [slots] segment an element is decoding, in all k of its slots (-1: none)
+  int* plan;            // [elems + 1] scratch
+  int L, num_steps;     // id row length; steps per segment of the job
+  int* out_ids;         // caller's [n_segments][L]
+  int* out_all;         // caller's [n_segments][k][L] or nullptr
+  float* out_scores;    // caller's [n_segments][k] or nullptr
+  int n_new, first_seg;
+  int n_layers;
+  const char* src[kRefillMaxLayers];
+  char* dst[kRefillMaxLayers];
+  const char* src_sc[kRefillMaxLayers];
+  char* dst_sc[kRefillMaxLayers];
+  int src_batch, src_entry0, dst_batch;
+  size_t row_bytes, sc_bytes;
+};
+int launch_beam_refill(const BeamRefillArgs& a, hipStream_t s);
+// start of an mt3_engine_transcribe_beams job: every slot finished and without a segment (the first refill starts the
+// elements), slot i on cache row i, no fork pending; n_done[g] = group_slots[g] for the `groups` row groups
+struct GroupSlots {
+  int n[4];
+};
+int launch_beam_stream_init(int* done, int* slot_seg, int* fork_src, int* slot_row, int* n_done, int slots, int groups,
+                            const GroupSlots& group_slots, hipStream_t s);
 int launch_iota(int* dst, int n, hipStream_t s);
 int launch_set_float(float* dst, float v, hipStream_t s);
 int launch_beam1_finalize(int* ids, int L, const int* beam_len, int B, hipStream_t s);

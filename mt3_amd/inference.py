@@ -56,7 +56,7 @@ class InferenceModel(object):
 
     def __init__(self, checkpoint_path, model_type="mt3", *, config: Optional[network.T5Config] = None,
                  dtype: str = "float32", batch_size: int = 8, early_exit: bool = True,
-                 decoding: str = "beam1", max_slots: int = 256, schedule: str = "refill", num_beams: int = 4):
+                 decoding: str = "beam1", max_slots: int = 256, schedule: Optional[str] = None, num_beams: int = 4):
         """dtype: 'float32' (default) = the reference's own precision (gin/model.gin:50 restores and runs
         float32): f32 MFMA operands, f32 K/V cache, token-exact against the oracle.  'bfloat16' is the explicit
         opt-in fast path (bf16 operands and caches, f32 accumulation / residual / softmax; what bench.py times;
@@ -65,11 +65,14 @@ class InferenceModel(object):
         that many rows: 3.2 GB per 64 slots in f32 at the MT3 shape); the engine starts at `batch_size` slots and is rebuilt
         with more (next power of two) when a job has more segments.  schedule: 'refill' = one mt3_engine_transcribe call
         per job (in-flight batching; needs early_exit); 'batch' = the reference's loop, one batch-synchronous engine call
-        per `batch_size` segments (NB:295-301).
-        decoding: 'beam1' (default) / 'greedy' as above; 'beam' = t5x beam_search with num_decodes = `num_beams` (1 .. 8,
-        Transformer.decode_beams): segments are encoded and beam-decoded in batch-synchronous chunks of
-        max_slots // num_beams segments (each beam is a decode slot), and `schedule='refill'` is ignored (in-flight
-        refill of beam groups is not implemented)."""
+        per `batch_size` segments (NB:295-301).  None (the default) = 'refill' for 'beam1' / 'greedy'; for decoding='beam'
+        it is 'batch' until the comparison of tools/bench_beams.py --refill has been measured in favour of 'refill'
+        (the beam row) -- pass schedule='refill' to run the beam search with in-flight batching.
+        decoding: 'beam1' (default) / 'greedy' as above; 'beam' = t5x beam_search with num_decodes = `num_beams` (1 .. 8):
+        each beam is a decode slot, so a job runs max_slots // num_beams segments at a time.  With schedule='refill' it
+        is one mt3_engine_transcribe_beams call per job (Transformer.transcribe(num_beams=k): a segment whose search has
+        closed hands its slots to the next segment); with schedule='batch' the segments are encoded and beam-decoded in
+        batch-synchronous chunks of max_slots // num_beams (Transformer.decode_beams).  Same tokens either way."""
         if model_type == "ismir2021":
             num_velocity_bins = 127
             self.encoding_spec = note_sequences.NoteEncodingSpec
@@ -82,6 +85,8 @@ class InferenceModel(object):
             raise ValueError("unknown model_type: %s" % model_type)
 
         self.batch_size = batch_size             # the reference's 8 (NB:190): what input_shapes reports
+        if schedule is None:
+            schedule = "batch" if decoding == "beam" else "refill"
         if schedule not in ("refill", "batch"):
             raise ValueError("schedule must be 'refill' or 'batch', got %r" % (schedule,))
         self.schedule = schedule
@@ -195,11 +200,16 @@ class InferenceModel(object):
         return torch.cat(out, 0).cpu().numpy()
 
     def _predict_tokens_beam(self, x):
-        """decoding='beam': batch-synchronous chunks of max_slots // k segments, k engine rows (beams) per segment"""
+        """decoding='beam', k engine rows (beams) per segment: one in-flight batched call (schedule='refill'), or
+        batch-synchronous chunks of max_slots // k segments (schedule='batch')"""
         import torch
         k = self.num_beams
         chunk = max(1, self.max_slots // k)
         self._ensure_slots(min(x.shape[0], chunk) * k)
+        if self.schedule == "refill" and self.early_exit:
+            # ONE engine call for the whole job: a closed element restarts on the job's next segment
+            self.rows_per_engine_call = [int(x.shape[0]) * k]
+            return self.vocabulary.decode_tf(self.model.transcribe(x, num_beams=k)).cpu().numpy()
         chunk = max(1, min(chunk, self.model.max_batch // k))
         out = []
         self.rows_per_engine_call = []

@@ -266,18 +266,46 @@ class Transformer:
 
     def transcribe(self, encoder_input_tokens, num_steps: Optional[int] = None, beam1: bool = False,
                    use_graph: bool = True, single_stream: bool = False, debug_poll_steps: int = 0,
-                   debug_row_groups: int = 0, debug_skip_encoder_passes: bool = False):
+                   debug_row_groups: int = 0, debug_skip_encoder_passes: bool = False,
+                   num_beams: Optional[int] = None, return_all: bool = False):
         """mt3_engine_transcribe: encode + decode of ANY number of segments through the engine's `max_batch` decode slots
         with in-flight batching -- a slot whose segment has finished restarts on the next one (the reference's loop over
         `.batch(8)` calls of predict_batch_with_aux, NB:295-301, without its batch-synchronous wait for the longest row).
         encoder_input_tokens: CUDA f32 [N, T, input_depth].  Returns int32 CUDA [N, L] ids, row i = segment i, bit-identical
-        to encode() + decode(early_exit=True) of that segment; `self.transcribe_stats` says what ran."""
+        to encode() + decode(early_exit=True) of that segment; `self.transcribe_stats` says what ran.
+        num_beams = k (1 .. 8): mt3_engine_transcribe_beams -- the k-beam search of `decode_beams` with in-flight batching
+        of max_batch // k elements of k slots each (each segment is passed once).  Returns the ids [N, L] of the best
+        decode, or with `return_all` all k decodes [N, k, L] and their scores [N, k] in increasing order of score:
+        bit-identical to encode(x, num_beams=k) + decode_beams(k, early_exit=True) of each segment."""
         import torch
         x = encoder_input_tokens
         if x.dim() != 3 or x.shape[1] != self.input_length or x.shape[2] != self.config.input_depth:
             raise ValueError(f"expected [N, {self.input_length}, {self.config.input_depth}], got {tuple(x.shape)}")
         x = x.to(device="cuda", dtype=torch.float32).contiguous()
         N, L = x.shape[0], self.max_decode_length
+        if num_beams is not None:
+            k = int(num_beams)
+            if k < 1 or k > min(_lib.MAX_BEAMS, self.max_batch):
+                raise ValueError(f"num_beams must be 1 .. {min(_lib.MAX_BEAMS, self.max_batch)}, got {num_beams}")
+            if beam1 or debug_poll_steps or debug_row_groups or debug_skip_encoder_passes:
+                raise ValueError("num_beams goes with neither beam1 nor the debug_* schedule parameters")
+            ids = torch.empty((N, L), device="cuda", dtype=torch.int32)
+            all_ids = torch.empty((N, k, L), device="cuda", dtype=torch.int32) if return_all else None
+            scores = torch.empty((N, k), device="cuda", dtype=torch.float32) if return_all else None
+            flags = (0 if use_graph else _lib.DECODE_NO_GRAPH) | (_lib.DECODE_SINGLE_STREAM if single_stream else 0)
+            st = _lib.TranscribeStats()
+            _lib.check(self._lib.mt3_engine_transcribe_beams(
+                self._h, x.data_ptr(), N, k, num_steps or L, flags, ids.data_ptr(),
+                all_ids.data_ptr() if return_all else None, scores.data_ptr() if return_all else None, C.byref(st),
+                torch.cuda.current_stream().cuda_stream))
+            self._batch = int(st.slots)
+            self._encoded_beams = k
+            self.transcribe_stats = {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
+            self.last_transcribe_stats = self.transcribe_stats
+            self.steps_run = st.steps_run
+            return (all_ids, scores) if return_all else ids
+        if return_all:
+            raise ValueError("return_all needs num_beams")
         ids = torch.empty((N, L), device="cuda", dtype=torch.int32)
         flags = (0 if use_graph else _lib.DECODE_NO_GRAPH) | (_lib.DECODE_BEAM1 if beam1 else 0) | \
             (_lib.DECODE_SINGLE_STREAM if single_stream else 0)
@@ -292,6 +320,7 @@ class Transformer:
                                                        C.byref(st), torch.cuda.current_stream().cuda_stream))
         self._batch = min(N, self.max_batch)
         self.transcribe_stats = {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
+        self.last_transcribe_stats = self.transcribe_stats
         self.steps_run = st.steps_run
         return ids
 

@@ -1,11 +1,12 @@
 """Command line: WAV files -> MIDI files (the notebook's upload / transcribe / download cells in one call).
 
     python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
-                                 IN.wav [IN2.wav ...] [-o OUT]
+                                 [--decoding beam1|greedy|beam] [--num-beams K] IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
 engine as one job (`InferenceModel.transcribe_wavs`).  --checkpoint is handed to `InferenceModel` as it is: a t5x
-checkpoint directory, a flat or compact `.npz`, or `random:<seed>`.
+checkpoint directory, a flat or compact `.npz`, or `random:<seed>`.  --decoding beam runs t5x beam_search with
+--num-beams K decodes (1 .. 8) per segment (`InferenceModel(decoding="beam", num_beams=K)`).
 """
 from __future__ import annotations
 
@@ -21,9 +22,14 @@ def plan(argv=None):
     ap.add_argument("--checkpoint", required=True, help="t5x checkpoint directory, .npz, or random:<seed>")
     ap.add_argument("--model", default="mt3", choices=("mt3", "ismir2021"))
     ap.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
+    ap.add_argument("--decoding", default="beam1", choices=("beam1", "greedy", "beam"),
+                    help="token selection: beam1 (default, the reference's), greedy, or beam (k-beam search, see --num-beams)")
+    ap.add_argument("--num-beams", type=int, default=4, metavar="K", help="decodes per segment with --decoding beam (1 .. 8)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
+    if not 1 <= args.num_beams <= 8:
+        ap.error("--num-beams must be 1 .. 8")
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
@@ -45,7 +51,8 @@ def main(argv=None) -> int:
     args, outputs = plan(argv)
     from . import inference, midi_io
     try:
-        model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype)
+        model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype, decoding=args.decoding,
+                                         num_beams=args.num_beams)
         sequences = model.transcribe_wavs(args.inputs)
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
