@@ -508,14 +508,14 @@ __global__ __launch_bounds__(256) void refill_cross_kernel(RefillArgs a, int par
   char* dst;
   size_t bytes;
   if (what < 2) {
-    bytes = a.row_bytes;
-    src = a.src[l] + (static_cast<size_t>(what) * a.src_batch + a.src_entry0 + i) * bytes;
-    dst = a.dst[l] + (static_cast<size_t>(what) * a.dst_batch + row) * bytes;
+    bytes = a.x.row_bytes;
+    src = a.x.src[l] + (static_cast<size_t>(what) * a.x.src_batch + a.x.src_entry0 + i) * bytes;
+    dst = a.x.dst[l] + (static_cast<size_t>(what) * a.x.dst_batch + row) * bytes;
   } else {
-    if (!a.src_sc[l]) return;
-    bytes = a.sc_bytes;
-    src = a.src_sc[l] + static_cast<size_t>(a.src_entry0 + i) * bytes;
-    dst = a.dst_sc[l] + static_cast<size_t>(row) * bytes;
+    if (!a.x.src_sc[l]) return;
+    bytes = a.x.sc_bytes;
+    src = a.x.src_sc[l] + static_cast<size_t>(a.x.src_entry0 + i) * bytes;
+    dst = a.x.dst_sc[l] + static_cast<size_t>(row) * bytes;
   }
   const size_t n16 = bytes >> 4;                                   // rows are multiples of 16 bytes (64 elements per key)
   const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
@@ -565,21 +565,24 @@ __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
   if (a.rp.q_out) put_row_projection(a.rp, slot, 0, 0, tid, 128);
 }
 
+static bool bad_staged_cross(const StagedCross& x, int n_new) {   // a copy of n_new staged segments that cannot be right
+  return x.n_layers <= 0 || x.n_layers > kRefillMaxLayers || x.row_bytes % 16 || x.sc_bytes % 16 || x.src_batch <= 0 ||
+         x.dst_batch <= 0 || x.src_entry0 < 0 || x.src_entry0 + n_new > x.src_batch;
+}
+
 int launch_refill(const RefillArgs& a, hipStream_t s) {
   if (!a.done || !a.slot_row || !a.slot_seg || !a.step || !a.cur_tok || !a.n_done || !a.y || !a.table || !a.pos || !a.ids ||
       !a.out_ids || !a.plan || a.rows <= 0 || a.n_new < 0 || a.n_new > a.rows || a.emb % 16 || a.ids_stride <= 0 ||
       (a.beam_f && (!a.beam_len || !a.beam_len_row)) || (a.y_ct && !a.y_ss) ||
       (a.rp.q_out && (!a.rp.ew || !a.rp.pw || a.rp.q_n % 4)))
     return mt3::fail(MT3_ERR_INVALID, "refill: bad arguments");
-  if (a.n_new > 0 && (a.n_layers <= 0 || a.n_layers > kRefillMaxLayers || a.row_bytes % 16 || a.sc_bytes % 16 ||
-                      a.src_batch <= 0 || a.dst_batch <= 0 || a.src_entry0 < 0 || a.src_entry0 + a.n_new > a.src_batch))
-    return mt3::fail(MT3_ERR_INVALID, "refill: bad staging chunk");
+  if (a.n_new > 0 && bad_staged_cross(a.x, a.n_new)) return mt3::fail(MT3_ERR_INVALID, "refill: bad staging chunk");
   hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, a.done, a.plan, a.n_done, a.rows, a.n_new, 1);
   if (a.n_new > 0) {
     // a K or V row of one layer is H*T*64 elements (98 KB ... 393 KB): 8 blocks of 256 lanes per row keep >= 1000
     // workgroups in flight for a handful of segments
     const int parts = 8;
-    hipLaunchKernelGGL(refill_cross_kernel, dim3(a.n_new, a.n_layers * 3, parts), dim3(256), 0, s, a, parts);
+    hipLaunchKernelGGL(refill_cross_kernel, dim3(a.n_new, a.x.n_layers * 3, parts), dim3(256), 0, s, a, parts);
   }
   hipLaunchKernelGGL(refill_slot_kernel, dim3(a.rows), dim3(128), 0, s, a);
   MT3_HIP_CHECK(hipGetLastError());
@@ -940,8 +943,7 @@ int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int
   return MT3_OK;
 }
 
-// ------------------------------------------------------------------------------- refill of beam elements
-// (BeamRefillArgs, kernels.h)
+// ------------------------------------------------------- refill of beam elements (BeamRefillArgs, kernels.h)
 __global__ __launch_bounds__(256) void beam_refill_cross_kernel(BeamRefillArgs a, int parts) {
   const int i = blockIdx.x, k = a.b.k;
   const int n_fin = a.plan[a.b.elems];
@@ -952,14 +954,14 @@ __global__ __launch_bounds__(256) void beam_refill_cross_kernel(BeamRefillArgs a
   char* dst;
   size_t bytes;
   if (what < 2) {
-    bytes = a.row_bytes;
-    src = a.src[l] + (static_cast<size_t>(what) * a.src_batch + a.src_entry0 + i) * bytes;
-    dst = a.dst[l] + static_cast<size_t>(what) * a.dst_batch * bytes;
+    bytes = a.x.row_bytes;
+    src = a.x.src[l] + (static_cast<size_t>(what) * a.x.src_batch + a.x.src_entry0 + i) * bytes;
+    dst = a.x.dst[l] + static_cast<size_t>(what) * a.x.dst_batch * bytes;
   } else {
-    if (!a.src_sc[l]) return;
-    bytes = a.sc_bytes;
-    src = a.src_sc[l] + static_cast<size_t>(a.src_entry0 + i) * bytes;
-    dst = a.dst_sc[l];
+    if (!a.x.src_sc[l]) return;
+    bytes = a.x.sc_bytes;
+    src = a.x.src_sc[l] + static_cast<size_t>(a.x.src_entry0 + i) * bytes;
+    dst = a.x.dst_sc[l];
   }
   u32x4* d4[kBeamMaxK];
 #pragma unroll
@@ -1063,16 +1065,13 @@ int launch_beam_refill(const BeamRefillArgs& a, hipStream_t s) {
       a.L <= 0 || a.num_steps <= 0 || a.num_steps > a.L || a.n_new < 0 || a.n_new > b.elems ||
       (a.rp.q_out && (!a.rp.ew || !a.rp.pw || a.rp.q_n % 4)))
     return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad arguments");
-  if (a.n_new > 0 && (a.n_layers <= 0 || a.n_layers > kRefillMaxLayers || a.row_bytes % 16 || a.sc_bytes % 16 ||
-                      a.src_batch <= 0 || a.dst_batch <= 0 || a.src_entry0 < 0 || a.src_entry0 + a.n_new > a.src_batch))
-    return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad staging chunk");
+  if (a.n_new > 0 && bad_staged_cross(a.x, a.n_new)) return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad staging chunk");
   const size_t lds = (static_cast<size_t>(a.num_steps) + a.L) * b.k * sizeof(unsigned short);
   if (lds > 65536) return mt3::fail(MT3_ERR_INVALID, "beam_refill: history and decodes of an element exceed 64 KB of LDS");
   hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, b.done, a.plan, b.n_done, b.elems, a.n_new, b.k);
   if (a.n_new > 0) {
-    // as refill_cross_kernel, with twice the parts: a block stores every piece it loads k times
-    const int parts = 16;
-    hipLaunchKernelGGL(beam_refill_cross_kernel, dim3(a.n_new, a.n_layers * 3, parts), dim3(256), 0, s, a, parts);
+    const int parts = 16;     // twice refill_cross_kernel's: a block stores every piece it loads k times
+    hipLaunchKernelGGL(beam_refill_cross_kernel, dim3(a.n_new, a.x.n_layers * 3, parts), dim3(256), 0, s, a, parts);
   }
   hipLaunchKernelGGL(beam_refill_elem_kernel, dim3(b.elems), dim3(256), lds, s, a);
   MT3_HIP_CHECK(hipGetLastError());

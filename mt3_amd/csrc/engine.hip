@@ -22,6 +22,10 @@
 //     independent row groups, one graph BRANCH each (fork/join capture over several streams), so that one
 //     chain's latency-bound GEMMs run beside another chain's HBM-bound K/V streaming; it paid +6 % with the
 //     first kernels and nothing with the current ones, so the default is one chain.
+//   * host side, every decoding entry point is the same three pieces: a start on the caller's stream (reset_slots,
+//     embed_bos, reset_beam1_state), one GroupJob dealt to the row groups' worker threads (post_groups / run_one_group
+//     around run_group, or around run_group_stream for the in-flight batched jobs, which run_stream_job drives), and
+//     a join (decode_finish, or run_stream_job's own).
 //   * sized for 288 GB HBM: all workspaces for max_batch are allocated up front
 //     (B=256: ~3.3 GB KV cache + ~0.9 GB cross K/V + ~0.5 GB activations in bf16).
 #include <hip/hip_runtime.h>
@@ -143,23 +147,26 @@ struct GroupGraph {
   hipGraphExec_t exec;
 };
 
-// what mt3_engine_decode left for mt3_engine_decode_wait
+// The job in flight: what every group of it leaves behind (run_one_group), and what mt3_engine_decode left for
+// mt3_engine_decode_wait (decode_finish)
 struct PendingDecode {
   bool active = false;
   int posted = 0;               // workers that hold a job of this decode
   int groups = 1;
-  bool beam1 = false;
+  int rcs[kMaxGroups] = {};
+  int ran[kMaxGroups] = {};
   bool used_graph[kMaxGroups] = {};
+  std::string errs[kMaxGroups];
+  // decode_finish: where the ids go
+  bool beam1 = false;
   int batch = 0;
   int32_t* d_ids = nullptr;
   hipStream_t s = nullptr;
-  int beams = 0;                // mt3_engine_decode_beams: k (0: mt3_engine_decode)
+  // ... and what only the k-beam finalisation reads (mt3_engine_decode_beams)
+  int beams = 0;                // k (0: mt3_engine_decode)
   int num_steps = 0;
   int32_t* d_all_ids = nullptr;
   float* d_scores = nullptr;
-  int rcs[kMaxGroups] = {};
-  int ran[kMaxGroups] = {};
-  std::string errs[kMaxGroups];
 };
 
 }  // namespace
@@ -1455,9 +1462,15 @@ static int row_groups_for(const mt3_engine_config& c, int batch, bool early_exit
   return batch >= 128 ? 2 : 1;
 }
 
-// Row groups of mt3_engine_transcribe (in-flight batching keeps every group's rows full, so the rule of the canonical
-// full-length schedule applies, not the ragged one's)
-static int stream_row_groups_for(const mt3_engine_config& c, int slots) { return row_groups_for(c, slots); }
+// Row groups of a streaming job (mt3_engine_transcribe, mt3_engine_transcribe_beams) over `units` units of `unit` slots:
+// in-flight batching keeps every group's rows full, so the rule of the canonical full-length schedule applies, not the
+// ragged one's; a group holds whole units and at least 16 slots (groups_override > 0: mt3_debug_engine_transcribe's choice)
+static int stream_groups_for(const mt3_engine_config& c, int flags, int units, int unit, int groups_override) {
+  const bool one = (flags & MT3_DECODE_SINGLE_STREAM) || (c.options & MT3_OPT_NO_ROW_GROUPS);
+  int groups = groups_override > 0 ? groups_override : one ? 1 : row_groups_for(c, units * unit);
+  while (groups > 1 && (units / groups) * unit < 16) --groups;
+  return groups;
+}
 
 // ---- persistent group workers
 static void worker_main(Worker* w, int dev) {
@@ -1742,6 +1755,88 @@ static int ensure_group_streams(mt3_engine* e, int groups) {
   return MT3_OK;
 }
 
+using mt3feed::Feed;       // csrc/feed.h: the segment queue of the streaming jobs
+using mt3feed::FeedRange;
+using mt3feed::feed_fail;
+using mt3feed::feed_pop;
+using mt3feed::feed_release;
+using mt3feed::feed_wait;
+
+// ---- the scaffold every row-group job shares (mt3_engine_decode, _decode_beams, _transcribe, _transcribe_beams)
+// A job deals `units` units of `unit` slots each to `groups` row groups: greedy and beam-1 jobs have unit = 1, k-beam jobs
+// unit = k, so that every group boundary is an element boundary.
+struct GroupJob {
+  int units, unit, groups, variant, num_steps;
+  bool early, use_graph;
+  bool own_streams;           // group g runs on part_stream[g] behind part_begin; false: the one group, on the caller's stream
+  hipStream_t s;              // the caller's stream
+  float* d_first_logits;      // (GroupRun: the caller's-stream schedule only)
+  float* d_step_logits;
+};
+
+// Starts a job: the step-graph cache is trimmed (no worker is running here) and e->pending is the job's
+static PendingDecode& begin_job(mt3_engine* e) {
+  if (e->group_graphs.size() > 96) drop_group_graphs(e);
+  e->pending = PendingDecode();
+  return e->pending;
+}
+
+// Group g of job j, on the calling thread: `loop` (run_group or run_group_stream) on the group's GroupRun; what it did
+// goes to e->pending, and is returned.
+using GroupLoop = std::function<int(GroupRun&)>;
+static int run_one_group(mt3_engine* e, const GroupJob& j, int g, const GroupLoop& loop) {
+  PendingDecode& q = e->pending;
+  GroupRun r{};
+  chain_rows(j.units, j.groups, g, &r.row0, &r.rows);
+  r.row0 *= j.unit;
+  r.rows *= j.unit;
+  r.batch = j.units * j.unit;
+  r.variant = j.variant | (j.groups > 1 ? kVarBeside : 0);
+  r.num_steps = j.num_steps;
+  r.slot = g;
+  r.early = j.early;
+  r.use_graph = j.use_graph;
+  r.s = j.own_streams ? e->part_stream[g] : j.s;
+  r.d_first_logits = j.d_first_logits;
+  r.d_step_logits = j.d_step_logits;
+  hipError_t he = j.own_streams ? hipStreamWaitEvent(r.s, e->part_begin, 0) : hipSuccess;
+  if (he == hipSuccess) {
+    q.rcs[g] = loop(r);
+    if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
+  }
+  q.ran[g] = r.ran;
+  q.used_graph[g] = r.used_graph;
+  // The group's host thread WAITS for its stream.  Measured (r3, f32, B = 256, 4 groups): 1095 ms per 1024-step
+  // decode when every group stream has a host thread in hipStreamSynchronize, 1166-1170 ms when only the
+  // caller's stream (waiting for events of the groups) is synchronised -- a stream nobody waits on retires its
+  // commands through the runtime's interrupt path.  (The caller's stream is the caller's to wait for.)
+  if (j.own_streams && he == hipSuccess) he = wait_stream(e, g, r.s);
+  if (q.rcs[g] == MT3_OK && he != hipSuccess) {
+    q.rcs[g] = MT3_ERR_HIP;
+    q.errs[g] = hipGetErrorString(he);
+  }
+  return q.rcs[g];
+}
+
+// Hands every group of job j to its worker thread.  feed == nullptr (the decodes): a group whose worker could not be
+// started runs on the calling thread, after the posted ones started.  Otherwise (the streaming jobs, whose calling thread
+// is the feed's producer): a group that fails fails the feed -- nobody may wait for its entries any more -- and false is
+// returned as soon as a worker could not be started.
+static bool post_groups(mt3_engine* e, const GroupJob& j, const GroupLoop& loop, Feed* feed) {
+  PendingDecode& p = e->pending;
+  p.groups = j.groups;
+  p.active = true;                                       // every other entry point of the engine refuses meanwhile
+  for (int g = 0; g < j.groups; ++g) {
+    auto body = [e, j, g, loop, feed]() {
+      if (run_one_group(e, j, g, loop) != MT3_OK && feed) feed_fail(*feed);
+    };
+    if (worker_post(e, g, body)) p.posted = g + 1;
+    else if (feed) return false;
+    else body();
+  }
+  return true;
+}
+
 // Joins the decode that is in flight: waits for its workers, then (on the caller's stream) the beam-1 finalisation
 // and the copy of the ids.  Every group thread has waited for its stream, so the caller's stream needs no event.
 static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
@@ -1774,6 +1869,38 @@ static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
   return MT3_OK;
 }
 
+// ---- the start of a job, on the caller's stream
+// Position 0 and BOS (= 0) for slots [0, n); `counters`: nothing finished (done flags, the groups' counters of finished
+// slots), `ids`: zeroed id rows -- mt3_engine_transcribe_beams starts every slot FINISHED (launch_beam_stream_init) and
+// the k-beam jobs keep their ids in the history
+static int reset_slots(mt3_engine* e, int n, bool counters, bool ids, hipStream_t s) {
+  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(n) * 4, s));
+  if (counters) MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
+  if (counters) MT3_HIP_CHECK(hipMemsetAsync(e->done, 0, static_cast<size_t>(n) * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(n) * 4, s));
+  if (ids) MT3_HIP_CHECK(hipMemsetAsync(e->ids, 0, static_cast<size_t>(n) * e->cfg.max_decode_len * 4, s));
+  return MT3_OK;
+}
+
+// decoder input of step 0 for slots [0, n): Embed(BOS) + FixedEmbed[0]; later steps get theirs from the argmax kernel
+static int embed_bos(mt3_engine* e, int n, hipStream_t s) {
+  const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
+  return mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
+                            e->cfg.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, n, e->cfg.emb_dim, rp, s);
+}
+
+// t5x beam_search(alpha = 0.6) with one beam (MT3_DECODE_BEAM1): live log-prob 0, nothing finished; the loop bound uses
+// the brevity penalty of num_steps + 1 (the dummy start token extends the length by one).  The value travels as a
+// kernel argument: no host buffer has to stay alive behind an asynchronous copy.
+static int reset_beam1_state(mt3_engine* e, int num_steps, hipStream_t s) {
+  const size_t Bm = static_cast<size_t>(e->cfg.max_batch);
+  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->beam_f, 0, 2 * Bm * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->beam_len, 0xFF, Bm * 4, s));   // -1
+  MT3_HIP_CHECK(hipMemsetAsync(e->beam_len_row, 0xFF, Bm * 4, s));
+  return MT3_OK;
+}
+
 // shared body of mt3_engine_decode / mt3_engine_decode_forced
 static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t debug_skip,
                        const int32_t* d_forced, float* d_step_logits, int32_t* d_ids, float* d_first_logits,
@@ -1794,20 +1921,11 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   if (d_forced && (beam1 || early || async))
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_forced: not combinable with BEAM1 / EARLY_EXIT / ASYNC");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = c.max_decode_len;
-  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(batch) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->done, 0, static_cast<size_t>(batch) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(batch) * 4, s));     // BOS = 0
-  MT3_HIP_CHECK(hipMemsetAsync(e->ids, 0, static_cast<size_t>(batch) * L * 4, s));
+  MT3_TRY(reset_slots(e, batch, true, true, s));
   if (d_forced)    // engine-owned copy: the step graph holds ITS address, whatever buffer the caller passes
-    MT3_HIP_CHECK(hipMemcpyAsync(e->forced, d_forced, static_cast<size_t>(batch) * L * 4, hipMemcpyDeviceToDevice, s));
-  // decoder input of step 0: Embed(BOS) + FixedEmbed[0]; later steps get theirs from the argmax kernel
-  {
-    const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
-    MT3_TRY(mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
-                               c.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, batch, c.emb_dim, rp, s));
-  }
+    MT3_HIP_CHECK(hipMemcpyAsync(e->forced, d_forced, static_cast<size_t>(batch) * c.max_decode_len * 4,
+                                 hipMemcpyDeviceToDevice, s));
+  MT3_TRY(embed_bos(e, batch, s));
   // Row retirement comes with the early exit: rows that have finished cost nothing from then on (mt3_hip.h).  Without
   // EARLY_EXIT every row runs every step -- the canonical full-length schedule the headline is quoted on.
   const bool retire = early && debug_skip == 0;
@@ -1817,24 +1935,16 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   // entry points), then kVar*
   const int variant = (debug_skip & 3) | (beam1 ? kVarBeam : 0) | (d_forced ? kVarForced : 0) | (retire ? kVarRetire : 0) |
                       (e->eos_on && !d_forced ? kVarEos : 0);
-  if (beam1) {
-    // t5x beam_search(alpha = 0.6): live log-prob 0, nothing finished; the loop bound uses the brevity
-    // penalty of max_decode_len + 1 (the dummy start token extends the length by one).  The value travels as a
-    // kernel argument: no host buffer has to stay alive behind an asynchronous copy.
-    MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));
-    MT3_HIP_CHECK(hipMemsetAsync(e->beam_f, 0, static_cast<size_t>(2) * c.max_batch * 4, s));
-    MT3_HIP_CHECK(hipMemsetAsync(e->beam_len, 0xFF, static_cast<size_t>(c.max_batch) * 4, s));   // -1
-    MT3_HIP_CHECK(hipMemsetAsync(e->beam_len_row, 0xFF, static_cast<size_t>(c.max_batch) * 4, s));
-  }
-  if (e->group_graphs.size() > 96) drop_group_graphs(e);      // (no worker is running here)
-  PendingDecode& p = e->pending;
-  p = PendingDecode();
+  if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
+  PendingDecode& p = begin_job(e);
   p.beam1 = beam1;
   p.batch = batch;
   p.d_ids = d_ids;
   p.s = s;
   const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
   const int req_chains = (flags >> 8) & 0xF;
+  GroupJob j{batch, 1, 1, variant, num_steps, early, use_graph, false, s, d_first_logits, d_step_logits};
+  const GroupLoop loop = [e](GroupRun& r) { return run_group(e, r); };
 
   // ---- the row-group schedule (see mt3_engine::part_stream): batches of >= 128 rows, unless the caller asked for
   // one stream / graph chains, or wants per-step logits (those live on the caller's stream)
@@ -1843,43 +1953,9 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
       !(c.options & MT3_OPT_NO_ROW_GROUPS) && debug_skip == 0 && !d_forced && !d_step_logits && !d_first_logits) {
     if (ensure_group_streams(e, groups) == MT3_OK) {
       MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-      p.groups = groups;
-      p.active = true;
-      for (int g = 0; g < groups; ++g) {
-        auto body = [e, g, groups, batch, variant, num_steps, early, use_graph]() {
-          PendingDecode& q = e->pending;
-          GroupRun r{};
-          chain_rows(batch, groups, g, &r.row0, &r.rows);
-          r.batch = batch;
-          r.variant = variant | kVarBeside;            // groups > 1 here
-          r.num_steps = num_steps;
-          r.slot = g;
-          r.early = early;
-          r.use_graph = use_graph;
-          r.s = e->part_stream[g];
-          hipError_t he = hipStreamWaitEvent(r.s, e->part_begin, 0);
-          if (he == hipSuccess) {
-            q.rcs[g] = run_group(e, r);
-            if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
-          }
-          q.ran[g] = r.ran;
-          q.used_graph[g] = r.used_graph;
-          // The group's host thread WAITS for its stream.  Measured (r3, f32, B = 256, 4 groups): 1095 ms per 1024-step
-          // decode when every group stream has a host thread in hipStreamSynchronize, 1166-1170 ms when only the
-          // caller's stream (waiting for events of the groups) is synchronised -- a stream nobody waits on retires its
-          // commands through the runtime's interrupt path.
-          if (he == hipSuccess) he = wait_stream(e, g, r.s);
-          if (q.rcs[g] == MT3_OK && he != hipSuccess) {
-            q.rcs[g] = MT3_ERR_HIP;
-            q.errs[g] = hipGetErrorString(he);
-          }
-        };
-        if (worker_post(e, g, body)) {
-          p.posted = g + 1;
-        } else {            // no thread to be had: this group runs on the calling thread (after the posted ones started)
-          body();
-        }
-      }
+      j.groups = groups;
+      j.own_streams = true;
+      post_groups(e, j, loop, nullptr);
       if (async) return MT3_OK;
       return decode_finish(e, h_steps_run);
     }
@@ -1917,38 +1993,19 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
     if (async) return MT3_OK;
     return decode_finish(e, h_steps_run);
   }
-  // one group = the whole batch, on the caller's stream
-  auto body = [e, batch, variant, num_steps, early, use_graph, s, d_first_logits, d_step_logits]() {
-    PendingDecode& q = e->pending;
-    GroupRun r{};
-    r.row0 = 0;
-    r.rows = r.batch = batch;
-    r.variant = variant;
-    r.num_steps = num_steps;
-    r.slot = 0;
-    r.early = early;
-    r.use_graph = use_graph;
-    r.s = s;
-    r.d_first_logits = d_first_logits;
-    r.d_step_logits = d_step_logits;
-    q.rcs[0] = run_group(e, r);
-    if (q.rcs[0] != MT3_OK) q.errs[0] = mt3_last_error();
-    q.ran[0] = r.ran;
-    q.used_graph[0] = r.used_graph;
-  };
-  p.active = true;
-  if (async && worker_post(e, 0, body)) {
-    p.posted = 1;
+  // one group = the whole batch, on the caller's stream (MT3_DECODE_ASYNC: driven by worker 0, if there is one to be had)
+  if (async) {
+    post_groups(e, j, loop, nullptr);
     return MT3_OK;
   }
-  body();
-  if (async) return MT3_OK;
+  p.active = true;
+  run_one_group(e, j, 0, loop);
   return decode_finish(e, h_steps_run);
 }
 
 // ----------------------------------------------------------------------------------------------- k-beam search
-// mt3_engine_decode_beams: the decode loop of mt3_engine_decode with the beam step (decode_ops.hip: beam_step_kernel +
-// beam_reorder_kernel) as the last launches of every step.  Slots b*k .. b*k + k - 1 are the beams of element b; the
+// mt3_engine_decode_beams: a GroupJob of k-slot units on run_group's loop, with the beam step (decode_ops.hip:
+// beam_step_kernel + beam_reorder_kernel) as the last launches of every step.  Slots b*k .. b*k + k - 1 are the beams of element b; the
 // slot -> cache-row map of row retirement is always in use (a beam takes over its parent's cache row), compaction
 // never is (beam groups stay in place), and a retired element's k slots are `done` from the step after it retired.
 static int ensure_beam_state(mt3_engine* e) {
@@ -1988,23 +2045,14 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   MT3_TRY(ensure_beam_state(e));
   const int slots = batch * k;
   const bool early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
-  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(slots) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->done, 0, static_cast<size_t>(slots) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(slots) * 4, s));     // BOS = 0
+  MT3_TRY(reset_slots(e, slots, true, false, s));
   MT3_HIP_CHECK(hipMemsetAsync(e->bk_forks, 0, 4, s));
-  {
-    const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
-    MT3_TRY(mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
-                               c.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, slots, c.emb_dim, rp, s));
-  }
+  MT3_TRY(embed_bos(e, slots, s));
   MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
   MT3_TRY(mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s));
-  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // as MT3_DECODE_BEAM1
+  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
   const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift);
-  if (e->group_graphs.size() > 96) drop_group_graphs(e);
-  PendingDecode& p = e->pending;
-  p = PendingDecode();
+  PendingDecode& p = begin_job(e);
   p.beams = k;
   p.num_steps = num_steps;
   p.batch = batch;
@@ -2012,82 +2060,35 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   p.d_all_ids = d_all_ids;
   p.d_scores = d_scores;
   p.s = s;
-  const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
-  // the row-group schedule of mt3_engine_decode, on B * k rows, with every group boundary on a beam-group boundary
+  GroupJob j{batch, k, 1, variant, num_steps, early, !(flags & MT3_DECODE_NO_GRAPH), false, s, nullptr, nullptr};
+  const GroupLoop loop = [e](GroupRun& r) { return run_group(e, r); };
+  // the row-group rule of mt3_engine_decode on batch * k slots (a group holds whole elements)
   int groups = row_groups_for(c, slots, early);
   if (groups > batch) groups = 1;
   if (groups > 1 && !(flags & MT3_DECODE_SINGLE_STREAM) && c.decode_chains <= 1 && !(c.options & MT3_OPT_NO_ROW_GROUPS)) {
     if (ensure_group_streams(e, groups) == MT3_OK) {
       MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-      p.groups = groups;
-      p.active = true;
-      for (int g = 0; g < groups; ++g) {
-        auto body = [e, g, groups, batch, k, slots, variant, num_steps, early, use_graph]() {
-          PendingDecode& q = e->pending;
-          GroupRun r{};
-          int e0, en;
-          chain_rows(batch, groups, g, &e0, &en);
-          r.row0 = e0 * k;
-          r.rows = en * k;
-          r.batch = slots;
-          r.variant = variant | kVarBeside;
-          r.num_steps = num_steps;
-          r.slot = g;
-          r.early = early;
-          r.use_graph = use_graph;
-          r.s = e->part_stream[g];
-          hipError_t he = hipStreamWaitEvent(r.s, e->part_begin, 0);
-          if (he == hipSuccess) {
-            q.rcs[g] = run_group(e, r);
-            if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
-          }
-          q.ran[g] = r.ran;
-          q.used_graph[g] = r.used_graph;
-          if (he == hipSuccess) he = wait_stream(e, g, r.s);
-          if (q.rcs[g] == MT3_OK && he != hipSuccess) {
-            q.rcs[g] = MT3_ERR_HIP;
-            q.errs[g] = hipGetErrorString(he);
-          }
-        };
-        if (worker_post(e, g, body)) p.posted = g + 1;
-        else body();
-      }
-      MT3_TRY(decode_finish(e, h_steps_run));
-      MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));    // complete on return: the fork count is in host memory
-      return MT3_OK;
+      j.groups = groups;
+      j.own_streams = true;
+    } else {
+      ++e->part_failed;
     }
-    ++e->part_failed;
   }
-  p.groups = 1;
-  p.active = true;
-  GroupRun r{};
-  r.row0 = 0;
-  r.rows = r.batch = slots;
-  r.variant = variant;
-  r.num_steps = num_steps;
-  r.slot = 0;
-  r.early = early;
-  r.use_graph = use_graph;
-  r.s = s;
-  p.rcs[0] = run_group(e, r);
-  if (p.rcs[0] != MT3_OK) p.errs[0] = mt3_last_error();
-  p.ran[0] = r.ran;
-  p.used_graph[0] = r.used_graph;
+  if (j.own_streams) {
+    post_groups(e, j, loop, nullptr);
+  } else {            // one group = every slot, on the caller's stream and the calling thread
+    p.active = true;
+    run_one_group(e, j, 0, loop);
+  }
   MT3_TRY(decode_finish(e, h_steps_run));
-  MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
+  MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));    // complete on return: the fork count is in host memory
   return MT3_OK;
 }
 
 // ------------------------------------------------------------------------------------------- in-flight batching
-// mt3_engine_transcribe (mt3_hip.h): the engine's max_batch decode slots stay full while there are segments left.  The
-// queue between the encoder passes (producer: the calling thread) and the row groups (consumers) is csrc/feed.h.
-using mt3feed::Feed;
-using mt3feed::FeedRange;
-using mt3feed::feed_fail;
-using mt3feed::feed_pop;
-using mt3feed::feed_release;
-using mt3feed::feed_wait;
-
+// mt3_engine_transcribe, mt3_engine_transcribe_beams (mt3_hip.h): the engine's max_batch decode slots stay full while
+// there are segments left.  The queue between the encoder passes (producer: the calling thread, produce_chunks) and the
+// row groups (consumers: run_group_stream) is csrc/feed.h; run_stream_job runs the two sides of one job.
 static int ensure_stage(mt3_engine* e) {
   if (e->stage_cap) return MT3_OK;
   const mt3_engine_config& c = e->cfg;
@@ -2103,6 +2104,34 @@ static int ensure_stage(mt3_engine* e) {
   }
   e->stage_cap = cap;
   return MT3_OK;
+}
+
+// Chunk `chunk` of the staging ring, layer l: K/V rows [2][stage_cap][H][T][64] cache elements, and (e4m3 caches) the
+// scale rows [stage_cap][H][T]
+static char* stage_chunk_base(const mt3_engine* e, int l, int chunk) {
+  const size_t row_bytes = static_cast<size_t>(e->cfg.num_heads) * e->cfg.input_length * 64 * e->kv_esize;
+  return static_cast<char*>(e->stage_kv[l]) + static_cast<size_t>(chunk % kStageChunks) * 2 * e->stage_cap * row_bytes;
+}
+static float2* stage_chunk_scale(const mt3_engine* e, int l, int chunk) {
+  if (!e->kv_fp8) return nullptr;
+  return e->stage_scale[l] + static_cast<size_t>(chunk % kStageChunks) * e->stage_cap * e->cfg.num_heads * e->cfg.input_length;
+}
+
+// the staged run `rg` (sequence number -> ring chunk) and the caches of a `dst_batch`-row decode it is copied into
+static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_batch, mt3k::StagedCross* x) {
+  const mt3_engine_config& c = e->cfg;
+  x->n_layers = c.num_decoder_layers;
+  x->row_bytes = static_cast<size_t>(c.num_heads) * c.input_length * 64 * e->kv_esize;
+  x->sc_bytes = static_cast<size_t>(c.num_heads) * c.input_length * sizeof(float2);
+  for (int l = 0; l < c.num_decoder_layers; ++l) {
+    x->src[l] = stage_chunk_base(e, l, rg.seq);
+    x->dst[l] = static_cast<char*>(e->dec[l].cross_kv);
+    x->src_sc[l] = reinterpret_cast<const char*>(stage_chunk_scale(e, l, rg.seq));
+    x->dst_sc[l] = e->kv_fp8 ? reinterpret_cast<char*>(e->dec[l].cross_scale) : nullptr;
+  }
+  x->src_batch = rg.batch;
+  x->src_entry0 = rg.entry0;
+  x->dst_batch = dst_batch;
 }
 
 // the refill launches of one run of staged segments for row group `r` (rg == nullptr: finished slots only hand their
@@ -2139,21 +2168,7 @@ static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRan
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
-    a.n_layers = c.num_decoder_layers;
-    a.row_bytes = static_cast<size_t>(c.num_heads) * c.input_length * 64 * e->kv_esize;
-    a.sc_bytes = static_cast<size_t>(c.num_heads) * c.input_length * sizeof(float2);
-    const size_t chunk = static_cast<size_t>(rg->seq % kStageChunks);
-    for (int l = 0; l < c.num_decoder_layers; ++l) {
-      a.src[l] = static_cast<const char*>(e->stage_kv[l]) + chunk * 2 * e->stage_cap * a.row_bytes;
-      a.dst[l] = static_cast<char*>(e->dec[l].cross_kv);
-      if (e->kv_fp8) {
-        a.src_sc[l] = reinterpret_cast<const char*>(e->stage_scale[l]) + chunk * e->stage_cap * a.sc_bytes;
-        a.dst_sc[l] = reinterpret_cast<char*>(e->dec[l].cross_scale);
-      }
-    }
-    a.src_batch = rg->batch;
-    a.src_entry0 = rg->entry0;
-    a.dst_batch = r.batch;
+    fill_staged_cross(e, *rg, r.batch, &a.x);
   }
   return mt3k::launch_refill(a, r.s);
 }
@@ -2192,21 +2207,7 @@ static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* 
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
-    a.n_layers = c.num_decoder_layers;
-    a.row_bytes = static_cast<size_t>(c.num_heads) * c.input_length * 64 * e->kv_esize;
-    a.sc_bytes = static_cast<size_t>(c.num_heads) * c.input_length * sizeof(float2);
-    const size_t chunk = static_cast<size_t>(rg->seq % kStageChunks);
-    for (int l = 0; l < c.num_decoder_layers; ++l) {
-      a.src[l] = static_cast<const char*>(e->stage_kv[l]) + chunk * 2 * e->stage_cap * a.row_bytes;
-      a.dst[l] = static_cast<char*>(e->dec[l].cross_kv);
-      if (e->kv_fp8) {
-        a.src_sc[l] = reinterpret_cast<const char*>(e->stage_scale[l]) + chunk * e->stage_cap * a.sc_bytes;
-        a.dst_sc[l] = reinterpret_cast<char*>(e->dec[l].cross_scale);
-      }
-    }
-    a.src_batch = rg->batch;
-    a.src_entry0 = rg->entry0;
-    a.dst_batch = r.batch;
+    fill_staged_cross(e, *rg, r.batch, &a.x);
   }
   return mt3k::launch_beam_refill(a, r.s);
 }
@@ -2258,10 +2259,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
         n_fin -= got[i].n * unit;
       }
     }
-    if (n_fin == r.rows) {                       // the other groups took every segment: nothing to decode here
-      r.used_graph = r.use_graph;
-      return MT3_OK;
-    }
+    if (n_fin == r.rows) return MT3_OK;          // the other groups took every segment: nothing to decode here
     seen_fin = n_fin;
   }
   for (long t = 0;; ++t) {
@@ -2340,7 +2338,6 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
 static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStream_t s, bool skip_encoder) {
   const mt3_engine_config& c = e->cfg;
   const size_t seg_floats = static_cast<size_t>(c.input_length) * c.input_depth;
-  const size_t row = static_cast<size_t>(c.num_heads) * c.input_length * 64;
   const int min_batch = e->stage_cap < kStageMinBatch ? e->stage_cap : kStageMinBatch;
   std::vector<void*> kv(c.num_decoder_layers);
   std::vector<float2*> sc(c.num_decoder_layers, nullptr);
@@ -2348,10 +2345,9 @@ static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStre
   for (int q = 0; rc == MT3_OK; ++q) {
     int first, n, pad;
     if (!mt3feed::feed_claim(f, q, e->stage_cap, min_batch, &first, &n, &pad)) break;
-    const size_t chunk = static_cast<size_t>(q % kStageChunks);
     for (int l = 0; l < c.num_decoder_layers; ++l) {
-      kv[l] = static_cast<char*>(e->stage_kv[l]) + chunk * 2 * e->stage_cap * row * e->kv_esize;
-      if (e->kv_fp8) sc[l] = e->stage_scale[l] + chunk * e->stage_cap * c.num_heads * c.input_length;
+      kv[l] = stage_chunk_base(e, l, q);
+      sc[l] = stage_chunk_scale(e, l, q);
     }
     CrossDst dst;
     dst.kv = kv.data();
@@ -2364,6 +2360,51 @@ static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStre
     mt3feed::feed_publish(f, q, first, n, pad);
   }
   mt3feed::feed_finish(f, rc != MT3_OK);
+  return rc;
+}
+
+// what a streaming job did: the longest group's steps and the feed's counters
+struct StreamCounts {
+  int most, polls, refills, starved, produced;
+};
+
+// The streaming job j of entry point `who`, from its posting to its end: the row groups run run_group_stream on their
+// workers while the calling thread encodes segments [next_seg, n_segments) into the staging ring (segments below next_seg
+// sit in the caches already); then the groups' outcomes are folded into one.  The device-side start of the slots is the
+// entry point's, enqueued on j.s before this and closed with part_begin.
+static int run_stream_job(mt3_engine* e, const std::string& who, const GroupJob& j, const float* d_inputs, int n_segments,
+                          int next_seg, int32_t* d_ids, int poll, const BeamOut* bo, bool skip_encoder, StreamCounts* n) {
+  Feed feed;
+  feed.n_total = n_segments;
+  feed.next_seg = next_seg;
+  feed.finished = next_seg == n_segments;
+  PendingDecode& p = begin_job(e);
+  int rc = MT3_OK;
+  if (!post_groups(e, j, [e, &feed, d_ids, poll, bo](GroupRun& r) { return run_group_stream(e, r, feed, d_ids, poll, bo); },
+                   &feed)) {
+    feed_fail(feed);
+    rc = mt3::fail(MT3_ERR_HIP, who + ": could not start a row group's worker thread");
+  } else if (!feed.finished) {
+    rc = produce_chunks(e, feed, d_inputs, j.s, skip_encoder);
+  }
+  const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
+  for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
+  p.active = false;
+  e->compactions = e->compactions_now.exchange(0);
+  e->last_groups = j.groups;
+  e->last_used_graph = 1;
+  n->most = 0;
+  for (int g = 0; g < p.posted; ++g) {
+    if (rc == MT3_OK && p.rcs[g] != MT3_OK)
+      rc = mt3::fail(p.rcs[g], who + " (row group " + std::to_string(g) + "): " + p.errs[g]);
+    n->most = p.ran[g] > n->most ? p.ran[g] : n->most;
+    if (!p.used_graph[g]) e->last_used_graph = 0;
+  }
+  n->polls = feed.polls;
+  n->refills = feed.refills;
+  n->starved = feed.starved;
+  n->produced = feed.produced;
+  if (rc != MT3_OK && !producer_err.empty()) return mt3::fail(rc, producer_err);
   return rc;
 }
 
@@ -2386,111 +2427,37 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   const int L = c.max_decode_len, S = n_segments < c.max_batch ? n_segments : c.max_batch;
   const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
   if (n_segments > S) MT3_TRY(ensure_stage(e));
-  int groups = ((flags & MT3_DECODE_SINGLE_STREAM) || (c.options & MT3_OPT_NO_ROW_GROUPS)) ? 1 : stream_row_groups_for(c, S);
-  if (groups_override > 0) groups = groups_override;
-  while (groups > 1 && S / groups < 16) --groups;
+  const int groups = stream_groups_for(c, flags, S, 1, groups_override);
   const int poll = poll_steps > 0 ? poll_steps : kStreamPollSteps;
   if (ensure_group_streams(e, groups) != MT3_OK)
     return mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe: could not create the row groups' streams");
 
-  // ---- the first S segments go straight into the caches; every slot starts as in mt3_engine_decode
+  // ---- the first S segments go straight into the caches, slot i starts on segment i
   MT3_TRY(encode_impl(e, d_inputs, S, nullptr, CrossDst{}, s));
   e->cur_batch = S;
   MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, static_cast<size_t>(n_segments) * L * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(S) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->done, 0, static_cast<size_t>(S) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(S) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->ids, 0, static_cast<size_t>(S) * L * 4, s));
-  {
-    const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
-    MT3_TRY(mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
-                               c.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, S, c.emb_dim, rp, s));
-  }
+  MT3_TRY(reset_slots(e, S, true, true, s));
+  MT3_TRY(embed_bos(e, S, s));
   MT3_TRY(mt3k::launch_iota(e->slot_row, S, s));
-  MT3_TRY(mt3k::launch_iota(e->slot_seg, S, s));         // slot i starts on segment i
-  if (beam1) {
-    MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));
-    MT3_HIP_CHECK(hipMemsetAsync(e->beam_f, 0, static_cast<size_t>(2) * c.max_batch * 4, s));
-    MT3_HIP_CHECK(hipMemsetAsync(e->beam_len, 0xFF, static_cast<size_t>(c.max_batch) * 4, s));
-    MT3_HIP_CHECK(hipMemsetAsync(e->beam_len_row, 0xFF, static_cast<size_t>(c.max_batch) * 4, s));
-  }
-  if (e->group_graphs.size() > 96) drop_group_graphs(e);
+  MT3_TRY(mt3k::launch_iota(e->slot_seg, S, s));
+  if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   e->stream_max_len = num_steps;
   const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0);
-  const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-
-  Feed feed;
-  feed.n_total = n_segments;
-  feed.next_seg = S;
-  feed.finished = n_segments == S;
-  PendingDecode& p = e->pending;
-  p = PendingDecode();
-  p.groups = groups;
-  p.active = true;                                       // every other entry point of the engine refuses meanwhile
-  bool posted_all = true;
-  for (int g = 0; g < groups && posted_all; ++g) {
-    auto body = [e, g, groups, S, variant, num_steps, use_graph, &feed, d_ids, poll]() {
-      PendingDecode& q = e->pending;
-      GroupRun r{};
-      chain_rows(S, groups, g, &r.row0, &r.rows);
-      r.batch = S;
-      r.variant = variant | (groups > 1 ? kVarBeside : 0);
-      r.num_steps = num_steps;
-      r.slot = g;
-      r.early = true;
-      r.use_graph = use_graph;
-      r.s = e->part_stream[g];
-      hipError_t he = hipStreamWaitEvent(r.s, e->part_begin, 0);
-      if (he == hipSuccess) {
-        q.rcs[g] = run_group_stream(e, r, feed, d_ids, poll);
-        if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
-        he = wait_stream(e, g, r.s);
-      }
-      if (q.rcs[g] == MT3_OK && he != hipSuccess) {
-        q.rcs[g] = MT3_ERR_HIP;
-        q.errs[g] = hipGetErrorString(he);
-      }
-      q.ran[g] = r.ran;
-      q.used_graph[g] = r.used_graph;
-      if (q.rcs[g] != MT3_OK) feed_fail(feed);           // nobody may wait for this group's entries any more
-    };
-    if (worker_post(e, g, body)) p.posted = g + 1;
-    else posted_all = false;
-  }
-  int rc = MT3_OK;
-  if (!posted_all) {
-    feed_fail(feed);
-    rc = mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe: could not start a row group's worker thread");
-  } else if (n_segments > S) {
-    rc = produce_chunks(e, feed, d_inputs, s, skip_encoder);
-  }
-  const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
-  for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
-  p.active = false;
-  e->compactions = e->compactions_now.exchange(0);
-  e->last_groups = groups;
-  int most = 0;
-  e->last_used_graph = 1;
-  for (int g = 0; g < p.posted; ++g) {
-    if (rc == MT3_OK && p.rcs[g] != MT3_OK)
-      rc = mt3::fail(p.rcs[g], "mt3_engine_transcribe (row group " + std::to_string(g) + "): " + p.errs[g]);
-    most = p.ran[g] > most ? p.ran[g] : most;
-    if (!p.used_graph[g]) e->last_used_graph = 0;
-  }
+  const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
+  StreamCounts n{};
+  const int rc = run_stream_job(e, "mt3_engine_transcribe", j, d_inputs, n_segments, S, d_ids, poll, nullptr, skip_encoder, &n);
   mt3_transcribe_stats st{};
   st.slots = S;
   st.groups = groups;
-  st.steps_run = most;
-  st.polls = feed.polls;
-  st.refills = feed.refills;
-  st.starved_polls = feed.starved;
-  st.encoder_chunks = feed.produced;
+  st.steps_run = n.most;
+  st.polls = n.polls;
+  st.refills = n.refills;
+  st.starved_polls = n.starved;
+  st.encoder_chunks = n.produced;
   st.compactions = e->compactions;
   st.used_graph = e->last_used_graph;
   if (h_stats) *h_stats = st;
-  if (rc != MT3_OK && !producer_err.empty()) return mt3::fail(rc, producer_err);
   return rc;
 }
 
@@ -2508,8 +2475,8 @@ int mt3_debug_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_
                          skip_encoder_passes != 0);
 }
 
-// mt3_engine_transcribe_beams: in-flight batching of the k-beam search.  E = min(n_segments, max_batch / k) elements of k
-// slots each; EVERY segment, the first E included, reaches its element through the staging ring (one code path, and no
+// mt3_engine_transcribe_beams: in-flight batching of the k-beam search, a GroupJob of E = min(n_segments, max_batch / k)
+// units of k slots each; EVERY segment, the first E included, reaches its element through the staging ring (one code path, and no
 // k-fold copy of the inputs for a direct first encode): the groups start with every element finished and empty, and the
 // feed starts at segment 0.
 int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_beams,
@@ -2539,21 +2506,14 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
   MT3_TRY(ensure_beam_state(e));
   MT3_TRY(ensure_stage(e));
   const int E = n_segments < c.max_batch / k ? n_segments : c.max_batch / k, slots = E * k;
-  // transcribe_impl's group rule on E * k slots, group boundaries on element boundaries
-  int groups = ((flags & MT3_DECODE_SINGLE_STREAM) || (c.options & MT3_OPT_NO_ROW_GROUPS)) ? 1 : stream_row_groups_for(c, slots);
-  while (groups > 1 && (E / groups) * k < 16) --groups;
+  const int groups = stream_groups_for(c, flags, E, k, 0);
   if (ensure_group_streams(e, groups) != MT3_OK)
     return mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe_beams: could not create the row groups' streams");
 
   // ---- every slot finished and empty; valid (BOS) input rows so that the dense launches of empty slots read numbers
-  MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(slots) * 4, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(slots) * 4, s));
+  MT3_TRY(reset_slots(e, slots, false, false, s));
   MT3_HIP_CHECK(hipMemsetAsync(e->bk_forks, 0, 4, s));
-  {
-    const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
-    MT3_TRY(mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
-                               c.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, slots, c.emb_dim, rp, s));
-  }
+  MT3_TRY(embed_bos(e, slots, s));
   {
     mt3k::GroupSlots gs{};
     for (int g = 0; g < groups; ++g) {
@@ -2563,86 +2523,26 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
     }
     MT3_TRY(mt3k::launch_beam_stream_init(e->done, e->slot_seg, e->bk_fork_src, e->slot_row, e->n_done, slots, groups, gs, s));
   }
-  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // as mt3_engine_decode_beams
-  if (e->group_graphs.size() > 96) drop_group_graphs(e);
+  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
   e->cur_batch = slots;
   e->stream_max_len = num_steps;
   const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift);
-  const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-
-  Feed feed;
-  feed.n_total = n_segments;
-  PendingDecode& p = e->pending;
-  p = PendingDecode();
-  p.groups = groups;
-  p.active = true;
+  const GroupJob j{E, k, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   const BeamOut bo{k, d_all_ids, d_scores};
-  bool posted_all = true;
-  for (int g = 0; g < groups && posted_all; ++g) {
-    auto body = [e, g, groups, E, k, slots, variant, num_steps, use_graph, &feed, d_ids, &bo]() {
-      PendingDecode& q = e->pending;
-      GroupRun r{};
-      int e0, en;
-      chain_rows(E, groups, g, &e0, &en);
-      r.row0 = e0 * k;
-      r.rows = en * k;
-      r.batch = slots;
-      r.variant = variant | (groups > 1 ? kVarBeside : 0);
-      r.num_steps = num_steps;
-      r.slot = g;
-      r.early = true;
-      r.use_graph = use_graph;
-      r.s = e->part_stream[g];
-      hipError_t he = hipStreamWaitEvent(r.s, e->part_begin, 0);
-      if (he == hipSuccess) {
-        q.rcs[g] = run_group_stream(e, r, feed, d_ids, kStreamPollSteps, &bo);
-        if (q.rcs[g] != MT3_OK) q.errs[g] = mt3_last_error();
-        he = wait_stream(e, g, r.s);
-      }
-      if (q.rcs[g] == MT3_OK && he != hipSuccess) {
-        q.rcs[g] = MT3_ERR_HIP;
-        q.errs[g] = hipGetErrorString(he);
-      }
-      q.ran[g] = r.ran;
-      q.used_graph[g] = r.used_graph;
-      if (q.rcs[g] != MT3_OK) feed_fail(feed);
-    };
-    if (worker_post(e, g, body)) p.posted = g + 1;
-    else posted_all = false;
-  }
-  int rc = MT3_OK;
-  if (!posted_all) {
-    feed_fail(feed);
-    rc = mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe_beams: could not start a row group's worker thread");
-  } else {
-    rc = produce_chunks(e, feed, d_inputs, s, false);
-  }
-  const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
-  for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
-  p.active = false;
-  e->compactions = e->compactions_now.exchange(0);
-  e->last_groups = groups;
-  int most = 0;
-  e->last_used_graph = 1;
-  for (int g = 0; g < p.posted; ++g) {
-    if (rc == MT3_OK && p.rcs[g] != MT3_OK)
-      rc = mt3::fail(p.rcs[g], "mt3_engine_transcribe_beams (row group " + std::to_string(g) + "): " + p.errs[g]);
-    most = p.ran[g] > most ? p.ran[g] : most;
-    if (!p.used_graph[g]) e->last_used_graph = 0;
-  }
-  if (rc != MT3_OK) return producer_err.empty() ? rc : mt3::fail(rc, producer_err);
+  StreamCounts n{};
+  MT3_TRY(run_stream_job(e, "mt3_engine_transcribe_beams", j, d_inputs, n_segments, 0, d_ids, kStreamPollSteps, &bo, false, &n));
   // every group thread has waited for its stream: the fork count of the job is final
   MT3_HIP_CHECK(hipMemcpyAsync(e->h_pinned + kForksPinned, e->bk_forks, 4, hipMemcpyDeviceToHost, s));
   MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
   mt3_transcribe_stats st{};
   st.slots = slots;
   st.groups = groups;
-  st.steps_run = most;
-  st.polls = feed.polls;
-  st.refills = (feed.refills - E) * k;
-  st.starved_polls = feed.starved;
-  st.encoder_chunks = feed.produced;
+  st.steps_run = n.most;
+  st.polls = n.polls;
+  st.refills = (n.refills - E) * k;
+  st.starved_polls = n.starved;
+  st.encoder_chunks = n.produced;
   st.compactions = 0;
   st.used_graph = e->last_used_graph;
   if (h_stats) *h_stats = st;

@@ -187,6 +187,18 @@ int launch_compact(const CompactArgs& c, hipStream_t s);
 // position).  The others decode nothing from then on (slot_seg = -1) until a later refill.  All slot-indexed pointers are
 // those of the group's first slot; ids / beam_len_row / the caches are batch bases (reached through slot_row).
 constexpr int kRefillMaxLayers = 16;
+// The staged cross-attention K/V of a run of segments and the caches they are copied into: per decoder layer, staging
+// chunk [2][src_batch][row_bytes] (the run starts at entry src_entry0) -> cache [2][dst_batch][row_bytes]; with e4m3
+// caches also the scale rows [src_batch][sc_bytes] -> [dst_batch][sc_bytes] (src_sc[l] == nullptr: none)
+struct StagedCross {
+  int n_layers;
+  const char* src[kRefillMaxLayers];
+  char* dst[kRefillMaxLayers];
+  const char* src_sc[kRefillMaxLayers];
+  char* dst_sc[kRefillMaxLayers];
+  int src_batch, src_entry0, dst_batch;
+  size_t row_bytes, sc_bytes;
+};
 struct RefillArgs {
   int* done;
   int* slot_row;
@@ -212,15 +224,7 @@ struct RefillArgs {
   int rows;             // slots of the group in use
   int n_new;            // segments handed out by this call (<= finished slots)
   int first_seg;
-  // cross-attention K/V: per decoder layer, staging chunk [2][src_batch][row_bytes] -> cache [2][dst_batch][row_bytes];
-  // with e4m3 caches also the scale rows [src_batch][sc_bytes] -> [dst_batch][sc_bytes]
-  int n_layers;
-  const char* src[kRefillMaxLayers];
-  char* dst[kRefillMaxLayers];
-  const char* src_sc[kRefillMaxLayers];
-  char* dst_sc[kRefillMaxLayers];
-  int src_batch, src_entry0, dst_batch;
-  size_t row_bytes, sc_bytes;
+  StagedCross x;        // where their cross-attention K/V come from and go to (read when n_new > 0)
 };
 int launch_refill(const RefillArgs& a, hipStream_t s);
 // ---- k-beam search (mt3_engine_decode_beams; the rule is stated in include/mt3_hip.h)
@@ -300,13 +304,7 @@ struct BeamRefillArgs {
   int* out_all;         // caller's [n_segments][k][L] or nullptr
   float* out_scores;    // caller's [n_segments][k] or nullptr
   int n_new, first_seg;
-  int n_layers;
-  const char* src[kRefillMaxLayers];
-  char* dst[kRefillMaxLayers];
-  const char* src_sc[kRefillMaxLayers];
-  char* dst_sc[kRefillMaxLayers];
-  int src_batch, src_entry0, dst_batch;
-  size_t row_bytes, sc_bytes;
+  StagedCross x;        // as RefillArgs::x
 };
 int launch_beam_refill(const BeamRefillArgs& a, hipStream_t s);
 // start of an mt3_engine_transcribe_beams job: every slot finished and without a segment (the first refill starts the
