@@ -530,6 +530,47 @@ int mt3_op_decode_attention_fp8(const void* d_q, int32_t q_stride, void* d_kcach
 /* d_src bf16 [2][rows][64] (K rows, then V rows) -> d_dst e4m3 [2][rows][64] + d_scales [rows] f32 pairs */
 int mt3_op_kv_quantize_fp8(const void* d_src, void* d_dst, void* d_scales, int32_t rows, void* stream);
 
+/* The token-rule kernels of the decode loop on SCRIPTED logits: the launches the engine ends every decode step with
+ * (greedy / beam-1 pick, k-beam step, fork copies, finalisation), on logits the caller wrote instead of a model's, with
+ * state the call allocates and frees.  Test drivers: they synchronise `stream` and return when the result is complete.
+ * Common: d_ss != NULL makes the logits of step t UNNORMALISED rows with d_ss [num_steps][rows][n_ss] partial sums
+ * (1 <= n_ss <= 64): the kernels scale row r by rsqrt(sum(d_ss[t][r]) / dim + 1e-6) before anything else, as they do for
+ * the engine's folded logits projection.  max_len > 0 closes a row / element once its position counter reaches max_len
+ * (0: off), as the in-flight batching jobs do.  NULL pointers (other than the optional ones), k outside 1 .. 8 and, for the
+ * beam step, vocab outside [2k, 2048] return MT3_ERR_INVALID before anything touches the device.
+ *
+ * mt3_op_beam_search_scripted: the search of mt3_engine_decode_beams over `elems` elements of k beams; d_logits
+ * [num_steps][elems * k][vocab] f32, row b*k + j of step t = what live beam j of element b sees at step t.  The slot ->
+ * cache-row map starts as the identity; the call stops after the step at which every element is retired or closed
+ * (*h_steps_run).  d_ids [elems][num_steps], d_all_ids [elems][k][num_steps], d_scores [elems][k] as
+ * mt3_engine_decode_beams returns them (an element that max_len closed with nothing finished returns its live beams of
+ * max_len tokens).  h_trace (host) [num_steps][4][elems * k] int32: after step t the slot -> row map, the fork source of
+ * each slot (-1: none), the done flags and the next input tokens; h_live (host) [num_steps][elems * k]: the live
+ * log-probs (rows of steps that did not run are not written).  *h_forks: the fork count
+ * (MT3_STATUS_LAST_DECODE_FORKS).  d_table [vocab][dim_e] / d_pos [num_steps + 1][dim_e] / d_y_next [elems * k][dim_e]
+ * f32 (all or none, dim_e % 16 == 0): each step also writes the next input row of every slot of an open element,
+ * table[token] + pos[t + 1] (the single-stream f32 form). */
+int mt3_op_beam_search_scripted(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                                int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                                const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
+                                float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks,
+                                int32_t* h_steps_run, void* stream);
+/* num_steps steps of the token kernel of mt3_engine_decode on d_logits [num_steps][rows][vocab] (vocab >= 2, any size;
+ * with d_ss the scaled logits are written back in place): mode 0 = greedy (first arg-max, 0 after EOS), mode 1 =
+ * MT3_DECODE_BEAM1 including its finalisation.  No teacher forcing, no EOS schedule.  d_ids [rows][num_steps];
+ * h_done (host) [num_steps][rows]: the done flags after each step. */
+int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                int32_t* h_done, void* stream);
+/* The fork copies of one k-beam step on caller-owned caches: for every slot with d_fork_src[slot] >= 0 and
+ * d_done[slot] == 0, positions [0, d_step[slot]) of row d_fork_src[slot] are copied into row d_slot_row[slot] of every
+ * layer's K and V cache [rows][H][cap][64] of kv_esize-byte elements (1, 2 or 4) and, where given, of its scale pairs
+ * [rows][H][cap] (h_scale == NULL or h_scale[l] == NULL: none).  h_k / h_v / h_scale: HOST arrays of n_layers (<= 16)
+ * device pointers. */
+int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots, void* const* h_k,
+                        void* const* h_v, void* const* h_scale, const int32_t* d_fork_src, const int32_t* d_slot_row,
+                        const int32_t* d_step, const int32_t* d_done, void* stream);
+
 /* MXFP8 dense path (dense_dtype MT3_FP8_E4M3; no counterpart in the reference, whose DenseGeneral is f32,
  * mt3/layers.py:311-360): operands are OCP e4m3fn bytes [rows][K] with one E8M0 power-of-two scale per 32 consecutive
  * K elements [rows][K/32]: scale = 2^(floor(log2 amax) - 7), so amax / scale lies in [128, 256) and nothing

@@ -123,6 +123,13 @@ SIGNATURES = {
     "mt3_op_decode_attention_fp8": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32,
                                               _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_kv_quantize_fp8": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "mt3_op_beam_search_scripted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "mt3_op_token_steps_scripted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _P, _P, _P]),
+    "mt3_op_beam_reorder": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P),
+                                      C.POINTER(_P), _P, _P, _P, _P, _P]),
     "mt3_host_mx8_quantize": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
     "mt3_op_mx8_quantize": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_op_gemm_mx8": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,

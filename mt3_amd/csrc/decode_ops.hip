@@ -1178,3 +1178,195 @@ extern "C" int mt3_ids_to_tokens(const int32_t* d_ids, int32_t batch, int32_t le
                                  int32_t* d_tokens, void* stream) {
   return mt3k::launch_ids_to_tokens(d_ids, batch, length, num_regular, d_tokens, static_cast<hipStream_t>(stream));
 }
+
+// ------------------------------------------------------------------ scripted drivers of the token-rule kernels
+// mt3_op_beam_search_scripted / mt3_op_token_steps_scripted / mt3_op_beam_reorder (mt3_hip.h): the launchers above on
+// logits the caller wrote, with state these calls own.  Test drivers: synchronous, one allocation for the whole state.
+namespace {
+
+#define MT3_OP_TRY(expr)            \
+  do {                              \
+    const int _rc = (expr);         \
+    if (_rc != MT3_OK) return _rc;  \
+  } while (0)
+
+// one zero-filled device allocation carved into 256-byte aligned pieces; freed when the call returns
+struct Scratch {
+  char* base = nullptr;
+  size_t size = 0, used = 0;
+  ~Scratch() {
+    if (base) (void)hipFree(base);
+  }
+  static size_t piece(size_t bytes) { return (bytes + 255) / 256 * 256; }
+  int alloc(size_t bytes, hipStream_t s) {
+    MT3_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&base), bytes));
+    size = bytes;
+    MT3_HIP_CHECK(hipMemsetAsync(base, 0, bytes, s));
+    return MT3_OK;
+  }
+  template <typename T>
+  T* take(size_t n) {
+    T* p = reinterpret_cast<T*>(base + used);
+    used += piece(n * sizeof(T));
+    return p;
+  }
+};
+
+// the brevity-penalty table of a search over `num_steps` positions, as the engine uploads and bounds it
+int upload_brevity(float* d_bp, int num_steps, hipStream_t s) {
+  const std::vector<float> bp = mt3k::brevity_table(num_steps);
+  MT3_HIP_CHECK(hipMemcpyAsync(d_bp, bp.data(), bp.size() * 4, hipMemcpyHostToDevice, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));                    // `bp` leaves scope
+  return mt3k::launch_set_float(d_bp, mt3k::brevity_penalty(num_steps + 1), s);
+}
+
+bool bad_scale(const float* d_ss, int n_ss, int dim) { return d_ss && (n_ss < 1 || n_ss > 64 || dim <= 0); }
+
+}  // namespace
+
+extern "C" int mt3_op_beam_search_scripted(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim,
+                                           int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
+                                           const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids,
+                                           int32_t* d_all_ids, float* d_scores, float* d_y_next, int32_t* h_trace,
+                                           float* h_live, int32_t* h_forks, int32_t* h_steps_run, void* stream) {
+  if (!d_logits || !d_ids || !d_all_ids || !d_scores || !h_trace || !h_live || !h_forks || !h_steps_run)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: null argument");
+  if (k < 1 || k > mt3k::kBeamMaxK || vocab < 2 * k || vocab > 2048)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: k must be 1 .. 8 and 2k <= vocab <= 2048");
+  if (elems <= 0 || elems > 4096 || num_steps <= 0 || num_steps > 4096 || max_len < 0 || bad_scale(d_ss, n_ss, dim))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: elems / num_steps / max_len / row scale out of range");
+  if ((d_table != nullptr) != (d_pos != nullptr) || (d_table != nullptr) != (d_y_next != nullptr) ||
+      (d_table && (dim_e <= 0 || dim_e % 16)))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: the tables and the next-row output come together, "
+                                      "dim_e % 16 == 0");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int slots = elems * k;
+  const size_t n = static_cast<size_t>(slots), hist = static_cast<size_t>(num_steps) * n;
+  Scratch m;
+  MT3_OP_TRY(m.alloc(9 * Scratch::piece(n * 4) + 2 * Scratch::piece(hist * 4) + 2 * Scratch::piece(4) +
+                         Scratch::piece((static_cast<size_t>(num_steps) + 3) * 4),
+                     s));
+  mt3k::BeamKArgs b{};
+  b.vocab = vocab;
+  b.k = k;
+  b.elems = elems;
+  b.live = m.take<float>(n);
+  b.fin_score = m.take<float>(n);
+  b.fin_step = m.take<int>(n);
+  b.fin_beam = m.take<int>(n);
+  b.hist_par = m.take<int>(hist);
+  b.hist_tok = m.take<int>(hist);
+  b.hist_stride = slots;
+  b.slot_row = m.take<int>(n);
+  b.fork_src = m.take<int>(n);
+  b.done = m.take<int>(n);
+  b.step = m.take<int>(n);
+  b.cur_tok = m.take<int>(n);
+  b.fork_count = m.take<int>(1);
+  b.n_done = m.take<int>(1);
+  float* d_bp = m.take<float>(static_cast<size_t>(num_steps) + 3);
+  b.bp = d_bp;
+  b.table = d_table;
+  b.pos_table = d_pos;
+  b.max_pos = num_steps + 1;
+  b.y_next = d_y_next;
+  b.dim = dim_e;
+  b.max_len = max_len;
+  MT3_HIP_CHECK(hipMemsetAsync(b.fork_src, 0xFF, n * 4, s));               // -1: no fork pending
+  MT3_OP_TRY(mt3k::launch_iota(b.slot_row, slots, s));
+  MT3_OP_TRY(mt3k::launch_beam_init(b.live, b.fin_score, b.fin_step, b.fin_beam, slots, k, s));
+  MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
+  int ran = 0;
+  for (int t = 0; t < num_steps; ++t) {
+    b.logits = const_cast<float*>(d_logits) + static_cast<size_t>(t) * n * vocab;
+    const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
+    MT3_OP_TRY(mt3k::launch_beam_step(b, mt3k::RowProj{}, ls, s));
+    int32_t* tr = h_trace + static_cast<size_t>(t) * 4 * n;
+    MT3_HIP_CHECK(hipMemcpyAsync(tr, b.slot_row, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(tr + n, b.fork_src, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(tr + 2 * n, b.done, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(tr + 3 * n, b.cur_tok, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(h_live + static_cast<size_t>(t) * n, b.live, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipStreamSynchronize(s));
+    ran = t + 1;
+    bool all_done = true;
+    for (size_t i = 0; i < n; ++i) all_done = all_done && tr[2 * n + i] != 0;
+    if (all_done) break;                                   // every element retired or closed: the search is over
+  }
+  // an element that max_len closed has max_len steps of history: that is where its live beams are walked back from
+  const int walk = max_len > 0 && max_len < num_steps ? max_len : num_steps;
+  MT3_OP_TRY(mt3k::launch_beam_finalize(b, num_steps, walk, d_ids, d_all_ids, d_scores, s));
+  MT3_HIP_CHECK(hipMemcpyAsync(h_forks, b.fork_count, 4, hipMemcpyDeviceToHost, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
+  *h_steps_run = ran;
+  return MT3_OK;
+}
+
+extern "C" int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                           int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
+                                           int32_t* d_ids, int32_t* h_done, void* stream) {
+  if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, "mt3_op_token_steps_scripted: null argument");
+  if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
+      max_len < 0 || bad_scale(d_ss, n_ss, dim))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_token_steps_scripted: mode is 0 (greedy) or 1 (beam-1); rows, vocab >= 2, "
+                                      "num_steps, max_len or the row scale out of range");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t n = static_cast<size_t>(rows);
+  Scratch m;
+  MT3_OP_TRY(m.alloc(5 * Scratch::piece(n * 4) + Scratch::piece(2 * n * 4) + Scratch::piece(4) +
+                         Scratch::piece((static_cast<size_t>(num_steps) + 3) * 4),
+                     s));
+  int* cur_tok = m.take<int>(n);
+  int* done = m.take<int>(n);
+  int* step = m.take<int>(n);
+  int* len = m.take<int>(n);
+  int* len_row = m.take<int>(n);
+  float* f = m.take<float>(2 * n);
+  int* n_done = m.take<int>(1);
+  float* d_bp = m.take<float>(static_cast<size_t>(num_steps) + 3);
+  MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, n * num_steps * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(len, 0xFF, n * 4, s));                       // -1: nothing finished
+  MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
+  MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
+  const mt3k::BeamState beam{f, len, d_bp, rows, len_row};
+  // a row that max_len closes is retired, as it is in the engine's streaming jobs (the only ones that set max_len)
+  const mt3k::StepRetire rt{max_len > 0 ? 1 : 0, nullptr, nullptr, nullptr, max_len};
+  for (int t = 0; t < num_steps; ++t) {
+    const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
+    MT3_OP_TRY(mt3k::launch_argmax_step(d_logits + static_cast<size_t>(t) * n * vocab, vocab, d_ids, num_steps, cur_tok,
+                                        done, n_done, step, nullptr, nullptr, num_steps + 1, nullptr, nullptr, nullptr, 0,
+                                        rows, mode == 1 ? &beam : nullptr, nullptr, 0, mt3k::RowProj{}, ls, rt, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(h_done + static_cast<size_t>(t) * n, done, n * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (mode == 1) MT3_OP_TRY(mt3k::launch_beam1_finalize(d_ids, num_steps, len_row, rows, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
+  return MT3_OK;
+}
+
+extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots,
+                                   void* const* h_k, void* const* h_v, void* const* h_scale, const int32_t* d_fork_src,
+                                   const int32_t* d_slot_row, const int32_t* d_step, const int32_t* d_done,
+                                   void* stream) {
+  if (!h_k || !h_v || !d_fork_src || !d_slot_row || !d_step || !d_done)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_reorder: null argument");
+  if (n_layers <= 0 || n_layers > mt3k::kRefillMaxLayers)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_reorder: 1 .. 16 layers");
+  mt3k::BeamReorderArgs r{};
+  r.n_layers = n_layers;
+  r.H = H;
+  r.cap = cap;
+  r.kv_esize = kv_esize;
+  r.slots = slots;
+  for (int l = 0; l < n_layers; ++l) {
+    r.k[l] = static_cast<char*>(h_k[l]);
+    r.v[l] = static_cast<char*>(h_v[l]);
+    r.scale[l] = h_scale ? static_cast<float2*>(h_scale[l]) : nullptr;
+  }
+  r.fork_src = d_fork_src;
+  r.slot_row = d_slot_row;
+  r.step = d_step;
+  r.done = d_done;
+  MT3_OP_TRY(mt3k::launch_beam_reorder(r, static_cast<hipStream_t>(stream)));
+  MT3_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  return MT3_OK;
+}

@@ -342,8 +342,7 @@ struct mt3_engine {
 
 namespace {
 
-// t5x decoding.brevity_penalty(alpha = 0.6, length): ((5 + length) / 6) ^ alpha
-float brevity_penalty(int length) { return static_cast<float>(std::pow((5.0 + length) / 6.0, 0.6)); }
+using mt3k::brevity_penalty;     // t5x decoding.brevity_penalty(alpha = 0.6, length), kernels.h
 
 int dmalloc(mt3_engine* e, void** p, size_t bytes) {
   MT3_HIP_CHECK(hipMalloc(p, bytes));
@@ -1272,8 +1271,7 @@ int mt3_engine_finalize(mt3_engine* e) {
   if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->beam_len_row), static_cast<size_t>(Bm) * 4))) return rc;
   {
     // beam_cfg[0]: loop bound of the current call; beam_cfg[1 + n] = brevity_penalty(n), n = 0 .. L + 1
-    std::vector<float> bp(static_cast<size_t>(L) + 3, 0.f);
-    for (int n = 0; n <= L + 1; ++n) bp[1 + n] = brevity_penalty(n);
+    const std::vector<float> bp = mt3k::brevity_table(L);
     if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->beam_cfg), bp.size() * 4))) return rc;
     MT3_HIP_CHECK(hipMemcpy(e->beam_cfg, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
   }

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+#include <vector>
+
 #include "mt3_hip.h"
 
 namespace mt3k {
@@ -113,6 +116,15 @@ int launch_embed(const float* table, const float* pos, const int* tok, const int
 // per-row state of the beam-1 search (t5x beam_search, num_decodes = 1): f = [live_logp | best finished
 // score], the second array `rows` floats after the first; len = prefix length of the best finished
 // hypothesis or -1; cfg[0] = brevity_penalty(max_len + 1), cfg[1 + n] = brevity_penalty(n) (device memory)
+// t5x decoding.brevity_penalty(alpha = 0.6, length): ((5 + length) / 6) ^ alpha
+inline float brevity_penalty(int length) { return static_cast<float>(std::pow((5.0 + length) / 6.0, 0.6)); }
+// host image of BeamState::cfg / BeamKArgs::bp for id rows of L positions: [0] = 0, the bound of a call (set per call to
+// brevity_penalty(num_steps + 1)), [1 + n] = brevity_penalty(n), n = 0 .. L + 1
+inline std::vector<float> brevity_table(int L) {
+  std::vector<float> bp(static_cast<size_t>(L) + 3, 0.f);
+  for (int n = 0; n <= L + 1; ++n) bp[1 + n] = brevity_penalty(n);
+  return bp;
+}
 struct BeamState {
   float* f;
   int* len;

@@ -24,10 +24,11 @@ def brevity_penalty(n, alpha=0.6):
     return ((5.0 + n) / 6.0) ** alpha
 
 
-def beam_search(step, reorder, batch, k, num_steps, alpha=0.6, eos_id=EOS):
+def beam_search(step, reorder, batch, k, num_steps, alpha=0.6, eos_id=EOS, on_step=None):
     """step(tok [batch*k] int64 tensor, t) -> logits [batch*k, V]; reorder(index [batch*k]) makes row j of every
     per-row state (the self-attention cache) a copy of row index[j].  Returns (decodes [batch, k, num_steps] int32,
-    scores [batch, k] float64, steps_run), decodes in increasing order of score."""
+    scores [batch, k] float64, steps_run), decodes in increasing order of score.  on_step(t, live_lp, live_seq, index,
+    retired), if given, sees the state each step leaves (the arrays are the search's own: copy what is kept)."""
     n = batch * k
     live_lp = np.full((batch, k), NEG_INF)
     live_lp[:, 0] = 0.0
@@ -85,6 +86,8 @@ def beam_search(step, reorder, batch, k, num_steps, alpha=0.6, eos_id=EOS):
                 new_tok[b * k + j] = token
             if fin_valid[b, k - 1] and fin_score[b, k - 1] > live_lp[b, 0] / bp_max:
                 retired[b] = True
+        if on_step is not None:
+            on_step(t, live_lp, live_seq, index, retired)
         reorder(torch.from_numpy(index))
         tok = torch.from_numpy(new_tok)
     decodes = np.zeros((batch, k, num_steps), np.int32)
