@@ -452,6 +452,39 @@ int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t
                      const int32_t* d_decoder_inputs /* NULL: shift right */, const float* d_weights /* NULL: target > 0 */,
                      float* d_sequence_scores, float* d_token_scores, float* d_logits, void* stream);
 
+/* Scoring of a whole job: mt3_engine_encode + mt3_engine_score over ANY number of segments, with the statistics a note
+ * confidence is made of.  It sits behind the same reference call as mt3_engine_score -- t5x score_batch with
+ * return_intermediates on the features mt3_amd.models.convert_features builds (mt3/models.py:121-152) -- looped over the
+ * batches of a file as the notebook loops predict_batch_with_aux (NB:295-301).
+ * d_inputs [n_segments, T, input_depth] f32 (log-mel); d_targets [n_segments, length] int32 (0 = padding).  The decoder
+ * inputs are shift_right(targets) and the weights target > 0 (the NULL defaults of mt3_engine_score).
+ * d_sequence_scores [n_segments] f32; d_token_scores [n_segments, length] f32 or NULL; d_top1_ids [n_segments, length]
+ * int32 or NULL: the arg-max of the position's logits, the LOWEST id on equal logits (lax.top_k's tie rule, as the beam
+ * kernels rank); d_top1_scores [n_segments, length] f32 or NULL: its log-probability logits[top1] - logsumexp(logits),
+ * so token score - top1 score is the margin of the target to the model's best token (0 when they are the same).  Where
+ * the target is 0 all three are 0.
+ * Work: chunks of at most max_batch segments; per chunk the encoder pass and cross-K/V of mt3_engine_encode into the
+ * caches, then the prefill of mt3_engine_score against them.  Without a top-1 output the reduction is the one of
+ * mt3_engine_score; with one, a kernel that finds the arg-max in the pass that finds the maximum (same reduction order,
+ * same token scores).  Everything is enqueued on `stream` (no graph, no row groups, no worker threads); the call does not
+ * block (the FIRST scoring call of an f32 engine waits once for the plane copies of its decoder matrices).
+ * Contract: segment i's sequence score and token scores are BIT-IDENTICAL to mt3_engine_encode of its chunk (segments
+ * [c * max_batch, min(n_segments, (c + 1) * max_batch))) + mt3_engine_score, under the encoder-reproducibility condition
+ * mt3_engine_encode documents (f32: always; bf16: passes of 8 or more segments).  In bf16 a last chunk of n < 8 segments
+ * is encoded in a pass of min(8, max_batch) rows behind the segments in front of it, exactly as mt3_engine_transcribe
+ * pads its staging passes, so a segment's scores do not depend on where the job ends.
+ * State: the call leaves the engine "encoded" with its last pass, as a sequence of mt3_engine_encode calls would: the
+ * last chunk's segments in cache rows 0 .. n-1 (bf16, padded last chunk: the pass's 8 rows, the chunk's segments last).
+ * It does not touch the decode state.  MT3_STATUS_SCORE_CHUNKS reports the prefill chunks of the whole call.
+ * MT3_ERR_INVALID, before any device work: a NULL engine, inputs, targets or sequence scores; n_segments < 1; length
+ * outside 1 .. max_decode_len; an engine that is not finalized; a decode in flight (MT3_DECODE_ASYNC); e4m3 K/V caches
+ * (kv_cache_dtype MT3_FP8_E4M3: out of scope, as for mt3_engine_score).  Ids outside [0, vocab) are clamped. */
+int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs /* [n_segments, T, input_depth] log-mel */,
+                              int32_t n_segments, int32_t length, const int32_t* d_targets /* [n_segments, length] */,
+                              float* d_sequence_scores /* [n_segments] */, float* d_token_scores /* [n, length] or NULL */,
+                              int32_t* d_top1_ids /* [n, length] or NULL */, float* d_top1_scores /* [n, length] or NULL */,
+                              void* stream);
+
 /* Engine facts a caller cannot see from results alone (a negative return is an mt3_status).
  * GRAPH_FALLBACKS: decode calls so far whose step graph could not be captured/instantiated and that therefore
  * ran as direct launches (same ids, slower) -- the fallback is counted, never silent;
@@ -465,7 +498,7 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_PARTITION_FALLBACKS = 8 /* decodes that wanted the row-group schedule but could not set it up */,
        MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */,
        MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams / mt3_engine_transcribe_beams */,
-       MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score */ };
+       MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score / mt3_engine_score_segments (all its encoder chunks) */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -571,6 +604,16 @@ int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esi
                         void* const* h_v, void* const* h_scale, const int32_t* d_fork_src, const int32_t* d_slot_row,
                         const int32_t* d_step, const int32_t* d_done, void* stream);
 
+/* The statistics kernel of mt3_engine_score_segments on SCRIPTED logits (t5x score_batch's log-softmax / gather with
+ * the row's arg-max next to it): per row, token score = (logits[target] - logsumexp(logits)) * weight with the bits
+ * mt3_engine_score gives for the same logits, top-1 id = the arg-max (lowest id on equal logits), top-1 score =
+ * logits[top1] - logsumexp(logits); a row whose target is 0 gets 0, 0 and 0 and is not read.
+ * d_logits [rows][vocab] f32, d_targets [rows] int32 (0 = padding; ids outside [0, vocab) are clamped as mt3_engine_score
+ * clamps them), d_weights [rows] f32 or NULL.  d_token_scores / d_top1_ids / d_top1_scores [rows] (each may be NULL).
+ * One launch on `stream`, nothing allocated or waited for.  MT3_ERR_INVALID: NULL logits/targets, rows < 1, vocab < 2. */
+int mt3_op_score_token_stats(const float* d_logits, const int32_t* d_targets, const float* d_weights, int32_t rows,
+                             int32_t vocab, float* d_token_scores, int32_t* d_top1_ids, float* d_top1_scores, void* stream);
+
 /* MXFP8 dense path (dense_dtype MT3_FP8_E4M3; no counterpart in the reference, whose DenseGeneral is f32,
  * mt3/layers.py:311-360): operands are OCP e4m3fn bytes [rows][K] with one E8M0 power-of-two scale per 32 consecutive
  * K elements [rows][K/32]: scale = 2^(floor(log2 amax) - 7), so amax / scale lies in [128, 256) and nothing
@@ -626,6 +669,21 @@ int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const
                      const int32_t* h_has_max_time, const double* h_max_times,
                      mt3_note* h_notes, int64_t notes_capacity, int64_t* n_notes,
                      int64_t* invalid_events, int64_t* dropped_events, double* total_time);
+/* mt3_notes_decode with each note's tokens: the same notes in the same order, the same counts and total_time (one state
+ * machine serves both), plus h_note_tokens [notes_capacity][2] int64 (written for the notes returned; may be NULL).  The
+ * reference's state machine (note_sequences.decode_note_event, mt3/note_sequences.py:284-387) keeps no such link.
+ *   [j][0]  index INTO h_tokens of the PITCH or DRUM token whose event created note j: the onset that entered the
+ *           active notes (for a note carried over segments it lies in an earlier segment), or, for drums and the
+ *           onsets-only spec, the token that emitted the note.
+ *   [j][1]  index of the token that ended it: a PITCH token at velocity 0, the PITCH token of a re-onset, or the TIE
+ *           token that closed a tie section in which the note was not declared; -1 where no token ended it (notes
+ *           flushed at the end, the default durations of drums and onsets-only notes). */
+int mt3_notes_decode_traced(const mt3_codec* c, int32_t spec, int32_t n_segments, const int32_t* h_tokens,
+                            const int64_t* h_seg_offsets, const double* h_start_times,
+                            const int32_t* h_has_max_time, const double* h_max_times,
+                            mt3_note* h_notes, int64_t notes_capacity, int64_t* n_notes,
+                            int64_t* invalid_events, int64_t* dropped_events, double* total_time,
+                            int64_t* h_note_tokens /* [notes_capacity][2] */);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,7 @@ SIGNATURES = {
                                               C.POINTER(TranscribeStats), _P]),
     "mt3_engine_decode_forced": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_engine_score": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "mt3_engine_score_segments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_status": (C.c_int, [_P, C.c_int32]),
     "mt3_debug_engine_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mt3_debug_engine_transcribe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
@@ -110,6 +111,7 @@ SIGNATURES = {
     "mt3_debug_engine_poison_caches": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "mt3_debug_engine_set_eos_schedule": (C.c_int, [_P, _P, C.c_int32]),
     "mt3_ids_to_tokens": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mt3_op_score_token_stats": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_op_gemm": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                               C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_gemm_ex": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
@@ -141,6 +143,9 @@ SIGNATURES = {
     "mt3_notes_decode": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64,
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]),
+    "mt3_notes_decode_traced": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_double), _P]),
 }
 
 _lib = None

@@ -2630,9 +2630,12 @@ static int ensure_score_planes(mt3_engine* e, hipStream_t s) {
   return MT3_OK;
 }
 
-static int score_impl(mt3_engine* e, int32_t batch, int32_t length, const int32_t* d_targets,
+// The prefill and the reduction of `batch` segments whose cross-K/V sit in cache rows row0 .. row0 + batch - 1 of the
+// last encoder pass; the caller arrays start at the first of them.  d_top1_ids / d_top1_scores (either): the reduction
+// is launch_score_stats instead of launch_score_reduce (same token and sequence scores)
+static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0, const int32_t* d_targets,
                       const int32_t* d_decoder_inputs, const float* d_weights, float* d_sequence_scores,
-                      float* d_token_scores, float* d_logits, hipStream_t s) {
+                      float* d_token_scores, int32_t* d_top1_ids, float* d_top1_scores, float* d_logits, hipStream_t s) {
   const mt3_engine_config& c = e->cfg;
   const int dt = c.compute_dtype, emb = c.emb_dim, hd = e->HD(), H = c.num_heads, T = c.input_length, V = c.vocab_size;
   const int Lp = (length + 63) / 64 * 64;
@@ -2694,13 +2697,13 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, const int32_
       MT3_TRY(resid(e->sc_attn, L.wo, L.wo_p, hd));
       MT3_TRY(normed(L.wq_x, L.wq_x_p, e->sc_q, hd, hd, MT3_EPI_STORE));
       {
-        // the cross K/V cache of the encoded batch: [2][cur_batch][H][T][64]; the chunk's segments start at row seg0
+        // the cross K/V cache of the encoded batch: [2][cur_batch][H][T][64]; the chunk's segments start at row row0 + seg0
         const size_t head = static_cast<size_t>(T) * 64;
         mt3k::ScoreAttnArgs a{};
         a.q = e->sc_q;
         a.q_stride = hd;
-        a.k = static_cast<const char*>(L.cross_kv) + static_cast<size_t>(seg0) * H * head * es;
-        a.v = static_cast<const char*>(L.cross_kv) + (static_cast<size_t>(e->cur_batch) + seg0) * H * head * es;
+        a.k = static_cast<const char*>(L.cross_kv) + static_cast<size_t>(row0 + seg0) * H * head * es;
+        a.v = static_cast<const char*>(L.cross_kv) + (static_cast<size_t>(e->cur_batch) + row0 + seg0) * H * head * es;
         a.kv_stride = 64;
         a.kv_bstride = static_cast<long long>(H) * head;
         a.kv_hstride = static_cast<long long>(head);
@@ -2721,7 +2724,8 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, const int32_
     {
       mt3k::ScoreReduceArgs a{e->sc_logits, e->sc_tgt, d_weights, e->sc_tok, d_token_scores, d_sequence_scores,
                               M, Lp, length, seg0, V};
-      MT3_TRY(mt3k::launch_score_reduce(a, s));
+      if (d_top1_ids || d_top1_scores) MT3_TRY(mt3k::launch_score_stats(mt3k::ScoreStatsArgs{a, d_top1_ids, d_top1_scores}, s));
+      else MT3_TRY(mt3k::launch_score_reduce(a, s));
     }
     if (d_logits) {
       const size_t row = static_cast<size_t>(length) * V * 4;
@@ -2748,8 +2752,46 @@ int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
   if (batch <= 0 || batch > e->cur_batch)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: batch must be in 1 .. the batch of the preceding encode");
-  return score_impl(e, batch, length, d_targets, d_decoder_inputs, d_weights, d_sequence_scores, d_token_scores, d_logits,
-                    static_cast<hipStream_t>(stream));
+  return score_impl(e, batch, length, 0, d_targets, d_decoder_inputs, d_weights, d_sequence_scores, d_token_scores, nullptr,
+                    nullptr, d_logits, static_cast<hipStream_t>(stream));
+}
+
+int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t length,
+                              const int32_t* d_targets, float* d_sequence_scores, float* d_token_scores,
+                              int32_t* d_top1_ids, float* d_top1_scores, void* stream) {
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: null engine");
+  if (!d_inputs || !d_targets || !d_sequence_scores)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: null inputs, targets or sequence scores");
+  if (n_segments < 1) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: n_segments must be >= 1");
+  if (length < 1 || length > e->cfg.max_decode_len)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: length must be in 1 .. max_decode_len");
+  if (e->kv_fp8)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: engines with e4m3 K/V caches (kv_cache_dtype MT3_FP8_E4M3) cannot score");
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: engine not finalized");
+  if (e->pending.active)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+  const mt3_engine_config& c = e->cfg;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t seg_floats = static_cast<size_t>(c.input_length) * c.input_depth;
+  // the chunks and their padding are those of the staging passes of mt3_engine_transcribe (feed.h): in bf16 a short last
+  // chunk is encoded behind the `pad` segments in front of it, so that its pass takes the tiles of a full one
+  const int min_batch = c.compute_dtype == MT3_BF16 ? std::min(c.max_batch, kStageMinBatch) : 0;
+  Feed feed;
+  feed.n_total = n_segments;
+  int chunks = 0;
+  for (int q = 0;; ++q) {
+    int first, n, pad;
+    if (!mt3feed::feed_claim(feed, q, c.max_batch, min_batch, &first, &n, &pad)) break;
+    MT3_TRY(encode_impl(e, d_inputs + static_cast<size_t>(first - pad) * seg_floats, pad + n, nullptr, CrossDst{}, s));
+    e->cur_batch = pad + n;
+    const size_t at = static_cast<size_t>(first) * length;
+    MT3_TRY(score_impl(e, n, length, pad, d_targets + at, nullptr, nullptr, d_sequence_scores + first,
+                       d_token_scores ? d_token_scores + at : nullptr, d_top1_ids ? d_top1_ids + at : nullptr,
+                       d_top1_scores ? d_top1_scores + at : nullptr, nullptr, s));
+    chunks += e->score_chunks;
+  }
+  e->score_chunks = chunks;
+  return MT3_OK;
 }
 
 // ---- mt3_hip_debug.h

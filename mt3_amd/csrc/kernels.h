@@ -367,6 +367,14 @@ struct ScoreReduceArgs {
   int rows, Lp, length, seg0, vocab;
 };
 int launch_score_reduce(const ScoreReduceArgs& a, hipStream_t s);
+// launch_score_reduce with the arg-max of every row next to its token score (score_token_stats_kernel, then the same
+// score_sum_kernel): token scores with launch_score_reduce's bits
+struct ScoreStatsArgs {
+  ScoreReduceArgs r;
+  int* top1_ids;          // caller [batch][length] or nullptr: arg-max of the row (lowest id on ties), 0 where target == 0
+  float* top1_scores;     // caller [batch][length] or nullptr: log_softmax(logits)[top1], 0 where target == 0
+};
+int launch_score_stats(const ScoreStatsArgs& a, hipStream_t s);
 // f32 [n] -> three bf16 planes (gemm_x6_kernel's weight operand)
 int launch_planes(const float* w, void* hi, void* mid, void* lo, size_t n, hipStream_t s);
 

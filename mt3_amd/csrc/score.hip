@@ -16,7 +16,8 @@
 //     visible key (a padding position at 0) writes a zero row.
 // (3) score_logprob_kernel: per row, log_softmax(logits)[target] * weight (0 where target == 0); the per-segment sum
 //     (score_sum_kernel) runs over the positions in a FIXED order in double, so a sequence score has the same bits on
-//     every run and in every batch.
+//     every run and in every batch.  score_token_stats_kernel (mt3_engine_score_segments with a top-1 output) is the
+//     same reduction with the row's arg-max (lowest id on ties) and its log-probability next to the token score.
 // (4) planes_kernel: an f32 matrix as the three bf16 planes of gemm_x6_kernel (hi = rne(w), mid = rne(w - hi), lo =
 //     rne(w - hi - mid)), the same split upload_planes makes on the host, for the decoder matrices the f32 engine's
 //     encoder-sized tile needs only when it scores.
@@ -307,6 +308,89 @@ int launch_score_reduce(const ScoreReduceArgs& a, hipStream_t s) {
   return MT3_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------- token statistics
+// (value, id) pairs: the larger value wins, the LOWER id on equal values (lax.top_k's tie rule, as the beam kernels rank).
+// The rule is symmetric, so after the butterfly every lane of a wave holds the same pair; the four waves are then
+// combined in the order 0, 1, 2, 3.  The value that comes out is the one block_reduce<float>(.., true) finds.
+__device__ __forceinline__ void argmax_take(float& v, int& id, float u, int uid) {
+  const bool take = u > v || (u == v && uid < id);
+  v = take ? u : v;
+  id = take ? uid : id;
+}
+
+__device__ __forceinline__ void block_argmax(float& v, int& id, float* red_v, int* red_i) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const float u = __shfl_xor(v, off);
+    const int uid = __shfl_xor(id, off);
+    argmax_take(v, id, u, uid);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) {
+    red_v[wave] = v;
+    red_i[wave] = id;
+  }
+  __syncthreads();
+  v = red_v[0];
+  id = red_i[0];
+  for (int w = 1; w < 4; ++w) argmax_take(v, id, red_v[w], red_i[w]);
+}
+
+// score_logprob_kernel plus the row's arg-max and its log-probability (mt3_engine_score_segments with a top-1 output,
+// mt3_op_score_token_stats): the maximum and the sum of exp are reduced in score_logprob_kernel's order, so the token
+// score has its bits; the arg-max rides in the pass that finds the maximum.
+__global__ __launch_bounds__(256) void score_token_stats_kernel(ScoreStatsArgs s) {
+  __shared__ float redf[4];
+  __shared__ int redi[4];
+  const ScoreReduceArgs& a = s.r;
+  const int r = blockIdx.x, seg = r / a.Lp, t = r % a.Lp;
+  if (t >= a.length) return;                      // block-uniform
+  int tgt = a.tgt_pad[r];
+  tgt = tgt < 0 ? 0 : (tgt >= a.vocab ? a.vocab - 1 : tgt);      // (the engine's rows arrive clamped by score_embed_kernel)
+  float sc = 0.f, top = 0.f;
+  int top_id = 0;
+  if (tgt != 0) {
+    const float* x = a.logits + static_cast<size_t>(r) * a.vocab;
+    float mx = -3.0e38f;
+    int id = 0x7fffffff;                          // nothing above -3e38 seen yet
+    for (int i = threadIdx.x; i < a.vocab; i += 256) {
+      const float v = x[i];
+      if (v > mx) {                               // ascending i: the first of equal values stays
+        mx = v;
+        id = i;
+      }
+    }
+    block_argmax(mx, id, redf, redi);
+    top_id = id < a.vocab ? id : 0;
+    float se = 0.f;
+    for (int i = threadIdx.x; i < a.vocab; i += 256) se += expf(x[i] - mx);
+    se = block_reduce<float>(se, redf, false);
+    const float w = a.weights ? a.weights[static_cast<size_t>(a.seg0 + seg) * a.length + t] : 1.f;
+    const float lse = logf(se);
+    sc = (x[tgt] - mx - lse) * w;
+    top = x[top_id] - mx - lse;
+  }
+  if (threadIdx.x == 0) {
+    const size_t o = static_cast<size_t>(a.seg0 + seg) * a.length + t;
+    if (a.tok_pad) a.tok_pad[r] = sc;
+    if (a.token_scores) a.token_scores[o] = sc;
+    if (s.top1_ids) s.top1_ids[o] = top_id;
+    if (s.top1_scores) s.top1_scores[o] = top;
+  }
+}
+
+int launch_score_stats(const ScoreStatsArgs& s, hipStream_t st) {
+  const ScoreReduceArgs& a = s.r;
+  if (!a.logits || !a.tgt_pad || !a.tok_pad || !a.seq_scores || a.Lp % 64 || a.length <= 0 || a.length > a.Lp ||
+      a.rows % a.Lp || a.vocab < 2)
+    return mt3::fail(MT3_ERR_INVALID, "score_stats: bad arguments");
+  hipLaunchKernelGGL(score_token_stats_kernel, dim3(a.rows), dim3(256), 0, st, s);
+  MT3_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(score_sum_kernel, dim3(a.rows / a.Lp), dim3(256), 0, st, a);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------ planes
 __global__ __launch_bounds__(256) void planes_kernel(const float* __restrict__ w, __bf16* __restrict__ hi,
                                                      __bf16* __restrict__ mid, __bf16* __restrict__ lo, size_t n) {
@@ -331,3 +415,18 @@ int launch_planes(const float* w, void* hi, void* mid, void* lo, size_t n, hipSt
 }
 
 }  // namespace mt3k
+
+// ---- include/mt3_hip.h: the statistics kernel on scripted logits (every row a "segment" of one position)
+extern "C" int mt3_op_score_token_stats(const float* d_logits, const int32_t* d_targets, const float* d_weights,
+                                        int32_t rows, int32_t vocab, float* d_token_scores, int32_t* d_top1_ids,
+                                        float* d_top1_scores, void* stream) {
+  if (!d_logits || !d_targets) return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_token_stats: null logits or targets");
+  if (rows < 1 || vocab < 2) return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_token_stats: rows must be >= 1 and vocab >= 2");
+  mt3k::ScoreStatsArgs s{};
+  s.r = mt3k::ScoreReduceArgs{d_logits, d_targets, d_weights, nullptr, d_token_scores, nullptr, rows, 1, 1, 0, vocab};
+  s.top1_ids = d_top1_ids;
+  s.top1_scores = d_top1_scores;
+  hipLaunchKernelGGL(mt3k::score_token_stats_kernel, dim3(rows), dim3(256), 0, static_cast<hipStream_t>(stream), s);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}

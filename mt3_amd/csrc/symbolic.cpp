@@ -15,6 +15,7 @@
 // reference's own expressions (start + steps / steps_per_second), so they are
 // bit-identical; build with -ffp-contract=off.
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <numeric>
@@ -83,11 +84,12 @@ struct Active {
   int pitch, program;
   double onset;
   int velocity;
+  int64_t token;      // index of the onset's token in the caller's flat buffer (mt3_notes_decode_traced)
 };
 
 class NoteMachine {
  public:
-  NoteMachine(int spec, const CodecTable& codec) : spec_(spec), codec_(codec) {}
+  NoteMachine(int spec, const CodecTable& codec, bool keep_trace) : spec_(spec), codec_(codec), keep_trace_(keep_trace) {}
 
   void begin_segment() {
     if (spec_ == MT3_SPEC_TIES) {  // begin_tied_pitches_section
@@ -97,7 +99,8 @@ class NoteMachine {
   }
 
   // returns false where the reference raises ValueError (caller counts it invalid)
-  bool consume(double time, int type, int value) {
+  // at_token: the index of the event in the caller's flat token buffer (kept with the notes it creates / ends)
+  bool consume(double time, int type, int value, int64_t at_token) {
     if (spec_ == MT3_SPEC_ONSETS) {
       if (type != MT3_EV_PITCH) return false;
       mt3_note n{};
@@ -106,6 +109,7 @@ class NoteMachine {
       n.pitch = value;
       n.velocity = kDefaultVelocity;
       notes.push_back(n);
+      if (keep_trace_) trace.push_back({at_token, -1});
       total_time = std::max(total_time, time + kDefaultNoteDuration);
       return true;
     }
@@ -124,20 +128,20 @@ class NoteMachine {
           if (at < 0) return false;
           const Active a = active_[at];
           active_.erase(active_.begin() + at);
-          emit(a.onset, time, value, a.velocity, prog, false);
+          emit(a.onset, time, value, a.velocity, prog, false, a.token, at_token);
         } else {
           if (at >= 0) {  // re-onset of a sounding note: end it, start a new one
             const Active a = active_[at];
             active_.erase(active_.begin() + at);
-            emit(a.onset, time, value, a.velocity, prog, false);
+            emit(a.onset, time, value, a.velocity, prog, false, a.token, at_token);
           }
-          active_.push_back(Active{value, prog, time, current_velocity_});
+          active_.push_back(Active{value, prog, time, current_velocity_, at_token});
         }
         return true;
       }
       case MT3_EV_DRUM:
         if (current_velocity_ == 0) return false;
-        emit(time, time + kDefaultNoteDuration, value, current_velocity_, 0, true);
+        emit(time, time + kDefaultNoteDuration, value, current_velocity_, 0, true, at_token, -1);
         return true;
       case MT3_EV_VELOCITY:
         // vocabularies.bin_to_velocity: int(127 * bin / num_bins), 0 stays 0
@@ -156,7 +160,7 @@ class NoteMachine {
           bool is_tied = false;
           for (const auto& t : tied_) is_tied |= (t.first == a.pitch && t.second == a.program);
           if (is_tied) keep.push_back(a);
-          else emit(a.onset, current_time_, a.pitch, a.velocity, a.program, false);
+          else emit(a.onset, current_time_, a.pitch, a.velocity, a.program, false, a.token, at_token);
         }
         active_.swap(keep);
         in_tie_section_ = false;
@@ -170,7 +174,7 @@ class NoteMachine {
   void flush() {
     if (spec_ == MT3_SPEC_ONSETS) return;  // NoteOnsetEncodingSpec: flush = identity
     for (const Active& a : active_) current_time_ = std::max(current_time_, a.onset + kMinNoteDuration);
-    for (const Active& a : active_) emit(a.onset, current_time_, a.pitch, a.velocity, a.program, false);
+    for (const Active& a : active_) emit(a.onset, current_time_, a.pitch, a.velocity, a.program, false, a.token, -1);
     active_.clear();
     // assign_instruments: order of first appearance of a program, skipping 9
     std::vector<std::pair<int, int>> seen;
@@ -189,6 +193,7 @@ class NoteMachine {
   }
 
   std::vector<mt3_note> notes;
+  std::vector<std::array<int64_t, 2>> trace;      // keep_trace: per note, the tokens that started / ended it (-1: none)
   double total_time = 0.0;
 
  private:
@@ -197,7 +202,8 @@ class NoteMachine {
       if (active_[i].pitch == pitch && active_[i].program == program) return static_cast<int>(i);
     return -1;
   }
-  void emit(double start, double end, int pitch, int velocity, int program, bool drum) {
+  void emit(double start, double end, int pitch, int velocity, int program, bool drum, int64_t on_token,
+            int64_t end_token) {
     end = std::max(end, start + kMinNoteDuration);
     mt3_note n{};
     n.start_time = start;
@@ -207,11 +213,13 @@ class NoteMachine {
     n.program = program;
     n.is_drum = drum ? 1 : 0;
     notes.push_back(n);
+    if (keep_trace_) trace.push_back({on_token, end_token});
     total_time = std::max(total_time, end);
   }
 
   int spec_;
   const CodecTable& codec_;
+  bool keep_trace_;
   double current_time_ = 0.0;
   int current_velocity_ = kDefaultVelocity;
   int current_program_ = 0;
@@ -267,17 +275,19 @@ int mt3_codec_encode_event(const mt3_codec* c, int32_t type, int32_t value, int3
   return MT3_OK;
 }
 
-int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const int32_t* h_tokens,
-                     const int64_t* h_seg_offsets, const double* h_start_times,
-                     const int32_t* h_has_max_time, const double* h_max_times,
-                     mt3_note* h_notes, int64_t notes_capacity, int64_t* n_notes,
-                     int64_t* invalid_events, int64_t* dropped_events, double* total_time) {
+// the machine behind mt3_notes_decode (h_note_tokens == nullptr) and mt3_notes_decode_traced; `who` names the entry
+// point in its error messages
+static int notes_decode_impl(const std::string& who, const mt3_codec* c, int32_t spec, int32_t n_segments,
+                             const int32_t* h_tokens, const int64_t* h_seg_offsets, const double* h_start_times,
+                             const int32_t* h_has_max_time, const double* h_max_times, mt3_note* h_notes,
+                             int64_t notes_capacity, int64_t* n_notes, int64_t* invalid_events, int64_t* dropped_events,
+                             double* total_time, int64_t* h_note_tokens) {
   CodecTable codec(c);
-  if (!codec.ok) return mt3::fail(MT3_ERR_INVALID, "mt3_notes_decode: malformed codec");
+  if (!codec.ok) return mt3::fail(MT3_ERR_INVALID, who + ": malformed codec");
   if (spec < MT3_SPEC_ONSETS || spec > MT3_SPEC_TIES || n_segments < 0 || !n_notes)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_notes_decode: bad spec / arguments");
+    return mt3::fail(MT3_ERR_INVALID, who + ": bad spec / arguments");
   if (n_segments > 0 && (!h_seg_offsets || !h_start_times))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_notes_decode: null segment arrays");
+    return mt3::fail(MT3_ERR_INVALID, who + ": null segment arrays");
 
   // sorted(predictions, key=start_time): stable
   std::vector<int> order(n_segments);
@@ -285,7 +295,7 @@ int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const
   std::stable_sort(order.begin(), order.end(),
                    [&](int a, int b) { return h_start_times[a] < h_start_times[b]; });
 
-  NoteMachine m(spec, codec);
+  NoteMachine m(spec, codec, h_note_tokens != nullptr);
   int64_t invalid = 0, dropped = 0;
   for (int k = 0; k < n_segments; ++k) {
     const int s = order[k];
@@ -301,7 +311,7 @@ int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const
     }
     const double start = h_start_times[s];
     const int64_t b = h_seg_offsets[s], e = h_seg_offsets[s + 1];
-    if (e < b) return mt3::fail(MT3_ERR_INVALID, "mt3_notes_decode: seg_offsets not monotone");
+    if (e < b) return mt3::fail(MT3_ERR_INVALID, who + ": seg_offsets not monotone");
     int64_t steps = 0;
     double now = start;
     for (int64_t i = b; i < e; ++i) {
@@ -314,7 +324,7 @@ int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const
         if (has_max && max_time != 0.0 && now > max_time) { dropped += e - i; break; }
       } else {
         steps = 0;
-        if (!m.consume(now, type, value)) ++invalid;
+        if (!m.consume(now, type, value, i)) ++invalid;
       }
     }
   }
@@ -323,12 +333,34 @@ int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const
   if (invalid_events) *invalid_events = invalid;
   if (dropped_events) *dropped_events = dropped;
   if (total_time) *total_time = m.total_time;
-  if (*n_notes > notes_capacity) return mt3::fail(MT3_ERR_CAPACITY, "mt3_notes_decode: notes buffer too small");
+  if (*n_notes > notes_capacity) return mt3::fail(MT3_ERR_CAPACITY, who + ": notes buffer too small");
   if (*n_notes > 0) {
-    if (!h_notes) return mt3::fail(MT3_ERR_INVALID, "mt3_notes_decode: null notes buffer");
+    if (!h_notes) return mt3::fail(MT3_ERR_INVALID, who + ": null notes buffer");
     std::memcpy(h_notes, m.notes.data(), sizeof(mt3_note) * m.notes.size());
+    if (h_note_tokens) std::memcpy(h_note_tokens, m.trace.data(), sizeof(int64_t) * 2 * m.trace.size());
   }
   return MT3_OK;
+}
+
+
+int mt3_notes_decode(const mt3_codec* c, int32_t spec, int32_t n_segments, const int32_t* h_tokens,
+                     const int64_t* h_seg_offsets, const double* h_start_times,
+                     const int32_t* h_has_max_time, const double* h_max_times,
+                     mt3_note* h_notes, int64_t notes_capacity, int64_t* n_notes,
+                     int64_t* invalid_events, int64_t* dropped_events, double* total_time) {
+  return notes_decode_impl("mt3_notes_decode", c, spec, n_segments, h_tokens, h_seg_offsets, h_start_times, h_has_max_time,
+                           h_max_times, h_notes, notes_capacity, n_notes, invalid_events, dropped_events, total_time, nullptr);
+}
+
+int mt3_notes_decode_traced(const mt3_codec* c, int32_t spec, int32_t n_segments, const int32_t* h_tokens,
+                            const int64_t* h_seg_offsets, const double* h_start_times,
+                            const int32_t* h_has_max_time, const double* h_max_times,
+                            mt3_note* h_notes, int64_t notes_capacity, int64_t* n_notes,
+                            int64_t* invalid_events, int64_t* dropped_events, double* total_time,
+                            int64_t* h_note_tokens) {
+  return notes_decode_impl("mt3_notes_decode_traced", c, spec, n_segments, h_tokens, h_seg_offsets, h_start_times,
+                           h_has_max_time, h_max_times, h_notes, notes_capacity, n_notes, invalid_events, dropped_events,
+                           total_time, h_note_tokens);
 }
 
 }  // extern "C"

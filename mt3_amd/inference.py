@@ -177,29 +177,32 @@ class InferenceModel(object):
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
         """batch['encoder_input_tokens']: f32 [B, T, 512] (numpy or CUDA tensor) -> int32 [B, 1024]
         with -1 from EOS on and -2 for invalid ids (vocabulary.decode_tf)."""
+        return self.vocabulary.decode_tf(self._predict_ids(batch)).cpu().numpy()
+
+    def _predict_ids(self, batch: Dict[str, Any]):
+        """the engine's side of `predict_tokens`: the raw vocabulary ids, int32 CUDA [B, 1024]"""
         import torch
         x = batch["encoder_input_tokens"]
         x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, np.float32))
         x = x.cuda()
         beam1 = self.decoding == "beam1"
         if self.decoding == "beam":
-            return self._predict_tokens_beam(x)
+            return self._predict_ids_beam(x)
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: finished rows restart on the job's next segments
             self._ensure_slots(x.shape[0])
             self.rows_per_engine_call = [int(x.shape[0])]
-            return self.vocabulary.decode_tf(self.model.transcribe(x, beam1=beam1)).cpu().numpy()
+            return self.model.transcribe(x, beam1=beam1)
         out = []
         step = min(self.batch_size, self.model.max_batch)
         self.rows_per_engine_call = []
         for s in range(0, x.shape[0], step):
             self.model.encode(x[s:s + step])
-            ids = self.model.decode(early_exit=self.early_exit, beam1=beam1)
-            out.append(self.vocabulary.decode_tf(ids))
+            out.append(self.model.decode(early_exit=self.early_exit, beam1=beam1))
             self.rows_per_engine_call.append(int(min(step, x.shape[0] - s)))
-        return torch.cat(out, 0).cpu().numpy()
+        return torch.cat(out, 0)
 
-    def _predict_tokens_beam(self, x):
+    def _predict_ids_beam(self, x):
         """decoding='beam', k engine rows (beams) per segment: one in-flight batched call (schedule='refill'), or
         batch-synchronous chunks of max_slots // k segments (schedule='batch')"""
         import torch
@@ -209,16 +212,16 @@ class InferenceModel(object):
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: a closed element restarts on the job's next segment
             self.rows_per_engine_call = [int(x.shape[0]) * k]
-            return self.vocabulary.decode_tf(self.model.transcribe(x, num_beams=k)).cpu().numpy()
+            return self.model.transcribe(x, num_beams=k)
         chunk = max(1, min(chunk, self.model.max_batch // k))
         out = []
         self.rows_per_engine_call = []
         for s in range(0, x.shape[0], chunk):
             self.model.encode(x[s:s + chunk], num_beams=k)
             ids, _ = self.model.decode_beams(k, early_exit=self.early_exit)
-            out.append(self.vocabulary.decode_tf(ids))
+            out.append(ids)
             self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
-        return torch.cat(out, 0).cpu().numpy()
+        return torch.cat(out, 0)
 
     def __call__(self, audio, sample_rate: int = SAMPLE_RATE):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
@@ -232,17 +235,67 @@ class InferenceModel(object):
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
         return self._transcribe_examples(self._wav_examples(wav_data))
 
-    def _transcribe_examples(self, examples):
-        """the examples of one file, their log-mel in _logmel_dev -> NoteSequence"""
+    def _transcribe_examples(self, examples, scored: bool = False):
+        """the examples of one file, their log-mel in _logmel_dev -> NoteSequence (scored: and the notes' scores)"""
         # the frontend kernel has already written the feature converter's form of every segment -- [T, 512] rows, 0.0
         # after a short last segment's frames (mt3/models.py:48-98 via models.convert_features) -- and it is still on the
         # device: no host round trip between preprocess and predict_tokens
         batch, self._logmel_dev = {"encoder_input_tokens": self._logmel_dev}, None
-        tokens = self.predict_tokens(batch)
+        if not scored:
+            tokens = self.predict_tokens(batch)
+            predictions = [self.postprocess(t, ex) for t, ex in zip(tokens, examples)]
+            result = metrics_utils.event_predictions_to_ns(predictions, codec=self.codec,
+                                                           encoding_spec=self.encoding_spec)
+            return result["est_ns"]
+        ids = self._predict_ids(batch)
+        tokens = self.vocabulary.decode_tf(ids).cpu().numpy()
         predictions = [self.postprocess(t, ex) for t, ex in zip(tokens, examples)]
-        result = metrics_utils.event_predictions_to_ns(predictions, codec=self.codec,
-                                                       encoding_spec=self.encoding_spec)
-        return result["est_ns"]
+        result = metrics_utils.event_predictions_to_ns_traced(predictions, codec=self.codec,
+                                                              encoding_spec=self.encoding_spec)
+        return result["est_ns"], self._note_scores(batch["encoder_input_tokens"], ids, result["note_tokens"])
+
+    def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE):
+        """`__call__` with a confidence for every note: (NoteSequence, scores).  The notes are those of `__call__` (same
+        decode: the model's `decoding` and `schedule`); afterwards the decoded id rows are scored teacher-forced in one
+        `Transformer.score_segments` call (ids after EOS are 0 = padding; length = the longest row) and each note is
+        linked to the tokens that made it (`metrics_utils.event_predictions_to_ns_traced`).  scores: float64 arrays
+        aligned with the NoteSequence's notes --
+          'onset_logprob'  log-probability of the PITCH / DRUM token that started the note
+          'end_logprob'    log-probability of the token that ended it; NaN where no token did (flushed notes, drums)
+          'onset_margin'   onset_logprob minus the log-probability of the model's best token at that position: 0 when
+                           the decoded token is the model's arg-max, negative otherwise
+          'note_tokens'    int64 [n_notes, 2, 2]: (segment, position) of the onset and the end token, (-1, -1) for none
+        Not available with e4m3 K/V caches (ValueError, as `score`)."""
+        self._refuse_e4m3("transcribe_scored")
+        return self._transcribe_examples(self._examples(audio, sample_rate), scored=True)
+
+    def transcribe_wav_scored(self, wav_data):
+        """The file-level form of `transcribe_scored`: `transcribe_wav` plus the notes' confidences."""
+        self._refuse_e4m3("transcribe_wav_scored")
+        return self._transcribe_examples(self._wav_examples(wav_data), scored=True)
+
+    def _refuse_e4m3(self, who):
+        if self.model_config.kv_dtype:
+            raise ValueError("%s() is not available with kv_dtype=%r: e4m3 K/V caches cannot score"
+                             % (who, self.model_config.kv_dtype))
+
+    def _note_scores(self, x, ids, note_tokens):
+        """x: the job's log-mel (CUDA); ids: its decoded rows int32 CUDA [N, 1024]; note_tokens [n_notes, 2, 2] ->
+        the scores dict of `transcribe_scored`"""
+        import torch
+        eos = (ids == self.vocabulary.eos_id).int()
+        ids = torch.where(torch.cumsum(eos, 1) - eos > 0, torch.zeros_like(ids), ids)      # 0 (padding) after the first EOS
+        used = (ids != 0).any(0).nonzero()
+        length = int(used.max()) + 1 if used.numel() else 1
+        _, tok, _, top = self.model.score_segments(x, ids[:, :length].contiguous(), return_token_scores=True,
+                                                   return_top1=True)
+        tok, top = tok.cpu().numpy().astype(np.float64), top.cpu().numpy().astype(np.float64)
+        seg, pos = note_tokens[:, :, 0], note_tokens[:, :, 1]
+        have = seg >= 0
+        at = (np.where(have, seg, 0), np.where(have, pos, 0))
+        logp = np.where(have, tok[at], np.nan)
+        return {"onset_logprob": logp[:, 0], "end_logprob": logp[:, 1],
+                "onset_margin": np.where(have[:, 0], tok[at][:, 0] - top[at][:, 0], np.nan), "note_tokens": note_tokens}
 
     def score(self, audio, targets, return_token_scores: bool = False, *, sample_rate: int = SAMPLE_RATE):
         """Teacher-forced scores of token rows for this audio (t5x score_batch; the reference's infer(mode='score')

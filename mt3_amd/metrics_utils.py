@@ -20,6 +20,12 @@ assert NOTE_DTYPE.itemsize == C.sizeof(_lib.NoteStruct)
 
 def _decode(codec, spec_id, flat, offs, start_times, max_times=None):
     """mt3_notes_decode on a flat token array: (notes as a NOTE_DTYPE array, invalid, dropped, total_time)"""
+    return _decode_full(codec, spec_id, flat, offs, start_times, max_times, False)[:4]
+
+
+def _decode_full(codec, spec_id, flat, offs, start_times, max_times, trace):
+    """always five items: `_decode`'s four and the trace -- with `trace` (mt3_notes_decode_traced) int64 [n_notes, 2], the
+    flat indices of each note's onset and end tokens; None otherwise (mt3_notes_decode)"""
     lib = _lib.load()
     n = len(offs) - 1
     flat = np.ascontiguousarray(flat, np.int32) if n and offs[-1] else np.zeros(1, np.int32)
@@ -33,10 +39,14 @@ def _decode(codec, spec_id, flat, offs, start_times, max_times=None):
     cap = max(64, int(offs[-1]) + 8)          # a token emits at most one note
     notes = np.empty(cap, NOTE_DTYPE)
     n_notes, inv, drop, total = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
-    _lib.check(lib.mt3_notes_decode(C.byref(codec.desc), spec_id, n, flat.ctypes.data, offs.ctypes.data,
-                                    st.ctypes.data, has_p, mt_p, C.c_void_p(notes.ctypes.data), cap, C.byref(n_notes),
-                                    C.byref(inv), C.byref(drop), C.byref(total)))
-    return notes[: n_notes.value], inv.value, drop.value, total.value
+    args = (C.byref(codec.desc), spec_id, n, flat.ctypes.data, offs.ctypes.data, st.ctypes.data, has_p, mt_p,
+            C.c_void_p(notes.ctypes.data), cap, C.byref(n_notes), C.byref(inv), C.byref(drop), C.byref(total))
+    if not trace:
+        _lib.check(lib.mt3_notes_decode(*args))
+        return notes[: n_notes.value], inv.value, drop.value, total.value, None
+    note_tokens = np.full((cap, 2), -1, np.int64)
+    _lib.check(lib.mt3_notes_decode_traced(*args, C.c_void_p(note_tokens.ctypes.data)))
+    return notes[: n_notes.value], inv.value, drop.value, total.value, note_tokens[: n_notes.value]
 
 
 def decode_token_rows(codec, encoding_spec, rows, start_times, lengths=None):
@@ -67,21 +77,47 @@ def note_sequence_from_records(rec, total_time: float):
 
 
 def _run(codec, spec_id, tokens_list, start_times, max_times=None):
+    """(NoteSequence, invalid events, dropped events) of the segments"""
+    return _run_full(codec, spec_id, tokens_list, start_times, max_times, False)[:3]
+
+
+def _run_full(codec, spec_id, tokens_list, start_times, max_times, trace):
+    """always four items: `_run`'s three and, with `trace`, int64 [n_notes, 2, 2] (segment, position) pairs of each note's
+    onset and end token ((-1, -1): none); None otherwise"""
     n = len(tokens_list)
     toks = [np.asarray(t, np.int32).reshape(-1) for t in tokens_list]
     offs = np.zeros(n + 1, np.int64)
     if n:
         np.cumsum([t.size for t in toks], out=offs[1:])
     flat = np.concatenate(toks) if n and offs[-1] else np.zeros(1, np.int32)
-    rec, inv, drop, total = _decode(codec, spec_id, flat, offs, start_times, max_times)
-    return note_sequence_from_records(rec, total), inv, drop
+    rec, inv, drop, total, flat_idx = _decode_full(codec, spec_id, flat, offs, start_times, max_times, trace)
+    if flat_idx is None:
+        return note_sequence_from_records(rec, total), inv, drop, None
+    # flat index -> (segment, position in that segment's row); -1 -> (-1, -1)
+    seg = np.searchsorted(offs, flat_idx, side="right") - 1
+    note_tokens = np.stack([seg, flat_idx - offs[np.clip(seg, 0, max(n - 1, 0))]], axis=-1).astype(np.int64)
+    note_tokens[flat_idx < 0] = -1
+    return note_sequence_from_records(rec, total), inv, drop, note_tokens
 
 
 def event_predictions_to_ns(predictions: Sequence[Mapping[str, Any]], codec: event_codec.Codec,
                             encoding_spec: note_sequences.NoteEncodingSpecType) -> Mapping[str, Any]:
     """predictions: dicts with 'est_tokens', 'start_time' (and optionally 'raw_inputs')."""
-    ns, inv, drop = _run(codec, encoding_spec.spec_id, [p["est_tokens"] for p in predictions],
-                         [p["start_time"] for p in predictions])
+    return _predictions_to_ns(predictions, codec, encoding_spec, False)
+
+
+def event_predictions_to_ns_traced(predictions: Sequence[Mapping[str, Any]], codec: event_codec.Codec,
+                                   encoding_spec: note_sequences.NoteEncodingSpecType) -> Mapping[str, Any]:
+    """`event_predictions_to_ns` plus 'note_tokens': int64 [n_notes, 2, 2], for each note of est_ns.notes the (index into
+    `predictions`, position in that prediction's 'est_tokens') of the token that started it ([:, 0]: the PITCH / DRUM
+    onset, possibly in an earlier segment) and of the token that ended it ([:, 1]: a note-off PITCH, a re-onset or the
+    TIE that closed an undeclared note; (-1, -1) where no token did) -- mt3_notes_decode_traced (include/mt3_hip.h)."""
+    return _predictions_to_ns(predictions, codec, encoding_spec, True)
+
+
+def _predictions_to_ns(predictions, codec, encoding_spec, trace):
+    ns, inv, drop, note_tokens = _run_full(codec, encoding_spec.spec_id, [p["est_tokens"] for p in predictions],
+                                           [p["start_time"] for p in predictions], None, trace)
     order = sorted(range(len(predictions)), key=lambda i: predictions[i]["start_time"])
     raws = [np.asarray(predictions[i].get("raw_inputs", [])) for i in order]
     raws = [r for r in raws if r.size]
@@ -91,6 +127,7 @@ def event_predictions_to_ns(predictions: Sequence[Mapping[str, Any]], codec: eve
         "est_ns": ns,
         "est_invalid_events": inv,
         "est_dropped_events": drop,
+        **({"note_tokens": note_tokens} if trace else {}),
     }
 
 

@@ -430,6 +430,45 @@ class Transformer:
             return seq
         return (seq,) + ((tok,) if return_token_scores else ()) + ((logits,) if return_logits else ())
 
+    def score_segments(self, x, targets, return_token_scores: bool = False, return_top1: bool = False):
+        """mt3_engine_score_segments: `encode` + `score` over ANY number of segments in chunks of `max_batch`, with the
+        statistics a note confidence is made of (include/mt3_hip.h states the contract).  x: CUDA f32 [N, T, input_depth]
+        log-mel; targets: int32 [N, 1 .. L] vocabulary ids (0 = padding), CUDA or host; decoder inputs are
+        shift_right(targets), weights target > 0.  Returns the f32 CUDA sequence scores [N], or a tuple (scores,
+        token_scores [N, length] if asked, top1_ids int32 [N, length] and top1_scores [N, length] if `return_top1`):
+        the arg-max of each position's logits (lowest id on ties) and its log-probability.  Leaves the engine encoded
+        with the last chunk, as a loop of `encode` calls would."""
+        import torch
+        if self.config.kv_dtype:
+            raise ValueError("scoring is not available with kv_dtype=%r (e4m3 cross caches are out of scope)"
+                             % (self.config.kv_dtype,))
+        if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] != self.input_length or x.shape[2] != self.config.input_depth:
+            raise ValueError(f"expected [N >= 1, {self.input_length}, {self.config.input_depth}], got {tuple(x.shape)}")
+        x = x.to(device="cuda", dtype=torch.float32).contiguous()
+        N = int(x.shape[0])
+        tgt = torch.as_tensor(targets)
+        if tgt.dim() != 2 or tgt.shape[0] != N or tgt.shape[1] < 1 or tgt.shape[1] > self.max_decode_length:
+            raise ValueError(f"targets must be [N={N}, 1 .. {self.max_decode_length}], got {tuple(tgt.shape)}")
+        n = int(tgt.shape[1])
+        tgt = tgt.to(device="cuda", dtype=torch.int32).contiguous()
+        if int(tgt.min()) < 0 or int(tgt.max()) >= self.config.vocab_size:
+            raise ValueError("target ids must lie in [0, vocab_size)")
+        seq = torch.empty((N,), device="cuda", dtype=torch.float32)
+        tok = torch.empty((N, n), device="cuda", dtype=torch.float32) if return_token_scores else None
+        top_id = torch.empty((N, n), device="cuda", dtype=torch.int32) if return_top1 else None
+        top_sc = torch.empty((N, n), device="cuda", dtype=torch.float32) if return_top1 else None
+        ptr = (lambda t: t.data_ptr() if t is not None else None)
+        _lib.check(self._lib.mt3_engine_score_segments(self._h, x.data_ptr(), N, n, tgt.data_ptr(), ptr(seq), ptr(tok),
+                                                       ptr(top_id), ptr(top_sc), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.current_stream().synchronize()          # the converted inputs must outlive the work the call enqueued
+        last = N - (N - 1) // self.max_batch * self.max_batch          # segments of the last chunk
+        pad8 = self.config.dtype == "bfloat16" and N > self.max_batch  # (bf16: encoded in a pass of at least 8 rows)
+        self._batch = max(last, min(8, self.max_batch)) if pad8 else last
+        self._encoded_beams = 1
+        if not (return_token_scores or return_top1):
+            return seq
+        return (seq,) + ((tok,) if return_token_scores else ()) + ((top_id, top_sc) if return_top1 else ())
+
     def debug_set_score_chunk(self, segments: int = 0):
         """mt3_debug_engine_set_score_chunk: segments per chunk of `score` (0: the workspace default)."""
         _lib.check(self._lib.mt3_debug_engine_set_score_chunk(self._h, int(segments)))

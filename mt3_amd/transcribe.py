@@ -1,16 +1,22 @@
 """Command line: WAV files -> MIDI files (the notebook's upload / transcribe / download cells in one call).
 
     python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
-                                 [--decoding beam1|greedy|beam] [--num-beams K] IN.wav [IN2.wav ...] [-o OUT]
+                                 [--decoding beam1|greedy|beam] [--num-beams K] [--confidences]
+                                 IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
 engine as one job (`InferenceModel.transcribe_wavs`).  --checkpoint is handed to `InferenceModel` as it is: a t5x
 checkpoint directory, a flat or compact `.npz`, or `random:<seed>`.  --decoding beam runs t5x beam_search with
---num-beams K decodes (1 .. 8) per segment (`InferenceModel(decoding="beam", num_beams=K)`).
+--num-beams K decodes (1 .. 8) per segment (`InferenceModel(decoding="beam", num_beams=K)`).  --confidences also writes
+NAME.confidence.json beside each NAME.mid: one record per note, in the NoteSequence's order, with the note's fields and
+`onset_logprob`, `end_logprob` (null where no token ended the note) and `onset_margin` of
+`InferenceModel.transcribe_wav_scored` (each file is then a job of its own: decode, then one scoring pass).
 """
 from __future__ import annotations
 
 import argparse
+import json
+import math
 import os
 import sys
 
@@ -25,6 +31,8 @@ def plan(argv=None):
     ap.add_argument("--decoding", default="beam1", choices=("beam1", "greedy", "beam"),
                     help="token selection: beam1 (default, the reference's), greedy, or beam (k-beam search, see --num-beams)")
     ap.add_argument("--num-beams", type=int, default=4, metavar="K", help="decodes per segment with --decoding beam (1 .. 8)")
+    ap.add_argument("--confidences", action="store_true",
+                    help="also write NAME.confidence.json beside each NAME.mid: per-note token log-probabilities")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -53,7 +61,11 @@ def main(argv=None) -> int:
     try:
         model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype, decoding=args.decoding,
                                          num_beams=args.num_beams)
-        sequences = model.transcribe_wavs(args.inputs)
+        if args.confidences:
+            scored = [model.transcribe_wav_scored(path) for path in args.inputs]
+            sequences, scores = [ns for ns, _ in scored], [sc for _, sc in scored]
+        else:
+            sequences, scores = model.transcribe_wavs(args.inputs), None
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -61,7 +73,24 @@ def main(argv=None) -> int:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         midi_io.note_sequence_to_midi_file(ns, path)
         print("%s: %d notes" % (path, len(ns.notes)))
+    for ns, sc, path in zip(sequences, scores or [], outputs):
+        with open(confidence_path(path), "w") as f:
+            json.dump(confidence_records(ns, sc), f, indent=1)
     return 0
+
+
+def confidence_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".confidence.json"
+
+
+def confidence_records(ns, scores):
+    """one JSON-ready record per note of `ns`, in its order: the note's fields and its three confidences (NaN -> None)"""
+    num = (lambda v: None if math.isnan(v) else float(v))
+    return [{"start_time": n.start_time, "end_time": n.end_time, "pitch": n.pitch, "velocity": n.velocity,
+             "program": n.program, "is_drum": bool(n.is_drum), "instrument": n.instrument,
+             "onset_logprob": num(scores["onset_logprob"][i]), "end_logprob": num(scores["end_logprob"][i]),
+             "onset_margin": num(scores["onset_margin"][i])}
+            for i, n in enumerate(ns.notes)]
 
 
 if __name__ == "__main__":
