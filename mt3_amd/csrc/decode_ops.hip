@@ -122,25 +122,43 @@ __device__ __forceinline__ void put_row_projection(const RowProj& rp, int b, int
   }
 }
 
-__global__ __launch_bounds__(128) void embed_kernel(const float* __restrict__ table, const float* __restrict__ pos,
-                                                     const int* __restrict__ tok, const int* __restrict__ step,
-                                                     float* __restrict__ y, void* __restrict__ y_ct,
-                                                     float* __restrict__ y_ss, int dim, RowProj rp) {
-  const int b = blockIdx.x;
-  const float* e = table + static_cast<size_t>(tok[b]) * dim;
-  const float* p = pos + static_cast<size_t>(step[b]) * dim;
-  for (int i = threadIdx.x * 4; i < dim; i += 512) {
+// The one writer of a decoder input row (InputRow): slot's row = table[tok] + pos[min(t, max_pos - 1)] in every form
+// present -- f32, bf16 copy, per-16-column sums of squares, layer 0's projection by table lookup -- by the `nthreads`
+// threads tid = 0 .. nthreads - 1 of a block (or of a wave: nthreads = 64, tid = lane).  The result does not depend on
+// nthreads: each 16-column sum of squares is formed by ONE quad (tid & 3 == threadIdx.x & 3 for every caller) with
+// put_row_piece's fmaf chain and quad_sum, and with dim % 16 == 0 a quad is wholly inside or wholly outside the row.
+__device__ __forceinline__ void put_input_row(const InputRow& r, int slot, int tok, int t, int tid, int nthreads) {
+  if (t >= r.max_pos) t = r.max_pos - 1;
+  const float* e = r.table + static_cast<size_t>(tok) * r.dim;
+  const float* p = r.pos + static_cast<size_t>(t) * r.dim;
+  for (int i = tid * 4; i < r.dim; i += nthreads * 4) {
     const float4 a = *reinterpret_cast<const float4*>(e + i), c = *reinterpret_cast<const float4*>(p + i);
-    put_row_piece(make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w), y, y_ct, y_ss, b, dim, i);
+    put_row_piece(make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w), r.y, r.y_ct, r.y_ss, slot, r.dim, i);
   }
-  if (rp.q_out) put_row_projection(rp, b, tok[b], step[b], threadIdx.x, 128);
+  if (r.rp.q_out) put_row_projection(r.rp, slot, tok, t, tid, nthreads);
 }
 
-int launch_embed(const float* table, const float* pos, const int* tok, const int* step, float* y, void* y_ct,
-                 float* y_ss, int B, int dim, const RowProj& rp, hipStream_t s) {
-  if ((y_ct || y_ss) && (!y_ss || dim % 16)) return mt3::fail(MT3_ERR_INVALID, "embed: the split form needs y_ss and dim % 16 == 0");
-  if (rp.q_out && (!rp.ew || !rp.pw || rp.q_n % 4)) return mt3::fail(MT3_ERR_INVALID, "embed: row projection tables missing");
-  hipLaunchKernelGGL(embed_kernel, dim3(B), dim3(128), 0, s, table, pos, tok, step, y, y_ct, y_ss, dim, rp);
+// the one host-side check of an InputRow: MT3_OK, or the failure of launcher `who` (r.y == nullptr: a kernel that
+// writes no row, which then cannot write a projection either)
+static int bad_input_row(const InputRow& r, const char* who) {
+  const char* bad = nullptr;
+  if (r.rp.q_out && (!r.y || !r.rp.ew || !r.rp.pw || r.rp.q_n % 4))
+    bad = ": row projection needs the row output and its tables";
+  else if (r.y && (!r.table || !r.pos || r.max_pos < 1 || r.dim <= 0 || r.dim % 4))
+    bad = ": the input row needs its tables and dim % 4 == 0";
+  else if (r.y && (r.y_ct || r.y_ss) && (!r.y_ss || r.dim % 16))
+    bad = ": the split form needs y_ss and dim % 16 == 0";
+  return bad ? mt3::fail(MT3_ERR_INVALID, std::string(who) + bad) : MT3_OK;
+}
+
+__global__ __launch_bounds__(128) void embed_kernel(InputRow in, const int* __restrict__ tok, const int* __restrict__ step) {
+  put_input_row(in, blockIdx.x, tok[blockIdx.x], step[blockIdx.x], threadIdx.x, 128);
+}
+
+int launch_embed(const InputRow& in, const int* tok, const int* step, int B, hipStream_t s) {
+  if (!in.y || !tok || !step) return mt3::fail(MT3_ERR_INVALID, "embed: bad arguments");
+  if (const int rc = bad_input_row(in, "embed")) return rc;
+  hipLaunchKernelGGL(embed_kernel, dim3(B), dim3(128), 0, s, in, tok, step);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -174,19 +192,11 @@ struct Top2 {
 //   beam_cfg[0] = brevity_penalty(max_len + 1) of this call, beam_cfg[1 + n] = brevity_penalty(n) =
 //   ((5 + n) / 6) ^ alpha, tabulated on the host.
 template <bool BEAM1>
-__global__ __launch_bounds__(256) void argmax_step_kernel(float* __restrict__ logits, int vocab,
-                                                           int* __restrict__ ids, int ids_stride,
-                                                           int* __restrict__ cur_tok, int* __restrict__ done,
-                                                           int* __restrict__ n_done, int* __restrict__ step,
-                                                           const float* __restrict__ table,
-                                                           const float* __restrict__ pos_table, int max_pos,
-                                                           float* __restrict__ y_next, void* __restrict__ y_ct,
-                                                           float* __restrict__ y_ss, int dim,
-                                                           float* __restrict__ beam_f, int* __restrict__ beam_len,
-                                                           int* __restrict__ beam_len_row,
-                                                           const float* __restrict__ beam_cfg, int beam_rows,
-                                                           const int* __restrict__ forced, int forced_stride,
-                                                           RowProj rp, LogitScale ls, StepRetire rt) {
+__global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
+  const SlotState& st = a.st;
+  const StepRetire& rt = a.rt;
+  const LogitScale& ls = a.ls;
+  const int vocab = a.vocab;
   __shared__ float s_v[8], s_sum[4];
   __shared__ int s_i[8];
   __shared__ int s_tok, s_t;
@@ -194,9 +204,9 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(float* __restrict__ lo
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // row retirement: a finished slot is not touched again (its ids stay at the 0 they were initialised to, its
   // position counter stops: nothing reads it any more)
-  if (rt.retire && done[b]) return;
+  if (rt.retire && st.done[b]) return;
   const int out_row = rt.slot_row ? rt.slot_row[b] : b;        // row of `ids` / `eos_at` this slot decodes
-  float* row = logits + static_cast<size_t>(b) * vocab;
+  float* __restrict__ row = a.logits + static_cast<size_t>(b) * vocab;
   // Round 6: the whole row in registers (vocab <= 2048: eight values per thread), requested in ONE batch before anything
   // that has to be waited for.  The loops this replaces walked the row three times, one element per thread and trip, each
   // trip a dependent load (the compiler waited for every load before the next): a dozen memory round trips in a kernel
@@ -215,15 +225,15 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(float* __restrict__ lo
   int was_done = 0, t = 0, blen = -1, eos_len = 0x7fffffff;
   float live = 0.f, best = 0.f, bp_max = 1.f, bp_t = 1.f;
   if (tid == 0) {
-    was_done = done[b];
-    t = step[b];
+    was_done = st.done[b];
+    t = st.step[b];
     if (rt.eos_at) eos_len = rt.eos_at[rt.slot_seg ? rt.slot_seg[b] : out_row];
     if (BEAM1) {
-      live = beam_f[b];
-      best = beam_f[beam_rows + b];
-      blen = beam_len[b];
-      bp_max = beam_cfg[0];
-      bp_t = beam_cfg[1 + t + 1];
+      live = a.beam.f[b];
+      best = a.beam.f[a.beam.rows + b];
+      blen = a.beam.len[b];
+      bp_max = a.beam.cfg[0];
+      bp_t = a.beam.cfg[1 + t + 1];
     }
   }
   if (ls.ss) {
@@ -301,9 +311,9 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(float* __restrict__ lo
     int tok;
     bool finished = false;                // this step finishes the slot
     if (!BEAM1) {
-      if (forced) was_done = 0;           // teacher forcing: every step reports its own arg-max, no EOS bookkeeping
+      if (a.forced) was_done = 0;           // teacher forcing: every step reports its own arg-max, no EOS bookkeeping
       tok = was_done ? 0 : (t + 1 >= eos_len ? 1 : t2.i1);      // synthetic EOS schedule: a point mass on EOS
-      finished = !was_done && tok == 1 && !forced;   // EOS
+      finished = !was_done && tok == 1 && !a.forced;   // EOS
     } else {
       tok = 0;
       if (!was_done) {
@@ -328,63 +338,43 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(float* __restrict__ lo
         }
         tok = eos_slot == 1 ? t2.i2 : t2.i1;
         live += eos_slot == 1 ? lp2 : lp1;
-        beam_f[b] = live;
-        beam_f[beam_rows + b] = best;
-        beam_len[b] = blen;
-        beam_len_row[out_row] = blen;
+        a.beam.f[b] = live;
+        a.beam.f[a.beam.rows + b] = best;
+        a.beam.len[b] = blen;
+        a.beam.len_row[out_row] = blen;
         finished = blen >= 0 && best > live / bp_max;
       }
     }
     // in-flight batching: a slot that has written max_len ids is finished as well (the row ran out of positions)
     if (!was_done && rt.max_len > 0 && t + 1 >= rt.max_len) finished = true;
     if (finished) {
-      done[b] = 1;
-      atomicAdd(n_done, 1);
+      st.done[b] = 1;
+      atomicAdd(st.n_done, 1);
     }
-    ids[static_cast<size_t>(out_row) * ids_stride + t] = tok;
+    a.ids[static_cast<size_t>(out_row) * a.ids_stride + t] = tok;
     // teacher forcing (Transformer.decode on given decoder_input_tokens, network.py:303-361): the NEXT input is
     // the caller's token for position t + 1, whatever this step predicted
-    if (!BEAM1 && forced) tok = forced[static_cast<size_t>(b) * forced_stride + t];
-    cur_tok[b] = tok;
-    step[b] = t + 1;
+    if (!BEAM1 && a.forced) tok = a.forced[static_cast<size_t>(b) * a.forced_stride + t];
+    st.cur_tok[b] = tok;
+    st.step[b] = t + 1;
     s_tok = tok;
     s_t = t + 1;
   }
   __syncthreads();
   // the next step's decoder input row: Embed(tok) + FixedEmbed[t+1]  (saves the embed launch of every step)
-  if (y_next) {
-    const int tp = s_t < max_pos ? s_t : max_pos - 1;
-    const float* e = table + static_cast<size_t>(s_tok) * dim;
-    const float* p = pos_table + static_cast<size_t>(tp) * dim;
-    for (int i = tid * 4; i < dim; i += 1024) {
-      const float4 a = *reinterpret_cast<const float4*>(e + i), c = *reinterpret_cast<const float4*>(p + i);
-      put_row_piece(make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w), y_next, y_ct, y_ss, b, dim, i);
-    }
-    if (rp.q_out) put_row_projection(rp, b, s_tok, tp, tid, 256);
-  }
+  if (a.in.y) put_input_row(a.in, b, s_tok, s_t, tid, 256);
 }
 
-int launch_argmax_step(float* logits, int vocab, int* ids, int ids_stride, int* cur_tok, int* done,
-                       int* n_done, int* step, const float* table, const float* pos_table, int max_pos,
-                       float* y_next, void* y_ct, float* y_ss, int dim, int B, const BeamState* beam,
-                       const int* forced, int forced_stride, const RowProj& rp, const LogitScale& ls,
-                       const StepRetire& rt, hipStream_t s) {
-  if (beam && forced) return mt3::fail(MT3_ERR_INVALID, "argmax_step: teacher forcing is a greedy-path feature");
-  if (beam && !beam->len_row) return mt3::fail(MT3_ERR_INVALID, "argmax_step: the beam state needs its row-indexed lengths");
-  if (forced && (rt.retire || rt.slot_row || rt.eos_at || rt.slot_seg || rt.max_len))
+int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
+  const StepRetire& rt = a.rt;
+  if (a.beam.f && a.forced) return mt3::fail(MT3_ERR_INVALID, "argmax_step: teacher forcing is a greedy-path feature");
+  if (a.beam.f && !a.beam.len_row) return mt3::fail(MT3_ERR_INVALID, "argmax_step: the beam state needs its row-indexed lengths");
+  if (a.forced && (rt.retire || rt.slot_row || rt.eos_at || rt.slot_seg || rt.max_len))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: teacher forcing keeps every row live and in place");
-  if (ls.ss && (ls.n_ss <= 0 || ls.n_ss > 64 || ls.dim <= 0))
+  if (a.ls.ss && (a.ls.n_ss <= 0 || a.ls.n_ss > 64 || a.ls.dim <= 0))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: the row scale needs 1 .. 64 partial sums");
-  if (rp.q_out && (!y_next || !rp.ew || !rp.pw || rp.q_n % 4))
-    return mt3::fail(MT3_ERR_INVALID, "argmax_step: row projection needs the next-row output and its tables");
-  if (beam)
-    hipLaunchKernelGGL(argmax_step_kernel<true>, dim3(B), dim3(256), 0, s, logits, vocab, ids, ids_stride, cur_tok,
-                       done, n_done, step, table, pos_table, max_pos, y_next, y_ct, y_ss, dim, beam->f, beam->len,
-                       beam->len_row, beam->cfg, beam->rows, nullptr, 0, rp, ls, rt);
-  else
-    hipLaunchKernelGGL(argmax_step_kernel<false>, dim3(B), dim3(256), 0, s, logits, vocab, ids, ids_stride, cur_tok,
-                       done, n_done, step, table, pos_table, max_pos, y_next, y_ct, y_ss, dim, nullptr, nullptr, nullptr,
-                       nullptr, 0, forced, forced_stride, rp, ls, rt);
+  if (const int rc = bad_input_row(a.in, "argmax_step")) return rc;
+  hipLaunchKernelGGL(a.beam.f ? argmax_step_kernel<true> : argmax_step_kernel<false>, dim3(a.B), dim3(256), 0, s, a);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -415,57 +405,59 @@ __global__ __launch_bounds__(128) void compact_move_kernel(CompactArgs c) {
   const int n_live = c.perm[c.rows];
   if (i >= n_live) {
     if (!GATHER && tid == 0) {
-      c.done[i] = 1;
-      if (c.slot_seg) c.slot_seg[i] = -1;
+      c.st.done[i] = 1;
+      if (c.st.slot_seg) c.st.slot_seg[i] = -1;
     }
     return;
   }
   const size_t src = GATHER ? static_cast<size_t>(c.perm[i]) : static_cast<size_t>(i), dst = i;
-  const float *y = GATHER ? c.y : c.s_y, *ss = GATHER ? c.y_ss : c.s_y_ss, *q = GATHER ? c.qkvf : c.s_qkvf;
-  float *yo = GATHER ? c.s_y : c.y, *sso = GATHER ? c.s_y_ss : c.y_ss, *qo = GATHER ? c.s_qkvf : c.qkvf;
-  const uint2* ct = static_cast<const uint2*>(GATHER ? c.y_ct : c.s_y_ct);
-  uint2* cto = static_cast<uint2*>(GATHER ? c.s_y_ct : c.y_ct);
-  for (int k = tid; k < c.emb / 4; k += 128) {
-    reinterpret_cast<float4*>(yo + dst * c.emb)[k] = reinterpret_cast<const float4*>(y + src * c.emb)[k];
-    if (ct) cto[dst * (c.emb / 4) + k] = ct[src * (c.emb / 4) + k];
+  const InputRow& r = c.in;
+  const int emb = r.dim, q_n = r.rp.q_n;
+  const float *y = GATHER ? r.y : c.s_y, *ss = GATHER ? r.y_ss : c.s_y_ss, *q = GATHER ? r.rp.q_out : c.s_qkvf;
+  float *yo = GATHER ? c.s_y : r.y, *sso = GATHER ? c.s_y_ss : r.y_ss, *qo = GATHER ? c.s_qkvf : r.rp.q_out;
+  const uint2* ct = static_cast<const uint2*>(GATHER ? r.y_ct : c.s_y_ct);
+  uint2* cto = static_cast<uint2*>(GATHER ? c.s_y_ct : r.y_ct);
+  for (int k = tid; k < emb / 4; k += 128) {
+    reinterpret_cast<float4*>(yo + dst * emb)[k] = reinterpret_cast<const float4*>(y + src * emb)[k];
+    if (ct) cto[dst * (emb / 4) + k] = ct[src * (emb / 4) + k];
   }
   if (ss)
-    for (int k = tid; k < c.emb / 16; k += 128) sso[dst * (c.emb / 16) + k] = ss[src * (c.emb / 16) + k];
+    for (int k = tid; k < emb / 16; k += 128) sso[dst * (emb / 16) + k] = ss[src * (emb / 16) + k];
   if (q)
-    for (int k = tid; k < c.q_n / 4; k += 128)
-      reinterpret_cast<float4*>(qo + dst * c.q_n)[k] = reinterpret_cast<const float4*>(q + src * c.q_n)[k];
+    for (int k = tid; k < q_n / 4; k += 128)
+      reinterpret_cast<float4*>(qo + dst * q_n)[k] = reinterpret_cast<const float4*>(q + src * q_n)[k];
   if (tid == 0) {
     if (GATHER) {
-      c.s_int[4 * dst + 0] = c.slot_row[src];
-      c.s_int[4 * dst + 1] = c.step[src];
-      c.s_int[4 * dst + 2] = c.cur_tok[src];
-      c.s_int[4 * dst + 3] = c.beam_len ? c.beam_len[src] : 0;
-      if (c.slot_seg) c.s_seg[dst] = c.slot_seg[src];
-      if (c.beam_f) {
-        c.s_beam[2 * dst + 0] = c.beam_f[src];
-        c.s_beam[2 * dst + 1] = c.beam_f[c.beam_rows + src];
+      c.s_int[4 * dst + 0] = c.st.slot_row[src];
+      c.s_int[4 * dst + 1] = c.st.step[src];
+      c.s_int[4 * dst + 2] = c.st.cur_tok[src];
+      c.s_int[4 * dst + 3] = c.beam.len ? c.beam.len[src] : 0;
+      if (c.st.slot_seg) c.s_seg[dst] = c.st.slot_seg[src];
+      if (c.beam.f) {
+        c.s_beam[2 * dst + 0] = c.beam.f[src];
+        c.s_beam[2 * dst + 1] = c.beam.f[c.beam.rows + src];
       }
     } else {
-      c.slot_row[dst] = c.s_int[4 * dst + 0];
-      c.step[dst] = c.s_int[4 * dst + 1];
-      c.cur_tok[dst] = c.s_int[4 * dst + 2];
-      if (c.beam_len) c.beam_len[dst] = c.s_int[4 * dst + 3];
-      if (c.slot_seg) c.slot_seg[dst] = c.s_seg[dst];
-      if (c.beam_f) {
-        c.beam_f[dst] = c.s_beam[2 * dst + 0];
-        c.beam_f[c.beam_rows + dst] = c.s_beam[2 * dst + 1];
+      c.st.slot_row[dst] = c.s_int[4 * dst + 0];
+      c.st.step[dst] = c.s_int[4 * dst + 1];
+      c.st.cur_tok[dst] = c.s_int[4 * dst + 2];
+      if (c.beam.len) c.beam.len[dst] = c.s_int[4 * dst + 3];
+      if (c.st.slot_seg) c.st.slot_seg[dst] = c.s_seg[dst];
+      if (c.beam.f) {
+        c.beam.f[dst] = c.s_beam[2 * dst + 0];
+        c.beam.f[c.beam.rows + dst] = c.s_beam[2 * dst + 1];
       }
-      c.done[dst] = 0;
+      c.st.done[dst] = 0;
     }
   }
 }
 
 int launch_compact(const CompactArgs& c, hipStream_t s) {
-  if (!c.done || !c.slot_row || !c.step || !c.cur_tok || !c.y || !c.s_y || !c.s_int || !c.perm || c.rows <= 0 ||
-      c.emb % 16 || c.q_n % 4 || (c.y_ct && !c.s_y_ct) || (c.y_ss && !c.s_y_ss) || (c.qkvf && !c.s_qkvf) ||
-      (c.beam_f && (!c.s_beam || !c.beam_len)) || (c.slot_seg && !c.s_seg))
+  if (!c.st.done || !c.st.slot_row || !c.st.step || !c.st.cur_tok || !c.in.y || !c.s_y || !c.s_int || !c.perm || c.rows <= 0 ||
+      c.in.dim % 16 || c.in.rp.q_n % 4 || (c.in.y_ct && !c.s_y_ct) || (c.in.y_ss && !c.s_y_ss) || (c.in.rp.q_out && !c.s_qkvf) ||
+      (c.beam.f && (!c.s_beam || !c.beam.len)) || (c.st.slot_seg && !c.s_seg))
     return mt3::fail(MT3_ERR_INVALID, "compact: bad arguments");
-  hipLaunchKernelGGL(compact_plan_kernel, dim3(1), dim3(64), 0, s, c.done, c.perm, c.rows);
+  hipLaunchKernelGGL(compact_plan_kernel, dim3(1), dim3(64), 0, s, c.st.done, c.perm, c.rows);
   hipLaunchKernelGGL(compact_move_kernel<true>, dim3(c.rows), dim3(128), 0, s, c);
   hipLaunchKernelGGL(compact_move_kernel<false>, dim3(c.rows), dim3(128), 0, s, c);
   MT3_HIP_CHECK(hipGetLastError());
@@ -480,7 +472,7 @@ int launch_compact(const CompactArgs& c, hipStream_t s) {
 //          into the cache rows of slot plan[i]  (16-byte pieces, 256 lanes, a row of H*T*64 elements in `parts` pieces)
 //   slot   block i: id row of slot plan[i] -> the caller's row of the segment it decoded (beam-1: the finished
 //          hypothesis, as beam1_finalize_kernel would leave it); i < n_new: restart on segment first_seg + i
-// (unit > 1: the plan is over ELEMENTS of `unit` slots each -- beam groups, keyed on the element's first slot)
+// (unit > 1: plan and cross copy are over ELEMENTS of `unit` slots each -- beam groups, keyed on the element's first slot)
 __global__ __launch_bounds__(64) void refill_plan_kernel(const int* __restrict__ done, int* __restrict__ plan,
                                                           int* __restrict__ n_done, int rows, int n_new, int unit) {
   const int lane = threadIdx.x;
@@ -498,42 +490,51 @@ __global__ __launch_bounds__(64) void refill_plan_kernel(const int* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void refill_cross_kernel(RefillArgs a, int parts) {
+// the slots of plan entry i are plan[i] * unit + j, j < unit: every 16-byte piece is loaded once and stored to each
+__global__ __launch_bounds__(256) void refill_cross_kernel(StagedCross x, const int* __restrict__ plan,
+                                                            const int* __restrict__ slot_row, int rows, int n_new,
+                                                            int unit, int parts) {
   const int i = blockIdx.x;
-  const int n_fin = a.plan[a.rows];
-  if (i >= a.n_new || i >= n_fin) return;
-  const int row = a.slot_row[a.plan[i]];
+  if (i >= n_new || i >= plan[rows]) return;
+  const int s0 = plan[i] * unit;
   const int l = blockIdx.y / 3, what = blockIdx.y % 3;          // 0: K rows, 1: V rows, 2: scale rows (e4m3 caches)
   const char* src;
   char* dst;
   size_t bytes;
   if (what < 2) {
-    bytes = a.x.row_bytes;
-    src = a.x.src[l] + (static_cast<size_t>(what) * a.x.src_batch + a.x.src_entry0 + i) * bytes;
-    dst = a.x.dst[l] + (static_cast<size_t>(what) * a.x.dst_batch + row) * bytes;
+    bytes = x.row_bytes;
+    src = x.src[l] + (static_cast<size_t>(what) * x.src_batch + x.src_entry0 + i) * bytes;
+    dst = x.dst[l] + static_cast<size_t>(what) * x.dst_batch * bytes;
   } else {
-    if (!a.x.src_sc[l]) return;
-    bytes = a.x.sc_bytes;
-    src = a.x.src_sc[l] + static_cast<size_t>(a.x.src_entry0 + i) * bytes;
-    dst = a.x.dst_sc[l] + static_cast<size_t>(row) * bytes;
+    if (!x.src_sc[l]) return;
+    bytes = x.sc_bytes;
+    src = x.src_sc[l] + static_cast<size_t>(x.src_entry0 + i) * bytes;
+    dst = x.dst_sc[l];
   }
+  u32x4* d4[kBeamMaxK];
+#pragma unroll
+  for (int j = 0; j < kBeamMaxK; ++j)       // (entries past `unit` repeat the first slot's row and are never stored to)
+    d4[j] = reinterpret_cast<u32x4*>(dst + static_cast<size_t>(slot_row[s0 + (j < unit ? j : 0)]) * bytes);
   const size_t n16 = bytes >> 4;                                   // rows are multiples of 16 bytes (64 elements per key)
   const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
-  u32x4* d4 = reinterpret_cast<u32x4*>(dst);
-  for (size_t k = static_cast<size_t>(blockIdx.z) * 256 + threadIdx.x; k < n16; k += static_cast<size_t>(parts) * 256)
-    d4[k] = __builtin_nontemporal_load(s4 + k);
+  for (size_t p = static_cast<size_t>(blockIdx.z) * 256 + threadIdx.x; p < n16; p += static_cast<size_t>(parts) * 256) {
+    const u32x4 v = __builtin_nontemporal_load(s4 + p);
+#pragma unroll
+    for (int j = 0; j < kBeamMaxK; ++j)
+      if (j < unit) d4[j][p] = v;
+  }
 }
 
 __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
   const int i = blockIdx.x, tid = threadIdx.x;
   if (i >= a.plan[a.rows]) return;
   const int slot = a.plan[i];
-  const int row = a.slot_row[slot];
-  const int seg_old = a.slot_seg[slot];
+  const int row = a.st.slot_row[slot];
+  const int seg_old = a.st.slot_seg[slot];
   int* idrow = a.ids + static_cast<size_t>(row) * a.ids_stride;
   if (seg_old >= 0) {
     // the finished hypothesis of the beam-1 search: live[:n] + EOS + padding (beam1_finalize_kernel); n < 0: the live one
-    const int n = a.beam_len ? a.beam_len_row[row] : -1;
+    const int n = a.beam.len ? a.beam.len_row[row] : -1;
     int* out = a.out_ids + static_cast<size_t>(seg_old) * a.ids_stride;
     for (int k = tid; k < a.ids_stride; k += 128) out[k] = (n >= 0 && k >= n) ? (k == n ? 1 : 0) : idrow[k];
   }
@@ -543,26 +544,22 @@ __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
   if (restart)
     for (int k = tid; k < a.ids_stride; k += 128) idrow[k] = 0;
   if (tid == 0) {
-    a.slot_seg[slot] = restart ? a.first_seg + i : -1;
+    a.st.slot_seg[slot] = restart ? a.first_seg + i : -1;
     if (restart) {
-      a.step[slot] = 0;
-      a.cur_tok[slot] = 0;                                       // BOS
-      a.done[slot] = 0;
-      if (a.beam_f) {                                            // t5x beam_search: live log-prob 0, nothing finished
-        a.beam_f[slot] = 0.f;
-        a.beam_f[a.beam_rows + slot] = 0.f;
-        a.beam_len[slot] = -1;
-        a.beam_len_row[row] = -1;
+      a.st.step[slot] = 0;
+      a.st.cur_tok[slot] = 0;                                       // BOS
+      a.st.done[slot] = 0;
+      if (a.beam.f) {                                            // t5x beam_search: live log-prob 0, nothing finished
+        a.beam.f[slot] = 0.f;
+        a.beam.f[a.beam.rows + slot] = 0.f;
+        a.beam.len[slot] = -1;
+        a.beam.len_row[row] = -1;
       }
     }
   }
   if (!restart) return;
   // decoder input of position 0: Embed(BOS) + FixedEmbed[0], in the forms the step reads (embed_kernel)
-  for (int k = tid * 4; k < a.emb; k += 512) {
-    const float4 e4 = *reinterpret_cast<const float4*>(a.table + k), p4 = *reinterpret_cast<const float4*>(a.pos + k);
-    put_row_piece(make_float4(e4.x + p4.x, e4.y + p4.y, e4.z + p4.z, e4.w + p4.w), a.y, a.y_ct, a.y_ss, slot, a.emb, k);
-  }
-  if (a.rp.q_out) put_row_projection(a.rp, slot, 0, 0, tid, 128);
+  put_input_row(a.in, slot, 0, 0, tid, 128);
 }
 
 static bool bad_staged_cross(const StagedCross& x, int n_new) {   // a copy of n_new staged segments that cannot be right
@@ -570,20 +567,27 @@ static bool bad_staged_cross(const StagedCross& x, int n_new) {   // a copy of n
          x.dst_batch <= 0 || x.src_entry0 < 0 || x.src_entry0 + n_new > x.src_batch;
 }
 
+// the plan (refill_plan_kernel) and the copy of the first n_new staged segments of `x` into the slots it names
+static int launch_refill_plan_cross(const SlotState& st, int* plan, int rows, int n_new, int unit, const StagedCross& x,
+                                    int parts, const char* who, hipStream_t s) {
+  if (n_new > 0 && bad_staged_cross(x, n_new)) return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": bad staging chunk");
+  hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, st.done, plan, st.n_done, rows, n_new, unit);
+  if (n_new > 0)
+    hipLaunchKernelGGL(refill_cross_kernel, dim3(n_new, x.n_layers * 3, parts), dim3(256), 0, s, x, plan, st.slot_row, rows,
+                       n_new, unit, parts);
+  return MT3_OK;
+}
+
 int launch_refill(const RefillArgs& a, hipStream_t s) {
-  if (!a.done || !a.slot_row || !a.slot_seg || !a.step || !a.cur_tok || !a.n_done || !a.y || !a.table || !a.pos || !a.ids ||
-      !a.out_ids || !a.plan || a.rows <= 0 || a.n_new < 0 || a.n_new > a.rows || a.emb % 16 || a.ids_stride <= 0 ||
-      (a.beam_f && (!a.beam_len || !a.beam_len_row)) || (a.y_ct && !a.y_ss) ||
-      (a.rp.q_out && (!a.rp.ew || !a.rp.pw || a.rp.q_n % 4)))
+  const SlotState& st = a.st;
+  if (!st.done || !st.slot_row || !st.slot_seg || !st.step || !st.cur_tok || !st.n_done || !a.in.y || a.in.dim % 16 || !a.ids ||
+      !a.out_ids || !a.plan || a.rows <= 0 || a.n_new < 0 || a.n_new > a.rows || a.ids_stride <= 0 ||
+      (a.beam.f && (!a.beam.len || !a.beam.len_row)))
     return mt3::fail(MT3_ERR_INVALID, "refill: bad arguments");
-  if (a.n_new > 0 && bad_staged_cross(a.x, a.n_new)) return mt3::fail(MT3_ERR_INVALID, "refill: bad staging chunk");
-  hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, a.done, a.plan, a.n_done, a.rows, a.n_new, 1);
-  if (a.n_new > 0) {
-    // a K or V row of one layer is H*T*64 elements (98 KB ... 393 KB): 8 blocks of 256 lanes per row keep >= 1000
-    // workgroups in flight for a handful of segments
-    const int parts = 8;
-    hipLaunchKernelGGL(refill_cross_kernel, dim3(a.n_new, a.x.n_layers * 3, parts), dim3(256), 0, s, a, parts);
-  }
+  if (const int rc = bad_input_row(a.in, "refill")) return rc;
+  // a K or V row of one layer is H*T*64 elements (98 KB ... 393 KB): 8 blocks of 256 lanes per row keep >= 1000
+  // workgroups in flight for a handful of segments
+  if (const int rc = launch_refill_plan_cross(st, a.plan, a.rows, a.n_new, 1, a.x, 8, "refill", s)) return rc;
   hipLaunchKernelGGL(refill_slot_kernel, dim3(a.rows), dim3(128), 0, s, a);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
@@ -601,7 +605,7 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
 //      the history, the slot -> cache-row map (a beam takes over its parent's row; the extra children of a parent take
 //      the rows of parents nobody chose and are marked for beam_reorder_kernel) and the retirement;
 //   4. each wave writes its slot's next input row, as the greedy / beam-1 kernel does.
-__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, RowProj rp, LogitScale ls) {
+__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls) {
   constexpr int kPerLane = 32;                         // vocab <= 2048: lane l holds i = l + 64 * vt + 256 * u
   __shared__ float c_score[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int c_tok[2 * kBeamMaxK * kBeamMaxK];
@@ -609,8 +613,8 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
   __shared__ int s_tok[kBeamMaxK];
   const int k = a.k, k2 = 2 * k, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int s0 = blockIdx.x * k, slot = s0 + w;
-  if (a.done[s0]) return;                              // retired element: its state is final
-  const int t = a.step[s0];
+  if (a.st.done[s0]) return;                              // retired element: its state is final
+  const int t = a.st.step[s0];
   const float* row = a.logits + static_cast<size_t>(slot) * a.vocab;
   float xv[kPerLane];
 #pragma unroll
@@ -775,7 +779,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
       // cache rows: the first child of a parent takes the parent's row, every further child a row nobody chose
       int orow[kBeamMaxK], nchild[kBeamMaxK];
       for (int j = 0; j < k; ++j) {
-        orow[j] = a.slot_row[s0 + j];
+        orow[j] = a.st.slot_row[s0 + j];
         nchild[j] = 0;
       }
       for (int j = 0; j < k; ++j) ++nchild[nl_par[j]];
@@ -800,46 +804,35 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
           src = orow[p];
           ++forks;
         }
-        a.slot_row[s0 + j] = nrow;
+        a.st.slot_row[s0 + j] = nrow;
         a.fork_src[s0 + j] = src;
         par_out[j] = p;
         tok_out[j] = s_tok[j];
         a.live[s0 + j] = nl_score[j];
-        a.cur_tok[s0 + j] = s_tok[j];
-        a.step[s0 + j] = t + 1;
-        if (closed) a.done[s0 + j] = 1;
+        a.st.cur_tok[s0 + j] = s_tok[j];
+        a.st.step[s0 + j] = t + 1;
+        if (closed) a.st.done[s0 + j] = 1;
       }
       if (forks && !closed) atomicAdd(a.fork_count, forks);    // a closed element's forks are never copied
-      if (closed) atomicAdd(a.n_done, k);
+      if (closed) atomicAdd(a.st.n_done, k);
     }
   }
   __syncthreads();
   // the next step's input row of this wave's slot: Embed(tok) + FixedEmbed[t+1]
-  if (a.y_next) {
-    const int tok = s_tok[w], tp = t + 1 < a.max_pos ? t + 1 : a.max_pos - 1;
-    const float* e = a.table + static_cast<size_t>(tok) * a.dim;
-    const float* p = a.pos_table + static_cast<size_t>(tp) * a.dim;
-    for (int i = lane * 4; i < a.dim; i += 256) {
-      const float4 x = *reinterpret_cast<const float4*>(e + i), c = *reinterpret_cast<const float4*>(p + i);
-      put_row_piece(make_float4(x.x + c.x, x.y + c.y, x.z + c.z, x.w + c.w), a.y_next, a.y_ct, a.y_ss, slot, a.dim, i);
-    }
-    if (rp.q_out) put_row_projection(rp, slot, tok, tp, lane, 64);
-  }
+  if (a.in.y) put_input_row(a.in, slot, s_tok[w], t + 1, lane, 64);
 }
 
-int launch_beam_step(const BeamKArgs& a, const RowProj& rp, const LogitScale& ls, hipStream_t s) {
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, hipStream_t s) {
   if (a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || a.vocab < 2 * a.k || a.vocab > 2048)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: k must be 1 .. 8 and 2k <= vocab <= 2048");
-  if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.slot_row ||
-      !a.fork_src || !a.fork_count || !a.done || !a.n_done || !a.step || !a.cur_tok || !a.bp)
+  if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.st.slot_row ||
+      !a.fork_src || !a.fork_count || !a.st.done || !a.st.n_done || !a.st.step || !a.st.cur_tok || !a.bp)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: missing state");
   if (ls.ss && (ls.n_ss <= 0 || ls.n_ss > 64 || ls.dim <= 0))
     return mt3::fail(MT3_ERR_INVALID, "beam_step: the row scale needs 1 .. 64 partial sums");
-  if (a.y_next && (a.dim % 16 || ((a.y_ct || a.y_ss) && !a.y_ss)))
-    return mt3::fail(MT3_ERR_INVALID, "beam_step: the next input row needs dim % 16 == 0 and y_ss with the split form");
-  if (rp.q_out && (!a.y_next || !rp.ew || !rp.pw || rp.q_n % 4))
-    return mt3::fail(MT3_ERR_INVALID, "beam_step: row projection needs the next-row output and its tables");
-  hipLaunchKernelGGL(beam_step_kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, rp, ls);
+  if (a.in.y && a.in.dim % 16) return mt3::fail(MT3_ERR_INVALID, "beam_step: the next input row needs dim % 16 == 0");
+  if (const int rc = bad_input_row(a.in, "beam_step")) return rc;
+  hipLaunchKernelGGL(beam_step_kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -944,39 +937,6 @@ int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int
 }
 
 // ------------------------------------------------------- refill of beam elements (BeamRefillArgs, kernels.h)
-__global__ __launch_bounds__(256) void beam_refill_cross_kernel(BeamRefillArgs a, int parts) {
-  const int i = blockIdx.x, k = a.b.k;
-  const int n_fin = a.plan[a.b.elems];
-  if (i >= a.n_new || i >= n_fin) return;
-  const int s0 = a.plan[i] * k;
-  const int l = blockIdx.y / 3, what = blockIdx.y % 3;          // 0: K rows, 1: V rows, 2: scale rows (e4m3 caches)
-  const char* src;
-  char* dst;
-  size_t bytes;
-  if (what < 2) {
-    bytes = a.x.row_bytes;
-    src = a.x.src[l] + (static_cast<size_t>(what) * a.x.src_batch + a.x.src_entry0 + i) * bytes;
-    dst = a.x.dst[l] + static_cast<size_t>(what) * a.x.dst_batch * bytes;
-  } else {
-    if (!a.x.src_sc[l]) return;
-    bytes = a.x.sc_bytes;
-    src = a.x.src_sc[l] + static_cast<size_t>(a.x.src_entry0 + i) * bytes;
-    dst = a.x.dst_sc[l];
-  }
-  u32x4* d4[kBeamMaxK];
-#pragma unroll
-  for (int j = 0; j < kBeamMaxK; ++j)       // (entries past k repeat beam 0's row and are never stored to)
-    d4[j] = reinterpret_cast<u32x4*>(dst + static_cast<size_t>(a.b.slot_row[s0 + (j < k ? j : 0)]) * bytes);
-  const size_t n16 = bytes >> 4;
-  const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
-  for (size_t x = static_cast<size_t>(blockIdx.z) * 256 + threadIdx.x; x < n16; x += static_cast<size_t>(parts) * 256) {
-    const u32x4 v = __builtin_nontemporal_load(s4 + x);
-#pragma unroll
-    for (int j = 0; j < kBeamMaxK; ++j)
-      if (j < k) d4[j][x] = v;
-  }
-}
-
 // dynamic LDS: the element's history columns [n_hist][k] (token | parent << 11: vocab <= 2048, k <= 8), then the k
 // decodes [k][L], both as 16-bit values
 __global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a) {
@@ -984,11 +944,11 @@ __global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a)
   const int i = blockIdx.x, tid = threadIdx.x, k = a.b.k, L = a.L;
   if (i >= a.plan[a.b.elems]) return;
   const int s0 = a.plan[i] * k;
-  const int seg_old = a.slot_seg[s0];
+  const int seg_old = a.b.st.slot_seg[s0];
   if (seg_old >= 0) {
     unsigned short* s_hist = s_mem;
     unsigned short* s_out = s_mem + static_cast<size_t>(a.num_steps) * k;
-    const int ran = a.b.step[s0];
+    const int ran = a.b.st.step[s0];
     const int n_hist = ran < a.num_steps ? ran : a.num_steps;   // steps the element ran (its history rows)
     for (int x = tid; x < n_hist * k; x += 256) {
       const int u = x / k, j = x - u * k;
@@ -1034,45 +994,36 @@ __global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a)
   const bool restart = i < a.n_new;
   if (tid < k) {
     const int slot = s0 + tid;
-    a.slot_seg[slot] = restart ? a.first_seg + i : -1;
+    a.b.st.slot_seg[slot] = restart ? a.first_seg + i : -1;
     if (restart) {
       a.b.live[slot] = tid == 0 ? 0.f : kBeamNegInf;
       a.b.fin_score[slot] = kBeamNegInf;
       a.b.fin_step[slot] = -1;
       a.b.fin_beam[slot] = -1;
       a.b.fork_src[slot] = -1;
-      a.b.step[slot] = 0;
-      a.b.cur_tok[slot] = 0;                               // BOS
-      a.b.done[slot] = 0;
+      a.b.st.step[slot] = 0;
+      a.b.st.cur_tok[slot] = 0;                               // BOS
+      a.b.st.done[slot] = 0;
     }
   }
   if (!restart) return;
   // decoder input of position 0 for all k slots: Embed(BOS) + FixedEmbed[0], in the forms the step reads (embed_kernel)
-  for (int c = tid * 4; c < a.b.dim; c += 1024) {
-    const float4 e4 = *reinterpret_cast<const float4*>(a.b.table + c), p4 = *reinterpret_cast<const float4*>(a.b.pos_table + c);
-    const float4 v = make_float4(e4.x + p4.x, e4.y + p4.y, e4.z + p4.z, e4.w + p4.w);
-    for (int j = 0; j < k; ++j) put_row_piece(v, a.b.y_next, a.b.y_ct, a.b.y_ss, s0 + j, a.b.dim, c);
-  }
-  if (a.rp.q_out)
-    for (int j = 0; j < k; ++j) put_row_projection(a.rp, s0 + j, 0, 0, tid, 256);
+  for (int j = 0; j < k; ++j) put_input_row(a.b.in, s0 + j, 0, 0, tid, 256);
 }
 
 int launch_beam_refill(const BeamRefillArgs& a, hipStream_t s) {
   const BeamKArgs& b = a.b;
+  const SlotState& st = b.st;
   if (b.k < 1 || b.k > kBeamMaxK || b.elems <= 0 || b.vocab > 2048 || !b.live || !b.fin_score || !b.fin_step || !b.fin_beam ||
-      !b.hist_par || !b.hist_tok || !b.slot_row || !b.fork_src || !b.done || !b.n_done || !b.step || !b.cur_tok ||
-      !b.table || !b.pos_table || !b.y_next || b.dim % 16 || (b.y_ct && !b.y_ss) || !a.slot_seg || !a.plan || !a.out_ids ||
-      a.L <= 0 || a.num_steps <= 0 || a.num_steps > a.L || a.n_new < 0 || a.n_new > b.elems ||
-      (a.rp.q_out && (!a.rp.ew || !a.rp.pw || a.rp.q_n % 4)))
+      !b.hist_par || !b.hist_tok || !st.slot_row || !b.fork_src || !st.done || !st.n_done || !st.step || !st.cur_tok ||
+      !st.slot_seg || !b.in.y || b.in.dim % 16 || !a.plan || !a.out_ids || a.L <= 0 || a.num_steps <= 0 || a.num_steps > a.L ||
+      a.n_new < 0 || a.n_new > b.elems)
     return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad arguments");
-  if (a.n_new > 0 && bad_staged_cross(a.x, a.n_new)) return mt3::fail(MT3_ERR_INVALID, "beam_refill: bad staging chunk");
+  if (const int rc = bad_input_row(b.in, "beam_refill")) return rc;
   const size_t lds = (static_cast<size_t>(a.num_steps) + a.L) * b.k * sizeof(unsigned short);
   if (lds > 65536) return mt3::fail(MT3_ERR_INVALID, "beam_refill: history and decodes of an element exceed 64 KB of LDS");
-  hipLaunchKernelGGL(refill_plan_kernel, dim3(1), dim3(64), 0, s, b.done, a.plan, b.n_done, b.elems, a.n_new, b.k);
-  if (a.n_new > 0) {
-    const int parts = 16;     // twice refill_cross_kernel's: a block stores every piece it loads k times
-    hipLaunchKernelGGL(beam_refill_cross_kernel, dim3(a.n_new, a.x.n_layers * 3, parts), dim3(256), 0, s, a, parts);
-  }
+  // parts: twice the greedy refill's, a block stores every piece it loads k times
+  if (const int rc = launch_refill_plan_cross(st, a.plan, b.elems, a.n_new, b.k, a.x, 16, "beam_refill", s)) return rc;
   hipLaunchKernelGGL(beam_refill_elem_kernel, dim3(b.elems), dim3(256), lds, s, a);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
@@ -1257,35 +1208,35 @@ extern "C" int mt3_op_beam_search_scripted(const float* d_logits, const float* d
   b.hist_par = m.take<int>(hist);
   b.hist_tok = m.take<int>(hist);
   b.hist_stride = slots;
-  b.slot_row = m.take<int>(n);
+  b.st.slot_row = m.take<int>(n);
   b.fork_src = m.take<int>(n);
-  b.done = m.take<int>(n);
-  b.step = m.take<int>(n);
-  b.cur_tok = m.take<int>(n);
+  b.st.done = m.take<int>(n);
+  b.st.step = m.take<int>(n);
+  b.st.cur_tok = m.take<int>(n);
   b.fork_count = m.take<int>(1);
-  b.n_done = m.take<int>(1);
+  b.st.n_done = m.take<int>(1);
   float* d_bp = m.take<float>(static_cast<size_t>(num_steps) + 3);
   b.bp = d_bp;
-  b.table = d_table;
-  b.pos_table = d_pos;
-  b.max_pos = num_steps + 1;
-  b.y_next = d_y_next;
-  b.dim = dim_e;
+  b.in.table = d_table;
+  b.in.pos = d_pos;
+  b.in.max_pos = num_steps + 1;
+  b.in.y = d_y_next;
+  b.in.dim = dim_e;
   b.max_len = max_len;
   MT3_HIP_CHECK(hipMemsetAsync(b.fork_src, 0xFF, n * 4, s));               // -1: no fork pending
-  MT3_OP_TRY(mt3k::launch_iota(b.slot_row, slots, s));
+  MT3_OP_TRY(mt3k::launch_iota(b.st.slot_row, slots, s));
   MT3_OP_TRY(mt3k::launch_beam_init(b.live, b.fin_score, b.fin_step, b.fin_beam, slots, k, s));
   MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
   int ran = 0;
   for (int t = 0; t < num_steps; ++t) {
     b.logits = const_cast<float*>(d_logits) + static_cast<size_t>(t) * n * vocab;
     const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_beam_step(b, mt3k::RowProj{}, ls, s));
+    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, s));
     int32_t* tr = h_trace + static_cast<size_t>(t) * 4 * n;
-    MT3_HIP_CHECK(hipMemcpyAsync(tr, b.slot_row, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(tr, b.st.slot_row, n * 4, hipMemcpyDeviceToHost, s));
     MT3_HIP_CHECK(hipMemcpyAsync(tr + n, b.fork_src, n * 4, hipMemcpyDeviceToHost, s));
-    MT3_HIP_CHECK(hipMemcpyAsync(tr + 2 * n, b.done, n * 4, hipMemcpyDeviceToHost, s));
-    MT3_HIP_CHECK(hipMemcpyAsync(tr + 3 * n, b.cur_tok, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(tr + 2 * n, b.st.done, n * 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(tr + 3 * n, b.st.cur_tok, n * 4, hipMemcpyDeviceToHost, s));
     MT3_HIP_CHECK(hipMemcpyAsync(h_live + static_cast<size_t>(t) * n, b.live, n * 4, hipMemcpyDeviceToHost, s));
     MT3_HIP_CHECK(hipStreamSynchronize(s));
     ran = t + 1;
@@ -1316,27 +1267,32 @@ extern "C" int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, i
   MT3_OP_TRY(m.alloc(5 * Scratch::piece(n * 4) + Scratch::piece(2 * n * 4) + Scratch::piece(4) +
                          Scratch::piece((static_cast<size_t>(num_steps) + 3) * 4),
                      s));
-  int* cur_tok = m.take<int>(n);
-  int* done = m.take<int>(n);
-  int* step = m.take<int>(n);
+  mt3k::ArgmaxStepArgs a{};
+  a.vocab = vocab;
+  a.ids = d_ids;
+  a.ids_stride = num_steps;
+  a.st.cur_tok = m.take<int>(n);
+  a.st.done = m.take<int>(n);
+  a.st.step = m.take<int>(n);
   int* len = m.take<int>(n);
   int* len_row = m.take<int>(n);
   float* f = m.take<float>(2 * n);
-  int* n_done = m.take<int>(1);
+  a.st.n_done = m.take<int>(1);
   float* d_bp = m.take<float>(static_cast<size_t>(num_steps) + 3);
+  a.in.max_pos = num_steps + 1;
+  if (mode == 1) a.beam = mt3k::BeamState{f, len, d_bp, rows, len_row};
+  // a row that max_len closes is retired, as it is in the engine's streaming jobs (the only ones that set max_len)
+  a.rt = mt3k::StepRetire{max_len > 0 ? 1 : 0, nullptr, nullptr, nullptr, max_len};
+  a.B = rows;
   MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, n * num_steps * 4, s));
   MT3_HIP_CHECK(hipMemsetAsync(len, 0xFF, n * 4, s));                       // -1: nothing finished
   MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
   MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
-  const mt3k::BeamState beam{f, len, d_bp, rows, len_row};
-  // a row that max_len closes is retired, as it is in the engine's streaming jobs (the only ones that set max_len)
-  const mt3k::StepRetire rt{max_len > 0 ? 1 : 0, nullptr, nullptr, nullptr, max_len};
   for (int t = 0; t < num_steps; ++t) {
-    const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_argmax_step(d_logits + static_cast<size_t>(t) * n * vocab, vocab, d_ids, num_steps, cur_tok,
-                                        done, n_done, step, nullptr, nullptr, num_steps + 1, nullptr, nullptr, nullptr, 0,
-                                        rows, mode == 1 ? &beam : nullptr, nullptr, 0, mt3k::RowProj{}, ls, rt, s));
-    MT3_HIP_CHECK(hipMemcpyAsync(h_done + static_cast<size_t>(t) * n, done, n * 4, hipMemcpyDeviceToHost, s));
+    a.logits = d_logits + static_cast<size_t>(t) * n * vocab;
+    a.ls = mt3k::LogitScale{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
+    MT3_OP_TRY(mt3k::launch_argmax_step(a, s));
+    MT3_HIP_CHECK(hipMemcpyAsync(h_done + static_cast<size_t>(t) * n, a.st.done, n * 4, hipMemcpyDeviceToHost, s));
   }
   if (mode == 1) MT3_OP_TRY(mt3k::launch_beam1_finalize(d_ids, num_steps, len_row, rows, s));
   MT3_HIP_CHECK(hipStreamSynchronize(s));

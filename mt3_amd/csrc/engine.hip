@@ -688,12 +688,44 @@ inline bool chain_op_is_heavy(const mt3_engine* e, int op) {
   return op < 8 * e->cfg.num_decoder_layers && ((op & 7) == 1 || (op & 7) == 4);
 }
 
+// the per-slot state of slots [row0, ...) of the row group that counts its finished slots in n_done[done_slot]
+mt3k::SlotState slot_state(mt3_engine* e, int row0, int done_slot) {
+  return mt3k::SlotState{e->done + row0, e->slot_row + row0, e->slot_seg + row0,
+                         e->step + row0, e->cur_tok + row0,  e->n_done + done_slot};
+}
+
+// the decoder input rows of slots [row0, ...) and what they are written from.  The one place that knows which forms the
+// engine keeps: the bf16 copy with the split form of the bf16 path (f32: the compute-type rows ARE the f32 rows), the
+// sums of squares with the split form, layer 0's projected rows with the qkv-fold
+mt3k::InputRow input_row(mt3_engine* e, int row0) {
+  const mt3_engine_config& c = e->cfg;
+  const size_t r0 = static_cast<size_t>(row0);
+  const int emb = c.emb_dim, n4 = 4 * e->HD();
+  mt3k::InputRow in{};
+  in.table = e->embedding;
+  in.pos = e->pos_table;
+  in.max_pos = kMaxPos;
+  in.y = e->y + r0 * emb;                        // the token-pick kernels leave the next input row in buffer 0
+  if (e->y_split && c.compute_dtype == MT3_BF16) in.y_ct = static_cast<char*>(e->y_ct) + r0 * emb * 2;
+  if (e->y_split) in.y_ss = e->y_ss + r0 * (emb / 16);
+  in.dim = emb;
+  in.rp = mt3k::RowProj{e->ew0, e->pw0, e->qkv_fold ? e->qkvf + r0 * n4 : nullptr, n4};
+  return in;
+}
+
+// the beam-1 state of slots [row0, ...); its row-indexed lengths start at row crow0 (row0, or 0 under a slot map)
+mt3k::BeamState beam1_state(mt3_engine* e, int row0, size_t crow0) {
+  return mt3k::BeamState{e->beam_f + row0, e->beam_len + row0, e->beam_cfg, e->cfg.max_batch, e->beam_len_row + crow0};
+}
+
 // the k-beam state of slots [row0, row0 + rows) (the kernel-side pointers are those of the first slot)
-mt3k::BeamKArgs beam_args(mt3_engine* e, int row0, int rows, int k) {
+mt3k::BeamKArgs beam_args(mt3_engine* e, int row0, int rows, int k, int done_slot = 0) {
   mt3k::BeamKArgs b{};
   b.vocab = e->cfg.vocab_size;
   b.k = k;
   b.elems = rows / k;
+  b.st = slot_state(e, row0, done_slot);
+  b.in = input_row(e, row0);
   b.live = e->bk_live + row0;
   b.fin_score = e->bk_fin_score + row0;
   b.fin_step = e->bk_fin_step + row0;
@@ -701,12 +733,8 @@ mt3k::BeamKArgs beam_args(mt3_engine* e, int row0, int rows, int k) {
   b.hist_par = e->bk_par + row0;
   b.hist_tok = e->bk_tok + row0;
   b.hist_stride = e->cfg.max_batch;
-  b.slot_row = e->slot_row + row0;
   b.fork_src = e->bk_fork_src + row0;
   b.fork_count = e->bk_forks;
-  b.done = e->done + row0;
-  b.step = e->step + row0;
-  b.cur_tok = e->cur_tok + row0;
   b.bp = e->beam_cfg;
   return b;
 }
@@ -716,7 +744,6 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   const int dt = c.compute_dtype, emb = c.emb_dim, hd = e->HD(), H = c.num_heads, T = c.input_length;
   const int Lmax = c.max_decode_len;
   const size_t es = e->esize, kes = e->kv_esize;
-  const bool small = true;
   const int nl = c.num_decoder_layers;
   const bool split = e->y_split, fold = e->qkv_fold;
   // row retirement: the step's slots [row0, row0 + rows) reach their cache rows / id rows through e->slot_row, so the
@@ -726,12 +753,13 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   const bool f32 = dt == MT3_F32;
   // the decoder input row of this step (Embed(tok) + FixedEmbed[t]) is already in `y`: written by the
   // embed launch before the first step and by the previous step's argmax kernel afterwards
-  float* y = e->y + static_cast<size_t>(row0) * emb;
+  const mt3k::InputRow in = input_row(e, row0);
+  float* y = in.y;
   // residual rows as the norm-fused GEMMs see them: f32 with in-kernel statistics, or (split form) the
   // compute-type rows with the producer's partial sums (f32: the rows themselves)
-  char* y_ct = !split ? nullptr : f32 ? reinterpret_cast<char*>(y) : static_cast<char*>(e->y_ct) + static_cast<size_t>(row0) * emb * es;
-  char* y_copy = split && !f32 ? y_ct : nullptr;     // where producers of a residual row leave its bf16 copy
-  float* y_ss = split ? e->y_ss + static_cast<size_t>(row0) * (emb / 16) : nullptr;
+  char* y_copy = static_cast<char*>(in.y_ct);        // where producers of a residual row leave its bf16 copy
+  char* y_ct = !split ? nullptr : f32 ? reinterpret_cast<char*>(y) : y_copy;
+  float* y_ss = in.y_ss;
   auto normed = [&](const void* Wt, void* out, int N, int ldo) {
     mt3k::GemmArgs g = gemm_args(split ? static_cast<const void*>(y_ct) : static_cast<const void*>(y), Wt, out, rows, N,
                                  emb, ldo);
@@ -753,30 +781,21 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   char* attn_d = static_cast<char*>(e->attn_d) + static_cast<size_t>(row0) * hd * es;
   char* q_d = static_cast<char*>(e->q_d) + static_cast<size_t>(row0) * hd * es;
   char* h_d = static_cast<char*>(e->h_d) + static_cast<size_t>(row0) * c.mlp_dim * es;
-  float* qkvf = fold ? e->qkvf + static_cast<size_t>(row0) * 4 * hd : nullptr;
+  float* qkvf = in.rp.q_out;
   float* logits = e->logits + static_cast<size_t>(row0) * c.vocab_size;
   int* step = e->step + row0;                    // per-row position counters
   if (op == 8 * nl) {
     if (fold) return MT3_OK;                  // the logits projection rode in the last layer's MLP out-projection launch
     return mt3k::launch_gemm(dt, normed(e->logits_w, logits, c.vocab_size, c.vocab_size), !split, nrm, MT3_EPI_F32,
-                             small, s);
+                             true, s);
   }
   if (op == 8 * nl + 1 && (skip & kVarBeams)) {
     // k-beam search: the beam step, then the cache-row copies of the beams that forked
-    mt3k::BeamKArgs b = beam_args(e, row0, rows, (skip >> kVarBeamsShift) & 15);
+    mt3k::BeamKArgs b = beam_args(e, row0, rows, (skip >> kVarBeamsShift) & 15, done_slot);
     b.logits = logits;
-    b.n_done = e->n_done + done_slot;
-    b.table = e->embedding;
-    b.pos_table = e->pos_table;
-    b.max_pos = kMaxPos;
-    b.y_next = y;
-    b.y_ct = y_copy;
-    b.y_ss = y_ss;
-    b.dim = emb;
     b.max_len = (skip & kVarStream) ? e->stream_max_len : 0;
-    const mt3k::RowProj rp{e->ew0, e->pw0, qkvf, 4 * hd};
     const mt3k::LogitScale ls{fold ? y_ss : nullptr, emb / 16, emb};
-    MT3_TRY(mt3k::launch_beam_step(b, rp, ls, s));
+    MT3_TRY(mt3k::launch_beam_step(b, ls, s));
     mt3k::BeamReorderArgs r{};
     r.n_layers = nl;
     r.H = H;
@@ -795,20 +814,23 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     return mt3k::launch_beam_reorder(r, s);
   }
   if (op == 8 * nl + 1) {
-    const mt3k::BeamState beam{e->beam_f + row0, e->beam_len + row0, e->beam_cfg, c.max_batch, e->beam_len_row + crow0};
-    const mt3k::RowProj rp{e->ew0, e->pw0, qkvf, 4 * hd};
+    mt3k::ArgmaxStepArgs a{};
+    a.logits = logits;
+    a.vocab = c.vocab_size;
+    a.ids = e->ids + crow0 * Lmax;
+    a.ids_stride = Lmax;
+    a.st = slot_state(e, row0, done_slot);
+    a.in = in;
+    if (skip & kVarBeam) a.beam = beam1_state(e, row0, crow0);
+    if (skip & kVarForced) a.forced = e->forced + static_cast<size_t>(row0) * Lmax;
+    a.forced_stride = Lmax;
     // folded logits arrive unnormalised: the row scale comes from the final residual row's partial sums
-    const mt3k::LogitScale ls{fold ? y_ss : nullptr, emb / 16, emb};
+    a.ls = mt3k::LogitScale{fold ? y_ss : nullptr, emb / 16, emb};
     const bool streaming = (skip & kVarStream) != 0;
-    const mt3k::StepRetire rt{retire ? 1 : 0, retire ? e->slot_row + row0 : nullptr,
-                              (skip & kVarEos) ? e->eos_at + crow0 : nullptr, streaming ? e->slot_seg + row0 : nullptr,
-                              streaming ? e->stream_max_len : 0};
-    return mt3k::launch_argmax_step(logits, c.vocab_size, e->ids + crow0 * Lmax, Lmax,
-                                    e->cur_tok + row0, e->done + row0, e->n_done + done_slot, step, e->embedding, e->pos_table,
-                                    kMaxPos, y, y_copy, y_ss, emb, rows,
-                                    (skip & kVarBeam) ? &beam : nullptr,
-                                    (skip & kVarForced) ? e->forced + static_cast<size_t>(row0) * Lmax : nullptr, Lmax, rp, ls,
-                                    rt, s);
+    a.rt = mt3k::StepRetire{retire ? 1 : 0, retire ? a.st.slot_row : nullptr, (skip & kVarEos) ? e->eos_at + crow0 : nullptr,
+                            streaming ? a.st.slot_seg : nullptr, streaming ? e->stream_max_len : 0};
+    a.B = rows;
+    return mt3k::launch_argmax_step(a, s);
   }
   LayerDev& L = e->dec[op >> 3];
   switch (op & 7) {
@@ -818,9 +840,9 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
         mt3k::GemmArgs g = normed(L.wqkv_ext, qkv_d, 4 * hd, 3 * hd);
         g.out2 = e->qf + static_cast<size_t>(row0) * hd;
         g.n_split = 3 * hd;
-        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiStoreQ, small, s);
+        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiStoreQ, true, s);
       }
-      return mt3k::launch_gemm(dt, normed(L.wqkv, qkv_d, 3 * hd, 3 * hd), !split, nrm, MT3_EPI_STORE, small, s);
+      return mt3k::launch_gemm(dt, normed(L.wqkv, qkv_d, 3 * hd, 3 * hd), !split, nrm, MT3_EPI_STORE, true, s);
     case 1: {
       if (skip & 1) return MT3_OK;
       mt3k::DecAttnArgs a{};
@@ -859,12 +881,12 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
         g.out2 = fold ? qkvf + 3 * hd : e->qf + static_cast<size_t>(row0) * hd;
         g.ld2 = fold ? 4 * hd : 0;
         g.n_split = emb;
-        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, small, s);
+        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, true, s);
       }
-      return mt3k::launch_gemm(dt, resid(attn_d, L.wo, hd), false, 0, MT3_EPI_RESID, small, s);
+      return mt3k::launch_gemm(dt, resid(attn_d, L.wo, hd), false, 0, MT3_EPI_RESID, true, s);
     case 3:
       if (e->q_fold) return MT3_OK;           // folded into ops 0 and 2
-      return mt3k::launch_gemm(dt, normed(L.wq_x, q_d, hd, hd), !split, nrm, MT3_EPI_STORE, small, s);
+      return mt3k::launch_gemm(dt, normed(L.wq_x, q_d, hd, hd), !split, nrm, MT3_EPI_STORE, true, s);
     case 4: {
       if (skip & 2) return MT3_OK;
       mt3k::DecAttnArgs x{};
@@ -891,7 +913,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
       return mt3k::launch_decode_attention(dt, x, s);
     }
     case 5:
-      return mt3k::launch_gemm(dt, resid(attn_d, L.wo_x, hd), false, 0, MT3_EPI_RESID, small, s);
+      return mt3k::launch_gemm(dt, resid(attn_d, L.wo_x, hd), false, 0, MT3_EPI_RESID, true, s);
     case 6: {
       mt3k::GemmArgs g = normed(L.wi, h_d, 2 * c.mlp_dim, c.mlp_dim);
       g.concurrent = beside;
@@ -907,9 +929,9 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
         g.out2 = last ? logits : qkvf;
         g.ld2 = nx;
         g.n_split = 2 * c.mlp_dim;
-        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiGegluP, small, s);
+        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiGegluP, true, s);
       }
-      return mt3k::launch_gemm(dt, g, !split, nrm, MT3_EPI_GEGLU, small, s);
+      return mt3k::launch_gemm(dt, g, !split, nrm, MT3_EPI_GEGLU, true, s);
     }
     default:
       if (fold) {
@@ -922,15 +944,13 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
         g.out2 = last ? logits : qkvf;
         g.ld2 = nx;
         g.n_split = emb;
-        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, small, s);
+        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, true, s);
       }
-      return mt3k::launch_gemm(dt, resid(h_d, L.wo_mlp, c.mlp_dim), false, 0, MT3_EPI_RESID, small, s);
+      return mt3k::launch_gemm(dt, resid(h_d, L.wo_mlp, c.mlp_dim), false, 0, MT3_EPI_RESID, true, s);
   }
 }
 
-int enqueue_chain_step(mt3_engine* e, int row0, int rows, int chain, int B_total, int skip, hipStream_t s,
-                       int done_slot = 0) {
-  (void)chain;
+int enqueue_chain_step(mt3_engine* e, int row0, int rows, int B_total, int skip, hipStream_t s, int done_slot = 0) {
   for (int op = 0, n = chain_num_ops(e); op < n; ++op)
     MT3_TRY(enqueue_chain_op(e, row0, rows, B_total, skip, op, s, done_slot));
   return MT3_OK;
@@ -955,7 +975,7 @@ int enqueue_decode_step(mt3_engine* e, int B, int skip, int n, hipStream_t s) {
   for (int k = 0; k < n; ++k) {
     int row0, rows;
     chain_rows(B, n, k, &row0, &rows);
-    MT3_TRY(enqueue_chain_step(e, row0, rows, k, B, skip, s));
+    MT3_TRY(enqueue_chain_step(e, row0, rows, B, skip, s));
   }
   return MT3_OK;
 }
@@ -990,7 +1010,7 @@ int ensure_graph(mt3_engine* e, int B, int skip, int n) {
   for (int k = 0; k < n && he == hipSuccess && rc == MT3_OK; ++k) {
     int row0, rows;
     chain_rows(B, n, k, &row0, &rows);
-    rc = enqueue_chain_step(e, row0, rows, k, B, skip, e->cap_stream[k]);
+    rc = enqueue_chain_step(e, row0, rows, B, skip, e->cap_stream[k]);
   }
   // join
   for (int k = 1; k < n && he == hipSuccess && rc == MT3_OK; ++k) {
@@ -1561,7 +1581,7 @@ static hipGraphExec_t group_graph(mt3_engine* e, int variant, int batch, int row
     (void)hipGetLastError();
     return nullptr;
   }
-  const int rc = enqueue_chain_step(e, row0, rows, slot, batch, variant, cs, slot);
+  const int rc = enqueue_chain_step(e, row0, rows, batch, variant, cs, slot);
   hipGraph_t g = nullptr;
   hipGraphExec_t x = nullptr;
   const hipError_t end = hipStreamEndCapture(cs, &g);
@@ -1641,43 +1661,25 @@ struct Throttle {
 };
 
 static int compact_group(mt3_engine* e, const GroupRun& r, int cur) {
-  const mt3_engine_config& c = e->cfg;
   const size_t r0 = static_cast<size_t>(r.row0);
-  const int emb = c.emb_dim, n4 = 4 * e->HD();
   mt3k::CompactArgs a{};
-  a.done = e->done + r0;
-  a.slot_row = e->slot_row + r0;
-  a.step = e->step + r0;
-  a.cur_tok = e->cur_tok + r0;
+  a.st = slot_state(e, r.row0, r.slot);
+  a.in = input_row(e, r.row0);
+  const size_t emb = a.in.dim, n4 = a.in.rp.q_n;
   if (r.variant & kVarBeam) {
-    a.beam_f = e->beam_f + r0;
-    a.beam_len = e->beam_len + r0;
-    a.beam_rows = c.max_batch;
+    a.beam = beam1_state(e, r.row0, 0);
     a.s_beam = e->cs_beam + 2 * r0;
   }
-  a.y = e->y + r0 * emb;                                  // the arg-max kernel leaves the next input row in buffer 0
+  // scratch for the forms in use
   a.s_y = e->cs_y + r0 * emb;
-  if (e->y_split && c.compute_dtype == MT3_BF16) {
-    a.y_ct = static_cast<char*>(e->y_ct) + r0 * emb * 2;
-    a.s_y_ct = static_cast<char*>(e->cs_y_ct) + r0 * emb * 2;
-  }
-  if (e->y_split) {
-    a.y_ss = e->y_ss + r0 * (emb / 16);
-    a.s_y_ss = e->cs_y_ss + r0 * (emb / 16);
-  }
-  if (e->qkv_fold) {
-    a.qkvf = e->qkvf + r0 * n4;
-    a.s_qkvf = e->cs_qkvf + r0 * n4;
-  }
-  a.emb = emb;
-  a.q_n = n4;
+  if (a.in.y_ct) a.s_y_ct = static_cast<char*>(e->cs_y_ct) + r0 * emb * 2;
+  if (a.in.y_ss) a.s_y_ss = e->cs_y_ss + r0 * (emb / 16);
+  if (a.in.rp.q_out) a.s_qkvf = e->cs_qkvf + r0 * n4;
   a.s_int = e->cs_int + 4 * r0;
   a.perm = e->cs_perm + r0 + r.slot;
   a.rows = cur;
-  if (r.variant & kVarStream) {
-    a.slot_seg = e->slot_seg + r0;
-    a.s_seg = e->cs_seg + r0;
-  }
+  if (r.variant & kVarStream) a.s_seg = e->cs_seg + r0;
+  else a.st.slot_seg = nullptr;                           // no segments: the map does not travel
   return mt3k::launch_compact(a, r.s);
 }
 
@@ -1702,7 +1704,7 @@ static int run_group(mt3_engine* e, GroupRun& r) {
       }
     }
     if (r.use_graph) MT3_HIP_CHECK(hipGraphLaunch(exec, r.s));
-    else MT3_TRY(enqueue_chain_step(e, r.row0, cur, r.slot, r.batch, r.variant, r.s, r.slot));
+    else MT3_TRY(enqueue_chain_step(e, r.row0, cur, r.batch, r.variant, r.s, r.slot));
     ++r.ran;
     if (whole && t == 0 && r.d_first_logits)
       MT3_HIP_CHECK(hipMemcpyAsync(r.d_first_logits, e->logits, static_cast<size_t>(r.batch) * c.vocab_size * 4,
@@ -1882,9 +1884,7 @@ static int reset_slots(mt3_engine* e, int n, bool counters, bool ids, hipStream_
 
 // decoder input of step 0 for slots [0, n): Embed(BOS) + FixedEmbed[0]; later steps get theirs from the argmax kernel
 static int embed_bos(mt3_engine* e, int n, hipStream_t s) {
-  const mt3k::RowProj rp{e->ew0, e->pw0, e->qkv_fold ? e->qkvf : nullptr, 4 * e->HD()};
-  return mt3k::launch_embed(e->embedding, e->pos_table, e->cur_tok, e->step, e->y,
-                            e->cfg.compute_dtype == MT3_BF16 ? e->y_ct : nullptr, e->y_ss, n, e->cfg.emb_dim, rp, s);
+  return mt3k::launch_embed(input_row(e, 0), e->cur_tok, e->step, n, s);
 }
 
 // t5x beam_search(alpha = 0.6) with one beam (MT3_DECODE_BEAM1): live log-prob 0, nothing finished; the loop bound uses
@@ -2137,27 +2137,10 @@ static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_
 static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRange* rg, int32_t* d_out) {
   const mt3_engine_config& c = e->cfg;
   const size_t r0 = static_cast<size_t>(r.row0);
-  const int emb = c.emb_dim, n4 = 4 * e->HD();
   mt3k::RefillArgs a{};
-  a.done = e->done + r0;
-  a.slot_row = e->slot_row + r0;
-  a.slot_seg = e->slot_seg + r0;
-  a.step = e->step + r0;
-  a.cur_tok = e->cur_tok + r0;
-  a.n_done = e->n_done + r.slot;
-  if (r.variant & kVarBeam) {
-    a.beam_f = e->beam_f + r0;
-    a.beam_len = e->beam_len + r0;
-    a.beam_len_row = e->beam_len_row;
-    a.beam_rows = c.max_batch;
-  }
-  a.y = e->y + r0 * emb;                                   // the arg-max kernel leaves the next input row in buffer 0
-  if (e->y_split && c.compute_dtype == MT3_BF16) a.y_ct = static_cast<char*>(e->y_ct) + r0 * emb * 2;
-  if (e->y_split) a.y_ss = e->y_ss + r0 * (emb / 16);
-  a.emb = emb;
-  a.table = e->embedding;
-  a.pos = e->pos_table;
-  a.rp = mt3k::RowProj{e->ew0, e->pw0, e->qkv_fold ? e->qkvf + r0 * n4 : nullptr, n4};
+  a.st = slot_state(e, r.row0, r.slot);
+  a.in = input_row(e, r.row0);
+  if (r.variant & kVarBeam) a.beam = beam1_state(e, r.row0, 0);
   a.ids = e->ids;
   a.ids_stride = c.max_decode_len;
   a.out_ids = d_out;
@@ -2182,21 +2165,9 @@ struct BeamOut {
 // run `rg` of staged segments (rg == nullptr: hand-over only)
 static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* rg, int32_t* d_out, const BeamOut& bo) {
   const mt3_engine_config& c = e->cfg;
-  const size_t r0 = static_cast<size_t>(r.row0);
-  const int emb = c.emb_dim, n4 = 4 * e->HD();
   mt3k::BeamRefillArgs a{};
-  a.b = beam_args(e, r.row0, r.rows, bo.k);
-  a.b.n_done = e->n_done + r.slot;
-  a.b.table = e->embedding;
-  a.b.pos_table = e->pos_table;
-  a.b.max_pos = kMaxPos;
-  a.b.y_next = e->y + r0 * emb;
-  if (e->y_split && c.compute_dtype == MT3_BF16) a.b.y_ct = static_cast<char*>(e->y_ct) + r0 * emb * 2;
-  if (e->y_split) a.b.y_ss = e->y_ss + r0 * (emb / 16);
-  a.b.dim = emb;
-  a.rp = mt3k::RowProj{e->ew0, e->pw0, e->qkv_fold ? e->qkvf + r0 * n4 : nullptr, n4};
-  a.slot_seg = e->slot_seg + r0;
-  a.plan = e->refill_plan + r0 + r.slot;
+  a.b = beam_args(e, r.row0, r.rows, bo.k, r.slot);
+  a.plan = e->refill_plan + r.row0 + r.slot;
   a.L = c.max_decode_len;
   a.num_steps = r.num_steps;
   a.out_ids = d_out;
@@ -2272,7 +2243,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
       }
     }
     if (r.use_graph) MT3_HIP_CHECK(hipGraphLaunch(exec, r.s));
-    else MT3_TRY(enqueue_chain_step(e, r.row0, cur, r.slot, r.batch, r.variant, r.s, r.slot));
+    else MT3_TRY(enqueue_chain_step(e, r.row0, cur, r.batch, r.variant, r.s, r.slot));
     ++r.ran;
     if (t % kPoll != kPoll - 1) continue;
     // ---- the previous interval's snapshot

@@ -92,8 +92,6 @@ int launch_rmsnorm(int dtype, const float* x, const float* scale, void* out_ct, 
                    hipStream_t s);
 // x f32 [rows][dim] -> bf16 copy + per-16-column sums of squares (the split residual form, see GemmArgs)
 int launch_residual_split(const float* x, void* x_ct, float* x_ss, int rows, int dim, hipStream_t s);
-// y[b] = table[tok[b]] + pos[step[b]]
-// y_ct / y_ss (both or neither): bf16 copy of the rows and their per-16-column sums of squares (see GemmArgs)
 // first-layer projections by table lookup (the decoder's first QKV launch folded away): when q_out != nullptr the
 // kernels that produce a decoder input row Embed(tok) + FixedEmbed[t] also write its UNNORMALISED projection
 // q_out[b][0 .. q_n) = ew[tok] + pw[t]  (ew = embedding . W, pw = position table . W, both f32 [rows][q_n])
@@ -103,6 +101,28 @@ struct RowProj {
   float* q_out;
   int q_n;
 };
+// A decoder input row Embed(tok) + FixedEmbed[min(t, max_pos - 1)] and the forms it is written in (put_input_row,
+// decode_ops.hip; checked by one validator there).  The slot-indexed pointers are those of the step's or group's first slot.
+struct InputRow {
+  const float* table;   // token embedding [vocab][dim] (row 0 = BOS)
+  const float* pos;     // position table [max_pos][dim]
+  int max_pos;
+  float* y;             // [slots][dim] f32 rows (nullptr: the kernel writes no input row)
+  void* y_ct;           // bf16 copy (nullptr: f32 engine, or no split form)
+  float* y_ss;          // [slots][dim / 16] sums of squares of every 16-column group (nullptr: single residual stream)
+  int dim;
+  RowProj rp;           // q_out = the slots' layer-0 rows (nullptr: no qkv-fold)
+};
+// The per-slot state that lives from one step to the next.  Pointers of the step's or group's first slot (n_done: the
+// row group's counter of finished slots); a kernel reads the ones it needs.
+struct SlotState {
+  int* done;            // [slots] set once the slot has finished (EOS / search closed / out of positions)
+  int* slot_row;        // [slots] slot -> row of the caches and of `ids`
+  int* slot_seg;        // [slots] in-flight batching: the segment the slot decodes (-1: none)
+  int* step;            // [slots] position counter
+  int* cur_tok;         // [slots] input token of the next step
+  int* n_done;
+};
 // logits that arrive UNNORMALISED (the logits projection folded into the last layer's MLP out-projection launch): the
 // kernel that picks the token applies the decoder_norm row scale rsqrt(sum(ss[b][0 .. n_ss)) / dim + 1e-6) itself and
 // writes the scaled logits back (ss == nullptr: the logits are final)
@@ -111,8 +131,8 @@ struct LogitScale {
   int n_ss;
   int dim;
 };
-int launch_embed(const float* table, const float* pos, const int* tok, const int* step, float* y, void* y_ct,
-                 float* y_ss, int B, int dim, const RowProj& rp, hipStream_t s);
+// in.y[b] = table[tok[b]] + pos[step[b]] for b < B, in every form `in` holds
+int launch_embed(const InputRow& in, const int* tok, const int* step, int B, hipStream_t s);
 // per-row state of the beam-1 search (t5x beam_search, num_decodes = 1): f = [live_logp | best finished
 // score], the second array `rows` floats after the first; len = prefix length of the best finished
 // hypothesis or -1; cfg[0] = brevity_penalty(max_len + 1), cfg[1 + n] = brevity_penalty(n) (device memory)
@@ -152,30 +172,31 @@ struct StepRetire {
   const int* slot_seg;
   int max_len;
 };
-// token pick + bookkeeping for one decode step (see decode_ops.hip); beam == nullptr: greedy;
-// forced != nullptr (greedy only): teacher forcing, the next input token is forced[b * forced_stride + t]
-int launch_argmax_step(float* logits, int vocab, int* ids, int ids_stride, int* cur_tok, int* done,
-                       int* n_done, int* step, const float* table, const float* pos_table, int max_pos,
-                       float* y_next, void* y_ct, float* y_ss, int dim, int B, const BeamState* beam,
-                       const int* forced, int forced_stride, const RowProj& rp, const LogitScale& ls,
-                       const StepRetire& rt, hipStream_t s);
+// token pick + bookkeeping for one decode step (see decode_ops.hip): slot b < B picks from logits[b], writes
+// ids[row * ids_stride + t] and the next step's input row
+struct ArgmaxStepArgs {
+  float* logits;        // [B][vocab]
+  int vocab;
+  int* ids;
+  int ids_stride;
+  SlotState st;         // (slot_row / slot_seg are read through `rt`, which says whether they are in use)
+  InputRow in;
+  BeamState beam;       // f == nullptr: greedy
+  const int* forced;    // greedy only: teacher forcing, the next input token is forced[b * forced_stride + t]
+  int forced_stride;
+  LogitScale ls;
+  StepRetire rt;
+  int B;
+};
+int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that
 // lives from one step to the next -- the next step's input row in its three forms, layer 0's projected row, position
 // counter, current token, beam-search state, the slot -> row map -- moves from slot perm[i] to slot i (i < n_live) by
 // way of a scratch copy; slots [n_live, rows) are marked done.  All pointers are those of the group's first slot.
 struct CompactArgs {
-  int* done;
-  int* slot_row;
-  int* step;
-  int* cur_tok;
-  float* beam_f;        // [2][beam_rows] (nullptr: greedy)
-  int* beam_len;
-  int beam_rows;
-  float* y;             // [rows][emb] f32 input rows of the next step
-  void* y_ct;           // bf16 copy (nullptr: f32 engine)
-  float* y_ss;          // [rows][emb / 16] (nullptr: single residual stream)
-  float* qkvf;          // [rows][q_n] (nullptr: no qkv-fold)
-  int emb, q_n;
+  SlotState st;         // slot_seg == nullptr: no in-flight batching (a dropped slot decodes nothing: -1)
+  InputRow in;          // y / y_ct / y_ss / rp.q_out (each nullptr: not in use), dim, rp.q_n
+  BeamState beam;       // f == nullptr: greedy (f and len travel with the slot)
   // scratch of the same shapes (slot-indexed from the group's first slot as well)
   float* s_y;
   void* s_y_ct;
@@ -183,11 +204,9 @@ struct CompactArgs {
   float* s_qkvf;
   int* s_int;           // [rows][4]: slot_row, step, cur_tok, beam_len
   float* s_beam;        // [rows][2]
+  int* s_seg;           // [rows]
   int* perm;            // [rows + 1]: perm[i] = source slot of new slot i; perm[rows] = n_live
   int rows;             // slots of the group in use before the compaction
-  // in-flight batching: the slot -> segment map travels with the slot; a dropped slot decodes nothing (-1)
-  int* slot_seg;        // (nullptr: not in use)
-  int* s_seg;           // scratch [rows]
 };
 int launch_compact(const CompactArgs& c, hipStream_t s);
 // Refill of finished slots (in-flight batching, mt3_engine_transcribe): at a poll of a row group's loop every FINISHED
@@ -212,23 +231,9 @@ struct StagedCross {
   size_t row_bytes, sc_bytes;
 };
 struct RefillArgs {
-  int* done;
-  int* slot_row;
-  int* slot_seg;
-  int* step;
-  int* cur_tok;
-  int* n_done;          // the group's counter of finished slots: decremented by the number of slots refilled
-  float* beam_f;        // [2][beam_rows] (nullptr: greedy)
-  int* beam_len;
-  int* beam_len_row;    // batch base
-  int beam_rows;
-  float* y;             // [rows][emb] f32 input rows of the next step
-  void* y_ct;           // bf16 copy (nullptr: f32 engine)
-  float* y_ss;          // (nullptr: single residual stream)
-  int emb;
-  const float* table;   // token embedding (row 0 = BOS) and position table (row 0)
-  const float* pos;
-  RowProj rp;           // q_out = the group's qkvf rows (nullptr: no qkv-fold)
+  SlotState st;         // n_done is decremented by the number of slots refilled
+  InputRow in;          // the BOS row is in.table[0] + in.pos[0]
+  BeamState beam;       // f == nullptr: greedy; len_row is the batch base
   int* ids;             // engine id rows [max_batch][ids_stride] (batch base)
   int ids_stride;
   int* out_ids;         // caller's [n_segments][ids_stride]
@@ -247,6 +252,9 @@ constexpr float kBeamNegInf = -1.0e7f;       // t5x decoding.NEG_INF
 struct BeamKArgs {
   float* logits;
   int vocab, k, elems;
+  SlotState st;         // slot_row is rewritten (a beam takes over its parent's row); done is set for all k slots once the
+                        // element is retired, n_done then grows by k
+  InputRow in;          // the next step's input rows
   float* live;          // [slots] running log-prob of each live beam, best first within an element
   float* fin_score;     // [slots] the element's k finished entries, best first (kBeamNegInf: unfilled)
   int* fin_step;        // [slots] step of the entry's EOS (-1: unfilled)
@@ -254,27 +262,15 @@ struct BeamKArgs {
   int* hist_par;        // [L][hist_stride] parent beam of the new beam in each slot
   int* hist_tok;        // [L][hist_stride] its token
   int hist_stride;
-  int* slot_row;        // [slots] slot -> self-attention cache row (rewritten: a beam takes over its parent's row)
   int* fork_src;        // [slots] row to copy positions [0, t] from into the slot's new row (-1: no copy)
   int* fork_count;      // running count of forks (copies)
-  int* done;            // [slots] set for all k slots once the element is retired
-  int* n_done;          // finished slots of the row group (+k per retired element)
-  int* step;
-  int* cur_tok;
   const float* bp;      // BeamState::cfg
-  const float* table;
-  const float* pos_table;
-  int max_pos;
-  float* y_next;
-  void* y_ct;
-  float* y_ss;
-  int dim;
   // > 0 (mt3_engine_transcribe_beams): an element whose position counter reaches max_len is closed whether or not its
   // search has -- its k slots are marked done and counted, its live and finished sets stay as the step left them (in
   // mt3_engine_decode_beams the host loop's bound does that: it passes 0)
   int max_len;
 };
-int launch_beam_step(const BeamKArgs& a, const RowProj& rp, const LogitScale& ls, hipStream_t s);
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, hipStream_t s);
 // copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
 // (and e4m3 scale rows), for every slot that forked this step; the grid covers every slot x layer x head
 struct BeamReorderArgs {
@@ -297,8 +293,8 @@ int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int
 // counterpart of launch_refill, three launches on the group's stream at a poll of the group's loop.
 //   plan   refill_plan_kernel over elements (an element is finished when its first slot is done): plan[i] = i-th finished
 //          element, plan[elems] = how many; the group's counter of finished slots drops by k per restarted element
-//   cross  the cross-attention K/V (and e4m3 scale rows) of segment first_seg + i from the staging chunk into EACH of the k
-//          cache rows slot_row[s0 .. s0 + k) of element plan[i]: every 16-byte piece is loaded once and stored k times
+//   cross  refill_cross_kernel with unit = k: the cross-attention K/V (and e4m3 scale rows) of segment first_seg + i from
+//          the staging chunk into EACH of the k cache rows slot_row[s0 .. s0 + k) of element plan[i]
 //   elem   block i: the k decodes of element plan[i] are walked back from the history (beam_finalize_kernel's walk, on a
 //          copy of the element's history columns in LDS) straight into the caller's rows of the segment it held; then,
 //          i < n_new: the element restarts on segment first_seg + i (live = [0, NEG_INF, ...], nothing finished, position 0,
@@ -307,9 +303,7 @@ int launch_beam_finalize(const BeamKArgs& a, int L, int num_steps, int* ids, int
 // b: the group's beam state (pointers of the group's first slot, b.elems = elements of the group); the self-attention
 // caches need nothing: an element's slot_row entries stay a permutation of its own k rows.
 struct BeamRefillArgs {
-  BeamKArgs b;
-  RowProj rp;           // q_out = the group's qkvf rows (nullptr: no qkv-fold)
-  int* slot_seg;        // [slots] segment an element is decoding, in all k of its slots (-1: none)
+  BeamKArgs b;          // b.st.slot_seg: the segment an element is decoding, in all k of its slots (-1: none)
   int* plan;            // [elems + 1] scratch
   int L, num_steps;     // id row length; steps per segment of the job
   int* out_ids;         // caller's [n_segments][L]
