@@ -604,6 +604,102 @@ int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esi
                         void* const* h_v, void* const* h_scale, const int32_t* d_fork_src, const int32_t* d_slot_row,
                         const int32_t* d_step, const int32_t* d_done, void* stream);
 
+/* The slot-moving launches of the decode loop on SCRIPTED slot state: the input-row writer (every decode step, refill),
+ * the compaction of row retirement (MT3_DECODE_EARLY_EXIT) and the refills of in-flight batching
+ * (mt3_engine_transcribe, mt3_engine_transcribe_beams), each alone on device memory the CALLER owns and has filled
+ * (tests/test_gpu_slot_moves.py).  Test drivers: scratch the caller has no business with (the plan / permutation, the
+ * compaction's scratch rows) is allocated, 0xFF-filled and freed by the call, which synchronises `stream` before it
+ * returns.  Every argument error -- what the launch itself refuses, a missing pointer, a size out of range -- returns
+ * MT3_ERR_INVALID before anything touches a device.  The views below mirror the engine's own descriptions; pointers
+ * are those of the first slot of the region the call works on, optional ones may be NULL.
+ *
+ * mt3_input_row_view: a decoder input row table[tok] + pos[min(t, max_pos - 1)] and the forms it is written in: y f32
+ * [slots][dim]; y_ct its bf16 copy (round to nearest even); y_ss [slots][dim / 16] the sums of squares of each 16-column
+ * group (y_ct needs y_ss, both need dim % 16 == 0; y alone dim % 4 == 0); q_out [slots][q_n] = ew[tok] + pw[min(t,
+ * max_pos - 1)] (q_n % 4 == 0; needs ew, pw and y). */
+typedef struct mt3_input_row_view {
+  const float* table;
+  const float* pos;
+  int32_t max_pos, dim;
+  float* y;
+  void* y_ct;
+  float* y_ss;
+  const float* ew;
+  const float* pw;
+  float* q_out;
+  int32_t q_n, reserved;
+} mt3_input_row_view;
+/* per-slot int32 state: done flag, slot -> row of the caches and id rows, segment the slot decodes (-1: none), position
+ * counter, next input token; n_done: the group's counter of finished slots (one int32) */
+typedef struct mt3_slot_state_view {
+  int32_t* done;
+  int32_t* slot_row;
+  int32_t* slot_seg;
+  int32_t* step;
+  int32_t* cur_tok;
+  int32_t* n_done;
+} mt3_slot_state_view;
+/* staged cross-attention K/V of a run of segments and the caches they go to.  src / dst / src_sc / dst_sc: HOST arrays
+ * of n_layers (<= 16) device pointers: per layer, staging chunk [2][src_batch][row_bytes] (the run starts at entry
+ * src_entry0) -> cache [2][dst_batch][row_bytes], and scale rows [src_batch][sc_bytes] -> [dst_batch][sc_bytes] where
+ * src_sc != NULL and src_sc[l] != NULL.  row_bytes and sc_bytes are multiples of 16. */
+typedef struct mt3_staged_cross_view {
+  int32_t n_layers, src_batch, src_entry0, dst_batch;
+  uint64_t row_bytes, sc_bytes;
+  const void* const* src;
+  void* const* dst;
+  const void* const* src_sc;
+  void* const* dst_sc;
+} mt3_staged_cross_view;
+/* state of the k-beam search over `elems` elements of k slots (slot = element * k + beam): live log-probs, the finished
+ * entries best first (score, step of the EOS or -1, beam whose prefix it ends), the history [L][hist_stride] of parent
+ * beam and token per step and slot, the pending fork sources */
+typedef struct mt3_beam_k_view {
+  int32_t k, elems, vocab, hist_stride;
+  float* live;
+  float* fin_score;
+  int32_t* fin_step;
+  int32_t* fin_beam;
+  int32_t* hist_par;
+  int32_t* hist_tok;
+  int32_t* fork_src;
+} mt3_beam_k_view;
+/* in->y[r] (and the other forms `in` holds) = the input row of token d_tok[r] at position d_t[r], r < rows */
+int mt3_op_embed_rows(const mt3_input_row_view* in, const int32_t* d_tok, const int32_t* d_t, int32_t rows,
+                      void* stream);
+/* Row retirement over slots [0, rows): the state of the i-th live slot (done == 0, ascending) moves to slot i -- in->y,
+ * y_ct, y_ss, q_out (tables unused; dim % 16 == 0; y_ct needs y_ss, as everywhere), slot_row, step, cur_tok, slot_seg (optional) and, with d_beam_f, the
+ * beam-1 state d_beam_f[slot], d_beam_f[beam_rows + slot] (beam_rows >= rows) and d_beam_len[slot]; done becomes 0 for
+ * the n live slots and 1 for slots [n, rows), whose slot_seg becomes -1 and whose other state keeps its bytes.
+ * h_perm (host, optional) [rows + 1]: the permutation, h_perm[i < n] = source of slot i, h_perm[rows] = n (entries
+ * [n, rows) are not written: 0xFF bytes). */
+int mt3_op_slot_compact(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f, int32_t beam_rows,
+                        int32_t* d_beam_len, int32_t rows, int32_t* h_perm, void* stream);
+/* The refill of mt3_engine_transcribe over slots [0, rows): every finished slot with slot_seg >= 0 hands id row
+ * d_ids[slot_row] ([..][ids_stride]) to d_out_ids[slot_seg] (with d_beam_f and n = d_beam_len_row[row] >= 0: ids[:n], 1,
+ * zeros); the first n_new finished slots restart on segments first_seg, first_seg + 1, ... (zeroed id row, counters,
+ * beam-1 state, the BOS row in every form of `in`, the staged cross K/V of entry src_entry0 + i of `x` into cache row
+ * slot_row[slot]); the others get slot_seg = -1; *n_done drops by the number restarted.  d_beam_f needs d_beam_len
+ * and d_beam_len_row (indexed by row).  x may be NULL when n_new == 0.  h_plan (host, optional) [rows + 1]: the finished
+ * slots ascending, h_plan[rows] = how many. */
+int mt3_op_slot_refill(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f, int32_t beam_rows,
+                       int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids, int32_t ids_stride,
+                       int32_t* d_out_ids, int32_t rows, int32_t n_new, int32_t first_seg,
+                       const mt3_staged_cross_view* x, int32_t* h_plan, void* stream);
+/* The refill of mt3_engine_transcribe_beams over b->elems elements: every finished element (first slot done) with
+ * slot_seg >= 0 has its k decodes walked back from the history into d_out_all[seg] [k][L] / d_out_scores[seg] [k]
+ * (increasing score; optional) and the best into d_out_ids[seg] [L]; the first n_new restart (live = [0, -1e7, ...],
+ * nothing finished, no fork pending, BOS rows, the staged cross K/V into each of the element's k cache rows); *n_done
+ * drops by k per restarted element.  vocab <= 2048, k <= 8, num_steps <= L, (num_steps + L) * k * 2 <= 65536. */
+int mt3_op_beam_refill(const mt3_beam_k_view* b, const mt3_slot_state_view* st, const mt3_input_row_view* in, int32_t L,
+                       int32_t num_steps, int32_t* d_out_ids, int32_t* d_out_all, float* d_out_scores, int32_t n_new,
+                       int32_t first_seg, const mt3_staged_cross_view* x, int32_t* h_plan, void* stream);
+/* start of an mt3_engine_transcribe_beams job: done = 1, slot_seg = fork_src = -1, slot_row = slot for slots [0, slots);
+ * d_n_done[g] = h_group_slots[g] for g < groups (1 .. 4; host array) */
+int mt3_op_beam_stream_init(int32_t* d_done, int32_t* d_slot_seg, int32_t* d_fork_src, int32_t* d_slot_row,
+                            int32_t* d_n_done, int32_t slots, int32_t groups, const int32_t* h_group_slots,
+                            void* stream);
+
 /* The statistics kernel of mt3_engine_score_segments on SCRIPTED logits (t5x score_batch's log-softmax / gather with
  * the row's arg-max next to it): per row, token score = (logits[target] - logsumexp(logits)) * weight with the bits
  * mt3_engine_score gives for the same logits, top-1 id = the arg-max (lowest id on equal logits), top-1 score =

@@ -71,8 +71,31 @@ class NoteStruct(C.Structure):
                 ("instrument", C.c_int32), ("reserved", C.c_int32)]
 
 
-# every symbol include/mt3_hip.h and include/mt3_hip_debug.h declare: (name, restype, argtypes)
 _P = C.c_void_p
+
+
+# the views of the slot-move test drivers (mt3_op_embed_rows ... mt3_op_beam_stream_init)
+class InputRowView(C.Structure):               # mt3_input_row_view
+    _fields_ = [("table", _P), ("pos", _P), ("max_pos", C.c_int32), ("dim", C.c_int32), ("y", _P), ("y_ct", _P),
+                ("y_ss", _P), ("ew", _P), ("pw", _P), ("q_out", _P), ("q_n", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SlotStateView(C.Structure):              # mt3_slot_state_view
+    _fields_ = [(n, _P) for n in ("done", "slot_row", "slot_seg", "step", "cur_tok", "n_done")]
+
+
+class StagedCrossView(C.Structure):            # mt3_staged_cross_view
+    _fields_ = [(n, C.c_int32) for n in ("n_layers", "src_batch", "src_entry0", "dst_batch")] + \
+               [("row_bytes", C.c_uint64), ("sc_bytes", C.c_uint64)] + \
+               [(n, C.POINTER(_P)) for n in ("src", "dst", "src_sc", "dst_sc")]
+
+
+class BeamKView(C.Structure):                  # mt3_beam_k_view
+    _fields_ = [(n, C.c_int32) for n in ("k", "elems", "vocab", "hist_stride")] + \
+               [(n, _P) for n in ("live", "fin_score", "fin_step", "fin_beam", "hist_par", "hist_tok", "fork_src")]
+
+
+# every symbol include/mt3_hip.h and include/mt3_hip_debug.h declare: (name, restype, argtypes)
 SIGNATURES = {
     "mt3_last_error": (C.c_char_p, []),
     "mt3_abi_version": (C.c_int, []),
@@ -132,6 +155,14 @@ SIGNATURES = {
                                               C.c_int32, _P, _P, _P]),
     "mt3_op_beam_reorder": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P),
                                       C.POINTER(_P), _P, _P, _P, _P, _P]),
+    "mt3_op_embed_rows": (C.c_int, [C.POINTER(InputRowView), _P, _P, C.c_int32, _P]),
+    "mt3_op_slot_compact": (C.c_int, [C.POINTER(SlotStateView), C.POINTER(InputRowView), _P, C.c_int32, _P, C.c_int32, _P,
+                                      _P]),
+    "mt3_op_slot_refill": (C.c_int, [C.POINTER(SlotStateView), C.POINTER(InputRowView), _P, C.c_int32, _P, _P, _P,
+                                     C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(StagedCrossView), _P, _P]),
+    "mt3_op_beam_refill": (C.c_int, [C.POINTER(BeamKView), C.POINTER(SlotStateView), C.POINTER(InputRowView), C.c_int32,
+                                     C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(StagedCrossView), _P, _P]),
+    "mt3_op_beam_stream_init": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "mt3_host_mx8_quantize": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
     "mt3_op_mx8_quantize": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_op_gemm_mx8": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,

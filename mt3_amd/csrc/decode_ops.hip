@@ -992,6 +992,7 @@ __global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a)
     if (tid < k && a.out_scores) a.out_scores[static_cast<size_t>(seg_old) * k + tid] = score;
   }
   const bool restart = i < a.n_new;
+  __syncthreads();                  // every wave has read the old segment before threads < k write the new one
   if (tid < k) {
     const int slot = s0 + tid;
     a.b.st.slot_seg[slot] = restart ? a.first_seg + i : -1;
@@ -1141,7 +1142,7 @@ namespace {
     if (_rc != MT3_OK) return _rc;  \
   } while (0)
 
-// one zero-filled device allocation carved into 256-byte aligned pieces; freed when the call returns
+// one zero-filled (or `fill`-filled) device allocation carved into 256-byte aligned pieces; freed when the call returns
 struct Scratch {
   char* base = nullptr;
   size_t size = 0, used = 0;
@@ -1149,10 +1150,10 @@ struct Scratch {
     if (base) (void)hipFree(base);
   }
   static size_t piece(size_t bytes) { return (bytes + 255) / 256 * 256; }
-  int alloc(size_t bytes, hipStream_t s) {
+  int alloc(size_t bytes, hipStream_t s, int fill = 0) {
     MT3_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&base), bytes));
     size = bytes;
-    MT3_HIP_CHECK(hipMemsetAsync(base, 0, bytes, s));
+    MT3_HIP_CHECK(hipMemsetAsync(base, fill, bytes, s));
     return MT3_OK;
   }
   template <typename T>
@@ -1324,5 +1325,225 @@ extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int
   r.done = d_done;
   MT3_OP_TRY(mt3k::launch_beam_reorder(r, static_cast<hipStream_t>(stream)));
   MT3_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  return MT3_OK;
+}
+
+// ------------------------------------------------------------------ drivers of the slot-moving launches
+// mt3_op_embed_rows / mt3_op_slot_compact / mt3_op_slot_refill / mt3_op_beam_refill / mt3_op_beam_stream_init
+// (mt3_hip.h): the launchers above, unchanged, on slot state the caller owns.  Everything a launcher refuses is refused
+// here first, before the driver's own scratch is allocated.
+namespace {
+
+mt3k::InputRow input_row_of(const mt3_input_row_view& v) {
+  mt3k::InputRow r{};
+  r.table = v.table;
+  r.pos = v.pos;
+  r.max_pos = v.max_pos;
+  r.y = v.y;
+  r.y_ct = v.y_ct;
+  r.y_ss = v.y_ss;
+  r.dim = v.dim;
+  r.rp = mt3k::RowProj{v.ew, v.pw, v.q_out, v.q_n};
+  return r;
+}
+
+mt3k::SlotState slot_state_of(const mt3_slot_state_view& v) {
+  return mt3k::SlotState{v.done, v.slot_row, v.slot_seg, v.step, v.cur_tok, v.n_done};
+}
+
+// a written input row in the split-capable layout the slot movers take: the row, its tables, dim % 16 == 0
+bool bad_written_row(const mt3k::InputRow& r) {
+  return !r.y || !r.table || !r.pos || r.max_pos < 1 || r.dim <= 0 || r.dim % 16 || (r.y_ct && !r.y_ss) ||
+         (r.rp.q_out && (!r.rp.ew || !r.rp.pw || r.rp.q_n <= 0 || r.rp.q_n % 4));
+}
+
+// MT3_OK and `out` filled, or what is wrong with a staged-cross view of n_new segments (unused when n_new == 0)
+int staged_cross_of(const mt3_staged_cross_view* v, int n_new, const char* who, mt3k::StagedCross* out) {
+  *out = mt3k::StagedCross{};
+  if (n_new <= 0) return MT3_OK;
+  const std::string w(who);
+  if (!v || !v->src || !v->dst) return mt3::fail(MT3_ERR_INVALID, w + ": segments to hand out need a staging chunk");
+  if (v->n_layers <= 0 || v->n_layers > mt3k::kRefillMaxLayers || v->row_bytes == 0 || v->row_bytes % 16 ||
+      v->sc_bytes % 16 || v->src_batch <= 0 || v->dst_batch <= 0 || v->src_entry0 < 0 ||
+      static_cast<long long>(v->src_entry0) + n_new > v->src_batch)
+    return mt3::fail(MT3_ERR_INVALID, w + ": bad staging chunk");
+  out->n_layers = v->n_layers;
+  out->src_batch = v->src_batch;
+  out->src_entry0 = v->src_entry0;
+  out->dst_batch = v->dst_batch;
+  out->row_bytes = v->row_bytes;
+  out->sc_bytes = v->sc_bytes;
+  for (int l = 0; l < v->n_layers; ++l) {
+    out->src[l] = static_cast<const char*>(v->src[l]);
+    out->dst[l] = static_cast<char*>(v->dst[l]);
+    out->src_sc[l] = v->src_sc ? static_cast<const char*>(v->src_sc[l]) : nullptr;
+    out->dst_sc[l] = v->dst_sc ? static_cast<char*>(v->dst_sc[l]) : nullptr;
+    if (!out->src[l] || !out->dst[l]) return mt3::fail(MT3_ERR_INVALID, w + ": missing staging chunk or cache of a layer");
+    if (out->src_sc[l] && (!out->dst_sc[l] || v->sc_bytes == 0))
+      return mt3::fail(MT3_ERR_INVALID, w + ": staged scale rows need their cache rows and sc_bytes");
+  }
+  return MT3_OK;
+}
+
+constexpr int kOpMaxSlots = 1 << 16;
+
+}  // namespace
+
+extern "C" int mt3_op_embed_rows(const mt3_input_row_view* in, const int32_t* d_tok, const int32_t* d_t, int32_t rows,
+                                 void* stream) {
+  if (!in || !in->y || !d_tok || !d_t) return mt3::fail(MT3_ERR_INVALID, "mt3_op_embed_rows: null argument");
+  if (rows <= 0 || rows > kOpMaxSlots) return mt3::fail(MT3_ERR_INVALID, "mt3_op_embed_rows: 1 .. 65536 rows");
+  if (in->q_out && in->q_n <= 0) return mt3::fail(MT3_ERR_INVALID, "mt3_op_embed_rows: the row projection needs q_n > 0");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MT3_OP_TRY(mt3k::launch_embed(input_row_of(*in), d_tok, d_t, rows, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
+  return MT3_OK;
+}
+
+extern "C" int mt3_op_slot_compact(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f,
+                                   int32_t beam_rows, int32_t* d_beam_len, int32_t rows, int32_t* h_perm, void* stream) {
+  if (!st || !in || !st->done || !st->slot_row || !st->step || !st->cur_tok || !in->y)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_compact: null argument");
+  if (rows <= 0 || rows > kOpMaxSlots || in->dim <= 0 || in->dim % 16 || (in->q_out && (in->q_n <= 0 || in->q_n % 4)) ||
+      (in->y_ct && !in->y_ss))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_compact: 1 .. 65536 rows, dim % 16 == 0, q_n % 4 == 0, y_ss with y_ct");
+  if (d_beam_f ? (!d_beam_len || beam_rows < rows) : d_beam_len != nullptr)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_compact: the beam state is f (two arrays beam_rows >= rows apart) "
+                                      "and len, together");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t n = static_cast<size_t>(rows), dim = static_cast<size_t>(in->dim);
+  const size_t q_n = in->q_out ? static_cast<size_t>(in->q_n) : 0;
+  Scratch m;
+  MT3_OP_TRY(m.alloc(Scratch::piece(n * dim * 4) + Scratch::piece(n * dim * 2) + Scratch::piece(n * dim / 16 * 4) +
+                         Scratch::piece(n * q_n * 4) + Scratch::piece(n * 16) + Scratch::piece(n * 8) +
+                         Scratch::piece(n * 4) + Scratch::piece((n + 1) * 4),
+                     s, 0xFF));
+  mt3k::CompactArgs c{};
+  c.st = slot_state_of(*st);
+  c.in = input_row_of(*in);
+  if (!in->q_out) c.in.rp = mt3k::RowProj{};
+  c.beam = mt3k::BeamState{d_beam_f, d_beam_len, nullptr, beam_rows, nullptr};
+  // the scatter pass reads a form back from its scratch wherever that scratch exists: a form that is not in use has none
+  c.s_y = m.take<float>(n * dim);
+  unsigned short* s_y_ct = m.take<unsigned short>(n * dim);
+  float* s_y_ss = m.take<float>(n * dim / 16);
+  float* s_qkvf = m.take<float>(n * q_n);
+  c.s_y_ct = in->y_ct ? s_y_ct : nullptr;
+  c.s_y_ss = in->y_ss ? s_y_ss : nullptr;
+  c.s_qkvf = in->q_out ? s_qkvf : nullptr;
+  c.s_int = m.take<int>(n * 4);
+  c.s_beam = m.take<float>(n * 2);
+  c.s_seg = m.take<int>(n);
+  c.perm = m.take<int>(n + 1);
+  c.rows = rows;
+  MT3_OP_TRY(mt3k::launch_compact(c, s));
+  if (h_perm) MT3_HIP_CHECK(hipMemcpyAsync(h_perm, c.perm, (n + 1) * 4, hipMemcpyDeviceToHost, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
+  return MT3_OK;
+}
+
+extern "C" int mt3_op_slot_refill(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f,
+                                  int32_t beam_rows, int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids,
+                                  int32_t ids_stride, int32_t* d_out_ids, int32_t rows, int32_t n_new, int32_t first_seg,
+                                  const mt3_staged_cross_view* x, int32_t* h_plan, void* stream) {
+  if (!st || !in || !st->done || !st->slot_row || !st->slot_seg || !st->step || !st->cur_tok || !st->n_done || !d_ids ||
+      !d_out_ids)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: null argument");
+  if (rows <= 0 || rows > kOpMaxSlots || n_new < 0 || n_new > rows || ids_stride <= 0 || first_seg < 0)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: 1 .. 65536 rows, 0 <= n_new <= rows, ids_stride > 0, "
+                                      "first_seg >= 0");
+  if (d_beam_f ? (!d_beam_len || !d_beam_len_row || beam_rows < rows) : (d_beam_len || d_beam_len_row))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: the beam state is f (two arrays beam_rows >= rows apart), "
+                                      "len and len_row, together");
+  mt3k::RefillArgs a{};
+  a.in = input_row_of(*in);
+  if (bad_written_row(a.in))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: the input row needs y, its tables, dim % 16 == 0, y_ss with "
+                                      "y_ct, and ew / pw / q_n % 4 == 0 with q_out");
+  MT3_OP_TRY(staged_cross_of(x, n_new, "mt3_op_slot_refill", &a.x));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t n = static_cast<size_t>(rows);
+  Scratch m;
+  MT3_OP_TRY(m.alloc(Scratch::piece((n + 1) * 4), s, 0xFF));
+  a.st = slot_state_of(*st);
+  a.beam = mt3k::BeamState{d_beam_f, d_beam_len, nullptr, beam_rows, d_beam_len_row};
+  a.ids = d_ids;
+  a.ids_stride = ids_stride;
+  a.out_ids = d_out_ids;
+  a.plan = m.take<int>(n + 1);
+  a.rows = rows;
+  a.n_new = n_new;
+  a.first_seg = first_seg;
+  MT3_OP_TRY(mt3k::launch_refill(a, s));
+  if (h_plan) MT3_HIP_CHECK(hipMemcpyAsync(h_plan, a.plan, (n + 1) * 4, hipMemcpyDeviceToHost, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
+  return MT3_OK;
+}
+
+extern "C" int mt3_op_beam_refill(const mt3_beam_k_view* b, const mt3_slot_state_view* st, const mt3_input_row_view* in,
+                                  int32_t L, int32_t num_steps, int32_t* d_out_ids, int32_t* d_out_all,
+                                  float* d_out_scores, int32_t n_new, int32_t first_seg, const mt3_staged_cross_view* x,
+                                  int32_t* h_plan, void* stream) {
+  if (!b || !st || !in || !b->live || !b->fin_score || !b->fin_step || !b->fin_beam || !b->hist_par || !b->hist_tok ||
+      !b->fork_src || !st->done || !st->slot_row || !st->slot_seg || !st->step || !st->cur_tok || !st->n_done || !d_out_ids)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_refill: null argument");
+  if (b->k < 1 || b->k > mt3k::kBeamMaxK || b->vocab < 1 || b->vocab > 2048)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_refill: k must be 1 .. 8 and vocab <= 2048");
+  if (b->elems <= 0 || b->elems > kOpMaxSlots / mt3k::kBeamMaxK || b->hist_stride < b->elems * b->k || n_new < 0 ||
+      n_new > b->elems || first_seg < 0)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_refill: 1 .. 8192 elems, hist_stride >= elems * k, 0 <= n_new <= "
+                                      "elems, first_seg >= 0");
+  if (L <= 0 || num_steps <= 0 || num_steps > L)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_refill: 1 <= num_steps <= L");
+  if ((static_cast<size_t>(num_steps) + L) * b->k * sizeof(unsigned short) > 65536)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_refill: history and decodes of an element exceed 64 KB of LDS");
+  mt3k::BeamRefillArgs a{};
+  a.b.in = input_row_of(*in);
+  if (bad_written_row(a.b.in))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_refill: the input row needs y, its tables, dim % 16 == 0, y_ss with "
+                                      "y_ct, and ew / pw / q_n % 4 == 0 with q_out");
+  MT3_OP_TRY(staged_cross_of(x, n_new, "mt3_op_beam_refill", &a.x));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t n = static_cast<size_t>(b->elems);
+  Scratch m;
+  MT3_OP_TRY(m.alloc(Scratch::piece((n + 1) * 4), s, 0xFF));
+  a.b.vocab = b->vocab;
+  a.b.k = b->k;
+  a.b.elems = b->elems;
+  a.b.st = slot_state_of(*st);
+  a.b.live = b->live;
+  a.b.fin_score = b->fin_score;
+  a.b.fin_step = b->fin_step;
+  a.b.fin_beam = b->fin_beam;
+  a.b.hist_par = b->hist_par;
+  a.b.hist_tok = b->hist_tok;
+  a.b.hist_stride = b->hist_stride;
+  a.b.fork_src = b->fork_src;
+  a.plan = m.take<int>(n + 1);
+  a.L = L;
+  a.num_steps = num_steps;
+  a.out_ids = d_out_ids;
+  a.out_all = d_out_all;
+  a.out_scores = d_out_scores;
+  a.n_new = n_new;
+  a.first_seg = first_seg;
+  MT3_OP_TRY(mt3k::launch_beam_refill(a, s));
+  if (h_plan) MT3_HIP_CHECK(hipMemcpyAsync(h_plan, a.plan, (n + 1) * 4, hipMemcpyDeviceToHost, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
+  return MT3_OK;
+}
+
+extern "C" int mt3_op_beam_stream_init(int32_t* d_done, int32_t* d_slot_seg, int32_t* d_fork_src, int32_t* d_slot_row,
+                                       int32_t* d_n_done, int32_t slots, int32_t groups, const int32_t* h_group_slots,
+                                       void* stream) {
+  if (!d_done || !d_slot_seg || !d_fork_src || !d_slot_row || !d_n_done || !h_group_slots)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_stream_init: null argument");
+  if (slots <= 0 || slots > kOpMaxSlots || groups < 1 || groups > 4)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_stream_init: 1 .. 65536 slots in 1 .. 4 groups");
+  mt3k::GroupSlots gs{};
+  for (int g = 0; g < groups; ++g) gs.n[g] = h_group_slots[g];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MT3_OP_TRY(mt3k::launch_beam_stream_init(d_done, d_slot_seg, d_fork_src, d_slot_row, d_n_done, slots, groups, gs, s));
+  MT3_HIP_CHECK(hipStreamSynchronize(s));
   return MT3_OK;
 }
