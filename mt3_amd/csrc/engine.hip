@@ -75,32 +75,39 @@ struct HostWeight {
   std::vector<int64_t> shape;
 };
 
+// One weight matrix on the device: output-major [N][K] in the compute type, and the other forms of the same numbers
+// that some launches read instead (made by upload_dense and ensure_score_planes)
+struct Dense {
+  void* w = nullptr;         // [N][K] compute type (a qkv-fold layer's `wi` goes on past row N, see LayerDev)
+  int N = 0, K = 0;
+  // f32 engine, encoder-sized launches (gemm_x6_kernel): three bf16 planes (hi / mid / lo) [N][K].  Encoder matrices and
+  // wkv_x get them at finalize, the decoder's other matrices with the first mt3_engine_score call (the decode step never
+  // reads them)
+  void* p[3] = {};
+  // MXFP8 dense path (dense_dtype MT3_FP8_E4M3; encoder matrices and wkv_x): e4m3 bytes [N][K] + E8M0 block scales [N][K / 32]
+  uint8_t *q = nullptr, *sc = nullptr;
+};
+constexpr int kFormPlanes = 1, kFormMx8 = 2;     // upload_dense: the forms a matrix gets beside the compute type
+
 struct LayerDev {
-  void* wqkv = nullptr;      // [3HD][emb]
-  void* wo = nullptr;        // [emb][HD]
-  void* wq_x = nullptr;      // decoder cross query [HD][emb]
-  void* wkv_x = nullptr;     // decoder cross key|value [2HD][emb]
-  void* wo_x = nullptr;      // decoder cross out [emb][HD]
+  Dense wqkv;                // [3HD][emb]
+  Dense wo;                  // [emb][HD]
+  Dense wq_x;                // decoder cross query [HD][emb]
+  Dense wkv_x;               // decoder cross key|value [2HD][emb]
+  Dense wo_x;                // decoder cross out [emb][HD]
   // q-fold (bf16 decode): the cross-attention q-projection rides in the two neighbouring launches
-  void* wqkv_ext = nullptr;  // decoder [3HD + HD][emb]: wqkv rows, then the cross query rows (pre_cross norm scale folded)
-  void* wo_ext = nullptr;    // decoder [emb + HD][HD]: self out-projection rows, then (Wo . (s2 * Wq_x))^T
+  Dense wqkv_ext;            // decoder [3HD + HD][emb]: wqkv rows, then the cross query rows (pre_cross norm scale folded)
+  Dense wo_ext;              // decoder [emb + HD][HD]: self out-projection rows, then (Wo . (s2 * Wq_x))^T
   // qkv-fold (round 3): the NEXT layer's q | k | v | cross-q projections ride in this layer's GEGLU and MLP
   // out-projection launches.  Wext = the next layer's scaled [q | k | v | cross-q] (last layer: the scaled logits matrix)
-  void* w_fold = nullptr;    // decoder [emb + nx][mlp]: rows < emb = Wo_mlp^T; rows >= emb = (Wo_mlp . Wext)^T
-  void* wi = nullptr;        // [2*mlp][emb] interleaved gate/linear; qkv-fold decoder layers: + Wext^T [nx][emb], zero
-                             // rows up to a multiple of 64
-  void* wo_mlp = nullptr;    // [emb][mlp]
+  Dense w_fold;              // decoder [emb + nx][mlp]: rows < emb = Wo_mlp^T; rows >= emb = (Wo_mlp . Wext)^T
+  Dense wi;                  // [2*mlp][emb] interleaved gate/linear.  qkv-fold decoder layers: the buffer goes on with
+                             // Wext^T [nx][emb] and zero rows up to a multiple of 64, which only the decode step's
+                             // GEGLU launch reads (it states its own N)
+  Dense wo_mlp;              // [emb][mlp]
   void* self_k = nullptr;    // decoder [Bm][H][L][64]
   void* self_v = nullptr;
   void* cross_kv = nullptr;  // decoder [2][B][H][T][64]
-  // MXFP8 dense path (dense_dtype MT3_FP8_E4M3): the same matrices as e4m3 bytes + E8M0 block scales [rows][K / 32]
-  uint8_t *wqkv_q = nullptr, *wqkv_sc = nullptr, *wo_q = nullptr, *wo_sc = nullptr, *wi_q = nullptr, *wi_sc = nullptr,
-          *wo_mlp_q = nullptr, *wo_mlp_sc = nullptr, *wkv_x_q = nullptr, *wkv_x_sc = nullptr;
-  // f32 engine, encoder-sized launches (gemm_x6_kernel): the same matrices as three bf16 planes (hi / mid / lo) [N][K]
-  void *wqkv_p[3] = {}, *wo_p[3] = {}, *wi_p[3] = {}, *wo_mlp_p[3] = {}, *wkv_x_p[3] = {};
-  // ... and, for DECODER layers, built by the first mt3_engine_score call (the decode step never reads them): the planes of
-  // wqkv / wo / wi / wo_mlp above plus the cross-attention query and out-projection
-  void *wq_x_p[3] = {}, *wo_x_p[3] = {};
   // fp8 (e4m3) K/V caches only: {k_scale, v_scale} per cached row
   float2* self_scale = nullptr;    // [Bm][H][L]
   float2* cross_scale = nullptr;   // [B][H][T]
@@ -188,12 +195,11 @@ struct mt3_engine {
   uint8_t *h_q = nullptr, *h_sc = nullptr;         // GEGLU output [M][mlp], written by the GEGLU epilogue
   uint8_t *enc_q = nullptr, *enc_sc = nullptr;     // normed encoder output [M][emb] (A of the cross-K/V projections)
 
-  void* enc_in = nullptr;        // [emb][input_depth]
-  void* enc_in_p[3] = {};        // f32 engine: its three bf16 planes
+  Dense enc_in;                  // [emb][input_depth]
   bool x6 = false;               // f32 engine: the encoder's dense layers multiply on the bf16 pipes (three planes per operand)
   float* enc_norm = nullptr;     // [emb] f32
   float* embedding = nullptr;    // [V][emb] f32
-  void* logits_w = nullptr;      // [V][emb] (decoder_norm folded)
+  Dense logits_w;                // [V][emb] (decoder_norm folded)
   float* pos_table = nullptr;    // [kMaxPos][emb] f32
   std::vector<LayerDev> enc, dec;
 
@@ -324,8 +330,7 @@ struct mt3_engine {
   int score_Lp = 0;              // rows per segment: max_decode_len rounded up to 64
   int score_chunk_req = 0;       // mt3_debug_engine_set_score_chunk (0: the workspace default)
   int score_chunks = 0;          // chunks of the most recent score call
-  bool score_planes = false;     // f32 engine (x6): the decoder's plane copies exist
-  void* logits_p[3] = {};        // f32 engine (x6): planes of logits_w
+  bool score_planes = false;     // f32 engine (x6): the plane copies of the decoder's matrices and of logits_w exist
   float* sc_y = nullptr;         // [rows][emb] f32 residual rows
   void* sc_y_ct = nullptr;       // bf16: compute-type copy [rows][emb] ...
   float* sc_y_ss = nullptr;      // ... and per-16-column sums of squares [rows][emb / 16]
@@ -344,6 +349,12 @@ namespace {
 
 using mt3k::brevity_penalty;     // t5x decoding.brevity_penalty(alpha = 0.6, length), kernels.h
 
+#define MT3_TRY(expr)           \
+  do {                          \
+    int _rc = (expr);           \
+    if (_rc != MT3_OK) return _rc; \
+  } while (0)
+
 int dmalloc(mt3_engine* e, void** p, size_t bytes) {
   MT3_HIP_CHECK(hipMalloc(p, bytes));
   e->allocs.push_back(*p);
@@ -351,58 +362,53 @@ int dmalloc(mt3_engine* e, void** p, size_t bytes) {
   return MT3_OK;
 }
 
-// upload a host f32 matrix as the compute type
-int upload_ct(mt3_engine* e, const std::vector<float>& h, void** d) {
-  int rc = dmalloc(e, d, h.size() * e->esize);
-  if (rc) return rc;
+// Upload a host f32 matrix [N][K] as the compute type and, of `forms` (kFormPlanes | kFormMx8), as those the engine
+// multiplies with: three bf16 planes on the f32 engine's three-plane tile (mt3_engine::x6), MXFP8 on the MXFP8 dense path.
+// `h` may go on past row N: all of it is uploaded in the compute type, the other forms cover [N][K]
+int upload_dense(mt3_engine* e, const std::vector<float>& h, int N, int K, int forms, Dense* D) {
+  const size_t n = static_cast<size_t>(N) * K;
+  if (h.size() < n) return mt3::fail(MT3_ERR_INVALID, "upload_dense: the host matrix is smaller than [N][K]");
+  D->N = N;
+  D->K = K;
+  MT3_TRY(dmalloc(e, &D->w, h.size() * e->esize));
   if (e->cfg.compute_dtype == MT3_BF16) {
     std::vector<uint16_t> t(h.size());
     for (size_t i = 0; i < h.size(); ++i) t[i] = f32_to_bf16_bits(h[i]);
-    MT3_HIP_CHECK(hipMemcpy(*d, t.data(), t.size() * 2, hipMemcpyHostToDevice));
+    MT3_HIP_CHECK(hipMemcpy(D->w, t.data(), t.size() * 2, hipMemcpyHostToDevice));
   } else {
-    MT3_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    MT3_HIP_CHECK(hipMemcpy(D->w, h.data(), h.size() * 4, hipMemcpyHostToDevice));
   }
-  return MT3_OK;
-}
-
-// upload a host f32 matrix [rows][K] as MXFP8 (only when the engine runs the MXFP8 dense path)
-int upload_mx8(mt3_engine* e, const std::vector<float>& h, int64_t rows, int64_t K, uint8_t** q, uint8_t** sc) {
-  if (!e->dense_fp8) return MT3_OK;
-  std::vector<uint8_t> hq(h.size()), hs(static_cast<size_t>(rows) * (K / 32));
-  int rc = mt3_host_mx8_quantize(h.data(), rows, K, hq.data(), hs.data());
-  if (rc) return rc;
-  if ((rc = dmalloc(e, reinterpret_cast<void**>(q), hq.size()))) return rc;
-  if ((rc = dmalloc(e, reinterpret_cast<void**>(sc), hs.size()))) return rc;
-  MT3_HIP_CHECK(hipMemcpy(*q, hq.data(), hq.size(), hipMemcpyHostToDevice));
-  MT3_HIP_CHECK(hipMemcpy(*sc, hs.data(), hs.size(), hipMemcpyHostToDevice));
-  return MT3_OK;
-}
-
-// upload a host f32 matrix as its three bf16 planes: hi = rne(w), mid = rne(w - hi), lo = rne(w - hi - mid) (both
-// differences exact); only when the engine multiplies f32 operands that way (mt3_engine::x6)
-int upload_planes(mt3_engine* e, const std::vector<float>& h, void* (&p)[3]) {
-  if (!e->x6) return MT3_OK;
-  std::vector<uint16_t> pl[3];
-  for (auto& v : pl) v.resize(h.size());
-  for (size_t i = 0; i < h.size(); ++i) {
-    auto val = [](uint16_t b) {
-      const uint32_t u = static_cast<uint32_t>(b) << 16;
-      float f;
-      std::memcpy(&f, &u, 4);
-      return f;
-    };
-    const uint16_t hi = f32_to_bf16_bits(h[i]);
-    const float r1 = h[i] - val(hi);
-    const uint16_t mi = f32_to_bf16_bits(r1);
-    const float r2 = r1 - val(mi);
-    pl[0][i] = hi;
-    pl[1][i] = mi;
-    pl[2][i] = f32_to_bf16_bits(r2);
+  if ((forms & kFormPlanes) && e->x6) {
+    // hi = rne(w), mid = rne(w - hi), lo = rne(w - hi - mid) (both differences exact)
+    std::vector<uint16_t> pl[3];
+    for (auto& v : pl) v.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      auto val = [](uint16_t b) {
+        const uint32_t u = static_cast<uint32_t>(b) << 16;
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+      };
+      const uint16_t hi = f32_to_bf16_bits(h[i]);
+      const float r1 = h[i] - val(hi);
+      const uint16_t mi = f32_to_bf16_bits(r1);
+      const float r2 = r1 - val(mi);
+      pl[0][i] = hi;
+      pl[1][i] = mi;
+      pl[2][i] = f32_to_bf16_bits(r2);
+    }
+    for (int k = 0; k < 3; ++k) {
+      MT3_TRY(dmalloc(e, &D->p[k], n * 2));
+      MT3_HIP_CHECK(hipMemcpy(D->p[k], pl[k].data(), n * 2, hipMemcpyHostToDevice));
+    }
   }
-  for (int k = 0; k < 3; ++k) {
-    int rc = dmalloc(e, &p[k], h.size() * 2);
-    if (rc) return rc;
-    MT3_HIP_CHECK(hipMemcpy(p[k], pl[k].data(), h.size() * 2, hipMemcpyHostToDevice));
+  if ((forms & kFormMx8) && e->dense_fp8) {
+    std::vector<uint8_t> hq(n), hs(static_cast<size_t>(N) * (K / 32));
+    MT3_TRY(mt3_host_mx8_quantize(h.data(), N, K, hq.data(), hs.data()));
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&D->q), hq.size()));
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&D->sc), hs.size()));
+    MT3_HIP_CHECK(hipMemcpy(D->q, hq.data(), hq.size(), hipMemcpyHostToDevice));
+    MT3_HIP_CHECK(hipMemcpy(D->sc, hs.data(), hs.size(), hipMemcpyHostToDevice));
   }
   return MT3_OK;
 }
@@ -446,7 +452,7 @@ int build_attention(mt3_engine* e, const std::string& prefix, const float* scale
   const HostWeight *q = find(e, prefix + "/query/kernel", emb, hd), *k = find(e, prefix + "/key/kernel", emb, hd),
                    *v = find(e, prefix + "/value/kernel", emb, hd), *o = find(e, prefix + "/out/kernel", hd, emb);
   if (!q || !k || !v || !o) return MT3_ERR_MISSING;
-  int rc;
+  const int all = kFormPlanes | kFormMx8;
   std::vector<float> ot(static_cast<size_t>(emb) * hd);
   put_transposed(ot, hd, 0, *o, nullptr);
   if (!cross) {
@@ -454,43 +460,55 @@ int build_attention(mt3_engine* e, const std::string& prefix, const float* scale
     put_transposed(t, emb, 0, *q, scale);
     put_transposed(t, emb, hd, *k, scale);
     put_transposed(t, emb, 2 * hd, *v, scale);
-    if ((rc = upload_ct(e, t, &L->wqkv))) return rc;
-    if ((rc = upload_ct(e, ot, &L->wo))) return rc;
-    if (encoder) {
-      if ((rc = upload_planes(e, t, L->wqkv_p))) return rc;
-      if ((rc = upload_planes(e, ot, L->wo_p))) return rc;
-      if ((rc = upload_mx8(e, t, 3 * hd, emb, &L->wqkv_q, &L->wqkv_sc))) return rc;
-      if ((rc = upload_mx8(e, ot, emb, hd, &L->wo_q, &L->wo_sc))) return rc;
-    }
+    MT3_TRY(upload_dense(e, t, 3 * hd, emb, encoder ? all : 0, &L->wqkv));
+    MT3_TRY(upload_dense(e, ot, emb, hd, encoder ? all : 0, &L->wo));
   } else {
     std::vector<float> tq(static_cast<size_t>(hd) * emb), tkv(static_cast<size_t>(2) * hd * emb);
     put_transposed(tq, emb, 0, *q, scale);         // query side sees the pre_cross_attention norm
     put_transposed(tkv, emb, 0, *k, nullptr);      // key/value side sees `encoded` (already normed)
     put_transposed(tkv, emb, hd, *v, nullptr);
-    if ((rc = upload_ct(e, tq, &L->wq_x))) return rc;
-    if ((rc = upload_ct(e, tkv, &L->wkv_x))) return rc;
-    if ((rc = upload_planes(e, tkv, L->wkv_x_p))) return rc;
-    if ((rc = upload_mx8(e, tkv, 2 * hd, emb, &L->wkv_x_q, &L->wkv_x_sc))) return rc;
-    if ((rc = upload_ct(e, ot, &L->wo_x))) return rc;
+    MT3_TRY(upload_dense(e, tq, hd, emb, 0, &L->wq_x));
+    MT3_TRY(upload_dense(e, tkv, 2 * hd, emb, all, &L->wkv_x));     // the encoder pass multiplies with it
+    MT3_TRY(upload_dense(e, ot, emb, hd, 0, &L->wo_x));
   }
   return MT3_OK;
 }
 
-// q-fold matrices of one decoder layer (see mt3_engine::qf)
-int build_q_fold(mt3_engine* e, const std::string& P, const float* s1, const float* s2, LayerDev* L) {
+const float* scale_of(mt3_engine* e, const std::string& name) {
+  const HostWeight* w = find(e, name, e->cfg.emb_dim, -1);
+  return w ? w->data.data() : nullptr;
+}
+
+// Wext^T of decoder layer l: output-major [4HD][emb] = scaled q | k | v of the self-attention, scaled cross-attention
+// query (what the q-fold's QKV launch multiplies with, and what the qkv-fold folds into the previous layer's launches)
+int wext_t(mt3_engine* e, int l, std::vector<float>* t) {
   const int emb = e->cfg.emb_dim, hd = e->HD();
-  const std::string S = P + "/self_attention", X = P + "/encoder_decoder_attention";
-  const HostWeight *q = find(e, S + "/query/kernel", emb, hd), *k = find(e, S + "/key/kernel", emb, hd),
-                   *v = find(e, S + "/value/kernel", emb, hd), *o = find(e, S + "/out/kernel", hd, emb),
-                   *qx = find(e, X + "/query/kernel", emb, hd);
-  if (!q || !k || !v || !o || !qx) return MT3_ERR_MISSING;
-  std::vector<float> t(static_cast<size_t>(4) * hd * emb);
-  put_transposed(t, emb, 0, *q, s1);
-  put_transposed(t, emb, hd, *k, s1);
-  put_transposed(t, emb, 2 * hd, *v, s1);
-  put_transposed(t, emb, 3 * hd, *qx, s2);
-  int rc;
-  if ((rc = upload_ct(e, t, &L->wqkv_ext))) return rc;
+  const std::string P = "decoder/layers_" + std::to_string(l);
+  const float* s1 = scale_of(e, P + "/pre_self_attention_layer_norm/scale");
+  const float* s2 = scale_of(e, P + "/pre_cross_attention_layer_norm/scale");
+  const HostWeight *q = find(e, P + "/self_attention/query/kernel", emb, hd),
+                   *k = find(e, P + "/self_attention/key/kernel", emb, hd),
+                   *v = find(e, P + "/self_attention/value/kernel", emb, hd),
+                   *qx = find(e, P + "/encoder_decoder_attention/query/kernel", emb, hd);
+  if (!s1 || !s2 || !q || !k || !v || !qx) return MT3_ERR_MISSING;
+  t->assign(static_cast<size_t>(4) * hd * emb, 0.f);
+  put_transposed(*t, emb, 0, *q, s1);
+  put_transposed(*t, emb, hd, *k, s1);
+  put_transposed(*t, emb, 2 * hd, *v, s1);
+  put_transposed(*t, emb, 3 * hd, *qx, s2);
+  return MT3_OK;
+}
+
+// q-fold matrices of one decoder layer (see mt3_engine::qf)
+int build_q_fold(mt3_engine* e, int l, const float* s2, LayerDev* L) {
+  const int emb = e->cfg.emb_dim, hd = e->HD();
+  const std::string P = "decoder/layers_" + std::to_string(l);
+  const HostWeight *o = find(e, P + "/self_attention/out/kernel", hd, emb),
+                   *qx = find(e, P + "/encoder_decoder_attention/query/kernel", emb, hd);
+  if (!o || !qx) return MT3_ERR_MISSING;
+  std::vector<float> t;
+  MT3_TRY(wext_t(e, l, &t));
+  MT3_TRY(upload_dense(e, t, 4 * hd, emb, 0, &L->wqkv_ext));
   // rows [0, emb): Wo^T;  rows [emb, emb + hd): P^T with P[k][n] = sum_e Wo[k][e] * s2[e] * Wq_x[e][n]  (double)
   std::vector<float> u(static_cast<size_t>(emb + hd) * hd);
   put_transposed(u, hd, 0, *o, nullptr);
@@ -505,11 +523,10 @@ int build_q_fold(mt3_engine* e, const std::string& P, const float* s1, const flo
     }
     for (int n = 0; n < hd; ++n) u[static_cast<size_t>(emb + n) * hd + kk] = static_cast<float>(acc[n]);
   }
-  return upload_ct(e, u, &L->wo_ext);
+  return upload_dense(e, u, emb + hd, hd, 0, &L->wo_ext);
 }
 
 mt3k::GemmArgs gemm_args(const void* A, const void* Wt, void* out, int M, int N, int K, int ldo);
-const float* scale_of(mt3_engine* e, const std::string& name);
 
 // qkv-fold matrices and tables (see mt3_engine::qkv_fold); wi_host[l] = layer l's GEGLU matrix as build_mlp laid it
 // out, which leaves here with the layer's Wext^T rows appended.  The matrix products (Wo_mlp . Wext per layer: 0.8 GFLOP;
@@ -518,23 +535,6 @@ const float* scale_of(mt3_engine* e, const std::string& name);
 int build_qkv_fold(mt3_engine* e, const std::vector<std::vector<float>>& wi_host) {
   const mt3_engine_config& c = e->cfg;
   const int emb = c.emb_dim, hd = e->HD(), mlp = c.mlp_dim, n4 = 4 * hd, nl = c.num_decoder_layers;
-  // Wext^T of layer l: output-major [4HD][emb] = scaled q | k | v of the self-attention, scaled cross-attention query
-  auto wext_t = [&](int l, std::vector<float>* t) -> int {
-    const std::string P = "decoder/layers_" + std::to_string(l);
-    const float* s1 = scale_of(e, P + "/pre_self_attention_layer_norm/scale");
-    const float* s2 = scale_of(e, P + "/pre_cross_attention_layer_norm/scale");
-    const HostWeight *q = find(e, P + "/self_attention/query/kernel", emb, hd),
-                     *k = find(e, P + "/self_attention/key/kernel", emb, hd),
-                     *v = find(e, P + "/self_attention/value/kernel", emb, hd),
-                     *qx = find(e, P + "/encoder_decoder_attention/query/kernel", emb, hd);
-    if (!s1 || !s2 || !q || !k || !v || !qx) return MT3_ERR_MISSING;
-    t->assign(static_cast<size_t>(n4) * emb, 0.f);
-    put_transposed(*t, emb, 0, *q, s1);
-    put_transposed(*t, emb, hd, *k, s1);
-    put_transposed(*t, emb, 2 * hd, *v, s1);
-    put_transposed(*t, emb, 3 * hd, *qx, s2);
-    return MT3_OK;
-  };
   float *d_wext = nullptr, *d_wo = nullptr, *d_prod = nullptr;
   auto cleanup = [&]() {
     if (d_wext) (void)hipFree(d_wext);
@@ -554,7 +554,7 @@ int build_qkv_fold(mt3_engine* e, const std::vector<std::vector<float>>& wi_host
     const int nx = last ? c.vocab_size : n4;
     const HostWeight* wo = find(e, "decoder/layers_" + std::to_string(l) + "/mlp/wo/kernel", mlp, emb);
     if (!wo) rc = MT3_ERR_MISSING;
-    if (rc == MT3_OK && !last) rc = wext_t(l + 1, &wt);
+    if (rc == MT3_OK && !last) rc = wext_t(e, l + 1, &wt);
     if (rc == MT3_OK && last) {
       const float* sn = scale_of(e, "decoder/decoder_norm/scale");
       const HostWeight* wl = find(e, "decoder/logits_dense/kernel", emb, c.vocab_size);
@@ -580,7 +580,7 @@ int build_qkv_fold(mt3_engine* e, const std::vector<std::vector<float>>& wi_host
     for (int k = 0; k < mlp; ++k)
       for (int n = 0; n < emb; ++n) w[static_cast<size_t>(n) * mlp + k] = wo->data[static_cast<size_t>(k) * emb + n];
     std::memcpy(w.data() + static_cast<size_t>(emb) * mlp, prod.data(), static_cast<size_t>(nx) * mlp * 4);
-    rc = upload_ct(e, w, &e->dec[l].w_fold);
+    rc = upload_dense(e, w, emb + nx, mlp, 0, &e->dec[l].w_fold);
     if (rc != MT3_OK) break;
     // GEGLU launch: [wi_0 | wi_1 interleaved ; Wext^T ; zero rows up to whole 64-column tiles], K = emb
     const size_t n_wi = static_cast<size_t>(2) * mlp * emb, nx64 = (static_cast<size_t>(nx) + 63) / 64 * 64;
@@ -591,10 +591,10 @@ int build_qkv_fold(mt3_engine* e, const std::vector<std::vector<float>>& wi_host
     w.assign(n_wi + nx64 * emb, 0.f);
     std::memcpy(w.data(), wi_host[l].data(), n_wi * 4);
     std::memcpy(w.data() + n_wi, wt.data(), static_cast<size_t>(nx) * emb * 4);
-    rc = upload_ct(e, w, &e->dec[l].wi);
+    rc = upload_dense(e, w, 2 * mlp, emb, 0, &e->dec[l].wi);     // (N: the GEGLU rows, see LayerDev::wi)
   }
   // layer 0: its input row is Embed(tok) + FixedEmbed[t], so its projection is the sum of two table rows
-  if (he == hipSuccess && rc == MT3_OK) rc = wext_t(0, &wt);
+  if (he == hipSuccess && rc == MT3_OK) rc = wext_t(e, 0, &wt);
   if (he == hipSuccess && rc == MT3_OK) {
     he = hipMemcpy(d_wext, wt.data(), wt.size() * 4, hipMemcpyHostToDevice);
     if (he == hipSuccess) rc = dmalloc(e, reinterpret_cast<void**>(&e->ew0), static_cast<size_t>(c.vocab_size) * n4 * 4);
@@ -633,25 +633,11 @@ int build_mlp(mt3_engine* e, const std::string& prefix, const float* scale, Laye
   }
   std::vector<float> ot(static_cast<size_t>(emb) * mlp);
   put_transposed(ot, mlp, 0, *wo, nullptr);
-  int rc;
-  if (keep_wi) {
-    if ((rc = upload_ct(e, ot, &L->wo_mlp))) return rc;
-    keep_wi->swap(t);
-    return MT3_OK;
-  }
-  if ((rc = upload_ct(e, t, &L->wi))) return rc;
-  if (encoder) {
-    if ((rc = upload_planes(e, t, L->wi_p))) return rc;
-    if ((rc = upload_planes(e, ot, L->wo_mlp_p))) return rc;
-    if ((rc = upload_mx8(e, t, 2 * mlp, emb, &L->wi_q, &L->wi_sc))) return rc;
-    if ((rc = upload_mx8(e, ot, emb, mlp, &L->wo_mlp_q, &L->wo_mlp_sc))) return rc;
-  }
-  return upload_ct(e, ot, &L->wo_mlp);
-}
-
-const float* scale_of(mt3_engine* e, const std::string& name) {
-  const HostWeight* w = find(e, name, e->cfg.emb_dim, -1);
-  return w ? w->data.data() : nullptr;
+  const int forms = encoder ? kFormPlanes | kFormMx8 : 0;
+  MT3_TRY(upload_dense(e, ot, emb, mlp, forms, &L->wo_mlp));
+  if (keep_wi) keep_wi->swap(t);
+  else MT3_TRY(upload_dense(e, t, 2 * mlp, emb, forms, &L->wi));
+  return MT3_OK;
 }
 
 mt3k::GemmArgs gemm_args(const void* A, const void* Wt, void* out, int M, int N, int K, int ldo) {
@@ -666,12 +652,6 @@ mt3k::GemmArgs gemm_args(const void* A, const void* Wt, void* out, int M, int N,
   g.ldo = ldo;
   return g;
 }
-
-#define MT3_TRY(expr)           \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc != MT3_OK) return _rc; \
-  } while (0)
 
 // One decode step of rows [row0, row0 + rows) -- a "chain".  The batch of a decode call is split into
 // `e->chains` such chains; they are data-independent (a segment never looks at another segment), so
@@ -739,44 +719,120 @@ mt3k::BeamKArgs beam_args(mt3_engine* e, int row0, int rows, int k, int done_slo
   return b;
 }
 
+// A residual stream: M f32 rows of emb columns and, in the split form, what travels with them -- per row the sums of
+// squares of every 16-column group and (bf16) a compute-type copy, kept up to date by every producer of the rows -- so
+// that the norm-fused GEMMs read compute-type operands and need no statistics pass of their own
+struct Resid {
+  float* y = nullptr;        // [M][emb]
+  void* ct = nullptr;        // split, bf16: [M][emb] (f32 engine: none)
+  float* ss = nullptr;       // split: [M][emb / 16]
+  bool split = false;
+  bool x6 = false;           // products of this stream run on the three-plane tile (f32 engine, encoder-sized passes)
+  int M = 0;
+  // the rows as a norm-fused GEMM reads them.  Split form of the f32 engine: the compute-type rows ARE the f32 rows, and
+  // no copy is written
+  const void* a() const { return split && ct ? ct : y; }
+};
+
+// the decode step's rows: `rows` slots from the one `in` starts at (input_row)
+Resid decode_rows(const mt3_engine* e, const mt3k::InputRow& in, int rows) {
+  return Resid{in.y, in.y_ct, in.y_ss, e->y_split, false, rows};
+}
+
+// an encoder pass of M rows
+Resid encoder_rows(const mt3_engine* e, int M, bool small) {
+  const mt3_engine_config& c = e->cfg;
+  const int emb = c.emb_dim;
+  // (gemm_x6_kernel addresses its operands with 32-bit byte offsets: a batch whose widest f32 activation matrix reaches
+  // 4 GB -- 4096 segments at the MT3 shape -- takes the f32-instruction tiles instead of failing)
+  const int widest = std::max(std::max(c.input_depth, emb), std::max(e->HD(), c.mlp_dim));
+  const bool x6_fits = static_cast<size_t>(M) * widest * 4 < (1ull << 32);
+  // the split residual form feeds the LDS-DMA tile (K <= 1024); the decode-sized tile a small batch selects holds the
+  // partial sums of K <= 512 or K = 768 only, so a small batch of a wider model stays on the single f32 stream
+  const bool xs = e->x_split && !(small && !(emb <= 512 || emb == 768));
+  return Resid{e->x, xs ? e->x_ct : nullptr, xs ? e->x_ss : nullptr, xs, e->x6 && x6_fits, M};
+}
+
+bool score_split(const mt3_engine* e) {
+  const int emb = e->cfg.emb_dim;
+  return e->cfg.compute_dtype == MT3_BF16 && emb % 64 == 0 && emb <= 1024;
+}
+
+// a chunk of M rows of the score workspace
+Resid score_rows(const mt3_engine* e, int M) {
+  const bool split = score_split(e);
+  return Resid{e->sc_y, split ? e->sc_y_ct : nullptr, split ? e->sc_y_ss : nullptr, split, e->x6, M};
+}
+
+mt3k::GemmArgs gemm_args(const void* A, const Dense& W, void* out, int M, int ldo) {
+  return gemm_args(A, W.w, out, M, W.N, W.K, ldo);
+}
+
+// g (made by gemm_args from W) on the three-plane tile (x6: W's planes, f32 A and f32 outputs) or on launch_gemm's tiles
+int dense_gemm(mt3_engine* e, bool x6, mt3k::GemmArgs g, const Dense& W, bool a_f32, int norm, int epi, bool small,
+               hipStream_t s) {
+  if (!x6) return mt3k::launch_gemm(e->cfg.compute_dtype, g, a_f32, norm, epi, small, s);
+  g.Wt = W.p[0];
+  return mt3k::launch_gemm_x6(g, W.p[1], W.p[2], norm != 0, epi == MT3_EPI_F32 ? MT3_EPI_STORE : epi, s);
+}
+
+// What a decode-step launch carries beside the plain product (GemmArgs): N > 0: the launch's output columns where they
+// are not W.N; columns [n_split, N) are a second product that goes to out2 (kEpiStoreQ / kEpiResidQ / kEpiGegluP);
+// concurrent: the launch runs beside other row groups' launches
+struct GemmExtra {
+  int N = 0;
+  float* out2 = nullptr;
+  int ld2 = 0, n_split = 0, concurrent = 0;
+};
+
+mt3k::GemmArgs gemm_args(const void* A, const Dense& W, void* out, int M, int ldo, const GemmExtra& x) {
+  mt3k::GemmArgs g = gemm_args(A, W, out, M, ldo);
+  if (x.N) g.N = x.N;
+  g.out2 = x.out2;
+  g.ld2 = x.ld2;
+  g.n_split = x.n_split;
+  g.concurrent = x.concurrent;
+  return g;
+}
+
+// the normalised rows of R into a projection: out = epi(rmsnorm(R) . W^T) (the norm's scale is folded into W's rows)
+int normed_gemm(mt3_engine* e, const Resid& R, const Dense& W, void* out, int ldo, int epi, bool small, hipStream_t s,
+                const GemmExtra& x = {}) {
+  mt3k::GemmArgs g = gemm_args(R.a(), W, out, R.M, ldo, x);
+  g.a_ss = R.ss;
+  return dense_gemm(e, R.x6, g, W, !R.split, R.split ? 2 : 1, epi, small, s);
+}
+
+// a product added back into the rows of R: R += A . W^T, every form of R kept up to date
+int resid_gemm(mt3_engine* e, const Dense& W, const void* A, const Resid& R, bool small, hipStream_t s,
+               const GemmExtra& x = {}) {
+  mt3k::GemmArgs g = gemm_args(A, W, R.y, R.M, e->cfg.emb_dim, x);
+  g.out_ct = R.ct;
+  g.out_ss = R.ss;
+  return dense_gemm(e, R.x6, g, W, false, 0, x.out2 ? mt3k::kEpiResidQ : MT3_EPI_RESID, small, s);
+}
+
 int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, int op, hipStream_t s, int done_slot = 0) {
   const mt3_engine_config& c = e->cfg;
   const int dt = c.compute_dtype, emb = c.emb_dim, hd = e->HD(), H = c.num_heads, T = c.input_length;
   const int Lmax = c.max_decode_len;
   const size_t es = e->esize, kes = e->kv_esize;
   const int nl = c.num_decoder_layers;
-  const bool split = e->y_split, fold = e->qkv_fold;
+  const bool fold = e->qkv_fold;
   // row retirement: the step's slots [row0, row0 + rows) reach their cache rows / id rows through e->slot_row, so the
   // cache and id base pointers stay those of the whole batch
   const bool retire = (skip & kVarRetire) != 0;
   const size_t crow0 = retire ? 0 : static_cast<size_t>(row0);
-  const bool f32 = dt == MT3_F32;
   // the decoder input row of this step (Embed(tok) + FixedEmbed[t]) is already in `y`: written by the
   // embed launch before the first step and by the previous step's argmax kernel afterwards
   const mt3k::InputRow in = input_row(e, row0);
-  float* y = in.y;
-  // residual rows as the norm-fused GEMMs see them: f32 with in-kernel statistics, or (split form) the
-  // compute-type rows with the producer's partial sums (f32: the rows themselves)
-  char* y_copy = static_cast<char*>(in.y_ct);        // where producers of a residual row leave its bf16 copy
-  char* y_ct = !split ? nullptr : f32 ? reinterpret_cast<char*>(y) : y_copy;
+  const Resid R = decode_rows(e, in, rows);
   float* y_ss = in.y_ss;
-  auto normed = [&](const void* Wt, void* out, int N, int ldo) {
-    mt3k::GemmArgs g = gemm_args(split ? static_cast<const void*>(y_ct) : static_cast<const void*>(y), Wt, out, rows, N,
-                                 emb, ldo);
-    g.a_ss = y_ss;
-    return g;
-  };
-  // this step belongs to one of several row groups / graph chains (GemmArgs::concurrent).  Under row retirement
-  // rows < B_total also holds for a LONE stream after a compaction, hence the explicit bit
-  const int beside = ((skip & kVarBeside) || (!retire && rows < B_total)) ? 1 : 0;
-  auto resid = [&](const void* A, const void* Wt, int K) {
-    mt3k::GemmArgs g = gemm_args(A, Wt, y, rows, emb, K, emb);
-    g.out_ct = y_copy;
-    g.out_ss = y_ss;
-    g.concurrent = beside;
-    return g;
-  };
-  const int nrm = split ? 2 : 1;
+  // this step belongs to one of several row groups / graph chains (GemmArgs::concurrent: every residual add and the
+  // GEGLU launch).  Under row retirement rows < B_total also holds for a LONE stream after a compaction, hence the
+  // explicit bit
+  GemmExtra ex;
+  ex.concurrent = ((skip & kVarBeside) || (!retire && rows < B_total)) ? 1 : 0;
   char* qkv_d = static_cast<char*>(e->qkv_d) + static_cast<size_t>(row0) * 3 * hd * es;
   char* attn_d = static_cast<char*>(e->attn_d) + static_cast<size_t>(row0) * hd * es;
   char* q_d = static_cast<char*>(e->q_d) + static_cast<size_t>(row0) * hd * es;
@@ -786,8 +842,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   int* step = e->step + row0;                    // per-row position counters
   if (op == 8 * nl) {
     if (fold) return MT3_OK;                  // the logits projection rode in the last layer's MLP out-projection launch
-    return mt3k::launch_gemm(dt, normed(e->logits_w, logits, c.vocab_size, c.vocab_size), !split, nrm, MT3_EPI_F32,
-                             true, s);
+    return normed_gemm(e, R, e->logits_w, logits, c.vocab_size, MT3_EPI_F32, true, s);
   }
   if (op == 8 * nl + 1 && (skip & kVarBeams)) {
     // k-beam search: the beam step, then the cache-row copies of the beams that forked
@@ -837,12 +892,12 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     case 0:
       if (fold) return MT3_OK;                // rode in the previous layer's MLP out-projection launch / the row's producer
       if (e->q_fold) {
-        mt3k::GemmArgs g = normed(L.wqkv_ext, qkv_d, 4 * hd, 3 * hd);
-        g.out2 = e->qf + static_cast<size_t>(row0) * hd;
-        g.n_split = 3 * hd;
-        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiStoreQ, true, s);
+        GemmExtra q;
+        q.out2 = e->qf + static_cast<size_t>(row0) * hd;
+        q.n_split = 3 * hd;
+        return normed_gemm(e, R, L.wqkv_ext, qkv_d, 3 * hd, mt3k::kEpiStoreQ, true, s, q);
       }
-      return mt3k::launch_gemm(dt, normed(L.wqkv, qkv_d, 3 * hd, 3 * hd), !split, nrm, MT3_EPI_STORE, true, s);
+      return normed_gemm(e, R, L.wqkv, qkv_d, 3 * hd, MT3_EPI_STORE, true, s);
     case 1: {
       if (skip & 1) return MT3_OK;
       mt3k::DecAttnArgs a{};
@@ -876,17 +931,15 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     }
     case 2:
       if (e->q_fold) {
-        mt3k::GemmArgs g = resid(attn_d, L.wo_ext, hd);
-        g.N = emb + hd;
-        g.out2 = fold ? qkvf + 3 * hd : e->qf + static_cast<size_t>(row0) * hd;
-        g.ld2 = fold ? 4 * hd : 0;
-        g.n_split = emb;
-        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, true, s);
+        ex.out2 = fold ? qkvf + 3 * hd : e->qf + static_cast<size_t>(row0) * hd;
+        ex.ld2 = fold ? 4 * hd : 0;
+        ex.n_split = emb;
+        return resid_gemm(e, L.wo_ext, attn_d, R, true, s, ex);
       }
-      return mt3k::launch_gemm(dt, resid(attn_d, L.wo, hd), false, 0, MT3_EPI_RESID, true, s);
+      return resid_gemm(e, L.wo, attn_d, R, true, s, ex);
     case 3:
       if (e->q_fold) return MT3_OK;           // folded into ops 0 and 2
-      return mt3k::launch_gemm(dt, normed(L.wq_x, q_d, hd, hd), !split, nrm, MT3_EPI_STORE, true, s);
+      return normed_gemm(e, R, L.wq_x, q_d, hd, MT3_EPI_STORE, true, s);
     case 4: {
       if (skip & 2) return MT3_OK;
       mt3k::DecAttnArgs x{};
@@ -913,10 +966,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
       return mt3k::launch_decode_attention(dt, x, s);
     }
     case 5:
-      return mt3k::launch_gemm(dt, resid(attn_d, L.wo_x, hd), false, 0, MT3_EPI_RESID, true, s);
-    case 6: {
-      mt3k::GemmArgs g = normed(L.wi, h_d, 2 * c.mlp_dim, c.mlp_dim);
-      g.concurrent = beside;
+      return resid_gemm(e, L.wo_x, attn_d, R, true, s, ex);
+    case 6:
       if (fold) {
         // what consumes the row this layer is about to finish, unnormalised -- the NEXT layer's q | k | v | cross-q (4HD
         // columns of qkvf), after the last layer the logits -- is y2 . Wext + h . (Wo_mlp . Wext).  The first term needs
@@ -925,28 +976,25 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
         // previous step's logits into its arg-max), and op 7 adds the second term.
         const bool last = (op >> 3) + 1 == nl;
         const int nx = last ? c.vocab_size : 4 * hd;
-        g.N = 2 * c.mlp_dim + (nx + 63) / 64 * 64;
-        g.out2 = last ? logits : qkvf;
-        g.ld2 = nx;
-        g.n_split = 2 * c.mlp_dim;
-        return mt3k::launch_gemm(dt, g, false, 2, mt3k::kEpiGegluP, true, s);
+        ex.N = 2 * c.mlp_dim + (nx + 63) / 64 * 64;
+        ex.out2 = last ? logits : qkvf;
+        ex.ld2 = nx;
+        ex.n_split = 2 * c.mlp_dim;
+        return normed_gemm(e, R, L.wi, h_d, c.mlp_dim, mt3k::kEpiGegluP, true, s, ex);
       }
-      return mt3k::launch_gemm(dt, g, !split, nrm, MT3_EPI_GEGLU, true, s);
-    }
+      return normed_gemm(e, R, L.wi, h_d, c.mlp_dim, MT3_EPI_GEGLU, true, s, ex);
     default:
       if (fold) {
         // MLP out-projection + residual, and -- as extra output columns over the same K = mlp -- h . (Wo_mlp . Wext),
         // added to the part of the next consumer's row that op 6 left in qkvf / logits
         const bool last = (op >> 3) + 1 == nl;
         const int nx = last ? c.vocab_size : 4 * hd;
-        mt3k::GemmArgs g = resid(h_d, L.w_fold, c.mlp_dim);
-        g.N = emb + nx;
-        g.out2 = last ? logits : qkvf;
-        g.ld2 = nx;
-        g.n_split = emb;
-        return mt3k::launch_gemm(dt, g, false, 0, mt3k::kEpiResidQ, true, s);
+        ex.out2 = last ? logits : qkvf;
+        ex.ld2 = nx;
+        ex.n_split = emb;
+        return resid_gemm(e, L.w_fold, h_d, R, true, s, ex);
       }
-      return mt3k::launch_gemm(dt, resid(h_d, L.wo_mlp, c.mlp_dim), false, 0, MT3_EPI_RESID, true, s);
+      return resid_gemm(e, L.wo_mlp, h_d, R, true, s, ex);
   }
 }
 
@@ -1132,8 +1180,7 @@ int mt3_engine_finalize(mt3_engine* e) {
     if (!w) return MT3_ERR_MISSING;
     std::vector<float> t(static_cast<size_t>(emb) * c.input_depth);
     put_transposed(t, c.input_depth, 0, *w, nullptr);
-    if ((rc = upload_ct(e, t, &e->enc_in))) return rc;
-    if ((rc = upload_planes(e, t, e->enc_in_p))) return rc;
+    if ((rc = upload_dense(e, t, emb, c.input_depth, kFormPlanes, &e->enc_in))) return rc;
   }
   e->enc.resize(c.num_encoder_layers);
   for (int l = 0; l < c.num_encoder_layers; ++l) {
@@ -1174,7 +1221,7 @@ int mt3_engine_finalize(mt3_engine* e) {
     if (!s1 || !s2 || !s3) return MT3_ERR_MISSING;
     if ((rc = build_attention(e, P + "/self_attention", s1, false, &e->dec[l]))) return rc;
     if ((rc = build_attention(e, P + "/encoder_decoder_attention", s2, true, &e->dec[l]))) return rc;
-    if (q_fold && (rc = build_q_fold(e, P, s1, s2, &e->dec[l]))) return rc;
+    if (q_fold && (rc = build_q_fold(e, l, s2, &e->dec[l]))) return rc;
     if ((rc = build_mlp(e, P + "/mlp", s3, &e->dec[l], false, e->qkv_fold ? &dec_wi[l] : nullptr))) return rc;
     const size_t kvb = static_cast<size_t>(Bm) * c.num_heads * L * 64 * e->kv_esize;
     if ((rc = dmalloc(e, &e->dec[l].self_k, kvb))) return rc;
@@ -1202,7 +1249,7 @@ int mt3_engine_finalize(mt3_engine* e) {
     if (!sn || !w) return MT3_ERR_MISSING;
     std::vector<float> t(static_cast<size_t>(c.vocab_size) * emb);
     put_transposed(t, emb, 0, *w, sn);
-    if ((rc = upload_ct(e, t, &e->logits_w))) return rc;
+    if ((rc = upload_dense(e, t, c.vocab_size, emb, 0, &e->logits_w))) return rc;
   }
   // ---- sinusoidal table (layers.py:51-82): [sin | cos] halves, scale = -ln(10000)/(emb/2 - 1)
   {
@@ -1317,59 +1364,35 @@ static int encode_impl(mt3_engine* e, const float* d_inputs, int32_t batch, floa
   const int dt = c.compute_dtype, emb = c.emb_dim, hd = e->HD(), T = c.input_length;
   const int M = batch * T;
   const bool small = M < 2048;
-  // (gemm_x6_kernel addresses its operands with 32-bit byte offsets: a batch whose widest f32 activation matrix reaches
-  // 4 GB -- 4096 segments at the MT3 shape -- takes the f32-instruction path below instead of failing)
-  const int widest = std::max(std::max(c.input_depth, emb), std::max(hd, c.mlp_dim));
-  const bool x6_fits = static_cast<size_t>(M) * widest * 4 < (1ull << 32);
-  if (e->x6 && x6_fits) {
-    // f32 engine: every dense layer and the attention on the bf16 pipes with three planes per operand (gemm.hip,
-    // gemm_x6_kernel: at least as exact as the f32 matrix instruction, 2.7x its rate).  Since round 5 at EVERY batch size
-    // (up to round 4 passes of fewer than 2048 rows took the f32 instruction's decode-sized tiles, so a segment's f32
-    // encoder output depended on the batch it sat in by ~1e-7 -- ADVICE r4): a file's last short batch, a refill chunk of
-    // mt3_engine_transcribe and a 1250-segment corpus call now give a segment the same bits
-    auto x6 = [&](const void* A, void* (&W)[3], void* out, int N, int K, int ldo, bool norm, int epi, int seq) {
-      mt3k::GemmArgs g = gemm_args(A, W[0], out, M, N, K, ldo);
-      g.aux = e->pos_table;
-      g.seq_len = seq;
-      return mt3k::launch_gemm_x6(g, W[1], W[2], norm, epi, s);
-    };
-    MT3_TRY(x6(d_inputs, e->enc_in_p, e->x, emb, c.input_depth, emb, false, MT3_EPI_POS, T));
-    for (int l = 0; l < c.num_encoder_layers; ++l) {
-      LayerDev& L = e->enc[l];
-      MT3_TRY(x6(e->x, L.wqkv_p, e->qkv, 3 * hd, emb, 3 * hd, true, MT3_EPI_STORE, 0));
-      MT3_TRY(mt3k::launch_encoder_attention_x6(e->qkv, e->attn, batch, T, c.num_heads, s));
-      MT3_TRY(x6(e->attn, L.wo_p, e->x, emb, hd, emb, false, MT3_EPI_RESID, 0));
-      MT3_TRY(x6(e->x, L.wi_p, e->hbuf, 2 * c.mlp_dim, emb, c.mlp_dim, true, MT3_EPI_GEGLU, 0));
-      MT3_TRY(x6(e->hbuf, L.wo_mlp_p, e->x, emb, c.mlp_dim, emb, false, MT3_EPI_RESID, 0));
-    }
-    MT3_TRY(mt3k::launch_rmsnorm(dt, e->x, e->enc_norm, e->enc_out, d_encoded_f32, M, emb, s));
-    for (int l = 0; l < c.num_decoder_layers; ++l)
-      MT3_TRY(x6(e->enc_out, e->dec[l].wkv_x_p, ckv(l), 2 * hd, emb, 2 * hd, false, MT3_EPI_HEADS, T));
-    return MT3_OK;
-  }
+  // f32 engine (R.x6): every dense layer and the attention on the bf16 pipes with three planes per operand (gemm.hip,
+  // gemm_x6_kernel: at least as exact as the f32 matrix instruction, 2.7x its rate).  Since round 5 at EVERY batch size
+  // (up to round 4 passes of fewer than 2048 rows took the f32 instruction's decode-sized tiles, so a segment's f32
+  // encoder output depended on the batch it sat in by ~1e-7 -- ADVICE r4): a file's last short batch, a refill chunk of
+  // mt3_engine_transcribe and a 1250-segment corpus call now give a segment the same bits
+  const Resid R = encoder_rows(e, M, small);
   {
-    mt3k::GemmArgs g = gemm_args(d_inputs, e->enc_in, e->x, M, emb, c.input_depth, emb);
+    mt3k::GemmArgs g = gemm_args(d_inputs, e->enc_in, e->x, M, emb);
     g.aux = e->pos_table;
     g.seq_len = T;
-    MT3_TRY(mt3k::launch_gemm(dt, g, true, false, MT3_EPI_POS, small, s));
+    MT3_TRY(dense_gemm(e, R.x6, g, e->enc_in, true, 0, MT3_EPI_POS, small, s));
   }
   if (e->dense_fp8) {
     // MXFP8 encoder: x travels as f32 rows + e4m3/E8M0 copy + per-16-column sums of squares; every GEMM operand is
     // MXFP8, written in that form by its producer (the quantiser below, the RESID / GEGLU epilogues)
-    auto mx = [&](const uint8_t* A, const uint8_t* a_sc, const uint8_t* W, const uint8_t* w_sc, int N, int K) {
+    auto mx = [&](const uint8_t* A, const uint8_t* a_sc, const Dense& W) {
       mt3k::Mx8Args g{};
       g.A = A;
       g.a_sc = a_sc;
-      g.W = W;
-      g.w_sc = w_sc;
+      g.W = W.q;
+      g.w_sc = W.sc;
       g.M = M;
-      g.N = N;
-      g.K = K;
-      g.ldo = N;
+      g.N = W.N;
+      g.K = W.K;
+      g.ldo = W.N;
       return g;
     };
-    auto resid = [&](const uint8_t* A, const uint8_t* a_sc, const uint8_t* W, const uint8_t* w_sc, int K) {
-      mt3k::Mx8Args g = mx(A, a_sc, W, w_sc, emb, K);
+    auto mx_add = [&](const uint8_t* A, const uint8_t* a_sc, const Dense& W) {
+      mt3k::Mx8Args g = mx(A, a_sc, W);
       g.out = e->x;
       g.out_q = e->x_q;
       g.out_sc = e->x_sc;
@@ -1380,28 +1403,28 @@ static int encode_impl(mt3_engine* e, const float* d_inputs, int32_t batch, floa
     for (int l = 0; l < c.num_encoder_layers; ++l) {
       LayerDev& L = e->enc[l];
       {
-        mt3k::Mx8Args g = mx(e->x_q, e->x_sc, L.wqkv_q, L.wqkv_sc, 3 * hd, emb);
+        mt3k::Mx8Args g = mx(e->x_q, e->x_sc, L.wqkv);
         g.out = e->qkv;
         g.a_ss = e->x_ss;
         MT3_TRY(mt3k::launch_gemm_mx8(g, MT3_EPI_STORE, s));
       }
       MT3_TRY(mt3k::launch_encoder_attention(dt, e->qkv, e->attn, batch, T, c.num_heads, s));
       MT3_TRY(mt3k::launch_mx8_quantize(e->attn, false, M, hd, e->attn_q, e->attn_sc, nullptr, s));
-      MT3_TRY(resid(e->attn_q, e->attn_sc, L.wo_q, L.wo_sc, hd));
+      MT3_TRY(mx_add(e->attn_q, e->attn_sc, L.wo));
       {
-        mt3k::Mx8Args g = mx(e->x_q, e->x_sc, L.wi_q, L.wi_sc, 2 * c.mlp_dim, emb);
+        mt3k::Mx8Args g = mx(e->x_q, e->x_sc, L.wi);
         g.ldo = c.mlp_dim;
         g.a_ss = e->x_ss;
         g.out_q = e->h_q;
         g.out_sc = e->h_sc;
         MT3_TRY(mt3k::launch_gemm_mx8(g, MT3_EPI_GEGLU, s));
       }
-      MT3_TRY(resid(e->h_q, e->h_sc, L.wo_mlp_q, L.wo_mlp_sc, c.mlp_dim));
+      MT3_TRY(mx_add(e->h_q, e->h_sc, L.wo_mlp));
     }
     MT3_TRY(mt3k::launch_rmsnorm(dt, e->x, e->enc_norm, e->enc_out, d_encoded_f32, M, emb, s));
     MT3_TRY(mt3k::launch_mx8_quantize(e->enc_out, false, M, emb, e->enc_q, e->enc_sc, nullptr, s));
     for (int l = 0; l < c.num_decoder_layers; ++l) {
-      mt3k::Mx8Args g = mx(e->enc_q, e->enc_sc, e->dec[l].wkv_x_q, e->dec[l].wkv_x_sc, 2 * hd, emb);
+      mt3k::Mx8Args g = mx(e->enc_q, e->enc_sc, e->dec[l].wkv_x);
       g.out = e->kv_fp8 ? e->cross_stage : ckv(l);
       g.seq_len = T;
       MT3_TRY(mt3k::launch_gemm_mx8(g, MT3_EPI_HEADS, s));
@@ -1411,37 +1434,22 @@ static int encode_impl(mt3_engine* e, const float* d_inputs, int32_t batch, floa
     }
     return MT3_OK;
   }
-  // the split residual form feeds the LDS-DMA tile (K <= 1024); the decode-sized tile a small batch selects holds the
-  // partial sums of K <= 512 or K = 768 only, so a small batch of a wider model stays on the single f32 stream
-  const bool xs = e->x_split && !(small && !(emb <= 512 || emb == 768));
-  if (xs) MT3_TRY(mt3k::launch_residual_split(e->x, e->x_ct, e->x_ss, M, emb, s));
-  auto normed = [&](const void* Wt, void* out, int N, int ldo) {
-    mt3k::GemmArgs g = gemm_args(xs ? static_cast<const void*>(e->x_ct) : static_cast<const void*>(e->x), Wt, out, M,
-                                 N, emb, ldo);
-    g.a_ss = xs ? e->x_ss : nullptr;
-    return g;
-  };
-  auto resid = [&](const void* A, const void* Wt, int K) {
-    mt3k::GemmArgs g = gemm_args(A, Wt, e->x, M, emb, K, emb);
-    g.out_ct = xs ? e->x_ct : nullptr;
-    g.out_ss = xs ? e->x_ss : nullptr;
-    return g;
-  };
-  const int nrm = xs ? 2 : 1;
+  if (R.split) MT3_TRY(mt3k::launch_residual_split(e->x, e->x_ct, e->x_ss, M, emb, s));
   for (int l = 0; l < c.num_encoder_layers; ++l) {
     LayerDev& L = e->enc[l];
-    MT3_TRY(mt3k::launch_gemm(dt, normed(L.wqkv, e->qkv, 3 * hd, 3 * hd), !xs, nrm, MT3_EPI_STORE, small, s));
-    MT3_TRY(mt3k::launch_encoder_attention(dt, e->qkv, e->attn, batch, T, c.num_heads, s));
-    MT3_TRY(mt3k::launch_gemm(dt, resid(e->attn, L.wo, hd), false, 0, MT3_EPI_RESID, small, s));
-    MT3_TRY(mt3k::launch_gemm(dt, normed(L.wi, e->hbuf, 2 * c.mlp_dim, c.mlp_dim), !xs, nrm, MT3_EPI_GEGLU, small, s));
-    MT3_TRY(mt3k::launch_gemm(dt, resid(e->hbuf, L.wo_mlp, c.mlp_dim), false, 0, MT3_EPI_RESID, small, s));
+    MT3_TRY(normed_gemm(e, R, L.wqkv, e->qkv, 3 * hd, MT3_EPI_STORE, small, s));
+    if (R.x6) MT3_TRY(mt3k::launch_encoder_attention_x6(e->qkv, e->attn, batch, T, c.num_heads, s));
+    else MT3_TRY(mt3k::launch_encoder_attention(dt, e->qkv, e->attn, batch, T, c.num_heads, s));
+    MT3_TRY(resid_gemm(e, L.wo, e->attn, R, small, s));
+    MT3_TRY(normed_gemm(e, R, L.wi, e->hbuf, c.mlp_dim, MT3_EPI_GEGLU, small, s));
+    MT3_TRY(resid_gemm(e, L.wo_mlp, e->hbuf, R, small, s));
   }
   MT3_TRY(mt3k::launch_rmsnorm(dt, e->x, e->enc_norm, e->enc_out, d_encoded_f32, M, emb, s));
   for (int l = 0; l < c.num_decoder_layers; ++l) {
-    mt3k::GemmArgs g = gemm_args(e->enc_out, e->dec[l].wkv_x, e->kv_fp8 ? e->cross_stage : ckv(l), M,
-                                 2 * hd, emb, 2 * hd);
+    const Dense& W = e->dec[l].wkv_x;
+    mt3k::GemmArgs g = gemm_args(e->enc_out, W, e->kv_fp8 ? e->cross_stage : ckv(l), M, 2 * hd);
     g.seq_len = T;
-    MT3_TRY(mt3k::launch_gemm(dt, g, false, false, MT3_EPI_HEADS, small, s));
+    MT3_TRY(dense_gemm(e, R.x6, g, W, false, 0, MT3_EPI_HEADS, small, s));
     if (e->kv_fp8)     // bf16 [2][B][H][T][64] -> e4m3 rows + one power-of-two scale per (row, head, position)
       MT3_TRY(mt3k::launch_kv_quantize_fp8(e->cross_stage, ckv(l), csc(l),
                                            batch * c.num_heads * T, s));
@@ -2549,11 +2557,6 @@ static int score_default_chunk(const mt3_engine* e) {
   return std::max(1, std::min(e->cfg.max_batch, kScoreRows / Lp));
 }
 
-static bool score_split(const mt3_engine* e) {
-  const int emb = e->cfg.emb_dim;
-  return e->cfg.compute_dtype == MT3_BF16 && emb % 64 == 0 && emb <= 1024;
-}
-
 static int ensure_score_workspace(mt3_engine* e, int segs) {
   if (e->score_cap >= segs) return MT3_OK;
   const mt3_engine_config& c = e->cfg;
@@ -2578,24 +2581,17 @@ static int ensure_score_workspace(mt3_engine* e, int segs) {
 }
 
 // f32 engine on the three-plane tile: plane copies of the decoder matrices it scores with (built once, on the device,
-// from the f32 matrices finalize uploaded -- the same split upload_planes makes on the host)
+// from the f32 matrices finalize uploaded -- the same split upload_dense makes on the host)
 static int ensure_score_planes(mt3_engine* e, hipStream_t s) {
   if (!e->x6 || e->score_planes) return MT3_OK;
-  const mt3_engine_config& c = e->cfg;
-  const size_t hd = e->HD(), emb = c.emb_dim, mlp = c.mlp_dim;
-  auto planes = [&](const void* w, size_t n, void* (&p)[3]) -> int {
-    for (int k = 0; k < 3; ++k) MT3_TRY(dmalloc(e, &p[k], n * 2));
-    return mt3k::launch_planes(static_cast<const float*>(w), p[0], p[1], p[2], n, s);
-  };
-  for (LayerDev& L : e->dec) {
-    MT3_TRY(planes(L.wqkv, 3 * hd * emb, L.wqkv_p));
-    MT3_TRY(planes(L.wo, emb * hd, L.wo_p));
-    MT3_TRY(planes(L.wq_x, hd * emb, L.wq_x_p));
-    MT3_TRY(planes(L.wo_x, emb * hd, L.wo_x_p));
-    MT3_TRY(planes(L.wi, 2 * mlp * emb, L.wi_p));
-    MT3_TRY(planes(L.wo_mlp, emb * mlp, L.wo_mlp_p));
+  std::vector<Dense*> all;
+  for (LayerDev& L : e->dec) all.insert(all.end(), {&L.wqkv, &L.wo, &L.wq_x, &L.wo_x, &L.wi, &L.wo_mlp});
+  all.push_back(&e->logits_w);
+  for (Dense* D : all) {
+    const size_t n = static_cast<size_t>(D->N) * D->K;
+    for (int k = 0; k < 3; ++k) MT3_TRY(dmalloc(e, &D->p[k], n * 2));
+    MT3_TRY(mt3k::launch_planes(static_cast<const float*>(D->w), D->p[0], D->p[1], D->p[2], n, s));
   }
-  MT3_TRY(planes(e->logits_w, static_cast<size_t>(c.vocab_size) * emb, e->logits_p));
   MT3_HIP_CHECK(hipStreamSynchronize(s));     // later calls may come on other streams
   e->score_planes = true;
   return MT3_OK;
@@ -2613,7 +2609,6 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0
   const int chunk = e->score_chunk_req > 0 ? e->score_chunk_req : score_default_chunk(e);
   MT3_TRY(ensure_score_workspace(e, chunk));
   MT3_TRY(ensure_score_planes(e, s));
-  const bool split = score_split(e), x6 = e->x6;
   const size_t es = e->esize;
   int chunks = 0;
   for (int seg0 = 0; seg0 < batch; seg0 += chunk, ++chunks) {
@@ -2623,29 +2618,13 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0
                              M, Lp, length, seg0, emb, V};
       MT3_TRY(mt3k::launch_score_embed(a, s));
     }
-    if (split) MT3_TRY(mt3k::launch_residual_split(e->sc_y, e->sc_y_ct, e->sc_y_ss, M, emb, s));
-    // the residual rows normalised into a projection (the norm scale is folded into W's rows): three planes (f32
-    // engine), the bf16 LDS-DMA tile from the split rows, or the encoder-sized tile with in-kernel statistics
-    auto normed = [&](const void* W, void* (&P)[3], void* out, int N, int ldo, int epi) -> int {
-      if (x6) {
-        mt3k::GemmArgs g = gemm_args(e->sc_y, P[0], out, M, N, emb, ldo);
-        return mt3k::launch_gemm_x6(g, P[1], P[2], true, epi == MT3_EPI_F32 ? MT3_EPI_STORE : epi, s);
-      }
-      mt3k::GemmArgs g = gemm_args(split ? static_cast<const void*>(e->sc_y_ct) : static_cast<const void*>(e->sc_y), W,
-                                   out, M, N, emb, ldo);
-      g.a_ss = split ? e->sc_y_ss : nullptr;
-      return mt3k::launch_gemm(dt, g, !split, split ? 2 : 1, epi, false, s);
-    };
-    auto resid = [&](const void* A, const void* W, void* (&P)[3], int K) -> int {
-      mt3k::GemmArgs g = gemm_args(A, x6 ? P[0] : W, e->sc_y, M, emb, K, emb);
-      if (x6) return mt3k::launch_gemm_x6(g, P[1], P[2], false, MT3_EPI_RESID, s);
-      g.out_ct = split ? e->sc_y_ct : nullptr;
-      g.out_ss = split ? e->sc_y_ss : nullptr;
-      return mt3k::launch_gemm(dt, g, false, 0, MT3_EPI_RESID, false, s);
-    };
+    // three planes (f32 engine), the bf16 LDS-DMA tile from the split rows, or the encoder-sized tile with in-kernel
+    // statistics
+    const Resid R = score_rows(e, M);
+    if (R.split) MT3_TRY(mt3k::launch_residual_split(e->sc_y, e->sc_y_ct, e->sc_y_ss, M, emb, s));
     for (int l = 0; l < c.num_decoder_layers; ++l) {
       LayerDev& L = e->dec[l];
-      MT3_TRY(normed(L.wqkv, L.wqkv_p, e->sc_qkv, 3 * hd, 3 * hd, MT3_EPI_STORE));
+      MT3_TRY(normed_gemm(e, R, L.wqkv, e->sc_qkv, 3 * hd, MT3_EPI_STORE, false, s));
       {
         mt3k::ScoreAttnArgs a{};
         a.q = e->sc_qkv;
@@ -2665,8 +2644,8 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0
         a.causal = 1;
         MT3_TRY(mt3k::launch_score_attention(dt, a, s));
       }
-      MT3_TRY(resid(e->sc_attn, L.wo, L.wo_p, hd));
-      MT3_TRY(normed(L.wq_x, L.wq_x_p, e->sc_q, hd, hd, MT3_EPI_STORE));
+      MT3_TRY(resid_gemm(e, L.wo, e->sc_attn, R, false, s));
+      MT3_TRY(normed_gemm(e, R, L.wq_x, e->sc_q, hd, MT3_EPI_STORE, false, s));
       {
         // the cross K/V cache of the encoded batch: [2][cur_batch][H][T][64]; the chunk's segments start at row row0 + seg0
         const size_t head = static_cast<size_t>(T) * 64;
@@ -2687,11 +2666,11 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0
         a.causal = 0;
         MT3_TRY(mt3k::launch_score_attention(dt, a, s));
       }
-      MT3_TRY(resid(e->sc_attn, L.wo_x, L.wo_x_p, hd));
-      MT3_TRY(normed(L.wi, L.wi_p, e->sc_h, 2 * c.mlp_dim, c.mlp_dim, MT3_EPI_GEGLU));
-      MT3_TRY(resid(e->sc_h, L.wo_mlp, L.wo_mlp_p, c.mlp_dim));
+      MT3_TRY(resid_gemm(e, L.wo_x, e->sc_attn, R, false, s));
+      MT3_TRY(normed_gemm(e, R, L.wi, e->sc_h, c.mlp_dim, MT3_EPI_GEGLU, false, s));
+      MT3_TRY(resid_gemm(e, L.wo_mlp, e->sc_h, R, false, s));
     }
-    MT3_TRY(normed(e->logits_w, e->logits_p, e->sc_logits, V, V, MT3_EPI_F32));     // decoder_norm folded
+    MT3_TRY(normed_gemm(e, R, e->logits_w, e->sc_logits, V, MT3_EPI_F32, false, s));     // decoder_norm folded
     {
       mt3k::ScoreReduceArgs a{e->sc_logits, e->sc_tgt, d_weights, e->sc_tok, d_token_scores, d_sequence_scores,
                               M, Lp, length, seg0, V};
