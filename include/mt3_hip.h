@@ -560,6 +560,41 @@ int mt3_op_decode_attention_fp8(const void* d_q, int32_t q_stride, void* d_kcach
                                 int32_t cap, const void* d_new_k, const void* d_new_v, int32_t kv_stride,
                                 const int32_t* d_step, int32_t n_keys, void* d_out, int32_t B, int32_t H,
                                 void* stream);
+/* The same kernels in EVERY form the decode loop launches them in (tests/test_gpu_decode_attention_forms.py): a view
+ * of all the launch's fields, pointers those of the first slot, optional ones NULL.  Test driver: it fills the launch
+ * description and launches on `stream`, nothing else (nothing allocated or waited for).
+ *   plain query:   q [B][q_stride] compute type (bf16 / f32 by `dtype`), as mt3_op_decode_attention.
+ *   folded query:  q NULL, q_f32 [B][q_stride] UNNORMALISED f32 products, q_ss [B][q_ss_n] the partial sums of squares of
+ *                  the residual row they were projected from (q_ss_n = emb / 16: 4 .. 64, a multiple of 4).  The kernel
+ *                  forms rs = rsqrt(sum(q_ss[b]) / (16 q_ss_n) + 1e-6) and uses round_ct(q_f32 * rs); with new_k / new_v
+ *                  those are f32 rows [B][kv_stride] too and round_ct(new * rs) is what is appended (e4m3 caches:
+ *                  quantised after the bf16 rounding).  q_stride (and kv_stride) % 4 == 0.
+ *   kv_scale:      non-NULL = e4m3 caches with their scale pairs [B][H][cap], as mt3_op_decode_attention_fp8 (bf16 only).
+ *   row retirement: done [B] per slot -- a slot with done != 0 is left alone: its out row, its cache row and its step
+ *                  entry are neither read nor written; cache_row [B] (needs done) maps slot b to the row of kcache /
+ *                  vcache / kv_scale it reads and appends in (NULL: row b).
+ * MT3_ERR_INVALID before anything touches a device: v NULL, q and q_f32 both NULL or both set, NULL caches / out, B, H
+ * or cap <= 0, n_keys outside 1 .. cap without step, new_k without new_v, q_f32 without q_ss or with q_ss_n outside
+ * 4 .. 64 / not a multiple of 4 or strides that are no multiple of 4, cache_row without done, kv_scale with f32. */
+typedef struct mt3_dec_attn_view {
+  const void* q;
+  int32_t q_stride, cap;
+  void* kcache;
+  void* vcache;
+  const void* new_k;
+  const void* new_v;
+  int32_t kv_stride, n_keys;
+  const int32_t* step;
+  void* out;
+  int32_t B, H;
+  void* kv_scale;
+  const float* q_f32;
+  const float* q_ss;
+  int32_t q_ss_n, reserved;
+  const int32_t* done;
+  const int32_t* cache_row;
+} mt3_dec_attn_view;
+int mt3_op_decode_attention_ex(int32_t dtype, const mt3_dec_attn_view* v, void* stream);
 /* d_src bf16 [2][rows][64] (K rows, then V rows) -> d_dst e4m3 [2][rows][64] + d_scales [rows] f32 pairs */
 int mt3_op_kv_quantize_fp8(const void* d_src, void* d_dst, void* d_scales, int32_t rows, void* stream);
 

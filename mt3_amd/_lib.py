@@ -95,6 +95,13 @@ class BeamKView(C.Structure):                  # mt3_beam_k_view
                [(n, _P) for n in ("live", "fin_score", "fin_step", "fin_beam", "hist_par", "hist_tok", "fork_src")]
 
 
+class DecAttnView(C.Structure):                # mt3_dec_attn_view (mt3_op_decode_attention_ex)
+    _fields_ = [("q", _P), ("q_stride", C.c_int32), ("cap", C.c_int32), ("kcache", _P), ("vcache", _P), ("new_k", _P),
+                ("new_v", _P), ("kv_stride", C.c_int32), ("n_keys", C.c_int32), ("step", _P), ("out", _P),
+                ("B", C.c_int32), ("H", C.c_int32), ("kv_scale", _P), ("q_f32", _P), ("q_ss", _P),
+                ("q_ss_n", C.c_int32), ("reserved", C.c_int32), ("done", _P), ("cache_row", _P)]
+
+
 # every symbol include/mt3_hip.h and include/mt3_hip_debug.h declare: (name, restype, argtypes)
 SIGNATURES = {
     "mt3_last_error": (C.c_char_p, []),
@@ -147,6 +154,7 @@ SIGNATURES = {
                                           C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_decode_attention_fp8": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32,
                                               _P, C.c_int32, C.c_int32, _P]),
+    "mt3_op_decode_attention_ex": (C.c_int, [C.c_int32, C.POINTER(DecAttnView), _P]),
     "mt3_op_kv_quantize_fp8": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "mt3_op_beam_search_scripted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,

@@ -370,6 +370,14 @@ __device__ __forceinline__ float key_group_sum(float v) {
   return v;
 }
 
+// a q . k sum in the base-2 softmax's units, rounded ONCE here: left to the compiler the product is contracted into the
+// subtraction of the running maximum (one FMA), the key that IS the maximum then gets the weight exp2(rounding error of
+// the product) instead of exp2(0) = 1, and a softmax over a single key no longer returns its V row bit for bit
+__device__ __forceinline__ float log2e_logit(float dot) {
+#pragma clang fp contract(off)
+  return dot * 1.4426950408889634f;
+}
+
 // 1 / rms of residual row b from its n (<= 64, a multiple of 4) partial sums of squares: lanes 0 .. n/4 - 1 of the
 // wave's first DPP row fetch a float4 each, the row is summed on the DPP network, lane 0's value is broadcast through
 // an SGPR -- the same order in every wave, a few VALU cycles instead of a six-step ds_bpermute butterfly
@@ -404,7 +412,6 @@ __global__ __launch_bounds__(NW * 64) void dec_attn_kernel(DecAttnArgs a) {
   constexpr int KPW = 64 / LPK;           // keys per wave per load
   constexpr int STRIDE = NW * KPW;        // keys per block iteration
   constexpr int UNROLL = 4;
-  constexpr float kLog2e = 1.4426950408889634f;
 
   __shared__ float s_m[NW][LPK], s_l[NW][LPK], s_acc[NW][LPK][KPL];
 
@@ -510,7 +517,7 @@ __global__ __launch_bounds__(NW * 64) void dec_attn_kernel(DecAttnArgs a) {
     float mn = m;
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      sc[u] = key_group_sum<LPK>(chunk_dot<CT>(qc, kv[u])) * kLog2e;
+      sc[u] = log2e_logit(key_group_sum<LPK>(chunk_dot<CT>(qc, kv[u])));
       if (base + slot + u * STRIDE < n_cache) mn = fmaxf(mn, sc[u]);
     }
     const float rs = __builtin_amdgcn_exp2f(m - mn);
@@ -544,7 +551,7 @@ __global__ __launch_bounds__(NW * 64) void dec_attn_kernel(DecAttnArgs a) {
   }
   if constexpr (APPEND) {
     // the new key: one lane group of the block carries it (weight 0 everywhere else)
-    const float s_new = key_group_sum<LPK>(chunk_dot<CT>(qc, new_k)) * kLog2e;
+    const float s_new = log2e_logit(key_group_sum<LPK>(chunk_dot<CT>(qc, new_k)));
     const bool mine = tid < LPK;
     const float mn = mine ? fmaxf(m, s_new) : m;
     const float rs = __builtin_amdgcn_exp2f(m - mn);
@@ -745,9 +752,10 @@ __global__ __launch_bounds__(NW * 64) void dec_attn_fp8_kernel(DecAttnArgs a) {
       }
     }
     const float rs1 = row_rs_from_partials(a.q_ss + static_cast<size_t>(b) * a.q_ss_n, a.q_ss_n, lane);
-    const float rs = rs1 * kLog2e;
+    // scale, round to bf16 as the GEMM epilogue would have (the query too: the same function of the same rows as the
+    // plain form and as dec_attn_kernel's folded form), then log2(e)
 #pragma unroll
-    for (int j = 0; j < EPL; ++j) q[j] *= rs;
+    for (int j = 0; j < EPL; ++j) q[j] = static_cast<float>(static_cast<__bf16>(q[j] * rs1)) * kLog2e;
     if constexpr (APPEND) {   // scale, round to bf16 as the GEMM epilogue would have
 #pragma unroll
       for (int j = 0; j < EPL; ++j) {
@@ -950,9 +958,16 @@ int launch_decode_attention(int dtype, const DecAttnArgs& a, hipStream_t s) {
   if (a.q_f32 && (!a.q_ss || a.q_ss_n <= 0 || a.q_ss_n > 64 || (a.q_ss_n & 3)))
     return mt3::fail(MT3_ERR_INVALID, "decode_attention: the unnormalised f32 query form needs the row's partial sums "
                                       "of squares (4 .. 64 of them, a multiple of 4)");
+  if (a.q_f32 && a.q) return mt3::fail(MT3_ERR_INVALID, "decode_attention: both query forms given (q and q_f32)");
   if (!a.step && (a.n_keys <= 0 || a.n_keys > a.cap)) return mt3::fail(MT3_ERR_INVALID, "decode_attention: n_keys");
   const bool append = a.new_k != nullptr;
   if (append && !a.new_v) return mt3::fail(MT3_ERR_INVALID, "decode_attention: new_k without new_v");
+  // the unnormalised f32 rows are fetched as float4
+  if (a.q_f32 && ((a.q_stride & 3) || (append && (a.kv_stride & 3))))
+    return mt3::fail(MT3_ERR_INVALID, "decode_attention: the unnormalised f32 rows need strides that are multiples of 4");
+  if (a.cache_row && !a.done)
+    return mt3::fail(MT3_ERR_INVALID, "decode_attention: cache_row without done (the kernels read the slot map only "
+                                      "next to the done flags)");
   // waves per (batch, head) workgroup.  B*H workgroups must all be resident for an even HBM stream:
   // at 84 VGPRs a CU holds 20 waves, so 3 waves per workgroup keeps B*H = 1536 groups (4608 waves)
   // co-resident on 256 CUs, while 4 would leave a 256-group second round running at 1/5 occupancy
@@ -1043,6 +1058,31 @@ int mt3_op_decode_attention_fp8(const void* d_q, int32_t q_stride, void* d_kcach
   a.B = B;
   a.H = H;
   return mt3k::launch_decode_attention(MT3_BF16, a, static_cast<hipStream_t>(stream));
+}
+
+int mt3_op_decode_attention_ex(int32_t dtype, const mt3_dec_attn_view* v, void* stream) {
+  if (!v) return mt3::fail(MT3_ERR_INVALID, "decode_attention_ex: null view");
+  mt3k::DecAttnArgs a{};
+  a.q = v->q;
+  a.q_stride = v->q_stride;
+  a.kcache = v->kcache;
+  a.vcache = v->vcache;
+  a.cap = v->cap;
+  a.new_k = v->new_k;
+  a.new_v = v->new_v;
+  a.kv_stride = v->kv_stride;
+  a.step = v->step;
+  a.n_keys = v->n_keys;
+  a.out = v->out;
+  a.B = v->B;
+  a.H = v->H;
+  a.kv_scale = static_cast<float2*>(v->kv_scale);
+  a.q_f32 = v->q_f32;
+  a.q_ss = v->q_ss;
+  a.q_ss_n = v->q_ss_n;
+  a.done = v->done;
+  a.cache_row = v->cache_row;
+  return mt3k::launch_decode_attention(dtype, a, static_cast<hipStream_t>(stream));
 }
 
 int mt3_op_kv_quantize_fp8(const void* d_src, void* d_dst, void* d_scales, int32_t rows, void* stream) {

@@ -946,6 +946,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
       x.q = q_d;
       x.q_stride = hd;
       if (e->q_fold) {
+        x.q = nullptr;                          // one query form per launch (launch_decode_attention refuses both)
         x.q_f32 = fold ? qkvf + 3 * hd : e->qf + static_cast<size_t>(row0) * hd;
         if (fold) x.q_stride = 4 * hd;
         x.q_ss = y_ss;

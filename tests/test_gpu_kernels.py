@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 from mt3_amd import _lib  # noqa: E402
+from tests.decode_attention_ref import _fp8_quant_ref  # noqa: E402
 
 BF16, F32 = _lib.MT3_BF16, _lib.MT3_F32
 
@@ -331,17 +332,6 @@ def test_decode_attention_cross(dtype):
 
 
 # ------------------------------------------------------------------ fp8 (e4m3) K/V cache
-def _fp8_quant_ref(x):
-    """rows [..., 64] (any float dtype) -> (uint8 e4m3fn bytes, power-of-two scale, dequantised f64): the rule of
-    fp8_quantize_quad: scale = 2^(exponent(amax) - 7) so that amax / scale is in [128, 256)."""
-    x = x.float()
-    amax = x.abs().amax(-1, keepdim=True)
-    e = torch.frexp(amax)[1].float() - 1                      # amax = m * 2^e, m in [1, 2)
-    scale = torch.where(amax > 0, torch.exp2(e - 7), torch.ones_like(amax))
-    q = (x / scale).to(torch.float8_e4m3fn)
-    return q.view(torch.uint8), scale.squeeze(-1), q.float().double() * scale.double()
-
-
 def test_kv_quantize_fp8_bit_exact():
     rows = 2 * 3 * 37
     g = torch.Generator(device="cuda").manual_seed(12)
