@@ -404,13 +404,42 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
                                 int32_t num_steps, int32_t flags, int32_t* d_ids, int32_t* d_all_ids /* NULL ok */,
                                 float* d_scores /* NULL ok */, mt3_transcribe_stats* h_stats, void* stream);
 
+/* Constrained decoding: per-segment token masks (allowed instruments are the use: mt3_codec_token_mask).  What a logit
+ * mask ahead of t5x decoding.beam_search does [from memory: t5x is not at hand, as for the beam search above]:
+ *   mask     a bit set over the vocabulary, words = ceil(vocab / 32) uint32: bit i % 32 of word i / 32 set = token i allowed.
+ *   rule     wherever the token rule reads the logit of a disallowed token it reads -inf: the token is never picked, never
+ *            a candidate of the beam-1 top 2 or the k-beam top 2k, and contributes exactly 0 to the log-sum-exp -- the
+ *            log-probabilities (live / finished scores) are renormalised over the allowed set.  The tie rules, beam-1 and
+ *            k-beam retirement, max_len, the synthetic EOS schedule (it still wins) and the next-input-row write are
+ *            unchanged.  Applied in the token kernels after the row scale and its write-back: the logits the engine hands
+ *            back (d_first_logits, per-step logits, the rows scaled in place) stay the model's own, unmasked.
+ *   segments h_seg_mask [n_segments]: the mask index of segment i, -1 = unconstrained; NULL: mask 0 for every segment
+ *            (n_masks must be 1).  In mt3_engine_decode "segment i" is batch row i, in mt3_engine_decode_beams element i,
+ *            in mt3_engine_transcribe / mt3_engine_transcribe_beams segment i of the job: the mask follows the segment
+ *            through compaction and refills.
+ * h_masks [n_masks][words] and h_seg_mask are HOST arrays, copied into engine-owned device memory by this call
+ * (synchronous, a setup call like mt3_engine_finalize); h_masks == NULL or n_masks == 0 clears.  The masks stay set for
+ * every later mt3_engine_decode / _decode_beams / _transcribe / _transcribe_beams until cleared; masked and unmasked steps
+ * never share a captured graph, and an unmasked decode runs the kernels, graphs and bits it ran before masks existed.
+ * mt3_engine_decode_forced, mt3_engine_score and mt3_engine_score_segments IGNORE masks (note confidences stay the
+ * unconstrained model's log-probabilities).  MT3_STATUS_TOKEN_MASKS reports the number of masks set.
+ * MT3_ERR_INVALID, before any device work: n_masks < 0; NULL h_seg_mask with n_masks > 1; n_segments < 1 with h_seg_mask;
+ * an index outside [-1, n_masks); a mask that forbids EOS (id 1); a mask that allows fewer than 2 tokens; bits at or past
+ * vocab set in the last word; an engine that is not finalized; a decode in flight.
+ * The decode / transcribe calls return MT3_ERR_INVALID before any device work for more rows / elements / segments than
+ * n_segments when a per-segment index is set and, for the beam calls, a mask in use with fewer than 2 * num_beams allowed
+ * tokens. */
+int mt3_engine_set_token_masks(mt3_engine* e, const uint32_t* h_masks /* [n_masks][words] */, int32_t n_masks,
+                               const int32_t* h_seg_mask /* [n_segments] or NULL */, int32_t n_segments);
+
 /* Teacher-forced cached decode: Transformer.decode (mt3/network.py:303-361) on GIVEN decoder inputs, driven one
  * token per call through the same cached step (layers.py:246-314) the autoregressive loop uses -- the input of
  * step 0 is BOS, the input of step t+1 is d_forced_ids[b][t] (i.e. decoder_input_tokens = shift_right(forced),
  * seqio autoregressive_inputs as in mt3/models.py:96).  d_forced_ids [batch, L] int32.  d_step_logits (may be
  * NULL): [num_steps, batch, vocab] f32, the logits of EVERY step (the parity tests compare them with the
  * reference's teacher-forced logits at all cache depths).  d_ids [batch, L]: the arg-max of each step (no EOS
- * bookkeeping).  flags: MT3_DECODE_NO_GRAPH, MT3_DECODE_CHAINS(n); not BEAM1 / EARLY_EXIT. */
+ * bookkeeping).  flags: MT3_DECODE_NO_GRAPH, MT3_DECODE_CHAINS(n); not BEAM1 / EARLY_EXIT.  Token masks
+ * (mt3_engine_set_token_masks) are ignored: the arg-max is the unconstrained model's. */
 int mt3_engine_decode_forced(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags,
                              const int32_t* d_forced_ids, float* d_step_logits, int32_t* d_ids, void* stream);
 
@@ -447,7 +476,8 @@ int mt3_engine_decode_forced(mt3_engine* e, int32_t batch, int32_t num_steps, in
  * of the same encoded rows after it returns the same ids.
  * MT3_ERR_INVALID: a decode in flight (MT3_DECODE_ASYNC), e4m3 K/V caches (kv_cache_dtype MT3_FP8_E4M3: out of scope),
  * length outside 1 .. max_decode_len, batch outside 1 .. the encoded batch, null targets or sequence scores.  Ids
- * outside [0, vocab) are the caller's error (they are clamped, the scores are then meaningless). */
+ * outside [0, vocab) are the caller's error (they are clamped, the scores are then meaningless).  Token masks
+ * (mt3_engine_set_token_masks) are ignored: the scores are the unconstrained model's log-probabilities. */
 int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t* d_targets,
                      const int32_t* d_decoder_inputs /* NULL: shift right */, const float* d_weights /* NULL: target > 0 */,
                      float* d_sequence_scores, float* d_token_scores, float* d_logits, void* stream);
@@ -478,7 +508,8 @@ int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t
  * It does not touch the decode state.  MT3_STATUS_SCORE_CHUNKS reports the prefill chunks of the whole call.
  * MT3_ERR_INVALID, before any device work: a NULL engine, inputs, targets or sequence scores; n_segments < 1; length
  * outside 1 .. max_decode_len; an engine that is not finalized; a decode in flight (MT3_DECODE_ASYNC); e4m3 K/V caches
- * (kv_cache_dtype MT3_FP8_E4M3: out of scope, as for mt3_engine_score).  Ids outside [0, vocab) are clamped. */
+ * (kv_cache_dtype MT3_FP8_E4M3: out of scope, as for mt3_engine_score).  Ids outside [0, vocab) are clamped.  Token
+ * masks (mt3_engine_set_token_masks) are ignored, as by mt3_engine_score. */
 int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs /* [n_segments, T, input_depth] log-mel */,
                               int32_t n_segments, int32_t length, const int32_t* d_targets /* [n_segments, length] */,
                               float* d_sequence_scores /* [n_segments] */, float* d_token_scores /* [n, length] or NULL */,
@@ -498,7 +529,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_PARTITION_FALLBACKS = 8 /* decodes that wanted the row-group schedule but could not set it up */,
        MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */,
        MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams / mt3_engine_transcribe_beams */,
-       MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score / mt3_engine_score_segments (all its encoder chunks) */ };
+       MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score / mt3_engine_score_segments (all its encoder chunks) */,
+       MT3_STATUS_TOKEN_MASKS = 12 /* masks set by mt3_engine_set_token_masks (0: none) */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -630,6 +662,19 @@ int mt3_op_beam_search_scripted(const float* d_logits, const float* d_ss, int32_
 int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
                                 int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
                                 int32_t* h_done, void* stream);
+/* The two drivers above with token masks (mt3_engine_set_token_masks states the rule): d_masks [n_masks][ceil(vocab / 32)]
+ * uint32 and d_row_mask, the mask index (-1: unconstrained) per ROW for the token kernel and per ELEMENT for the beam
+ * kernel (NULL: mask 0), both DEVICE arrays.  They are read back and checked first: MT3_ERR_INVALID for n_masks outside
+ * 1 .. 4096, an index outside [-1, n_masks), a mask without EOS, with bits past vocab, or with fewer than 2 (token
+ * kernel) / 2k (beam kernel) allowed tokens.  The logits in d_logits stay unmasked. */
+int mt3_op_beam_search_masked(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                              int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                              const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
+                              float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks, int32_t* h_steps_run,
+                              void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask);
+int mt3_op_token_steps_masked(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
+                              int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
+                              void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask);
 /* The fork copies of one k-beam step on caller-owned caches: for every slot with d_fork_src[slot] >= 0 and
  * d_done[slot] == 0, positions [0, d_step[slot]) of row d_fork_src[slot] are copied into row d_slot_row[slot] of every
  * layer's K and V cache [rows][H][cap][64] of kv_esize-byte elements (1, 2 or 4) and, where given, of its scale pairs
@@ -792,6 +837,13 @@ int mt3_build_codec(int32_t steps_per_second, int32_t max_shift_seconds, int32_t
 int mt3_codec_num_classes(const mt3_codec* c);
 int mt3_codec_decode_event(const mt3_codec* c, int32_t index, int32_t* type, int32_t* value);  /* MT3_ERR_INVALID = ValueError */
 int mt3_codec_encode_event(const mt3_codec* c, int32_t type, int32_t value, int32_t* index);
+/* The token mask of a set of instruments (mt3_engine_set_token_masks): h_mask [ceil(vocab / 32)] uint32 with every id
+ * below vocab allowed except the MT3_EV_PROGRAM events whose value is not in programs [n_programs] (n_programs < 0: all
+ * programs) and, with allow_drums == 0, the MT3_EV_DRUM events.  Token id = 3 + event index (mt3_ids_to_tokens); ids at
+ * or past vocab are never set.  MT3_ERR_INVALID: a program outside the codec's range, programs given for a codec without
+ * a program range, vocab < 3 or null pointers. */
+int mt3_codec_token_mask(const mt3_codec* c, int32_t vocab, const int32_t* programs, int32_t n_programs,
+                         int32_t allow_drums, uint32_t* h_mask);
 /* tokens: concatenated per-segment token rows (already trimmed at EOS); seg_offsets [n_segments+1];
  * h_has_max_time==NULL -> the combiner rule (max_time = next segment's start, none for the last);
  * otherwise explicit per-segment max_time (decode_events' own argument). */

@@ -13,6 +13,8 @@
 //   beam_step_kernel    one step of t5x beam_search with num_decodes = k (mt3_engine_decode_beams): one wave per live
 //                       beam, the k * 2k candidates merged in LDS, the slot -> cache-row map rewritten; with
 //                       beam_reorder_kernel (K/V copies of forked rows) and beam_finalize_kernel (history backtrack).
+//                       Both token kernels have a MASKED instantiation (constrained decoding, TokenMask in kernels.h):
+//                       the logit of a token the slot's mask disallows counts as -inf.
 //   ids_to_tokens_kernel GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271), bit-exact.
 #include <hip/hip_runtime.h>
 
@@ -182,6 +184,23 @@ struct Top2 {
   }
 };
 
+// Constrained decoding (TokenMask, kernels.h): what a logit mask ahead of t5x `beam_search` does -- a disallowed token's
+// logit is -inf wherever the token rule reads it.  (t5x is not at hand: written from memory, as the beam rule is.)
+constexpr float kMaskedLogit = -__builtin_inff();
+// the mask row of segment `seg`, nullptr = unconstrained; never indexes with a negative segment or mask index
+__device__ __forceinline__ const uint32_t* mask_row(const TokenMask& tm, int seg) {
+  if (seg < 0) return nullptr;
+  const int m = tm.seg_mask ? tm.seg_mask[seg] : 0;
+  return m < 0 ? nullptr : tm.masks + static_cast<size_t>(m) * tm.words;
+}
+__device__ __forceinline__ bool mask_allows(uint32_t word, int i) { return (word >> (i & 31)) & 1u; }
+// row[i] as the token rule reads it in the loops that walk the row in memory (vocab > 2048)
+template <bool MASKED>
+__device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mrow, int i) {
+  if (MASKED && mrow && !mask_allows(mrow[i >> 5], i)) return kMaskedLogit;
+  return row[i];
+}
+
 // BEAM1 = false: greedy pick (the product default).
 // BEAM1 = true : one step of t5x `beam_search` with num_decodes = 1: the two best
 //   candidates of log_softmax are taken; the LIVE hypothesis follows the best non-EOS one; an EOS candidate
@@ -191,7 +210,10 @@ struct Top2 {
 //   [live_logp | best_score] per row, beam_len the prefix length of the best finished hypothesis (-1: none);
 //   beam_cfg[0] = brevity_penalty(max_len + 1) of this call, beam_cfg[1 + n] = brevity_penalty(n) =
 //   ((5 + n) / 6) ^ alpha, tabulated on the host.
-template <bool BEAM1>
+// MASKED = true : a.tm restricts the pick of every slot to its segment's allowed tokens (exactly 0 in the exp-sum, never a
+//   candidate); the logits in memory, scaled or not, stay the model's own.  MASKED = false compiles from the statements
+//   the kernel had before masks existed.
+template <bool BEAM1, bool MASKED>
 __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   const SlotState& st = a.st;
   const StepRetire& rt = a.rt;
@@ -219,6 +241,20 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
     for (int u = 0; u < kPer; ++u) {
       const int i = tid + u * 256;
       xv[u] = row[i < vocab ? i : vocab - 1];
+    }
+  }
+  // MASKED: the mask word of each of those logits, requested in the same batch -- nothing has been waited for yet, so the
+  // words ride behind the logits and cost no round trip of their own
+  const uint32_t* mrow = nullptr;
+  uint32_t mw[kPer];
+  if (MASKED) {
+    mrow = mask_row(a.tm, rt.slot_seg ? rt.slot_seg[b] : out_row);
+    if (in_regs) {
+#pragma unroll
+      for (int u = 0; u < kPer; ++u) {
+        const int i = tid + u * 256;
+        mw[u] = mrow ? mrow[(i < vocab ? i : vocab - 1) >> 5] : 0xffffffffu;
+      }
     }
   }
   // thread 0 issues its state loads up front so that their latency hides behind the reductions
@@ -260,6 +296,11 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
       // (each thread re-reads below exactly the elements it just wrote: no barrier needed)
     }
   }
+  if (MASKED && in_regs) {                 // after the scale and its write-back: memory keeps the model's logits
+#pragma unroll
+    for (int u = 0; u < kPer; ++u)
+      if (!mask_allows(mw[u], tid)) xv[u] = kMaskedLogit;      // (i & 31 == tid & 31: i = tid + 256 u)
+  }
   Top2 t2{-3.0e38f, -3.0e38f, 0x7fffffff, 0x7fffffff};
   float acc = 0.f;
   if (in_regs) {
@@ -275,9 +316,9 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
         if (tid + u * 256 < vocab) acc += __expf(xv[u] - t2.v1);
     }
   } else {
-    for (int i = tid; i < vocab; i += 256) t2.insert(row[i], i);   // ascending i per thread
+    for (int i = tid; i < vocab; i += 256) t2.insert(rule_logit<MASKED>(row, mrow, i), i);   // ascending i per thread
     if (BEAM1) {
-      for (int i = tid; i < vocab; i += 256) acc += __expf(row[i] - t2.v1);
+      for (int i = tid; i < vocab; i += 256) acc += __expf(rule_logit<MASKED>(row, mrow, i) - t2.v1);
     }
   }
   const float own_max = t2.v1;
@@ -374,7 +415,12 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
   if (a.ls.ss && (a.ls.n_ss <= 0 || a.ls.n_ss > 64 || a.ls.dim <= 0))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: the row scale needs 1 .. 64 partial sums");
   if (const int rc = bad_input_row(a.in, "argmax_step")) return rc;
-  hipLaunchKernelGGL(a.beam.f ? argmax_step_kernel<true> : argmax_step_kernel<false>, dim3(a.B), dim3(256), 0, s, a);
+  if (a.tm.masks && (a.forced || a.tm.words != (a.vocab + 31) / 32))
+    return mt3::fail(MT3_ERR_INVALID, "argmax_step: token masks are ceil(vocab / 32) words and not for teacher forcing");
+  void (*kernel)(ArgmaxStepArgs);
+  if (a.tm.masks) kernel = a.beam.f ? argmax_step_kernel<true, true> : argmax_step_kernel<false, true>;
+  else kernel = a.beam.f ? argmax_step_kernel<true, false> : argmax_step_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3(a.B), dim3(256), 0, s, a);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -605,7 +651,10 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
 //      the history, the slot -> cache-row map (a beam takes over its parent's row; the extra children of a parent take
 //      the rows of parents nobody chose and are marked for beam_reorder_kernel) and the retirement;
 //   4. each wave writes its slot's next input row, as the greedy / beam-1 kernel does.
-__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls) {
+// MASKED = true: the logits of the tokens the element's mask (tm) disallows are -inf in steps 1 and 2 -- 0 in the
+// log-sum-exp, never among the 2k; a mask in use allows at least 2k tokens (checked on the host).
+template <bool MASKED>
+__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls, TokenMask tm) {
   constexpr int kPerLane = 32;                         // vocab <= 2048: lane l holds i = l + 64 * vt + 256 * u
   __shared__ float c_score[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int c_tok[2 * kBeamMaxK * kBeamMaxK];
@@ -622,6 +671,16 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
     const int i = lane + 64 * (j >> 3) + 256 * (j & 7);
     xv[j] = row[i < a.vocab ? i : a.vocab - 1];
   }
+  // MASKED: the mask word of every logit the lane holds, requested in the same batch as the logits
+  uint32_t mw[kPerLane];
+  if (MASKED) {
+    const uint32_t* mrow = mask_row(tm, tm.slot_seg ? tm.slot_seg[s0] : static_cast<int>(blockIdx.x));
+#pragma unroll
+    for (int j = 0; j < kPerLane; ++j) {
+      const int i = lane + 64 * (j >> 3) + 256 * (j & 7);
+      mw[j] = mrow ? mrow[(i < a.vocab ? i : a.vocab - 1) >> 5] : 0xffffffffu;
+    }
+  }
   const float live = a.live[slot];
   if (ls.ss) {                                         // folded logits projection (LogitScale)
     float p = lane < ls.n_ss ? ls.ss[static_cast<size_t>(slot) * ls.n_ss + lane] : 0.f;
@@ -630,6 +689,11 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
     const float rs = rsqrtf(p / static_cast<float>(ls.dim) + 1e-6f);
 #pragma unroll
     for (int j = 0; j < kPerLane; ++j) xv[j] *= rs;
+  }
+  if (MASKED) {
+#pragma unroll
+    for (int j = 0; j < kPerLane; ++j)
+      if (!mask_allows(mw[j], lane)) xv[j] = kMaskedLogit;     // (i & 31 == lane & 31: i = lane + a multiple of 64)
   }
   // log-sum-exp of the row, in argmax_step_kernel<true>'s order: per thread, per wave, then over the four waves
   float vmax[4], vsum[4];
@@ -822,7 +886,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
   if (a.in.y) put_input_row(a.in, slot, s_tok[w], t + 1, lane, 64);
 }
 
-int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, hipStream_t s) {
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, hipStream_t s) {
   if (a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || a.vocab < 2 * a.k || a.vocab > 2048)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: k must be 1 .. 8 and 2k <= vocab <= 2048");
   if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.st.slot_row ||
@@ -832,7 +896,10 @@ int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, hipStream_t s) {
     return mt3::fail(MT3_ERR_INVALID, "beam_step: the row scale needs 1 .. 64 partial sums");
   if (a.in.y && a.in.dim % 16) return mt3::fail(MT3_ERR_INVALID, "beam_step: the next input row needs dim % 16 == 0");
   if (const int rc = bad_input_row(a.in, "beam_step")) return rc;
-  hipLaunchKernelGGL(beam_step_kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls);
+  if (tm.masks && tm.words != (a.vocab + 31) / 32)
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: token masks are ceil(vocab / 32) words");
+  hipLaunchKernelGGL(tm.masks ? beam_step_kernel<true> : beam_step_kernel<false>, dim3(a.elems), dim3(64 * a.k), 0, s, a,
+                     ls, tm);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -1174,23 +1241,51 @@ int upload_brevity(float* d_bp, int num_steps, hipStream_t s) {
 
 bool bad_scale(const float* d_ss, int n_ss, int dim) { return d_ss && (n_ss < 1 || n_ss > 64 || dim <= 0); }
 
+// the masks of a masked driver, read back and checked on the host before a kernel indexes with them: every mask valid
+// (bad_token_mask) with at least `need` allowed tokens, every entry of d_row_mask [n] in [-1, n_masks)
+int driver_masks(const std::string& who, const uint32_t* d_masks, int n_masks, const int32_t* d_row_mask, int n, int vocab,
+                 int need, mt3k::TokenMask* tm) {
+  if (!d_masks || n_masks < 1 || n_masks > 4096) return mt3::fail(MT3_ERR_INVALID, who + ": 1 .. 4096 masks");
+  const int words = (vocab + 31) / 32;
+  std::vector<uint32_t> h(static_cast<size_t>(n_masks) * words);
+  MT3_HIP_CHECK(hipMemcpy(h.data(), d_masks, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int m = 0; m < n_masks; ++m) {
+    int allowed = 0;
+    if (const char* bad = mt3k::bad_token_mask(h.data() + static_cast<size_t>(m) * words, vocab, &allowed))
+      return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+    if (allowed < need) return mt3::fail(MT3_ERR_INVALID, who + ": a mask allows fewer than 2 * k tokens");
+  }
+  if (d_row_mask) {
+    std::vector<int32_t> r(static_cast<size_t>(n));
+    MT3_HIP_CHECK(hipMemcpy(r.data(), d_row_mask, r.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t v : r)
+      if (v < -1 || v >= n_masks) return mt3::fail(MT3_ERR_INVALID, who + ": mask index outside [-1, n_masks)");
+  }
+  *tm = mt3k::TokenMask{d_masks, d_row_mask, nullptr, words};
+  return MT3_OK;
+}
+
+
 }  // namespace
 
-extern "C" int mt3_op_beam_search_scripted(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim,
-                                           int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
-                                           const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids,
-                                           int32_t* d_all_ids, float* d_scores, float* d_y_next, int32_t* h_trace,
-                                           float* h_live, int32_t* h_forks, int32_t* h_steps_run, void* stream) {
+// shared body of mt3_op_beam_search_scripted (masked == false) and mt3_op_beam_search_masked
+static int beam_search_driver(const std::string& who, bool masked, const float* d_logits, const float* d_ss, int32_t n_ss,
+                              int32_t dim, int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
+                              const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids,
+                              float* d_scores, float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks,
+                              int32_t* h_steps_run, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                              const int32_t* d_row_mask) {
   if (!d_logits || !d_ids || !d_all_ids || !d_scores || !h_trace || !h_live || !h_forks || !h_steps_run)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: null argument");
+    return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if (k < 1 || k > mt3k::kBeamMaxK || vocab < 2 * k || vocab > 2048)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: k must be 1 .. 8 and 2k <= vocab <= 2048");
+    return mt3::fail(MT3_ERR_INVALID, who + ": k must be 1 .. 8 and 2k <= vocab <= 2048");
   if (elems <= 0 || elems > 4096 || num_steps <= 0 || num_steps > 4096 || max_len < 0 || bad_scale(d_ss, n_ss, dim))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: elems / num_steps / max_len / row scale out of range");
+    return mt3::fail(MT3_ERR_INVALID, who + ": elems / num_steps / max_len / row scale out of range");
   if ((d_table != nullptr) != (d_pos != nullptr) || (d_table != nullptr) != (d_y_next != nullptr) ||
       (d_table && (dim_e <= 0 || dim_e % 16)))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_beam_search_scripted: the tables and the next-row output come together, "
-                                      "dim_e % 16 == 0");
+    return mt3::fail(MT3_ERR_INVALID, who + ": the tables and the next-row output come together, dim_e % 16 == 0");
+  mt3k::TokenMask tm{};
+  if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, elems, vocab, 2 * k, &tm));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int slots = elems * k;
   const size_t n = static_cast<size_t>(slots), hist = static_cast<size_t>(num_steps) * n;
@@ -1232,7 +1327,7 @@ extern "C" int mt3_op_beam_search_scripted(const float* d_logits, const float* d
   for (int t = 0; t < num_steps; ++t) {
     b.logits = const_cast<float*>(d_logits) + static_cast<size_t>(t) * n * vocab;
     const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, s));
+    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, s));
     int32_t* tr = h_trace + static_cast<size_t>(t) * 4 * n;
     MT3_HIP_CHECK(hipMemcpyAsync(tr, b.st.slot_row, n * 4, hipMemcpyDeviceToHost, s));
     MT3_HIP_CHECK(hipMemcpyAsync(tr + n, b.fork_src, n * 4, hipMemcpyDeviceToHost, s));
@@ -1254,14 +1349,39 @@ extern "C" int mt3_op_beam_search_scripted(const float* d_logits, const float* d
   return MT3_OK;
 }
 
-extern "C" int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
-                                           int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
-                                           int32_t* d_ids, int32_t* h_done, void* stream) {
-  if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, "mt3_op_token_steps_scripted: null argument");
+extern "C" int mt3_op_beam_search_scripted(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim,
+                                           int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
+                                           const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids,
+                                           int32_t* d_all_ids, float* d_scores, float* d_y_next, int32_t* h_trace,
+                                           float* h_live, int32_t* h_forks, int32_t* h_steps_run, void* stream) {
+  return beam_search_driver("mt3_op_beam_search_scripted", false, d_logits, d_ss, n_ss, dim, elems, k, vocab, num_steps,
+                            max_len, d_table, d_pos, dim_e, d_ids, d_all_ids, d_scores, d_y_next, h_trace, h_live, h_forks,
+                            h_steps_run, stream, nullptr, 0, nullptr);
+}
+
+extern "C" int mt3_op_beam_search_masked(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                                         int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                                         const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids,
+                                         float* d_scores, float* d_y_next, int32_t* h_trace, float* h_live,
+                                         int32_t* h_forks, int32_t* h_steps_run, void* stream, const uint32_t* d_masks,
+                                         int32_t n_masks, const int32_t* d_row_mask) {
+  return beam_search_driver("mt3_op_beam_search_masked", true, d_logits, d_ss, n_ss, dim, elems, k, vocab, num_steps,
+                            max_len, d_table, d_pos, dim_e, d_ids, d_all_ids, d_scores, d_y_next, h_trace, h_live, h_forks,
+                            h_steps_run, stream, d_masks, n_masks, d_row_mask);
+}
+
+// shared body of mt3_op_token_steps_scripted (masked == false) and mt3_op_token_steps_masked
+static int token_steps_driver(const std::string& who, bool masked, float* d_logits, const float* d_ss, int32_t n_ss,
+                              int32_t dim, int32_t rows, int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
+                              int32_t* d_ids, int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                              const int32_t* d_row_mask) {
+  if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
       max_len < 0 || bad_scale(d_ss, n_ss, dim))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_token_steps_scripted: mode is 0 (greedy) or 1 (beam-1); rows, vocab >= 2, "
-                                      "num_steps, max_len or the row scale out of range");
+    return mt3::fail(MT3_ERR_INVALID, who + ": mode is 0 (greedy) or 1 (beam-1); rows, vocab >= 2, num_steps, max_len or "
+                                            "the row scale out of range");
+  mt3k::TokenMask tm{};
+  if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, rows, vocab, 2, &tm));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n = static_cast<size_t>(rows);
   Scratch m;
@@ -1285,6 +1405,7 @@ extern "C" int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, i
   // a row that max_len closes is retired, as it is in the engine's streaming jobs (the only ones that set max_len)
   a.rt = mt3k::StepRetire{max_len > 0 ? 1 : 0, nullptr, nullptr, nullptr, max_len};
   a.B = rows;
+  a.tm = tm;
   MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, n * num_steps * 4, s));
   MT3_HIP_CHECK(hipMemsetAsync(len, 0xFF, n * 4, s));                       // -1: nothing finished
   MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
@@ -1298,6 +1419,21 @@ extern "C" int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, i
   if (mode == 1) MT3_OP_TRY(mt3k::launch_beam1_finalize(d_ids, num_steps, len_row, rows, s));
   MT3_HIP_CHECK(hipStreamSynchronize(s));
   return MT3_OK;
+}
+
+extern "C" int mt3_op_token_steps_scripted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                           int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
+                                           int32_t* d_ids, int32_t* h_done, void* stream) {
+  return token_steps_driver("mt3_op_token_steps_scripted", false, d_logits, d_ss, n_ss, dim, rows, vocab, num_steps, mode,
+                            max_len, d_ids, h_done, stream, nullptr, 0, nullptr);
+}
+
+extern "C" int mt3_op_token_steps_masked(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                         int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                         int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                                         const int32_t* d_row_mask) {
+  return token_steps_driver("mt3_op_token_steps_masked", true, d_logits, d_ss, n_ss, dim, rows, vocab, num_steps, mode,
+                            max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask);
 }
 
 extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots,

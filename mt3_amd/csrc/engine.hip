@@ -117,14 +117,17 @@ struct LayerDev {
 // 4 = beam-1 token selection, 8 = teacher forcing, 16 = row retirement (finished slots cost nothing, the slot map is
 // in use), 32 = the synthetic EOS schedule (mt3_debug_engine_set_eos_schedule)
 // 64 = in-flight batching (mt3_engine_transcribe: finished slots restart on new segments, the slot -> segment map is in use)
-constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kNumVariants = 128;
+// 128 = token masks (mt3_engine_set_token_masks): the step ends with the MASKED token / beam kernel, so masked and unmasked
+// steps never share a captured graph
+constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kVarMask = 128,
+              kNumVariants = 256;
 // not a step variant of its own (never an index into graph_exec): set in GroupRun::variant when the decode runs as SEVERAL
 // row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
 // keeps such steps apart from a lone stream's steps of the same shape
-constexpr int kVarBeside = 128;
+constexpr int kVarBeside = 256;
 // not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
 // number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
-constexpr int kVarBeams = 256, kVarBeamsShift = 9;
+constexpr int kVarBeams = 512, kVarBeamsShift = 10;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
 // to kStageChunkCap segments each (one encoder pass per chunk)
@@ -259,6 +262,14 @@ struct mt3_engine {
                                  // mt3_engine_transcribe -- per segment
   int eos_cap = 0;
   bool eos_on = false;
+  // Constrained decoding (mt3_engine_set_token_masks): engine-owned copies, whose addresses the kVarMask step graphs hold
+  uint32_t* tm_masks = nullptr;  // [tm_mask_cap] words: tm_n masks of ceil(vocab / 32) words
+  int* tm_seg = nullptr;         // [tm_seg_cap] mask index per row / element / segment
+  size_t tm_mask_cap = 0, tm_seg_cap = 0;
+  int tm_n = 0;                  // masks set (0: unconstrained)
+  bool tm_seg_on = false;        // a per-segment index is set (false: mask 0 for every segment); baked into the step graphs
+  std::vector<int> tm_allowed;   // host: allowed tokens of each mask
+  std::vector<int> tm_seg_host;  // host copy of the per-segment index
   // In-flight batching (mt3_engine_transcribe): slot_seg maps a slot to the SEGMENT it is decoding (-1: none); a
   // finished slot hands its id row to the caller's output and restarts on the next encoded segment (launch_refill)
   int* slot_seg = nullptr;       // [max_batch]
@@ -850,7 +861,13 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     b.logits = logits;
     b.max_len = (skip & kVarStream) ? e->stream_max_len : 0;
     const mt3k::LogitScale ls{fold ? y_ss : nullptr, emb / 16, emb};
-    MT3_TRY(mt3k::launch_beam_step(b, ls, s));
+    mt3k::TokenMask tm{};
+    if (skip & kVarMask) {     // in-flight: the element's segment; a batch call: element row0 / k + block
+      const bool streaming = (skip & kVarStream) != 0;
+      const int* seg = !e->tm_seg_on ? nullptr : (streaming ? e->tm_seg : e->tm_seg + row0 / b.k);
+      tm = mt3k::TokenMask{e->tm_masks, seg, streaming ? e->slot_seg + row0 : nullptr, (c.vocab_size + 31) / 32};
+    }
+    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, s));
     mt3k::BeamReorderArgs r{};
     r.n_layers = nl;
     r.H = H;
@@ -885,6 +902,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     a.rt = mt3k::StepRetire{retire ? 1 : 0, retire ? a.st.slot_row : nullptr, (skip & kVarEos) ? e->eos_at + crow0 : nullptr,
                             streaming ? a.st.slot_seg : nullptr, streaming ? e->stream_max_len : 0};
     a.B = rows;
+    if (skip & kVarMask)       // indexed as eos_at is: by segment, or by the row the slot decodes
+      a.tm = mt3k::TokenMask{e->tm_masks, e->tm_seg_on ? e->tm_seg + crow0 : nullptr, nullptr, (c.vocab_size + 31) / 32};
     return mt3k::launch_argmax_step(a, s);
   }
   LayerDev& L = e->dec[op >> 3];
@@ -1909,6 +1928,19 @@ static int reset_beam1_state(mt3_engine* e, int num_steps, hipStream_t s) {
 }
 
 // shared body of mt3_engine_decode / mt3_engine_decode_forced
+// MT3_OK, or why a job of `n` rows / elements / segments whose step needs `need` candidates cannot run under the masks set
+static int masks_fit(const mt3_engine* e, const char* who, int n, int need) {
+  if (!e->tm_n) return MT3_OK;
+  if (e->tm_seg_on && n > static_cast<int>(e->tm_seg_host.size()))
+    return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": more rows or segments than the token masks' n_segments");
+  for (int i = 0; i < (e->tm_seg_on ? n : 1); ++i) {
+    const int m = e->tm_seg_on ? e->tm_seg_host[i] : 0;
+    if (m >= 0 && e->tm_allowed[m] < need)
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": a token mask in use allows fewer than 2 * num_beams tokens");
+  }
+  return MT3_OK;
+}
+
 static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t debug_skip,
                        const int32_t* d_forced, float* d_step_logits, int32_t* d_ids, float* d_first_logits,
                        int32_t* h_steps_run, void* stream) {
@@ -1927,6 +1959,8 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   const bool async = (flags & MT3_DECODE_ASYNC) != 0;
   if (d_forced && (beam1 || early || async))
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_forced: not combinable with BEAM1 / EARLY_EXIT / ASYNC");
+  const bool masked = e->tm_n > 0 && !d_forced;          // teacher forcing ignores token masks
+  if (masked) MT3_TRY(masks_fit(e, "mt3_engine_decode", batch, 2));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(reset_slots(e, batch, true, true, s));
   if (d_forced)    // engine-owned copy: the step graph holds ITS address, whatever buffer the caller passes
@@ -1941,7 +1975,7 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   // step variant: bits 1 / 2 = mt3_debug_engine_decode's skipped kernels (mt3_hip_debug.h; never set by the product
   // entry points), then kVar*
   const int variant = (debug_skip & 3) | (beam1 ? kVarBeam : 0) | (d_forced ? kVarForced : 0) | (retire ? kVarRetire : 0) |
-                      (e->eos_on && !d_forced ? kVarEos : 0);
+                      (e->eos_on && !d_forced ? kVarEos : 0) | (masked ? kVarMask : 0);
   if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   PendingDecode& p = begin_job(e);
   p.beam1 = beam1;
@@ -2049,6 +2083,7 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: the beam step needs 2 * num_beams <= vocab <= 2048");
   if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: more than 16 decoder layers");
+  MT3_TRY(masks_fit(e, "mt3_engine_decode_beams", batch, 2 * k));
   MT3_TRY(ensure_beam_state(e));
   const int slots = batch * k;
   const bool early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
@@ -2058,7 +2093,7 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
   MT3_TRY(mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s));
   MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
-  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift);
+  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0);
   PendingDecode& p = begin_job(e);
   p.beams = k;
   p.num_steps = num_steps;
@@ -2401,6 +2436,7 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   if (c.num_decoder_layers > mt3k::kRefillMaxLayers) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: at most 16 decoder layers");
   if (e->eos_on && n_segments > e->eos_cap)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: the synthetic EOS schedule is shorter than n_segments");
+  MT3_TRY(masks_fit(e, "mt3_engine_transcribe", n_segments, 2));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int L = c.max_decode_len, S = n_segments < c.max_batch ? n_segments : c.max_batch;
   const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
@@ -2420,7 +2456,7 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   MT3_TRY(mt3k::launch_iota(e->slot_seg, S, s));
   if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   e->stream_max_len = num_steps;
-  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0);
+  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | (e->tm_n ? kVarMask : 0);
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
   const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   StreamCounts n{};
@@ -2480,6 +2516,7 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
   if (e->eos_on)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the synthetic EOS schedule drives the greedy / beam-1 token kernel only");
+  MT3_TRY(masks_fit(e, "mt3_engine_transcribe_beams", n_segments, 2 * k));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(ensure_beam_state(e));
   MT3_TRY(ensure_stage(e));
@@ -2504,7 +2541,7 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
   MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
   e->cur_batch = slots;
   e->stream_max_len = num_steps;
-  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift);
+  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0);
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
   const GroupJob j{E, k, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   const BeamOut bo{k, d_all_ids, d_scores};
@@ -2782,6 +2819,70 @@ int mt3_debug_engine_set_eos_schedule(mt3_engine* e, const int32_t* h_lengths, i
   return MT3_OK;
 }
 
+int mt3_engine_set_token_masks(mt3_engine* e, const uint32_t* h_masks, int32_t n_masks, const int32_t* h_seg_mask,
+                               int32_t n_segments) {
+  const char* who = "mt3_engine_set_token_masks: ";
+  if (!e) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "null engine");
+  const bool clear = !h_masks || n_masks == 0;
+  const int vocab = e->cfg.vocab_size, words = (vocab + 31) / 32;
+  std::vector<int> allowed;
+  // ---- what is wrong with the arguments themselves, then with the engine's state; nothing below touches the device before
+  if (n_masks < 0) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_masks must not be negative");
+  if (!clear) {
+    if (!h_seg_mask && n_masks > 1)
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "several masks need a per-segment index");
+    if (h_seg_mask && n_segments < 1)
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_segments must be positive with a per-segment index");
+    if (h_seg_mask)
+      for (int i = 0; i < n_segments; ++i)
+        if (h_seg_mask[i] < -1 || h_seg_mask[i] >= n_masks)
+          return mt3::fail(MT3_ERR_INVALID, std::string(who) + "mask index outside [-1, n_masks)");
+    allowed.resize(static_cast<size_t>(n_masks));
+    for (int m = 0; m < n_masks; ++m)
+      if (const char* bad = mt3k::bad_token_mask(h_masks + static_cast<size_t>(m) * words, vocab, &allowed[m]))
+        return mt3::fail(MT3_ERR_INVALID, std::string(who) + bad);
+  }
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "engine not finalized");
+  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "a decode is in flight");
+  if (clear) {
+    e->tm_n = 0;
+    return MT3_OK;
+  }
+  // a setup call: nothing a caller enqueued earlier may still read the masks this call replaces
+  MT3_HIP_CHECK(hipDeviceSynchronize());
+  const size_t n_words = static_cast<size_t>(n_masks) * words, n_seg = h_seg_mask ? static_cast<size_t>(n_segments) : 0;
+  // the kVarMask step graphs hold the addresses of both arrays and whether the index is in use: when a larger array or the
+  // other form replaces what they captured they go (as the EOS schedule's regrow has it; the old arrays stay in the
+  // engine's allocation list until destroy)
+  bool stale = e->tm_masks && (n_seg > 0) != e->tm_seg_on;
+  if (n_words > e->tm_mask_cap) {
+    uint32_t* grown = nullptr;
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_words * 4));
+    stale = stale || e->tm_masks != nullptr;
+    e->tm_masks = grown;
+    e->tm_mask_cap = n_words;
+  }
+  if (n_seg > e->tm_seg_cap) {
+    int* grown = nullptr;
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_seg * 4));
+    stale = stale || e->tm_seg != nullptr;
+    e->tm_seg = grown;
+    e->tm_seg_cap = n_seg;
+  }
+  if (stale) {
+    drop_graph(e);
+    drop_group_graphs(e);
+  }
+  e->tm_n = 0;                    // (a failed copy leaves the engine unconstrained, not half set)
+  MT3_HIP_CHECK(hipMemcpy(e->tm_masks, h_masks, n_words * 4, hipMemcpyHostToDevice));
+  if (n_seg) MT3_HIP_CHECK(hipMemcpy(e->tm_seg, h_seg_mask, n_seg * 4, hipMemcpyHostToDevice));
+  e->tm_seg_on = n_seg > 0;
+  e->tm_seg_host.assign(h_seg_mask, h_seg_mask + n_seg);
+  e->tm_allowed = allowed;
+  e->tm_n = n_masks;
+  return MT3_OK;
+}
+
 int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_score_chunk: engine not finalized");
   if (segments < 0 || segments > e->cfg.max_batch)
@@ -2824,6 +2925,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_LAST_DECODE_COMPACTIONS: return e->compactions;
     case MT3_STATUS_LAST_DECODE_FORKS: return e->h_pinned ? e->h_pinned[kForksPinned] : 0;
     case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
+    case MT3_STATUS_TOKEN_MASKS: return e->tm_n;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

@@ -131,6 +131,31 @@ struct LogitScale {
   int n_ss;
   int dim;
 };
+// Constrained decoding (mt3_engine_set_token_masks; the rule: include/mt3_hip.h): bit sets over the vocabulary, `words` =
+// ceil(vocab / 32) uint32 each, bit i % 32 of word i / 32 set = token i allowed.  The kernel that picks the token treats
+// the logit of a disallowed token as -inf (after the LogitScale multiply and its write-back: the logits in memory stay the
+// model's own).  The mask of a slot is masks + seg_mask[seg] * words, seg = the segment index the EOS schedule uses (token
+// kernel) / the element's segment (beam kernel); a negative seg or index: unconstrained.  masks == nullptr: no mask -- the
+// launchers then run the unmasked instantiations, whose statements do not mention this struct.
+struct TokenMask {
+  const uint32_t* masks;  // [n_masks][words]
+  const int* seg_mask;    // [segments] mask index per segment, -1 = unconstrained (nullptr: mask 0 for every segment);
+                          // offset like StepRetire::eos_at / by the step's first element
+  const int* slot_seg;    // beam kernel only: [slots] the segment of an element's first slot (nullptr: element = block)
+  int words;
+};
+// the one host-side check of a mask of ceil(vocab / 32) words: nullptr and *allowed = its number of allowed tokens, or
+// what is wrong with it (EOS, id 1, must stay reachable; a pick needs two candidates; no bits past the vocabulary)
+inline const char* bad_token_mask(const uint32_t* h_mask, int vocab, int* allowed) {
+  const int words = (vocab + 31) / 32;
+  int n = 0;
+  for (int w = 0; w < words; ++w) n += __builtin_popcount(h_mask[w]);
+  *allowed = n;
+  if (vocab % 32 && (h_mask[words - 1] >> (vocab % 32))) return "bits at or past vocab are set in the last word";
+  if (!(h_mask[0] & 2u)) return "a mask must allow EOS (id 1)";
+  if (n < 2) return "a mask must allow at least 2 tokens";
+  return nullptr;
+}
 // in.y[b] = table[tok[b]] + pos[step[b]] for b < B, in every form `in` holds
 int launch_embed(const InputRow& in, const int* tok, const int* step, int B, hipStream_t s);
 // per-row state of the beam-1 search (t5x beam_search, num_decodes = 1): f = [live_logp | best finished
@@ -187,6 +212,7 @@ struct ArgmaxStepArgs {
   LogitScale ls;
   StepRetire rt;
   int B;
+  TokenMask tm;         // masks == nullptr: unconstrained (rt.slot_seg / rt.slot_row give the segment, tm.slot_seg is unused)
 };
 int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that
@@ -270,7 +296,7 @@ struct BeamKArgs {
   // mt3_engine_decode_beams the host loop's bound does that: it passes 0)
   int max_len;
 };
-int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, hipStream_t s);
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, hipStream_t s);
 // copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
 // (and e4m3 scale rows), for every slot that forked this step; the grid covers every slot x layer x head
 struct BeamReorderArgs {

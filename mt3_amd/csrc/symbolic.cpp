@@ -275,6 +275,40 @@ int mt3_codec_encode_event(const mt3_codec* c, int32_t type, int32_t value, int3
   return MT3_OK;
 }
 
+int mt3_codec_token_mask(const mt3_codec* c, int32_t vocab, const int32_t* programs, int32_t n_programs,
+                         int32_t allow_drums, uint32_t* h_mask) {
+  CodecTable t(c);
+  if (!t.ok) return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_mask: malformed codec");
+  if (!h_mask || vocab < 3 || (n_programs > 0 && !programs))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_mask: null argument or vocab < 3");
+  int pk = -1;
+  for (int k = 0; k < t.n; ++k)
+    if (t.type[k] == MT3_EV_PROGRAM) pk = k;
+  if (n_programs >= 0 && pk < 0)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_mask: the codec has no program range");
+  for (int i = 0; i < n_programs; ++i)
+    if (programs[i] < t.lo[pk] || programs[i] > t.hi[pk])
+      return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_mask: program outside the codec's range");
+  const int words = (vocab + 31) / 32;
+  for (int w = 0; w < words; ++w) h_mask[w] = 0xffffffffu;
+  if (vocab % 32) h_mask[words - 1] = (1u << (vocab % 32)) - 1u;
+  const auto forbid = [&](int k, int v) {                     // token id = 3 + event index (mt3_ids_to_tokens)
+    const int id = 3 + t.start[k] + v - t.lo[k];
+    if (id < vocab) h_mask[id >> 5] &= ~(1u << (id & 31));
+  };
+  for (int k = 0; k < t.n; ++k) {
+    if (t.type[k] == MT3_EV_DRUM && !allow_drums)
+      for (int v = t.lo[k]; v <= t.hi[k]; ++v) forbid(k, v);
+    if (k == pk && n_programs >= 0)
+      for (int v = t.lo[k]; v <= t.hi[k]; ++v) {
+        bool listed = false;
+        for (int i = 0; i < n_programs; ++i) listed = listed || programs[i] == v;
+        if (!listed) forbid(k, v);
+      }
+  }
+  return MT3_OK;
+}
+
 // the machine behind mt3_notes_decode (h_note_tokens == nullptr) and mt3_notes_decode_traced; `who` names the entry
 // point in its error messages
 static int notes_decode_impl(const std::string& who, const mt3_codec* c, int32_t spec, int32_t n_segments,

@@ -25,6 +25,7 @@ alpha 0.6, which is what the reference's predict_batch_with_aux runs (SURVEY.md 
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import json
 import os
@@ -113,6 +114,7 @@ class InferenceModel(object):
             "vocab_size": vocabularies.num_embeddings(self.vocabulary), "dtype": dtype,
             "input_depth": spectrograms.input_depth(self.spectrogram_config)})
         self._params = None
+        self._job_masks = None                   # (masks, per-segment index or None) of the constrained call in flight
         self.model = network.Transformer(self.model_config, input_length=self.inputs_length,
                                          max_decode_length=self.outputs_length, max_batch=self.batch_size)
         self.restore_from_checkpoint(checkpoint_path)
@@ -173,6 +175,67 @@ class InferenceModel(object):
                                          max_decode_length=self.outputs_length, max_batch=slots)
         self.model.load_params(self._params)
 
+    # ------------------------------------------------------------------ constrained decoding
+    def _token_masks(self, programs, drums, segments_per_file=None):
+        """The `programs=` / `drums=` keywords of the transcribing methods -> None (unconstrained) or (masks uint32
+        [n_masks, words], per-segment mask index or None).  programs: the MIDI programs the transcription may use (None:
+        any); drums=False forbids drum notes.  segments_per_file (the `_many` / `wavs` forms): either keyword may then hold
+        one entry per file -- programs=[[0], [33]], drums=[True, False] -- and every segment of a file carries its file's
+        mask index (-1 for a file without a constraint)."""
+        files = len(segments_per_file) if segments_per_file is not None else 0
+        listy = (lambda v: isinstance(v, (list, tuple, np.ndarray)))
+        per_file = segments_per_file is not None and (
+            listy(drums) or (listy(programs) and any(p is None or listy(p) for p in programs)))
+        if not per_file:
+            if listy(drums):
+                raise ValueError("drums must be one bool for a single file")
+            if programs is None and drums:
+                return None
+            return self._mask_rows([(programs, drums)]), None
+        prog = list(programs) if listy(programs) and any(p is None or listy(p) for p in programs) else [programs] * files
+        drum = list(drums) if listy(drums) else [drums] * files
+        if len(prog) != files or len(drum) != files:
+            raise ValueError("programs / drums per file: %d / %d entries for %d files" % (len(prog), len(drum), files))
+        keys, index = [], []
+        for p, d in zip(prog, drum):
+            key = (None if p is None else tuple(sorted(set(int(v) for v in p))), bool(d))
+            if key == (None, True):
+                index.append(-1)
+                continue
+            if key not in keys:
+                keys.append(key)
+            index.append(keys.index(key))
+        if not keys:
+            return None
+        seg = np.repeat(np.asarray(index, np.int32), np.asarray(segments_per_file, np.int64))
+        return self._mask_rows(keys), seg
+
+    def _mask_rows(self, constraints):
+        try:
+            self.codec.event_type_range("program")
+        except ValueError:
+            raise ValueError("programs= / drums= need a vocabulary with program tokens") from None
+        return np.stack([vocabularies.token_mask(self.codec, self.model_config.vocab_size,
+                                                 None if p is None else list(p), bool(d)) for p, d in constraints])
+
+    @contextlib.contextmanager
+    def _constrained(self, job):
+        """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`); the masks are cleared on the way out,
+        also on error"""
+        self._job_masks = job
+        try:
+            yield
+        finally:
+            self._job_masks = None
+            if job is not None and self.model is not None:
+                self.model.clear_token_masks()
+
+    def _set_masks(self, lo: int, hi: int):
+        """before an engine call on segments [lo, hi) of the job: their masks on the engine that will run it"""
+        if self._job_masks is not None:
+            masks, seg = self._job_masks
+            self.model.set_token_masks(masks, None if seg is None else seg[lo:hi])
+
     # ------------------------------------------------------------------ model call
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
         """batch['encoder_input_tokens']: f32 [B, T, 512] (numpy or CUDA tensor) -> int32 [B, 1024]
@@ -192,12 +255,14 @@ class InferenceModel(object):
             # ONE engine call for the whole job: finished rows restart on the job's next segments
             self._ensure_slots(x.shape[0])
             self.rows_per_engine_call = [int(x.shape[0])]
+            self._set_masks(0, int(x.shape[0]))
             return self.model.transcribe(x, beam1=beam1)
         out = []
         step = min(self.batch_size, self.model.max_batch)
         self.rows_per_engine_call = []
         for s in range(0, x.shape[0], step):
             self.model.encode(x[s:s + step])
+            self._set_masks(s, s + step)
             out.append(self.model.decode(early_exit=self.early_exit, beam1=beam1))
             self.rows_per_engine_call.append(int(min(step, x.shape[0] - s)))
         return torch.cat(out, 0)
@@ -212,28 +277,35 @@ class InferenceModel(object):
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: a closed element restarts on the job's next segment
             self.rows_per_engine_call = [int(x.shape[0]) * k]
+            self._set_masks(0, int(x.shape[0]))
             return self.model.transcribe(x, num_beams=k)
         chunk = max(1, min(chunk, self.model.max_batch // k))
         out = []
         self.rows_per_engine_call = []
         for s in range(0, x.shape[0], chunk):
             self.model.encode(x[s:s + chunk], num_beams=k)
+            self._set_masks(s, s + chunk)
             ids, _ = self.model.decode_beams(k, early_exit=self.early_exit)
             out.append(ids)
             self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
         return torch.cat(out, 0)
 
-    def __call__(self, audio, sample_rate: int = SAMPLE_RATE):
+    def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
-        notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`."""
-        return self._transcribe_examples(self._examples(audio, sample_rate))
+        notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`.
+        programs / drums (every transcribing method takes them): constrained decoding -- programs=[0, 33] lets the
+        decode use those MIDI programs only, drums=False forbids drum notes; the excluded tokens are impossible at the
+        token pick (Transformer.set_token_masks), so the search takes the best ALLOWED continuation."""
+        with self._constrained(self._token_masks(programs, drums)):
+            return self._transcribe_examples(self._examples(audio, sample_rate))
 
-    def transcribe_wav(self, wav_data):
+    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
-        return self._transcribe_examples(self._wav_examples(wav_data))
+        with self._constrained(self._token_masks(programs, drums)):
+            return self._transcribe_examples(self._wav_examples(wav_data))
 
     def _transcribe_examples(self, examples, scored: bool = False):
         """the examples of one file, their log-mel in _logmel_dev -> NoteSequence (scored: and the notes' scores)"""
@@ -254,7 +326,7 @@ class InferenceModel(object):
                                                               encoding_spec=self.encoding_spec)
         return result["est_ns"], self._note_scores(batch["encoder_input_tokens"], ids, result["note_tokens"])
 
-    def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE):
+    def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True):
         """`__call__` with a confidence for every note: (NoteSequence, scores).  The notes are those of `__call__` (same
         decode: the model's `decoding` and `schedule`); afterwards the decoded id rows are scored teacher-forced in one
         `Transformer.score_segments` call (ids after EOS are 0 = padding; length = the longest row) and each note is
@@ -265,14 +337,17 @@ class InferenceModel(object):
           'onset_margin'   onset_logprob minus the log-probability of the model's best token at that position: 0 when
                            the decoded token is the model's arg-max, negative otherwise
           'note_tokens'    int64 [n_notes, 2, 2]: (segment, position) of the onset and the end token, (-1, -1) for none
-        Not available with e4m3 K/V caches (ValueError, as `score`)."""
+        Not available with e4m3 K/V caches (ValueError, as `score`).  With programs / drums the DECODE is constrained; the
+        scores stay the unconstrained model's log-probabilities (scoring ignores token masks)."""
         self._refuse_e4m3("transcribe_scored")
-        return self._transcribe_examples(self._examples(audio, sample_rate), scored=True)
+        with self._constrained(self._token_masks(programs, drums)):
+            return self._transcribe_examples(self._examples(audio, sample_rate), scored=True)
 
-    def transcribe_wav_scored(self, wav_data):
+    def transcribe_wav_scored(self, wav_data, *, programs=None, drums: bool = True):
         """The file-level form of `transcribe_scored`: `transcribe_wav` plus the notes' confidences."""
         self._refuse_e4m3("transcribe_wav_scored")
-        return self._transcribe_examples(self._wav_examples(wav_data), scored=True)
+        with self._constrained(self._token_masks(programs, drums)):
+            return self._transcribe_examples(self._wav_examples(wav_data), scored=True)
 
     def _refuse_e4m3(self, who):
         if self.model_config.kv_dtype:
@@ -329,26 +404,28 @@ class InferenceModel(object):
         tok = np.concatenate(tok) if tok else np.zeros((0, n), np.float64)
         return scores, [tok[i, : len(r)] for i, r in enumerate(rows)]
 
-    def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None) -> List[Any]:
+    def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
+                        drums=True) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
         machine is sequential within a file and independent across files, mt3/metrics_utils.py:92-116).  Returns one
         NoteSequence per file, each identical to `self(audio)`.  sample_rates: one rate per file (default: all 16 kHz),
-        as for `__call__`."""
+        as for `__call__`.  programs / drums: as for `__call__`, or one entry per file (programs=[[0], [33]]): every segment
+        of a file carries its file's mask, so one job holds files with different instruments."""
         if sample_rates is None:
             sample_rates = [SAMPLE_RATE] * len(audios)
         if len(sample_rates) != len(audios):
             raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
         return self._transcribe_files([functools.partial(self._examples, audio, sr)
-                                       for audio, sr in zip(audios, sample_rates)])
+                                       for audio, sr in zip(audios, sample_rates)], programs, drums)
 
-    def transcribe_wavs(self, wavs: Sequence[Any]) -> List[Any]:
+    def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
-        `self.transcribe_wav(wav)`."""
-        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs])
+        `self.transcribe_wav(wav)`.  programs / drums: as for `transcribe_many`."""
+        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums)
 
-    def _transcribe_files(self, make_examples):
+    def _transcribe_files(self, make_examples, programs=None, drums=True):
         """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
         NoteSequence per file, all segments through the engine as one job"""
         import torch
@@ -359,7 +436,8 @@ class InferenceModel(object):
         self._logmel_dev = None
         if not per_file:
             return []
-        tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
+        with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file])):
+            tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
         out, at = [], 0
         for examples in per_file:
             preds = [self.postprocess(t, ex) for t, ex in zip(tokens[at:at + len(examples)], examples)]

@@ -342,6 +342,28 @@ class Transformer:
         a = np.ascontiguousarray(lengths, dtype=np.int32)
         _lib.check(self._lib.mt3_debug_engine_set_eos_schedule(self._h, a.ctypes.data, int(a.size)))
 
+    def set_token_masks(self, masks, seg_mask=None):
+        """mt3_engine_set_token_masks: constrain every later decode / decode_beams / transcribe call until
+        `clear_token_masks`.  masks: uint32 [n_masks, ceil(vocab / 32)] (or one row), bit i % 32 of word i // 32 set =
+        token i allowed (`vocabularies.token_mask`); seg_mask: int32 mask index per batch row / beam element / segment of
+        the job, -1 = unconstrained (None: mask 0 everywhere, n_masks must be 1).  A disallowed token's logit counts as
+        -inf in the token pick and the log-sum-exp; returned logits stay unmasked.  decode_forced / score /
+        score_segments ignore masks."""
+        m = np.ascontiguousarray(masks, dtype=np.uint32)
+        m = m.reshape(1, -1) if m.ndim == 1 else m
+        words = (self.config.vocab_size + 31) // 32
+        if m.ndim != 2 or m.shape[1] != words:
+            raise ValueError("masks must be [n_masks, %d] uint32 words for vocab %d" % (words, self.config.vocab_size))
+        if seg_mask is None:
+            _lib.check(self._lib.mt3_engine_set_token_masks(self._h, m.ctypes.data, int(m.shape[0]), None, 0))
+            return
+        sm = np.ascontiguousarray(seg_mask, dtype=np.int32).reshape(-1)
+        _lib.check(self._lib.mt3_engine_set_token_masks(self._h, m.ctypes.data, int(m.shape[0]), sm.ctypes.data,
+                                                        int(sm.size)))
+
+    def clear_token_masks(self):
+        _lib.check(self._lib.mt3_engine_set_token_masks(self._h, None, 0, None, 0))
+
     def debug_decode(self, num_steps: Optional[int] = None, skip_self_attn: bool = False,
                      skip_cross_attn: bool = False, chains: int = 0, use_graph: bool = True):
         """mt3_debug_engine_decode (include/mt3_hip_debug.h): a decode with kernels left out of every step, for

@@ -2,6 +2,7 @@
 
     python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
                                  [--decoding beam1|greedy|beam] [--num-beams K] [--confidences]
+                                 [--programs P[,P...]] [--no-drums]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -11,6 +12,8 @@ checkpoint directory, a flat or compact `.npz`, or `random:<seed>`.  --decoding 
 NAME.confidence.json beside each NAME.mid: one record per note, in the NoteSequence's order, with the note's fields and
 `onset_logprob`, `end_logprob` (null where no token ended the note) and `onset_margin` of
 `InferenceModel.transcribe_wav_scored` (each file is then a job of its own: decode, then one scoring pass).
+--programs 0,33 restricts the decode of every input to those MIDI programs and --no-drums forbids drum notes (constrained
+decoding: the excluded tokens cannot be picked; `InferenceModel(..., programs=, drums=)`).
 """
 from __future__ import annotations
 
@@ -33,6 +36,9 @@ def plan(argv=None):
     ap.add_argument("--num-beams", type=int, default=4, metavar="K", help="decodes per segment with --decoding beam (1 .. 8)")
     ap.add_argument("--confidences", action="store_true",
                     help="also write NAME.confidence.json beside each NAME.mid: per-note token log-probabilities")
+    ap.add_argument("--programs", type=_program_list, default=None, metavar="P[,P...]",
+                    help="constrained decoding: the MIDI programs (0 .. 127) the transcription may use, for all inputs")
+    ap.add_argument("--no-drums", dest="drums", action="store_false", help="constrained decoding: no drum notes")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -55,6 +61,16 @@ def plan(argv=None):
     return args, outputs
 
 
+def _program_list(text: str):
+    try:
+        programs = [int(p) for p in text.split(",") if p.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError("--programs takes comma-separated integers, got %r" % (text,)) from None
+    if not programs or any(not 0 <= p <= 127 for p in programs):
+        raise argparse.ArgumentTypeError("--programs takes MIDI programs 0 .. 127, got %r" % (text,))
+    return programs
+
+
 def main(argv=None) -> int:
     args, outputs = plan(argv)
     from . import inference, midi_io
@@ -62,10 +78,11 @@ def main(argv=None) -> int:
         model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype, decoding=args.decoding,
                                          num_beams=args.num_beams)
         if args.confidences:
-            scored = [model.transcribe_wav_scored(path) for path in args.inputs]
+            scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums)
+                      for path in args.inputs]
             sequences, scores = [ns for ns, _ in scored], [sc for _, sc in scored]
         else:
-            sequences, scores = model.transcribe_wavs(args.inputs), None
+            sequences, scores = model.transcribe_wavs(args.inputs, programs=args.programs, drums=args.drums), None
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1

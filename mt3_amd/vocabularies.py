@@ -122,6 +122,25 @@ def vocabulary_from_codec(codec: event_codec.Codec) -> GenericTokenVocabulary:
     return GenericTokenVocabulary(codec.num_classes, extra_ids=DEFAULT_EXTRA_IDS)
 
 
+def token_mask(codec: event_codec.Codec, vocab_size: int, programs=None, drums: bool = True) -> np.ndarray:
+    """The token mask of a set of instruments (`mt3_codec_token_mask`), uint32 [ceil(vocab_size / 32)]: bit i % 32 of word
+    i // 32 set = vocabulary id i allowed.  Every id below `vocab_size` is allowed except the program tokens of programs
+    not listed (programs=None: every program stays) and, with drums=False, the drum tokens.  What
+    `Transformer.set_token_masks` takes.  ValueError for a program the codec does not hold."""
+    mask = np.zeros(((int(vocab_size) + 31) // 32,), np.uint32)
+    if programs is None:
+        prog, n = None, -1
+    else:
+        prog = np.ascontiguousarray(list(programs), dtype=np.int32)
+        n = int(prog.size)
+    lib = _lib.load()
+    rc = lib.mt3_codec_token_mask(C.byref(codec.desc), int(vocab_size), prog.ctypes.data if n > 0 else None, n,
+                                  1 if drums else 0, mask.ctypes.data)
+    if rc != 0:
+        raise ValueError(lib.mt3_last_error().decode())
+    return mask
+
+
 def num_embeddings(vocabulary: GenericTokenVocabulary) -> int:
     return 128 * math.ceil(vocabulary.vocab_size / 128)
 
