@@ -790,6 +790,83 @@ int mt3_op_beam_stream_init(int32_t* d_done, int32_t* d_slot_seg, int32_t* d_for
 int mt3_op_score_token_stats(const float* d_logits, const int32_t* d_targets, const float* d_weights, int32_t rows,
                              int32_t vocab, float* d_token_scores, int32_t* d_top1_ids, float* d_top1_scores, void* stream);
 
+/* The other kernels of the scoring path (mt3_engine_score, mt3_engine_score_segments), each alone on memory the CALLER
+ * owns and has filled (tests/test_gpu_score_attention.py, test_gpu_score_embed_reduce.py, test_gpu_three_plane_ops.py).
+ * Test drivers: each fills the launch description and launches on `stream`, nothing allocated or waited for.  Every
+ * argument error returns MT3_ERR_INVALID, with the entry point's name in mt3_last_error(), before anything touches a
+ * device.  A chunk holds rows = segments * Lp rows, row = seg * Lp + t, Lp a multiple of 64; caller arrays are
+ * [batch][length] with the chunk's first segment at index seg0.
+ *
+ * mt3_op_score_attention: the prefill attention, 64 queries by 64 keys per step, out = softmax(q . K^T) V with UNSCALED
+ * logits over the visible keys; q / k / v / out are bf16 or f32 by `dtype`.
+ *   query (b, i, h)   q + (b * Lq + i) * q_stride + h * 64            out likewise with out_stride
+ *   key   (b, j, h)   k + b * kv_bstride + h * kv_hstride + j * kv_stride   (v likewise; all strides in elements)
+ *   causal != 0       n_keys == Lq; query i sees key j iff j <= i and (key_tgt == NULL or key_tgt[b * Lq + j] != 0).  The K
+ *                     and V rows of a key whose target is 0 are never loaded (they may hold anything, NaN and Inf
+ *                     included); a causal-hidden key with a non-zero target IS loaded and gets probability exactly 0,
+ *                     so it has to be finite.  A query with no visible key gets a row of zeros.
+ *   causal == 0       every query sees keys 0 .. n_keys - 1 (n_keys a multiple of 64); key_tgt must be NULL.
+ *   self-attention on qkv rows [B * Lq][3][H][64]: q_stride = kv_stride = 3 * H * 64, kv_bstride = Lq * 3 * H * 64, kv_hstride
+ *   = 64; cross-attention on a cache [2][Bc][H][T][64]: kv_stride = 64, kv_hstride = T * 64, kv_bstride = H * T * 64.
+ * MT3_ERR_INVALID: NULL view; unknown dtype; key_tgt with causal == 0; q, k or v not on 16 bytes, or q_stride, kv_stride,
+ * kv_bstride or kv_hstride no multiple of 16 bytes (8 bf16 / 4 f32 elements: the kernel loads rows in 16-byte pieces);
+ * q_stride or out_stride below H * 64, kv_stride below 64; NULL q / k / v / out; B, H or Lq <= 0; Lq no multiple of 64;
+ * causal with n_keys != Lq; otherwise n_keys <= 0 or no multiple of 64. */
+typedef struct mt3_score_attn_view {
+  const void* q;
+  int32_t q_stride, reserved0;
+  const void* k;
+  const void* v;
+  int32_t kv_stride, reserved1;
+  int64_t kv_bstride, kv_hstride;
+  const int32_t* key_tgt;
+  void* out;
+  int32_t out_stride, B, H, Lq, n_keys, causal;
+} mt3_score_attn_view;
+int mt3_op_score_attention(int32_t dtype, const mt3_score_attn_view* v, void* stream);
+/* Decoder input rows of a chunk.  Row r = seg * Lp + t, src = (seg0 + seg) * length + t:
+ *   d_tgt_pad[r] = t < length ? clamp(d_targets[src]) : 0
+ *   tok          = t >= length ? 0 : d_dec_in ? clamp(d_dec_in[src]) : t == 0 ? 0 (BOS) : clamp(d_targets[src - 1])
+ *   d_y[r][:]    = d_table[tok][:] + d_pos[t][:]      (f32, one addition per element)
+ * clamp: ids below 0 become 0, ids at or above vocab become vocab - 1.  d_table [vocab][dim], d_pos [>= Lp][dim], d_y
+ * [rows][dim] f32; d_targets / d_dec_in the caller's [batch][length] int32 (d_dec_in may be NULL: shift right); nothing
+ * outside d_y[0 .. rows) and d_tgt_pad[0 .. rows) is written.
+ * MT3_ERR_INVALID: rows < 1, Lp < 64 or no multiple of 64, rows no multiple of Lp, length outside 1 .. Lp, seg0 < 0, dim
+ * < 4 or no multiple of 4, vocab < 1, table / pos / y not on 16 bytes, NULL table / pos / targets / tgt_pad / y. */
+int mt3_op_score_embed(const float* d_table, const float* d_pos, const int32_t* d_targets, const int32_t* d_dec_in,
+                       int32_t* d_tgt_pad, float* d_y, int32_t rows, int32_t Lp, int32_t length, int32_t seg0, int32_t dim,
+                       int32_t vocab, void* stream);
+/* The reduction of a chunk: per row r = seg * Lp + t with t < length, o = (seg0 + seg) * length + t,
+ *   score = d_tgt_pad[r] == 0 ? 0 : (logits[r][tgt] - logsumexp(logits[r])) * (d_weights ? d_weights[o] : 1)
+ * goes to d_tok_pad[r] and, if given, d_token_scores[o]; then d_seq_scores[seg0 + seg] = float(sum over t < length of
+ * d_tok_pad[seg * Lp + t]), summed in double in a fixed order.  Rows with t >= length are neither read nor written.
+ * With d_top1_ids or d_top1_scores (caller [batch][length], either may be NULL) the launch is the statistics kernel of
+ * mt3_engine_score_segments (mt3_op_score_token_stats states its outputs); the token and sequence scores have the
+ * same bits either way.  d_logits [rows][vocab] f32, d_tgt_pad [rows] int32 (as mt3_op_score_embed leaves them).
+ * MT3_ERR_INVALID: rows / Lp / length / seg0 as for mt3_op_score_embed, vocab < 1 (< 2 with a top-1 output), NULL logits /
+ * tgt_pad / tok_pad / seq_scores. */
+int mt3_op_score_reduce(const float* d_logits, const int32_t* d_tgt_pad, const float* d_weights, float* d_tok_pad,
+                        float* d_token_scores, float* d_seq_scores, int32_t rows, int32_t Lp, int32_t length, int32_t seg0,
+                        int32_t vocab, int32_t* d_top1_ids, float* d_top1_scores, void* stream);
+/* d_w f32 [n] -> the three bf16 planes of mt3_op_gemm_x6's weight operand, [n] each: hi = rne_bf16(w), mid = rne_bf16(w -
+ * hi), lo = rne_bf16(w - hi - mid), both differences exact in f32 (the rule the engine applies to its weights on the
+ * host).  Nothing at or past index n is written.  MT3_ERR_INVALID: a NULL pointer, n < 1 or n > 2^39. */
+int mt3_op_planes(const float* d_w, void* d_hi, void* d_mid, void* d_lo, int64_t n, void* stream);
+/* The f32 engine's encoder-sized GEMM tile (128 x 128, six bf16 products per f32 product; MT3_OPT_ENCODER_F32_MFMA states
+ * the arithmetic): d_out = epilogue( [rms(A)] * A[M][K] @ W[N][K]^T ), A f32 (row stride K), W as the planes mt3_op_planes
+ * made of the f32 [N][K] matrix, outputs f32.  (norm, epilogue): (1, MT3_EPI_STORE), (1, MT3_EPI_GEGLU) -- d_out [M][N / 2],
+ * W rows interleaved gate / linear in 16s as for mt3_op_gemm -- (0, MT3_EPI_RESID), (0, MT3_EPI_POS) with d_aux f32
+ * [seq_len][N], (0, MT3_EPI_HEADS) with d_out [2][M / seq_len][N / 128][seq_len][64].  Any M >= 1: rows at and past M are
+ * neither stored nor, for MT3_EPI_RESID, read back.
+ * MT3_ERR_INVALID: M < 1, N < 128 or no multiple of 128, K < 64 or no multiple of 64, a NULL A / plane / out, A or W of
+ * 4 GB or more, POS without d_aux or seq_len, HEADS with seq_len < 1 or M no multiple of it, any other (norm, epilogue). */
+int mt3_op_gemm_x6(const float* d_A, const void* d_W_hi, const void* d_W_mid, const void* d_W_lo, int32_t norm,
+                   int32_t epilogue, float* d_out, int32_t M, int32_t N, int32_t K, const float* d_aux, int32_t seq_len,
+                   void* stream);
+/* mt3_op_encoder_attention in the f32 engine's default arithmetic: Q, K, V and P as three bf16 planes each.  d_qkv f32
+ * [B, T, 3, H, 64] -> d_out f32 [B, T, H*64].  MT3_ERR_INVALID: a NULL pointer, B or H < 1, T other than 256 or 512. */
+int mt3_op_encoder_attention_x6(const float* d_qkv, float* d_out, int32_t B, int32_t T, int32_t H, void* stream);
+
 /* MXFP8 dense path (dense_dtype MT3_FP8_E4M3; no counterpart in the reference, whose DenseGeneral is f32,
  * mt3/layers.py:311-360): operands are OCP e4m3fn bytes [rows][K] with one E8M0 power-of-two scale per 32 consecutive
  * K elements [rows][K/32]: scale = 2^(floor(log2 amax) - 7), so amax / scale lies in [128, 256) and nothing

@@ -102,6 +102,13 @@ class DecAttnView(C.Structure):                # mt3_dec_attn_view (mt3_op_decod
                 ("q_ss_n", C.c_int32), ("reserved", C.c_int32), ("done", _P), ("cache_row", _P)]
 
 
+class ScoreAttnView(C.Structure):              # mt3_score_attn_view (mt3_op_score_attention)
+    _fields_ = [("q", _P), ("q_stride", C.c_int32), ("reserved0", C.c_int32), ("k", _P), ("v", _P),
+                ("kv_stride", C.c_int32), ("reserved1", C.c_int32), ("kv_bstride", C.c_int64), ("kv_hstride", C.c_int64),
+                ("key_tgt", _P), ("out", _P)] + \
+               [(n, C.c_int32) for n in ("out_stride", "B", "H", "Lq", "n_keys", "causal")]
+
+
 # every symbol include/mt3_hip.h and include/mt3_hip_debug.h declare: (name, restype, argtypes)
 SIGNATURES = {
     "mt3_last_error": (C.c_char_p, []),
@@ -143,6 +150,15 @@ SIGNATURES = {
     "mt3_debug_engine_set_eos_schedule": (C.c_int, [_P, _P, C.c_int32]),
     "mt3_ids_to_tokens": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mt3_op_score_token_stats": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mt3_op_score_attention": (C.c_int, [C.c_int32, C.POINTER(ScoreAttnView), _P]),
+    "mt3_op_score_embed": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, _P]),
+    "mt3_op_score_reduce": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                      _P]),
+    "mt3_op_planes": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
+    "mt3_op_gemm_x6": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
+                                 _P]),
+    "mt3_op_encoder_attention_x6": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mt3_op_gemm": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                               C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_gemm_ex": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,

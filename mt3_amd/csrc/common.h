@@ -11,6 +11,11 @@ namespace mt3 {
 // Records the message for mt3_last_error() (thread-local) and returns `code`.
 int fail(int code, const std::string& msg);
 
+// What a launcher refused (MT3_ERR_INVALID, before its launch), reported under the name of the entry point that was called.
+inline int fail_as(const char* entry, int rc) {
+  return rc == MT3_ERR_INVALID ? fail(rc, std::string(entry) + ": " + mt3_last_error()) : rc;
+}
+
 }  // namespace mt3
 
 #define MT3_HIP_CHECK(expr)                                                                        \

@@ -229,3 +229,9 @@ int launch_encoder_attention_x6(const void* qkv, void* out, int B, int T, int H,
 }
 
 }  // namespace mt3k
+
+// include/mt3_hip.h: the kernel alone
+extern "C" int mt3_op_encoder_attention_x6(const float* d_qkv, float* d_out, int32_t B, int32_t T, int32_t H, void* stream) {
+  return mt3::fail_as("mt3_op_encoder_attention_x6",
+                      mt3k::launch_encoder_attention_x6(d_qkv, d_out, B, T, H, static_cast<hipStream_t>(stream)));
+}

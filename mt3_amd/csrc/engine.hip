@@ -47,11 +47,6 @@
 #include "common.h"
 #include "feed.h"
 #include "kernels.h"
-
-namespace mt3k {
-// enc_attention_x6.hip: the f32 engine's encoder attention with Q, K, V and P as three bf16 planes each
-int launch_encoder_attention_x6(const void* qkv, void* out, int B, int T, int H, hipStream_t s);
-}  // namespace mt3k
 #include "mx8.h"
 #include "mt3_hip.h"
 #include "mt3_hip_debug.h"

@@ -1369,6 +1369,26 @@ extern "C" int mt3_op_gemm_side(int32_t dtype, const void* d_A, const void* d_Wt
                            static_cast<hipStream_t>(stream));
 }
 
+// gemm_x6_kernel alone: the weight as the three planes mt3_op_planes makes
+extern "C" int mt3_op_gemm_x6(const float* d_A, const void* d_W_hi, const void* d_W_mid, const void* d_W_lo, int32_t norm,
+                              int32_t epilogue, float* d_out, int32_t M, int32_t N, int32_t K, const float* d_aux,
+                              int32_t seq_len, void* stream) {
+  if (N < 128) return mt3::fail(MT3_ERR_INVALID, "mt3_op_gemm_x6: N must be a positive multiple of 128");
+  mt3k::GemmArgs g{};
+  g.A = d_A;
+  g.Wt = d_W_hi;
+  g.out = d_out;
+  g.aux = d_aux;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = K;
+  g.ldo = epilogue == MT3_EPI_GEGLU ? N / 2 : N;
+  g.seq_len = seq_len;
+  return mt3::fail_as("mt3_op_gemm_x6", mt3k::launch_gemm_x6(g, d_W_mid, d_W_lo, norm != 0, epilogue,
+                                                            static_cast<hipStream_t>(stream)));
+}
+
 #if MT3_EXP & 32
 // experiment build only: copy the phase accumulators out (16 x 8 uint64) and clear them
 extern "C" int mt3_exp_gemm_phases(unsigned long long* h_out) {

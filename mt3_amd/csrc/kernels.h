@@ -53,6 +53,9 @@ int launch_gemm_x6(const GemmArgs& g, const void* Wm, const void* Wl, bool norm,
 
 // encoder self-attention, qkv [B, T, 3, H, 64] -> out [B, T, H*64]
 int launch_encoder_attention(int dtype, const void* qkv, void* out, int B, int T, int H, hipStream_t s);
+// the f32 engine's encoder attention with Q, K, V and P as three bf16 planes each (enc_attention_x6.hip): f32 qkv
+// [B * T][3 * H * 64] -> f32 out [B * T][H * 64]; T = 256 or 512
+int launch_encoder_attention_x6(const void* qkv, void* out, int B, int T, int H, hipStream_t s);
 
 struct DecAttnArgs {
   const void* q;        // [B, q_stride] compute type; head h at +h*64

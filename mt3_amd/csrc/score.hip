@@ -430,3 +430,78 @@ extern "C" int mt3_op_score_token_stats(const float* d_logits, const int32_t* d_
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
+
+// ---- include/mt3_hip.h: the other kernels of the scoring path, one at a time (test drivers: the launch description is
+// filled and launched on `stream`, nothing else)
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int mt3_op_score_attention(int32_t dtype, const mt3_score_attn_view* v, void* stream) {
+  const char* const me = "mt3_op_score_attention";
+  if (!v) return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_attention: null view");
+  if (dtype != MT3_BF16 && dtype != MT3_F32) return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_attention: unknown dtype");
+  if (v->key_tgt && !v->causal)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_attention: key_tgt is read by the causal form only");
+  // the kernel loads query, K and V rows as 16-byte pieces
+  const int per16 = dtype == MT3_BF16 ? 8 : 4;
+  if (v->q_stride % per16 || v->kv_stride % per16 || v->kv_bstride % per16 || v->kv_hstride % per16 || !aligned16(v->q) ||
+      !aligned16(v->k) || !aligned16(v->v))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_attention: q / k / v and their strides must keep every row on 16 bytes");
+  if (v->H > 0 && (v->q_stride < v->H * 64 || v->out_stride < v->H * 64 || v->kv_stride < 64))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_attention: q_stride / out_stride below H * 64 or kv_stride below 64");
+  mt3k::ScoreAttnArgs a{};
+  a.q = v->q;
+  a.q_stride = v->q_stride;
+  a.k = v->k;
+  a.v = v->v;
+  a.kv_stride = v->kv_stride;
+  a.kv_bstride = v->kv_bstride;
+  a.kv_hstride = v->kv_hstride;
+  a.key_tgt = v->key_tgt;
+  a.out = v->out;
+  a.out_stride = v->out_stride;
+  a.B = v->B;
+  a.H = v->H;
+  a.Lq = v->Lq;
+  a.n_keys = v->n_keys;
+  a.causal = v->causal;
+  return mt3::fail_as(me, mt3k::launch_score_attention(dtype, a, static_cast<hipStream_t>(stream)));
+}
+
+// rows / Lp / length of a chunk as launch_score_embed and launch_score_reduce take them (they divide by Lp)
+static const char* bad_chunk(int32_t rows, int32_t Lp, int32_t length, int32_t seg0) {
+  if (rows < 1 || Lp < 64 || seg0 < 0) return "rows must be >= 1, Lp >= 64 and seg0 >= 0";
+  if (Lp % 64 || rows % Lp || length < 1 || length > Lp) return "Lp must be a multiple of 64, rows one of Lp, length in 1 .. Lp";
+  return nullptr;
+}
+
+extern "C" int mt3_op_score_embed(const float* d_table, const float* d_pos, const int32_t* d_targets,
+                                  const int32_t* d_dec_in, int32_t* d_tgt_pad, float* d_y, int32_t rows, int32_t Lp,
+                                  int32_t length, int32_t seg0, int32_t dim, int32_t vocab, void* stream) {
+  const char* const me = "mt3_op_score_embed";
+  if (const char* why = bad_chunk(rows, Lp, length, seg0)) return mt3::fail(MT3_ERR_INVALID, std::string(me) + ": " + why);
+  if (dim < 4 || dim % 4 || vocab < 1 || !aligned16(d_table) || !aligned16(d_pos) || !aligned16(d_y))
+    return mt3::fail(MT3_ERR_INVALID, "mt3_op_score_embed: dim must be a positive multiple of 4, vocab >= 1, table / pos / "
+                                      "y on 16 bytes");
+  const mt3k::ScoreEmbedArgs a{d_table, d_pos, d_targets, d_dec_in, d_tgt_pad, d_y, rows, Lp, length, seg0, dim, vocab};
+  return mt3::fail_as(me, mt3k::launch_score_embed(a, static_cast<hipStream_t>(stream)));
+}
+
+extern "C" int mt3_op_score_reduce(const float* d_logits, const int32_t* d_tgt_pad, const float* d_weights,
+                                   float* d_tok_pad, float* d_token_scores, float* d_seq_scores, int32_t rows, int32_t Lp,
+                                   int32_t length, int32_t seg0, int32_t vocab, int32_t* d_top1_ids, float* d_top1_scores,
+                                   void* stream) {
+  const char* const me = "mt3_op_score_reduce";
+  if (const char* why = bad_chunk(rows, Lp, length, seg0)) return mt3::fail(MT3_ERR_INVALID, std::string(me) + ": " + why);
+  const mt3k::ScoreReduceArgs a{d_logits, d_tgt_pad, d_weights, d_tok_pad, d_token_scores, d_seq_scores,
+                                rows, Lp, length, seg0, vocab};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d_top1_ids || d_top1_scores)
+    return mt3::fail_as(me, mt3k::launch_score_stats(mt3k::ScoreStatsArgs{a, d_top1_ids, d_top1_scores}, s));
+  return mt3::fail_as(me, mt3k::launch_score_reduce(a, s));
+}
+
+extern "C" int mt3_op_planes(const float* d_w, void* d_hi, void* d_mid, void* d_lo, int64_t n, void* stream) {
+  if (n < 1 || n > (int64_t{1} << 39)) return mt3::fail(MT3_ERR_INVALID, "mt3_op_planes: n must be in 1 .. 2^39");
+  return mt3::fail_as("mt3_op_planes", mt3k::launch_planes(d_w, d_hi, d_mid, d_lo, static_cast<size_t>(n),
+                                                          static_cast<hipStream_t>(stream)));
+}
