@@ -432,6 +432,48 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
 int mt3_engine_set_token_masks(mt3_engine* e, const uint32_t* h_masks /* [n_masks][words] */, int32_t n_masks,
                                const int32_t* h_seg_mask /* [n_segments] or NULL */, int32_t n_segments);
 
+/* Prompted decoding: per-segment forced token prefixes -- the `inputs=prompt` of t5x's decode function,
+ * which MT3 always passes as zeros.  For MT3 the prefix is the tie section that opens a segment
+ * (vocabularies.tie_section_prompt).  [from memory: t5x is not at hand, as for the beam search and the masks above]
+ *   prompt   a row P[0 .. p-1] of vocabulary ids, 1 <= p <= stride, every id in [2, vocab); id 0 is padding and ends the
+ *            prompt, EOS (id 1) cannot be forced.  Step t of a segment is the step at its position counter t; its input is
+ *            BOS at t = 0 and otherwise the token emitted at t - 1.  The prompt is ingested as t5x does it: the decode loop
+ *            steps through it and the token kernel forces the pick -- caches, position counters and every attention launch
+ *            stay what they are, and the ids are those of mt3_engine_decode_forced on the same tokens, bit for bit.
+ *   greedy   for t < p, ids[t] = P[t] and the next input row is Embed(P[t]) + pos[t + 1]; the row never finishes inside
+ *            its prompt.  From t = p the pick is the unprompted one.
+ *   beam-1   (MT3_DECODE_BEAM1) for t < p the live hypothesis takes P[t]; its live log-prob is unchanged (prompt tokens are
+ *            not scored); no EOS candidate is made, so the finished score and length are untouched; the stop test is not
+ *            evaluated.  From t = p the rule is the unprompted one: an EOS candidate at step t scores logp / bp(t + 1), t + 1
+ *            the absolute length with the prompt included, logp the sum over the free tokens only.
+ *   k-beam   for t < p all k slots of the element take P[t]; the k live log-probs stay [0, NEG_INF, ...], so step p expands
+ *            beam 0 only, exactly as step 0 does without a prompt; no candidate enters the finished set, nothing forks, the
+ *            slot -> row map is unchanged (the k cache rows hold the same K/V for positions < p) and the retirement test is
+ *            skipped.  From t = p the rule is the unprompted one with the same absolute-length brevity penalty; at k = 1 the
+ *            ids are bit-identical to beam-1.
+ *   logits   d_first_logits, the per-step logits and the rows scaled in place stay the model's own.
+ *   masks    a prompt token is emitted even where the segment's token mask forbids it; masks apply from t = p.  Inside the
+ *            prompt the prompt also wins over the synthetic EOS schedule.
+ *   bounds   max_len and num_steps mean what they meant; a decode / transcribe call whose num_steps is <= the longest
+ *            prompt in use returns MT3_ERR_INVALID before any device work.
+ *   segments h_seg_prompt [n_segments]: the prompt index of segment i, -1 = none; NULL: prompt 0 for every segment
+ *            (n_prompts must be 1).  "Segment i" is what it is for the masks: batch row i in mt3_engine_decode, element i in
+ *            mt3_engine_decode_beams, segment i of the job in mt3_engine_transcribe / _transcribe_beams -- the prompt follows
+ *            the segment through compaction and refills (a refilled slot restarts at position 0 on its new segment's prompt).
+ * h_prompts [n_prompts][stride] (0-padded) and h_seg_prompt are HOST arrays, copied into engine-owned device memory by
+ * this call (synchronous, a setup call); h_prompts == NULL or n_prompts == 0 clears.  The prompts stay set for every later
+ * mt3_engine_decode / _decode_beams / _transcribe / _transcribe_beams until cleared; prompted and unprompted steps never
+ * share a captured graph, and an unprompted decode runs the kernels, graphs and bits it ran before prompts existed.
+ * mt3_engine_decode_forced, mt3_engine_score and mt3_engine_score_segments IGNORE prompts, as they ignore masks.
+ * MT3_STATUS_PROMPTS reports the number of prompts set.
+ * MT3_ERR_INVALID, before any device work: n_prompts < 0; stride < 1; stride >= max_decode_len; NULL h_seg_prompt with
+ * n_prompts > 1; n_segments < 1 with h_seg_prompt; an index outside [-1, n_prompts); an id outside {0} and [2, vocab); a
+ * non-zero id after a 0; an empty prompt (a first id of 0); an engine that is not finalized; a decode in flight.
+ * The decode / transcribe calls return MT3_ERR_INVALID before any device work for more rows / elements / segments than
+ * n_segments when a per-segment index is set. */
+int mt3_engine_set_prompts(mt3_engine* e, const int32_t* h_prompts /* [n_prompts][stride], 0-padded */, int32_t n_prompts,
+                           int32_t stride, const int32_t* h_seg_prompt /* [n_segments] or NULL */, int32_t n_segments);
+
 /* Teacher-forced cached decode: Transformer.decode (mt3/network.py:303-361) on GIVEN decoder inputs, driven one
  * token per call through the same cached step (layers.py:246-314) the autoregressive loop uses -- the input of
  * step 0 is BOS, the input of step t+1 is d_forced_ids[b][t] (i.e. decoder_input_tokens = shift_right(forced),
@@ -530,7 +572,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_LAST_DECODE_COMPACTIONS = 9 /* live-row compactions of the most recent decode (all row groups) */,
        MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams / mt3_engine_transcribe_beams */,
        MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score / mt3_engine_score_segments (all its encoder chunks) */,
-       MT3_STATUS_TOKEN_MASKS = 12 /* masks set by mt3_engine_set_token_masks (0: none) */ };
+       MT3_STATUS_TOKEN_MASKS = 12 /* masks set by mt3_engine_set_token_masks (0: none) */,
+       MT3_STATUS_PROMPTS = 13 /* prompts set by mt3_engine_set_prompts (0: none) */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -675,6 +718,21 @@ int mt3_op_beam_search_masked(const float* d_logits, const float* d_ss, int32_t 
 int mt3_op_token_steps_masked(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
                               int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
                               void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask);
+/* The two masked drivers with prompts (mt3_engine_set_prompts states the rule): d_prompts [.][stride] int32, 0-padded, and
+ * d_row_prompt, the prompt index (-1: none) per ROW for the token kernel and per ELEMENT for the beam kernel (NULL: prompt
+ * 0), both DEVICE arrays; the prompts are rows 0 .. the largest index.  They are read back and checked first:
+ * MT3_ERR_INVALID for a stride outside 1 .. 4096, an index outside [-1, 4096) or a prompt mt3_engine_set_prompts would
+ * refuse.  d_masks == NULL: no masks (n_masks and d_row_mask are then ignored); d_prompts == NULL: no prompts. */
+int mt3_op_beam_search_prompted(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                                int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                                const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
+                                float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks, int32_t* h_steps_run,
+                                void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                                const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt);
+int mt3_op_token_steps_prompted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
+                                int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
+                                void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                                const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt);
 /* The fork copies of one k-beam step on caller-owned caches: for every slot with d_fork_src[slot] >= 0 and
  * d_done[slot] == 0, positions [0, d_step[slot]) of row d_fork_src[slot] are copied into row d_slot_row[slot] of every
  * layer's K and V cache [rows][H][cap][64] of kv_esize-byte elements (1, 2 or 4) and, where given, of its scale pairs

@@ -25,7 +25,8 @@ OPT_SPIN_WAITS = 64
 DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
- STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS, STATUS_TOKEN_MASKS) = range(13)
+ STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS, STATUS_TOKEN_MASKS,
+ STATUS_PROMPTS) = range(14)
 (MT3_PCM_U8, MT3_PCM_S16, MT3_PCM_S24, MT3_PCM_S32, MT3_PCM_F32, MT3_PCM_F64) = range(6)     # mt3_pcm_decode formats
 PCM_MAX_CHANNELS = 7
 MAX_BEAMS = 8                                  # mt3_engine_decode_beams: 1 <= num_beams <= 8
@@ -141,6 +142,7 @@ SIGNATURES = {
     "mt3_engine_score": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_score_segments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_set_token_masks": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    "mt3_engine_set_prompts": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "mt3_engine_status": (C.c_int, [_P, C.c_int32]),
     "mt3_debug_engine_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mt3_debug_engine_transcribe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
@@ -183,6 +185,12 @@ SIGNATURES = {
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.c_int32, _P]),
     "mt3_op_token_steps_masked": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
+    "mt3_op_beam_search_prompted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
+                                              _P, C.c_int32, _P]),
+    "mt3_op_token_steps_prompted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
     "mt3_op_beam_reorder": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P),
                                       C.POINTER(_P), _P, _P, _P, _P, _P]),
     "mt3_op_embed_rows": (C.c_int, [C.POINTER(InputRowView), _P, _P, C.c_int32, _P]),

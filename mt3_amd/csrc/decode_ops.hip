@@ -14,7 +14,8 @@
 //                       beam, the k * 2k candidates merged in LDS, the slot -> cache-row map rewritten; with
 //                       beam_reorder_kernel (K/V copies of forked rows) and beam_finalize_kernel (history backtrack).
 //                       Both token kernels have a MASKED instantiation (constrained decoding, TokenMask in kernels.h):
-//                       the logit of a token the slot's mask disallows counts as -inf.
+//                       the logit of a token the slot's mask disallows counts as -inf.  Both have a PROMPT instantiation
+//                       (prompted decoding, TokenPrompt in kernels.h): a slot inside its prompt emits the prompt's token.
 //   ids_to_tokens_kernel GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271), bit-exact.
 #include <hip/hip_runtime.h>
 
@@ -201,6 +202,14 @@ __device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mr
   return row[i];
 }
 
+// Prompted decoding (TokenPrompt, kernels.h): the prompt token of segment `seg` at position t, 0 = the slot is past its
+// prompt or has none; never indexes with a negative segment, prompt index or a position at or past the stride
+__device__ __forceinline__ int prompt_token(const TokenPrompt& tp, int seg, int t) {
+  if (seg < 0 || t >= tp.stride) return 0;
+  const int p = tp.seg_prompt ? tp.seg_prompt[seg] : 0;
+  return p < 0 ? 0 : tp.prompts[static_cast<size_t>(p) * tp.stride + t];
+}
+
 // BEAM1 = false: greedy pick (the product default).
 // BEAM1 = true : one step of t5x `beam_search` with num_decodes = 1: the two best
 //   candidates of log_softmax are taken; the LIVE hypothesis follows the best non-EOS one; an EOS candidate
@@ -213,7 +222,12 @@ __device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mr
 // MASKED = true : a.tm restricts the pick of every slot to its segment's allowed tokens (exactly 0 in the exp-sum, never a
 //   candidate); the logits in memory, scaled or not, stay the model's own.  MASKED = false compiles from the statements
 //   the kernel had before masks existed.
-template <bool BEAM1, bool MASKED>
+// PROMPT = true : a slot at a position inside its segment's prompt (a.tp) emits the prompt's token P[t] whatever the
+//   logits say -- the synthetic EOS schedule and the mask included -- and its next input row is written from P[t]; the
+//   beam-1 state (live log-prob, finished score and length) is left alone and the stop test is not evaluated, so the slot
+//   never finishes there but by max_len.  The branch is block-uniform.  PROMPT = false compiles from the statements the
+//   kernel had before prompts existed.
+template <bool BEAM1, bool MASKED, bool PROMPT>
 __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   const SlotState& st = a.st;
   const StepRetire& rt = a.rt;
@@ -257,6 +271,10 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
       }
     }
   }
+  // PROMPT: the slot's prompt token at its own position, one dword per block requested in the same batch (0: not inside a
+  // prompt); only thread 0 reads it
+  int ptok = 0;
+  if (PROMPT) ptok = prompt_token(a.tp, rt.slot_seg ? rt.slot_seg[b] : out_row, st.step[b]);
   // thread 0 issues its state loads up front so that their latency hides behind the reductions
   int was_done = 0, t = 0, blen = -1, eos_len = 0x7fffffff;
   float live = 0.f, best = 0.f, bp_max = 1.f, bp_t = 1.f;
@@ -351,7 +369,11 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
     }
     int tok;
     bool finished = false;                // this step finishes the slot
-    if (!BEAM1) {
+    if (PROMPT && ptok != 0) {
+      // inside the prompt: the token is given, nothing is scored, no EOS candidate is made and the stop test is skipped
+      tok = was_done ? 0 : ptok;
+      if (BEAM1 && !was_done) a.beam.len_row[out_row] = blen;
+    } else if (!BEAM1) {
       if (a.forced) was_done = 0;           // teacher forcing: every step reports its own arg-max, no EOS bookkeeping
       tok = was_done ? 0 : (t + 1 >= eos_len ? 1 : t2.i1);      // synthetic EOS schedule: a point mass on EOS
       finished = !was_done && tok == 1 && !a.forced;   // EOS
@@ -417,9 +439,16 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
   if (const int rc = bad_input_row(a.in, "argmax_step")) return rc;
   if (a.tm.masks && (a.forced || a.tm.words != (a.vocab + 31) / 32))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: token masks are ceil(vocab / 32) words and not for teacher forcing");
+  if (a.tp.prompts && (a.forced || a.tp.stride < 1))
+    return mt3::fail(MT3_ERR_INVALID, "argmax_step: prompts have a stride of at least 1 and are not for teacher forcing");
   void (*kernel)(ArgmaxStepArgs);
-  if (a.tm.masks) kernel = a.beam.f ? argmax_step_kernel<true, true> : argmax_step_kernel<false, true>;
-  else kernel = a.beam.f ? argmax_step_kernel<true, false> : argmax_step_kernel<false, false>;
+  if (a.tp.prompts) {
+    if (a.tm.masks) kernel = a.beam.f ? argmax_step_kernel<true, true, true> : argmax_step_kernel<false, true, true>;
+    else kernel = a.beam.f ? argmax_step_kernel<true, false, true> : argmax_step_kernel<false, false, true>;
+  } else {
+    if (a.tm.masks) kernel = a.beam.f ? argmax_step_kernel<true, true, false> : argmax_step_kernel<false, true, false>;
+    else kernel = a.beam.f ? argmax_step_kernel<true, false, false> : argmax_step_kernel<false, false, false>;
+  }
   hipLaunchKernelGGL(kernel, dim3(a.B), dim3(256), 0, s, a);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
@@ -653,8 +682,13 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
 //   4. each wave writes its slot's next input row, as the greedy / beam-1 kernel does.
 // MASKED = true: the logits of the tokens the element's mask (tm) disallows are -inf in steps 1 and 2 -- 0 in the
 // log-sum-exp, never among the 2k; a mask in use allows at least 2k tokens (checked on the host).
-template <bool MASKED>
-__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls, TokenMask tm) {
+// PROMPT = true: an element at a position inside its segment's prompt (tp) takes P[t] in all k slots: the k live
+// log-probs, the finished set and the slot -> row map stay as they are (no candidate, no fork: fork_src = -1, every
+// beam its own parent in the history), the retirement test is skipped, and each wave writes its slot's next input row
+// from P[t].  The branch is element-uniform.  live stays [0, NEG_INF, ...], so the first free step expands beam 0 only,
+// as step 0 does without a prompt, and the k cache rows hold the same K/V for the prompt's positions.
+template <bool MASKED, bool PROMPT>
+__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls, TokenMask tm, TokenPrompt tp) {
   constexpr int kPerLane = 32;                         // vocab <= 2048: lane l holds i = l + 64 * vt + 256 * u
   __shared__ float c_score[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int c_tok[2 * kBeamMaxK * kBeamMaxK];
@@ -679,6 +713,28 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
     for (int j = 0; j < kPerLane; ++j) {
       const int i = lane + 64 * (j >> 3) + 256 * (j & 7);
       mw[j] = mrow ? mrow[(i < a.vocab ? i : a.vocab - 1) >> 5] : 0xffffffffu;
+    }
+  }
+  if (PROMPT) {
+    // the element's prompt token at its own position, requested in the same batch as the logits (0: not inside a prompt)
+    const int ptok = prompt_token(tp, tp.slot_seg ? tp.slot_seg[s0] : static_cast<int>(blockIdx.x), t);
+    if (ptok != 0) {
+      __syncthreads();             // every wave has read the element's done flag and position before thread 0 rewrites them
+      if (threadIdx.x == 0) {
+        // in-flight batching: an element that has run max_len steps is closed (the row ran out of positions)
+        const bool closed = a.max_len > 0 && t + 1 >= a.max_len;
+        for (int j = 0; j < k; ++j) {
+          a.fork_src[s0 + j] = -1;
+          a.hist_par[static_cast<size_t>(t) * a.hist_stride + s0 + j] = j;
+          a.hist_tok[static_cast<size_t>(t) * a.hist_stride + s0 + j] = ptok;
+          a.st.cur_tok[s0 + j] = ptok;
+          a.st.step[s0 + j] = t + 1;
+          if (closed) a.st.done[s0 + j] = 1;
+        }
+        if (closed) atomicAdd(a.st.n_done, k);
+      }
+      if (a.in.y) put_input_row(a.in, slot, ptok, t + 1, lane, 64);
+      return;
     }
   }
   const float live = a.live[slot];
@@ -886,7 +942,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
   if (a.in.y) put_input_row(a.in, slot, s_tok[w], t + 1, lane, 64);
 }
 
-int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, hipStream_t s) {
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp, hipStream_t s) {
   if (a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || a.vocab < 2 * a.k || a.vocab > 2048)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: k must be 1 .. 8 and 2k <= vocab <= 2048");
   if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.st.slot_row ||
@@ -898,8 +954,11 @@ int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& 
   if (const int rc = bad_input_row(a.in, "beam_step")) return rc;
   if (tm.masks && tm.words != (a.vocab + 31) / 32)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: token masks are ceil(vocab / 32) words");
-  hipLaunchKernelGGL(tm.masks ? beam_step_kernel<true> : beam_step_kernel<false>, dim3(a.elems), dim3(64 * a.k), 0, s, a,
-                     ls, tm);
+  if (tp.prompts && tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "beam_step: prompts have a stride of at least 1");
+  void (*kernel)(BeamKArgs, LogitScale, TokenMask, TokenPrompt);
+  if (tp.prompts) kernel = tm.masks ? beam_step_kernel<true, true> : beam_step_kernel<false, true>;
+  else kernel = tm.masks ? beam_step_kernel<true, false> : beam_step_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls, tm, tp);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -1265,16 +1324,43 @@ int driver_masks(const std::string& who, const uint32_t* d_masks, int n_masks, c
   return MT3_OK;
 }
 
+// the prompts of a prompted driver, read back and checked on the host before a kernel indexes with them: every entry of
+// d_row_prompt [n] at least -1 (the prompts it names are rows 0 .. its largest entry; nullptr: prompt 0 for every row),
+// every prompt valid (bad_prompt)
+int driver_prompts(const std::string& who, const int32_t* d_prompts, int stride, const int32_t* d_row_prompt, int n,
+                   int vocab, mt3k::TokenPrompt* tp) {
+  if (stride < 1 || stride > 4096) return mt3::fail(MT3_ERR_INVALID, who + ": the prompt stride must be 1 .. 4096");
+  int n_prompts = 1;
+  if (d_row_prompt) {
+    std::vector<int32_t> r(static_cast<size_t>(n));
+    MT3_HIP_CHECK(hipMemcpy(r.data(), d_row_prompt, r.size() * 4, hipMemcpyDeviceToHost));
+    n_prompts = 0;
+    for (int32_t v : r) {
+      if (v < -1 || v >= 4096) return mt3::fail(MT3_ERR_INVALID, who + ": prompt index outside [-1, 4096)");
+      if (v + 1 > n_prompts) n_prompts = v + 1;
+    }
+  }
+  std::vector<int32_t> h(static_cast<size_t>(n_prompts) * stride);
+  if (!h.empty()) MT3_HIP_CHECK(hipMemcpy(h.data(), d_prompts, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int p = 0; p < n_prompts; ++p) {
+    int len = 0;
+    if (const char* bad = mt3k::bad_prompt(h.data() + static_cast<size_t>(p) * stride, stride, vocab, &len))
+      return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  }
+  *tp = mt3k::TokenPrompt{d_prompts, d_row_prompt, nullptr, stride};
+  return MT3_OK;
+}
 
 }  // namespace
 
-// shared body of mt3_op_beam_search_scripted (masked == false) and mt3_op_beam_search_masked
+// shared body of mt3_op_beam_search_scripted (masked == false), mt3_op_beam_search_masked and mt3_op_beam_search_prompted
 static int beam_search_driver(const std::string& who, bool masked, const float* d_logits, const float* d_ss, int32_t n_ss,
                               int32_t dim, int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
                               const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids,
                               float* d_scores, float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks,
                               int32_t* h_steps_run, void* stream, const uint32_t* d_masks, int32_t n_masks,
-                              const int32_t* d_row_mask) {
+                              const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
+                              const int32_t* d_row_prompt = nullptr) {
   if (!d_logits || !d_ids || !d_all_ids || !d_scores || !h_trace || !h_live || !h_forks || !h_steps_run)
     return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if (k < 1 || k > mt3k::kBeamMaxK || vocab < 2 * k || vocab > 2048)
@@ -1286,6 +1372,8 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
     return mt3::fail(MT3_ERR_INVALID, who + ": the tables and the next-row output come together, dim_e % 16 == 0");
   mt3k::TokenMask tm{};
   if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, elems, vocab, 2 * k, &tm));
+  mt3k::TokenPrompt tp{};
+  if (d_prompts) MT3_OP_TRY(driver_prompts(who, d_prompts, stride, d_row_prompt, elems, vocab, &tp));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int slots = elems * k;
   const size_t n = static_cast<size_t>(slots), hist = static_cast<size_t>(num_steps) * n;
@@ -1327,7 +1415,7 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   for (int t = 0; t < num_steps; ++t) {
     b.logits = const_cast<float*>(d_logits) + static_cast<size_t>(t) * n * vocab;
     const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, s));
+    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, tp, s));
     int32_t* tr = h_trace + static_cast<size_t>(t) * 4 * n;
     MT3_HIP_CHECK(hipMemcpyAsync(tr, b.st.slot_row, n * 4, hipMemcpyDeviceToHost, s));
     MT3_HIP_CHECK(hipMemcpyAsync(tr + n, b.fork_src, n * 4, hipMemcpyDeviceToHost, s));
@@ -1370,11 +1458,24 @@ extern "C" int mt3_op_beam_search_masked(const float* d_logits, const float* d_s
                             h_steps_run, stream, d_masks, n_masks, d_row_mask);
 }
 
-// shared body of mt3_op_token_steps_scripted (masked == false) and mt3_op_token_steps_masked
+extern "C" int mt3_op_beam_search_prompted(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim,
+                                           int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
+                                           const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids,
+                                           int32_t* d_all_ids, float* d_scores, float* d_y_next, int32_t* h_trace,
+                                           float* h_live, int32_t* h_forks, int32_t* h_steps_run, void* stream,
+                                           const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                                           const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt) {
+  return beam_search_driver("mt3_op_beam_search_prompted", d_masks != nullptr, d_logits, d_ss, n_ss, dim, elems, k, vocab,
+                            num_steps, max_len, d_table, d_pos, dim_e, d_ids, d_all_ids, d_scores, d_y_next, h_trace, h_live,
+                            h_forks, h_steps_run, stream, d_masks, n_masks, d_row_mask, d_prompts, stride, d_row_prompt);
+}
+
+// shared body of mt3_op_token_steps_scripted (masked == false), mt3_op_token_steps_masked and mt3_op_token_steps_prompted
 static int token_steps_driver(const std::string& who, bool masked, float* d_logits, const float* d_ss, int32_t n_ss,
                               int32_t dim, int32_t rows, int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
                               int32_t* d_ids, int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
-                              const int32_t* d_row_mask) {
+                              const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
+                              const int32_t* d_row_prompt = nullptr) {
   if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
       max_len < 0 || bad_scale(d_ss, n_ss, dim))
@@ -1382,6 +1483,8 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
                                             "the row scale out of range");
   mt3k::TokenMask tm{};
   if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, rows, vocab, 2, &tm));
+  mt3k::TokenPrompt tp{};
+  if (d_prompts) MT3_OP_TRY(driver_prompts(who, d_prompts, stride, d_row_prompt, rows, vocab, &tp));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n = static_cast<size_t>(rows);
   Scratch m;
@@ -1406,6 +1509,7 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
   a.rt = mt3k::StepRetire{max_len > 0 ? 1 : 0, nullptr, nullptr, nullptr, max_len};
   a.B = rows;
   a.tm = tm;
+  a.tp = tp;
   MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, n * num_steps * 4, s));
   MT3_HIP_CHECK(hipMemsetAsync(len, 0xFF, n * 4, s));                       // -1: nothing finished
   MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
@@ -1434,6 +1538,16 @@ extern "C" int mt3_op_token_steps_masked(float* d_logits, const float* d_ss, int
                                          const int32_t* d_row_mask) {
   return token_steps_driver("mt3_op_token_steps_masked", true, d_logits, d_ss, n_ss, dim, rows, vocab, num_steps, mode,
                             max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask);
+}
+
+extern "C" int mt3_op_token_steps_prompted(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                           int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                           int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                                           const int32_t* d_row_mask, const int32_t* d_prompts, int32_t stride,
+                                           const int32_t* d_row_prompt) {
+  return token_steps_driver("mt3_op_token_steps_prompted", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
+                            num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
+                            d_row_prompt);
 }
 
 extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots,

@@ -114,15 +114,17 @@ struct LayerDev {
 // 64 = in-flight batching (mt3_engine_transcribe: finished slots restart on new segments, the slot -> segment map is in use)
 // 128 = token masks (mt3_engine_set_token_masks): the step ends with the MASKED token / beam kernel, so masked and unmasked
 // steps never share a captured graph
+// 256 = prompts (mt3_engine_set_prompts): the step ends with the PROMPT token / beam kernel, so prompted and unprompted steps
+// never share a captured graph
 constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kVarMask = 128,
-              kNumVariants = 256;
+              kVarPrompt = 256, kNumVariants = 512;
 // not a step variant of its own (never an index into graph_exec): set in GroupRun::variant when the decode runs as SEVERAL
 // row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
 // keeps such steps apart from a lone stream's steps of the same shape
-constexpr int kVarBeside = 256;
+constexpr int kVarBeside = 512;
 // not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
 // number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
-constexpr int kVarBeams = 512, kVarBeamsShift = 10;
+constexpr int kVarBeams = 1024, kVarBeamsShift = 11;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
 // to kStageChunkCap segments each (one encoder pass per chunk)
@@ -265,6 +267,15 @@ struct mt3_engine {
   bool tm_seg_on = false;        // a per-segment index is set (false: mask 0 for every segment); baked into the step graphs
   std::vector<int> tm_allowed;   // host: allowed tokens of each mask
   std::vector<int> tm_seg_host;  // host copy of the per-segment index
+  // Prompted decoding (mt3_engine_set_prompts): engine-owned copies, whose addresses the kVarPrompt step graphs hold
+  int* tp_prompts = nullptr;     // [tp_prompt_cap] ids: tp_n prompts of tp_stride ids, 0-padded
+  int* tp_seg = nullptr;         // [tp_seg_cap] prompt index per row / element / segment
+  size_t tp_prompt_cap = 0, tp_seg_cap = 0;
+  int tp_n = 0;                  // prompts set (0: none)
+  int tp_stride = 0;             // baked into the step graphs, as is tp_seg_on
+  bool tp_seg_on = false;        // a per-segment index is set (false: prompt 0 for every segment)
+  std::vector<int> tp_len;       // host: length of each prompt
+  std::vector<int> tp_seg_host;  // host copy of the per-segment index
   // In-flight batching (mt3_engine_transcribe): slot_seg maps a slot to the SEGMENT it is decoding (-1: none); a
   // finished slot hands its id row to the caller's output and restarts on the next encoded segment (launch_refill)
   int* slot_seg = nullptr;       // [max_batch]
@@ -862,7 +873,13 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
       const int* seg = !e->tm_seg_on ? nullptr : (streaming ? e->tm_seg : e->tm_seg + row0 / b.k);
       tm = mt3k::TokenMask{e->tm_masks, seg, streaming ? e->slot_seg + row0 : nullptr, (c.vocab_size + 31) / 32};
     }
-    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, s));
+    mt3k::TokenPrompt tp{};
+    if (skip & kVarPrompt) {   // indexed as the masks are
+      const bool streaming = (skip & kVarStream) != 0;
+      const int* seg = !e->tp_seg_on ? nullptr : (streaming ? e->tp_seg : e->tp_seg + row0 / b.k);
+      tp = mt3k::TokenPrompt{e->tp_prompts, seg, streaming ? e->slot_seg + row0 : nullptr, e->tp_stride};
+    }
+    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, tp, s));
     mt3k::BeamReorderArgs r{};
     r.n_layers = nl;
     r.H = H;
@@ -899,6 +916,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     a.B = rows;
     if (skip & kVarMask)       // indexed as eos_at is: by segment, or by the row the slot decodes
       a.tm = mt3k::TokenMask{e->tm_masks, e->tm_seg_on ? e->tm_seg + crow0 : nullptr, nullptr, (c.vocab_size + 31) / 32};
+    if (skip & kVarPrompt)     // indexed as the masks are
+      a.tp = mt3k::TokenPrompt{e->tp_prompts, e->tp_seg_on ? e->tp_seg + crow0 : nullptr, nullptr, e->tp_stride};
     return mt3k::launch_argmax_step(a, s);
   }
   LayerDev& L = e->dec[op >> 3];
@@ -1936,6 +1955,20 @@ static int masks_fit(const mt3_engine* e, const char* who, int n, int need) {
   return MT3_OK;
 }
 
+// MT3_OK, or why a job of `n` rows / elements / segments of `num_steps` steps cannot run under the prompts set: a segment
+// must have at least one free step after its prompt
+static int prompts_fit(const mt3_engine* e, const char* who, int n, int num_steps) {
+  if (!e->tp_n) return MT3_OK;
+  if (e->tp_seg_on && n > static_cast<int>(e->tp_seg_host.size()))
+    return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": more rows or segments than the prompts' n_segments");
+  for (int i = 0; i < (e->tp_seg_on ? n : 1); ++i) {
+    const int p = e->tp_seg_on ? e->tp_seg_host[i] : 0;
+    if (p >= 0 && num_steps <= e->tp_len[p])
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": num_steps must exceed the longest prompt in use");
+  }
+  return MT3_OK;
+}
+
 static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t debug_skip,
                        const int32_t* d_forced, float* d_step_logits, int32_t* d_ids, float* d_first_logits,
                        int32_t* h_steps_run, void* stream) {
@@ -1956,6 +1989,8 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_forced: not combinable with BEAM1 / EARLY_EXIT / ASYNC");
   const bool masked = e->tm_n > 0 && !d_forced;          // teacher forcing ignores token masks
   if (masked) MT3_TRY(masks_fit(e, "mt3_engine_decode", batch, 2));
+  const bool prompted = e->tp_n > 0 && !d_forced;        // ... and prompts
+  if (prompted) MT3_TRY(prompts_fit(e, "mt3_engine_decode", batch, num_steps));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(reset_slots(e, batch, true, true, s));
   if (d_forced)    // engine-owned copy: the step graph holds ITS address, whatever buffer the caller passes
@@ -1970,7 +2005,7 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   // step variant: bits 1 / 2 = mt3_debug_engine_decode's skipped kernels (mt3_hip_debug.h; never set by the product
   // entry points), then kVar*
   const int variant = (debug_skip & 3) | (beam1 ? kVarBeam : 0) | (d_forced ? kVarForced : 0) | (retire ? kVarRetire : 0) |
-                      (e->eos_on && !d_forced ? kVarEos : 0) | (masked ? kVarMask : 0);
+                      (e->eos_on && !d_forced ? kVarEos : 0) | (masked ? kVarMask : 0) | (prompted ? kVarPrompt : 0);
   if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   PendingDecode& p = begin_job(e);
   p.beam1 = beam1;
@@ -2079,6 +2114,7 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: more than 16 decoder layers");
   MT3_TRY(masks_fit(e, "mt3_engine_decode_beams", batch, 2 * k));
+  MT3_TRY(prompts_fit(e, "mt3_engine_decode_beams", batch, num_steps));
   MT3_TRY(ensure_beam_state(e));
   const int slots = batch * k;
   const bool early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
@@ -2088,7 +2124,7 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
   MT3_TRY(mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s));
   MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
-  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0);
+  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0) | (e->tp_n ? kVarPrompt : 0);
   PendingDecode& p = begin_job(e);
   p.beams = k;
   p.num_steps = num_steps;
@@ -2432,6 +2468,7 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   if (e->eos_on && n_segments > e->eos_cap)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: the synthetic EOS schedule is shorter than n_segments");
   MT3_TRY(masks_fit(e, "mt3_engine_transcribe", n_segments, 2));
+  MT3_TRY(prompts_fit(e, "mt3_engine_transcribe", n_segments, num_steps));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int L = c.max_decode_len, S = n_segments < c.max_batch ? n_segments : c.max_batch;
   const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
@@ -2451,7 +2488,8 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   MT3_TRY(mt3k::launch_iota(e->slot_seg, S, s));
   if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   e->stream_max_len = num_steps;
-  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | (e->tm_n ? kVarMask : 0);
+  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | (e->tm_n ? kVarMask : 0) |
+                      (e->tp_n ? kVarPrompt : 0);
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
   const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   StreamCounts n{};
@@ -2512,6 +2550,7 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
   if (e->eos_on)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the synthetic EOS schedule drives the greedy / beam-1 token kernel only");
   MT3_TRY(masks_fit(e, "mt3_engine_transcribe_beams", n_segments, 2 * k));
+  MT3_TRY(prompts_fit(e, "mt3_engine_transcribe_beams", n_segments, num_steps));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(ensure_beam_state(e));
   MT3_TRY(ensure_stage(e));
@@ -2536,7 +2575,8 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
   MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
   e->cur_batch = slots;
   e->stream_max_len = num_steps;
-  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0);
+  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0) |
+                      (e->tp_n ? kVarPrompt : 0);
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
   const GroupJob j{E, k, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   const BeamOut bo{k, d_all_ids, d_scores};
@@ -2878,6 +2918,72 @@ int mt3_engine_set_token_masks(mt3_engine* e, const uint32_t* h_masks, int32_t n
   return MT3_OK;
 }
 
+int mt3_engine_set_prompts(mt3_engine* e, const int32_t* h_prompts, int32_t n_prompts, int32_t stride,
+                           const int32_t* h_seg_prompt, int32_t n_segments) {
+  const char* who = "mt3_engine_set_prompts: ";
+  if (!e) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "null engine");
+  const bool clear = !h_prompts || n_prompts == 0;
+  std::vector<int> len;
+  // ---- what is wrong with the arguments themselves, then with the engine's state; nothing below touches the device before
+  if (n_prompts < 0) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_prompts must not be negative");
+  if (!clear) {
+    if (stride < 1) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "stride must be at least 1");
+    if (stride >= e->cfg.max_decode_len)
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "stride must be below max_decode_len");
+    if (!h_seg_prompt && n_prompts > 1)
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "several prompts need a per-segment index");
+    if (h_seg_prompt && n_segments < 1)
+      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_segments must be positive with a per-segment index");
+    if (h_seg_prompt)
+      for (int i = 0; i < n_segments; ++i)
+        if (h_seg_prompt[i] < -1 || h_seg_prompt[i] >= n_prompts)
+          return mt3::fail(MT3_ERR_INVALID, std::string(who) + "prompt index outside [-1, n_prompts)");
+    len.resize(static_cast<size_t>(n_prompts));
+    for (int p = 0; p < n_prompts; ++p)
+      if (const char* bad = mt3k::bad_prompt(h_prompts + static_cast<size_t>(p) * stride, stride, e->cfg.vocab_size, &len[p]))
+        return mt3::fail(MT3_ERR_INVALID, std::string(who) + bad);
+  }
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "engine not finalized");
+  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "a decode is in flight");
+  if (clear) {
+    e->tp_n = 0;
+    return MT3_OK;
+  }
+  // a setup call: nothing a caller enqueued earlier may still read the prompts this call replaces
+  MT3_HIP_CHECK(hipDeviceSynchronize());
+  const size_t n_ids = static_cast<size_t>(n_prompts) * stride, n_seg = h_seg_prompt ? static_cast<size_t>(n_segments) : 0;
+  // the kVarPrompt step graphs hold the addresses of both arrays, the stride and whether the index is in use: when a larger
+  // array, another stride or the other form replaces what they captured they go (as the masks' graphs do)
+  bool stale = e->tp_prompts && ((n_seg > 0) != e->tp_seg_on || stride != e->tp_stride);
+  if (n_ids > e->tp_prompt_cap) {
+    int* grown = nullptr;
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_ids * 4));
+    stale = stale || e->tp_prompts != nullptr;
+    e->tp_prompts = grown;
+    e->tp_prompt_cap = n_ids;
+  }
+  if (n_seg > e->tp_seg_cap) {
+    int* grown = nullptr;
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_seg * 4));
+    stale = stale || e->tp_seg != nullptr;
+    e->tp_seg = grown;
+    e->tp_seg_cap = n_seg;
+  }
+  if (stale) {
+    drop_graph(e);
+    drop_group_graphs(e);
+  }
+  e->tp_n = 0;                    // (a failed copy leaves the engine unprompted, not half set)
+  MT3_HIP_CHECK(hipMemcpy(e->tp_prompts, h_prompts, n_ids * 4, hipMemcpyHostToDevice));
+  if (n_seg) MT3_HIP_CHECK(hipMemcpy(e->tp_seg, h_seg_prompt, n_seg * 4, hipMemcpyHostToDevice));
+  e->tp_seg_on = n_seg > 0;
+  e->tp_stride = stride;
+  e->tp_seg_host.assign(h_seg_prompt, h_seg_prompt + n_seg);
+  e->tp_len = len;
+  e->tp_n = n_prompts;
+  return MT3_OK;
+}
+
 int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_score_chunk: engine not finalized");
   if (segments < 0 || segments > e->cfg.max_batch)
@@ -2921,6 +3027,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_LAST_DECODE_FORKS: return e->h_pinned ? e->h_pinned[kForksPinned] : 0;
     case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
     case MT3_STATUS_TOKEN_MASKS: return e->tm_n;
+    case MT3_STATUS_PROMPTS: return e->tp_n;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

@@ -159,6 +159,32 @@ inline const char* bad_token_mask(const uint32_t* h_mask, int vocab, int* allowe
   if (n < 2) return "a mask must allow at least 2 tokens";
   return nullptr;
 }
+// Prompted decoding (mt3_engine_set_prompts; the rule: include/mt3_hip.h): forced token prefixes, `stride` ids each, padded
+// with 0.  A slot at position t < stride whose segment's prompt holds P[t] != 0 is INSIDE its prompt: the kernel that picks
+// the token emits P[t], writes the next input row from it and leaves the search state alone (no score, no EOS candidate, no
+// stop test, no fork).  The prompt of a slot is prompts + seg_prompt[seg] * stride, seg as for TokenMask; a negative seg or
+// index: no prompt.  prompts == nullptr: none -- the launchers then run the unprompted instantiations, whose statements do
+// not mention this struct.
+struct TokenPrompt {
+  const int* prompts;     // [n_prompts][stride]
+  const int* seg_prompt;  // [segments] prompt index per segment, -1 = none (nullptr: prompt 0 for every segment); offset
+                          // like TokenMask::seg_mask
+  const int* slot_seg;    // beam kernel only: [slots] the segment of an element's first slot (nullptr: element = block)
+  int stride;
+};
+// the one host-side check of a prompt row of `stride` ids: nullptr and *len = its length (the index of the first 0, or
+// stride), or what is wrong with it (EOS, id 1, cannot be forced; 0 is padding and ends the prompt)
+inline const char* bad_prompt(const int* h_prompt, int stride, int vocab, int* len) {
+  int n = 0;
+  while (n < stride && h_prompt[n] != 0) ++n;
+  *len = n;
+  for (int i = 0; i < stride; ++i) {
+    if (h_prompt[i] != 0 && (h_prompt[i] < 2 || h_prompt[i] >= vocab)) return "a prompt id outside {0} and [2, vocab)";
+    if (i > n && h_prompt[i] != 0) return "a non-zero prompt id after a 0";
+  }
+  if (n == 0) return "an empty prompt (its first id is 0)";
+  return nullptr;
+}
 // in.y[b] = table[tok[b]] + pos[step[b]] for b < B, in every form `in` holds
 int launch_embed(const InputRow& in, const int* tok, const int* step, int B, hipStream_t s);
 // per-row state of the beam-1 search (t5x beam_search, num_decodes = 1): f = [live_logp | best finished
@@ -216,6 +242,7 @@ struct ArgmaxStepArgs {
   StepRetire rt;
   int B;
   TokenMask tm;         // masks == nullptr: unconstrained (rt.slot_seg / rt.slot_row give the segment, tm.slot_seg is unused)
+  TokenPrompt tp;       // prompts == nullptr: none (the segment as for tm; tp.slot_seg is unused)
 };
 int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that
@@ -299,7 +326,7 @@ struct BeamKArgs {
   // mt3_engine_decode_beams the host loop's bound does that: it passes 0)
   int max_len;
 };
-int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, hipStream_t s);
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp, hipStream_t s);
 // copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
 // (and e4m3 scale rows), for every slot that forked this step; the grid covers every slot x layer x head
 struct BeamReorderArgs {

@@ -115,6 +115,7 @@ class InferenceModel(object):
             "input_depth": spectrograms.input_depth(self.spectrogram_config)})
         self._params = None
         self._job_masks = None                   # (masks, per-segment index or None) of the constrained call in flight
+        self._job_prompts = None                 # per-segment prompts (id list or None) of the prompted call in flight
         self.model = network.Transformer(self.model_config, input_length=self.inputs_length,
                                          max_decode_length=self.outputs_length, max_batch=self.batch_size)
         self.restore_from_checkpoint(checkpoint_path)
@@ -218,23 +219,51 @@ class InferenceModel(object):
         return np.stack([vocabularies.token_mask(self.codec, self.model_config.vocab_size,
                                                  None if p is None else list(p), bool(d)) for p, d in constraints])
 
+    @staticmethod
+    def _segment_prompts(prompts, n_segments: int):
+        """The `prompts=` keyword for one file of `n_segments` segments -> None (no prompt at all) or a list with one
+        entry per segment, an id list or None.  prompts: a sequence with one entry per segment -- an id sequence (the
+        segment's output begins with it: `vocabularies.tie_section_prompt`), or None / empty for none; a shorter sequence
+        is padded with None, a longer one raises ValueError."""
+        if prompts is None:
+            return None
+        rows = [None if p is None or len(p) == 0 else [int(v) for v in p] for p in prompts]
+        if len(rows) > n_segments:
+            raise ValueError("prompts has %d entries; the audio has %d segments" % (len(rows), n_segments))
+        rows += [None] * (n_segments - len(rows))
+        return rows if any(r is not None for r in rows) else None
+
     @contextlib.contextmanager
-    def _constrained(self, job):
-        """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`); the masks are cleared on the way out,
-        also on error"""
+    def _constrained(self, job, prompts=None):
+        """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`) and `prompts` (`_segment_prompts` of
+        the whole job); masks and prompts are cleared on the way out, also on error"""
         self._job_masks = job
+        self._job_prompts = prompts
         try:
             yield
         finally:
             self._job_masks = None
+            self._job_prompts = None
             if job is not None and self.model is not None:
                 self.model.clear_token_masks()
+            if prompts is not None and self.model is not None:
+                self.model.set_prompts(None)
 
     def _set_masks(self, lo: int, hi: int):
-        """before an engine call on segments [lo, hi) of the job: their masks on the engine that will run it"""
+        """before an engine call on segments [lo, hi) of the job: their masks and prompts on the engine that will run it"""
         if self._job_masks is not None:
             masks, seg = self._job_masks
             self.model.set_token_masks(masks, None if seg is None else seg[lo:hi])
+        if self._job_prompts is not None:
+            rows, index = [], []
+            for p in self._job_prompts[lo:hi]:
+                if p is None:
+                    index.append(-1)
+                    continue
+                if p not in rows:
+                    rows.append(p)
+                index.append(rows.index(p))
+            self.model.set_prompts(rows, index if rows else None)
 
     # ------------------------------------------------------------------ model call
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
@@ -290,22 +319,29 @@ class InferenceModel(object):
             self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
         return torch.cat(out, 0)
 
-    def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True):
+    def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True, prompts=None):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
         notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`.
         programs / drums (every transcribing method takes them): constrained decoding -- programs=[0, 33] lets the
         decode use those MIDI programs only, drums=False forbids drum notes; the excluded tokens are impossible at the
-        token pick (Transformer.set_token_masks), so the search takes the best ALLOWED continuation."""
-        with self._constrained(self._token_masks(programs, drums)):
-            return self._transcribe_examples(self._examples(audio, sample_rate))
+        token pick (Transformer.set_token_masks), so the search takes the best ALLOWED continuation.
+        prompts (every transcribing method but the scoring-only ones takes it): prompted decoding -- one entry per segment,
+        an id sequence the segment's output must begin with (`vocabularies.tie_section_prompt(codec, notes)`: the notes
+        still sounding when the segment starts; `tie_section_prompt(codec, [])`: a known silent start) or None / empty for
+        none; shorter than the segments: padded with None, longer: ValueError.  The decode continues from the prompt
+        (Transformer.set_prompts) and the notes are read from prompt + continuation.  Composes with programs / drums."""
+        examples = self._examples(audio, sample_rate)
+        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples))):
+            return self._transcribe_examples(examples)
 
-    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True):
+    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
-        with self._constrained(self._token_masks(programs, drums)):
-            return self._transcribe_examples(self._wav_examples(wav_data))
+        examples = self._wav_examples(wav_data)
+        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples))):
+            return self._transcribe_examples(examples)
 
     def _transcribe_examples(self, examples, scored: bool = False):
         """the examples of one file, their log-mel in _logmel_dev -> NoteSequence (scored: and the notes' scores)"""
@@ -326,7 +362,8 @@ class InferenceModel(object):
                                                               encoding_spec=self.encoding_spec)
         return result["est_ns"], self._note_scores(batch["encoder_input_tokens"], ids, result["note_tokens"])
 
-    def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True):
+    def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True,
+                          prompts=None):
         """`__call__` with a confidence for every note: (NoteSequence, scores).  The notes are those of `__call__` (same
         decode: the model's `decoding` and `schedule`); afterwards the decoded id rows are scored teacher-forced in one
         `Transformer.score_segments` call (ids after EOS are 0 = padding; length = the longest row) and each note is
@@ -338,10 +375,12 @@ class InferenceModel(object):
                            the decoded token is the model's arg-max, negative otherwise
           'note_tokens'    int64 [n_notes, 2, 2]: (segment, position) of the onset and the end token, (-1, -1) for none
         Not available with e4m3 K/V caches (ValueError, as `score`).  With programs / drums the DECODE is constrained; the
-        scores stay the unconstrained model's log-probabilities (scoring ignores token masks)."""
+        scores stay the unconstrained model's log-probabilities (scoring ignores token masks).  With prompts the prompt's
+        tokens are scored like any other decoded token (scoring ignores prompts)."""
         self._refuse_e4m3("transcribe_scored")
-        with self._constrained(self._token_masks(programs, drums)):
-            return self._transcribe_examples(self._examples(audio, sample_rate), scored=True)
+        examples = self._examples(audio, sample_rate)
+        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples))):
+            return self._transcribe_examples(examples, scored=True)
 
     def transcribe_wav_scored(self, wav_data, *, programs=None, drums: bool = True):
         """The file-level form of `transcribe_scored`: `transcribe_wav` plus the notes' confidences."""
@@ -405,27 +444,28 @@ class InferenceModel(object):
         return scores, [tok[i, : len(r)] for i, r in enumerate(rows)]
 
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
-                        drums=True) -> List[Any]:
+                        drums=True, prompts=None) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
         machine is sequential within a file and independent across files, mt3/metrics_utils.py:92-116).  Returns one
         NoteSequence per file, each identical to `self(audio)`.  sample_rates: one rate per file (default: all 16 kHz),
         as for `__call__`.  programs / drums: as for `__call__`, or one entry per file (programs=[[0], [33]]): every segment
-        of a file carries its file's mask, so one job holds files with different instruments."""
+        of a file carries its file's mask, so one job holds files with different instruments.  prompts: one `__call__`-style
+        sequence (or None) per file."""
         if sample_rates is None:
             sample_rates = [SAMPLE_RATE] * len(audios)
         if len(sample_rates) != len(audios):
             raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
         return self._transcribe_files([functools.partial(self._examples, audio, sr)
-                                       for audio, sr in zip(audios, sample_rates)], programs, drums)
+                                       for audio, sr in zip(audios, sample_rates)], programs, drums, prompts)
 
-    def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True) -> List[Any]:
+    def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
-        `self.transcribe_wav(wav)`.  programs / drums: as for `transcribe_many`."""
-        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums)
+        `self.transcribe_wav(wav)`.  programs / drums / prompts: as for `transcribe_many`."""
+        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums, prompts)
 
-    def _transcribe_files(self, make_examples, programs=None, drums=True):
+    def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None):
         """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
         NoteSequence per file, all segments through the engine as one job"""
         import torch
@@ -436,7 +476,15 @@ class InferenceModel(object):
         self._logmel_dev = None
         if not per_file:
             return []
-        with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file])):
+        job_prompts = None
+        if prompts is not None:
+            if len(prompts) != len(per_file):
+                raise ValueError("prompts has %d entries for %d files" % (len(prompts), len(per_file)))
+            rows = []
+            for p, ex in zip(prompts, per_file):
+                rows += self._segment_prompts(p, len(ex)) or [None] * len(ex)
+            job_prompts = rows if any(r is not None for r in rows) else None
+        with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts):
             tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
         out, at = [], 0
         for examples in per_file:

@@ -364,6 +364,34 @@ class Transformer:
     def clear_token_masks(self):
         _lib.check(self._lib.mt3_engine_set_token_masks(self._h, None, 0, None, 0))
 
+    def set_prompts(self, prompts, seg_prompt=None):
+        """mt3_engine_set_prompts: forced token prefixes for every later decode / decode_beams / transcribe call until
+        cleared (`set_prompts(None)`).  prompts: a list of id sequences (padded with 0 to the longest) or a 2-D int array
+        [n_prompts, stride], ids in [2, vocab), 0 = padding; None or [] clears.  seg_prompt: int32 prompt index per batch
+        row / beam element / segment of the job, -1 = none (None: prompt 0 everywhere, n_prompts must be 1).  A segment's
+        output begins with its prompt (`vocabularies.tie_section_prompt` builds MT3's: the tie section); the prompt's
+        tokens are not scored, and the search continues from there.  decode_forced / score / score_segments ignore
+        prompts."""
+        if prompts is None or len(prompts) == 0:
+            _lib.check(self._lib.mt3_engine_set_prompts(self._h, None, 0, 0, None, 0))
+            return
+        if isinstance(prompts, np.ndarray):
+            p = np.ascontiguousarray(prompts, dtype=np.int32)
+            p = p.reshape(1, -1) if p.ndim == 1 else p
+        else:
+            rows = [np.asarray(r, dtype=np.int32).reshape(-1) for r in prompts]
+            p = np.zeros((len(rows), max(1, max(r.size for r in rows))), np.int32)
+            for i, r in enumerate(rows):
+                p[i, :r.size] = r
+        if p.ndim != 2:
+            raise ValueError("prompts must be a list of id sequences or a 2-D array")
+        if seg_prompt is None:
+            _lib.check(self._lib.mt3_engine_set_prompts(self._h, p.ctypes.data, int(p.shape[0]), int(p.shape[1]), None, 0))
+            return
+        sp = np.ascontiguousarray(seg_prompt, dtype=np.int32).reshape(-1)
+        _lib.check(self._lib.mt3_engine_set_prompts(self._h, p.ctypes.data, int(p.shape[0]), int(p.shape[1]),
+                                                    sp.ctypes.data, int(sp.size)))
+
     def debug_decode(self, num_steps: Optional[int] = None, skip_self_attn: bool = False,
                      skip_cross_attn: bool = False, chains: int = 0, use_graph: bool = True):
         """mt3_debug_engine_decode (include/mt3_hip_debug.h): a decode with kernels left out of every step, for

@@ -141,6 +141,30 @@ def token_mask(codec: event_codec.Codec, vocab_size: int, programs=None, drums: 
     return mask
 
 
+def tie_section_prompt(codec: event_codec.Codec, notes, remove_redundant_programs: bool = False) -> list:
+    """The vocabulary ids of the tie section that declares `notes`, an iterable of (program, pitch), as still sounding: a
+    prompt for `Transformer.set_prompts` / the `prompts=` keyword of the transcribing methods.  It is the section the
+    encode side writes for those active notes -- `note_sequences.note_encoding_state_to_events`: a `program, pitch` pair
+    per note, sorted by program, then pitch, then `tie` -- as `run_length_encoding.segment_targets` puts it in front of a
+    segment, already shifted by the 3 special ids.  No notes: the bare `tie` id (a known silent start).
+    remove_redundant_programs: drop a program token equal to the one before it, as `remove_redundant_state_changes`
+    does to the targets the model is trained on.  ValueError for a codec without ties (or without the notes' events)."""
+    try:
+        codec.event_type_range("tie")
+    except ValueError:
+        raise ValueError("tie_section_prompt needs a codec with a tie event") from None
+    E = event_codec.Event
+    special = GenericTokenVocabulary(codec.num_classes)._num_special_tokens
+    out, last_program = [], None
+    for program, pitch in sorted(set((int(p), int(q)) for p, q in notes)):
+        if not (remove_redundant_programs and program == last_program):
+            out.append(codec.encode_event(E("program", program)) + special)
+        last_program = program
+        out.append(codec.encode_event(E("pitch", pitch)) + special)
+    out.append(codec.encode_event(E("tie", 0)) + special)
+    return out
+
+
 def num_embeddings(vocabulary: GenericTokenVocabulary) -> int:
     return 128 * math.ceil(vocabulary.vocab_size / 128)
 
