@@ -612,6 +612,38 @@ int mt3_op_gemm_ex(int32_t dtype, const void* d_A, int32_t a_is_f32, int32_t nor
 int mt3_op_gemm_side(int32_t dtype, const void* d_A, const void* d_Wt, void* d_out, int32_t M, int32_t n_split,
                      int32_t n_side, int32_t K, int32_t epilogue, const float* d_a_ss, void* d_out_ct, float* d_out_ss,
                      float* d_side, int32_t concurrent, void* stream);
+/* The decode-sized tiles in EVERY form the decode loop launches them in (tests/test_gpu_decode_gemm_forms.py): a view of
+ * all the launch's fields, optional pointers NULL.  Test driver: it fills the launch description and launches the
+ * decode-sized tile (small = 1) on `stream`, nothing else (nothing allocated or waited for).
+ *   A [M][lda] (lda 0: K) f32 (a_is_f32) or compute type; Wt [N][K] compute type; norm 0 / 1 / 2 and a_ss as for
+ *   mt3_op_gemm_ex; out rows are ldo elements apart (GEGLU: >= N / 2, or n_split / 2 with out2; else >= N, or n_split).
+ *   epilogue: one of MT3_EPI_*.  out_ct / out_ss: MT3_EPI_RESID, as for mt3_op_gemm_ex (out_ct [M][ldo], out_ss
+ *   [M][width / 16]).
+ *   out2 != NULL (MT3_EPI_STORE, MT3_EPI_RESID, MT3_EPI_GEGLU only) makes the weight rows [n_split, N) a SECOND product
+ *   of the same rows, as for mt3_op_gemm_side: plain f32, no row scale, no activation, row r at out2 + r * ld2 (ld2 0:
+ *   N - n_split).  STORE and GEGLU store it, RESID adds it to what is there; columns at and past the side width of a
+ *   wider row (ld2 > N - n_split: a region inside a wider buffer) are neither read nor written.  GEGLU: N - n_split is
+ *   padded to whole 64-column tiles and only the first ld2 columns are written.  n_split a multiple of 64.
+ *   concurrent != 0 with f32 operands, M >= 256 and MT3_EPI_RESID / MT3_EPI_GEGLU selects the 64 x 32 x 128 tile.
+ * MT3_ERR_INVALID before anything touches a device: v NULL, norm outside 0 .. 2, an epilogue outside MT3_EPI_*, out2
+ * with an epilogue that has no second product, lda < K, ldo below the primary width, ld2 < 0 or (STORE / RESID) a
+ * non-zero ld2 below N - n_split, out_ct / out_ss not as mt3_op_gemm_ex takes them, and whatever the launcher refuses
+ * for the engine too (NULL operands, shapes that are no multiple of the tile, n_split, a_ss without norm 2, ...). */
+typedef struct mt3_gemm_view {
+  const void* A;
+  const void* Wt;
+  void* out;
+  int32_t M, N, K;
+  int32_t lda, ldo;
+  int32_t a_is_f32, norm, epilogue;
+  const float* a_ss;
+  void* out_ct;
+  float* out_ss;
+  float* out2;
+  int32_t n_split, ld2;
+  int32_t concurrent, reserved;
+} mt3_gemm_view;
+int mt3_op_gemm_decode(int32_t dtype, const mt3_gemm_view* v, void* stream);
 /* x f32 [rows][dim] -> compute-type copy [rows][dim] + per-16-column sums of squares [rows][dim/16] */
 int mt3_op_residual_split(int32_t dtype, const float* d_x, void* d_x_ct, float* d_x_ss, int32_t rows, int32_t dim,
                           void* stream);

@@ -103,6 +103,13 @@ class DecAttnView(C.Structure):                # mt3_dec_attn_view (mt3_op_decod
                 ("q_ss_n", C.c_int32), ("reserved", C.c_int32), ("done", _P), ("cache_row", _P)]
 
 
+class GemmView(C.Structure):                   # mt3_gemm_view (mt3_op_gemm_decode)
+    _fields_ = [("A", _P), ("Wt", _P), ("out", _P)] + \
+               [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldo", "a_is_f32", "norm", "epilogue")] + \
+               [("a_ss", _P), ("out_ct", _P), ("out_ss", _P), ("out2", _P)] + \
+               [(n, C.c_int32) for n in ("n_split", "ld2", "concurrent", "reserved")]
+
+
 class ScoreAttnView(C.Structure):              # mt3_score_attn_view (mt3_op_score_attention)
     _fields_ = [("q", _P), ("q_stride", C.c_int32), ("reserved0", C.c_int32), ("k", _P), ("v", _P),
                 ("kv_stride", C.c_int32), ("reserved1", C.c_int32), ("kv_bstride", C.c_int64), ("kv_hstride", C.c_int64),
@@ -167,6 +174,7 @@ SIGNATURES = {
                                  C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_op_gemm_side": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                    _P, C.c_int32, _P]),
+    "mt3_op_gemm_decode": (C.c_int, [C.c_int32, C.POINTER(GemmView), _P]),
     "mt3_op_residual_split": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_encoder_attention": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mt3_op_decode_attention": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,

@@ -1369,6 +1369,47 @@ extern "C" int mt3_op_gemm_side(int32_t dtype, const void* d_A, const void* d_Wt
                            static_cast<hipStream_t>(stream));
 }
 
+// the decode-sized tiles with every GemmArgs field the decode loop sets (engine.hip: enqueue_chain_op): a test driver
+extern "C" int mt3_op_gemm_decode(int32_t dtype, const mt3_gemm_view* v, void* stream) {
+  if (!v) return mt3::fail(MT3_ERR_INVALID, "gemm_decode: null view");
+  if (v->norm < 0 || v->norm > 2) return mt3::fail(MT3_ERR_INVALID, "gemm_decode: norm must be 0, 1 or 2");
+  if (v->epilogue < MT3_EPI_STORE || v->epilogue > MT3_EPI_HEADS)
+    return mt3::fail(MT3_ERR_INVALID, "gemm_decode: epilogue must be one of MT3_EPI_*");
+  int epi = v->epilogue;
+  if (v->out2) {      // the second-product variant, as resid_gemm / normed_gemm select it
+    if (epi == MT3_EPI_STORE) epi = mt3k::kEpiStoreQ;
+    else if (epi == MT3_EPI_RESID) epi = mt3k::kEpiResidQ;
+    else if (epi == MT3_EPI_GEGLU) epi = mt3k::kEpiGegluP;
+    else return mt3::fail(MT3_ERR_INVALID, "gemm_decode: out2 needs MT3_EPI_STORE, MT3_EPI_RESID or MT3_EPI_GEGLU");
+    if (v->ld2 < 0 || (epi != mt3k::kEpiGegluP && v->ld2 != 0 && v->ld2 < v->N - v->n_split))
+      return mt3::fail(MT3_ERR_INVALID, "gemm_decode: ld2 must be 0 or at least the side width N - n_split");
+  }
+  const int lda = v->lda ? v->lda : v->K;
+  const int width = v->out2 ? v->n_split : v->N;       // the primary output region
+  if (lda < v->K || v->ldo < (v->epilogue == MT3_EPI_GEGLU ? width / 2 : width))
+    return mt3::fail(MT3_ERR_INVALID, "gemm_decode: lda below K or ldo below the width of the primary output");
+  if (dtype == MT3_BF16 ? (v->out_ct != nullptr) != (v->out_ss != nullptr) : v->out_ct != nullptr)
+    return mt3::fail(MT3_ERR_INVALID, "gemm_decode: bf16: out_ct and out_ss come together; f32: out_ss alone (the rows are "
+                                      "their own compute-type copy)");
+  mt3k::GemmArgs g{};
+  g.A = v->A;
+  g.Wt = v->Wt;
+  g.out = v->out;
+  g.M = v->M;
+  g.N = v->N;
+  g.K = v->K;
+  g.lda = lda;
+  g.ldo = v->ldo;
+  g.a_ss = v->a_ss;
+  g.out_ct = v->out_ct;
+  g.out_ss = v->out_ss;
+  g.out2 = v->out2;
+  g.n_split = v->n_split;
+  g.ld2 = v->ld2;
+  g.concurrent = v->concurrent != 0;
+  return mt3k::launch_gemm(dtype, g, v->a_is_f32 != 0, v->norm, epi, true, static_cast<hipStream_t>(stream));
+}
+
 // gemm_x6_kernel alone: the weight as the three planes mt3_op_planes makes
 extern "C" int mt3_op_gemm_x6(const float* d_A, const void* d_W_hi, const void* d_W_mid, const void* d_W_lo, int32_t norm,
                               int32_t epilogue, float* d_out, int32_t M, int32_t N, int32_t K, const float* d_aux,
