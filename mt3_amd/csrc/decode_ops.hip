@@ -13,9 +13,9 @@
 //   beam_step_kernel    one step of t5x beam_search with num_decodes = k (mt3_engine_decode_beams): one wave per live
 //                       beam, the k * 2k candidates merged in LDS, the slot -> cache-row map rewritten; with
 //                       beam_reorder_kernel (K/V copies of forked rows) and beam_finalize_kernel (history backtrack).
-//                       Both token kernels have a MASKED instantiation (constrained decoding, TokenMask in kernels.h):
-//                       the logit of a token the slot's mask disallows counts as -inf.  Both have a PROMPT instantiation
-//                       (prompted decoding, TokenPrompt in kernels.h): a slot inside its prompt emits the prompt's token.
+//                       Both token kernels read up to two per-segment tables (SegTable in kernels.h): the MASKED
+//                       instantiations count the logit of a token the slot's mask row disallows as -inf, the PROMPT
+//                       instantiations emit the prompt row's token while the slot is inside it.
 //   ids_to_tokens_kernel GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271), bit-exact.
 #include <hip/hip_runtime.h>
 
@@ -185,15 +185,23 @@ struct Top2 {
   }
 };
 
-// Constrained decoding (TokenMask, kernels.h): what a logit mask ahead of t5x `beam_search` does -- a disallowed token's
-// logit is -inf wherever the token rule reads it.  (t5x is not at hand: written from memory, as the beam rule is.)
-constexpr float kMaskedLogit = -__builtin_inff();
-// the mask row of segment `seg`, nullptr = unconstrained; never indexes with a negative segment or mask index
-__device__ __forceinline__ const uint32_t* mask_row(const TokenMask& tm, int seg) {
-  if (seg < 0) return nullptr;
-  const int m = tm.seg_mask ? tm.seg_mask[seg] : 0;
-  return m < 0 ? nullptr : tm.masks + static_cast<size_t>(m) * tm.words;
+// the segment slot `slot` decodes: what the EOS schedule, the masks and the prompts are indexed by.  slot_seg: the in-flight
+// map (nullptr: `direct`, the row the slot decodes / the beam kernel's block)
+__device__ __forceinline__ int slot_segment(const int* slot_seg, int slot, int direct) {
+  return slot_seg ? slot_seg[slot] : direct;
 }
+// the row of segment `seg` in a per-segment table (SegTable, kernels.h), nullptr = none; never indexes with a negative
+// segment or row index
+template <typename T>
+__device__ __forceinline__ const T* seg_table_row(const SegTable<T>& tb, int seg) {
+  if (seg < 0) return nullptr;
+  const int r = tb.seg_row ? tb.seg_row[seg] : 0;
+  return r < 0 ? nullptr : tb.rows + static_cast<size_t>(r) * tb.stride;
+}
+
+// Constrained decoding (TokenMask): what a logit mask ahead of t5x `beam_search` does -- a disallowed token's logit is
+// -inf wherever the token rule reads it.  (t5x is not at hand: written from memory, as the beam rule is.)
+constexpr float kMaskedLogit = -__builtin_inff();
 __device__ __forceinline__ bool mask_allows(uint32_t word, int i) { return (word >> (i & 31)) & 1u; }
 // row[i] as the token rule reads it in the loops that walk the row in memory (vocab > 2048)
 template <bool MASKED>
@@ -202,12 +210,12 @@ __device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mr
   return row[i];
 }
 
-// Prompted decoding (TokenPrompt, kernels.h): the prompt token of segment `seg` at position t, 0 = the slot is past its
-// prompt or has none; never indexes with a negative segment, prompt index or a position at or past the stride
+// Prompted decoding (TokenPrompt): the prompt token of segment `seg` at position t, 0 = the slot is past its prompt or has
+// none; never reads a position at or past the stride
 __device__ __forceinline__ int prompt_token(const TokenPrompt& tp, int seg, int t) {
-  if (seg < 0 || t >= tp.stride) return 0;
-  const int p = tp.seg_prompt ? tp.seg_prompt[seg] : 0;
-  return p < 0 ? 0 : tp.prompts[static_cast<size_t>(p) * tp.stride + t];
+  if (t >= tp.stride) return 0;
+  const int* row = seg_table_row(tp, seg);
+  return row ? row[t] : 0;
 }
 
 // BEAM1 = false: greedy pick (the product default).
@@ -262,7 +270,7 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   const uint32_t* mrow = nullptr;
   uint32_t mw[kPer];
   if (MASKED) {
-    mrow = mask_row(a.tm, rt.slot_seg ? rt.slot_seg[b] : out_row);
+    mrow = seg_table_row(a.tm, slot_segment(rt.slot_seg, b, out_row));
     if (in_regs) {
 #pragma unroll
       for (int u = 0; u < kPer; ++u) {
@@ -274,14 +282,14 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   // PROMPT: the slot's prompt token at its own position, one dword per block requested in the same batch (0: not inside a
   // prompt); only thread 0 reads it
   int ptok = 0;
-  if (PROMPT) ptok = prompt_token(a.tp, rt.slot_seg ? rt.slot_seg[b] : out_row, st.step[b]);
+  if (PROMPT) ptok = prompt_token(a.tp, slot_segment(rt.slot_seg, b, out_row), st.step[b]);
   // thread 0 issues its state loads up front so that their latency hides behind the reductions
   int was_done = 0, t = 0, blen = -1, eos_len = 0x7fffffff;
   float live = 0.f, best = 0.f, bp_max = 1.f, bp_t = 1.f;
   if (tid == 0) {
     was_done = st.done[b];
     t = st.step[b];
-    if (rt.eos_at) eos_len = rt.eos_at[rt.slot_seg ? rt.slot_seg[b] : out_row];
+    if (rt.eos_at) eos_len = rt.eos_at[slot_segment(rt.slot_seg, b, out_row)];
     if (BEAM1) {
       live = a.beam.f[b];
       best = a.beam.f[a.beam.rows + b];
@@ -437,16 +445,16 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
   if (a.ls.ss && (a.ls.n_ss <= 0 || a.ls.n_ss > 64 || a.ls.dim <= 0))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: the row scale needs 1 .. 64 partial sums");
   if (const int rc = bad_input_row(a.in, "argmax_step")) return rc;
-  if (a.tm.masks && (a.forced || a.tm.words != (a.vocab + 31) / 32))
+  if (a.tm.rows && (a.forced || a.tm.stride != (a.vocab + 31) / 32))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: token masks are ceil(vocab / 32) words and not for teacher forcing");
-  if (a.tp.prompts && (a.forced || a.tp.stride < 1))
+  if (a.tp.rows && (a.forced || a.tp.stride < 1))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: prompts have a stride of at least 1 and are not for teacher forcing");
   void (*kernel)(ArgmaxStepArgs);
-  if (a.tp.prompts) {
-    if (a.tm.masks) kernel = a.beam.f ? argmax_step_kernel<true, true, true> : argmax_step_kernel<false, true, true>;
+  if (a.tp.rows) {
+    if (a.tm.rows) kernel = a.beam.f ? argmax_step_kernel<true, true, true> : argmax_step_kernel<false, true, true>;
     else kernel = a.beam.f ? argmax_step_kernel<true, false, true> : argmax_step_kernel<false, false, true>;
   } else {
-    if (a.tm.masks) kernel = a.beam.f ? argmax_step_kernel<true, true, false> : argmax_step_kernel<false, true, false>;
+    if (a.tm.rows) kernel = a.beam.f ? argmax_step_kernel<true, true, false> : argmax_step_kernel<false, true, false>;
     else kernel = a.beam.f ? argmax_step_kernel<true, false, false> : argmax_step_kernel<false, false, false>;
   }
   hipLaunchKernelGGL(kernel, dim3(a.B), dim3(256), 0, s, a);
@@ -708,7 +716,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
   // MASKED: the mask word of every logit the lane holds, requested in the same batch as the logits
   uint32_t mw[kPerLane];
   if (MASKED) {
-    const uint32_t* mrow = mask_row(tm, tm.slot_seg ? tm.slot_seg[s0] : static_cast<int>(blockIdx.x));
+    const uint32_t* mrow = seg_table_row(tm, slot_segment(tm.slot_seg, s0, blockIdx.x));
 #pragma unroll
     for (int j = 0; j < kPerLane; ++j) {
       const int i = lane + 64 * (j >> 3) + 256 * (j & 7);
@@ -717,7 +725,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
   }
   if (PROMPT) {
     // the element's prompt token at its own position, requested in the same batch as the logits (0: not inside a prompt)
-    const int ptok = prompt_token(tp, tp.slot_seg ? tp.slot_seg[s0] : static_cast<int>(blockIdx.x), t);
+    const int ptok = prompt_token(tp, slot_segment(tp.slot_seg, s0, blockIdx.x), t);
     if (ptok != 0) {
       __syncthreads();             // every wave has read the element's done flag and position before thread 0 rewrites them
       if (threadIdx.x == 0) {
@@ -952,12 +960,12 @@ int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& 
     return mt3::fail(MT3_ERR_INVALID, "beam_step: the row scale needs 1 .. 64 partial sums");
   if (a.in.y && a.in.dim % 16) return mt3::fail(MT3_ERR_INVALID, "beam_step: the next input row needs dim % 16 == 0");
   if (const int rc = bad_input_row(a.in, "beam_step")) return rc;
-  if (tm.masks && tm.words != (a.vocab + 31) / 32)
+  if (tm.rows && tm.stride != (a.vocab + 31) / 32)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: token masks are ceil(vocab / 32) words");
-  if (tp.prompts && tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "beam_step: prompts have a stride of at least 1");
+  if (tp.rows && tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "beam_step: prompts have a stride of at least 1");
   void (*kernel)(BeamKArgs, LogitScale, TokenMask, TokenPrompt);
-  if (tp.prompts) kernel = tm.masks ? beam_step_kernel<true, true> : beam_step_kernel<false, true>;
-  else kernel = tm.masks ? beam_step_kernel<true, false> : beam_step_kernel<false, false>;
+  if (tp.rows) kernel = tm.rows ? beam_step_kernel<true, true> : beam_step_kernel<false, true>;
+  else kernel = tm.rows ? beam_step_kernel<true, false> : beam_step_kernel<false, false>;
   hipLaunchKernelGGL(kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls, tm, tp);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
@@ -1300,6 +1308,16 @@ int upload_brevity(float* d_bp, int num_steps, hipStream_t s) {
 
 bool bad_scale(const float* d_ss, int n_ss, int dim) { return d_ss && (n_ss < 1 || n_ss > 64 || dim <= 0); }
 
+// the per-row index of a driver's table, d_index [n], read back into *h and checked on the host before a kernel indexes
+// with it: every entry in [-1, bound), or the failure `bad`
+int driver_index(const std::string& who, const int32_t* d_index, int n, int bound, const char* bad, std::vector<int32_t>* h) {
+  h->resize(static_cast<size_t>(n));
+  MT3_HIP_CHECK(hipMemcpy(h->data(), d_index, h->size() * 4, hipMemcpyDeviceToHost));
+  for (int32_t v : *h)
+    if (v < -1 || v >= bound) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  return MT3_OK;
+}
+
 // the masks of a masked driver, read back and checked on the host before a kernel indexes with them: every mask valid
 // (bad_token_mask) with at least `need` allowed tokens, every entry of d_row_mask [n] in [-1, n_masks)
 int driver_masks(const std::string& who, const uint32_t* d_masks, int n_masks, const int32_t* d_row_mask, int n, int vocab,
@@ -1314,12 +1332,8 @@ int driver_masks(const std::string& who, const uint32_t* d_masks, int n_masks, c
       return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
     if (allowed < need) return mt3::fail(MT3_ERR_INVALID, who + ": a mask allows fewer than 2 * k tokens");
   }
-  if (d_row_mask) {
-    std::vector<int32_t> r(static_cast<size_t>(n));
-    MT3_HIP_CHECK(hipMemcpy(r.data(), d_row_mask, r.size() * 4, hipMemcpyDeviceToHost));
-    for (int32_t v : r)
-      if (v < -1 || v >= n_masks) return mt3::fail(MT3_ERR_INVALID, who + ": mask index outside [-1, n_masks)");
-  }
+  std::vector<int32_t> r;
+  if (d_row_mask) MT3_OP_TRY(driver_index(who, d_row_mask, n, n_masks, "mask index outside [-1, n_masks)", &r));
   *tm = mt3k::TokenMask{d_masks, d_row_mask, nullptr, words};
   return MT3_OK;
 }
@@ -1332,13 +1346,10 @@ int driver_prompts(const std::string& who, const int32_t* d_prompts, int stride,
   if (stride < 1 || stride > 4096) return mt3::fail(MT3_ERR_INVALID, who + ": the prompt stride must be 1 .. 4096");
   int n_prompts = 1;
   if (d_row_prompt) {
-    std::vector<int32_t> r(static_cast<size_t>(n));
-    MT3_HIP_CHECK(hipMemcpy(r.data(), d_row_prompt, r.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> r;
+    MT3_OP_TRY(driver_index(who, d_row_prompt, n, 4096, "prompt index outside [-1, 4096)", &r));
     n_prompts = 0;
-    for (int32_t v : r) {
-      if (v < -1 || v >= 4096) return mt3::fail(MT3_ERR_INVALID, who + ": prompt index outside [-1, 4096)");
-      if (v + 1 > n_prompts) n_prompts = v + 1;
-    }
+    for (int32_t v : r) n_prompts = std::max(n_prompts, v + 1);
   }
   std::vector<int32_t> h(static_cast<size_t>(n_prompts) * stride);
   if (!h.empty()) MT3_HIP_CHECK(hipMemcpy(h.data(), d_prompts, h.size() * 4, hipMemcpyDeviceToHost));

@@ -32,6 +32,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <cstdlib>
@@ -176,6 +177,20 @@ struct PendingDecode {
   float* d_scores = nullptr;
 };
 
+// A per-segment table as the engine owns it (set_seg_table; the kernels' view of it: seg_view / mt3k::SegTable).  The
+// step graphs of its kVar* bit hold the addresses of both arrays, the stride and whether the index is in use.
+template <typename T>
+struct SegTableHost {
+  T* rows = nullptr;             // [rows_cap] elements: n rows of `stride`
+  int* seg = nullptr;            // [seg_cap] row index per row / element / segment of a job
+  size_t rows_cap = 0, seg_cap = 0;
+  int n = 0;                     // rows set (0: the table is not in use)
+  int stride = 0;                // elements of T per row
+  bool seg_on = false;           // a per-segment index is set (false: row 0 for every segment)
+  std::vector<int> seg_host;     // host copy of the per-segment index
+  std::vector<int> stat;         // host, per row: what the job checks read (fits)
+};
+
 }  // namespace
 
 struct mt3_engine {
@@ -259,23 +274,10 @@ struct mt3_engine {
                                  // mt3_engine_transcribe -- per segment
   int eos_cap = 0;
   bool eos_on = false;
-  // Constrained decoding (mt3_engine_set_token_masks): engine-owned copies, whose addresses the kVarMask step graphs hold
-  uint32_t* tm_masks = nullptr;  // [tm_mask_cap] words: tm_n masks of ceil(vocab / 32) words
-  int* tm_seg = nullptr;         // [tm_seg_cap] mask index per row / element / segment
-  size_t tm_mask_cap = 0, tm_seg_cap = 0;
-  int tm_n = 0;                  // masks set (0: unconstrained)
-  bool tm_seg_on = false;        // a per-segment index is set (false: mask 0 for every segment); baked into the step graphs
-  std::vector<int> tm_allowed;   // host: allowed tokens of each mask
-  std::vector<int> tm_seg_host;  // host copy of the per-segment index
-  // Prompted decoding (mt3_engine_set_prompts): engine-owned copies, whose addresses the kVarPrompt step graphs hold
-  int* tp_prompts = nullptr;     // [tp_prompt_cap] ids: tp_n prompts of tp_stride ids, 0-padded
-  int* tp_seg = nullptr;         // [tp_seg_cap] prompt index per row / element / segment
-  size_t tp_prompt_cap = 0, tp_seg_cap = 0;
-  int tp_n = 0;                  // prompts set (0: none)
-  int tp_stride = 0;             // baked into the step graphs, as is tp_seg_on
-  bool tp_seg_on = false;        // a per-segment index is set (false: prompt 0 for every segment)
-  std::vector<int> tp_len;       // host: length of each prompt
-  std::vector<int> tp_seg_host;  // host copy of the per-segment index
+  SegTableHost<uint32_t> tm;     // constrained decoding (mt3_engine_set_token_masks, kVarMask): masks of ceil(vocab / 32)
+                                 // words; stat = the allowed tokens of each
+  SegTableHost<int> tp;          // prompted decoding (mt3_engine_set_prompts, kVarPrompt): 0-padded id rows; stat = the
+                                 // length of each
   // In-flight batching (mt3_engine_transcribe): slot_seg maps a slot to the SEGMENT it is decoding (-1: none); a
   // finished slot hands its id row to the caller's output and restarts on the next encoded segment (launch_refill)
   int* slot_seg = nullptr;       // [max_batch]
@@ -371,6 +373,27 @@ using mt3k::brevity_penalty;     // t5x decoding.brevity_penalty(alpha = 0.6, le
     int _rc = (expr);           \
     if (_rc != MT3_OK) return _rc; \
   } while (0)
+
+// the kernels' view of a table for one step: the index starts at the step's first row / element `seg0` (0 with `slot_seg`,
+// the in-flight map of the step's first slot, which then names the segment)
+template <typename T>
+mt3k::SegTable<T> seg_view(const SegTableHost<T>& tb, size_t seg0, const int* slot_seg) {
+  return mt3k::SegTable<T>{tb.rows, tb.seg_on ? tb.seg + seg0 : nullptr, slot_seg, tb.stride};
+}
+
+// MT3_OK, or why a job of `n` rows / elements / segments cannot run under table `tb` (`whose`): the per-row statistic of
+// every row in use must lie in [lo, hi], else `why`
+template <typename T>
+int fits(const SegTableHost<T>& tb, const char* who, int n, int lo, int hi, const char* whose, const char* why) {
+  if (!tb.n) return MT3_OK;
+  if (tb.seg_on && n > static_cast<int>(tb.seg_host.size()))
+    return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": more rows or segments than " + whose + " n_segments");
+  for (int i = 0; i < (tb.seg_on ? n : 1); ++i) {
+    const int r = tb.seg_on ? tb.seg_host[i] : 0;
+    if (r >= 0 && (tb.stat[r] < lo || tb.stat[r] > hi)) return mt3::fail(MT3_ERR_INVALID, std::string(who) + why);
+  }
+  return MT3_OK;
+}
 
 int dmalloc(mt3_engine* e, void** p, size_t bytes) {
   MT3_HIP_CHECK(hipMalloc(p, bytes));
@@ -867,18 +890,12 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     b.logits = logits;
     b.max_len = (skip & kVarStream) ? e->stream_max_len : 0;
     const mt3k::LogitScale ls{fold ? y_ss : nullptr, emb / 16, emb};
-    mt3k::TokenMask tm{};
-    if (skip & kVarMask) {     // in-flight: the element's segment; a batch call: element row0 / k + block
-      const bool streaming = (skip & kVarStream) != 0;
-      const int* seg = !e->tm_seg_on ? nullptr : (streaming ? e->tm_seg : e->tm_seg + row0 / b.k);
-      tm = mt3k::TokenMask{e->tm_masks, seg, streaming ? e->slot_seg + row0 : nullptr, (c.vocab_size + 31) / 32};
-    }
-    mt3k::TokenPrompt tp{};
-    if (skip & kVarPrompt) {   // indexed as the masks are
-      const bool streaming = (skip & kVarStream) != 0;
-      const int* seg = !e->tp_seg_on ? nullptr : (streaming ? e->tp_seg : e->tp_seg + row0 / b.k);
-      tp = mt3k::TokenPrompt{e->tp_prompts, seg, streaming ? e->slot_seg + row0 : nullptr, e->tp_stride};
-    }
+    // both tables are indexed by the element's segment in flight, by element row0 / k + block in a batch call
+    const bool streaming = (skip & kVarStream) != 0;
+    const size_t seg0 = streaming ? 0 : static_cast<size_t>(row0 / b.k);
+    const int* slot_seg = streaming ? e->slot_seg + row0 : nullptr;
+    const mt3k::TokenMask tm = (skip & kVarMask) ? seg_view(e->tm, seg0, slot_seg) : mt3k::TokenMask{};
+    const mt3k::TokenPrompt tp = (skip & kVarPrompt) ? seg_view(e->tp, seg0, slot_seg) : mt3k::TokenPrompt{};
     MT3_TRY(mt3k::launch_beam_step(b, ls, tm, tp, s));
     mt3k::BeamReorderArgs r{};
     r.n_layers = nl;
@@ -914,10 +931,9 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     a.rt = mt3k::StepRetire{retire ? 1 : 0, retire ? a.st.slot_row : nullptr, (skip & kVarEos) ? e->eos_at + crow0 : nullptr,
                             streaming ? a.st.slot_seg : nullptr, streaming ? e->stream_max_len : 0};
     a.B = rows;
-    if (skip & kVarMask)       // indexed as eos_at is: by segment, or by the row the slot decodes
-      a.tm = mt3k::TokenMask{e->tm_masks, e->tm_seg_on ? e->tm_seg + crow0 : nullptr, nullptr, (c.vocab_size + 31) / 32};
-    if (skip & kVarPrompt)     // indexed as the masks are
-      a.tp = mt3k::TokenPrompt{e->tp_prompts, e->tp_seg_on ? e->tp_seg + crow0 : nullptr, nullptr, e->tp_stride};
+    // both tables are indexed as eos_at is: by segment, or by the row the slot decodes (a.rt says which)
+    if (skip & kVarMask) a.tm = seg_view(e->tm, crow0, nullptr);
+    if (skip & kVarPrompt) a.tp = seg_view(e->tp, crow0, nullptr);
     return mt3k::launch_argmax_step(a, s);
   }
   LayerDev& L = e->dec[op >> 3];
@@ -1119,6 +1135,11 @@ extern "C" {
 
 static void workers_stop(mt3_engine* e);
 static void drop_group_graphs(mt3_engine* e);
+// every captured step graph: what a setup call does when a graph may hold an address or a constant it replaces
+static void drop_step_graphs(mt3_engine* e) {
+  drop_graph(e);
+  drop_group_graphs(e);
+}
 
 int mt3_engine_create(const mt3_engine_config* cfg, mt3_engine** out) {
   if (!cfg || !out) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_create: null argument");
@@ -1166,8 +1187,7 @@ int mt3_engine_create(const mt3_engine_config* cfg, mt3_engine** out) {
 void mt3_engine_destroy(mt3_engine* e) {
   if (!e) return;
   workers_stop(e);                 // joins a decode that is still in flight
-  drop_graph(e);
-  drop_group_graphs(e);
+  drop_step_graphs(e);
   for (int k = 0; k < kMaxChains; ++k) {
     if (e->cap_stream[k]) (void)hipStreamDestroy(e->cap_stream[k]);
     if (e->cap_event[k]) (void)hipEventDestroy(e->cap_event[k]);
@@ -1941,34 +1961,17 @@ static int reset_beam1_state(mt3_engine* e, int num_steps, hipStream_t s) {
   return MT3_OK;
 }
 
+// The masks, then the prompts, against a job of `n` rows / elements / segments: a step needs `need` candidates among a
+// mask's allowed tokens, and a segment at least one free step of `num_steps` after its prompt.  MT3_OK and *var = the
+// kVarMask / kVarPrompt bits of the job's step variant.
+static int seg_tables_fit(const mt3_engine* e, const char* who, int n, int need, int num_steps, int* var) {
+  MT3_TRY(fits(e->tm, who, n, need, INT_MAX, "the token masks'", ": a token mask in use allows fewer than 2 * num_beams tokens"));
+  MT3_TRY(fits(e->tp, who, n, 0, num_steps - 1, "the prompts'", ": num_steps must exceed the longest prompt in use"));
+  *var = (e->tm.n ? kVarMask : 0) | (e->tp.n ? kVarPrompt : 0);
+  return MT3_OK;
+}
+
 // shared body of mt3_engine_decode / mt3_engine_decode_forced
-// MT3_OK, or why a job of `n` rows / elements / segments whose step needs `need` candidates cannot run under the masks set
-static int masks_fit(const mt3_engine* e, const char* who, int n, int need) {
-  if (!e->tm_n) return MT3_OK;
-  if (e->tm_seg_on && n > static_cast<int>(e->tm_seg_host.size()))
-    return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": more rows or segments than the token masks' n_segments");
-  for (int i = 0; i < (e->tm_seg_on ? n : 1); ++i) {
-    const int m = e->tm_seg_on ? e->tm_seg_host[i] : 0;
-    if (m >= 0 && e->tm_allowed[m] < need)
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": a token mask in use allows fewer than 2 * num_beams tokens");
-  }
-  return MT3_OK;
-}
-
-// MT3_OK, or why a job of `n` rows / elements / segments of `num_steps` steps cannot run under the prompts set: a segment
-// must have at least one free step after its prompt
-static int prompts_fit(const mt3_engine* e, const char* who, int n, int num_steps) {
-  if (!e->tp_n) return MT3_OK;
-  if (e->tp_seg_on && n > static_cast<int>(e->tp_seg_host.size()))
-    return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": more rows or segments than the prompts' n_segments");
-  for (int i = 0; i < (e->tp_seg_on ? n : 1); ++i) {
-    const int p = e->tp_seg_on ? e->tp_seg_host[i] : 0;
-    if (p >= 0 && num_steps <= e->tp_len[p])
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": num_steps must exceed the longest prompt in use");
-  }
-  return MT3_OK;
-}
-
 static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t debug_skip,
                        const int32_t* d_forced, float* d_step_logits, int32_t* d_ids, float* d_first_logits,
                        int32_t* h_steps_run, void* stream) {
@@ -1987,10 +1990,8 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   const bool async = (flags & MT3_DECODE_ASYNC) != 0;
   if (d_forced && (beam1 || early || async))
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_forced: not combinable with BEAM1 / EARLY_EXIT / ASYNC");
-  const bool masked = e->tm_n > 0 && !d_forced;          // teacher forcing ignores token masks
-  if (masked) MT3_TRY(masks_fit(e, "mt3_engine_decode", batch, 2));
-  const bool prompted = e->tp_n > 0 && !d_forced;        // ... and prompts
-  if (prompted) MT3_TRY(prompts_fit(e, "mt3_engine_decode", batch, num_steps));
+  int seg_var = 0;                                       // teacher forcing ignores token masks and prompts
+  if (!d_forced) MT3_TRY(seg_tables_fit(e, "mt3_engine_decode", batch, 2, num_steps, &seg_var));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(reset_slots(e, batch, true, true, s));
   if (d_forced)    // engine-owned copy: the step graph holds ITS address, whatever buffer the caller passes
@@ -2005,7 +2006,7 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   // step variant: bits 1 / 2 = mt3_debug_engine_decode's skipped kernels (mt3_hip_debug.h; never set by the product
   // entry points), then kVar*
   const int variant = (debug_skip & 3) | (beam1 ? kVarBeam : 0) | (d_forced ? kVarForced : 0) | (retire ? kVarRetire : 0) |
-                      (e->eos_on && !d_forced ? kVarEos : 0) | (masked ? kVarMask : 0) | (prompted ? kVarPrompt : 0);
+                      (e->eos_on && !d_forced ? kVarEos : 0) | seg_var;
   if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   PendingDecode& p = begin_job(e);
   p.beam1 = beam1;
@@ -2113,8 +2114,8 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: the beam step needs 2 * num_beams <= vocab <= 2048");
   if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: more than 16 decoder layers");
-  MT3_TRY(masks_fit(e, "mt3_engine_decode_beams", batch, 2 * k));
-  MT3_TRY(prompts_fit(e, "mt3_engine_decode_beams", batch, num_steps));
+  int seg_var = 0;
+  MT3_TRY(seg_tables_fit(e, "mt3_engine_decode_beams", batch, 2 * k, num_steps, &seg_var));
   MT3_TRY(ensure_beam_state(e));
   const int slots = batch * k;
   const bool early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
@@ -2124,7 +2125,7 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
   MT3_TRY(mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s));
   MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
-  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0) | (e->tp_n ? kVarPrompt : 0);
+  const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift) | seg_var;
   PendingDecode& p = begin_job(e);
   p.beams = k;
   p.num_steps = num_steps;
@@ -2467,8 +2468,8 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   if (c.num_decoder_layers > mt3k::kRefillMaxLayers) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: at most 16 decoder layers");
   if (e->eos_on && n_segments > e->eos_cap)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: the synthetic EOS schedule is shorter than n_segments");
-  MT3_TRY(masks_fit(e, "mt3_engine_transcribe", n_segments, 2));
-  MT3_TRY(prompts_fit(e, "mt3_engine_transcribe", n_segments, num_steps));
+  int seg_var = 0;
+  MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe", n_segments, 2, num_steps, &seg_var));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int L = c.max_decode_len, S = n_segments < c.max_batch ? n_segments : c.max_batch;
   const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
@@ -2488,8 +2489,7 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
   MT3_TRY(mt3k::launch_iota(e->slot_seg, S, s));
   if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
   e->stream_max_len = num_steps;
-  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | (e->tm_n ? kVarMask : 0) |
-                      (e->tp_n ? kVarPrompt : 0);
+  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | seg_var;
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
   const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   StreamCounts n{};
@@ -2549,8 +2549,8 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
   if (e->eos_on)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the synthetic EOS schedule drives the greedy / beam-1 token kernel only");
-  MT3_TRY(masks_fit(e, "mt3_engine_transcribe_beams", n_segments, 2 * k));
-  MT3_TRY(prompts_fit(e, "mt3_engine_transcribe_beams", n_segments, num_steps));
+  int seg_var = 0;
+  MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe_beams", n_segments, 2 * k, num_steps, &seg_var));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(ensure_beam_state(e));
   MT3_TRY(ensure_stage(e));
@@ -2575,8 +2575,7 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
   MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
   e->cur_batch = slots;
   e->stream_max_len = num_steps;
-  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift) | (e->tm_n ? kVarMask : 0) |
-                      (e->tp_n ? kVarPrompt : 0);
+  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift) | seg_var;
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
   const GroupJob j{E, k, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
   const BeamOut bo{k, d_all_ids, d_scores};
@@ -2826,6 +2825,72 @@ int mt3_debug_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int
   return decode_impl(e, batch, num_steps, flags, skip, nullptr, nullptr, d_ids, nullptr, nullptr, stream);
 }
 
+extern "C++" {
+// a device array of at least n elements in *p: a larger one takes the place of one too small, which stays in the engine's
+// allocation list until destroy; *replaced is set when a graph may hold the old one's address (there was one)
+template <typename T, typename C>
+static int grow(mt3_engine* e, T** p, C* cap, size_t n, bool* replaced) {
+  if (n <= static_cast<size_t>(*cap)) return MT3_OK;
+  T* grown = nullptr;
+  MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n * sizeof(T)));
+  *replaced = *replaced || *p != nullptr;
+  *p = grown;
+  *cap = static_cast<C>(n);
+  return MT3_OK;
+}
+
+// shared body of mt3_engine_set_token_masks / mt3_engine_set_prompts (fn: "<function>: ", noun: "mask" / "prompt"): n rows
+// of `stride` elements and, with h_seg, an index of n_segments entries; h_rows == nullptr or n == 0 clears.  bad_stride:
+// what is wrong with the stride (nullptr: nothing); bad_row(row, &stat): what is wrong with a row, or nullptr and its
+// statistic.
+template <typename T, typename BadRow>
+static int set_seg_table(mt3_engine* e, SegTableHost<T>& tb, const std::string& fn, const std::string& noun, const T* h_rows,
+                         int n, int stride, const char* bad_stride, const int32_t* h_seg, int n_segments, BadRow bad_row) {
+  const bool clear = !h_rows || n == 0;
+  std::vector<int> stat;
+  // ---- what is wrong with the arguments themselves, then with the engine's state; nothing below touches the device before
+  if (n < 0) return mt3::fail(MT3_ERR_INVALID, fn + "n_" + noun + "s must not be negative");
+  if (!clear) {
+    if (bad_stride) return mt3::fail(MT3_ERR_INVALID, fn + bad_stride);
+    if (!h_seg && n > 1) return mt3::fail(MT3_ERR_INVALID, fn + "several " + noun + "s need a per-segment index");
+    if (h_seg && n_segments < 1)
+      return mt3::fail(MT3_ERR_INVALID, fn + "n_segments must be positive with a per-segment index");
+    if (h_seg)
+      for (int i = 0; i < n_segments; ++i)
+        if (h_seg[i] < -1 || h_seg[i] >= n)
+          return mt3::fail(MT3_ERR_INVALID, fn + noun + " index outside [-1, n_" + noun + "s)");
+    stat.resize(static_cast<size_t>(n));
+    for (int r = 0; r < n; ++r)
+      if (const char* bad = bad_row(h_rows + static_cast<size_t>(r) * stride, &stat[r]))
+        return mt3::fail(MT3_ERR_INVALID, fn + bad);
+  }
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, fn + "engine not finalized");
+  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, fn + "a decode is in flight");
+  if (clear) {
+    tb.n = 0;
+    return MT3_OK;
+  }
+  // a setup call: nothing a caller enqueued earlier may still read the rows this call replaces
+  MT3_HIP_CHECK(hipDeviceSynchronize());
+  const size_t n_elems = static_cast<size_t>(n) * stride, n_seg = h_seg ? static_cast<size_t>(n_segments) : 0;
+  // the table's step graphs hold the addresses of both arrays, the stride and whether the index is in use: when a larger
+  // array, another stride or the other form replaces what they captured they go
+  bool stale = tb.rows && ((n_seg > 0) != tb.seg_on || stride != tb.stride);
+  MT3_TRY(grow(e, &tb.rows, &tb.rows_cap, n_elems, &stale));
+  MT3_TRY(grow(e, &tb.seg, &tb.seg_cap, n_seg, &stale));
+  if (stale) drop_step_graphs(e);
+  tb.n = 0;                       // (a failed copy leaves the table out of use, not half set)
+  MT3_HIP_CHECK(hipMemcpy(tb.rows, h_rows, n_elems * sizeof(T), hipMemcpyHostToDevice));
+  if (n_seg) MT3_HIP_CHECK(hipMemcpy(tb.seg, h_seg, n_seg * 4, hipMemcpyHostToDevice));
+  tb.seg_on = n_seg > 0;
+  tb.stride = stride;
+  tb.seg_host.assign(h_seg, h_seg + n_seg);
+  tb.stat = stat;
+  tb.n = n;
+  return MT3_OK;
+}
+}  // extern "C++"
+
 int mt3_debug_engine_set_eos_schedule(mt3_engine* e, const int32_t* h_lengths, int32_t n) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_eos_schedule: engine not finalized");
   if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_eos_schedule: a decode is in flight");
@@ -2834,16 +2899,11 @@ int mt3_debug_engine_set_eos_schedule(mt3_engine* e, const int32_t* h_lengths, i
     return MT3_OK;
   }
   if (n <= 0) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_eos_schedule: n must be positive");
-  if (n > e->eos_cap) {
-    // a schedule per SEGMENT of an mt3_engine_transcribe call: a larger array (the captured step graphs hold the old
-    // address, so they go; the old array stays in the engine's allocation list until destroy)
-    int* grown = nullptr;
-    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), static_cast<size_t>(n) * 4));
-    drop_graph(e);
-    drop_group_graphs(e);
-    e->eos_at = grown;
-    e->eos_cap = n;
-  }
+  // a schedule per SEGMENT of an mt3_engine_transcribe call: a larger array (the captured step graphs hold the old
+  // address, so they go)
+  bool stale = false;
+  MT3_TRY(grow(e, &e->eos_at, &e->eos_cap, static_cast<size_t>(n), &stale));
+  if (stale) drop_step_graphs(e);
   std::vector<int32_t> h(static_cast<size_t>(e->eos_cap), 0x7fffffff);       // rows / segments past n: never
   for (int i = 0; i < n; ++i) {
     if (h_lengths[i] < 1) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_eos_schedule: lengths must be >= 1");
@@ -2856,132 +2916,23 @@ int mt3_debug_engine_set_eos_schedule(mt3_engine* e, const int32_t* h_lengths, i
 
 int mt3_engine_set_token_masks(mt3_engine* e, const uint32_t* h_masks, int32_t n_masks, const int32_t* h_seg_mask,
                                int32_t n_segments) {
-  const char* who = "mt3_engine_set_token_masks: ";
-  if (!e) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "null engine");
-  const bool clear = !h_masks || n_masks == 0;
-  const int vocab = e->cfg.vocab_size, words = (vocab + 31) / 32;
-  std::vector<int> allowed;
-  // ---- what is wrong with the arguments themselves, then with the engine's state; nothing below touches the device before
-  if (n_masks < 0) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_masks must not be negative");
-  if (!clear) {
-    if (!h_seg_mask && n_masks > 1)
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "several masks need a per-segment index");
-    if (h_seg_mask && n_segments < 1)
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_segments must be positive with a per-segment index");
-    if (h_seg_mask)
-      for (int i = 0; i < n_segments; ++i)
-        if (h_seg_mask[i] < -1 || h_seg_mask[i] >= n_masks)
-          return mt3::fail(MT3_ERR_INVALID, std::string(who) + "mask index outside [-1, n_masks)");
-    allowed.resize(static_cast<size_t>(n_masks));
-    for (int m = 0; m < n_masks; ++m)
-      if (const char* bad = mt3k::bad_token_mask(h_masks + static_cast<size_t>(m) * words, vocab, &allowed[m]))
-        return mt3::fail(MT3_ERR_INVALID, std::string(who) + bad);
-  }
-  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "engine not finalized");
-  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "a decode is in flight");
-  if (clear) {
-    e->tm_n = 0;
-    return MT3_OK;
-  }
-  // a setup call: nothing a caller enqueued earlier may still read the masks this call replaces
-  MT3_HIP_CHECK(hipDeviceSynchronize());
-  const size_t n_words = static_cast<size_t>(n_masks) * words, n_seg = h_seg_mask ? static_cast<size_t>(n_segments) : 0;
-  // the kVarMask step graphs hold the addresses of both arrays and whether the index is in use: when a larger array or the
-  // other form replaces what they captured they go (as the EOS schedule's regrow has it; the old arrays stay in the
-  // engine's allocation list until destroy)
-  bool stale = e->tm_masks && (n_seg > 0) != e->tm_seg_on;
-  if (n_words > e->tm_mask_cap) {
-    uint32_t* grown = nullptr;
-    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_words * 4));
-    stale = stale || e->tm_masks != nullptr;
-    e->tm_masks = grown;
-    e->tm_mask_cap = n_words;
-  }
-  if (n_seg > e->tm_seg_cap) {
-    int* grown = nullptr;
-    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_seg * 4));
-    stale = stale || e->tm_seg != nullptr;
-    e->tm_seg = grown;
-    e->tm_seg_cap = n_seg;
-  }
-  if (stale) {
-    drop_graph(e);
-    drop_group_graphs(e);
-  }
-  e->tm_n = 0;                    // (a failed copy leaves the engine unconstrained, not half set)
-  MT3_HIP_CHECK(hipMemcpy(e->tm_masks, h_masks, n_words * 4, hipMemcpyHostToDevice));
-  if (n_seg) MT3_HIP_CHECK(hipMemcpy(e->tm_seg, h_seg_mask, n_seg * 4, hipMemcpyHostToDevice));
-  e->tm_seg_on = n_seg > 0;
-  e->tm_seg_host.assign(h_seg_mask, h_seg_mask + n_seg);
-  e->tm_allowed = allowed;
-  e->tm_n = n_masks;
-  return MT3_OK;
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_masks: null engine");
+  const int vocab = e->cfg.vocab_size;
+  return set_seg_table(e, e->tm, "mt3_engine_set_token_masks: ", "mask", h_masks, n_masks, (vocab + 31) / 32, nullptr,
+                       h_seg_mask, n_segments,
+                       [vocab](const uint32_t* m, int* allowed) { return mt3k::bad_token_mask(m, vocab, allowed); });
 }
 
 int mt3_engine_set_prompts(mt3_engine* e, const int32_t* h_prompts, int32_t n_prompts, int32_t stride,
                            const int32_t* h_seg_prompt, int32_t n_segments) {
-  const char* who = "mt3_engine_set_prompts: ";
-  if (!e) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "null engine");
-  const bool clear = !h_prompts || n_prompts == 0;
-  std::vector<int> len;
-  // ---- what is wrong with the arguments themselves, then with the engine's state; nothing below touches the device before
-  if (n_prompts < 0) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_prompts must not be negative");
-  if (!clear) {
-    if (stride < 1) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "stride must be at least 1");
-    if (stride >= e->cfg.max_decode_len)
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "stride must be below max_decode_len");
-    if (!h_seg_prompt && n_prompts > 1)
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "several prompts need a per-segment index");
-    if (h_seg_prompt && n_segments < 1)
-      return mt3::fail(MT3_ERR_INVALID, std::string(who) + "n_segments must be positive with a per-segment index");
-    if (h_seg_prompt)
-      for (int i = 0; i < n_segments; ++i)
-        if (h_seg_prompt[i] < -1 || h_seg_prompt[i] >= n_prompts)
-          return mt3::fail(MT3_ERR_INVALID, std::string(who) + "prompt index outside [-1, n_prompts)");
-    len.resize(static_cast<size_t>(n_prompts));
-    for (int p = 0; p < n_prompts; ++p)
-      if (const char* bad = mt3k::bad_prompt(h_prompts + static_cast<size_t>(p) * stride, stride, e->cfg.vocab_size, &len[p]))
-        return mt3::fail(MT3_ERR_INVALID, std::string(who) + bad);
-  }
-  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "engine not finalized");
-  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, std::string(who) + "a decode is in flight");
-  if (clear) {
-    e->tp_n = 0;
-    return MT3_OK;
-  }
-  // a setup call: nothing a caller enqueued earlier may still read the prompts this call replaces
-  MT3_HIP_CHECK(hipDeviceSynchronize());
-  const size_t n_ids = static_cast<size_t>(n_prompts) * stride, n_seg = h_seg_prompt ? static_cast<size_t>(n_segments) : 0;
-  // the kVarPrompt step graphs hold the addresses of both arrays, the stride and whether the index is in use: when a larger
-  // array, another stride or the other form replaces what they captured they go (as the masks' graphs do)
-  bool stale = e->tp_prompts && ((n_seg > 0) != e->tp_seg_on || stride != e->tp_stride);
-  if (n_ids > e->tp_prompt_cap) {
-    int* grown = nullptr;
-    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_ids * 4));
-    stale = stale || e->tp_prompts != nullptr;
-    e->tp_prompts = grown;
-    e->tp_prompt_cap = n_ids;
-  }
-  if (n_seg > e->tp_seg_cap) {
-    int* grown = nullptr;
-    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&grown), n_seg * 4));
-    stale = stale || e->tp_seg != nullptr;
-    e->tp_seg = grown;
-    e->tp_seg_cap = n_seg;
-  }
-  if (stale) {
-    drop_graph(e);
-    drop_group_graphs(e);
-  }
-  e->tp_n = 0;                    // (a failed copy leaves the engine unprompted, not half set)
-  MT3_HIP_CHECK(hipMemcpy(e->tp_prompts, h_prompts, n_ids * 4, hipMemcpyHostToDevice));
-  if (n_seg) MT3_HIP_CHECK(hipMemcpy(e->tp_seg, h_seg_prompt, n_seg * 4, hipMemcpyHostToDevice));
-  e->tp_seg_on = n_seg > 0;
-  e->tp_stride = stride;
-  e->tp_seg_host.assign(h_seg_prompt, h_seg_prompt + n_seg);
-  e->tp_len = len;
-  e->tp_n = n_prompts;
-  return MT3_OK;
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_prompts: null engine");
+  const int vocab = e->cfg.vocab_size;
+  const char* bad_stride = stride < 1                         ? "stride must be at least 1"
+                           : stride >= e->cfg.max_decode_len ? "stride must be below max_decode_len"
+                                                             : nullptr;
+  return set_seg_table(e, e->tp, "mt3_engine_set_prompts: ", "prompt", h_prompts, n_prompts, stride, bad_stride, h_seg_prompt,
+                       n_segments,
+                       [=](const int* p, int* len) { return mt3k::bad_prompt(p, stride, vocab, len); });
 }
 
 int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments) {
@@ -3026,8 +2977,8 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_LAST_DECODE_COMPACTIONS: return e->compactions;
     case MT3_STATUS_LAST_DECODE_FORKS: return e->h_pinned ? e->h_pinned[kForksPinned] : 0;
     case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
-    case MT3_STATUS_TOKEN_MASKS: return e->tm_n;
-    case MT3_STATUS_PROMPTS: return e->tp_n;
+    case MT3_STATUS_TOKEN_MASKS: return e->tm.n;
+    case MT3_STATUS_PROMPTS: return e->tp.n;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

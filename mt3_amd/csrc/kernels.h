@@ -134,19 +134,30 @@ struct LogitScale {
   int n_ss;
   int dim;
 };
-// Constrained decoding (mt3_engine_set_token_masks; the rule: include/mt3_hip.h): bit sets over the vocabulary, `words` =
-// ceil(vocab / 32) uint32 each, bit i % 32 of word i / 32 set = token i allowed.  The kernel that picks the token treats
-// the logit of a disallowed token as -inf (after the LogitScale multiply and its write-back: the logits in memory stay the
-// model's own).  The mask of a slot is masks + seg_mask[seg] * words, seg = the segment index the EOS schedule uses (token
-// kernel) / the element's segment (beam kernel); a negative seg or index: unconstrained.  masks == nullptr: no mask -- the
-// launchers then run the unmasked instantiations, whose statements do not mention this struct.
-struct TokenMask {
-  const uint32_t* masks;  // [n_masks][words]
-  const int* seg_mask;    // [segments] mask index per segment, -1 = unconstrained (nullptr: mask 0 for every segment);
-                          // offset like StepRetire::eos_at / by the step's first element
+// A per-segment table: fixed-stride rows in device memory and an optional index from segment to row.  The one indexing
+// contract (seg_table_row, decode_ops.hip): the row of segment `seg` is rows + seg_row[seg] * stride; a null seg_row means
+// row 0 for every segment; a negative seg or a negative index means no row.  rows == nullptr: no table -- the launchers
+// then run the instantiations whose statements do not mention it.  `seg` is the segment index the EOS schedule uses
+// (token kernel: rt.slot_seg[b] in in-flight jobs, else the row the slot decodes; its slot_seg here is unused) / the
+// element's segment (beam kernel: slot_seg[first slot], else the block).  Its two uses:
+//   TokenMask   constrained decoding (mt3_engine_set_token_masks; the rule: include/mt3_hip.h): bit sets over the
+//               vocabulary, stride = ceil(vocab / 32) uint32 each, bit i % 32 of word i / 32 set = token i allowed.  The
+//               kernel that picks the token treats the logit of a disallowed token as -inf (after the LogitScale multiply
+//               and its write-back: the logits in memory stay the model's own).  No row: unconstrained.
+//   TokenPrompt prompted decoding (mt3_engine_set_prompts; the rule: include/mt3_hip.h): forced token prefixes, `stride`
+//               ids each, padded with 0.  A slot at position t < stride whose row holds P[t] != 0 is INSIDE its prompt: the
+//               kernel that picks the token emits P[t], writes the next input row from it and leaves the search state alone
+//               (no score, no EOS candidate, no stop test, no fork).  No row: no prompt.
+template <typename T>
+struct SegTable {
+  const T* rows;          // [n_rows][stride]
+  const int* seg_row;     // [segments] row index per segment, -1 = none (nullptr: row 0 for every segment); offset like
+                          // StepRetire::eos_at / by the step's first element
   const int* slot_seg;    // beam kernel only: [slots] the segment of an element's first slot (nullptr: element = block)
-  int words;
+  int stride;             // elements of T per row
 };
+using TokenMask = SegTable<uint32_t>;
+using TokenPrompt = SegTable<int>;
 // the one host-side check of a mask of ceil(vocab / 32) words: nullptr and *allowed = its number of allowed tokens, or
 // what is wrong with it (EOS, id 1, must stay reachable; a pick needs two candidates; no bits past the vocabulary)
 inline const char* bad_token_mask(const uint32_t* h_mask, int vocab, int* allowed) {
@@ -159,19 +170,6 @@ inline const char* bad_token_mask(const uint32_t* h_mask, int vocab, int* allowe
   if (n < 2) return "a mask must allow at least 2 tokens";
   return nullptr;
 }
-// Prompted decoding (mt3_engine_set_prompts; the rule: include/mt3_hip.h): forced token prefixes, `stride` ids each, padded
-// with 0.  A slot at position t < stride whose segment's prompt holds P[t] != 0 is INSIDE its prompt: the kernel that picks
-// the token emits P[t], writes the next input row from it and leaves the search state alone (no score, no EOS candidate, no
-// stop test, no fork).  The prompt of a slot is prompts + seg_prompt[seg] * stride, seg as for TokenMask; a negative seg or
-// index: no prompt.  prompts == nullptr: none -- the launchers then run the unprompted instantiations, whose statements do
-// not mention this struct.
-struct TokenPrompt {
-  const int* prompts;     // [n_prompts][stride]
-  const int* seg_prompt;  // [segments] prompt index per segment, -1 = none (nullptr: prompt 0 for every segment); offset
-                          // like TokenMask::seg_mask
-  const int* slot_seg;    // beam kernel only: [slots] the segment of an element's first slot (nullptr: element = block)
-  int stride;
-};
 // the one host-side check of a prompt row of `stride` ids: nullptr and *len = its length (the index of the first 0, or
 // stride), or what is wrong with it (EOS, id 1, cannot be forced; 0 is padding and ends the prompt)
 inline const char* bad_prompt(const int* h_prompt, int stride, int vocab, int* len) {
@@ -241,8 +239,8 @@ struct ArgmaxStepArgs {
   LogitScale ls;
   StepRetire rt;
   int B;
-  TokenMask tm;         // masks == nullptr: unconstrained (rt.slot_seg / rt.slot_row give the segment, tm.slot_seg is unused)
-  TokenPrompt tp;       // prompts == nullptr: none (the segment as for tm; tp.slot_seg is unused)
+  TokenMask tm;         // rows == nullptr: unconstrained
+  TokenPrompt tp;       // rows == nullptr: none
 };
 int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that

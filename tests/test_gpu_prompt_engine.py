@@ -275,6 +275,38 @@ def test_clearing_restores_the_unprompted_decode():
     assert eng.status(_lib.STATUS_PROMPTS) == 0 and eng.status(_lib.STATUS_GRAPH_FALLBACKS) == 0
 
 
+def test_another_stride_or_form_within_capacity_leaves_no_stale_graph():
+    """The step graphs hold the prompts' stride and whether the index is in use: a set call that changes either without
+    growing an array (so no new address forces it) must still drop them."""
+    eng, lm = _engine("float32", B), _lm(B)
+    eng.encode(lm)
+
+    def graph_equals_direct_and_rows_begin_with(prompts):
+        got = eng.decode(num_steps=S).clone()
+        assert eng.status(_lib.STATUS_LAST_DECODE_USED_GRAPH) == 1
+        assert torch.equal(eng.decode(num_steps=S, use_graph=False), got)
+        assert eng.status(_lib.STATUS_LAST_DECODE_USED_GRAPH) == 0
+        g = got.cpu().numpy()
+        for b in range(B):
+            assert list(g[b, :len(prompts[b])]) == prompts[b], b
+
+    try:
+        wide = _random_prompts(B, [8, 3, 5, 1], seed=11)                      # stride 8, an index
+        eng.set_prompts(wide, list(range(B)))
+        graph_equals_direct_and_rows_begin_with(wide)
+        narrow = _random_prompts(B, [4, 2, 1, 3], seed=12)                    # stride 4: fits the same arrays
+        eng.set_prompts(narrow, list(range(B)))
+        assert eng.status(_lib.STATUS_PROMPTS) == B
+        graph_equals_direct_and_rows_begin_with(narrow)
+        one = _random_prompts(1, [4], seed=13)                                # the same stride, no index
+        eng.set_prompts(one)
+        assert eng.status(_lib.STATUS_PROMPTS) == 1
+        graph_equals_direct_and_rows_begin_with(one * B)
+    finally:
+        eng.set_prompts(None)
+    assert eng.status(_lib.STATUS_GRAPH_FALLBACKS) == 0
+
+
 def test_masks_and_prompts_together():
     eng, lm = _engine("float32", B), _lm(B)
     eng.encode(lm)

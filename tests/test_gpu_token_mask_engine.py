@@ -231,6 +231,32 @@ def test_set_grow_clear_with_graphs_and_refusals():
     assert torch.equal(eng.decode(num_steps=S), first)
 
 
+def test_one_mask_after_indexed_masks_leaves_no_stale_graph():
+    """The step graphs hold whether the per-segment index is in use: a single mask without an index fits the arrays three
+    indexed masks left, so no new address forces the drop -- the change of form must."""
+    eng, lm = _engine("float32", 8), _lm(8)
+    eng.encode(lm)
+    first = eng.decode(num_steps=S)
+    em = _emitted(first, 6)
+    assert len(em) >= 3
+    seg = np.array([2, 1, 0, -1, 2, 1, 0, -1], np.int32)
+    try:
+        eng.set_token_masks(np.stack([_mask(em[:2]), _mask(em[2:4]), _mask(em[4:6])]), seg)
+        eng.decode(num_steps=S)
+        assert eng.status(_lib.STATUS_LAST_DECODE_USED_GRAPH) == 1
+        one = _mask(em)                                      # forbids what every row emitted, the unindexed rows included
+        eng.set_token_masks(one)
+        assert eng.status(_lib.STATUS_TOKEN_MASKS) == 1
+        got = eng.decode(num_steps=S).clone()
+        assert eng.status(_lib.STATUS_LAST_DECODE_USED_GRAPH) == 1
+        assert torch.equal(eng.decode(num_steps=S, use_graph=False), got)
+        assert eng.status(_lib.STATUS_LAST_DECODE_USED_GRAPH) == 0
+        assert _allowed(one)[got.cpu().numpy()[:, :S]].all()
+    finally:
+        eng.clear_token_masks()
+    assert eng.status(_lib.STATUS_GRAPH_FALLBACKS) == 0
+
+
 def test_forced_decode_and_scoring_ignore_masks():
     eng, lm = _engine("float32", 8), _lm(8)
     eng.encode(lm)
