@@ -474,6 +474,91 @@ int mt3_engine_set_token_masks(mt3_engine* e, const uint32_t* h_masks /* [n_mask
 int mt3_engine_set_prompts(mt3_engine* e, const int32_t* h_prompts /* [n_prompts][stride], 0-padded */, int32_t n_prompts,
                            int32_t stride, const int32_t* h_seg_prompt /* [n_segments] or NULL */, int32_t n_segments);
 
+/* Well-formed decoding: the event grammar of MT3's output in the token kernels.  The masks and prompts above are static per
+ * segment; this rule depends on what the slot has emitted.  It keeps the search off the continuations the note decoder
+ * (mt3_notes_decode; run_length_encoding.decode_events with note_sequences.decode_note_event) throws away: a shift that
+ * runs backwards ("event time < current time", an invalid event), a shift past the segment's end (every remaining token
+ * dropped), a `tie` outside the tie section, anything but program / pitch / tie inside it.
+ *   grammar  mt3_token_grammar, vocabulary ids (token id = 3 + event index): the shift of value v is shift_first + v,
+ *            v < shift_count; max_steps the largest shift a free pick may take; tie_id; the program and pitch id ranges;
+ *            with_ties: segments open with a tie section (MT3_SPEC_TIES).  mt3_codec_token_grammar fills it from a codec.
+ *   state    one int32 per slot: bit 31 = inside the tie section, bit 30 = the previous token was a shift, bits 0 .. 29 =
+ *            t, the time of the last shift in steps.  A slot starts at {with_ties, 0, 0} at position 0: at the start of a
+ *            decode and at every refill (mt3g_initial).
+ *   advance  applied to EVERY emitted token, free or forced by a prompt (mt3g_advance): a shift of value v sets
+ *            t = prev_shift ? min(t + v, 2^29) : v and prev_shift = 1 (what decode_events does with cur_steps); tie_id
+ *            clears the tie-section bit and prev_shift; any other id clears prev_shift.  A slot that has finished keeps the
+ *            state its last token left.
+ *   allowed  applies to a FREE pick only (mt3g_allowed).  EOS (id 1) is always allowed.  Inside the tie section an id
+ *            is allowed iff it is a program id, a pitch id or tie_id.  After it tie_id is not allowed, a shift id of value v
+ *            is allowed iff !prev_shift && t <= v <= max_steps, and every other id is allowed (pads, extra ids and the other
+ *            event types are the mask's business).
+ *   rule     a disallowed id is what a masked id is: -inf wherever the token rule reads the logit -- never picked, never
+ *            one of the beam-1 top 2 or the k-beam top 2k, exactly 0 in the log-sum-exp; applied after the row scale and
+ *            its write-back, so the logits handed back stay the model's own.  With a token mask set as well the allowed
+ *            set is the intersection.
+ *   prompts  win inside the prompt, as they win over masks; the state still advances through the forced tokens, so a
+ *            tie-section prompt leaves the slot behind the section (and two forced shifts in a row add up).
+ *   EOS      the synthetic EOS schedule still wins.
+ *   beam-1   the state follows the live hypothesis.
+ *   k-beam   the state of new slot j is advance(state[parent_j], tok_j): all k parent states are read before any is written
+ *            (one block owns an element); finished candidates carry no state.
+ * mt3_engine_set_token_grammar is a synchronous setup call like mt3_engine_set_token_masks, global to the engine (not per
+ * segment); g == NULL clears.  The grammar stays set for every later mt3_engine_decode / _decode_beams / _transcribe /
+ * _transcribe_beams until cleared; steps with a grammar never share a captured graph with steps without one, and a decode
+ * without one runs the kernels, graphs and bits it ran before the grammar existed.  mt3_engine_decode_forced,
+ * mt3_engine_score and mt3_engine_score_segments IGNORE the grammar, as they ignore masks.  MT3_STATUS_TOKEN_GRAMMAR
+ * reports 0 / 1.
+ * MT3_ERR_INVALID, before any device work: a range outside [3, vocab) or empty; overlapping ranges (tie_id counts as a
+ * range of one); max_steps outside [1, shift_count - 1]; an engine that is not finalized; a decode in flight.
+ * The decode / transcribe calls return MT3_ERR_INVALID before any device work for a token mask in use whose intersection
+ * with the grammar leaves fewer than 2 (the beam calls: 2 * num_beams) allowed ids in the tie-section state or in the worst
+ * state after it (no shift, no tie). */
+typedef struct mt3_token_grammar {
+  int32_t shift_first, shift_count, max_steps, tie_id, program_first, program_count, pitch_first, pitch_count, with_ties;
+} mt3_token_grammar;
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MT3_RULE_FN static __host__ __device__ __inline__
+#else
+#define MT3_RULE_FN static inline
+#endif
+#define MT3_GRAMMAR_TIE_SECTION 0x80000000u
+#define MT3_GRAMMAR_PREV_SHIFT 0x40000000u
+#define MT3_GRAMMAR_TIME 0x3fffffffu
+MT3_RULE_FN int32_t mt3g_initial(const mt3_token_grammar* g) {
+  return (int32_t)(g->with_ties ? MT3_GRAMMAR_TIE_SECTION : 0u);
+}
+MT3_RULE_FN int32_t mt3g_advance(const mt3_token_grammar* g, int32_t state, int32_t tok) {
+  const uint32_t s = (uint32_t)state, v = (uint32_t)(tok - g->shift_first);
+  if (v < (uint32_t)g->shift_count) {
+    uint32_t t = v;
+    if (s & MT3_GRAMMAR_PREV_SHIFT) {
+      t = (s & MT3_GRAMMAR_TIME) + v;
+      if (t > (1u << 29)) t = 1u << 29;
+    }
+    return (int32_t)((s & MT3_GRAMMAR_TIE_SECTION) | MT3_GRAMMAR_PREV_SHIFT | t);
+  }
+  if (tok == g->tie_id) return (int32_t)(s & MT3_GRAMMAR_TIME);
+  return (int32_t)(s & ~MT3_GRAMMAR_PREV_SHIFT);
+}
+MT3_RULE_FN int mt3g_allowed(const mt3_token_grammar* g, int32_t state, int32_t id) {
+  const uint32_t s = (uint32_t)state, v = (uint32_t)(id - g->shift_first);
+  if (id == 1) return 1;
+  if (s & MT3_GRAMMAR_TIE_SECTION)
+    return id == g->tie_id || (uint32_t)(id - g->program_first) < (uint32_t)g->program_count ||
+           (uint32_t)(id - g->pitch_first) < (uint32_t)g->pitch_count;
+  if (id == g->tie_id) return 0;
+  if (v < (uint32_t)g->shift_count)
+    return !(s & MT3_GRAMMAR_PREV_SHIFT) && v >= (s & MT3_GRAMMAR_TIME) && v <= (uint32_t)g->max_steps;
+  return 1;
+}
+/* the three inline functions above (mt3g_*: the one statement of the rule, compiled into the token kernels and the host
+ * checks alike) as exported symbols, for bindings that cannot read the header's inline functions */
+int32_t mt3_token_grammar_initial(const mt3_token_grammar* g);
+int32_t mt3_token_grammar_advance(const mt3_token_grammar* g, int32_t state, int32_t tok);
+int32_t mt3_token_grammar_allowed(const mt3_token_grammar* g, int32_t state, int32_t id);
+int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g /* NULL clears */);
+
 /* Teacher-forced cached decode: Transformer.decode (mt3/network.py:303-361) on GIVEN decoder inputs, driven one
  * token per call through the same cached step (layers.py:246-314) the autoregressive loop uses -- the input of
  * step 0 is BOS, the input of step t+1 is d_forced_ids[b][t] (i.e. decoder_input_tokens = shift_right(forced),
@@ -573,7 +658,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_LAST_DECODE_FORKS = 10 /* cache-row copies of the most recent mt3_engine_decode_beams / mt3_engine_transcribe_beams */,
        MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score / mt3_engine_score_segments (all its encoder chunks) */,
        MT3_STATUS_TOKEN_MASKS = 12 /* masks set by mt3_engine_set_token_masks (0: none) */,
-       MT3_STATUS_PROMPTS = 13 /* prompts set by mt3_engine_set_prompts (0: none) */ };
+       MT3_STATUS_PROMPTS = 13 /* prompts set by mt3_engine_set_prompts (0: none) */,
+       MT3_STATUS_TOKEN_GRAMMAR = 14 /* 1: a grammar is set by mt3_engine_set_token_grammar (0: none) */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -765,6 +851,24 @@ int mt3_op_token_steps_prompted(float* d_logits, const float* d_ss, int32_t n_ss
                                 int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
                                 void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
                                 const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt);
+/* The two prompted drivers with the event grammar (mt3_engine_set_token_grammar states the rule): h_grammar is a HOST
+ * descriptor, checked first as mt3_engine_set_token_grammar checks it (MT3_ERR_INVALID; and for a mask whose intersection
+ * with the grammar leaves fewer than 2 / 2k ids in the tie-section state or the worst state after it); NULL: no grammar --
+ * the call is then the _prompted driver, bit for bit.  h_state (HOST, [num_steps][rows] for the token kernel,
+ * [num_steps][elems * k] for the beam kernel, may be NULL) receives the packed grammar state of every slot after each
+ * step (rows of steps that did not run stay untouched). */
+int mt3_op_beam_search_grammar(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                               int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                               const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
+                               float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks, int32_t* h_steps_run,
+                               void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                               const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                               const mt3_token_grammar* h_grammar, int32_t* h_state);
+int mt3_op_token_steps_grammar(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
+                               int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
+                               void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                               const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                               const mt3_token_grammar* h_grammar, int32_t* h_state);
 /* The fork copies of one k-beam step on caller-owned caches: for every slot with d_fork_src[slot] >= 0 and
  * d_done[slot] == 0, positions [0, d_step[slot]) of row d_fork_src[slot] are copied into row d_slot_row[slot] of every
  * layer's K and V cache [rows][H][cap][64] of kv_esize-byte elements (1, 2 or 4) and, where given, of its scale pairs
@@ -1011,6 +1115,13 @@ int mt3_codec_encode_event(const mt3_codec* c, int32_t type, int32_t value, int3
  * a program range, vocab < 3 or null pointers. */
 int mt3_codec_token_mask(const mt3_codec* c, int32_t vocab, const int32_t* programs, int32_t n_programs,
                          int32_t allow_drums, uint32_t* h_mask);
+/* The event grammar of a codec (mt3_engine_set_token_grammar): the id ranges of the codec's shift, pitch and program
+ * events and of its tie event (token id = 3 + event index), with_ties = (spec == MT3_SPEC_TIES), and max_steps, the largest
+ * shift a free pick may take -- the segment's length in steps: floor(input_length * hop_width / sample_rate *
+ * steps_per_second), 204 for `mt3` and 409 for `ismir2021`.  MT3_ERR_INVALID: null pointers, a malformed codec or one
+ * without a pitch, tie or program range, max_steps < 1, max_steps above the codec's largest shift (a canonical stream
+ * then needs two shifts in a row, which the rule forbids), or ranges that do not fit below vocab. */
+int mt3_codec_token_grammar(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t max_steps, mt3_token_grammar* out);
 /* tokens: concatenated per-segment token rows (already trimmed at EOS); seg_offsets [n_segments+1];
  * h_has_max_time==NULL -> the combiner rule (max_time = next segment's start, none for the last);
  * otherwise explicit per-segment max_time (decode_events' own argument). */

@@ -26,7 +26,7 @@ DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
  STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS, STATUS_TOKEN_MASKS,
- STATUS_PROMPTS) = range(14)
+ STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR) = range(15)
 (MT3_PCM_U8, MT3_PCM_S16, MT3_PCM_S24, MT3_PCM_S32, MT3_PCM_F32, MT3_PCM_F64) = range(6)     # mt3_pcm_decode formats
 PCM_MAX_CHANNELS = 7
 MAX_BEAMS = 8                                  # mt3_engine_decode_beams: 1 <= num_beams <= 8
@@ -64,6 +64,11 @@ class EventRange(C.Structure):
 
 class CodecDesc(C.Structure):
     _fields_ = [("steps_per_second", C.c_double), ("num_ranges", C.c_int32), ("ranges", EventRange * 8)]
+
+
+class TokenGrammar(C.Structure):               # mt3_token_grammar
+    _fields_ = [(n, C.c_int32) for n in ("shift_first", "shift_count", "max_steps", "tie_id", "program_first",
+                                         "program_count", "pitch_first", "pitch_count", "with_ties")]
 
 
 class NoteStruct(C.Structure):
@@ -150,6 +155,10 @@ SIGNATURES = {
     "mt3_engine_score_segments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_set_token_masks": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     "mt3_engine_set_prompts": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "mt3_engine_set_token_grammar": (C.c_int, [_P, C.POINTER(TokenGrammar)]),
+    "mt3_token_grammar_initial": (C.c_int32, [C.POINTER(TokenGrammar)]),
+    "mt3_token_grammar_advance": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
+    "mt3_token_grammar_allowed": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
     "mt3_engine_status": (C.c_int, [_P, C.c_int32]),
     "mt3_debug_engine_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mt3_debug_engine_transcribe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
@@ -199,6 +208,13 @@ SIGNATURES = {
                                               _P, C.c_int32, _P]),
     "mt3_op_token_steps_prompted": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
+    "mt3_op_beam_search_grammar": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
+                                             _P, C.c_int32, _P, C.POINTER(TokenGrammar), _P]),
+    "mt3_op_token_steps_grammar": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
+                                             C.POINTER(TokenGrammar), _P]),
     "mt3_op_beam_reorder": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P),
                                       C.POINTER(_P), _P, _P, _P, _P, _P]),
     "mt3_op_embed_rows": (C.c_int, [C.POINTER(InputRowView), _P, _P, C.c_int32, _P]),
@@ -218,6 +234,8 @@ SIGNATURES = {
     "mt3_codec_decode_event": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mt3_codec_encode_event": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "mt3_codec_token_mask": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    "mt3_codec_token_grammar": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(TokenGrammar)]),
     "mt3_notes_decode": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64,
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_double)]),

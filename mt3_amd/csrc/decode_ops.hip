@@ -15,7 +15,9 @@
 //                       beam_reorder_kernel (K/V copies of forked rows) and beam_finalize_kernel (history backtrack).
 //                       Both token kernels read up to two per-segment tables (SegTable in kernels.h): the MASKED
 //                       instantiations count the logit of a token the slot's mask row disallows as -inf, the PROMPT
-//                       instantiations emit the prompt row's token while the slot is inside it.
+//                       instantiations emit the prompt row's token while the slot is inside it.  The GRAMMAR
+//                       instantiations (TokenGrammar in kernels.h) keep one packed state per slot and count the ids the
+//                       event grammar disallows in that state as -inf as well.
 //   ids_to_tokens_kernel GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271), bit-exact.
 #include <hip/hip_runtime.h>
 
@@ -204,9 +206,12 @@ __device__ __forceinline__ const T* seg_table_row(const SegTable<T>& tb, int seg
 constexpr float kMaskedLogit = -__builtin_inff();
 __device__ __forceinline__ bool mask_allows(uint32_t word, int i) { return (word >> (i & 31)) & 1u; }
 // row[i] as the token rule reads it in the loops that walk the row in memory (vocab > 2048)
-template <bool MASKED>
-__device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mrow, int i) {
+// (GRAMMAR: also -inf where the event grammar `g` disallows id i in the slot's state `gs`)
+template <bool MASKED, bool GRAMMAR = false>
+__device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mrow, int i,
+                                            const mt3_token_grammar* g = nullptr, int gs = 0) {
   if (MASKED && mrow && !mask_allows(mrow[i >> 5], i)) return kMaskedLogit;
+  if (GRAMMAR && !mt3g_allowed(g, gs, i)) return kMaskedLogit;
   return row[i];
 }
 
@@ -235,7 +240,12 @@ __device__ __forceinline__ int prompt_token(const TokenPrompt& tp, int seg, int 
 //   beam-1 state (live log-prob, finished score and length) is left alone and the stop test is not evaluated, so the slot
 //   never finishes there but by max_len.  The branch is block-uniform.  PROMPT = false compiles from the statements the
 //   kernel had before prompts existed.
-template <bool BEAM1, bool MASKED, bool PROMPT>
+// GRAMMAR = true: the pick of every slot is restricted to the ids the event grammar a.gr allows in the slot's state
+//   st.gram[b] (the intersection with the mask; where the mask is applied), and the state is advanced by the token the slot
+//   emits, free, forced by the prompt or by the EOS schedule.  A fourth flag, but only on the <MASKED, PROMPT> forms: a
+//   grammar step without masks or prompts passes empty tables (no mask row: no word is loaded; stride 0: no prompt token).
+//   GRAMMAR = false compiles from the statements the kernel had before the grammar existed.
+template <bool BEAM1, bool MASKED, bool PROMPT, bool GRAMMAR = false>
 __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   const SlotState& st = a.st;
   const StepRetire& rt = a.rt;
@@ -283,6 +293,10 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   // prompt); only thread 0 reads it
   int ptok = 0;
   if (PROMPT) ptok = prompt_token(a.tp, slot_segment(rt.slot_seg, b, out_row), st.step[b]);
+  // GRAMMAR: the slot's packed state, one dword per block whose address needs nothing but the block index: requested in the
+  // same batch, waited for only where the ids are tested below
+  int gs = 0;
+  if (GRAMMAR) gs = st.gram[b];
   // thread 0 issues its state loads up front so that their latency hides behind the reductions
   int was_done = 0, t = 0, blen = -1, eos_len = 0x7fffffff;
   float live = 0.f, best = 0.f, bp_max = 1.f, bp_t = 1.f;
@@ -327,6 +341,11 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
     for (int u = 0; u < kPer; ++u)
       if (!mask_allows(mw[u], tid)) xv[u] = kMaskedLogit;      // (i & 31 == tid & 31: i = tid + 256 u)
   }
+  if (GRAMMAR && in_regs) {                // a handful of integer compares on the id each thread already knows
+#pragma unroll
+    for (int u = 0; u < kPer; ++u)
+      if (!mt3g_allowed(&a.gr.g, gs, tid + u * 256)) xv[u] = kMaskedLogit;
+  }
   Top2 t2{-3.0e38f, -3.0e38f, 0x7fffffff, 0x7fffffff};
   float acc = 0.f;
   if (in_regs) {
@@ -342,9 +361,10 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
         if (tid + u * 256 < vocab) acc += __expf(xv[u] - t2.v1);
     }
   } else {
-    for (int i = tid; i < vocab; i += 256) t2.insert(rule_logit<MASKED>(row, mrow, i), i);   // ascending i per thread
+    for (int i = tid; i < vocab; i += 256)                                                   // ascending i per thread
+      t2.insert(rule_logit<MASKED, GRAMMAR>(row, mrow, i, &a.gr.g, gs), i);
     if (BEAM1) {
-      for (int i = tid; i < vocab; i += 256) acc += __expf(rule_logit<MASKED>(row, mrow, i) - t2.v1);
+      for (int i = tid; i < vocab; i += 256) acc += __expf(rule_logit<MASKED, GRAMMAR>(row, mrow, i, &a.gr.g, gs) - t2.v1);
     }
   }
   const float own_max = t2.v1;
@@ -423,6 +443,7 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
       atomicAdd(st.n_done, 1);
     }
     a.ids[static_cast<size_t>(out_row) * a.ids_stride + t] = tok;
+    if (GRAMMAR && !was_done) st.gram[b] = mt3g_advance(&a.gr.g, gs, tok);   // a finished slot keeps its last state
     // teacher forcing (Transformer.decode on given decoder_input_tokens, network.py:303-361): the NEXT input is
     // the caller's token for position t + 1, whatever this step predicted
     if (!BEAM1 && a.forced) tok = a.forced[static_cast<size_t>(b) * a.forced_stride + t];
@@ -449,8 +470,13 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: token masks are ceil(vocab / 32) words and not for teacher forcing");
   if (a.tp.rows && (a.forced || a.tp.stride < 1))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: prompts have a stride of at least 1 and are not for teacher forcing");
+  if (a.gr.on && (a.forced || !a.st.gram || bad_token_grammar(a.gr.g, a.vocab)))
+    return mt3::fail(MT3_ERR_INVALID, "argmax_step: the grammar needs the slots' states and valid ranges and is not for "
+                                      "teacher forcing");
   void (*kernel)(ArgmaxStepArgs);
-  if (a.tp.rows) {
+  if (a.gr.on) {
+    kernel = a.beam.f ? argmax_step_kernel<true, true, true, true> : argmax_step_kernel<false, true, true, true>;
+  } else if (a.tp.rows) {
     if (a.tm.rows) kernel = a.beam.f ? argmax_step_kernel<true, true, true> : argmax_step_kernel<false, true, true>;
     else kernel = a.beam.f ? argmax_step_kernel<true, false, true> : argmax_step_kernel<false, false, true>;
   } else {
@@ -511,20 +537,22 @@ __global__ __launch_bounds__(128) void compact_move_kernel(CompactArgs c) {
       reinterpret_cast<float4*>(qo + dst * q_n)[k] = reinterpret_cast<const float4*>(q + src * q_n)[k];
   if (tid == 0) {
     if (GATHER) {
-      c.s_int[4 * dst + 0] = c.st.slot_row[src];
-      c.s_int[4 * dst + 1] = c.st.step[src];
-      c.s_int[4 * dst + 2] = c.st.cur_tok[src];
-      c.s_int[4 * dst + 3] = c.beam.len ? c.beam.len[src] : 0;
+      c.s_int[kCompactInts * dst + 0] = c.st.slot_row[src];
+      c.s_int[kCompactInts * dst + 1] = c.st.step[src];
+      c.s_int[kCompactInts * dst + 2] = c.st.cur_tok[src];
+      c.s_int[kCompactInts * dst + 3] = c.beam.len ? c.beam.len[src] : 0;
+      c.s_int[kCompactInts * dst + 4] = c.st.gram ? c.st.gram[src] : 0;
       if (c.st.slot_seg) c.s_seg[dst] = c.st.slot_seg[src];
       if (c.beam.f) {
         c.s_beam[2 * dst + 0] = c.beam.f[src];
         c.s_beam[2 * dst + 1] = c.beam.f[c.beam.rows + src];
       }
     } else {
-      c.st.slot_row[dst] = c.s_int[4 * dst + 0];
-      c.st.step[dst] = c.s_int[4 * dst + 1];
-      c.st.cur_tok[dst] = c.s_int[4 * dst + 2];
-      if (c.beam.len) c.beam.len[dst] = c.s_int[4 * dst + 3];
+      c.st.slot_row[dst] = c.s_int[kCompactInts * dst + 0];
+      c.st.step[dst] = c.s_int[kCompactInts * dst + 1];
+      c.st.cur_tok[dst] = c.s_int[kCompactInts * dst + 2];
+      if (c.beam.len) c.beam.len[dst] = c.s_int[kCompactInts * dst + 3];
+      if (c.st.gram) c.st.gram[dst] = c.s_int[kCompactInts * dst + 4];
       if (c.st.slot_seg) c.st.slot_seg[dst] = c.s_seg[dst];
       if (c.beam.f) {
         c.beam.f[dst] = c.s_beam[2 * dst + 0];
@@ -632,6 +660,7 @@ __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
       a.st.step[slot] = 0;
       a.st.cur_tok[slot] = 0;                                       // BOS
       a.st.done[slot] = 0;
+      if (a.st.gram) a.st.gram[slot] = a.gram0;
       if (a.beam.f) {                                            // t5x beam_search: live log-prob 0, nothing finished
         a.beam.f[slot] = 0.f;
         a.beam.f[a.beam.rows + slot] = 0.f;
@@ -695,13 +724,20 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
 // beam its own parent in the history), the retirement test is skipped, and each wave writes its slot's next input row
 // from P[t].  The branch is element-uniform.  live stays [0, NEG_INF, ...], so the first free step expands beam 0 only,
 // as step 0 does without a prompt, and the k cache rows hold the same K/V for the prompt's positions.
-template <bool MASKED, bool PROMPT>
-__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls, TokenMask tm, TokenPrompt tp) {
+// GRAMMAR = true: each beam's logits are restricted to the ids the event grammar allows in ITS slot's state (st.gram,
+// requested in the batch of the logits; where the mask is applied), and new slot j gets advance(state[parent_j], tok_j):
+// every wave leaves its state in LDS before the barrier the merge waits at, so all k parent states are read before lane 0
+// writes any.  Inside a prompt slot j advances its own state by P[t].  As in the token kernel the flag exists on the
+// <MASKED, PROMPT> form only, with empty tables where there are no masks or prompts.
+template <bool MASKED, bool PROMPT, bool GRAMMAR = false>
+__global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls, TokenMask tm, TokenPrompt tp,
+                                                                    TokenGrammar gr) {
   constexpr int kPerLane = 32;                         // vocab <= 2048: lane l holds i = l + 64 * vt + 256 * u
   __shared__ float c_score[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int c_tok[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int s_sel[2 * kBeamMaxK];
   __shared__ int s_tok[kBeamMaxK];
+  __shared__ int s_gs[kBeamMaxK];                         // GRAMMAR: the state of each beam's slot before this step
   const int k = a.k, k2 = 2 * k, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int s0 = blockIdx.x * k, slot = s0 + w;
   if (a.st.done[s0]) return;                              // retired element: its state is final
@@ -723,6 +759,11 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
       mw[j] = mrow ? mrow[(i < a.vocab ? i : a.vocab - 1) >> 5] : 0xffffffffu;
     }
   }
+  int gs = 0;
+  if (GRAMMAR) {                  // this beam's packed state: one dword per wave, requested in the same batch
+    gs = a.st.gram[slot];
+    if (lane == 0) s_gs[w] = gs;
+  }
   if (PROMPT) {
     // the element's prompt token at its own position, requested in the same batch as the logits (0: not inside a prompt)
     const int ptok = prompt_token(tp, slot_segment(tp.slot_seg, s0, blockIdx.x), t);
@@ -737,6 +778,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
           a.hist_tok[static_cast<size_t>(t) * a.hist_stride + s0 + j] = ptok;
           a.st.cur_tok[s0 + j] = ptok;
           a.st.step[s0 + j] = t + 1;
+          if (GRAMMAR) a.st.gram[s0 + j] = mt3g_advance(&gr.g, s_gs[j], ptok);
           if (closed) a.st.done[s0 + j] = 1;
         }
         if (closed) atomicAdd(a.st.n_done, k);
@@ -758,6 +800,11 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
 #pragma unroll
     for (int j = 0; j < kPerLane; ++j)
       if (!mask_allows(mw[j], lane)) xv[j] = kMaskedLogit;     // (i & 31 == lane & 31: i = lane + a multiple of 64)
+  }
+  if (GRAMMAR) {
+#pragma unroll
+    for (int j = 0; j < kPerLane; ++j)
+      if (!mt3g_allowed(&gr.g, gs, lane + 64 * (j >> 3) + 256 * (j & 7))) xv[j] = kMaskedLogit;
   }
   // log-sum-exp of the row, in argmax_step_kernel<true>'s order: per thread, per wave, then over the four waves
   float vmax[4], vsum[4];
@@ -939,6 +986,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
         a.live[s0 + j] = nl_score[j];
         a.st.cur_tok[s0 + j] = s_tok[j];
         a.st.step[s0 + j] = t + 1;
+        if (GRAMMAR) a.st.gram[s0 + j] = mt3g_advance(&gr.g, s_gs[p], s_tok[j]);
         if (closed) a.st.done[s0 + j] = 1;
       }
       if (forks && !closed) atomicAdd(a.fork_count, forks);    // a closed element's forks are never copied
@@ -950,7 +998,8 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
   if (a.in.y) put_input_row(a.in, slot, s_tok[w], t + 1, lane, 64);
 }
 
-int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp, hipStream_t s) {
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp,
+                     const TokenGrammar& gr, hipStream_t s) {
   if (a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || a.vocab < 2 * a.k || a.vocab > 2048)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: k must be 1 .. 8 and 2k <= vocab <= 2048");
   if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.st.slot_row ||
@@ -963,10 +1012,13 @@ int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& 
   if (tm.rows && tm.stride != (a.vocab + 31) / 32)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: token masks are ceil(vocab / 32) words");
   if (tp.rows && tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "beam_step: prompts have a stride of at least 1");
-  void (*kernel)(BeamKArgs, LogitScale, TokenMask, TokenPrompt);
-  if (tp.rows) kernel = tm.rows ? beam_step_kernel<true, true> : beam_step_kernel<false, true>;
+  if (gr.on && (!a.st.gram || bad_token_grammar(gr.g, a.vocab)))
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: the grammar needs the slots' states and valid ranges");
+  void (*kernel)(BeamKArgs, LogitScale, TokenMask, TokenPrompt, TokenGrammar);
+  if (gr.on) kernel = beam_step_kernel<true, true, true>;
+  else if (tp.rows) kernel = tm.rows ? beam_step_kernel<true, true> : beam_step_kernel<false, true>;
   else kernel = tm.rows ? beam_step_kernel<true, false> : beam_step_kernel<false, false>;
-  hipLaunchKernelGGL(kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls, tm, tp);
+  hipLaunchKernelGGL(kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls, tm, tp, gr);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -1139,6 +1191,7 @@ __global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a)
       a.b.st.step[slot] = 0;
       a.b.st.cur_tok[slot] = 0;                               // BOS
       a.b.st.done[slot] = 0;
+      if (a.b.st.gram) a.b.st.gram[slot] = a.gram0;
     }
   }
   if (!restart) return;
@@ -1362,16 +1415,37 @@ int driver_prompts(const std::string& who, const int32_t* d_prompts, int stride,
   return MT3_OK;
 }
 
+// the grammar of a grammar driver, checked on the host as mt3_engine_set_token_grammar and the decode calls check it: a
+// valid descriptor, and under every mask (d_masks == nullptr: none) at least `need` ids in the two bounding states
+int driver_grammar(const std::string& who, const mt3_token_grammar* h_grammar, const uint32_t* d_masks, int n_masks,
+                   int vocab, int need, mt3k::TokenGrammar* gr) {
+  if (const char* bad = mt3k::bad_token_grammar(*h_grammar, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  const int words = (vocab + 31) / 32;
+  std::vector<uint32_t> h(d_masks ? static_cast<size_t>(n_masks) * words : 0);
+  if (!h.empty()) MT3_HIP_CHECK(hipMemcpy(h.data(), d_masks, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int m = 0; m < (d_masks ? n_masks : 1); ++m) {
+    int in_tie = 0, after = 0;
+    mt3k::grammar_room(*h_grammar, d_masks ? h.data() + static_cast<size_t>(m) * words : nullptr, vocab, &in_tie, &after);
+    if ((h_grammar->with_ties && in_tie < need) || after < need)
+      return mt3::fail(MT3_ERR_INVALID, who + ": the grammar (with a mask) leaves fewer than 2 * k ids in a state");
+  }
+  gr->g = *h_grammar;
+  gr->on = 1;
+  return MT3_OK;
+}
+
 }  // namespace
 
-// shared body of mt3_op_beam_search_scripted (masked == false), mt3_op_beam_search_masked and mt3_op_beam_search_prompted
+// shared body of mt3_op_beam_search_scripted (masked == false), mt3_op_beam_search_masked, mt3_op_beam_search_prompted and
+// mt3_op_beam_search_grammar
 static int beam_search_driver(const std::string& who, bool masked, const float* d_logits, const float* d_ss, int32_t n_ss,
                               int32_t dim, int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
                               const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids,
                               float* d_scores, float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks,
                               int32_t* h_steps_run, void* stream, const uint32_t* d_masks, int32_t n_masks,
                               const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
-                              const int32_t* d_row_prompt = nullptr) {
+                              const int32_t* d_row_prompt = nullptr, const mt3_token_grammar* h_grammar = nullptr,
+                              int32_t* h_state = nullptr) {
   if (!d_logits || !d_ids || !d_all_ids || !d_scores || !h_trace || !h_live || !h_forks || !h_steps_run)
     return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if (k < 1 || k > mt3k::kBeamMaxK || vocab < 2 * k || vocab > 2048)
@@ -1381,15 +1455,19 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   if ((d_table != nullptr) != (d_pos != nullptr) || (d_table != nullptr) != (d_y_next != nullptr) ||
       (d_table && (dim_e <= 0 || dim_e % 16)))
     return mt3::fail(MT3_ERR_INVALID, who + ": the tables and the next-row output come together, dim_e % 16 == 0");
+  if (h_grammar)                                  // the descriptor itself: before anything is read back from the device
+    if (const char* bad = mt3k::bad_token_grammar(*h_grammar, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
   mt3k::TokenMask tm{};
   if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, elems, vocab, 2 * k, &tm));
   mt3k::TokenPrompt tp{};
   if (d_prompts) MT3_OP_TRY(driver_prompts(who, d_prompts, stride, d_row_prompt, elems, vocab, &tp));
+  mt3k::TokenGrammar gr{};
+  if (h_grammar) MT3_OP_TRY(driver_grammar(who, h_grammar, masked ? d_masks : nullptr, n_masks, vocab, 2 * k, &gr));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int slots = elems * k;
   const size_t n = static_cast<size_t>(slots), hist = static_cast<size_t>(num_steps) * n;
   Scratch m;
-  MT3_OP_TRY(m.alloc(9 * Scratch::piece(n * 4) + 2 * Scratch::piece(hist * 4) + 2 * Scratch::piece(4) +
+  MT3_OP_TRY(m.alloc(10 * Scratch::piece(n * 4) + 2 * Scratch::piece(hist * 4) + 2 * Scratch::piece(4) +
                          Scratch::piece((static_cast<size_t>(num_steps) + 3) * 4),
                      s));
   mt3k::BeamKArgs b{};
@@ -1408,6 +1486,7 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   b.st.done = m.take<int>(n);
   b.st.step = m.take<int>(n);
   b.st.cur_tok = m.take<int>(n);
+  if (gr.on) b.st.gram = m.take<int>(n);
   b.fork_count = m.take<int>(1);
   b.st.n_done = m.take<int>(1);
   float* d_bp = m.take<float>(static_cast<size_t>(num_steps) + 3);
@@ -1419,6 +1498,7 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   b.in.dim = dim_e;
   b.max_len = max_len;
   MT3_HIP_CHECK(hipMemsetAsync(b.fork_src, 0xFF, n * 4, s));               // -1: no fork pending
+  if (gr.on) MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.st.gram), mt3g_initial(&gr.g), n, s));
   MT3_OP_TRY(mt3k::launch_iota(b.st.slot_row, slots, s));
   MT3_OP_TRY(mt3k::launch_beam_init(b.live, b.fin_score, b.fin_step, b.fin_beam, slots, k, s));
   MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
@@ -1426,7 +1506,9 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   for (int t = 0; t < num_steps; ++t) {
     b.logits = const_cast<float*>(d_logits) + static_cast<size_t>(t) * n * vocab;
     const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, tp, s));
+    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, tp, gr, s));
+    if (gr.on && h_state)
+      MT3_HIP_CHECK(hipMemcpyAsync(h_state + static_cast<size_t>(t) * n, b.st.gram, n * 4, hipMemcpyDeviceToHost, s));
     int32_t* tr = h_trace + static_cast<size_t>(t) * 4 * n;
     MT3_HIP_CHECK(hipMemcpyAsync(tr, b.st.slot_row, n * 4, hipMemcpyDeviceToHost, s));
     MT3_HIP_CHECK(hipMemcpyAsync(tr + n, b.fork_src, n * 4, hipMemcpyDeviceToHost, s));
@@ -1481,25 +1563,31 @@ extern "C" int mt3_op_beam_search_prompted(const float* d_logits, const float* d
                             h_forks, h_steps_run, stream, d_masks, n_masks, d_row_mask, d_prompts, stride, d_row_prompt);
 }
 
-// shared body of mt3_op_token_steps_scripted (masked == false), mt3_op_token_steps_masked and mt3_op_token_steps_prompted
+// shared body of mt3_op_token_steps_scripted (masked == false), mt3_op_token_steps_masked, mt3_op_token_steps_prompted and
+// mt3_op_token_steps_grammar
 static int token_steps_driver(const std::string& who, bool masked, float* d_logits, const float* d_ss, int32_t n_ss,
                               int32_t dim, int32_t rows, int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
                               int32_t* d_ids, int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
                               const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
-                              const int32_t* d_row_prompt = nullptr) {
+                              const int32_t* d_row_prompt = nullptr, const mt3_token_grammar* h_grammar = nullptr,
+                              int32_t* h_state = nullptr) {
   if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
       max_len < 0 || bad_scale(d_ss, n_ss, dim))
     return mt3::fail(MT3_ERR_INVALID, who + ": mode is 0 (greedy) or 1 (beam-1); rows, vocab >= 2, num_steps, max_len or "
                                             "the row scale out of range");
+  if (h_grammar)                                  // the descriptor itself: before anything is read back from the device
+    if (const char* bad = mt3k::bad_token_grammar(*h_grammar, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
   mt3k::TokenMask tm{};
   if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, rows, vocab, 2, &tm));
   mt3k::TokenPrompt tp{};
   if (d_prompts) MT3_OP_TRY(driver_prompts(who, d_prompts, stride, d_row_prompt, rows, vocab, &tp));
+  mt3k::TokenGrammar gr{};
+  if (h_grammar) MT3_OP_TRY(driver_grammar(who, h_grammar, masked ? d_masks : nullptr, n_masks, vocab, 2, &gr));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n = static_cast<size_t>(rows);
   Scratch m;
-  MT3_OP_TRY(m.alloc(5 * Scratch::piece(n * 4) + Scratch::piece(2 * n * 4) + Scratch::piece(4) +
+  MT3_OP_TRY(m.alloc(6 * Scratch::piece(n * 4) + Scratch::piece(2 * n * 4) + Scratch::piece(4) +
                          Scratch::piece((static_cast<size_t>(num_steps) + 3) * 4),
                      s));
   mt3k::ArgmaxStepArgs a{};
@@ -1513,6 +1601,8 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
   int* len_row = m.take<int>(n);
   float* f = m.take<float>(2 * n);
   a.st.n_done = m.take<int>(1);
+  if (gr.on) a.st.gram = m.take<int>(n);
+  a.gr = gr;
   float* d_bp = m.take<float>(static_cast<size_t>(num_steps) + 3);
   a.in.max_pos = num_steps + 1;
   if (mode == 1) a.beam = mt3k::BeamState{f, len, d_bp, rows, len_row};
@@ -1524,12 +1614,15 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
   MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, n * num_steps * 4, s));
   MT3_HIP_CHECK(hipMemsetAsync(len, 0xFF, n * 4, s));                       // -1: nothing finished
   MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
+  if (gr.on) MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.st.gram), mt3g_initial(&gr.g), n, s));
   MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
   for (int t = 0; t < num_steps; ++t) {
     a.logits = d_logits + static_cast<size_t>(t) * n * vocab;
     a.ls = mt3k::LogitScale{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
     MT3_OP_TRY(mt3k::launch_argmax_step(a, s));
     MT3_HIP_CHECK(hipMemcpyAsync(h_done + static_cast<size_t>(t) * n, a.st.done, n * 4, hipMemcpyDeviceToHost, s));
+    if (gr.on && h_state)
+      MT3_HIP_CHECK(hipMemcpyAsync(h_state + static_cast<size_t>(t) * n, a.st.gram, n * 4, hipMemcpyDeviceToHost, s));
   }
   if (mode == 1) MT3_OP_TRY(mt3k::launch_beam1_finalize(d_ids, num_steps, len_row, rows, s));
   MT3_HIP_CHECK(hipStreamSynchronize(s));
@@ -1559,6 +1652,31 @@ extern "C" int mt3_op_token_steps_prompted(float* d_logits, const float* d_ss, i
   return token_steps_driver("mt3_op_token_steps_prompted", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
                             num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
                             d_row_prompt);
+}
+
+extern "C" int mt3_op_beam_search_grammar(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim,
+                                          int32_t elems, int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len,
+                                          const float* d_table, const float* d_pos, int32_t dim_e, int32_t* d_ids,
+                                          int32_t* d_all_ids, float* d_scores, float* d_y_next, int32_t* h_trace,
+                                          float* h_live, int32_t* h_forks, int32_t* h_steps_run, void* stream,
+                                          const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                                          const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                                          const mt3_token_grammar* h_grammar, int32_t* h_state) {
+  return beam_search_driver("mt3_op_beam_search_grammar", d_masks != nullptr, d_logits, d_ss, n_ss, dim, elems, k, vocab,
+                            num_steps, max_len, d_table, d_pos, dim_e, d_ids, d_all_ids, d_scores, d_y_next, h_trace, h_live,
+                            h_forks, h_steps_run, stream, d_masks, n_masks, d_row_mask, d_prompts, stride, d_row_prompt,
+                            h_grammar, h_state);
+}
+
+extern "C" int mt3_op_token_steps_grammar(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                          int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                          int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                                          const int32_t* d_row_mask, const int32_t* d_prompts, int32_t stride,
+                                          const int32_t* d_row_prompt, const mt3_token_grammar* h_grammar,
+                                          int32_t* h_state) {
+  return token_steps_driver("mt3_op_token_steps_grammar", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
+                            num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
+                            d_row_prompt, h_grammar, h_state);
 }
 
 extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots,
@@ -1676,7 +1794,7 @@ extern "C" int mt3_op_slot_compact(const mt3_slot_state_view* st, const mt3_inpu
   const size_t q_n = in->q_out ? static_cast<size_t>(in->q_n) : 0;
   Scratch m;
   MT3_OP_TRY(m.alloc(Scratch::piece(n * dim * 4) + Scratch::piece(n * dim * 2) + Scratch::piece(n * dim / 16 * 4) +
-                         Scratch::piece(n * q_n * 4) + Scratch::piece(n * 16) + Scratch::piece(n * 8) +
+                         Scratch::piece(n * q_n * 4) + Scratch::piece(n * mt3k::kCompactInts * 4) + Scratch::piece(n * 8) +
                          Scratch::piece(n * 4) + Scratch::piece((n + 1) * 4),
                      s, 0xFF));
   mt3k::CompactArgs c{};
@@ -1692,7 +1810,7 @@ extern "C" int mt3_op_slot_compact(const mt3_slot_state_view* st, const mt3_inpu
   c.s_y_ct = in->y_ct ? s_y_ct : nullptr;
   c.s_y_ss = in->y_ss ? s_y_ss : nullptr;
   c.s_qkvf = in->q_out ? s_qkvf : nullptr;
-  c.s_int = m.take<int>(n * 4);
+  c.s_int = m.take<int>(n * mt3k::kCompactInts);
   c.s_beam = m.take<float>(n * 2);
   c.s_seg = m.take<int>(n);
   c.perm = m.take<int>(n + 1);

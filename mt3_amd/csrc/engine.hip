@@ -117,15 +117,17 @@ struct LayerDev {
 // steps never share a captured graph
 // 256 = prompts (mt3_engine_set_prompts): the step ends with the PROMPT token / beam kernel, so prompted and unprompted steps
 // never share a captured graph
+// 512 = the event grammar (mt3_engine_set_token_grammar): the step ends with the GRAMMAR token / beam kernel, so steps with
+// a grammar never share a captured graph with steps without one
 constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kVarMask = 128,
-              kVarPrompt = 256, kNumVariants = 512;
+              kVarPrompt = 256, kVarGrammar = 512, kNumVariants = 1024;
 // not a step variant of its own (never an index into graph_exec): set in GroupRun::variant when the decode runs as SEVERAL
 // row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
 // keeps such steps apart from a lone stream's steps of the same shape
-constexpr int kVarBeside = 512;
+constexpr int kVarBeside = 1024;
 // not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
 // number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
-constexpr int kVarBeams = 1024, kVarBeamsShift = 11;
+constexpr int kVarBeams = 2048, kVarBeamsShift = 12;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
 // to kStageChunkCap segments each (one encoder pass per chunk)
@@ -189,6 +191,7 @@ struct SegTableHost {
   bool seg_on = false;           // a per-segment index is set (false: row 0 for every segment)
   std::vector<int> seg_host;     // host copy of the per-segment index
   std::vector<int> stat;         // host, per row: what the job checks read (fits)
+  std::vector<T> rows_host;      // host copy of the rows (the grammar's check of its intersection with the masks)
 };
 
 }  // namespace
@@ -278,6 +281,11 @@ struct mt3_engine {
                                  // words; stat = the allowed tokens of each
   SegTableHost<int> tp;          // prompted decoding (mt3_engine_set_prompts, kVarPrompt): 0-padded id rows; stat = the
                                  // length of each
+  mt3k::TokenGrammar gr{};       // well-formed decoding (mt3_engine_set_token_grammar, kVarGrammar): the descriptor travels by
+                                 // value in the step's kernel arguments (a graph that captured another one is dropped)
+  bool gr_seen = false;          // a descriptor has been set before (step graphs may hold it)
+  int* gram = nullptr;           // [max_batch] per slot: the packed grammar state (SlotState::gram); with a grammar set it
+                                 // travels with the slot and is reset with it, without one no launch is handed it
   // In-flight batching (mt3_engine_transcribe): slot_seg maps a slot to the SEGMENT it is decoding (-1: none); a
   // finished slot hands its id row to the caller's output and restarts on the next encoded segment (launch_refill)
   int* slot_seg = nullptr;       // [max_batch]
@@ -710,8 +718,9 @@ inline bool chain_op_is_heavy(const mt3_engine* e, int op) {
 
 // the per-slot state of slots [row0, ...) of the row group that counts its finished slots in n_done[done_slot]
 mt3k::SlotState slot_state(mt3_engine* e, int row0, int done_slot) {
-  return mt3k::SlotState{e->done + row0, e->slot_row + row0, e->slot_seg + row0,
-                         e->step + row0, e->cur_tok + row0,  e->n_done + done_slot};
+  // (the grammar state only with a grammar set: without one nothing moves, resets or reads it)
+  return mt3k::SlotState{e->done + row0, e->slot_row + row0, e->slot_seg + row0, e->step + row0,
+                         e->cur_tok + row0,  e->n_done + done_slot, e->gr.on ? e->gram + row0 : nullptr};
 }
 
 // the decoder input rows of slots [row0, ...) and what they are written from.  The one place that knows which forms the
@@ -896,7 +905,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     const int* slot_seg = streaming ? e->slot_seg + row0 : nullptr;
     const mt3k::TokenMask tm = (skip & kVarMask) ? seg_view(e->tm, seg0, slot_seg) : mt3k::TokenMask{};
     const mt3k::TokenPrompt tp = (skip & kVarPrompt) ? seg_view(e->tp, seg0, slot_seg) : mt3k::TokenPrompt{};
-    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, tp, s));
+    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, tp, (skip & kVarGrammar) ? e->gr : mt3k::TokenGrammar{}, s));
     mt3k::BeamReorderArgs r{};
     r.n_layers = nl;
     r.H = H;
@@ -934,6 +943,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     // both tables are indexed as eos_at is: by segment, or by the row the slot decodes (a.rt says which)
     if (skip & kVarMask) a.tm = seg_view(e->tm, crow0, nullptr);
     if (skip & kVarPrompt) a.tp = seg_view(e->tp, crow0, nullptr);
+    if (skip & kVarGrammar) a.gr = e->gr;
     return mt3k::launch_argmax_step(a, s);
   }
   LayerDev& L = e->dec[op >> 3];
@@ -1384,7 +1394,8 @@ int mt3_engine_finalize(mt3_engine* e) {
   if (e->y_split && c.compute_dtype == MT3_BF16 && (rc = dmalloc(e, &e->cs_y_ct, static_cast<size_t>(Bm) * emb * 2))) return rc;
   if (e->y_split && (rc = dmalloc(e, reinterpret_cast<void**>(&e->cs_y_ss), static_cast<size_t>(Bm) * (emb / 16) * 4))) return rc;
   if (e->qkv_fold && (rc = dmalloc(e, reinterpret_cast<void**>(&e->cs_qkvf), static_cast<size_t>(Bm) * 4 * hd * 4))) return rc;
-  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->cs_int), static_cast<size_t>(Bm) * 4 * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->cs_int), static_cast<size_t>(Bm) * mt3k::kCompactInts * 4))) return rc;
+  if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->gram), static_cast<size_t>(Bm) * 4))) return rc;
   if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->cs_beam), static_cast<size_t>(Bm) * 2 * 4))) return rc;
   if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->cs_perm), (static_cast<size_t>(Bm) + kMaxChains) * 4))) return rc;
   if ((rc = dmalloc(e, reinterpret_cast<void**>(&e->beam_f), static_cast<size_t>(2) * Bm * 4))) return rc;
@@ -1737,7 +1748,7 @@ static int compact_group(mt3_engine* e, const GroupRun& r, int cur) {
   if (a.in.y_ct) a.s_y_ct = static_cast<char*>(e->cs_y_ct) + r0 * emb * 2;
   if (a.in.y_ss) a.s_y_ss = e->cs_y_ss + r0 * (emb / 16);
   if (a.in.rp.q_out) a.s_qkvf = e->cs_qkvf + r0 * n4;
-  a.s_int = e->cs_int + 4 * r0;
+  a.s_int = e->cs_int + mt3k::kCompactInts * r0;
   a.perm = e->cs_perm + r0 + r.slot;
   a.rows = cur;
   if (r.variant & kVarStream) a.s_seg = e->cs_seg + r0;
@@ -1935,11 +1946,16 @@ static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
 // Position 0 and BOS (= 0) for slots [0, n); `counters`: nothing finished (done flags, the groups' counters of finished
 // slots), `ids`: zeroed id rows -- mt3_engine_transcribe_beams starts every slot FINISHED (launch_beam_stream_init) and
 // the k-beam jobs keep their ids in the history
+// the grammar state a slot starts in at position 0 (no grammar set: 0, which nothing reads)
+static int grammar_initial(const mt3_engine* e) { return e->gr.on ? mt3g_initial(&e->gr.g) : 0; }
+
 static int reset_slots(mt3_engine* e, int n, bool counters, bool ids, hipStream_t s) {
   MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(n) * 4, s));
   if (counters) MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
   if (counters) MT3_HIP_CHECK(hipMemsetAsync(e->done, 0, static_cast<size_t>(n) * 4, s));
   MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(n) * 4, s));
+  if (e->gr.on)
+    MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->gram), grammar_initial(e), static_cast<size_t>(n), s));
   if (ids) MT3_HIP_CHECK(hipMemsetAsync(e->ids, 0, static_cast<size_t>(n) * e->cfg.max_decode_len * 4, s));
   return MT3_OK;
 }
@@ -1962,12 +1978,28 @@ static int reset_beam1_state(mt3_engine* e, int num_steps, hipStream_t s) {
 }
 
 // The masks, then the prompts, against a job of `n` rows / elements / segments: a step needs `need` candidates among a
-// mask's allowed tokens, and a segment at least one free step of `num_steps` after its prompt.  MT3_OK and *var = the
-// kVarMask / kVarPrompt bits of the job's step variant.
+// mask's allowed tokens, and a segment at least one free step of `num_steps` after its prompt; with a grammar set, every
+// mask in use must leave `need` ids in the tie-section state and in the worst state after it (grammar_room).  MT3_OK and
+// *var = the kVarMask / kVarPrompt / kVarGrammar bits of the job's step variant.
 static int seg_tables_fit(const mt3_engine* e, const char* who, int n, int need, int num_steps, int* var) {
   MT3_TRY(fits(e->tm, who, n, need, INT_MAX, "the token masks'", ": a token mask in use allows fewer than 2 * num_beams tokens"));
   MT3_TRY(fits(e->tp, who, n, 0, num_steps - 1, "the prompts'", ": num_steps must exceed the longest prompt in use"));
-  *var = (e->tm.n ? kVarMask : 0) | (e->tp.n ? kVarPrompt : 0);
+  if (e->gr.on) {
+    const int vocab = e->cfg.vocab_size;
+    std::vector<char> seen(static_cast<size_t>(e->tm.n) + 1, 0);
+    for (int i = 0; i < (e->tm.n && e->tm.seg_on ? n : 1); ++i) {
+      const int r = !e->tm.n ? -1 : (e->tm.seg_on ? e->tm.seg_host[i] : 0);          // -1: no mask, the grammar alone
+      if (seen[r + 1]) continue;
+      seen[r + 1] = 1;
+      int in_tie = 0, after = 0;
+      mt3k::grammar_room(e->gr.g, r < 0 ? nullptr : e->tm.rows_host.data() + static_cast<size_t>(r) * e->tm.stride, vocab,
+                         &in_tie, &after);
+      if ((e->gr.g.with_ties && in_tie < need) || after < need)
+        return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": the grammar and a token mask in use leave fewer than 2 * "
+                                                             "num_beams ids in the tie section or after a shift");
+    }
+  }
+  *var = (e->tm.n ? kVarMask : 0) | (e->tp.n ? kVarPrompt : 0) | (e->gr.on ? kVarGrammar : 0);
   return MT3_OK;
 }
 
@@ -2222,6 +2254,7 @@ static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRan
   a.out_ids = d_out;
   a.plan = e->refill_plan + r0 + r.slot;
   a.rows = cur;
+  a.gram0 = grammar_initial(e);
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
@@ -2249,6 +2282,7 @@ static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* 
   a.out_ids = d_out;
   a.out_all = bo.all_ids;
   a.out_scores = bo.scores;
+  a.gram0 = grammar_initial(e);
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
@@ -2885,6 +2919,7 @@ static int set_seg_table(mt3_engine* e, SegTableHost<T>& tb, const std::string& 
   tb.seg_on = n_seg > 0;
   tb.stride = stride;
   tb.seg_host.assign(h_seg, h_seg + n_seg);
+  tb.rows_host.assign(h_rows, h_rows + n_elems);
   tb.stat = stat;
   tb.n = n;
   return MT3_OK;
@@ -2935,6 +2970,28 @@ int mt3_engine_set_prompts(mt3_engine* e, const int32_t* h_prompts, int32_t n_pr
                        [=](const int* p, int* len) { return mt3k::bad_prompt(p, stride, vocab, len); });
 }
 
+int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g) {
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_grammar: null engine");
+  if (g)
+    if (const char* bad = mt3k::bad_token_grammar(*g, e->cfg.vocab_size))
+      return mt3::fail(MT3_ERR_INVALID, std::string("mt3_engine_set_token_grammar: ") + bad);
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_grammar: engine not finalized");
+  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_grammar: a decode is in flight");
+  if (!g) {
+    e->gr.on = 0;                 // (the descriptor stays: the grammar's step graphs hold it and serve the same one again)
+    return MT3_OK;
+  }
+  // the grammar's step graphs hold the descriptor by value: another one and they go
+  if (e->gr_seen && std::memcmp(&e->gr.g, g, sizeof(*g)) != 0) {
+    MT3_HIP_CHECK(hipDeviceSynchronize());
+    drop_step_graphs(e);
+  }
+  e->gr.g = *g;
+  e->gr.on = 1;
+  e->gr_seen = true;
+  return MT3_OK;
+}
+
 int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_score_chunk: engine not finalized");
   if (segments < 0 || segments > e->cfg.max_batch)
@@ -2979,6 +3036,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
     case MT3_STATUS_TOKEN_MASKS: return e->tm.n;
     case MT3_STATUS_PROMPTS: return e->tp.n;
+    case MT3_STATUS_TOKEN_GRAMMAR: return e->gr.on ? 1 : 0;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

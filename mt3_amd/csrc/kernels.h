@@ -125,6 +125,8 @@ struct SlotState {
   int* step;            // [slots] position counter
   int* cur_tok;         // [slots] input token of the next step
   int* n_done;
+  int* gram;            // [slots] packed state of the event grammar (TokenGrammar; nullptr: not kept -- it then neither
+                        // travels with the slot nor is reset)
 };
 // logits that arrive UNNORMALISED (the logits projection folded into the last layer's MLP out-projection launch): the
 // kernel that picks the token applies the decoder_norm row scale rsqrt(sum(ss[b][0 .. n_ss)) / dim + 1e-6) itself and
@@ -182,6 +184,40 @@ inline const char* bad_prompt(const int* h_prompt, int stride, int vocab, int* l
   }
   if (n == 0) return "an empty prompt (its first id is 0)";
   return nullptr;
+}
+// Well-formed decoding (mt3_engine_set_token_grammar; the rule and the packed per-slot state: include/mt3_hip.h, mt3g_*).
+// The descriptor travels by value in the kernel arguments; `on` selects the GRAMMAR instantiations of the token kernels,
+// which read the slot's state from SlotState::gram in the batch of the logits, count a disallowed id as -inf where the
+// mask does, and write advance(state, emitted token) back.  on == 0: the launchers run the instantiations whose
+// statements do not mention it.
+struct TokenGrammar {
+  mt3_token_grammar g;
+  int on;
+};
+// the one host-side check of a grammar descriptor against a vocabulary: nullptr, or what is wrong with it
+inline const char* bad_token_grammar(const mt3_token_grammar& g, int vocab) {
+  const long long lo[4] = {g.shift_first, g.program_first, g.pitch_first, g.tie_id};
+  const long long n[4] = {g.shift_count, g.program_count, g.pitch_count, 1};
+  for (int i = 0; i < 4; ++i)
+    if (n[i] < 1 || lo[i] < 3 || lo[i] + n[i] > vocab) return "a grammar range is empty or outside [3, vocab)";
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j)
+      if (lo[i] < lo[j] + n[j] && lo[j] < lo[i] + n[i]) return "grammar ranges overlap";
+  if (g.max_steps < 1 || g.max_steps > g.shift_count - 1) return "max_steps must be in [1, shift_count - 1]";
+  return nullptr;
+}
+// the ids a free pick may take under grammar `g` and mask `h_mask` (nullptr: none) in the two states that bound every
+// other: *in_tie = the tie-section state, *after = the worst state after it (no shift, no tie)
+inline void grammar_room(const mt3_token_grammar& g, const uint32_t* h_mask, int vocab, int* in_tie, int* after) {
+  const int32_t s_tie = static_cast<int32_t>(MT3_GRAMMAR_TIE_SECTION), s_after = static_cast<int32_t>(MT3_GRAMMAR_PREV_SHIFT);
+  int a = 0, b = 0;
+  for (int i = 0; i < vocab; ++i) {
+    if (h_mask && !((h_mask[i >> 5] >> (i & 31)) & 1u)) continue;
+    a += mt3g_allowed(&g, s_tie, i);
+    b += mt3g_allowed(&g, s_after, i);
+  }
+  *in_tie = a;
+  *after = b;
 }
 // in.y[b] = table[tok[b]] + pos[step[b]] for b < B, in every form `in` holds
 int launch_embed(const InputRow& in, const int* tok, const int* step, int B, hipStream_t s);
@@ -241,12 +277,14 @@ struct ArgmaxStepArgs {
   int B;
   TokenMask tm;         // rows == nullptr: unconstrained
   TokenPrompt tp;       // rows == nullptr: none
+  TokenGrammar gr;      // on == 0: none; else st.gram holds the slots' states
 };
 int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that
 // lives from one step to the next -- the next step's input row in its three forms, layer 0's projected row, position
 // counter, current token, beam-search state, the slot -> row map -- moves from slot perm[i] to slot i (i < n_live) by
 // way of a scratch copy; slots [n_live, rows) are marked done.  All pointers are those of the group's first slot.
+constexpr int kCompactInts = 5;
 struct CompactArgs {
   SlotState st;         // slot_seg == nullptr: no in-flight batching (a dropped slot decodes nothing: -1)
   InputRow in;          // y / y_ct / y_ss / rp.q_out (each nullptr: not in use), dim, rp.q_n
@@ -256,7 +294,7 @@ struct CompactArgs {
   void* s_y_ct;
   float* s_y_ss;
   float* s_qkvf;
-  int* s_int;           // [rows][4]: slot_row, step, cur_tok, beam_len
+  int* s_int;           // [rows][kCompactInts]: slot_row, step, cur_tok, beam_len, grammar state
   float* s_beam;        // [rows][2]
   int* s_seg;           // [rows]
   int* perm;            // [rows + 1]: perm[i] = source slot of new slot i; perm[rows] = n_live
@@ -296,6 +334,7 @@ struct RefillArgs {
   int n_new;            // segments handed out by this call (<= finished slots)
   int first_seg;
   StagedCross x;        // where their cross-attention K/V come from and go to (read when n_new > 0)
+  int gram0;            // the grammar state a restarted slot begins in (st.gram != nullptr)
 };
 int launch_refill(const RefillArgs& a, hipStream_t s);
 // ---- k-beam search (mt3_engine_decode_beams; the rule is stated in include/mt3_hip.h)
@@ -324,7 +363,8 @@ struct BeamKArgs {
   // mt3_engine_decode_beams the host loop's bound does that: it passes 0)
   int max_len;
 };
-int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp, hipStream_t s);
+int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp,
+                     const TokenGrammar& gr, hipStream_t s);
 // copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
 // (and e4m3 scale rows), for every slot that forked this step; the grid covers every slot x layer x head
 struct BeamReorderArgs {
@@ -365,6 +405,7 @@ struct BeamRefillArgs {
   float* out_scores;    // caller's [n_segments][k] or nullptr
   int n_new, first_seg;
   StagedCross x;        // as RefillArgs::x
+  int gram0;            // as RefillArgs::gram0 (b.st.gram != nullptr)
 };
 int launch_beam_refill(const BeamRefillArgs& a, hipStream_t s);
 // start of an mt3_engine_transcribe_beams job: every slot finished and without a segment (the first refill starts the

@@ -309,6 +309,46 @@ int mt3_codec_token_mask(const mt3_codec* c, int32_t vocab, const int32_t* progr
   return MT3_OK;
 }
 
+int mt3_codec_token_grammar(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t max_steps, mt3_token_grammar* out) {
+  CodecTable t(c);
+  if (!c || !out) return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: null argument");
+  if (!t.ok) return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: malformed codec");
+  if (spec < MT3_SPEC_ONSETS || spec > MT3_SPEC_TIES) return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: bad spec");
+  int pitch = -1, tie = -1, program = -1;
+  for (int k = 0; k < t.n; ++k) {
+    if (t.type[k] == MT3_EV_PITCH) pitch = k;
+    if (t.type[k] == MT3_EV_TIE) tie = k;
+    if (t.type[k] == MT3_EV_PROGRAM) program = k;
+  }
+  if (pitch < 0 || tie < 0 || program < 0)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: the codec needs a pitch, a tie and a program range");
+  if (max_steps < 1) return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: max_steps must be at least 1");
+  // a time past the largest shift takes two shifts in a row in a canonical stream, which the rule forbids
+  if (max_steps > t.hi[0])
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: max_steps exceeds the codec's largest shift");
+  if (3 + t.num_classes() > vocab)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_token_grammar: the codec's ranges do not fit below vocab");
+  const auto count = [&](int k) { return t.hi[k] - t.lo[k] + 1; };       // token id = 3 + event index (mt3_ids_to_tokens)
+  out->shift_first = 3 + t.start[0];
+  out->shift_count = count(0);
+  out->max_steps = max_steps;
+  out->tie_id = 3 + t.start[tie];
+  out->program_first = 3 + t.start[program];
+  out->program_count = count(program);
+  out->pitch_first = 3 + t.start[pitch];
+  out->pitch_count = count(pitch);
+  out->with_ties = spec == MT3_SPEC_TIES ? 1 : 0;
+  return MT3_OK;
+}
+
+int32_t mt3_token_grammar_initial(const mt3_token_grammar* g) { return g ? mt3g_initial(g) : 0; }
+int32_t mt3_token_grammar_advance(const mt3_token_grammar* g, int32_t state, int32_t tok) {
+  return g ? mt3g_advance(g, state, tok) : state;
+}
+int32_t mt3_token_grammar_allowed(const mt3_token_grammar* g, int32_t state, int32_t id) {
+  return g ? mt3g_allowed(g, state, id) : 1;
+}
+
 // the machine behind mt3_notes_decode (h_note_tokens == nullptr) and mt3_notes_decode_traced; `who` names the entry
 // point in its error messages
 static int notes_decode_impl(const std::string& who, const mt3_codec* c, int32_t spec, int32_t n_segments,

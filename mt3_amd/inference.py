@@ -28,6 +28,7 @@ from __future__ import annotations
 import contextlib
 import functools
 import json
+import math
 import os
 import re
 from typing import Any, Dict, List, Optional, Sequence
@@ -116,6 +117,8 @@ class InferenceModel(object):
         self._params = None
         self._job_masks = None                   # (masks, per-segment index or None) of the constrained call in flight
         self._job_prompts = None                 # per-segment prompts (id list or None) of the prompted call in flight
+        self._job_grammar = None                 # the event grammar of the well-formed call in flight
+        self.last_event_counts = None            # invalid_events / dropped_events of the most recent transcribing call
         self.model = network.Transformer(self.model_config, input_length=self.inputs_length,
                                          max_decode_length=self.outputs_length, max_batch=self.batch_size)
         self.restore_from_checkpoint(checkpoint_path)
@@ -233,17 +236,28 @@ class InferenceModel(object):
         rows += [None] * (n_segments - len(rows))
         return rows if any(r is not None for r in rows) else None
 
+    def token_grammar(self):
+        """the event grammar of this model's codec, spec and segment length (`vocabularies.token_grammar`): max_steps is
+        the segment's length in steps, 204 for `mt3` and 409 for `ismir2021`"""
+        cfg = self.spectrogram_config
+        max_steps = int(math.floor(self.inputs_length * cfg.hop_width / cfg.sample_rate * self.codec.steps_per_second))
+        return vocabularies.token_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, max_steps)
+
     @contextlib.contextmanager
-    def _constrained(self, job, prompts=None):
-        """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`) and `prompts` (`_segment_prompts` of
-        the whole job); masks and prompts are cleared on the way out, also on error"""
+    def _constrained(self, job, prompts=None, well_formed=False):
+        """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`), `prompts` (`_segment_prompts` of
+        the whole job) and, with well_formed, the model's event grammar; all are cleared on the way out, also on error"""
         self._job_masks = job
         self._job_prompts = prompts
         try:
+            self._job_grammar = self.token_grammar() if well_formed else None
             yield
         finally:
             self._job_masks = None
             self._job_prompts = None
+            if self._job_grammar is not None and self.model is not None:
+                self.model.clear_token_grammar()
+            self._job_grammar = None
             if job is not None and self.model is not None:
                 self.model.clear_token_masks()
             if prompts is not None and self.model is not None:
@@ -264,6 +278,8 @@ class InferenceModel(object):
                     rows.append(p)
                 index.append(rows.index(p))
             self.model.set_prompts(rows, index if rows else None)
+        if self._job_grammar is not None:
+            self.model.set_token_grammar(self._job_grammar)
 
     # ------------------------------------------------------------------ model call
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
@@ -319,7 +335,8 @@ class InferenceModel(object):
             self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
         return torch.cat(out, 0)
 
-    def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True, prompts=None):
+    def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True, prompts=None,
+                 well_formed: bool = False):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
         notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`.
@@ -330,17 +347,24 @@ class InferenceModel(object):
         an id sequence the segment's output must begin with (`vocabularies.tie_section_prompt(codec, notes)`: the notes
         still sounding when the segment starts; `tie_section_prompt(codec, [])`: a known silent start) or None / empty for
         none; shorter than the segments: padded with None, longer: ValueError.  The decode continues from the prompt
-        (Transformer.set_prompts) and the notes are read from prompt + continuation.  Composes with programs / drums."""
+        (Transformer.set_prompts) and the notes are read from prompt + continuation.  Composes with programs / drums.
+        well_formed (every transcribing method takes it; default off): well-formed decoding -- the token pick follows the
+        event grammar of the model's codec (Transformer.set_token_grammar), so no token is spent on a shift that runs
+        backwards or past the segment's end, a `tie` outside the tie section or a malformed tie section, which the note
+        decoder would count in invalid_events / dropped_events and throw away.  Composes with the rest.
+        `last_event_counts` holds the note decoder's invalid_events / dropped_events of the most recent call."""
         examples = self._examples(audio, sample_rate)
-        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples))):
+        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
+                               well_formed):
             return self._transcribe_examples(examples)
 
-    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None):
+    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
         examples = self._wav_examples(wav_data)
-        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples))):
+        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
+                               well_formed):
             return self._transcribe_examples(examples)
 
     def _transcribe_examples(self, examples, scored: bool = False):
@@ -354,16 +378,23 @@ class InferenceModel(object):
             predictions = [self.postprocess(t, ex) for t, ex in zip(tokens, examples)]
             result = metrics_utils.event_predictions_to_ns(predictions, codec=self.codec,
                                                            encoding_spec=self.encoding_spec)
+            self._count_events([result])
             return result["est_ns"]
         ids = self._predict_ids(batch)
         tokens = self.vocabulary.decode_tf(ids).cpu().numpy()
         predictions = [self.postprocess(t, ex) for t, ex in zip(tokens, examples)]
         result = metrics_utils.event_predictions_to_ns_traced(predictions, codec=self.codec,
                                                               encoding_spec=self.encoding_spec)
+        self._count_events([result])
         return result["est_ns"], self._note_scores(batch["encoder_input_tokens"], ids, result["note_tokens"])
 
+    def _count_events(self, results):
+        """the note decoder's counts of the call that just ended, summed over its files"""
+        self.last_event_counts = {"invalid_events": int(sum(r["est_invalid_events"] for r in results)),
+                                  "dropped_events": int(sum(r["est_dropped_events"] for r in results))}
+
     def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True,
-                          prompts=None):
+                          prompts=None, well_formed: bool = False):
         """`__call__` with a confidence for every note: (NoteSequence, scores).  The notes are those of `__call__` (same
         decode: the model's `decoding` and `schedule`); afterwards the decoded id rows are scored teacher-forced in one
         `Transformer.score_segments` call (ids after EOS are 0 = padding; length = the longest row) and each note is
@@ -379,13 +410,14 @@ class InferenceModel(object):
         tokens are scored like any other decoded token (scoring ignores prompts)."""
         self._refuse_e4m3("transcribe_scored")
         examples = self._examples(audio, sample_rate)
-        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples))):
+        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
+                               well_formed):
             return self._transcribe_examples(examples, scored=True)
 
-    def transcribe_wav_scored(self, wav_data, *, programs=None, drums: bool = True):
+    def transcribe_wav_scored(self, wav_data, *, programs=None, drums: bool = True, well_formed: bool = False):
         """The file-level form of `transcribe_scored`: `transcribe_wav` plus the notes' confidences."""
         self._refuse_e4m3("transcribe_wav_scored")
-        with self._constrained(self._token_masks(programs, drums)):
+        with self._constrained(self._token_masks(programs, drums), None, well_formed):
             return self._transcribe_examples(self._wav_examples(wav_data), scored=True)
 
     def _refuse_e4m3(self, who):
@@ -444,7 +476,7 @@ class InferenceModel(object):
         return scores, [tok[i, : len(r)] for i, r in enumerate(rows)]
 
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
-                        drums=True, prompts=None) -> List[Any]:
+                        drums=True, prompts=None, well_formed: bool = False) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
@@ -458,14 +490,16 @@ class InferenceModel(object):
         if len(sample_rates) != len(audios):
             raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
         return self._transcribe_files([functools.partial(self._examples, audio, sr)
-                                       for audio, sr in zip(audios, sample_rates)], programs, drums, prompts)
+                                       for audio, sr in zip(audios, sample_rates)], programs, drums, prompts, well_formed)
 
-    def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None) -> List[Any]:
+    def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None,
+                        well_formed: bool = False) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
         `self.transcribe_wav(wav)`.  programs / drums / prompts: as for `transcribe_many`."""
-        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums, prompts)
+        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums, prompts,
+                                      well_formed)
 
-    def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None):
+    def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None, well_formed=False):
         """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
         NoteSequence per file, all segments through the engine as one job"""
         import torch
@@ -484,14 +518,15 @@ class InferenceModel(object):
             for p, ex in zip(prompts, per_file):
                 rows += self._segment_prompts(p, len(ex)) or [None] * len(ex)
             job_prompts = rows if any(r is not None for r in rows) else None
-        with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts):
+        with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts, well_formed):
             tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
-        out, at = [], 0
+        out, at, results = [], 0, []
         for examples in per_file:
             preds = [self.postprocess(t, ex) for t, ex in zip(tokens[at:at + len(examples)], examples)]
             at += len(examples)
-            out.append(metrics_utils.event_predictions_to_ns(preds, codec=self.codec,
-                                                             encoding_spec=self.encoding_spec)["est_ns"])
+            results.append(metrics_utils.event_predictions_to_ns(preds, codec=self.codec, encoding_spec=self.encoding_spec))
+            out.append(results[-1]["est_ns"])
+        self._count_events(results)
         return out
 
     # ------------------------------------------------------------------ host preprocessing

@@ -392,6 +392,17 @@ class Transformer:
         _lib.check(self._lib.mt3_engine_set_prompts(self._h, p.ctypes.data, int(p.shape[0]), int(p.shape[1]),
                                                     sp.ctypes.data, int(sp.size)))
 
+    def set_token_grammar(self, grammar):
+        """mt3_engine_set_token_grammar: well-formed decoding for every later decode / decode_beams / transcribe call
+        until `clear_token_grammar`.  grammar: a `_lib.TokenGrammar` (`vocabularies.token_grammar`).  The token pick then
+        never takes a shift that runs backwards, repeats or passes max_steps, a `tie` outside the tie section, or anything
+        but program / pitch / tie inside it; with token masks the allowed set is the intersection, prompts win inside the
+        prompt and advance the state.  decode_forced / score / score_segments ignore it."""
+        _lib.check(self._lib.mt3_engine_set_token_grammar(self._h, C.byref(grammar)))
+
+    def clear_token_grammar(self):
+        _lib.check(self._lib.mt3_engine_set_token_grammar(self._h, None))
+
     def debug_decode(self, num_steps: Optional[int] = None, skip_self_attn: bool = False,
                      skip_cross_attn: bool = False, chains: int = 0, use_graph: bool = True):
         """mt3_debug_engine_decode (include/mt3_hip_debug.h): a decode with kernels left out of every step, for

@@ -39,6 +39,9 @@ def plan(argv=None):
     ap.add_argument("--programs", type=_program_list, default=None, metavar="P[,P...]",
                     help="constrained decoding: the MIDI programs (0 .. 127) the transcription may use, for all inputs")
     ap.add_argument("--no-drums", dest="drums", action="store_false", help="constrained decoding: no drum notes")
+    ap.add_argument("--well-formed", action="store_true",
+                    help="well-formed decoding: the token pick follows the event grammar (no backwards or repeated shift, "
+                         "no stray tie), so nothing it emits is thrown away by the note decoder")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -78,11 +81,13 @@ def main(argv=None) -> int:
         model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype, decoding=args.decoding,
                                          num_beams=args.num_beams)
         if args.confidences:
-            scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums)
+            scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums,
+                                                  well_formed=args.well_formed)
                       for path in args.inputs]
             sequences, scores = [ns for ns, _ in scored], [sc for _, sc in scored]
         else:
-            sequences, scores = model.transcribe_wavs(args.inputs, programs=args.programs, drums=args.drums), None
+            sequences, scores = model.transcribe_wavs(args.inputs, programs=args.programs, drums=args.drums,
+                                                      well_formed=args.well_formed), None
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1

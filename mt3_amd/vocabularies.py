@@ -141,6 +141,20 @@ def token_mask(codec: event_codec.Codec, vocab_size: int, programs=None, drums: 
     return mask
 
 
+def token_grammar(codec: event_codec.Codec, vocab_size: int, spec, max_steps: int) -> _lib.TokenGrammar:
+    """The event grammar of `codec` (`mt3_codec_token_grammar`): what `Transformer.set_token_grammar` takes.  spec: a
+    `note_sequences` encoding spec or its id (ties: segments open with a tie section); max_steps: the largest shift a
+    free pick may take, the segment's length in steps -- floor(input_length * hop_width / sample_rate *
+    steps_per_second), 204 for `mt3` and 409 for `ismir2021`.  ValueError for what the library refuses."""
+    g = _lib.TokenGrammar()
+    lib = _lib.load()
+    rc = lib.mt3_codec_token_grammar(C.byref(codec.desc), int(getattr(spec, "spec_id", spec)), int(vocab_size),
+                                     int(max_steps), C.byref(g))
+    if rc != 0:
+        raise ValueError(lib.mt3_last_error().decode())
+    return g
+
+
 def tie_section_prompt(codec: event_codec.Codec, notes, remove_redundant_programs: bool = False) -> list:
     """The vocabulary ids of the tie section that declares `notes`, an iterable of (program, pitch), as still sounding: a
     prompt for `Transformer.set_prompts` / the `prompts=` keyword of the transcribing methods.  It is the section the
