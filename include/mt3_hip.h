@@ -38,6 +38,7 @@
 #ifndef MT3_HIP_H_
 #define MT3_HIP_H_
 
+#include <math.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -559,6 +560,86 @@ int32_t mt3_token_grammar_advance(const mt3_token_grammar* g, int32_t state, int
 int32_t mt3_token_grammar_allowed(const mt3_token_grammar* g, int32_t state, int32_t id);
 int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g /* NULL clears */);
 
+/* Temperature sampling with top-k / top-p: t5x decoding.temperature_sample in the greedy token kernel's place.  [from
+ * memory] -- t5x is not at hand, as for the beam rule; what binds is that the three statements of the rule agree: the
+ * inline functions below (mt3s_*), the token kernel that compiles them, and the numpy restatement mt3_amd/sampling.py.
+ *   params   mt3_sampling: temperature > 0 and finite; top_k in 0 .. 256 (0: off); 0 <= top_p < 1 (0: off); not both on
+ *            (t5x refuses that too); seed, the Philox key.
+ *   noise    counter based, one draw per (seed, stream, position, token id) and nothing else: a segment's sample depends
+ *            neither on the slot it decodes in, nor on the batch, the row group, graph replay or in-flight refills.
+ *            bits = word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter (stream lo, stream hi, t, id)
+ *            (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; all-zero key and counter give
+ *            0x6627e8d5); u = ((bits >> 9) + 0.5) * 2^-23, exact in f32 and never 0 or 1 (23 bits, not 24: with the half
+ *            added a 24-bit integer needs 25 bits, and f32 would round the largest ones up to u = 1, g = +inf);
+ *            g = -logf(-logf(u)) with the accurate logf (the Gumbel trick: arg-max of z + g is a draw from softmax(z)).
+ *   stream   h_seg_stream [n_segments] (host): the stream of segment i; NULL: the stream of segment i is i.  "Segment i" is
+ *            what it is for masks and prompts: batch row i of mt3_engine_decode, segment i of an mt3_engine_transcribe
+ *            job.  The stream follows the segment through compaction and refills.
+ *   pick     at a FREE position of a live slot, after the row scale and its write-back and after the mask and the grammar
+ *            have put -inf where they do: z_i = x_i / temperature in f32.  The candidates, ids with x_i > -inf, are
+ *            ordered larger x first, lower id on ties (the arg-max convention; the order of z but where two different x
+ *            round to one z, where x decides -- so that top_k = 1 is the greedy pick whatever the temperature).  Kept set:
+ *            top_k = k: the first k candidates; top_p = p: the shortest prefix whose softmax(z) mass is >= p, at least one
+ *            (the masses are summed in units of 2^-40 of the largest, exp(z_i - max z) truncated: integers, so no order of
+ *            summation shows; candidates below one unit are never needed); neither: every candidate.  The token is the
+ *            best of z_i + g_i over the kept set, larger first, lower id on ties.  top_k = 1 is therefore greedy, bit for
+ *            bit, ties included, whatever seed and temperature.
+ *   else     everything else is the greedy path's: prompts win inside the prompt, the synthetic EOS schedule wins, the
+ *            grammar state advances on every emitted token, max_len, early exit, retirement and the next input row are
+ *            unchanged, and the logits handed back stay the model's own.
+ * mt3_engine_set_sampling is a synchronous setup call like mt3_engine_set_token_masks; s == NULL clears (h_seg_stream and
+ * n_segments are then ignored).  Sampling stays set for every later mt3_engine_decode / mt3_engine_transcribe until
+ * cleared; sampled steps never share a captured graph with unsampled ones (the parameters live in device memory the graphs
+ * point to: another seed needs no new graph), and a decode without sampling runs the kernels, graphs and bits it ran before
+ * sampling existed.  mt3_engine_decode_forced, mt3_engine_score, mt3_engine_score_segments, mt3_engine_decode_beams and
+ * mt3_engine_transcribe_beams IGNORE it (the last two are t5x's other decoder); MT3_DECODE_BEAM1 with sampling set is
+ * MT3_ERR_INVALID.  MT3_STATUS_SAMPLING reports 0 / 1.  A mask / grammar intersection that passes the "at least 2 allowed
+ * ids" check of the greedy path needs nothing more.
+ * MT3_ERR_INVALID, before any device work: a parameter outside the ranges above; a vocabulary above 2048 (the kernel keeps
+ * the row in registers); n_segments < 1 with h_seg_stream; an engine that is not finalized; a decode in flight.  The
+ * decode / transcribe calls return MT3_ERR_INVALID before any device work for more rows or segments than n_segments when
+ * h_seg_stream was given. */
+typedef struct mt3_sampling {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  uint64_t seed;                  /* (8-byte aligned: 4 bytes of padding before it, sizeof == 24) */
+} mt3_sampling;
+#define MT3_SAMPLING_MAX_TOP_K 256
+#define MT3_SAMPLING_MAX_VOCAB 2048
+MT3_RULE_FN uint32_t mt3s_mulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }
+MT3_RULE_FN uint32_t mt3s_bits(uint64_t seed, uint64_t stream, int32_t t, int32_t id) {
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  uint32_t c0 = (uint32_t)stream, c1 = (uint32_t)(stream >> 32), c2 = (uint32_t)t, c3 = (uint32_t)id;
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = mt3s_mulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = mt3s_mulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+MT3_RULE_FN float mt3s_uniform(uint32_t bits) { return ((float)(bits >> 9) + 0.5f) * 1.1920928955078125e-7f; }
+MT3_RULE_FN float mt3s_gumbel(uint32_t bits) { return -logf(-logf(mt3s_uniform(bits))); }
+/* what is wrong with the parameters (NULL: nothing): the one host-side check, for the setter and the scripted driver */
+MT3_RULE_FN const char* mt3s_bad_params(const mt3_sampling* s) {
+  if (!(s->temperature > 0.f) || !(s->temperature <= 3.4028234663852886e38f)) return "temperature must be positive and finite";
+  if (s->top_k < 0 || s->top_k > MT3_SAMPLING_MAX_TOP_K) return "top_k must be in 0 .. 256";
+  if (!(s->top_p >= 0.f) || !(s->top_p < 1.f)) return "top_p must be in [0, 1)";
+  if (s->top_k > 0 && s->top_p > 0.f) return "top_k and top_p must not both be on";
+  return (const char*)0;
+}
+/* mt3s_bits and mt3s_gumbel as exported symbols (f32, as the device computes them), for bindings that cannot read the
+ * header's inline functions */
+uint32_t mt3_sampling_bits(uint64_t seed, uint64_t stream, int32_t t, int32_t id);
+float mt3_sampling_gumbel(uint32_t bits);
+int mt3_engine_set_sampling(mt3_engine* e, const mt3_sampling* s /* NULL clears */,
+                            const uint64_t* h_seg_stream /* [n_segments] or NULL */, int32_t n_segments);
+
 /* Teacher-forced cached decode: Transformer.decode (mt3/network.py:303-361) on GIVEN decoder inputs, driven one
  * token per call through the same cached step (layers.py:246-314) the autoregressive loop uses -- the input of
  * step 0 is BOS, the input of step t+1 is d_forced_ids[b][t] (i.e. decoder_input_tokens = shift_right(forced),
@@ -659,7 +740,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_SCORE_CHUNKS = 11 /* chunks of the most recent mt3_engine_score / mt3_engine_score_segments (all its encoder chunks) */,
        MT3_STATUS_TOKEN_MASKS = 12 /* masks set by mt3_engine_set_token_masks (0: none) */,
        MT3_STATUS_PROMPTS = 13 /* prompts set by mt3_engine_set_prompts (0: none) */,
-       MT3_STATUS_TOKEN_GRAMMAR = 14 /* 1: a grammar is set by mt3_engine_set_token_grammar (0: none) */ };
+       MT3_STATUS_TOKEN_GRAMMAR = 14 /* 1: a grammar is set by mt3_engine_set_token_grammar (0: none) */,
+       MT3_STATUS_SAMPLING = 15 /* 1: sampling is set by mt3_engine_set_sampling (0: none) */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -869,6 +951,16 @@ int mt3_op_token_steps_grammar(float* d_logits, const float* d_ss, int32_t n_ss,
                                void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
                                const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
                                const mt3_token_grammar* h_grammar, int32_t* h_state);
+/* The grammar token driver with temperature sampling (mt3_engine_set_sampling states the rule): h_sampling is a HOST
+ * descriptor, checked first as mt3_engine_set_sampling checks it (MT3_ERR_INVALID; also for vocab > 2048 and for mode 1,
+ * beam-1, which does not sample); NULL: no sampling -- the call is then the _grammar driver, bit for bit.  h_row_stream
+ * (HOST, [rows], may be NULL: the stream of row i is i) gives the noise stream of each row. */
+int mt3_op_token_steps_sampled(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
+                               int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
+                               void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                               const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                               const mt3_token_grammar* h_grammar, int32_t* h_state, const mt3_sampling* h_sampling,
+                               const uint64_t* h_row_stream);
 /* The fork copies of one k-beam step on caller-owned caches: for every slot with d_fork_src[slot] >= 0 and
  * d_done[slot] == 0, positions [0, d_step[slot]) of row d_fork_src[slot] are copied into row d_slot_row[slot] of every
  * layer's K and V cache [rows][H][cap][64] of kv_esize-byte elements (1, 2 or 4) and, where given, of its scale pairs

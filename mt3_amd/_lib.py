@@ -26,7 +26,8 @@ DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
  STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS, STATUS_TOKEN_MASKS,
- STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR) = range(15)
+ STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR, STATUS_SAMPLING) = range(16)
+SAMPLING_MAX_TOP_K, SAMPLING_MAX_VOCAB = 256, 2048      # mt3_engine_set_sampling
 (MT3_PCM_U8, MT3_PCM_S16, MT3_PCM_S24, MT3_PCM_S32, MT3_PCM_F32, MT3_PCM_F64) = range(6)     # mt3_pcm_decode formats
 PCM_MAX_CHANNELS = 7
 MAX_BEAMS = 8                                  # mt3_engine_decode_beams: 1 <= num_beams <= 8
@@ -69,6 +70,10 @@ class CodecDesc(C.Structure):
 class TokenGrammar(C.Structure):               # mt3_token_grammar
     _fields_ = [(n, C.c_int32) for n in ("shift_first", "shift_count", "max_steps", "tie_id", "program_first",
                                          "program_count", "pitch_first", "pitch_count", "with_ties")]
+
+
+class Sampling(C.Structure):                   # mt3_sampling (sizeof 24: seed is 8-byte aligned)
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
 class NoteStruct(C.Structure):
@@ -159,6 +164,9 @@ SIGNATURES = {
     "mt3_token_grammar_initial": (C.c_int32, [C.POINTER(TokenGrammar)]),
     "mt3_token_grammar_advance": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
     "mt3_token_grammar_allowed": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
+    "mt3_engine_set_sampling": (C.c_int, [_P, C.POINTER(Sampling), _P, C.c_int32]),
+    "mt3_sampling_bits": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
+    "mt3_sampling_gumbel": (C.c_float, [C.c_uint32]),
     "mt3_engine_status": (C.c_int, [_P, C.c_int32]),
     "mt3_debug_engine_decode": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mt3_debug_engine_transcribe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
@@ -215,6 +223,9 @@ SIGNATURES = {
     "mt3_op_token_steps_grammar": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
                                              C.POINTER(TokenGrammar), _P]),
+    "mt3_op_token_steps_sampled": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
+                                             C.POINTER(TokenGrammar), _P, C.POINTER(Sampling), _P]),
     "mt3_op_beam_reorder": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P),
                                       C.POINTER(_P), _P, _P, _P, _P, _P]),
     "mt3_op_embed_rows": (C.c_int, [C.POINTER(InputRowView), _P, _P, C.c_int32, _P]),

@@ -488,6 +488,253 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
   return MT3_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- temperature sampling
+// Order-preserving integer image of a logit: a larger float has a larger key (-0.f counts as +0.f, as cand_better's ==
+// counts them).  With the id below it, (key << 11) | (2047 - id) orders the candidates of a row of <= 2048 ids exactly as
+// cand_better does -- larger logit first, lower id on ties -- and no two candidates share a value.
+__device__ __forceinline__ unsigned long long cand_key(float v, int i) {
+  const uint32_t b = __float_as_uint(v == 0.f ? 0.f : v);
+  const uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return (static_cast<unsigned long long>(o) << 11) | static_cast<unsigned long long>(2047 - i);
+}
+
+// One decode step of temperature sampling (SampleStepArgs; the rule: include/mt3_hip.h): argmax_step_kernel's greedy
+// form -- the row in registers, the LogitScale multiply and its write-back, masks, prompts, the grammar, the EOS schedule,
+// max_len, retirement, the next input row -- with the pick of a free position drawn instead of taken.  One block of 256
+// per slot, eight values per thread (vocab <= 2048).
+//   kept set   a THRESHOLD SEARCH, not a sort: every candidate carries an integer weight (top-k: 1; top-p: its softmax
+//              mass in units of 2^-40 of the largest), and the key of the last kept candidate is the one at which the
+//              weight of all candidates at or above it first reaches the target (k, or ceil(p * total)).  It is found 8 bits
+//              at a time from the top of the 43-bit key: a 256-bin histogram of the weights in LDS (integer atomics: the
+//              sums do not depend on the order of arrival, so the step is bitwise reproducible), a suffix scan over the
+//              bins by one thread per bin, and the bin that crosses the target fixes the digit; six rounds.
+//   noise      mt3s_bits / mt3s_gumbel for the kept candidates only: the draw of (seed, stream, position, id) does not
+//              depend on who else is kept.
+//   pick       the cand_better-best of z + g: per thread, per wave by shuffles, over the four waves by thread 0.
+// Every branch on the slot's state (done, inside its prompt, at its scheduled EOS) is block-uniform.
+__global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
+  const ArgmaxStepArgs& a = sa.a;
+  const SlotState& st = a.st;
+  const StepRetire& rt = a.rt;
+  const LogitScale& ls = a.ls;
+  const int vocab = a.vocab;
+  __shared__ unsigned long long s_hist[256], s_wsum[4], s_tot[4], s_target;
+  __shared__ float s_v[4], s_m[4];
+  __shared__ int s_i[4];
+  __shared__ int s_tok, s_t, s_digit;
+  __shared__ float s_rs;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (rt.retire && st.done[b]) return;
+  const int out_row = rt.slot_row ? rt.slot_row[b] : b;
+  float* __restrict__ row = a.logits + static_cast<size_t>(b) * vocab;
+  constexpr int kPer = 8;
+  // the row in registers, its mask words, the prompt token, the grammar state and the slot's counters: one batch of loads
+  float xv[kPer];
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) {
+    const int i = tid + u * 256;
+    xv[u] = row[i < vocab ? i : vocab - 1];
+  }
+  const int seg = slot_segment(rt.slot_seg, b, out_row);
+  const uint32_t* mrow = a.tm.rows ? seg_table_row(a.tm, seg) : nullptr;
+  uint32_t mw[kPer];
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) {
+    const int i = tid + u * 256;
+    mw[u] = mrow ? mrow[(i < vocab ? i : vocab - 1) >> 5] : 0xffffffffu;
+  }
+  const int t = st.step[b], was_done = st.done[b];
+  const int ptok = a.tp.rows ? prompt_token(a.tp, seg, t) : 0;
+  const int gs = a.gr.on ? st.gram[b] : 0;
+  const int eos_len = rt.eos_at ? rt.eos_at[seg] : 0x7fffffff;
+  const mt3_sampling sp = *sa.params;
+  const uint64_t* srow = sa.stream.rows ? seg_table_row(sa.stream, seg) : nullptr;
+  const uint64_t stream = srow ? *srow : static_cast<uint64_t>(static_cast<int64_t>(sa.seg0) + seg);
+  if (ls.ss) {                                           // the folded logits projection, as the greedy kernel applies it
+    if (wave == 0) {
+      float p = lane < ls.n_ss ? ls.ss[static_cast<size_t>(b) * ls.n_ss + lane] : 0.f;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
+      if (lane == 0) s_rs = rsqrtf(p / static_cast<float>(ls.dim) + 1e-6f);
+    }
+    __syncthreads();
+    const float rs = s_rs;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const int i = tid + u * 256;
+      xv[u] *= rs;
+      if (i < vocab) row[i] = xv[u];
+    }
+  }
+  const bool free_pick = !was_done && ptok == 0 && t + 1 < eos_len;
+  int pick = 0x7fffffff;                                 // thread 0's, after the block below
+  if (free_pick) {
+    // the candidates: ids of the vocabulary whose logit the mask and the grammar leave above -inf
+    float z[kPer];
+    unsigned long long key[kPer];
+    bool keep[kPer];
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const int i = tid + u * 256;
+      bool c = i < vocab && mask_allows(mw[u], tid) && xv[u] > kMaskedLogit;     // (i & 31 == tid & 31)
+      if (c && a.gr.on) c = mt3g_allowed(&a.gr.g, gs, i);
+      keep[u] = c;
+      z[u] = c ? xv[u] / sp.temperature : kMaskedLogit;
+      key[u] = c ? cand_key(xv[u], i) : 0ull;
+    }
+    if (sp.top_k > 0 || sp.top_p > 0.f) {
+      unsigned long long w[kPer];
+      if (sp.top_k > 0) {
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) w[u] = keep[u] ? 1ull : 0ull;
+      } else {
+        float m = kMaskedLogit;
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) m = fmaxf(m, z[u]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if (lane == 0) s_m[wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+#pragma unroll
+        for (int u = 0; u < kPer; ++u)                   // softmax mass in units of 2^-40 of the largest, truncated
+          w[u] = keep[u] ? static_cast<unsigned long long>(expf(z[u] - m) * 1099511627776.0f) : 0ull;
+      }
+      unsigned long long tot = 0;
+#pragma unroll
+      for (int u = 0; u < kPer; ++u) tot += w[u];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+      if (lane == 0) s_tot[wave] = tot;
+      __syncthreads();
+      tot = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+      unsigned long long target;
+      if (sp.top_k > 0) {
+        target = static_cast<unsigned long long>(sp.top_k);
+      } else {
+        target = static_cast<unsigned long long>(ceil(static_cast<double>(sp.top_p) * static_cast<double>(tot)));
+        if (target < 1) target = 1;
+      }
+      if (target > tot) target = tot;
+      unsigned long long prefix = 0;                     // the digits of the threshold key found so far
+      if (tot > 0) {
+        for (int shift = 40; shift >= 0; shift -= 8) {
+          s_hist[tid] = 0;
+          __syncthreads();
+#pragma unroll
+          for (int u = 0; u < kPer; ++u)
+            if (w[u] && (key[u] >> (shift + 8)) == (prefix >> (shift + 8)))
+              atomicAdd(&s_hist[(key[u] >> shift) & 255], w[u]);
+          __syncthreads();
+          // thread tid owns bin 255 - tid: the inclusive scan over threads is the weight at or above the bin
+          const unsigned long long v = s_hist[255 - tid];
+          unsigned long long inc = v;
+#pragma unroll
+          for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long n = __shfl_up(inc, o);
+            if (lane >= o) inc += n;
+          }
+          if (lane == 63) s_wsum[wave] = inc;
+          __syncthreads();
+          for (int x = 0; x < wave; ++x) inc += s_wsum[x];
+          if (inc - v < target && target <= inc) {       // exactly one bin crosses the target (1 <= target <= total)
+            s_digit = 255 - tid;
+            s_target = target - (inc - v);
+          }
+          __syncthreads();
+          prefix |= static_cast<unsigned long long>(s_digit) << shift;
+          target = s_target;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kPer; ++u) keep[u] = w[u] != 0 && tot > 0 && key[u] >= prefix;
+    }
+    // the draw: the best of z + g over the kept set
+    float bv = kMaskedLogit;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      if (!keep[u]) continue;
+      const int i = tid + u * 256;
+      const float v = z[u] + mt3s_gumbel(mt3s_bits(sp.seed, stream, t, i));
+      if (cand_better(v, i, bv, bi)) {
+        bv = v;
+        bi = i;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (cand_better(ov, oi, bv, bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      s_v[wave] = bv;
+      s_i[wave] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+      for (int x = 1; x < 4; ++x)
+        if (cand_better(s_v[x], s_i[x], bv, bi)) {
+          bv = s_v[x];
+          bi = s_i[x];
+        }
+      pick = bi;
+    }
+  }
+  __syncthreads();              // every thread has read the slot's counters: thread 0 may write them
+  if (tid == 0) {
+    int tok;
+    bool finished = false;
+    if (ptok != 0) {
+      tok = was_done ? 0 : ptok;                         // inside the prompt: the token is given
+    } else {
+      // a row with no candidate at all (every logit -inf or NaN: the host checks rule it out) ends: EOS
+      tok = was_done ? 0 : (t + 1 >= eos_len || pick == 0x7fffffff ? 1 : pick);
+      finished = !was_done && tok == 1;
+    }
+    if (!was_done && rt.max_len > 0 && t + 1 >= rt.max_len) finished = true;
+    if (finished) {
+      st.done[b] = 1;
+      atomicAdd(st.n_done, 1);
+    }
+    a.ids[static_cast<size_t>(out_row) * a.ids_stride + t] = tok;
+    if (a.gr.on && !was_done) st.gram[b] = mt3g_advance(&a.gr.g, gs, tok);
+    st.cur_tok[b] = tok;
+    st.step[b] = t + 1;
+    s_tok = tok;
+    s_t = t + 1;
+  }
+  __syncthreads();
+  if (a.in.y) put_input_row(a.in, b, s_tok, s_t, tid, 256);
+}
+
+int launch_sample_step(const SampleStepArgs& sa, hipStream_t s) {
+  const ArgmaxStepArgs& a = sa.a;
+  if (!sa.params) return mt3::fail(MT3_ERR_INVALID, "sample_step: the sampling parameters are missing");
+  if (a.beam.f || a.forced)
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: sampling is a greedy-path feature (no beam-1, no teacher forcing)");
+  if (a.vocab < 2 || a.vocab > MT3_SAMPLING_MAX_VOCAB)
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: the vocabulary must be 2 .. 2048");
+  if (a.ls.ss && (a.ls.n_ss <= 0 || a.ls.n_ss > 64 || a.ls.dim <= 0))
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: the row scale needs 1 .. 64 partial sums");
+  if (const int rc = bad_input_row(a.in, "sample_step")) return rc;
+  if (a.tm.rows && a.tm.stride != (a.vocab + 31) / 32)
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: token masks are ceil(vocab / 32) words");
+  if (a.tp.rows && a.tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "sample_step: prompts have a stride of at least 1");
+  if (a.gr.on && (!a.st.gram || bad_token_grammar(a.gr.g, a.vocab)))
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: the grammar needs the slots' states and valid ranges");
+  if (sa.stream.rows && sa.stream.stride != 1)
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: the stream table holds one entry per row");
+  hipLaunchKernelGGL(sample_step_kernel, dim3(a.B), dim3(256), 0, s, sa);
+  MT3_HIP_CHECK(hipGetLastError());
+  return MT3_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- row retirement
 // Compaction of a row group's live slots (CompactArgs, kernels.h).  Three launches on the group's stream, issued at a
 // poll of the early-exit loop when the live rows fit a smaller number of 32-row GEMM tiles:
@@ -1563,14 +1810,15 @@ extern "C" int mt3_op_beam_search_prompted(const float* d_logits, const float* d
                             h_forks, h_steps_run, stream, d_masks, n_masks, d_row_mask, d_prompts, stride, d_row_prompt);
 }
 
-// shared body of mt3_op_token_steps_scripted (masked == false), mt3_op_token_steps_masked, mt3_op_token_steps_prompted and
-// mt3_op_token_steps_grammar
+// shared body of mt3_op_token_steps_scripted (masked == false), mt3_op_token_steps_masked, mt3_op_token_steps_prompted,
+// mt3_op_token_steps_grammar and mt3_op_token_steps_sampled (h_sampling == nullptr: every statement the others run, no other)
 static int token_steps_driver(const std::string& who, bool masked, float* d_logits, const float* d_ss, int32_t n_ss,
                               int32_t dim, int32_t rows, int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len,
                               int32_t* d_ids, int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
                               const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
                               const int32_t* d_row_prompt = nullptr, const mt3_token_grammar* h_grammar = nullptr,
-                              int32_t* h_state = nullptr) {
+                              int32_t* h_state = nullptr, const mt3_sampling* h_sampling = nullptr,
+                              const uint64_t* h_row_stream = nullptr) {
   if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
       max_len < 0 || bad_scale(d_ss, n_ss, dim))
@@ -1578,6 +1826,11 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
                                             "the row scale out of range");
   if (h_grammar)                                  // the descriptor itself: before anything is read back from the device
     if (const char* bad = mt3k::bad_token_grammar(*h_grammar, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  if (h_sampling) {                               // as mt3_engine_set_sampling and mt3_engine_decode check it
+    if (const char* bad = mt3s_bad_params(h_sampling)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+    if (vocab > MT3_SAMPLING_MAX_VOCAB) return mt3::fail(MT3_ERR_INVALID, who + ": sampling needs a vocabulary of at most 2048");
+    if (mode != 0) return mt3::fail(MT3_ERR_INVALID, who + ": beam-1 (mode 1) does not sample");
+  }
   mt3k::TokenMask tm{};
   if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, rows, vocab, 2, &tm));
   mt3k::TokenPrompt tp{};
@@ -1616,10 +1869,30 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
   MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
   if (gr.on) MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.st.gram), mt3g_initial(&gr.g), n, s));
   MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
+  // sampling: the parameters and the rows' streams in device memory of their own (freed with `sm`)
+  Scratch sm;
+  mt3k::SampleStepArgs sa{};
+  if (h_sampling) {
+    MT3_OP_TRY(sm.alloc(Scratch::piece(sizeof(mt3_sampling)) + Scratch::piece(n * 8) + Scratch::piece(n * 4), s));
+    mt3_sampling* d_sp = sm.take<mt3_sampling>(1);
+    uint64_t* d_stream = sm.take<uint64_t>(n);
+    int* d_row = sm.take<int>(n);                              // row i's stream is entry i of the table
+    MT3_HIP_CHECK(hipMemcpyAsync(d_sp, h_sampling, sizeof(mt3_sampling), hipMemcpyHostToDevice, s));
+    if (h_row_stream) MT3_HIP_CHECK(hipMemcpyAsync(d_stream, h_row_stream, n * 8, hipMemcpyHostToDevice, s));
+    MT3_OP_TRY(mt3k::launch_iota(d_row, rows, s));
+    MT3_HIP_CHECK(hipStreamSynchronize(s));                    // the host arrays are the caller's
+    sa.params = d_sp;
+    if (h_row_stream) sa.stream = mt3k::SampleStream{d_stream, d_row, nullptr, 1};
+  }
   for (int t = 0; t < num_steps; ++t) {
     a.logits = d_logits + static_cast<size_t>(t) * n * vocab;
     a.ls = mt3k::LogitScale{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_argmax_step(a, s));
+    if (h_sampling) {
+      sa.a = a;
+      MT3_OP_TRY(mt3k::launch_sample_step(sa, s));
+    } else {
+      MT3_OP_TRY(mt3k::launch_argmax_step(a, s));
+    }
     MT3_HIP_CHECK(hipMemcpyAsync(h_done + static_cast<size_t>(t) * n, a.st.done, n * 4, hipMemcpyDeviceToHost, s));
     if (gr.on && h_state)
       MT3_HIP_CHECK(hipMemcpyAsync(h_state + static_cast<size_t>(t) * n, a.st.gram, n * 4, hipMemcpyDeviceToHost, s));
@@ -1677,6 +1950,17 @@ extern "C" int mt3_op_token_steps_grammar(float* d_logits, const float* d_ss, in
   return token_steps_driver("mt3_op_token_steps_grammar", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
                             num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
                             d_row_prompt, h_grammar, h_state);
+}
+
+extern "C" int mt3_op_token_steps_sampled(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                          int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                          int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                                          const int32_t* d_row_mask, const int32_t* d_prompts, int32_t stride,
+                                          const int32_t* d_row_prompt, const mt3_token_grammar* h_grammar,
+                                          int32_t* h_state, const mt3_sampling* h_sampling, const uint64_t* h_row_stream) {
+  return token_steps_driver("mt3_op_token_steps_sampled", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
+                            num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
+                            d_row_prompt, h_grammar, h_state, h_sampling, h_row_stream);
 }
 
 extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots,

@@ -119,15 +119,17 @@ struct LayerDev {
 // never share a captured graph
 // 512 = the event grammar (mt3_engine_set_token_grammar): the step ends with the GRAMMAR token / beam kernel, so steps with
 // a grammar never share a captured graph with steps without one
+// 1024 = temperature sampling (mt3_engine_set_sampling): the step ends with sample_step_kernel in the token kernel's place,
+// so sampled and unsampled steps never share a captured graph
 constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kVarMask = 128,
-              kVarPrompt = 256, kVarGrammar = 512, kNumVariants = 1024;
+              kVarPrompt = 256, kVarGrammar = 512, kVarSample = 1024, kNumVariants = 2048;
 // not a step variant of its own (never an index into graph_exec): set in GroupRun::variant when the decode runs as SEVERAL
 // row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
 // keeps such steps apart from a lone stream's steps of the same shape
-constexpr int kVarBeside = 1024;
+constexpr int kVarBeside = 2048;
 // not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
 // number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
-constexpr int kVarBeams = 2048, kVarBeamsShift = 12;
+constexpr int kVarBeams = 4096, kVarBeamsShift = 13;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
 // to kStageChunkCap segments each (one encoder pass per chunk)
@@ -284,6 +286,14 @@ struct mt3_engine {
   mt3k::TokenGrammar gr{};       // well-formed decoding (mt3_engine_set_token_grammar, kVarGrammar): the descriptor travels by
                                  // value in the step's kernel arguments (a graph that captured another one is dropped)
   bool gr_seen = false;          // a descriptor has been set before (step graphs may hold it)
+  SegTableHost<uint64_t> sstream;  // temperature sampling (mt3_engine_set_sampling, kVarSample): the noise stream of every
+                                 // segment, one row of one entry each behind an identity index (not set: the stream of
+                                 // segment i is i)
+  mt3_sampling* samp = nullptr;  // device copy of the parameters, allocated by the first set: the sampled step graphs hold
+                                 // its address, so another seed or temperature needs no new graph
+  bool samp_on = false;
+  bool samp_seen = false, samp_table = false;   // sampling has been set before, and then with a stream table: the sampled
+                                 // step graphs hold whether there is one
   int* gram = nullptr;           // [max_batch] per slot: the packed grammar state (SlotState::gram); with a grammar set it
                                  // travels with the slot and is reset with it, without one no launch is handed it
   // In-flight batching (mt3_engine_transcribe): slot_seg maps a slot to the SEGMENT it is decoding (-1: none); a
@@ -944,6 +954,12 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     if (skip & kVarMask) a.tm = seg_view(e->tm, crow0, nullptr);
     if (skip & kVarPrompt) a.tp = seg_view(e->tp, crow0, nullptr);
     if (skip & kVarGrammar) a.gr = e->gr;
+    if (skip & kVarSample) {
+      // the stream table is indexed as the masks are; without one the stream is the row / segment index itself
+      mt3k::SampleStepArgs sa{a, e->samp, e->sstream.n ? seg_view(e->sstream, crow0, nullptr) : mt3k::SampleStream{},
+                              static_cast<int>(crow0)};
+      return mt3k::launch_sample_step(sa, s);
+    }
     return mt3k::launch_argmax_step(a, s);
   }
   LayerDev& L = e->dec[op >> 3];
@@ -2003,6 +2019,16 @@ static int seg_tables_fit(const mt3_engine* e, const char* who, int n, int need,
   return MT3_OK;
 }
 
+// Temperature sampling against a greedy-path job of `n` rows / segments (the beam calls, teacher forcing and scoring ignore
+// it): beam-1 does not sample, and a stream table must cover the job.  MT3_OK and *var |= kVarSample where it is set.
+static int sampling_fits(const mt3_engine* e, const char* who, int n, bool beam1, int* var) {
+  if (!e->samp_on) return MT3_OK;
+  if (beam1) return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": MT3_DECODE_BEAM1 does not sample (clear sampling first)");
+  MT3_TRY(fits(e->sstream, who, n, 0, 0, "the sampling streams'", ": a sampling stream is out of range"));
+  *var |= kVarSample;
+  return MT3_OK;
+}
+
 // shared body of mt3_engine_decode / mt3_engine_decode_forced
 static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t debug_skip,
                        const int32_t* d_forced, float* d_step_logits, int32_t* d_ids, float* d_first_logits,
@@ -2024,6 +2050,7 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_forced: not combinable with BEAM1 / EARLY_EXIT / ASYNC");
   int seg_var = 0;                                       // teacher forcing ignores token masks and prompts
   if (!d_forced) MT3_TRY(seg_tables_fit(e, "mt3_engine_decode", batch, 2, num_steps, &seg_var));
+  if (!d_forced) MT3_TRY(sampling_fits(e, "mt3_engine_decode", batch, beam1, &seg_var));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(reset_slots(e, batch, true, true, s));
   if (d_forced)    // engine-owned copy: the step graph holds ITS address, whatever buffer the caller passes
@@ -2504,6 +2531,7 @@ static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segme
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: the synthetic EOS schedule is shorter than n_segments");
   int seg_var = 0;
   MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe", n_segments, 2, num_steps, &seg_var));
+  MT3_TRY(sampling_fits(e, "mt3_engine_transcribe", n_segments, (flags & MT3_DECODE_BEAM1) != 0, &seg_var));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int L = c.max_decode_len, S = n_segments < c.max_batch ? n_segments : c.max_batch;
   const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
@@ -2992,6 +3020,42 @@ int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g) {
   return MT3_OK;
 }
 
+int mt3_engine_set_sampling(mt3_engine* e, const mt3_sampling* sp, const uint64_t* h_seg_stream, int32_t n_segments) {
+  const std::string fn = "mt3_engine_set_sampling: ";
+  if (!e) return mt3::fail(MT3_ERR_INVALID, fn + "null engine");
+  if (sp) {
+    if (const char* bad = mt3s_bad_params(sp)) return mt3::fail(MT3_ERR_INVALID, fn + bad);
+    if (e->cfg.vocab_size > MT3_SAMPLING_MAX_VOCAB)
+      return mt3::fail(MT3_ERR_INVALID, fn + "sampling needs a vocabulary of at most 2048");
+    if (h_seg_stream && n_segments < 1) return mt3::fail(MT3_ERR_INVALID, fn + "n_segments must be positive with h_seg_stream");
+  }
+  // the streams are a per-segment table of one entry per row behind the identity index (no streams, or clearing: no table);
+  // the shared body refuses an engine that is not finalized or has a decode in flight before it touches the device
+  const bool table = sp && h_seg_stream;
+  std::vector<int32_t> ident(table ? static_cast<size_t>(n_segments) : 0);
+  for (size_t i = 0; i < ident.size(); ++i) ident[i] = static_cast<int32_t>(i);
+  MT3_TRY(set_seg_table(e, e->sstream, fn, "stream", table ? h_seg_stream : nullptr, table ? n_segments : 0, 1, nullptr,
+                        table ? ident.data() : nullptr, n_segments, [](const uint64_t*, int* stat) {
+                          *stat = 0;
+                          return static_cast<const char*>(nullptr);
+                        }));
+  if (!sp) {
+    e->samp_on = false;
+    return MT3_OK;
+  }
+  e->samp_on = false;             // (a failed copy leaves sampling off, not half set)
+  // a setup call: nothing a caller enqueued earlier may still read the parameters this call replaces
+  MT3_HIP_CHECK(hipDeviceSynchronize());
+  // the sampled step graphs hold whether the streams come from a table: the other form and they go
+  if (e->samp_seen && e->samp_table != table) drop_step_graphs(e);
+  e->samp_seen = true;
+  e->samp_table = table;
+  if (!e->samp) MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->samp), sizeof(mt3_sampling)));
+  MT3_HIP_CHECK(hipMemcpy(e->samp, sp, sizeof(mt3_sampling), hipMemcpyHostToDevice));
+  e->samp_on = true;
+  return MT3_OK;
+}
+
 int mt3_debug_engine_set_score_chunk(mt3_engine* e, int32_t segments) {
   if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_score_chunk: engine not finalized");
   if (segments < 0 || segments > e->cfg.max_batch)
@@ -3037,6 +3101,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_TOKEN_MASKS: return e->tm.n;
     case MT3_STATUS_PROMPTS: return e->tp.n;
     case MT3_STATUS_TOKEN_GRAMMAR: return e->gr.on ? 1 : 0;
+    case MT3_STATUS_SAMPLING: return e->samp_on ? 1 : 0;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }
 }

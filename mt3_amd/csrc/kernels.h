@@ -280,6 +280,20 @@ struct ArgmaxStepArgs {
   TokenGrammar gr;      // on == 0: none; else st.gram holds the slots' states
 };
 int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
+// Temperature sampling (mt3_engine_set_sampling; the rule and the noise: include/mt3_hip.h, mt3s_*): the greedy step `a`
+// (no beam state, no teacher forcing) with the pick of a free position drawn by sample_step_kernel, which takes
+// argmax_step_kernel's place in the step.  The parameters are read from DEVICE memory, so that a captured step serves
+// every seed.  The noise stream of a slot is that of its segment: the entry of `stream`, a per-segment table of one
+// uint64 per row indexed as the masks are, or -- no table -- seg0 + the segment index the masks would be indexed by.
+// vocab <= MT3_SAMPLING_MAX_VOCAB: the row lives in registers, eight values per thread.
+using SampleStream = SegTable<uint64_t>;
+struct SampleStepArgs {
+  ArgmaxStepArgs a;
+  const mt3_sampling* params;   // device
+  SampleStream stream;          // rows == nullptr: stream = seg0 + segment
+  int seg0;
+};
+int launch_sample_step(const SampleStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that
 // lives from one step to the next -- the next step's input row in its three forms, layer 0's projected row, position
 // counter, current token, beam-search state, the slot -> row map -- moves from slot perm[i] to slot i (i < n_live) by

@@ -348,6 +348,9 @@ int32_t mt3_token_grammar_advance(const mt3_token_grammar* g, int32_t state, int
 int32_t mt3_token_grammar_allowed(const mt3_token_grammar* g, int32_t state, int32_t id) {
   return g ? mt3g_allowed(g, state, id) : 1;
 }
+// the noise of temperature sampling (mt3s_*, include/mt3_hip.h) as the host computes it
+uint32_t mt3_sampling_bits(uint64_t seed, uint64_t stream, int32_t t, int32_t id) { return mt3s_bits(seed, stream, t, id); }
+float mt3_sampling_gumbel(uint32_t bits) { return mt3s_gumbel(bits); }
 
 // the machine behind mt3_notes_decode (h_note_tokens == nullptr) and mt3_notes_decode_traced; `who` names the entry
 // point in its error messages

@@ -26,6 +26,7 @@ alpha 0.6, which is what the reference's predict_batch_with_aux runs (SURVEY.md 
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import functools
 import json
 import math
@@ -39,6 +40,7 @@ from . import audio_io
 from . import metrics_utils
 from . import network
 from . import note_sequences
+from . import sampling
 from . import spectrograms
 from . import vocabularies
 
@@ -58,7 +60,8 @@ class InferenceModel(object):
 
     def __init__(self, checkpoint_path, model_type="mt3", *, config: Optional[network.T5Config] = None,
                  dtype: str = "float32", batch_size: int = 8, early_exit: bool = True,
-                 decoding: str = "beam1", max_slots: int = 256, schedule: Optional[str] = None, num_beams: int = 4):
+                 decoding: str = "beam1", max_slots: int = 256, schedule: Optional[str] = None, num_beams: int = 4,
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0):
         """dtype: 'float32' (default) = the reference's own precision (gin/model.gin:50 restores and runs
         float32): f32 MFMA operands, f32 K/V cache, token-exact against the oracle.  'bfloat16' is the explicit
         opt-in fast path (bf16 operands and caches, f32 accumulation / residual / softmax; what bench.py times;
@@ -74,7 +77,13 @@ class InferenceModel(object):
         each beam is a decode slot, so a job runs max_slots // num_beams segments at a time.  With schedule='refill' it
         is one mt3_engine_transcribe_beams call per job (Transformer.transcribe(num_beams=k): a segment whose search has
         closed hands its slots to the next segment); with schedule='batch' the segments are encoded and beam-decoded in
-        batch-synchronous chunks of max_slots // num_beams (Transformer.decode_beams).  Same tokens either way."""
+        batch-synchronous chunks of max_slots // num_beams (Transformer.decode_beams).  Same tokens either way.
+        decoding='sample' = t5x temperature_sample (Transformer.set_sampling): every free token is DRAWN from
+        softmax(logits / temperature), cut to the top_k (1 .. 256) most likely tokens or to the smallest set of
+        probability top_p (0 .. 1); 0 turns either off, both on is an error.  The draw of a segment depends on `seed`, the
+        segment's index within its own file and its logits only: a file's notes are the same alone, in any
+        `transcribe_many` / `transcribe_wavs` job and on either schedule (f32; bf16 logits depend on the rows of a launch).
+        `sample(audio, num_samples=n)` draws n transcriptions with seeds seed .. seed + n - 1."""
         if model_type == "ismir2021":
             num_velocity_bins = 127
             self.encoding_spec = note_sequences.NoteEncodingSpec
@@ -96,8 +105,10 @@ class InferenceModel(object):
         self.outputs_length = 1024
         self.sequence_length = {"inputs": self.inputs_length, "targets": self.outputs_length}
         self.early_exit = early_exit
-        if decoding not in ("beam1", "greedy", "beam"):
-            raise ValueError("decoding must be 'beam1', 'greedy' or 'beam', got %r" % (decoding,))
+        if decoding not in ("beam1", "greedy", "beam", "sample"):
+            raise ValueError("decoding must be 'beam1', 'greedy', 'beam' or 'sample', got %r" % (decoding,))
+        self.sampling = sampling.SamplingParams(float(temperature), int(top_k), float(top_p), int(seed)).check()
+        self._job_streams = None                 # per-segment noise streams of the job in flight (None: the segment index)
         if decoding == "beam" and not 1 <= int(num_beams) <= min(8, self.max_slots):
             raise ValueError("num_beams must be 1 .. 8 (and <= max_slots), got %r" % (num_beams,))
         self.decoding = decoding
@@ -262,6 +273,8 @@ class InferenceModel(object):
                 self.model.clear_token_masks()
             if prompts is not None and self.model is not None:
                 self.model.set_prompts(None)
+            if self.decoding == "sample" and self.model is not None:
+                self.model.clear_sampling()
 
     def _set_masks(self, lo: int, hi: int):
         """before an engine call on segments [lo, hi) of the job: their masks and prompts on the engine that will run it"""
@@ -280,6 +293,10 @@ class InferenceModel(object):
             self.model.set_prompts(rows, index if rows else None)
         if self._job_grammar is not None:
             self.model.set_token_grammar(self._job_grammar)
+        if self.decoding == "sample":
+            # the stream of a segment is its index within its own file, whatever else the job or the engine call holds
+            streams = self._job_streams[lo:hi] if self._job_streams is not None else np.arange(lo, hi)
+            self.model.set_sampling(self.sampling, np.asarray(streams, dtype=np.uint64))
 
     # ------------------------------------------------------------------ model call
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
@@ -357,6 +374,25 @@ class InferenceModel(object):
         with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
                                well_formed):
             return self._transcribe_examples(examples)
+
+    def sample(self, audio, num_samples: int = 1, sample_rate: int = SAMPLE_RATE, **kw):
+        """`num_samples` transcriptions of the same audio, drawn with seeds seed .. seed + num_samples - 1 of the model's
+        sampling parameters (decoding='sample' for the length of the call, whatever the model's own decoding is) -> a list
+        of NoteSequences.  kw: the keywords of `__call__` (programs, drums, prompts, well_formed)."""
+        if int(num_samples) < 1:
+            raise ValueError("num_samples must be at least 1, got %r" % (num_samples,))
+        if self.decoding == "beam":
+            raise ValueError("sample() draws on the greedy path: not for a model with decoding='beam'")
+        was = (self.decoding, self.sampling)
+        out = []
+        try:
+            self.decoding = "sample"
+            for i in range(int(num_samples)):
+                self.sampling = dataclasses.replace(was[1], seed=(was[1].seed + i) % (1 << 64))
+                out.append(self(audio, sample_rate, **kw))
+        finally:
+            self.decoding, self.sampling = was
+        return out
 
     def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
@@ -518,8 +554,13 @@ class InferenceModel(object):
             for p, ex in zip(prompts, per_file):
                 rows += self._segment_prompts(p, len(ex)) or [None] * len(ex)
             job_prompts = rows if any(r is not None for r in rows) else None
-        with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts, well_formed):
-            tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
+        self._job_streams = np.concatenate([np.arange(len(ex)) for ex in per_file])
+        try:
+            with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts,
+                                   well_formed):
+                tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
+        finally:
+            self._job_streams = None
         out, at, results = [], 0, []
         for examples in per_file:
             preds = [self.postprocess(t, ex) for t, ex in zip(tokens[at:at + len(examples)], examples)]

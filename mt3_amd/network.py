@@ -403,6 +403,25 @@ class Transformer:
     def clear_token_grammar(self):
         _lib.check(self._lib.mt3_engine_set_token_grammar(self._h, None))
 
+    def set_sampling(self, params=None, seg_stream=None, **kw):
+        """mt3_engine_set_sampling: every later decode / transcribe call (greedy path; not beam1) DRAWS its free tokens --
+        t5x temperature_sample -- until `clear_sampling`.  params: a `sampling.SamplingParams`, or its fields as keywords
+        (temperature=1.0, top_k=0, top_p=0.0, seed=0).  seg_stream: the uint64 noise stream of each batch row / segment of
+        the job (None: row / segment i draws from stream i); a segment's sample depends on (seed, stream) and its logits
+        only, not on the slot, the batch or the schedule.  top_k=1 is greedy.  decode_beams, transcribe(num_beams=...),
+        decode_forced, score and score_segments ignore it."""
+        from . import sampling
+        p = (params if params is not None else sampling.SamplingParams(**kw)).check()
+        st = p.struct()
+        if seg_stream is None:
+            _lib.check(self._lib.mt3_engine_set_sampling(self._h, C.byref(st), None, 0))
+            return
+        ss = np.ascontiguousarray(np.asarray(seg_stream).astype(np.uint64)).reshape(-1)
+        _lib.check(self._lib.mt3_engine_set_sampling(self._h, C.byref(st), ss.ctypes.data, int(ss.size)))
+
+    def clear_sampling(self):
+        _lib.check(self._lib.mt3_engine_set_sampling(self._h, None, None, 0))
+
     def debug_decode(self, num_steps: Optional[int] = None, skip_self_attn: bool = False,
                      skip_cross_attn: bool = False, chains: int = 0, use_graph: bool = True):
         """mt3_debug_engine_decode (include/mt3_hip_debug.h): a decode with kernels left out of every step, for

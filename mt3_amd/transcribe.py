@@ -1,7 +1,8 @@
 """Command line: WAV files -> MIDI files (the notebook's upload / transcribe / download cells in one call).
 
     python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
-                                 [--decoding beam1|greedy|beam] [--num-beams K] [--confidences]
+                                 [--decoding beam1|greedy|beam|sample] [--num-beams K] [--confidences]
+                                 [--temperature T] [--top-k K] [--top-p P] [--seed N]
                                  [--programs P[,P...]] [--no-drums]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
@@ -14,6 +15,9 @@ NAME.confidence.json beside each NAME.mid: one record per note, in the NoteSeque
 `InferenceModel.transcribe_wav_scored` (each file is then a job of its own: decode, then one scoring pass).
 --programs 0,33 restricts the decode of every input to those MIDI programs and --no-drums forbids drum notes (constrained
 decoding: the excluded tokens cannot be picked; `InferenceModel(..., programs=, drums=)`).
+--decoding sample draws every token from softmax(logits / T) (t5x temperature_sample), cut to the --top-k most likely
+tokens or to the smallest set of probability --top-p; --seed picks the draw, which for a file is the same whatever other
+inputs share the job (`InferenceModel(decoding="sample", temperature=, top_k=, top_p=, seed=)`).
 """
 from __future__ import annotations
 
@@ -31,7 +35,13 @@ def plan(argv=None):
     ap.add_argument("--checkpoint", required=True, help="t5x checkpoint directory, .npz, or random:<seed>")
     ap.add_argument("--model", default="mt3", choices=("mt3", "ismir2021"))
     ap.add_argument("--dtype", default="float32", choices=("float32", "bfloat16"))
-    ap.add_argument("--decoding", default="beam1", choices=("beam1", "greedy", "beam"),
+    ap.add_argument("--temperature", type=float, default=1.0, metavar="T", help="--decoding sample: the temperature (> 0)")
+    ap.add_argument("--top-k", type=int, default=0, metavar="K", help="--decoding sample: keep the K most likely tokens "
+                    "(1 .. 256; 0: off)")
+    ap.add_argument("--top-p", type=float, default=0.0, metavar="P", help="--decoding sample: keep the smallest set of "
+                    "tokens of probability P (0 < P < 1; 0: off; not with --top-k)")
+    ap.add_argument("--seed", type=int, default=0, metavar="N", help="--decoding sample: the seed of the draw")
+    ap.add_argument("--decoding", default="beam1", choices=("beam1", "greedy", "beam", "sample"),
                     help="token selection: beam1 (default, the reference's), greedy, or beam (k-beam search, see --num-beams)")
     ap.add_argument("--num-beams", type=int, default=4, metavar="K", help="decodes per segment with --decoding beam (1 .. 8)")
     ap.add_argument("--confidences", action="store_true",
@@ -79,7 +89,8 @@ def main(argv=None) -> int:
     from . import inference, midi_io
     try:
         model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype, decoding=args.decoding,
-                                         num_beams=args.num_beams)
+                                         num_beams=args.num_beams, temperature=args.temperature, top_k=args.top_k,
+                                         top_p=args.top_p, seed=args.seed)
         if args.confidences:
             scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums,
                                                   well_formed=args.well_formed)
