@@ -560,6 +560,115 @@ int32_t mt3_token_grammar_advance(const mt3_token_grammar* g, int32_t state, int
 int32_t mt3_token_grammar_allowed(const mt3_token_grammar* g, int32_t state, int32_t id);
 int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g /* NULL clears */);
 
+/* Note-consistent decoding: the event grammar above plus the set of SOUNDING notes, in the token kernels.  The grammar's
+ * three integers cannot see the three events note_sequences.decode_note_event raises on inside one segment: "note-off for
+ * inactive pitch/program" (a velocity 0, then a pitch that is not sounding on the current program), "pitch/program is
+ * already tied" (the same pair declared twice in one tie section) and "velocity cannot be zero for drum event".  This rule
+ * keeps, per slot, the note decoder's own state and forbids exactly those.
+ *   descriptor mt3_note_grammar: the token grammar `g` (it IS the grammar while the note grammar is set), the velocity ids
+ *              (velocity value v is id velocity_first + v, v < velocity_count; value 0 is the note-off marker) and the drum
+ *              ids.  mt3_codec_note_grammar fills it from a codec.  g.with_ties must be 1: without a tie section the
+ *              notes begun in an earlier segment are legitimately ended here and only the host's carried-over state knows
+ *              them, so a per-segment rule would forbid correct tokens (`ismir2021`-style specs are refused).
+ *              g.program_count and g.pitch_count are at most 128 (MT3_NOTE_MAX_PROGRAMS / MT3_NOTE_MAX_PITCHES).
+ *   state      beyond the grammar's packed int: `note`, one int32 -- bits 0 .. 7 the current program VALUE (initial 0), bit
+ *              31 "the current velocity is zero" (initial clear): the note decoder's initial values, which the training
+ *              targets restate before first use; and `held`, a bit set [program_count][ceil(pitch_count / 32)] of uint32,
+ *              bit p % 32 of word p / 32 of row `program` set = (program, pitch value p) is sounding; all clear at position
+ *              0.  128 x 4 words = 2 KiB per slot at MT3's vocabulary.
+ *   advance    on EVERY emitted token, free or forced, after mt3g_advance's own rule and with the tie-section bit from
+ *              BEFORE it (mt3n_advance): a program id sets the program; a velocity id sets or clears the zero bit; a pitch
+ *              id p inside the tie section sets held[program][p]; after it it sets held[program][p] when the velocity is
+ *              non-zero and clears it when it is zero; every other id leaves the note state alone; a finished slot keeps
+ *              its state.
+ *   allowed    on a FREE pick only, on top of mt3g_allowed (mt3n_allowed): inside the tie section a pitch id is allowed iff
+ *              its bit is clear; after it, with velocity zero, a pitch id is allowed iff its bit is set and no drum id is
+ *              allowed.  An onset of a pitch that is already held stays allowed (the note decoder ends the old note and
+ *              counts nothing).
+ *   rule       a disallowed id is what a masked id is (mt3_engine_set_token_grammar: -inf where the token rule reads it,
+ *              after the row scale and its write-back; never in the top 2 / top 2k; exactly 0 in the log-sum-exp).  Prompts
+ *              win inside the prompt and advance the state; the synthetic EOS schedule still wins; masks intersect.
+ *   k-beam     the state of new slot j is advance(state[parent_j], tok_j), table included: all k parents' tables are read
+ *              before any is written, and a table is copied only where parent_j != j.
+ *   guarantee  every row emitted under the rule is accepted by the per-segment acceptor, for greedy, beam-1, sampled and
+ *              k-beam decodes.  What the engine CANNOT know is what the previous segment left sounding: a tie section may
+ *              still declare a note the host does not hold ("inactive pitch/program in tie section"), and a later note-off
+ *              of that same note in the same segment is then invalid for the host, which never accepted the declaration.
+ *              Closing that takes decoding a file's segments in order, each tie section prompted from the last.
+ * mt3_engine_set_note_grammar is a synchronous setup call, global to the engine; n == NULL clears.  Setting both a token
+ * grammar and a note grammar on one engine is MT3_ERR_INVALID: clear one first.  Setting, changing or clearing it drops
+ * the captured step graphs; steps with it never share a captured graph with other steps, and with it clear every decode
+ * runs the kernels, graphs and bits it ran before.  mt3_engine_decode_forced, mt3_engine_score and
+ * mt3_engine_score_segments ignore it.  MT3_STATUS_NOTE_GRAMMAR reports 0 / 1.
+ * MT3_ERR_INVALID, before any device work: what mt3_engine_set_token_grammar refuses in `g`; g.with_ties == 0; a velocity
+ * or drum range that is empty, outside [3, vocab) or overlaps another range; program_count or pitch_count above 128; a
+ * token grammar set; an engine that is not finalized; a decode in flight.  The room check of the decode / transcribe calls
+ * counts the worst state after the tie section without any pitch or drum id (velocity zero, nothing held). */
+typedef struct mt3_note_grammar {
+  mt3_token_grammar g;
+  int32_t velocity_first, velocity_count, drum_first, drum_count;
+} mt3_note_grammar;
+#define MT3_NOTE_MAX_PROGRAMS 128
+#define MT3_NOTE_MAX_PITCHES 128
+#define MT3_NOTE_ROW_WORDS 4 /* ceil(MT3_NOTE_MAX_PITCHES / 32): the words of one program's row at most */
+#define MT3_NOTE_VELOCITY_ZERO 0x80000000u
+#define MT3_NOTE_PROGRAM 0xffu
+MT3_RULE_FN int32_t mt3n_row_words(const mt3_note_grammar* n) { return (n->g.pitch_count + 31) >> 5; }
+MT3_RULE_FN int32_t mt3n_table_words(const mt3_note_grammar* n) { return n->g.program_count * mt3n_row_words(n); }
+/* the `note` int after `tok` (program and velocity ids; every other id leaves it alone) */
+MT3_RULE_FN int32_t mt3n_note_advance(const mt3_note_grammar* n, int32_t note, int32_t tok) {
+  const uint32_t s = (uint32_t)note, pv = (uint32_t)(tok - n->g.program_first), vv = (uint32_t)(tok - n->velocity_first);
+  if (pv < (uint32_t)n->g.program_count) return (int32_t)((s & ~MT3_NOTE_PROGRAM) | pv);
+  if (vv < (uint32_t)n->velocity_count) return (int32_t)(vv == 0 ? (s | MT3_NOTE_VELOCITY_ZERO) : (s & ~MT3_NOTE_VELOCITY_ZERO));
+  return note;
+}
+/* what `tok`, emitted in grammar state `gram_before` and note state `note`, does to held[program of `note`]: 0 nothing,
+ * 1 sets and 2 clears the bit of pitch value *pitch */
+MT3_RULE_FN int mt3n_pitch_effect(const mt3_note_grammar* n, int32_t gram_before, int32_t note, int32_t tok, int32_t* pitch) {
+  const uint32_t p = (uint32_t)(tok - n->g.pitch_first);
+  if (p >= (uint32_t)n->g.pitch_count) return 0;
+  *pitch = (int32_t)p;
+  if ((uint32_t)gram_before & MT3_GRAMMAR_TIE_SECTION) return 1;
+  return ((uint32_t)note & MT3_NOTE_VELOCITY_ZERO) ? 2 : 1;
+}
+/* what the note rule adds to mt3g_allowed; `row` = held[program of `note`], mt3n_row_words words */
+MT3_RULE_FN int mt3n_allowed_extra(const mt3_note_grammar* n, int32_t gram, int32_t note, const uint32_t* row, int32_t id) {
+  const uint32_t p = (uint32_t)(id - n->g.pitch_first);
+  if (p < (uint32_t)n->g.pitch_count) {
+    const int bit = (int)((row[p >> 5] >> (p & 31)) & 1u);
+    if ((uint32_t)gram & MT3_GRAMMAR_TIE_SECTION) return !bit;
+    return ((uint32_t)note & MT3_NOTE_VELOCITY_ZERO) ? bit : 1;
+  }
+  if (!((uint32_t)gram & MT3_GRAMMAR_TIE_SECTION) && ((uint32_t)note & MT3_NOTE_VELOCITY_ZERO) &&
+      (uint32_t)(id - n->drum_first) < (uint32_t)n->drum_count)
+    return 0;
+  return 1;
+}
+/* `held` = the slot's whole table, mt3n_table_words words */
+MT3_RULE_FN int mt3n_allowed(const mt3_note_grammar* n, int32_t gram, int32_t note, const uint32_t* held, int32_t id) {
+  return mt3g_allowed(&n->g, gram, id) &&
+         mt3n_allowed_extra(n, gram, note, held + ((uint32_t)note & MT3_NOTE_PROGRAM) * mt3n_row_words(n), id);
+}
+/* the note state after `tok`: updates `held` in place and returns the new `note`; gram_before = the grammar state `tok` was
+ * emitted in (the caller advances that one with mt3g_advance) */
+MT3_RULE_FN int32_t mt3n_advance(const mt3_note_grammar* n, int32_t gram_before, int32_t note, uint32_t* held, int32_t tok) {
+  int32_t p = 0;
+  const int eff = mt3n_pitch_effect(n, gram_before, note, tok, &p);
+  if (eff) {
+    uint32_t* w = held + ((uint32_t)note & MT3_NOTE_PROGRAM) * mt3n_row_words(n) + (p >> 5);
+    *w = eff == 1 ? (*w | (1u << (p & 31))) : (*w & ~(1u << (p & 31)));
+  }
+  return mt3n_note_advance(n, note, tok);
+}
+/* the inline functions above as exported symbols (gram_before / gram: the packed grammar state, mt3_token_grammar_*) */
+int32_t mt3_note_grammar_table_words(const mt3_note_grammar* n);
+int32_t mt3_note_grammar_advance(const mt3_note_grammar* n, int32_t gram_before, int32_t note, uint32_t* held, int32_t tok);
+int32_t mt3_note_grammar_allowed(const mt3_note_grammar* n, int32_t gram, int32_t note, const uint32_t* held, int32_t id);
+/* MT3_OK, or MT3_ERR_INVALID with what is wrong with the descriptor for a vocabulary of `vocab` ids (what
+ * mt3_engine_set_note_grammar checks; no engine and no device needed) */
+int mt3_note_grammar_check(const mt3_note_grammar* n, int32_t vocab);
+int mt3_engine_set_note_grammar(mt3_engine* e, const mt3_note_grammar* n /* NULL clears */);
+
 /* Temperature sampling with top-k / top-p: t5x decoding.temperature_sample in the greedy token kernel's place.  [from
  * memory] -- t5x is not at hand, as for the beam rule; what binds is that the three statements of the rule agree: the
  * inline functions below (mt3s_*), the token kernel that compiles them, and the numpy restatement mt3_amd/sampling.py.
@@ -741,7 +850,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_TOKEN_MASKS = 12 /* masks set by mt3_engine_set_token_masks (0: none) */,
        MT3_STATUS_PROMPTS = 13 /* prompts set by mt3_engine_set_prompts (0: none) */,
        MT3_STATUS_TOKEN_GRAMMAR = 14 /* 1: a grammar is set by mt3_engine_set_token_grammar (0: none) */,
-       MT3_STATUS_SAMPLING = 15 /* 1: sampling is set by mt3_engine_set_sampling (0: none) */ };
+       MT3_STATUS_SAMPLING = 15 /* 1: sampling is set by mt3_engine_set_sampling (0: none) */,
+       MT3_STATUS_NOTE_GRAMMAR = 16 /* 1: a note grammar is set by mt3_engine_set_note_grammar (0: none) */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -961,6 +1071,25 @@ int mt3_op_token_steps_sampled(float* d_logits, const float* d_ss, int32_t n_ss,
                                const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
                                const mt3_token_grammar* h_grammar, int32_t* h_state, const mt3_sampling* h_sampling,
                                const uint64_t* h_row_stream);
+/* The grammar drivers with the note rule (mt3_engine_set_note_grammar states it): h_notes is a HOST descriptor, checked
+ * first as mt3_engine_set_note_grammar checks it and, with a mask, for the room the rule leaves (MT3_ERR_INVALID); its `g`
+ * member is the grammar.  NULL: the calls are mt3_op_token_steps_sampled / mt3_op_beam_search_grammar with a NULL
+ * grammar, bit for bit.  h_state as there; h_note (HOST, [num_steps][slots], may be NULL) receives the `note` int of every
+ * slot after each step and h_held (HOST, [num_steps][slots][program_count * ceil(pitch_count / 32)], may be NULL) the whole
+ * table of every slot after each step (slots = rows, or elems * k). */
+int mt3_op_token_steps_notes(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
+                             int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
+                             void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                             const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                             const mt3_note_grammar* h_notes, int32_t* h_state, const mt3_sampling* h_sampling,
+                             const uint64_t* h_row_stream, int32_t* h_note, uint32_t* h_held);
+int mt3_op_beam_search_notes(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                             int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                             const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
+                             float* d_y_next, int32_t* h_trace, float* h_live, int32_t* h_forks, int32_t* h_steps_run,
+                             void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                             const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                             const mt3_note_grammar* h_notes, int32_t* h_state, int32_t* h_note, uint32_t* h_held);
 /* The fork copies of one k-beam step on caller-owned caches: for every slot with d_fork_src[slot] >= 0 and
  * d_done[slot] == 0, positions [0, d_step[slot]) of row d_fork_src[slot] are copied into row d_slot_row[slot] of every
  * layer's K and V cache [rows][H][cap][64] of kv_esize-byte elements (1, 2 or 4) and, where given, of its scale pairs
@@ -1214,6 +1343,10 @@ int mt3_codec_token_mask(const mt3_codec* c, int32_t vocab, const int32_t* progr
  * without a pitch, tie or program range, max_steps < 1, max_steps above the codec's largest shift (a canonical stream
  * then needs two shifts in a row, which the rule forbids), or ranges that do not fit below vocab. */
 int mt3_codec_token_grammar(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t max_steps, mt3_token_grammar* out);
+/* The note grammar of a codec (mt3_engine_set_note_grammar): mt3_codec_token_grammar's descriptor plus the id ranges of
+ * the codec's velocity and drum events.  MT3_ERR_INVALID as there, and for a codec without a velocity or drum range, a spec
+ * without a tie section, or more than 128 programs or pitches. */
+int mt3_codec_note_grammar(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t max_steps, mt3_note_grammar* out);
 /* tokens: concatenated per-segment token rows (already trimmed at EOS); seg_offsets [n_segments+1];
  * h_has_max_time==NULL -> the combiner rule (max_time = next segment's start, none for the last);
  * otherwise explicit per-segment max_time (decode_events' own argument). */

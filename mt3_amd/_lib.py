@@ -26,7 +26,7 @@ DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
  STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS, STATUS_TOKEN_MASKS,
- STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR, STATUS_SAMPLING) = range(16)
+ STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR, STATUS_SAMPLING, STATUS_NOTE_GRAMMAR) = range(17)
 SAMPLING_MAX_TOP_K, SAMPLING_MAX_VOCAB = 256, 2048      # mt3_engine_set_sampling
 (MT3_PCM_U8, MT3_PCM_S16, MT3_PCM_S24, MT3_PCM_S32, MT3_PCM_F32, MT3_PCM_F64) = range(6)     # mt3_pcm_decode formats
 PCM_MAX_CHANNELS = 7
@@ -70,6 +70,11 @@ class CodecDesc(C.Structure):
 class TokenGrammar(C.Structure):               # mt3_token_grammar
     _fields_ = [(n, C.c_int32) for n in ("shift_first", "shift_count", "max_steps", "tie_id", "program_first",
                                          "program_count", "pitch_first", "pitch_count", "with_ties")]
+
+
+class NoteGrammar(C.Structure):                # mt3_note_grammar
+    _fields_ = [("g", TokenGrammar)] + [(n, C.c_int32) for n in ("velocity_first", "velocity_count", "drum_first",
+                                                                  "drum_count")]
 
 
 class Sampling(C.Structure):                   # mt3_sampling (sizeof 24: seed is 8-byte aligned)
@@ -161,6 +166,11 @@ SIGNATURES = {
     "mt3_engine_set_token_masks": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     "mt3_engine_set_prompts": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "mt3_engine_set_token_grammar": (C.c_int, [_P, C.POINTER(TokenGrammar)]),
+    "mt3_engine_set_note_grammar": (C.c_int, [_P, C.POINTER(NoteGrammar)]),
+    "mt3_note_grammar_table_words": (C.c_int32, [C.POINTER(NoteGrammar)]),
+    "mt3_note_grammar_advance": (C.c_int32, [C.POINTER(NoteGrammar), C.c_int32, C.c_int32, _P, C.c_int32]),
+    "mt3_note_grammar_allowed": (C.c_int32, [C.POINTER(NoteGrammar), C.c_int32, C.c_int32, _P, C.c_int32]),
+    "mt3_note_grammar_check": (C.c_int, [C.POINTER(NoteGrammar), C.c_int32]),
     "mt3_token_grammar_initial": (C.c_int32, [C.POINTER(TokenGrammar)]),
     "mt3_token_grammar_advance": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
     "mt3_token_grammar_allowed": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
@@ -226,6 +236,13 @@ SIGNATURES = {
     "mt3_op_token_steps_sampled": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
                                              C.POINTER(TokenGrammar), _P, C.POINTER(Sampling), _P]),
+    "mt3_op_token_steps_notes": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
+                                           C.POINTER(NoteGrammar), _P, C.POINTER(Sampling), _P, _P, _P]),
+    "mt3_op_beam_search_notes": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
+                                           _P, C.c_int32, _P, C.POINTER(NoteGrammar), _P, _P, _P]),
     "mt3_op_beam_reorder": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P),
                                       C.POINTER(_P), _P, _P, _P, _P, _P]),
     "mt3_op_embed_rows": (C.c_int, [C.POINTER(InputRowView), _P, _P, C.c_int32, _P]),
@@ -245,6 +262,8 @@ SIGNATURES = {
     "mt3_codec_decode_event": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mt3_codec_encode_event": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "mt3_codec_token_mask": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, _P, C.c_int32, C.c_int32, _P]),
+    "mt3_codec_note_grammar": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(NoteGrammar)]),
     "mt3_codec_token_grammar": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(TokenGrammar)]),
     "mt3_notes_decode": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64,

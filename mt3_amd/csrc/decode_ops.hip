@@ -21,6 +21,8 @@
 //   ids_to_tokens_kernel GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271), bit-exact.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "common.h"
 #include "device.h"
 #include "kernels.h"
@@ -215,6 +217,67 @@ __device__ __forceinline__ float rule_logit(const float* row, const uint32_t* mr
   return row[i];
 }
 
+// Note-consistent decoding (TokenNotes; the rule: include/mt3_hip.h, mt3n_*).  What the NOTES instantiations read of a slot
+// before the pick: the `note` int and the copy of the current program's row, both at addresses that need only the slot index.
+struct NoteView {
+  int note;
+  uint32_t row[MT3_NOTE_ROW_WORDS];
+};
+__device__ __forceinline__ NoteView load_note_view(const SlotState& st, size_t slot) {
+  NoteView v;
+  v.note = st.note[slot];
+#pragma unroll
+  for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) v.row[x] = st.nrow[slot * MT3_NOTE_ROW_WORDS + x];
+  return v;
+}
+// row[i] under the mask, the grammar and the note rule (the loops that walk the row in memory)
+template <bool MASKED>
+__device__ __forceinline__ float rule_logit_notes(const float* row, const uint32_t* mrow, int i, const mt3_note_grammar* n,
+                                                  int gs, const NoteView& nv) {
+  if (MASKED && mrow && !mask_allows(mrow[i >> 5], i)) return kMaskedLogit;
+  if (!mt3g_allowed(&n->g, gs, i) || !mt3n_allowed_extra(n, gs, nv.note, nv.row, i)) return kMaskedLogit;
+  return row[i];
+}
+// The note state of slot `dst` after it emits `tok` from the state (gs, nv) its PARENT held before the step.  fork: dst is
+// not the parent's slot (a k-beam fork: the caller has copied the parent's table over with the pitch's bit applied on the
+// way, and dst's `note` and row copy are written in full); otherwise only what changes is written.  new_row: the row of the
+// new program where the caller has read it already (from the parent's table), else it is read from dst's own.  Called by
+// the one thread that owns dst's bookkeeping: plain vector read-modify-writes; the pitch's word comes from the row copy, so
+// only a program change reads the table.
+__device__ __forceinline__ void note_commit(const mt3_note_grammar& n, const SlotState& st, size_t dst, int gs,
+                                            const NoteView& nv, int tok, const uint32_t* new_row, bool fork) {
+  const int W = mt3n_row_words(&n);
+  const int nn = mt3n_note_advance(&n, nv.note, tok);
+  int pitch = 0;
+  const int eff = mt3n_pitch_effect(&n, gs, nv.note, tok, &pitch);
+  uint32_t* tab = st.held + dst * st.held_words;
+  uint32_t* nrow = st.nrow + dst * MT3_NOTE_ROW_WORDS;
+  uint32_t r[MT3_NOTE_ROW_WORDS];
+#pragma unroll
+  for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) r[x] = nv.row[x];
+  const bool new_prog = ((nn ^ nv.note) & static_cast<int>(MT3_NOTE_PROGRAM)) != 0;
+  if (eff) {
+    const int w = pitch >> 5;
+    const uint32_t bit = 1u << (pitch & 31), v = eff == 1 ? (nv.row[w] | bit) : (nv.row[w] & ~bit);
+#pragma unroll
+    for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x)
+      if (x == w) r[x] = v;
+    if (!fork) {
+      tab[(static_cast<uint32_t>(nv.note) & MT3_NOTE_PROGRAM) * W + w] = v;
+      nrow[w] = v;
+    }
+  } else if (new_prog) {
+#pragma unroll
+    for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x)
+      r[x] = x < W ? (new_row ? new_row[x] : tab[(static_cast<uint32_t>(nn) & MT3_NOTE_PROGRAM) * W + x]) : 0u;
+  }
+  if (fork || (new_prog && !eff)) {
+#pragma unroll
+    for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) nrow[x] = r[x];
+  }
+  if (fork || nn != nv.note) st.note[dst] = nn;
+}
+
 // Prompted decoding (TokenPrompt): the prompt token of segment `seg` at position t, 0 = the slot is past its prompt or has
 // none; never reads a position at or past the stride
 __device__ __forceinline__ int prompt_token(const TokenPrompt& tp, int seg, int t) {
@@ -245,7 +308,11 @@ __device__ __forceinline__ int prompt_token(const TokenPrompt& tp, int seg, int 
 //   emits, free, forced by the prompt or by the EOS schedule.  A fourth flag, but only on the <MASKED, PROMPT> forms: a
 //   grammar step without masks or prompts passes empty tables (no mask row: no word is loaded; stride 0: no prompt token).
 //   GRAMMAR = false compiles from the statements the kernel had before the grammar existed.
-template <bool BEAM1, bool MASKED, bool PROMPT, bool GRAMMAR = false>
+// NOTES = true  : on top of GRAMMAR only (a.gr.g == a.nt.n.g): the pick is further restricted by the note rule in the slot's
+//   note state (st.note[b] and the row copy st.nrow[b], requested with the grammar state: their addresses need only the
+//   block index), and thread 0 advances that state by the token the slot emits.  NOTES = false compiles from the
+//   statements the kernel had before the note rule existed.
+template <bool BEAM1, bool MASKED, bool PROMPT, bool GRAMMAR = false, bool NOTES = false>
 __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   const SlotState& st = a.st;
   const StepRetire& rt = a.rt;
@@ -297,6 +364,8 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
   // same batch, waited for only where the ids are tested below
   int gs = 0;
   if (GRAMMAR) gs = st.gram[b];
+  NoteView nv{};
+  if (NOTES) nv = load_note_view(st, b);
   // thread 0 issues its state loads up front so that their latency hides behind the reductions
   int was_done = 0, t = 0, blen = -1, eos_len = 0x7fffffff;
   float live = 0.f, best = 0.f, bp_max = 1.f, bp_t = 1.f;
@@ -346,6 +415,11 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
     for (int u = 0; u < kPer; ++u)
       if (!mt3g_allowed(&a.gr.g, gs, tid + u * 256)) xv[u] = kMaskedLogit;
   }
+  if (NOTES && in_regs) {
+#pragma unroll
+    for (int u = 0; u < kPer; ++u)
+      if (!mt3n_allowed_extra(&a.nt.n, gs, nv.note, nv.row, tid + u * 256)) xv[u] = kMaskedLogit;
+  }
   Top2 t2{-3.0e38f, -3.0e38f, 0x7fffffff, 0x7fffffff};
   float acc = 0.f;
   if (in_regs) {
@@ -359,6 +433,11 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
 #pragma unroll
       for (int u = 0; u < kPer; ++u)
         if (tid + u * 256 < vocab) acc += __expf(xv[u] - t2.v1);
+    }
+  } else if (NOTES) {
+    for (int i = tid; i < vocab; i += 256) t2.insert(rule_logit_notes<MASKED>(row, mrow, i, &a.nt.n, gs, nv), i);
+    if (BEAM1) {
+      for (int i = tid; i < vocab; i += 256) acc += __expf(rule_logit_notes<MASKED>(row, mrow, i, &a.nt.n, gs, nv) - t2.v1);
     }
   } else {
     for (int i = tid; i < vocab; i += 256)                                                   // ascending i per thread
@@ -444,6 +523,7 @@ __global__ __launch_bounds__(256) void argmax_step_kernel(ArgmaxStepArgs a) {
     }
     a.ids[static_cast<size_t>(out_row) * a.ids_stride + t] = tok;
     if (GRAMMAR && !was_done) st.gram[b] = mt3g_advance(&a.gr.g, gs, tok);   // a finished slot keeps its last state
+    if (NOTES && !was_done) note_commit(a.nt.n, st, b, gs, nv, tok, nullptr, false);
     // teacher forcing (Transformer.decode on given decoder_input_tokens, network.py:303-361): the NEXT input is
     // the caller's token for position t + 1, whatever this step predicted
     if (!BEAM1 && a.forced) tok = a.forced[static_cast<size_t>(b) * a.forced_stride + t];
@@ -473,8 +553,14 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s) {
   if (a.gr.on && (a.forced || !a.st.gram || bad_token_grammar(a.gr.g, a.vocab)))
     return mt3::fail(MT3_ERR_INVALID, "argmax_step: the grammar needs the slots' states and valid ranges and is not for "
                                       "teacher forcing");
+  if (a.nt.on && (!a.gr.on || !a.st.note || !a.st.nrow || !a.st.held || bad_note_grammar(a.nt.n, a.vocab) ||
+                  a.st.held_words != mt3n_table_words(&a.nt.n) || std::memcmp(&a.nt.n.g, &a.gr.g, sizeof(a.gr.g)) != 0))
+    return mt3::fail(MT3_ERR_INVALID, "argmax_step: the note rule needs its grammar set as the step's grammar, the slots' "
+                                      "note states and a valid descriptor");
   void (*kernel)(ArgmaxStepArgs);
-  if (a.gr.on) {
+  if (a.nt.on) {
+    kernel = a.beam.f ? argmax_step_kernel<true, true, true, true, true> : argmax_step_kernel<false, true, true, true, true>;
+  } else if (a.gr.on) {
     kernel = a.beam.f ? argmax_step_kernel<true, true, true, true> : argmax_step_kernel<false, true, true, true>;
   } else if (a.tp.rows) {
     if (a.tm.rows) kernel = a.beam.f ? argmax_step_kernel<true, true, true> : argmax_step_kernel<false, true, true>;
@@ -512,6 +598,9 @@ __device__ __forceinline__ unsigned long long cand_key(float v, int i) {
 //              depend on who else is kept.
 //   pick       the cand_better-best of z + g: per thread, per wave by shuffles, over the four waves by thread 0.
 // Every branch on the slot's state (done, inside its prompt, at its scheduled EOS) is block-uniform.
+// NOTES = true: the note rule on top of the grammar (a.nt; argmax_step_kernel's NOTES form says how); NOTES = false compiles
+// from the statements the kernel had before the note rule existed.
+template <bool NOTES>
 __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
   const ArgmaxStepArgs& a = sa.a;
   const SlotState& st = a.st;
@@ -546,6 +635,8 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
   const int t = st.step[b], was_done = st.done[b];
   const int ptok = a.tp.rows ? prompt_token(a.tp, seg, t) : 0;
   const int gs = a.gr.on ? st.gram[b] : 0;
+  NoteView nv{};
+  if (NOTES) nv = load_note_view(st, b);
   const int eos_len = rt.eos_at ? rt.eos_at[seg] : 0x7fffffff;
   const mt3_sampling sp = *sa.params;
   const uint64_t* srow = sa.stream.rows ? seg_table_row(sa.stream, seg) : nullptr;
@@ -578,6 +669,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
       const int i = tid + u * 256;
       bool c = i < vocab && mask_allows(mw[u], tid) && xv[u] > kMaskedLogit;     // (i & 31 == tid & 31)
       if (c && a.gr.on) c = mt3g_allowed(&a.gr.g, gs, i);
+      if (NOTES && c) c = mt3n_allowed_extra(&a.nt.n, gs, nv.note, nv.row, i);
       keep[u] = c;
       z[u] = c ? xv[u] / sp.temperature : kMaskedLogit;
       key[u] = c ? cand_key(xv[u], i) : 0ull;
@@ -704,6 +796,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
     }
     a.ids[static_cast<size_t>(out_row) * a.ids_stride + t] = tok;
     if (a.gr.on && !was_done) st.gram[b] = mt3g_advance(&a.gr.g, gs, tok);
+    if (NOTES && !was_done) note_commit(a.nt.n, st, b, gs, nv, tok, nullptr, false);
     st.cur_tok[b] = tok;
     st.step[b] = t + 1;
     s_tok = tok;
@@ -728,9 +821,14 @@ int launch_sample_step(const SampleStepArgs& sa, hipStream_t s) {
   if (a.tp.rows && a.tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "sample_step: prompts have a stride of at least 1");
   if (a.gr.on && (!a.st.gram || bad_token_grammar(a.gr.g, a.vocab)))
     return mt3::fail(MT3_ERR_INVALID, "sample_step: the grammar needs the slots' states and valid ranges");
+  if (a.nt.on && (!a.gr.on || !a.st.note || !a.st.nrow || !a.st.held || bad_note_grammar(a.nt.n, a.vocab) ||
+                  a.st.held_words != mt3n_table_words(&a.nt.n) || std::memcmp(&a.nt.n.g, &a.gr.g, sizeof(a.gr.g)) != 0))
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: the note rule needs its grammar set as the step's grammar, the slots' "
+                                      "note states and a valid descriptor");
   if (sa.stream.rows && sa.stream.stride != 1)
     return mt3::fail(MT3_ERR_INVALID, "sample_step: the stream table holds one entry per row");
-  hipLaunchKernelGGL(sample_step_kernel, dim3(a.B), dim3(256), 0, s, sa);
+  if (a.nt.on) hipLaunchKernelGGL(sample_step_kernel<true>, dim3(a.B), dim3(256), 0, s, sa);
+  else hipLaunchKernelGGL(sample_step_kernel<false>, dim3(a.B), dim3(256), 0, s, sa);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -782,6 +880,13 @@ __global__ __launch_bounds__(128) void compact_move_kernel(CompactArgs c) {
   if (q)
     for (int k = tid; k < q_n / 4; k += 128)
       reinterpret_cast<float4*>(qo + dst * q_n)[k] = reinterpret_cast<const float4*>(q + src * q_n)[k];
+  if (c.st.note) {
+    // the note table: staged like the rows above (gather into the scratch, scatter back), so that a slot that is the source
+    // of one move and the destination of another is read in full before it is written
+    const uint32_t* h = (GATHER ? c.st.held : c.s_held) + src * c.st.held_words;
+    uint32_t* ho = (GATHER ? c.s_held : c.st.held) + dst * c.st.held_words;
+    for (int k = tid; k < c.st.held_words; k += 128) ho[k] = h[k];
+  }
   if (tid == 0) {
     if (GATHER) {
       c.s_int[kCompactInts * dst + 0] = c.st.slot_row[src];
@@ -789,6 +894,11 @@ __global__ __launch_bounds__(128) void compact_move_kernel(CompactArgs c) {
       c.s_int[kCompactInts * dst + 2] = c.st.cur_tok[src];
       c.s_int[kCompactInts * dst + 3] = c.beam.len ? c.beam.len[src] : 0;
       c.s_int[kCompactInts * dst + 4] = c.st.gram ? c.st.gram[src] : 0;
+      if (c.st.note) {
+        c.s_int[kCompactInts * dst + 5] = c.st.note[src];
+        for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x)
+          c.s_int[kCompactInts * dst + 6 + x] = static_cast<int>(c.st.nrow[src * MT3_NOTE_ROW_WORDS + x]);
+      }
       if (c.st.slot_seg) c.s_seg[dst] = c.st.slot_seg[src];
       if (c.beam.f) {
         c.s_beam[2 * dst + 0] = c.beam.f[src];
@@ -800,6 +910,11 @@ __global__ __launch_bounds__(128) void compact_move_kernel(CompactArgs c) {
       c.st.cur_tok[dst] = c.s_int[kCompactInts * dst + 2];
       if (c.beam.len) c.beam.len[dst] = c.s_int[kCompactInts * dst + 3];
       if (c.st.gram) c.st.gram[dst] = c.s_int[kCompactInts * dst + 4];
+      if (c.st.note) {
+        c.st.note[dst] = c.s_int[kCompactInts * dst + 5];
+        for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x)
+          c.st.nrow[dst * MT3_NOTE_ROW_WORDS + x] = static_cast<uint32_t>(c.s_int[kCompactInts * dst + 6 + x]);
+      }
       if (c.st.slot_seg) c.st.slot_seg[dst] = c.s_seg[dst];
       if (c.beam.f) {
         c.beam.f[dst] = c.s_beam[2 * dst + 0];
@@ -813,7 +928,8 @@ __global__ __launch_bounds__(128) void compact_move_kernel(CompactArgs c) {
 int launch_compact(const CompactArgs& c, hipStream_t s) {
   if (!c.st.done || !c.st.slot_row || !c.st.step || !c.st.cur_tok || !c.in.y || !c.s_y || !c.s_int || !c.perm || c.rows <= 0 ||
       c.in.dim % 16 || c.in.rp.q_n % 4 || (c.in.y_ct && !c.s_y_ct) || (c.in.y_ss && !c.s_y_ss) || (c.in.rp.q_out && !c.s_qkvf) ||
-      (c.beam.f && (!c.s_beam || !c.beam.len)) || (c.st.slot_seg && !c.s_seg))
+      (c.beam.f && (!c.s_beam || !c.beam.len)) || (c.st.slot_seg && !c.s_seg) ||
+      (c.st.note && (!c.st.nrow || !c.st.held || !c.s_held || c.st.held_words <= 0)))
     return mt3::fail(MT3_ERR_INVALID, "compact: bad arguments");
   hipLaunchKernelGGL(compact_plan_kernel, dim3(1), dim3(64), 0, s, c.st.done, c.perm, c.rows);
   hipLaunchKernelGGL(compact_move_kernel<true>, dim3(c.rows), dim3(128), 0, s, c);
@@ -908,6 +1024,10 @@ __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
       a.st.cur_tok[slot] = 0;                                       // BOS
       a.st.done[slot] = 0;
       if (a.st.gram) a.st.gram[slot] = a.gram0;
+      if (a.st.note) {
+        a.st.note[slot] = 0;
+        for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) a.st.nrow[static_cast<size_t>(slot) * MT3_NOTE_ROW_WORDS + x] = 0u;
+      }
       if (a.beam.f) {                                            // t5x beam_search: live log-prob 0, nothing finished
         a.beam.f[slot] = 0.f;
         a.beam.f[a.beam.rows + slot] = 0.f;
@@ -917,6 +1037,8 @@ __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
     }
   }
   if (!restart) return;
+  if (a.st.note)                                                  // nothing sounds at position 0
+    for (int k = tid; k < a.st.held_words; k += 128) a.st.held[static_cast<size_t>(slot) * a.st.held_words + k] = 0u;
   // decoder input of position 0: Embed(BOS) + FixedEmbed[0], in the forms the step reads (embed_kernel)
   put_input_row(a.in, slot, 0, 0, tid, 128);
 }
@@ -976,15 +1098,23 @@ int launch_refill(const RefillArgs& a, hipStream_t s) {
 // every wave leaves its state in LDS before the barrier the merge waits at, so all k parent states are read before lane 0
 // writes any.  Inside a prompt slot j advances its own state by P[t].  As in the token kernel the flag exists on the
 // <MASKED, PROMPT> form only, with empty tables where there are no masks or prompts.
-template <bool MASKED, bool PROMPT, bool GRAMMAR = false>
+// NOTES = true (on top of GRAMMAR only; gr.g == nt.n.g): each beam's logits are further restricted by the note rule in ITS
+// slot's note state, and new slot j gets advance(state[parent_j], tok_j), the table of sounding notes included.  Every wave
+// leaves its `note` int and row copy in LDS with the grammar state; after the merge wave j reads its parent's table into
+// registers (at most 512 words: 8 per lane) -- only where parent_j != j -- and the row of a new program from the parent's
+// table, the block meets at a barrier, and only then are tables, row copies and note ints written: all k parents are read
+// before any slot is written.  The pitch's bit is applied on the way of the copy.
+template <bool MASKED, bool PROMPT, bool GRAMMAR = false, bool NOTES = false>
 __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, LogitScale ls, TokenMask tm, TokenPrompt tp,
-                                                                    TokenGrammar gr) {
+                                                                    TokenGrammar gr, TokenNotes nt) {
   constexpr int kPerLane = 32;                         // vocab <= 2048: lane l holds i = l + 64 * vt + 256 * u
   __shared__ float c_score[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int c_tok[2 * kBeamMaxK * kBeamMaxK];
   __shared__ int s_sel[2 * kBeamMaxK];
   __shared__ int s_tok[kBeamMaxK];
   __shared__ int s_gs[kBeamMaxK];                         // GRAMMAR: the state of each beam's slot before this step
+  __shared__ int s_note[kBeamMaxK], s_par[kBeamMaxK];     // NOTES: each slot's note int before the step; each new slot's parent
+  __shared__ uint32_t s_nrow[kBeamMaxK][MT3_NOTE_ROW_WORDS];   // NOTES: each slot's row copy before the step
   const int k = a.k, k2 = 2 * k, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int s0 = blockIdx.x * k, slot = s0 + w;
   if (a.st.done[s0]) return;                              // retired element: its state is final
@@ -1011,6 +1141,15 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
     gs = a.st.gram[slot];
     if (lane == 0) s_gs[w] = gs;
   }
+  NoteView nv{};
+  if (NOTES) {
+    nv = load_note_view(a.st, slot);
+    if (lane == 0) {
+      s_note[w] = nv.note;
+#pragma unroll
+      for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) s_nrow[w][x] = nv.row[x];
+    }
+  }
   if (PROMPT) {
     // the element's prompt token at its own position, requested in the same batch as the logits (0: not inside a prompt)
     const int ptok = prompt_token(tp, slot_segment(tp.slot_seg, s0, blockIdx.x), t);
@@ -1030,6 +1169,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
         }
         if (closed) atomicAdd(a.st.n_done, k);
       }
+      if (NOTES && lane == 0) note_commit(nt.n, a.st, slot, gs, nv, ptok, nullptr, false);   // its own slot: nothing forks
       if (a.in.y) put_input_row(a.in, slot, ptok, t + 1, lane, 64);
       return;
     }
@@ -1052,6 +1192,11 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
 #pragma unroll
     for (int j = 0; j < kPerLane; ++j)
       if (!mt3g_allowed(&gr.g, gs, lane + 64 * (j >> 3) + 256 * (j & 7))) xv[j] = kMaskedLogit;
+  }
+  if (NOTES) {
+#pragma unroll
+    for (int j = 0; j < kPerLane; ++j)
+      if (!mt3n_allowed_extra(&nt.n, gs, nv.note, nv.row, lane + 64 * (j >> 3) + 256 * (j & 7))) xv[j] = kMaskedLogit;
   }
   // log-sum-exp of the row, in argmax_step_kernel<true>'s order: per thread, per wave, then over the four waves
   float vmax[4], vsum[4];
@@ -1234,6 +1379,7 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
         a.st.cur_tok[s0 + j] = s_tok[j];
         a.st.step[s0 + j] = t + 1;
         if (GRAMMAR) a.st.gram[s0 + j] = mt3g_advance(&gr.g, s_gs[p], s_tok[j]);
+        if (NOTES) s_par[j] = p;
         if (closed) a.st.done[s0 + j] = 1;
       }
       if (forks && !closed) atomicAdd(a.fork_count, forks);    // a closed element's forks are never copied
@@ -1241,12 +1387,49 @@ __global__ __launch_bounds__(64 * kBeamMaxK) void beam_step_kernel(BeamKArgs a, 
     }
   }
   __syncthreads();
+  if (NOTES) {
+    const int p = s_par[w], tok = s_tok[w], pgs = s_gs[p], HW = a.st.held_words, W = mt3n_row_words(&nt.n);
+    NoteView pv;
+    pv.note = s_note[p];
+#pragma unroll
+    for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) pv.row[x] = s_nrow[p][x];
+    int pitch = 0;
+    const int eff = mt3n_pitch_effect(&nt.n, pgs, pv.note, tok, &pitch);
+    const int nn = mt3n_note_advance(&nt.n, pv.note, tok);
+    const bool fork = p != w;                             // wave-uniform
+    const uint32_t* ptab = a.st.held + static_cast<size_t>(s0 + p) * HW;
+    constexpr int kTabPerLane = MT3_NOTE_MAX_PROGRAMS * MT3_NOTE_ROW_WORDS / 64;
+    uint32_t tv[kTabPerLane];
+    if (fork) {
+#pragma unroll
+      for (int x = 0; x < kTabPerLane; ++x) tv[x] = lane + 64 * x < HW ? ptab[lane + 64 * x] : 0u;
+    }
+    const bool new_prog = !eff && ((nn ^ pv.note) & static_cast<int>(MT3_NOTE_PROGRAM)) != 0;
+    uint32_t nr[MT3_NOTE_ROW_WORDS] = {0u, 0u, 0u, 0u};
+    if (new_prog && lane == 0) {
+#pragma unroll
+      for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x)
+        if (x < W) nr[x] = ptab[(static_cast<uint32_t>(nn) & MT3_NOTE_PROGRAM) * W + x];
+    }
+    __syncthreads();                 // every parent's table and row are in registers: now the slots may be written
+    if (fork) {
+      const int target = eff ? static_cast<int>(static_cast<uint32_t>(pv.note) & MT3_NOTE_PROGRAM) * W + (pitch >> 5) : -1;
+      const uint32_t bit = 1u << (pitch & 31);
+      uint32_t* dtab = a.st.held + static_cast<size_t>(slot) * HW;
+#pragma unroll
+      for (int x = 0; x < kTabPerLane; ++x) {
+        const int idx = lane + 64 * x;
+        if (idx < HW) dtab[idx] = idx != target ? tv[x] : (eff == 1 ? (tv[x] | bit) : (tv[x] & ~bit));
+      }
+    }
+    if (lane == 0) note_commit(nt.n, a.st, slot, pgs, pv, tok, new_prog ? nr : nullptr, fork);
+  }
   // the next step's input row of this wave's slot: Embed(tok) + FixedEmbed[t+1]
   if (a.in.y) put_input_row(a.in, slot, s_tok[w], t + 1, lane, 64);
 }
 
 int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp,
-                     const TokenGrammar& gr, hipStream_t s) {
+                     const TokenGrammar& gr, const TokenNotes& nt, hipStream_t s) {
   if (a.k < 1 || a.k > kBeamMaxK || a.elems <= 0 || a.vocab < 2 * a.k || a.vocab > 2048)
     return mt3::fail(MT3_ERR_INVALID, "beam_step: k must be 1 .. 8 and 2k <= vocab <= 2048");
   if (!a.logits || !a.live || !a.fin_score || !a.fin_step || !a.fin_beam || !a.hist_par || !a.hist_tok || !a.st.slot_row ||
@@ -1261,11 +1444,16 @@ int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& 
   if (tp.rows && tp.stride < 1) return mt3::fail(MT3_ERR_INVALID, "beam_step: prompts have a stride of at least 1");
   if (gr.on && (!a.st.gram || bad_token_grammar(gr.g, a.vocab)))
     return mt3::fail(MT3_ERR_INVALID, "beam_step: the grammar needs the slots' states and valid ranges");
-  void (*kernel)(BeamKArgs, LogitScale, TokenMask, TokenPrompt, TokenGrammar);
-  if (gr.on) kernel = beam_step_kernel<true, true, true>;
+  if (nt.on && (!gr.on || !a.st.note || !a.st.nrow || !a.st.held || bad_note_grammar(nt.n, a.vocab) ||
+                a.st.held_words != mt3n_table_words(&nt.n) || std::memcmp(&nt.n.g, &gr.g, sizeof(gr.g)) != 0))
+    return mt3::fail(MT3_ERR_INVALID, "beam_step: the note rule needs its grammar set as the step's grammar, the slots' note "
+                                      "states and a valid descriptor");
+  void (*kernel)(BeamKArgs, LogitScale, TokenMask, TokenPrompt, TokenGrammar, TokenNotes);
+  if (nt.on) kernel = beam_step_kernel<true, true, true, true>;
+  else if (gr.on) kernel = beam_step_kernel<true, true, true>;
   else if (tp.rows) kernel = tm.rows ? beam_step_kernel<true, true> : beam_step_kernel<false, true>;
   else kernel = tm.rows ? beam_step_kernel<true, false> : beam_step_kernel<false, false>;
-  hipLaunchKernelGGL(kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls, tm, tp, gr);
+  hipLaunchKernelGGL(kernel, dim3(a.elems), dim3(64 * a.k), 0, s, a, ls, tm, tp, gr, nt);
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -1439,9 +1627,15 @@ __global__ __launch_bounds__(256) void beam_refill_elem_kernel(BeamRefillArgs a)
       a.b.st.cur_tok[slot] = 0;                               // BOS
       a.b.st.done[slot] = 0;
       if (a.b.st.gram) a.b.st.gram[slot] = a.gram0;
+      if (a.b.st.note) {
+        a.b.st.note[slot] = 0;
+        for (int x = 0; x < MT3_NOTE_ROW_WORDS; ++x) a.b.st.nrow[static_cast<size_t>(slot) * MT3_NOTE_ROW_WORDS + x] = 0u;
+      }
     }
   }
   if (!restart) return;
+  if (a.b.st.note)                                                // nothing sounds at position 0, in any of the k slots
+    for (int x = tid; x < k * a.b.st.held_words; x += 256) a.b.st.held[static_cast<size_t>(s0) * a.b.st.held_words + x] = 0u;
   // decoder input of position 0 for all k slots: Embed(BOS) + FixedEmbed[0], in the forms the step reads (embed_kernel)
   for (int j = 0; j < k; ++j) put_input_row(a.b.in, s0 + j, 0, 0, tid, 256);
 }
@@ -1681,6 +1875,40 @@ int driver_grammar(const std::string& who, const mt3_token_grammar* h_grammar, c
   return MT3_OK;
 }
 
+// the note rule of a notes driver: the descriptor checked as mt3_engine_set_note_grammar checks it, the room it leaves under
+// every mask (with driver_grammar's own check of n.g), and the slots' note states in device memory of their own, all zero:
+// program 0, velocity non-zero, nothing held
+int driver_notes(const std::string& who, const mt3_note_grammar* h_notes, const uint32_t* d_masks, int n_masks, int vocab,
+                 int need, size_t slots, hipStream_t s, Scratch* mem, mt3k::TokenNotes* nt, mt3k::SlotState* st) {
+  if (const char* bad = mt3k::bad_note_grammar(*h_notes, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  const int words = (vocab + 31) / 32;
+  std::vector<uint32_t> h(d_masks ? static_cast<size_t>(n_masks) * words : 0);
+  if (!h.empty()) MT3_HIP_CHECK(hipMemcpy(h.data(), d_masks, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int m = 0; m < (d_masks ? n_masks : 1); ++m)
+    if (mt3k::note_room_after(*h_notes, d_masks ? h.data() + static_cast<size_t>(m) * words : nullptr, vocab) < need)
+      return mt3::fail(MT3_ERR_INVALID, who + ": the note rule (with a mask) leaves fewer than 2 * k ids after a note-off "
+                                              "marker with nothing held");
+  const size_t hw = static_cast<size_t>(mt3n_table_words(h_notes));
+  MT3_OP_TRY(mem->alloc(Scratch::piece(slots * 4) + Scratch::piece(slots * MT3_NOTE_ROW_WORDS * 4) +
+                            Scratch::piece(slots * hw * 4),
+                        s));
+  st->note = mem->take<int>(slots);
+  st->nrow = mem->take<uint32_t>(slots * MT3_NOTE_ROW_WORDS);
+  st->held = mem->take<uint32_t>(slots * hw);
+  st->held_words = static_cast<int>(hw);
+  nt->n = *h_notes;
+  nt->on = 1;
+  return MT3_OK;
+}
+// the slots' note states after a step, into the caller's host arrays (either may be nullptr)
+int driver_notes_out(const mt3k::SlotState& st, size_t slots, int t, int32_t* h_note, uint32_t* h_held, hipStream_t s) {
+  const size_t hw = static_cast<size_t>(st.held_words);
+  if (h_note) MT3_HIP_CHECK(hipMemcpyAsync(h_note + static_cast<size_t>(t) * slots, st.note, slots * 4, hipMemcpyDeviceToHost, s));
+  if (h_held)
+    MT3_HIP_CHECK(hipMemcpyAsync(h_held + static_cast<size_t>(t) * slots * hw, st.held, slots * hw * 4, hipMemcpyDeviceToHost, s));
+  return MT3_OK;
+}
+
 }  // namespace
 
 // shared body of mt3_op_beam_search_scripted (masked == false), mt3_op_beam_search_masked, mt3_op_beam_search_prompted and
@@ -1692,7 +1920,9 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
                               int32_t* h_steps_run, void* stream, const uint32_t* d_masks, int32_t n_masks,
                               const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
                               const int32_t* d_row_prompt = nullptr, const mt3_token_grammar* h_grammar = nullptr,
-                              int32_t* h_state = nullptr) {
+                              int32_t* h_state = nullptr, const mt3_note_grammar* h_notes = nullptr,
+                              int32_t* h_note = nullptr, uint32_t* h_held = nullptr) {
+  if (h_notes) h_grammar = &h_notes->g;             // the note rule's grammar is the grammar
   if (!d_logits || !d_ids || !d_all_ids || !d_scores || !h_trace || !h_live || !h_forks || !h_steps_run)
     return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if (k < 1 || k > mt3k::kBeamMaxK || vocab < 2 * k || vocab > 2048)
@@ -1704,6 +1934,8 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
     return mt3::fail(MT3_ERR_INVALID, who + ": the tables and the next-row output come together, dim_e % 16 == 0");
   if (h_grammar)                                  // the descriptor itself: before anything is read back from the device
     if (const char* bad = mt3k::bad_token_grammar(*h_grammar, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  if (h_notes)
+    if (const char* bad = mt3k::bad_note_grammar(*h_notes, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
   mt3k::TokenMask tm{};
   if (masked) MT3_OP_TRY(driver_masks(who, d_masks, n_masks, d_row_mask, elems, vocab, 2 * k, &tm));
   mt3k::TokenPrompt tp{};
@@ -1744,6 +1976,9 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   b.in.y = d_y_next;
   b.in.dim = dim_e;
   b.max_len = max_len;
+  Scratch nm;
+  mt3k::TokenNotes nt{};
+  if (h_notes) MT3_OP_TRY(driver_notes(who, h_notes, masked ? d_masks : nullptr, n_masks, vocab, 2 * k, n, s, &nm, &nt, &b.st));
   MT3_HIP_CHECK(hipMemsetAsync(b.fork_src, 0xFF, n * 4, s));               // -1: no fork pending
   if (gr.on) MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.st.gram), mt3g_initial(&gr.g), n, s));
   MT3_OP_TRY(mt3k::launch_iota(b.st.slot_row, slots, s));
@@ -1753,7 +1988,8 @@ static int beam_search_driver(const std::string& who, bool masked, const float* 
   for (int t = 0; t < num_steps; ++t) {
     b.logits = const_cast<float*>(d_logits) + static_cast<size_t>(t) * n * vocab;
     const mt3k::LogitScale ls{d_ss ? d_ss + static_cast<size_t>(t) * n * n_ss : nullptr, n_ss, dim};
-    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, tp, gr, s));
+    MT3_OP_TRY(mt3k::launch_beam_step(b, ls, tm, tp, gr, nt, s));
+    if (nt.on) MT3_OP_TRY(driver_notes_out(b.st, n, t, h_note, h_held, s));
     if (gr.on && h_state)
       MT3_HIP_CHECK(hipMemcpyAsync(h_state + static_cast<size_t>(t) * n, b.st.gram, n * 4, hipMemcpyDeviceToHost, s));
     int32_t* tr = h_trace + static_cast<size_t>(t) * 4 * n;
@@ -1818,7 +2054,9 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
                               const int32_t* d_row_mask, const int32_t* d_prompts = nullptr, int32_t stride = 0,
                               const int32_t* d_row_prompt = nullptr, const mt3_token_grammar* h_grammar = nullptr,
                               int32_t* h_state = nullptr, const mt3_sampling* h_sampling = nullptr,
-                              const uint64_t* h_row_stream = nullptr) {
+                              const uint64_t* h_row_stream = nullptr, const mt3_note_grammar* h_notes = nullptr,
+                              int32_t* h_note = nullptr, uint32_t* h_held = nullptr) {
+  if (h_notes) h_grammar = &h_notes->g;             // the note rule's grammar is the grammar
   if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
       max_len < 0 || bad_scale(d_ss, n_ss, dim))
@@ -1826,6 +2064,8 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
                                             "the row scale out of range");
   if (h_grammar)                                  // the descriptor itself: before anything is read back from the device
     if (const char* bad = mt3k::bad_token_grammar(*h_grammar, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
+  if (h_notes)
+    if (const char* bad = mt3k::bad_note_grammar(*h_notes, vocab)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
   if (h_sampling) {                               // as mt3_engine_set_sampling and mt3_engine_decode check it
     if (const char* bad = mt3s_bad_params(h_sampling)) return mt3::fail(MT3_ERR_INVALID, who + ": " + bad);
     if (vocab > MT3_SAMPLING_MAX_VOCAB) return mt3::fail(MT3_ERR_INVALID, who + ": sampling needs a vocabulary of at most 2048");
@@ -1869,6 +2109,8 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
   MT3_HIP_CHECK(hipMemsetAsync(len_row, 0xFF, n * 4, s));
   if (gr.on) MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.st.gram), mt3g_initial(&gr.g), n, s));
   MT3_OP_TRY(upload_brevity(d_bp, num_steps, s));
+  Scratch nm;
+  if (h_notes) MT3_OP_TRY(driver_notes(who, h_notes, masked ? d_masks : nullptr, n_masks, vocab, 2, n, s, &nm, &a.nt, &a.st));
   // sampling: the parameters and the rows' streams in device memory of their own (freed with `sm`)
   Scratch sm;
   mt3k::SampleStepArgs sa{};
@@ -1896,6 +2138,7 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
     MT3_HIP_CHECK(hipMemcpyAsync(h_done + static_cast<size_t>(t) * n, a.st.done, n * 4, hipMemcpyDeviceToHost, s));
     if (gr.on && h_state)
       MT3_HIP_CHECK(hipMemcpyAsync(h_state + static_cast<size_t>(t) * n, a.st.gram, n * 4, hipMemcpyDeviceToHost, s));
+    if (a.nt.on) MT3_OP_TRY(driver_notes_out(a.st, n, t, h_note, h_held, s));
   }
   if (mode == 1) MT3_OP_TRY(mt3k::launch_beam1_finalize(d_ids, num_steps, len_row, rows, s));
   MT3_HIP_CHECK(hipStreamSynchronize(s));
@@ -1961,6 +2204,39 @@ extern "C" int mt3_op_token_steps_sampled(float* d_logits, const float* d_ss, in
   return token_steps_driver("mt3_op_token_steps_sampled", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
                             num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
                             d_row_prompt, h_grammar, h_state, h_sampling, h_row_stream);
+}
+
+extern "C" int mt3_op_token_steps_notes(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                        int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                        int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                                        const int32_t* d_row_mask, const int32_t* d_prompts, int32_t stride,
+                                        const int32_t* d_row_prompt, const mt3_note_grammar* h_notes, int32_t* h_state,
+                                        const mt3_sampling* h_sampling, const uint64_t* h_row_stream, int32_t* h_note,
+                                        uint32_t* h_held) {
+  return token_steps_driver("mt3_op_token_steps_notes", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
+                            num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
+                            d_row_prompt, nullptr, h_state, h_sampling, h_row_stream, h_notes, h_note, h_held);
+}
+
+extern "C" int mt3_op_beam_search_notes(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
+                                        int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
+                                        const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids,
+                                        float* d_scores, float* d_y_next, int32_t* h_trace, float* h_live,
+                                        int32_t* h_forks, int32_t* h_steps_run, void* stream, const uint32_t* d_masks,
+                                        int32_t n_masks, const int32_t* d_row_mask, const int32_t* d_prompts,
+                                        int32_t stride, const int32_t* d_row_prompt, const mt3_note_grammar* h_notes,
+                                        int32_t* h_state, int32_t* h_note, uint32_t* h_held) {
+  return beam_search_driver("mt3_op_beam_search_notes", d_masks != nullptr, d_logits, d_ss, n_ss, dim, elems, k, vocab,
+                            num_steps, max_len, d_table, d_pos, dim_e, d_ids, d_all_ids, d_scores, d_y_next, h_trace, h_live,
+                            h_forks, h_steps_run, stream, d_masks, n_masks, d_row_mask, d_prompts, stride, d_row_prompt,
+                            nullptr, h_state, h_notes, h_note, h_held);
+}
+
+extern "C" int mt3_note_grammar_check(const mt3_note_grammar* n, int32_t vocab) {
+  if (!n) return mt3::fail(MT3_ERR_INVALID, "mt3_note_grammar_check: null descriptor");
+  if (const char* bad = mt3k::bad_note_grammar(*n, vocab))
+    return mt3::fail(MT3_ERR_INVALID, std::string("mt3_note_grammar_check: ") + bad);
+  return MT3_OK;
 }
 
 extern "C" int mt3_op_beam_reorder(int32_t n_layers, int32_t H, int32_t cap, int32_t kv_esize, int32_t slots,

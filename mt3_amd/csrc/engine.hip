@@ -121,15 +121,17 @@ struct LayerDev {
 // a grammar never share a captured graph with steps without one
 // 1024 = temperature sampling (mt3_engine_set_sampling): the step ends with sample_step_kernel in the token kernel's place,
 // so sampled and unsampled steps never share a captured graph
+// 2048 = the note rule (mt3_engine_set_note_grammar; always with 512): the step ends with the NOTES token / sample / beam
+// kernel, so steps with the note rule never share a captured graph with other steps
 constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kVarMask = 128,
-              kVarPrompt = 256, kVarGrammar = 512, kVarSample = 1024, kNumVariants = 2048;
+              kVarPrompt = 256, kVarGrammar = 512, kVarSample = 1024, kVarNotes = 2048, kNumVariants = 4096;
 // not a step variant of its own (never an index into graph_exec): set in GroupRun::variant when the decode runs as SEVERAL
 // row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
 // keeps such steps apart from a lone stream's steps of the same shape
-constexpr int kVarBeside = 2048;
+constexpr int kVarBeside = 4096;
 // not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
 // number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
-constexpr int kVarBeams = 4096, kVarBeamsShift = 13;
+constexpr int kVarBeams = 8192, kVarBeamsShift = 14;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
 // to kStageChunkCap segments each (one encoder pass per chunk)
@@ -286,6 +288,12 @@ struct mt3_engine {
   mt3k::TokenGrammar gr{};       // well-formed decoding (mt3_engine_set_token_grammar, kVarGrammar): the descriptor travels by
                                  // value in the step's kernel arguments (a graph that captured another one is dropped)
   bool gr_seen = false;          // a descriptor has been set before (step graphs may hold it)
+  mt3k::TokenNotes nt{};         // note-consistent decoding (mt3_engine_set_note_grammar, kVarNotes).  While on, gr holds nt.n.g
+                                 // and is on as well: the note rule's grammar is the engine's grammar
+  int* note = nullptr;           // [max_batch] SlotState::note; allocated with the first note grammar, like the three below
+  uint32_t* nrow = nullptr;      // [max_batch][MT3_NOTE_ROW_WORDS] SlotState::nrow
+  uint32_t* held = nullptr;      // [max_batch][held_words] SlotState::held, held_words = mt3n_table_words(&nt.n)
+  uint32_t* cs_held = nullptr;   // [max_batch][held_words] compaction scratch of the tables
   SegTableHost<uint64_t> sstream;  // temperature sampling (mt3_engine_set_sampling, kVarSample): the noise stream of every
                                  // segment, one row of one entry each behind an identity index (not set: the stream of
                                  // segment i is i)
@@ -729,8 +737,15 @@ inline bool chain_op_is_heavy(const mt3_engine* e, int op) {
 // the per-slot state of slots [row0, ...) of the row group that counts its finished slots in n_done[done_slot]
 mt3k::SlotState slot_state(mt3_engine* e, int row0, int done_slot) {
   // (the grammar state only with a grammar set: without one nothing moves, resets or reads it)
-  return mt3k::SlotState{e->done + row0, e->slot_row + row0, e->slot_seg + row0, e->step + row0,
-                         e->cur_tok + row0,  e->n_done + done_slot, e->gr.on ? e->gram + row0 : nullptr};
+  mt3k::SlotState st{e->done + row0, e->slot_row + row0, e->slot_seg + row0, e->step + row0,
+                     e->cur_tok + row0,  e->n_done + done_slot, e->gr.on ? e->gram + row0 : nullptr};
+  if (e->nt.on) {                // (the note state only while the note rule is set, as the grammar state)
+    st.held_words = mt3n_table_words(&e->nt.n);
+    st.note = e->note + row0;
+    st.nrow = e->nrow + static_cast<size_t>(row0) * MT3_NOTE_ROW_WORDS;
+    st.held = e->held + static_cast<size_t>(row0) * st.held_words;
+  }
+  return st;
 }
 
 // the decoder input rows of slots [row0, ...) and what they are written from.  The one place that knows which forms the
@@ -915,7 +930,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     const int* slot_seg = streaming ? e->slot_seg + row0 : nullptr;
     const mt3k::TokenMask tm = (skip & kVarMask) ? seg_view(e->tm, seg0, slot_seg) : mt3k::TokenMask{};
     const mt3k::TokenPrompt tp = (skip & kVarPrompt) ? seg_view(e->tp, seg0, slot_seg) : mt3k::TokenPrompt{};
-    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, tp, (skip & kVarGrammar) ? e->gr : mt3k::TokenGrammar{}, s));
+    MT3_TRY(mt3k::launch_beam_step(b, ls, tm, tp, (skip & kVarGrammar) ? e->gr : mt3k::TokenGrammar{},
+                                   (skip & kVarNotes) ? e->nt : mt3k::TokenNotes{}, s));
     mt3k::BeamReorderArgs r{};
     r.n_layers = nl;
     r.H = H;
@@ -954,6 +970,7 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     if (skip & kVarMask) a.tm = seg_view(e->tm, crow0, nullptr);
     if (skip & kVarPrompt) a.tp = seg_view(e->tp, crow0, nullptr);
     if (skip & kVarGrammar) a.gr = e->gr;
+    if (skip & kVarNotes) a.nt = e->nt;
     if (skip & kVarSample) {
       // the stream table is indexed as the masks are; without one the stream is the row / segment index itself
       mt3k::SampleStepArgs sa{a, e->samp, e->sstream.n ? seg_view(e->sstream, crow0, nullptr) : mt3k::SampleStream{},
@@ -1765,6 +1782,7 @@ static int compact_group(mt3_engine* e, const GroupRun& r, int cur) {
   if (a.in.y_ss) a.s_y_ss = e->cs_y_ss + r0 * (emb / 16);
   if (a.in.rp.q_out) a.s_qkvf = e->cs_qkvf + r0 * n4;
   a.s_int = e->cs_int + mt3k::kCompactInts * r0;
+  if (a.st.note) a.s_held = e->cs_held + r0 * a.st.held_words;
   a.perm = e->cs_perm + r0 + r.slot;
   a.rows = cur;
   if (r.variant & kVarStream) a.s_seg = e->cs_seg + r0;
@@ -1972,6 +1990,11 @@ static int reset_slots(mt3_engine* e, int n, bool counters, bool ids, hipStream_
   MT3_HIP_CHECK(hipMemsetAsync(e->cur_tok, 0, static_cast<size_t>(n) * 4, s));
   if (e->gr.on)
     MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->gram), grammar_initial(e), static_cast<size_t>(n), s));
+  if (e->nt.on) {                // program 0, velocity non-zero, nothing held
+    MT3_HIP_CHECK(hipMemsetAsync(e->note, 0, static_cast<size_t>(n) * 4, s));
+    MT3_HIP_CHECK(hipMemsetAsync(e->nrow, 0, static_cast<size_t>(n) * MT3_NOTE_ROW_WORDS * 4, s));
+    MT3_HIP_CHECK(hipMemsetAsync(e->held, 0, static_cast<size_t>(n) * mt3n_table_words(&e->nt.n) * 4, s));
+  }
   if (ids) MT3_HIP_CHECK(hipMemsetAsync(e->ids, 0, static_cast<size_t>(n) * e->cfg.max_decode_len * 4, s));
   return MT3_OK;
 }
@@ -2013,9 +2036,15 @@ static int seg_tables_fit(const mt3_engine* e, const char* who, int n, int need,
       if ((e->gr.g.with_ties && in_tie < need) || after < need)
         return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": the grammar and a token mask in use leave fewer than 2 * "
                                                              "num_beams ids in the tie section or after a shift");
+      // the note rule's worst state after the tie section has no pitch and no drum id either
+      if (e->nt.on &&
+          mt3k::note_room_after(e->nt.n, r < 0 ? nullptr : e->tm.rows_host.data() + static_cast<size_t>(r) * e->tm.stride,
+                                vocab) < need)
+        return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": the note rule and a token mask in use leave fewer than 2 * "
+                                                             "num_beams ids after a note-off marker with nothing held");
     }
   }
-  *var = (e->tm.n ? kVarMask : 0) | (e->tp.n ? kVarPrompt : 0) | (e->gr.on ? kVarGrammar : 0);
+  *var = (e->tm.n ? kVarMask : 0) | (e->tp.n ? kVarPrompt : 0) | (e->gr.on ? kVarGrammar : 0) | (e->nt.on ? kVarNotes : 0);
   return MT3_OK;
 }
 
@@ -3005,6 +3034,10 @@ int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g) {
       return mt3::fail(MT3_ERR_INVALID, std::string("mt3_engine_set_token_grammar: ") + bad);
   if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_grammar: engine not finalized");
   if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_grammar: a decode is in flight");
+  if (e->nt.on) {                 // the note grammar's `g` is the engine's grammar: it is not this call's to replace or clear
+    if (g) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_token_grammar: a note grammar is set (clear it first)");
+    return MT3_OK;
+  }
   if (!g) {
     e->gr.on = 0;                 // (the descriptor stays: the grammar's step graphs hold it and serve the same one again)
     return MT3_OK;
@@ -3015,6 +3048,40 @@ int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g) {
     drop_step_graphs(e);
   }
   e->gr.g = *g;
+  e->gr.on = 1;
+  e->gr_seen = true;
+  return MT3_OK;
+}
+
+int mt3_engine_set_note_grammar(mt3_engine* e, const mt3_note_grammar* n) {
+  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_note_grammar: null engine");
+  if (n)
+    if (const char* bad = mt3k::bad_note_grammar(*n, e->cfg.vocab_size))
+      return mt3::fail(MT3_ERR_INVALID, std::string("mt3_engine_set_note_grammar: ") + bad);
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_note_grammar: engine not finalized");
+  if (e->pending.active) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_note_grammar: a decode is in flight");
+  if (n && e->gr.on && !e->nt.on)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_set_note_grammar: a token grammar is set (clear it first)");
+  if (!n && !e->nt.on) return MT3_OK;
+  if (n && !e->note) {            // the slots' note states: 2 KiB per slot at the largest descriptor, and as much scratch
+    const size_t Bm = static_cast<size_t>(e->cfg.max_batch);
+    const size_t table = static_cast<size_t>(MT3_NOTE_MAX_PROGRAMS) * MT3_NOTE_ROW_WORDS * 4;
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->nrow), Bm * MT3_NOTE_ROW_WORDS * 4));
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->held), Bm * table));
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->cs_held), Bm * table));
+    MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->note), Bm * 4));
+  }
+  // the step graphs hold the descriptor and the state pointers by value: setting, changing or clearing drops them
+  MT3_HIP_CHECK(hipDeviceSynchronize());
+  drop_step_graphs(e);
+  if (!n) {
+    e->nt.on = 0;
+    e->gr.on = 0;
+    return MT3_OK;
+  }
+  e->nt.n = *n;
+  e->nt.on = 1;
+  e->gr.g = n->g;
   e->gr.on = 1;
   e->gr_seen = true;
   return MT3_OK;
@@ -3100,7 +3167,8 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
     case MT3_STATUS_TOKEN_MASKS: return e->tm.n;
     case MT3_STATUS_PROMPTS: return e->tp.n;
-    case MT3_STATUS_TOKEN_GRAMMAR: return e->gr.on ? 1 : 0;
+    case MT3_STATUS_TOKEN_GRAMMAR: return e->gr.on && !e->nt.on ? 1 : 0;
+    case MT3_STATUS_NOTE_GRAMMAR: return e->nt.on ? 1 : 0;
     case MT3_STATUS_SAMPLING: return e->samp_on ? 1 : 0;
     default: return mt3::fail(MT3_ERR_INVALID, "mt3_engine_status: unknown item");
   }

@@ -127,6 +127,12 @@ struct SlotState {
   int* n_done;
   int* gram;            // [slots] packed state of the event grammar (TokenGrammar; nullptr: not kept -- it then neither
                         // travels with the slot nor is reset)
+  // note-consistent decoding (TokenNotes; the state: include/mt3_hip.h, mt3n_*).  note == nullptr: not kept
+  int* note;            // [slots] current program value | MT3_NOTE_VELOCITY_ZERO
+  uint32_t* nrow;       // [slots][MT3_NOTE_ROW_WORDS] a copy of held[slot][current program]: what the pick reads, at an
+                        // address that needs nothing but the slot index
+  uint32_t* held;       // [slots][held_words] the sounding (program, pitch) pairs
+  int held_words;       // mt3n_table_words of the descriptor in use
 };
 // logits that arrive UNNORMALISED (the logits projection folded into the last layer's MLP out-projection launch): the
 // kernel that picks the token applies the decoder_norm row scale rsqrt(sum(ss[b][0 .. n_ss)) / dim + 1e-6) itself and
@@ -194,6 +200,15 @@ struct TokenGrammar {
   mt3_token_grammar g;
   int on;
 };
+// Note-consistent decoding (mt3_engine_set_note_grammar; the rule: include/mt3_hip.h, mt3n_*).  on selects the NOTES
+// instantiations of the token kernels, which exist on top of the GRAMMAR ones only: the step's TokenGrammar then holds n.g.
+// They read the slot's `note` int and its copy of the current program's row (SlotState::note / nrow) in the batch of the
+// logits, count what the rule disallows as -inf where the grammar does, and the thread that owns the slot's bookkeeping
+// writes the advanced state back: plain read-modify-writes of the row copy and the table, one owner per slot.
+struct TokenNotes {
+  mt3_note_grammar n;
+  int on;
+};
 // the one host-side check of a grammar descriptor against a vocabulary: nullptr, or what is wrong with it
 inline const char* bad_token_grammar(const mt3_token_grammar& g, int vocab) {
   const long long lo[4] = {g.shift_first, g.program_first, g.pitch_first, g.tie_id};
@@ -205,6 +220,33 @@ inline const char* bad_token_grammar(const mt3_token_grammar& g, int vocab) {
       if (lo[i] < lo[j] + n[j] && lo[j] < lo[i] + n[i]) return "grammar ranges overlap";
   if (g.max_steps < 1 || g.max_steps > g.shift_count - 1) return "max_steps must be in [1, shift_count - 1]";
   return nullptr;
+}
+// the one host-side check of a note grammar descriptor against a vocabulary: nullptr, or what is wrong with it
+inline const char* bad_note_grammar(const mt3_note_grammar& n, int vocab) {
+  if (const char* bad = bad_token_grammar(n.g, vocab)) return bad;
+  if (!n.g.with_ties) return "the note rule needs a tie section (with_ties == 1)";
+  if (n.g.program_count > MT3_NOTE_MAX_PROGRAMS || n.g.pitch_count > MT3_NOTE_MAX_PITCHES)
+    return "the note rule keeps at most 128 programs and 128 pitches";
+  const long long lo[6] = {n.velocity_first, n.drum_first, n.g.shift_first, n.g.program_first, n.g.pitch_first, n.g.tie_id};
+  const long long c[6] = {n.velocity_count, n.drum_count, n.g.shift_count, n.g.program_count, n.g.pitch_count, 1};
+  for (int i = 0; i < 2; ++i)
+    if (c[i] < 1 || lo[i] < 3 || lo[i] + c[i] > vocab) return "a velocity or drum range is empty or outside [3, vocab)";
+  for (int i = 0; i < 2; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (lo[i] < lo[j] + c[j] && lo[j] < lo[i] + c[i]) return "a velocity or drum range overlaps another range";
+  return nullptr;
+}
+// grammar_room's count for the note rule: the ids of the worst state after the tie section, which now has no pitch and no
+// drum id either (velocity zero, nothing held); the tie-section state loses nothing (nothing declared yet)
+inline int note_room_after(const mt3_note_grammar& n, const uint32_t* h_mask, int vocab) {
+  const int32_t s_after = static_cast<int32_t>(MT3_GRAMMAR_PREV_SHIFT), note = static_cast<int32_t>(MT3_NOTE_VELOCITY_ZERO);
+  const uint32_t row[MT3_NOTE_ROW_WORDS] = {0, 0, 0, 0};
+  int b = 0;
+  for (int i = 0; i < vocab; ++i) {
+    if (h_mask && !((h_mask[i >> 5] >> (i & 31)) & 1u)) continue;
+    b += mt3g_allowed(&n.g, s_after, i) && mt3n_allowed_extra(&n, s_after, note, row, i);
+  }
+  return b;
 }
 // the ids a free pick may take under grammar `g` and mask `h_mask` (nullptr: none) in the two states that bound every
 // other: *in_tie = the tie-section state, *after = the worst state after it (no shift, no tie)
@@ -278,6 +320,7 @@ struct ArgmaxStepArgs {
   TokenMask tm;         // rows == nullptr: unconstrained
   TokenPrompt tp;       // rows == nullptr: none
   TokenGrammar gr;      // on == 0: none; else st.gram holds the slots' states
+  TokenNotes nt;        // on == 0: none; else gr.g == nt.n.g and st.note / nrow / held hold the slots' note states
 };
 int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // Temperature sampling (mt3_engine_set_sampling; the rule and the noise: include/mt3_hip.h, mt3s_*): the greedy step `a`
@@ -298,7 +341,7 @@ int launch_sample_step(const SampleStepArgs& a, hipStream_t s);
 // lives from one step to the next -- the next step's input row in its three forms, layer 0's projected row, position
 // counter, current token, beam-search state, the slot -> row map -- moves from slot perm[i] to slot i (i < n_live) by
 // way of a scratch copy; slots [n_live, rows) are marked done.  All pointers are those of the group's first slot.
-constexpr int kCompactInts = 5;
+constexpr int kCompactInts = 6 + MT3_NOTE_ROW_WORDS;
 struct CompactArgs {
   SlotState st;         // slot_seg == nullptr: no in-flight batching (a dropped slot decodes nothing: -1)
   InputRow in;          // y / y_ct / y_ss / rp.q_out (each nullptr: not in use), dim, rp.q_n
@@ -308,7 +351,8 @@ struct CompactArgs {
   void* s_y_ct;
   float* s_y_ss;
   float* s_qkvf;
-  int* s_int;           // [rows][kCompactInts]: slot_row, step, cur_tok, beam_len, grammar state
+  int* s_int;           // [rows][kCompactInts]: slot_row, step, cur_tok, beam_len, grammar state, note, the row copy
+  uint32_t* s_held;     // [rows][st.held_words]: the staged copy of the note tables (st.note != nullptr)
   float* s_beam;        // [rows][2]
   int* s_seg;           // [rows]
   int* perm;            // [rows + 1]: perm[i] = source slot of new slot i; perm[rows] = n_live
@@ -378,7 +422,7 @@ struct BeamKArgs {
   int max_len;
 };
 int launch_beam_step(const BeamKArgs& a, const LogitScale& ls, const TokenMask& tm, const TokenPrompt& tp,
-                     const TokenGrammar& gr, hipStream_t s);
+                     const TokenGrammar& gr, const TokenNotes& nt, hipStream_t s);
 // copies positions [0, step[slot]) of row fork_src[slot] into row slot_row[slot] of every layer's self-attention K/V
 // (and e4m3 scale rows), for every slot that forked this step; the grid covers every slot x layer x head
 struct BeamReorderArgs {

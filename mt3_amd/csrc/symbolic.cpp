@@ -341,6 +341,40 @@ int mt3_codec_token_grammar(const mt3_codec* c, int32_t spec, int32_t vocab, int
   return MT3_OK;
 }
 
+int mt3_codec_note_grammar(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t max_steps, mt3_note_grammar* out) {
+  if (!c || !out) return mt3::fail(MT3_ERR_INVALID, "mt3_codec_note_grammar: null argument");
+  mt3_note_grammar n{};
+  if (const int rc = mt3_codec_token_grammar(c, spec, vocab, max_steps, &n.g)) return rc;
+  CodecTable t(c);
+  int velocity = -1, drum = -1;
+  for (int k = 0; k < t.n; ++k) {
+    if (t.type[k] == MT3_EV_VELOCITY) velocity = k;
+    if (t.type[k] == MT3_EV_DRUM) drum = k;
+  }
+  if (velocity < 0 || drum < 0)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_note_grammar: the codec needs a velocity and a drum range");
+  if (t.lo[velocity] != 0)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_note_grammar: the codec's velocity range must start at 0");
+  if (!n.g.with_ties)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_note_grammar: the note rule needs a spec with a tie section");
+  if (n.g.program_count > MT3_NOTE_MAX_PROGRAMS || n.g.pitch_count > MT3_NOTE_MAX_PITCHES)
+    return mt3::fail(MT3_ERR_INVALID, "mt3_codec_note_grammar: more than 128 programs or pitches");
+  n.velocity_first = 3 + t.start[velocity];
+  n.velocity_count = t.hi[velocity] - t.lo[velocity] + 1;
+  n.drum_first = 3 + t.start[drum];
+  n.drum_count = t.hi[drum] - t.lo[drum] + 1;
+  *out = n;
+  return MT3_OK;
+}
+
+int32_t mt3_note_grammar_table_words(const mt3_note_grammar* n) { return n ? mt3n_table_words(n) : 0; }
+int32_t mt3_note_grammar_advance(const mt3_note_grammar* n, int32_t gram_before, int32_t note, uint32_t* held, int32_t tok) {
+  return n && held ? mt3n_advance(n, gram_before, note, held, tok) : note;
+}
+int32_t mt3_note_grammar_allowed(const mt3_note_grammar* n, int32_t gram, int32_t note, const uint32_t* held, int32_t id) {
+  return n && held ? mt3n_allowed(n, gram, note, held, id) : 1;
+}
+
 int32_t mt3_token_grammar_initial(const mt3_token_grammar* g) { return g ? mt3g_initial(g) : 0; }
 int32_t mt3_token_grammar_advance(const mt3_token_grammar* g, int32_t state, int32_t tok) {
   return g ? mt3g_advance(g, state, tok) : state;

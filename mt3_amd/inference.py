@@ -36,6 +36,7 @@ from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
 from . import audio_io
 from . import metrics_utils
 from . import network
@@ -254,20 +255,36 @@ class InferenceModel(object):
         max_steps = int(math.floor(self.inputs_length * cfg.hop_width / cfg.sample_rate * self.codec.steps_per_second))
         return vocabularies.token_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, max_steps)
 
+    def note_grammar(self):
+        """the note grammar of this model's codec, spec and segment length (`vocabularies.note_grammar`); ValueError for a
+        spec without a tie section"""
+        cfg = self.spectrogram_config
+        max_steps = int(math.floor(self.inputs_length * cfg.hop_width / cfg.sample_rate * self.codec.steps_per_second))
+        return vocabularies.note_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, max_steps)
+
     @contextlib.contextmanager
     def _constrained(self, job, prompts=None, well_formed=False):
         """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`), `prompts` (`_segment_prompts` of
-        the whole job) and, with well_formed, the model's event grammar; all are cleared on the way out, also on error"""
+        the whole job) and, with well_formed, the model's event grammar (True) or note grammar ("notes"); all are cleared
+        on the way out, also on error"""
+        if isinstance(well_formed, str) and well_formed != "notes":
+            raise ValueError('well_formed is False, True or "notes", got %r' % (well_formed,))
         self._job_masks = job
         self._job_prompts = prompts
         try:
-            self._job_grammar = self.token_grammar() if well_formed else None
+            if well_formed == "notes":
+                self._job_grammar = self.note_grammar()
+            else:
+                self._job_grammar = self.token_grammar() if well_formed else None
             yield
         finally:
             self._job_masks = None
             self._job_prompts = None
             if self._job_grammar is not None and self.model is not None:
-                self.model.clear_token_grammar()
+                if isinstance(self._job_grammar, _lib.NoteGrammar):
+                    self.model.clear_note_grammar()
+                else:
+                    self.model.clear_token_grammar()
             self._job_grammar = None
             if job is not None and self.model is not None:
                 self.model.clear_token_masks()
@@ -291,7 +308,9 @@ class InferenceModel(object):
                     rows.append(p)
                 index.append(rows.index(p))
             self.model.set_prompts(rows, index if rows else None)
-        if self._job_grammar is not None:
+        if isinstance(self._job_grammar, _lib.NoteGrammar):
+            self.model.set_note_grammar(self._job_grammar)
+        elif self._job_grammar is not None:
             self.model.set_token_grammar(self._job_grammar)
         if self.decoding == "sample":
             # the stream of a segment is its index within its own file, whatever else the job or the engine call holds
@@ -369,6 +388,9 @@ class InferenceModel(object):
         event grammar of the model's codec (Transformer.set_token_grammar), so no token is spent on a shift that runs
         backwards or past the segment's end, a `tie` outside the tie section or a malformed tie section, which the note
         decoder would count in invalid_events / dropped_events and throw away.  Composes with the rest.
+        well_formed="notes": that rule plus the set of sounding notes (Transformer.set_note_grammar): no note-off of a
+        pitch that is not sounding on the current program, no pair declared twice in a tie section, no drum at velocity 0.
+        ValueError for a model whose spec has no tie section.  True keeps the event grammar alone, and its bits.
         `last_event_counts` holds the note decoder's invalid_events / dropped_events of the most recent call."""
         examples = self._examples(audio, sample_rate)
         with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),

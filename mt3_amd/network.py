@@ -403,6 +403,17 @@ class Transformer:
     def clear_token_grammar(self):
         _lib.check(self._lib.mt3_engine_set_token_grammar(self._h, None))
 
+    def set_note_grammar(self, grammar):
+        """mt3_engine_set_note_grammar: note-consistent decoding for every later decode / decode_beams / transcribe call
+        until `clear_note_grammar`.  grammar: a `_lib.NoteGrammar` (`vocabularies.note_grammar`); its `g` member is the
+        event grammar, so no token grammar may be set beside it.  On top of `set_token_grammar`'s rule the token pick never
+        takes a note-off of a pitch that is not sounding on the current program, a second declaration of a pair in the tie
+        section, or a drum at velocity 0.  decode_forced / score / score_segments ignore it."""
+        _lib.check(self._lib.mt3_engine_set_note_grammar(self._h, C.byref(grammar)))
+
+    def clear_note_grammar(self):
+        _lib.check(self._lib.mt3_engine_set_note_grammar(self._h, None))
+
     def set_sampling(self, params=None, seg_stream=None, **kw):
         """mt3_engine_set_sampling: every later decode / transcribe call (greedy path; not beam1) DRAWS its free tokens --
         t5x temperature_sample -- until `clear_sampling`.  params: a `sampling.SamplingParams`, or its fields as keywords

@@ -155,6 +155,20 @@ def token_grammar(codec: event_codec.Codec, vocab_size: int, spec, max_steps: in
     return g
 
 
+def note_grammar(codec: event_codec.Codec, vocab_size: int, spec, max_steps: int) -> _lib.NoteGrammar:
+    """The note grammar of `codec` (`mt3_codec_note_grammar`): what `Transformer.set_note_grammar` takes -- the event
+    grammar of `token_grammar` plus the codec's velocity and drum ids.  ValueError for what the library refuses, a spec
+    without a tie section among it (the notes an earlier segment left sounding are then ended without being declared, which
+    a per-segment rule cannot tell from a note-off of a silent pitch)."""
+    n = _lib.NoteGrammar()
+    lib = _lib.load()
+    rc = lib.mt3_codec_note_grammar(C.byref(codec.desc), int(getattr(spec, "spec_id", spec)), int(vocab_size),
+                                    int(max_steps), C.byref(n))
+    if rc != 0:
+        raise ValueError(lib.mt3_last_error().decode())
+    return n
+
+
 def tie_section_prompt(codec: event_codec.Codec, notes, remove_redundant_programs: bool = False) -> list:
     """The vocabulary ids of the tie section that declares `notes`, an iterable of (program, pitch), as still sounding: a
     prompt for `Transformer.set_prompts` / the `prompts=` keyword of the transcribing methods.  It is the section the
