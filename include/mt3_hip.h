@@ -1281,6 +1281,14 @@ int mt3_op_gemm_x6(const float* d_A, const void* d_W_hi, const void* d_W_mid, co
 /* mt3_op_encoder_attention in the f32 engine's default arithmetic: Q, K, V and P as three bf16 planes each.  d_qkv f32
  * [B, T, 3, H, 64] -> d_out f32 [B, T, H*64].  MT3_ERR_INVALID: a NULL pointer, B or H < 1, T other than 256 or 512. */
 int mt3_op_encoder_attention_x6(const float* d_qkv, float* d_out, int32_t B, int32_t T, int32_t H, void* stream);
+/* The standalone T5 LayerNorm the engine applies once per encode (encoder_norm): per row of d_x f32 [rows][dim],
+ * y = x * rsqrt(mean(x^2) + 1e-6) * d_scale[dim] -- the 1e-6 sits INSIDE the root, so a row of zeros gives exactly 0 --,
+ * evaluated in f32.  d_out_ct [rows][dim] takes y in the compute type (bf16, rounded to nearest even, or f32 by `dtype`),
+ * d_out_f32 [rows][dim] takes y in f32; either may be NULL and is then not written.  Nothing at or past row `rows` is
+ * written.  MT3_ERR_INVALID: dtype other than MT3_BF16 / MT3_F32, a NULL d_x or d_scale, rows < 1, dim < 4 or
+ * dim % 4 != 0 (rows are read and written as float4). */
+int mt3_op_rmsnorm(int32_t dtype, const float* d_x, const float* d_scale, void* d_out_ct, float* d_out_f32,
+                   int32_t rows, int32_t dim, void* stream);
 
 /* MXFP8 dense path (dense_dtype MT3_FP8_E4M3; no counterpart in the reference, whose DenseGeneral is f32,
  * mt3/layers.py:311-360): operands are OCP e4m3fn bytes [rows][K] with one E8M0 power-of-two scale per 32 consecutive

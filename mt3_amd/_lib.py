@@ -195,6 +195,7 @@ SIGNATURES = {
     "mt3_op_gemm_x6": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
                                  _P]),
     "mt3_op_encoder_attention_x6": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mt3_op_rmsnorm": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_gemm": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                               C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "mt3_op_gemm_ex": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32,

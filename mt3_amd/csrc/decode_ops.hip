@@ -1754,6 +1754,15 @@ extern "C" int mt3_op_residual_split(int32_t dtype, const float* d_x, void* d_x_
   return mt3k::launch_residual_split(d_x, d_x_ct, d_x_ss, rows, dim, static_cast<hipStream_t>(stream));
 }
 
+// include/mt3_hip.h: the kernel alone (the engine launches it once per encode, for encoder_norm)
+extern "C" int mt3_op_rmsnorm(int32_t dtype, const float* d_x, const float* d_scale, void* d_out_ct, float* d_out_f32,
+                              int32_t rows, int32_t dim, void* stream) {
+  if (dtype != MT3_BF16 && dtype != MT3_F32) return mt3::fail(MT3_ERR_INVALID, "mt3_op_rmsnorm: dtype is MT3_BF16 or MT3_F32");
+  if (dim <= 0) return mt3::fail(MT3_ERR_INVALID, "mt3_op_rmsnorm: dim < 4");
+  return mt3::fail_as("mt3_op_rmsnorm", mt3k::launch_rmsnorm(dtype, d_x, d_scale, d_out_ct, d_out_f32, rows, dim,
+                                                             static_cast<hipStream_t>(stream)));
+}
+
 extern "C" int mt3_ids_to_tokens(const int32_t* d_ids, int32_t batch, int32_t length, int32_t num_regular,
                                  int32_t* d_tokens, void* stream) {
   return mt3k::launch_ids_to_tokens(d_ids, batch, length, num_regular, d_tokens, static_cast<hipStream_t>(stream));

@@ -12,6 +12,9 @@ mt3_op_score_attention, mt3_op_score_embed, mt3_op_score_reduce and mt3_op_plane
   embed rows          table[tok] + pos[t] in f32 with the shift-right / caller-input / padding / clamping rules.
   scores              (logits[target] - logsumexp) * weight in float64, 0 where the target is 0; per-segment sums.
   planes              the hi / mid / lo bf16 split (tests/test_three_plane_arithmetic.py: split3), as bf16 bit patterns.
+  three-plane product its error model: A W^T as the kernel's six plane products summed in float64, and with each of the
+                      three small products (mid.mid, hi.lo, lo.hi) left out in turn; x6_bound turns them into the bound of
+                      a case of tests/test_gpu_three_plane_ops.py: half of what the best five-product kernel would show.
 """
 import math
 
@@ -105,3 +108,60 @@ def planes_ref(w):
     """f32 [n] -> (hi, mid, lo) as uint16 bf16 bit patterns: the host split rule"""
     hi, mid, lo, _, _ = split3(w)
     return bf16_bits(hi), bf16_bits(mid), bf16_bits(lo)
+
+
+# ------------------------------------------------------------------------------- the three-plane product's error model
+X6_SIX = ((1, 1), (0, 2), (2, 0), (0, 1), (1, 0), (0, 0))         # mm, hl, lh, hm, mh, hh: gemm_x6_kernel's order
+X6_DROPS = {"mid.mid": (1, 1), "hi.lo": (0, 2), "lo.hi": (2, 0)}   # the three small products; first factor A, second W
+
+
+def planes64(x):
+    """torch f32 values -> their (hi, mid, lo) bf16 planes as float64 (the rule of planes_ref, on any device)"""
+    x = x.float()
+    hi = x.bfloat16().float()
+    r1 = x - hi
+    mid = r1.bfloat16().float()
+    lo = (r1 - mid).bfloat16().float()
+    return hi.double(), mid.double(), lo.double()
+
+
+def plane_product(A, W, drop=None):
+    """A f32 [M][K], W f32 [N][K] -> float64 [M][N]: A W^T as the sum over X6_SIX (without X6_DROPS[drop]) of the plane
+    products, each summed in float64 -- what gemm_x6_kernel forms, without its f32 accumulation"""
+    a, w = planes64(A), planes64(W)
+    return sum(a[i] @ w[j].T for i, j in X6_SIX if drop is None or (i, j) != X6_DROPS[drop])
+
+
+def x6_bound(today, errors_of):
+    """The bound of one three-plane case: the smaller of `today` and HALF the smallest error among the three five-product
+    emulations, provided the six-product emulation stays under a QUARTER of that; else `today`.  errors_of(drop) -> the
+    error figure of the emulation without that product (None: all six) against the case's float64 reference, taken the way
+    the test takes the kernel's.  -> (bound, distinguishes, six, {name: five-product error})"""
+    six = errors_of(None)
+    five = {name: errors_of(name) for name in X6_DROPS}
+    tight = min(today, 0.5 * min(five.values()))
+    ok = six < tight / 4
+    return (tight if ok else today), ok, six, five
+
+
+def gelu_tanh(x):
+    return 0.5 * x * (1 + torch.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
+
+
+def x6_epilogue(epi, prod, A, res=None, aux=None, seq=0):
+    """float64 prod [M][N] = A W^T (exact, or an emulation of it) -> what mt3_op_gemm_x6 stores for epilogue `epi`
+    ("STORE", "GEGLU": with the row's 1 / rms of A in float64; "RESID": res + prod; "POS": prod + aux[row % seq]; "HEADS":
+    [2][M / seq][N / 128][seq][64])"""
+    M, N = prod.shape
+    if epi in ("STORE", "GEGLU"):
+        prod = prod * torch.rsqrt((A.double() ** 2).mean(-1, keepdim=True) + 1e-6)
+    if epi == "STORE":
+        return prod
+    if epi == "GEGLU":                                     # rows [32q, 32q + 16) gate columns 16q .., the next 16 linear
+        p4 = prod.view(M, N // 32, 2, 16)
+        return (gelu_tanh(p4[:, :, 0]) * p4[:, :, 1]).reshape(M, N // 2)
+    if epi == "RESID":
+        return res.double() + prod
+    if epi == "POS":
+        return prod + aux.double()[torch.arange(M, device=prod.device) % seq]
+    return prod.view(M // seq, seq, 2, N // 128, 64).permute(2, 0, 3, 1, 4).contiguous()

@@ -1,9 +1,11 @@
 """tests/score_prefill_ref.py on the CPU: the prefill-attention reference (masked keys SELECTED away) against a second
 formulation -- a dense additive -inf mask through torch.softmax in float64 --, the zero-row rule, the error model without
-rounding, and the numpy forms of the embed row, the scores and the planes on hand-made cases."""
+rounding, the numpy forms of the embed row, the scores and the planes on hand-made cases, and the three-plane product's
+error model: on every shape of test_gemm_x6 six products stay under a quarter of the bound and no five reach it."""
 import math
 
 import numpy as np
+import pytest
 import torch
 
 from tests import score_prefill_ref as R
@@ -107,3 +109,42 @@ def test_embed_rows_scores_and_planes_on_small_cases():
     assert hi.tolist() == [0x3F80, 0x8000, 0x4180, 0x3F80] and mid[1] == 0 and lo[1] == 0
     assert mid[0] == 0x3700 and lo[0] == 0 and mid[2] == 0xB580                   # 2^-17; 16 - 2^-20: hi carries to 16
     assert mid[3] == 0x3B00 and lo[3] == 0x3680                                  # 2^-9, 2^-18
+
+
+# ------------------------------------------------------------------------------- the three-plane product's error model
+X6_TODAY = {"STORE": 2e-5, "RESID": 2e-5, "POS": 2e-5, "HEADS": 2e-5, "GEGLU": 3e-5}
+X6_CASES = [(epi, M, N, K) for epi in ("STORE", "RESID", "POS", "HEADS") for M in (1, 64, 130, 192)
+            for N, K in ((128, 64), (1152, 512), (512, 1024))] + [("GEGLU", M, 256, 512) for M in (1, 64, 130, 192)]
+
+
+def test_plane_product_is_the_product_up_to_the_three_products_it_leaves_out():
+    g = torch.Generator().manual_seed(5)
+    A, W = torch.randn(7, 64, generator=g), torch.randn(128, 64, generator=g)
+    exact = A.double() @ W.double().T
+    scale = A.double().abs() @ W.double().abs().T
+    assert float(((R.plane_product(A, W) - exact).abs() / scale).max()) < 3 * 2.0 ** -24 + 2.0 ** -25
+    for name in R.X6_DROPS:                                 # a 2^-16-sized term per element is missing
+        e = float(((R.plane_product(A, W, name) - exact).abs() / scale).max())
+        assert 2.0 ** -22 < e < 2.0 ** -15, (name, e)
+    for got, want in zip(R.planes64(A), R.planes_ref(A.numpy().ravel())):
+        assert np.array_equal(R.bf16_bits(got.float().numpy().ravel()), want)
+
+
+@pytest.mark.parametrize("epi,M,N,K", X6_CASES)
+def test_x6_bound_lets_six_products_through_and_no_five(epi, M, N, K):
+    """the shapes, epilogues and operand distributions of test_gemm_x6 (tests/test_gpu_three_plane_ops.py), which applies
+    the same rule to its own operands"""
+    g = torch.Generator().manual_seed(M * 7 + N + K)
+    seq = {1: 1, 64: 64, 130: 65, 192: 64}[M] if epi == "HEADS" else 64 if epi == "POS" else 0
+    A = torch.randn(M, K, generator=g) * (1 + 3 * torch.rand(M, 1, generator=g))
+    W = torch.randn(N, K, generator=g) / math.sqrt(K)
+    aux = torch.randn(seq, N, generator=g) if epi == "POS" else None
+    res = torch.randn(M, N, generator=g)
+    finish = lambda prod: R.x6_epilogue(epi, prod, A, res, aux, seq)
+    ref = finish(A.double() @ W.double().T)
+    rel = lambda got: float((got - ref).norm() / ref.norm())
+    tol, tells, six, five = R.x6_bound(X6_TODAY[epi], lambda drop: rel(finish(R.plane_product(A, W, drop))))
+    print(f"gemm_x6 {epi} M {M} N {N} K {K}: bound {tol:.2e} (today's {X6_TODAY[epi]:.0e}), six products {six:.2e}, without "
+          + ", ".join(f"{n} {e:.2e}" for n, e in five.items()))
+    assert tells and tol <= X6_TODAY[epi] and six < tol / 4
+    assert all(e >= 2 * tol for e in five.values()), five
