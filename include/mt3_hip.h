@@ -591,10 +591,10 @@ int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g /* NU
  *   k-beam     the state of new slot j is advance(state[parent_j], tok_j), table included: all k parents' tables are read
  *              before any is written, and a table is copied only where parent_j != j.
  *   guarantee  every row emitted under the rule is accepted by the per-segment acceptor, for greedy, beam-1, sampled and
- *              k-beam decodes.  What the engine CANNOT know is what the previous segment left sounding: a tie section may
- *              still declare a note the host does not hold ("inactive pitch/program in tie section"), and a later note-off
- *              of that same note in the same segment is then invalid for the host, which never accepted the declaration.
- *              Closing that takes decoding a file's segments in order, each tie section prompted from the last.
+ *              k-beam decodes.  The rule knows ONE segment: a tie section it is free to pick may declare a note the host
+ *              does not hold ("inactive pitch/program in tie section"), and a later note-off of that same note in the same
+ *              segment is then invalid for the host, which never accepted the declaration.  Tied decoding below closes
+ *              that: a file's segments decoded in order, each tie section prompted from the last (mt3_op_tie_prompts).
  * mt3_engine_set_note_grammar is a synchronous setup call, global to the engine; n == NULL clears.  Setting both a token
  * grammar and a note grammar on one engine is MT3_ERR_INVALID: clear one first.  Setting, changing or clearing it drops
  * the captured step graphs; steps with it never share a captured graph with other steps, and with it clear every decode
@@ -668,6 +668,62 @@ int32_t mt3_note_grammar_allowed(const mt3_note_grammar* n, int32_t gram, int32_
  * mt3_engine_set_note_grammar checks; no engine and no device needed) */
 int mt3_note_grammar_check(const mt3_note_grammar* n, int32_t vocab);
 int mt3_engine_set_note_grammar(mt3_engine* e, const mt3_note_grammar* n /* NULL clears */);
+
+/* Tied decoding: what a segment left sounding, as the tie section that opens the file's next segment.  The note rule above
+ * knows one segment; MT3's targets open every segment with the notes active at its start, and the host note decoder
+ * carries exactly that set from one segment into the next.  This is the step between: emitted id rows in, tie-section
+ * prompts for mt3_engine_set_prompts out, on the device.
+ *   replay   (mt3n_replay) row[0 .. len-1] is an engine id row: prompt included, 0-padded after EOS.  From gram =
+ *            mt3g_initial, note = 0 and an empty table, every id is applied with mt3n_advance (with the grammar state from
+ *            before it) and mt3g_advance, up to and without the first id <= 1 or the end of the row.  The table left is the
+ *            row's held set.
+ *   section  (mt3n_tie_section) the held pairs in ascending (program, pitch) order, a program id then a pitch id per pair;
+ *            with MT3_TIE_DROP_REDUNDANT_PROGRAMS a program id only where the program differs from the pair before; then
+ *            tie_id -- what vocabularies.tie_section_prompt writes (remove_redundant_programs = the flag).  Nothing held: the
+ *            bare tie_id.  More than `cap` pairs held: the first `cap` in that order are kept; the count returned is all of
+ *            them.  The row written has 2 * cap + 1 ids, 0 after tie_id.
+ * mt3_op_tie_prompts runs both for `rows` rows in one launch, one workgroup per row: the row's end and its first tie_id by
+ * block reductions, the last program and velocity id before every position by an inclusive max-scan, the last writer of each
+ * (program, pitch) by an LDS table of positions, the section by a popcount scan over the table's program rows.  Rows longer
+ * than the workgroup's tile of 1024 ids go through it tile by tile with the state carried over.  Its results are those of
+ * mt3n_replay + mt3n_tie_section, bit for bit (mt3_note_grammar_tie_prompt: the two on the host, as an exported symbol).
+ *   d_ids [rows][ids_stride] int32; d_prompts [rows][2 * cap + 1] int32; d_count [rows] int32: pairs held, before the cut
+ *   to `cap`; d_held [rows][mt3n_table_words] uint32 or NULL: the held tables.  Enqueued on `stream`; no synchronisation.
+ * MT3_ERR_INVALID, before any device work: a descriptor mt3_note_grammar_check refuses for every vocabulary; cap < 0 (or
+ * above 2^30 - 1); rows < 1; ids_stride < 1; flags other than MT3_TIE_DROP_REDUNDANT_PROGRAMS; a null pointer other than
+ * d_held. */
+#define MT3_TIE_DROP_REDUNDANT_PROGRAMS 1
+/* the held set of row[0 .. len-1] into held[mt3n_table_words] */
+MT3_RULE_FN void mt3n_replay(const mt3_note_grammar* n, const int32_t* row, int32_t len, uint32_t* held) {
+  int32_t gram = mt3g_initial(&n->g), note = 0;
+  for (int32_t w = 0; w < mt3n_table_words(n); ++w) held[w] = 0;
+  for (int32_t t = 0; t < len && row[t] > 1; ++t) {
+    note = mt3n_advance(n, gram, note, held, row[t]);
+    gram = mt3g_advance(&n->g, gram, row[t]);
+  }
+}
+/* the tie section of `held` into out[2 * cap + 1], 0-padded; returns the pairs held */
+MT3_RULE_FN int32_t mt3n_tie_section(const mt3_note_grammar* n, const uint32_t* held, int32_t cap, int32_t flags,
+                                     int32_t* out) {
+  int32_t count = 0, at = 0, last = -1;
+  for (int32_t r = 0; r < n->g.program_count; ++r)
+    for (int32_t p = 0; p < n->g.pitch_count; ++p) {
+      if (!((held[r * mt3n_row_words(n) + (p >> 5)] >> (p & 31)) & 1u)) continue;
+      if (count++ >= cap) continue;
+      if (!(flags & MT3_TIE_DROP_REDUNDANT_PROGRAMS) || r != last) out[at++] = n->g.program_first + r;
+      out[at++] = n->g.pitch_first + p;
+      last = r;
+    }
+  out[at++] = n->g.tie_id;
+  while (at < 2 * cap + 1) out[at++] = 0;
+  return count;
+}
+/* mt3n_replay + mt3n_tie_section of one HOST row: h_prompt [2 * cap + 1], h_held [mt3n_table_words] or NULL; returns the
+ * pairs held, or MT3_ERR_INVALID for what mt3_op_tie_prompts refuses */
+int32_t mt3_note_grammar_tie_prompt(const mt3_note_grammar* n, const int32_t* h_row, int32_t len, int32_t cap, int32_t flags,
+                                    int32_t* h_prompt, uint32_t* h_held /* or NULL */);
+int mt3_op_tie_prompts(const mt3_note_grammar* n, const int32_t* d_ids, int32_t rows, int32_t ids_stride, int32_t cap,
+                       int32_t flags, int32_t* d_prompts, int32_t* d_count, uint32_t* d_held /* or NULL */, void* stream);
 
 /* Temperature sampling with top-k / top-p: t5x decoding.temperature_sample in the greedy token kernel's place.  [from
  * memory] -- t5x is not at hand, as for the beam rule; what binds is that the three statements of the rule agree: the

@@ -34,6 +34,7 @@ MAX_BEAMS = 8                                  # mt3_engine_decode_beams: 1 <= n
 EV_SHIFT, EV_PITCH, EV_VELOCITY, EV_TIE, EV_PROGRAM, EV_DRUM = range(6)
 EVENT_TYPE_NAMES = ("shift", "pitch", "velocity", "tie", "program", "drum")
 SPEC_ONSETS, SPEC_NOTES, SPEC_TIES = range(3)
+TIE_DROP_REDUNDANT_PROGRAMS = 1                # mt3_op_tie_prompts flags
 
 
 class Mt3Error(RuntimeError):
@@ -171,6 +172,9 @@ SIGNATURES = {
     "mt3_note_grammar_advance": (C.c_int32, [C.POINTER(NoteGrammar), C.c_int32, C.c_int32, _P, C.c_int32]),
     "mt3_note_grammar_allowed": (C.c_int32, [C.POINTER(NoteGrammar), C.c_int32, C.c_int32, _P, C.c_int32]),
     "mt3_note_grammar_check": (C.c_int, [C.POINTER(NoteGrammar), C.c_int32]),
+    "mt3_note_grammar_tie_prompt": (C.c_int32, [C.POINTER(NoteGrammar), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "mt3_op_tie_prompts": (C.c_int, [C.POINTER(NoteGrammar), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                     _P]),
     "mt3_token_grammar_initial": (C.c_int32, [C.POINTER(TokenGrammar)]),
     "mt3_token_grammar_advance": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
     "mt3_token_grammar_allowed": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),

@@ -43,6 +43,7 @@ from . import network
 from . import note_sequences
 from . import sampling
 from . import spectrograms
+from . import ties
 from . import vocabularies
 
 SAMPLE_RATE = 16000
@@ -62,7 +63,8 @@ class InferenceModel(object):
     def __init__(self, checkpoint_path, model_type="mt3", *, config: Optional[network.T5Config] = None,
                  dtype: str = "float32", batch_size: int = 8, early_exit: bool = True,
                  decoding: str = "beam1", max_slots: int = 256, schedule: Optional[str] = None, num_beams: int = 4,
-                 temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0):
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, seed: int = 0, cap: int = 64,
+                 drop_redundant_programs: bool = True):
         """dtype: 'float32' (default) = the reference's own precision (gin/model.gin:50 restores and runs
         float32): f32 MFMA operands, f32 K/V cache, token-exact against the oracle.  'bfloat16' is the explicit
         opt-in fast path (bf16 operands and caches, f32 accumulation / residual / softmax; what bench.py times;
@@ -84,7 +86,10 @@ class InferenceModel(object):
         probability top_p (0 .. 1); 0 turns either off, both on is an error.  The draw of a segment depends on `seed`, the
         segment's index within its own file and its logits only: a file's notes are the same alone, in any
         `transcribe_many` / `transcribe_wavs` job and on either schedule (f32; bf16 logits depend on the rows of a launch).
-        `sample(audio, num_samples=n)` draws n transcriptions with seeds seed .. seed + n - 1."""
+        `sample(audio, num_samples=n)` draws n transcriptions with seeds seed .. seed + n - 1.
+        cap / drop_redundant_programs: for well_formed="tied" (`__call__`) -- the most (program, pitch) pairs a tie
+        section carried from one segment into the next may declare, and whether it repeats a program id that does not
+        change (True, the default, is the form MT3's targets have after remove_redundant_state_changes)."""
         if model_type == "ismir2021":
             num_velocity_bins = 127
             self.encoding_spec = note_sequences.NoteEncodingSpec
@@ -110,6 +115,12 @@ class InferenceModel(object):
             raise ValueError("decoding must be 'beam1', 'greedy', 'beam' or 'sample', got %r" % (decoding,))
         self.sampling = sampling.SamplingParams(float(temperature), int(top_k), float(top_p), int(seed)).check()
         self._job_streams = None                 # per-segment noise streams of the job in flight (None: the segment index)
+        if int(cap) < 0:
+            raise ValueError("cap must not be negative, got %r" % (cap,))
+        self.cap = int(cap)
+        self.drop_redundant_programs = bool(drop_redundant_programs)
+        self._job_tied = False                   # the call in flight is well_formed="tied": a wavefront over segment indices
+        self._tie_overflows = 0
         if decoding == "beam" and not 1 <= int(num_beams) <= min(8, self.max_slots):
             raise ValueError("num_beams must be 1 .. 8 (and <= max_slots), got %r" % (num_beams,))
         self.decoding = decoding
@@ -267,19 +278,31 @@ class InferenceModel(object):
         """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`), `prompts` (`_segment_prompts` of
         the whole job) and, with well_formed, the model's event grammar (True) or note grammar ("notes"); all are cleared
         on the way out, also on error"""
-        if isinstance(well_formed, str) and well_formed != "notes":
-            raise ValueError('well_formed is False, True or "notes", got %r' % (well_formed,))
+        if isinstance(well_formed, str) and well_formed not in ("notes", "tied"):
+            raise ValueError('well_formed is False, True, "notes" or "tied", got %r' % (well_formed,))
+        tied = isinstance(well_formed, str) and well_formed == "tied"
+        if tied:
+            if prompts is not None:
+                raise ValueError('well_formed="tied" writes every segment\'s prompt itself: not together with prompts=')
+            if 2 * self.cap + 1 >= self.outputs_length:
+                raise ValueError('well_formed="tied": a tie section of cap = %d pairs (%d ids) leaves no room in a decode '
+                                 "of %d steps" % (self.cap, 2 * self.cap + 1, self.outputs_length))
         self._job_masks = job
         self._job_prompts = prompts
+        self._tie_overflows = 0
         try:
-            if well_formed == "notes":
+            if well_formed == "notes" or tied:
                 self._job_grammar = self.note_grammar()
+                self._job_tied = tied
             else:
                 self._job_grammar = self.token_grammar() if well_formed else None
             yield
         finally:
             self._job_masks = None
             self._job_prompts = None
+            if self._job_tied and self.model is not None:
+                self.model.set_prompts(None)
+            self._job_tied = False
             if self._job_grammar is not None and self.model is not None:
                 if isinstance(self._job_grammar, _lib.NoteGrammar):
                     self.model.clear_note_grammar()
@@ -329,6 +352,8 @@ class InferenceModel(object):
         x = batch["encoder_input_tokens"]
         x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, np.float32))
         x = x.cuda()
+        if self._job_tied:
+            return self._predict_ids_tied(x)
         beam1 = self.decoding == "beam1"
         if self.decoding == "beam":
             return self._predict_ids_beam(x)
@@ -347,6 +372,47 @@ class InferenceModel(object):
             out.append(self.model.decode(early_exit=self.early_exit, beam1=beam1))
             self.rows_per_engine_call.append(int(min(step, x.shape[0] - s)))
         return torch.cat(out, 0)
+
+    def _predict_ids_tied(self, x):
+        """well_formed="tied": the job as a wavefront.  Pass j decodes segment j of every file that has one through
+        `_predict_ids` -- the job's masks, streams and decoding rule sliced to the pass's rows -- with segment 0 forced to
+        the bare `tie` and segment j + 1 forced to `Transformer.tie_prompts` of the file's row from pass j."""
+        import torch
+        N = int(x.shape[0])
+        seg = np.asarray(self._job_streams if self._job_streams is not None else np.arange(N), np.int64)
+        job = (self._job_masks, self._job_streams)
+        grammar = self._job_grammar
+        ids = torch.empty((N, self.outputs_length), device=x.device, dtype=torch.int32)
+        carried = {}                             # job row of segment j -> the prompt of the file's segment j + 1
+        bare = [int(grammar.g.tie_id)]
+        calls = []
+        self._job_tied = False                   # the passes themselves take the plain path
+        try:
+            for j in range(int(seg.max()) + 1 if N else 0):
+                rows = np.flatnonzero(seg == j)
+                if job[0] is not None:
+                    masks, index = job[0]
+                    self._job_masks = (masks, None if index is None else np.asarray(index)[rows])
+                self._job_streams = seg[rows]
+                self._job_prompts = [bare if j == 0 else carried[r - 1] for r in rows]
+                at = torch.from_numpy(rows).to(x.device)
+                out = self._predict_ids({"encoder_input_tokens": x.index_select(0, at)})
+                ids.index_copy_(0, at, out)
+                calls += self.rows_per_engine_call
+                go_on = [i for i, r in enumerate(rows) if r + 1 < N and seg[r + 1] == j + 1]
+                if not go_on:
+                    continue
+                src = out if len(go_on) == len(rows) else out.index_select(0, torch.tensor(go_on, device=x.device))
+                prompts, counts = self.model.tie_prompts(src, grammar, self.cap, self.drop_redundant_programs)
+                prompts, counts = prompts.cpu().numpy(), counts.cpu().numpy()
+                self._tie_overflows += int((counts > self.cap).sum())
+                carried = {int(rows[i]): ties.prompt_ids(p) for i, p in zip(go_on, prompts)}
+        finally:
+            self._job_tied = True
+            self._job_masks, self._job_streams = job
+            self._job_prompts = None
+        self.rows_per_engine_call = calls
+        return ids
 
     def _predict_ids_beam(self, x):
         """decoding='beam', k engine rows (beams) per segment: one in-flight batched call (schedule='refill'), or
@@ -391,7 +457,15 @@ class InferenceModel(object):
         well_formed="notes": that rule plus the set of sounding notes (Transformer.set_note_grammar): no note-off of a
         pitch that is not sounding on the current program, no pair declared twice in a tie section, no drum at velocity 0.
         ValueError for a model whose spec has no tie section.  True keeps the event grammar alone, and its bits.
-        `last_event_counts` holds the note decoder's invalid_events / dropped_events of the most recent call."""
+        well_formed="tied": the note rule, and every segment's tie section forced to what the file's previous segment left
+        sounding (`Transformer.tie_prompts`; the bare `tie` for a file's first segment) -- the decoding mode under which the
+        model sees at inference the tie sections it was trained with, and the host note decoder and the engine hold the
+        same set of notes at every segment boundary.  The job runs as a wavefront: pass j decodes segment j of every file
+        (`transcribe_many` / `transcribe_wavs`: all files' segment j in one engine call), so one file alone decodes its
+        segments one after another.  A tie section declares at most `cap` pairs (the model's keyword; default 64).
+        ValueError with prompts=, for a spec without a tie section, or when 2 * cap + 1 >= the decode length.
+        `last_event_counts` holds the note decoder's invalid_events / dropped_events of the most recent call and
+        tie_overflows, the segments whose held set exceeded `cap` on its way into the next (0 unless "tied")."""
         examples = self._examples(audio, sample_rate)
         with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
                                well_formed):
@@ -449,7 +523,8 @@ class InferenceModel(object):
     def _count_events(self, results):
         """the note decoder's counts of the call that just ended, summed over its files"""
         self.last_event_counts = {"invalid_events": int(sum(r["est_invalid_events"] for r in results)),
-                                  "dropped_events": int(sum(r["est_dropped_events"] for r in results))}
+                                  "dropped_events": int(sum(r["est_dropped_events"] for r in results)),
+                                  "tie_overflows": int(self._tie_overflows)}
 
     def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True,
                           prompts=None, well_formed: bool = False):

@@ -414,6 +414,29 @@ class Transformer:
     def clear_note_grammar(self):
         _lib.check(self._lib.mt3_engine_set_note_grammar(self._h, None))
 
+    def tie_prompts(self, ids, grammar, cap: int = 64, drop_redundant_programs: bool = True, return_held: bool = False):
+        """mt3_op_tie_prompts: what each emitted id row left sounding, as the tie section of the file's next segment.
+        ids: int32 CUDA [rows, n] engine id rows (what decode / transcribe return: prompt included, 0 after EOS); grammar:
+        a `_lib.NoteGrammar`.  Returns int32 CUDA prompts [rows, 2 * cap + 1] (0-padded rows for `set_prompts`; the bare
+        `tie` where nothing sounds) and counts [rows], the pairs held before the cut to `cap`; with return_held also the
+        held tables uint32-as-int32 [rows, table_words].  The rule: `mt3_amd/ties.py`."""
+        import torch
+        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1:
+            raise ValueError("ids must be a CUDA tensor [rows >= 1, n >= 1]")
+        if int(cap) < 0:
+            raise ValueError("cap must not be negative, got %r" % (cap,))
+        ids = ids.to(dtype=torch.int32).contiguous()
+        rows, cap = int(ids.shape[0]), int(cap)
+        prompts = torch.empty((rows, 2 * cap + 1), device=ids.device, dtype=torch.int32)
+        counts = torch.empty((rows,), device=ids.device, dtype=torch.int32)
+        words = int(self._lib.mt3_note_grammar_table_words(C.byref(grammar)))
+        held = torch.empty((rows, words), device=ids.device, dtype=torch.int32) if return_held else None
+        _lib.check(self._lib.mt3_op_tie_prompts(
+            C.byref(grammar), ids.data_ptr(), rows, int(ids.shape[1]), cap,
+            _lib.TIE_DROP_REDUNDANT_PROGRAMS if drop_redundant_programs else 0, prompts.data_ptr(), counts.data_ptr(),
+            held.data_ptr() if held is not None else None, torch.cuda.current_stream().cuda_stream))
+        return (prompts, counts, held) if return_held else (prompts, counts)
+
     def set_sampling(self, params=None, seg_stream=None, **kw):
         """mt3_engine_set_sampling: every later decode / transcribe call (greedy path; not beam1) DRAWS its free tokens --
         t5x temperature_sample -- until `clear_sampling`.  params: a `sampling.SamplingParams`, or its fields as keywords

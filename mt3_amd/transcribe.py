@@ -55,11 +55,17 @@ def plan(argv=None):
     ap.add_argument("--well-formed-notes", action="store_true",
                     help="note-consistent decoding: --well-formed plus the set of sounding notes, so no note-off of a silent "
                          "pitch, no pair tied twice and no drum at velocity 0 is emitted (models with a tie section)")
+    ap.add_argument("--well-formed-tied", action="store_true",
+                    help="tied decoding: --well-formed-notes, and every segment's tie section is forced to the notes the "
+                         "file's previous segment left sounding; the inputs' segments are decoded in order, all files' "
+                         "segment j together")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
     if args.well_formed_notes:
         args.well_formed = "notes"
+    if args.well_formed_tied:
+        args.well_formed = "tied"
     if not 1 <= args.num_beams <= 8:
         ap.error("--num-beams must be 1 .. 8")
     for path in args.inputs:
