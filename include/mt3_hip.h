@@ -1435,6 +1435,72 @@ int mt3_notes_decode_traced(const mt3_codec* c, int32_t spec, int32_t n_segments
                             int64_t* invalid_events, int64_t* dropped_events, double* total_time,
                             int64_t* h_note_tokens /* [notes_capacity][2] */);
 
+/* --------------------------------------------------- piano rolls and frame counts
+ * Replaces metrics_utils.get_prettymidi_pianoroll and metrics_utils.frame_metrics (mt3/metrics_utils.py:149-196, called
+ * at mt3/metrics.py:321-332 for 'Frame Precision' / 'Frame Recall' / 'Frame F1').  The reference delegates to
+ * pretty_midi.PrettyMIDI.get_piano_roll and sklearn.metrics.precision_recall_fscore_support; the rule below restates the
+ * reference's own lines plus the documented behaviour of those two calls [from memory, parity unpinned against the
+ * libraries themselves: neither is installable here].
+ *
+ * The roll of one set of notes at `fps` frames per second, with the flag `is_drum`:
+ *   length   a note with  is_drum != 0  or  end_time - start_time < 0.05  gets  end = start_time + 0.05  (float64; the
+ *            reference writes that into its argument's notes, here the caller's notes are read only);
+ *   width    F = int(fps * max end) over ALL the notes after that adjustment, drum notes included; no notes: F = 0.
+ *            The caller computes F (h_widths); the device never writes at or past a row's F whatever the notes say;
+ *   cells    roll[pitch, f0 : f1] += velocity  with  f0 = int(start_time * fps),  f1 = int(end * fps):  one float64
+ *            product each, truncated (Python's int(x * fs)), f1 cut to F; f1 <= f0 adds nothing.  Notes on one pitch, of
+ *            one program or several, sum;
+ *   drums    with is_drum == 0 a note whose own drum flag is set adds nothing (pretty_midi renders a drum instrument as
+ *            zeros) though it counted for F; with is_drum != 0 every note is rendered (the reference clears the
+ *            instruments' flags);
+ *   nothing else sounds: the two control changes the reference appends at the end time change no cell, and there is no
+ *   sustain pedal and no pitch bend.
+ * A note whose pitch is outside 0 .. 127 is skipped; a start or end that is negative or NaN counts as frame 0 (callers
+ * reject such notes before upload: Python's slice would count a negative index from the row's end).  Every cell is a sum
+ * of int32 velocities; it must stay below 2^24 in magnitude for its float32 to be exact (1,000 full-velocity notes on
+ * one cell are 127,000).
+ *
+ * mt3_op_pianoroll: the notes of a job -> all its rolls.  Roll i takes notes [h_note_offsets[i], h_note_offsets[i + 1])
+ *   of the five device arrays and is written as float32, row-major [128, h_widths[i]], at d_out + 128 *
+ *   h_col_offsets[i].  The rolls must not overlap and lie in order: h_col_offsets[i + 1] >= h_col_offsets[i] +
+ *   h_widths[i]; the whole span from roll 0's first cell to the last roll's end, gaps included, is written (zeros in
+ *   the gaps), nothing outside it.  The cost does not depend on the notes' durations: every note makes two int32 atomic
+ *   adds (+velocity at f0, -velocity at f1) into the zeroed span, and one workgroup per (roll, pitch) turns its row into
+ *   running sums in place -- integer sums, so the result does not depend on the order of the atomics.
+ *   The three host tables go to the kernels BY VALUE (128 rolls per launch; longer jobs are issued in pieces), so
+ *   they are free when the call returns; everything is enqueued on `stream`, nothing is allocated, copied to the host or
+ *   waited for.  MT3_ERR_INVALID, before any HIP call: n_rolls < 0, n_notes < 0, fps not finite or <= 0, a NULL table
+ *   with n_rolls > 0, a NULL note array with n_notes > 0, h_note_offsets not non-decreasing inside [0, n_notes], more
+ *   than 2^31 - 1 notes in one roll, a negative width or column offset, rolls out of order or overlapping, a span past
+ *   out_capacity (in floats) or NULL d_out with a non-empty span.  n_rolls == 0, or rolls that are all of width 0, is a
+ *   valid call that does nothing.
+ *
+ * The frame counts of a (reference roll, estimated roll) pair with `velocity_threshold`: the narrower roll counts as
+ * zero from its own width on (the reference pads it), ref_on = ref > velocity_threshold (strict), est_on = est > 0, and
+ * over all 128 * max(F_ref, F_est) cells  TP = #(ref_on & est_on),  FP = #(!ref_on & est_on),  FN = #(ref_on & !est_on).
+ * precision = TP / (TP + FP), recall = TP / (TP + FN), F1 = 2 P R / (P + R), each 0 where its denominator is 0
+ * (sklearn's value for the positive class; it warns, this library does not) -- left to the caller.
+ *
+ * mt3_op_frame_counts: d_counts [n_pairs][3] uint64 = (TP, FP, FN) of n_pairs pairs; pair i's rolls are float32
+ *   [128, width] at d_rolls + 128 * column offset, as mt3_op_pianoroll wrote them (a roll may serve several pairs).
+ *   d_counts is zeroed by the call; each workgroup counts with wave ballots and adds its three totals once.  Same
+ *   contract: tables by value (128 pairs per launch), nothing allocated, copied to the host or waited for.
+ *   MT3_ERR_INVALID, before any HIP call: n_pairs < 0, a NULL table or NULL d_counts with n_pairs > 0, a negative width
+ *   or column offset, a roll that ends past rolls_capacity (in floats), NULL d_rolls with a pair of non-zero width, or
+ *   |velocity_threshold| > 2^24 (the comparison is made in float32).  n_pairs == 0 is a valid call that does nothing.
+ */
+#define MT3_PIANOROLL_PITCHES 128
+#define MT3_PIANOROLL_MIN_NOTE_SECONDS 0.05
+
+int mt3_op_pianoroll(const double* d_start, const double* d_end, const int32_t* d_pitch, const int32_t* d_velocity,
+                     const int32_t* d_is_drum, int64_t n_notes, int32_t n_rolls, const int64_t* h_note_offsets /* [n_rolls + 1] */,
+                     const int64_t* h_col_offsets /* [n_rolls] */, const int32_t* h_widths /* [n_rolls] */, double fps,
+                     int32_t is_drum, float* d_out, int64_t out_capacity, void* stream);
+int mt3_op_frame_counts(const float* d_rolls, int64_t rolls_capacity, int32_t n_pairs,
+                        const int64_t* h_ref_col_offsets, const int32_t* h_ref_widths,
+                        const int64_t* h_est_col_offsets, const int32_t* h_est_widths /* each [n_pairs] */,
+                        int32_t velocity_threshold, uint64_t* d_counts /* [n_pairs][3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

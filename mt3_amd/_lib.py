@@ -35,6 +35,7 @@ EV_SHIFT, EV_PITCH, EV_VELOCITY, EV_TIE, EV_PROGRAM, EV_DRUM = range(6)
 EVENT_TYPE_NAMES = ("shift", "pitch", "velocity", "tie", "program", "drum")
 SPEC_ONSETS, SPEC_NOTES, SPEC_TIES = range(3)
 TIE_DROP_REDUNDANT_PROGRAMS = 1                # mt3_op_tie_prompts flags
+PIANOROLL_PITCHES, PIANOROLL_MIN_NOTE_SECONDS = 128, 0.05      # mt3_op_pianoroll
 
 
 class Mt3Error(RuntimeError):
@@ -277,6 +278,9 @@ SIGNATURES = {
     "mt3_notes_decode_traced": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64,
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_double), _P]),
+    "mt3_op_pianoroll": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_double, C.c_int32, _P,
+                                   C.c_int64, _P]),
+    "mt3_op_frame_counts": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P]),
 }
 
 _lib = None

@@ -632,6 +632,13 @@ class InferenceModel(object):
         return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums, prompts,
                                       well_formed)
 
+    @staticmethod
+    def pianoroll(ns, fps: float = 62.5):
+        """The piano roll of a transcription: a float32 CUDA tensor [128, int(fps * last end)], each note's velocity summed
+        into its frames (`mt3_amd.pianoroll.pianorolls([ns], fps)[0]`; drum notes are silent, as in pretty_midi's roll)."""
+        from . import pianoroll
+        return pianoroll.pianorolls([ns], fps)[0]
+
     def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None, well_formed=False):
         """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
         NoteSequence per file, all segments through the engine as one job"""

@@ -178,6 +178,43 @@ def program_aware_note_scores(ref_ns: NoteSequence, est_ns: NoteSequence, granul
     return out
 
 
+# ------------------------------------------------------------------------------------------------- frame-level scores
+def frame_scores_many(pairs: Sequence, fps: float = 62.5, velocity_threshold: int = 30,
+                      is_drum: bool = False) -> list:
+    """`frame_scores` of every (ref_ns, est_ns) pair, from ONE `pianoroll.frame_counts` call: all the rolls of the job
+    rasterised at once, all the cells counted at once, 24 bytes per pair copied back."""
+    from . import pianoroll
+
+    def prepared(ns):
+        if is_drum:
+            return ns
+        return NoteSequence(notes=[n for n in ns.notes if not n.is_drum], total_time=ns.total_time,
+                            ticks_per_quarter=ns.ticks_per_quarter)
+    pairs = list(pairs)
+    counts = pianoroll.frame_counts([prepared(r) for r, _ in pairs], [prepared(e) for _, e in pairs], fps,
+                                    velocity_threshold, is_drum)
+    out = []
+    for tp, fp, fn in counts:
+        p, r, f = pianoroll.precision_recall_f1(tp, fp, fn)
+        out.append({"Frame Precision": p, "Frame Recall": r, "Frame F1": f})
+    return out
+
+
+def frame_scores(ref_ns: NoteSequence, est_ns: NoteSequence, fps: float = 62.5, velocity_threshold: int = 30,
+                 is_drum: bool = False) -> Dict[str, float]:
+    """'Frame Precision' / 'Frame Recall' / 'Frame F1' as mt3/metrics.py:321-332 computes them for the whole
+    NoteSequence, at the reference's defaults (frame_fps 62.5, frame_velocity_threshold 30): the two piano rolls
+    (`metrics_utils.get_prettymidi_pianoroll`'s rule), the narrower zero-padded, a reference cell on above the threshold
+    and an estimated cell on above 0, precision / recall / F1 of the estimated cells -- rasterised and counted on the
+    device (mt3_amd/pianoroll.py; the rule is in include/mt3_hip.h) [pretty_midi's and sklearn's behaviour restated from
+    memory: PARITY UNPINNED against the libraries themselves; pinned here by tests/test_pianoroll_ref.py].
+    With is_drum=False the drum notes are REMOVED first, as the reference's remove_drums does (mt3/metrics.py:226-239),
+    so the rolls' widths and contents follow the drumless sequences.  The reference's per-track rows are the caller's
+    `frame_scores(extract_track(ref, program, is_drum), extract_track(est, program, is_drum), is_drum=spec.is_drum)` with a
+    track extraction of their own: with is_drum=True every note is rendered, each 0.05 s long."""
+    return frame_scores_many([(ref_ns, est_ns)], fps, velocity_threshold, is_drum)[0]
+
+
 # ------------------------------------------------------------------------------- precision-mode divergence report
 def token_stream_divergence(ref_tokens: np.ndarray, est_tokens: np.ndarray, codec=None, encoding_spec=None,
                             segment_seconds: float = 2.048) -> Dict[str, float]:

@@ -142,3 +142,21 @@ def combine_predictions_by_id(predictions, combine_predictions_fn):
     for p in predictions:
         by_id[p["unique_id"]].append(p)
     return {k: combine_predictions_fn(v) for k, v in by_id.items()}
+
+
+# --------------------------------------------------------------- frame-level: mt3/metrics_utils.py:149-196 by their names
+def get_prettymidi_pianoroll(ns: note_sequences.NoteSequence, fps: float, is_drum: bool) -> np.ndarray:
+    """mt3/metrics_utils.py:149-171: the piano roll pretty_midi would render from `ns`, float64 numpy [128, F] as the
+    reference returns it.  Rasterised on the device (mt3_amd.pianoroll.pianorolls, one call; there is no host path) and
+    copied back; callers with many sequences, or who want the roll to stay on the device, call `pianorolls` itself.
+    Unlike the reference, `ns` is left as it is: the 0.05 s minimum length is applied to a copy of the times."""
+    from . import pianoroll
+    return pianoroll.pianorolls([ns], fps, is_drum)[0].cpu().numpy().astype(np.float64)
+
+
+def frame_metrics(ref_pianoroll, est_pianoroll, velocity_threshold: int):
+    """mt3/metrics_utils.py:174-196: (precision, recall, f1) of the frames, Python floats.  The rolls are numpy arrays or
+    CUDA tensors [128, F_ref], [128, F_est]; the narrower counts as zero-padded, a reference cell is on above
+    `velocity_threshold`, an estimated cell above 0, and the cells are counted on the device (mt3_op_frame_counts)."""
+    from . import pianoroll
+    return pianoroll.precision_recall_f1(*pianoroll.roll_pair_counts(ref_pianoroll, est_pianoroll, velocity_threshold))

@@ -3,7 +3,7 @@
     python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
                                  [--decoding beam1|greedy|beam|sample] [--num-beams K] [--confidences]
                                  [--temperature T] [--top-k K] [--top-p P] [--seed N]
-                                 [--programs P[,P...]] [--no-drums]
+                                 [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -18,6 +18,9 @@ decoding: the excluded tokens cannot be picked; `InferenceModel(..., programs=, 
 --decoding sample draws every token from softmax(logits / T) (t5x temperature_sample), cut to the --top-k most likely
 tokens or to the smallest set of probability --top-p; --seed picks the draw, which for a file is the same whatever other
 inputs share the job (`InferenceModel(decoding="sample", temperature=, top_k=, top_p=, seed=)`).
+--pianoroll [FPS] also writes NAME.npy beside each NAME.mid: the transcription's piano roll, uint16 [128, frames] at FPS
+frames per second (default 62.5), each note's velocity summed into its frames (cut at 65535), drum notes silent
+(`mt3_amd.pianoroll.pianorolls`: the rolls of all inputs are rasterised in one call once the job's notes are decoded).
 """
 from __future__ import annotations
 
@@ -59,6 +62,9 @@ def plan(argv=None):
                     help="tied decoding: --well-formed-notes, and every segment's tie section is forced to the notes the "
                          "file's previous segment left sounding; the inputs' segments are decoded in order, all files' "
                          "segment j together")
+    ap.add_argument("--pianoroll", type=float, nargs="?", const=62.5, default=None, metavar="FPS",
+                    help="also write NAME.npy beside each NAME.mid: the piano roll, uint16 [128, frames] at FPS frames "
+                         "per second (default 62.5)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -68,6 +74,8 @@ def plan(argv=None):
         args.well_formed = "tied"
     if not 1 <= args.num_beams <= 8:
         ap.error("--num-beams must be 1 .. 8")
+    if args.pianoroll is not None and not (math.isfinite(args.pianoroll) and args.pianoroll > 0):
+        ap.error("--pianoroll takes a positive number of frames per second")
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
@@ -110,6 +118,12 @@ def main(argv=None) -> int:
         else:
             sequences, scores = model.transcribe_wavs(args.inputs, programs=args.programs, drums=args.drums,
                                                       well_formed=args.well_formed), None
+        rolls = None
+        if args.pianoroll is not None:
+            import numpy as np
+            from . import pianoroll
+            rolls = [r.clamp(0, 65535).to("cpu").numpy().astype(np.uint16)
+                     for r in pianoroll.pianorolls(sequences, args.pianoroll)]
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -120,7 +134,14 @@ def main(argv=None) -> int:
     for ns, sc, path in zip(sequences, scores or [], outputs):
         with open(confidence_path(path), "w") as f:
             json.dump(confidence_records(ns, sc), f, indent=1)
+    for roll, path in zip(rolls or [], outputs):
+        import numpy as np
+        np.save(pianoroll_path(path), roll)
     return 0
+
+
+def pianoroll_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".npy"
 
 
 def confidence_path(midi_path: str) -> str:
