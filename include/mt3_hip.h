@@ -1501,6 +1501,75 @@ int mt3_op_frame_counts(const float* d_rolls, int64_t rolls_capacity, int32_t n_
                         const int64_t* h_est_col_offsets, const int32_t* h_est_widths /* each [n_pairs] */,
                         int32_t velocity_threshold, uint64_t* d_counts /* [n_pairs][3] */, void* stream);
 
+/* --------------------------------------------------- rendering notes to audio
+ * The audible output: what the reference's Colab does with fluidsynth and mt3/summaries.py:111-161
+ * (_synthesize_example_notes, audio_summaries) with note_seq's synthesiser.  Neither a SoundFont nor any library
+ * synthesiser is available to this project, so the voice is its own -- the timbre of mt3_amd.synthetic.render_notes
+ * (which the trained fixture under tests/golden/ recognises) made deterministic: zero phases, a fixed summation order,
+ * no added noise.  PARITY WITH ANY LIBRARY IS NOT CLAIMED.  Programs are ignored: every tonal note has the one timbre.
+ *
+ * job      n_seq sequences; sequence i owns n_samples[i] float32 samples at the integer sample_rate (1 .. 384000 Hz),
+ *          which start at sample_offsets[i] of one output buffer.
+ * note     start, end (float64 seconds), pitch 0 .. 127, velocity 0 .. 127, is_drum.  g = velocity / 127 (float32
+ *          division); a note of velocity 0 adds nothing.  A note whose pitch is outside 0 .. 127 is skipped.
+ * time     of sample n relative to a note:  t = (double)n / sample_rate - start:  one float64 division, then one
+ *          float64 subtraction.
+ * tonal    (is_drum clear)  d = end - start >= 0 (float64).  The note sounds for  0 <= t < d + 0.04  (float64 sum).
+ *          env(t)  = min(t / 0.004, 1) * exp(-t / 0.7) * clamp(1 - (t - d) / 0.04, 0, 1)    (t - d in float64)
+ *          f0      = 440 * 2^((pitch - 69) / 12)  in float64  (the library takes 2^(r / 12), r = 0 .. 11, from a table of
+ *                    correctly rounded float64 values and scales by the octave: within 2 ulp of the expression)
+ *          tone(t) = sum over k = 1 .. 6 with  k * f0 < 0.475 * sample_rate  of  sin(2 pi frac((k * f0) * t)) / k,
+ *                    k ascending.  The product (k * f0) * t and its fractional part are float64 -- at t = 600 s the
+ *                    sixth partial of pitch 96 has turned 7.5 million times, and float32 holds no fraction of that --
+ *                    everything after is float32.
+ *          Zero phase, no randomness.
+ * drum     (is_drum set)  sounds for  0 <= t < 0.15  whatever its end.   x = u * exp(-t / 0.03),
+ *          u = (h(pitch * 2^20 + m) >> 8) * 2^-23 - 1  (exact in float32, in [-1, 1)),  m = the sample's index counted
+ *          from the note's first sounding sample (the least n with t >= 0),  h the 32-bit integer mix
+ *          x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16  (uint32 arithmetic).
+ * sample   the float32 sum of  g * env * tone  (tonal) or  g * x  (drum) over its sequence's notes, the notes taken in
+ *          ascending (start, end, pitch, velocity, is_drum) order whatever order the caller holds them in.  The order is
+ *          part of the rule: float32 sums do not commute, and the same notes must give the same bits.
+ * normalise (on by default in the Python layer)  peak = max |sample| over the sequence; if peak > 0 every sample is
+ *          multiplied by the float32  0.9f / peak  (the inf-norm of mt3/mixing.py:71-75); a silent sequence stays zeros.
+ * length   when the caller gives none:  n_samples = ceil(sample_rate * latest sounding instant), the sounding instant of
+ *          a tonal note being end + 0.04 and of a drum note start + 0.15, in float64 on the host
+ *          (mt3_amd.render.render_length, the only place lengths come from); no notes: 0 samples.
+ *
+ * mt3_op_render_notes: the notes of a job -> all its audio, in one call.  Sequence i takes notes [h_note_offsets[i],
+ *   h_note_offsets[i + 1]) of the six device arrays and writes d_out[h_sample_offsets[i] .. + h_n_samples[i]); the
+ *   spans must lie in order and must not overlap; NOTHING outside them is written, gaps between them included.
+ *   PRECONDITION the host cannot check (the arrays are on the device): within a sequence the notes are sorted ascending
+ *   by (start, end, pitch, velocity, is_drum), and d_reach[j] is the running maximum, from the sequence's first note to
+ *   note j, of the notes' sounding instants (end + 0.04, or start + 0.15 for a drum note).  Unsorted notes or a wrong
+ *   d_reach may give wrong audio; the kernels still read only the sequence's own notes and write only its own span.
+ *   A workgroup owns a tile of MT3_RENDER_TILE consecutive samples of one sequence and walks, in order, the notes from
+ *   the first whose d_reach comes up to the tile's first instant (less a guard of 2^-40, relative and absolute, that
+ *   covers the roundings of the rule) to the last whose start is not past the tile's last instant -- two binary
+ *   searches; a note in that range that ended before the tile is skipped.  No atomics in the accumulation.  With
+ *   normalize != 0 a second kernel takes max |sample| per sequence into d_peaks (an atomic max on the bit patterns of
+ *   non-negative floats: order-independent) and a third scales; d_peaks [n_seq] is zeroed by the call and holds the
+ *   peaks BEFORE scaling afterwards.  With normalize == 0 d_peaks is not touched and may be NULL.
+ *   Tables go to the kernels by value (128 sequences per launch); everything is enqueued on `stream`, nothing is
+ *   allocated, copied to the host or waited for.  MT3_ERR_INVALID, before any HIP call: n_seq < 0, n_notes < 0,
+ *   sample_rate outside 1 .. 384000, a NULL table with n_seq > 0, a NULL note array with n_notes > 0, h_note_offsets not
+ *   non-decreasing inside [0, n_notes], more than 2^31 - 1 notes in one sequence, a negative length or sample offset, a
+ *   sequence longer than MT3_RENDER_MAX_SAMPLES, spans out of order or overlapping, a span past out_capacity (in
+ *   floats), NULL d_out with a non-empty span, NULL d_peaks with normalize != 0 and a non-empty span.  n_seq == 0, or
+ *   sequences that are all of length 0, is a valid call that does nothing.
+ */
+#define MT3_RENDER_TILE 1024
+#define MT3_RENDER_MAX_SAMPLE_RATE 384000
+#define MT3_RENDER_MAX_SAMPLES (INT64_C(1) << 40)
+#define MT3_RENDER_RELEASE_SECONDS 0.04
+#define MT3_RENDER_DRUM_SECONDS 0.15
+
+int mt3_op_render_notes(const double* d_start, const double* d_end, const double* d_reach, const int32_t* d_pitch,
+                        const int32_t* d_velocity, const int32_t* d_is_drum, int64_t n_notes, int32_t n_seq,
+                        const int64_t* h_note_offsets /* [n_seq + 1] */, const int64_t* h_sample_offsets /* [n_seq] */,
+                        const int64_t* h_n_samples /* [n_seq] */, int32_t sample_rate, int32_t normalize, float* d_out,
+                        int64_t out_capacity, float* d_peaks /* [n_seq] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,8 @@ EVENT_TYPE_NAMES = ("shift", "pitch", "velocity", "tie", "program", "drum")
 SPEC_ONSETS, SPEC_NOTES, SPEC_TIES = range(3)
 TIE_DROP_REDUNDANT_PROGRAMS = 1                # mt3_op_tie_prompts flags
 PIANOROLL_PITCHES, PIANOROLL_MIN_NOTE_SECONDS = 128, 0.05      # mt3_op_pianoroll
+RENDER_TILE, RENDER_MAX_SAMPLE_RATE, RENDER_MAX_SAMPLES = 1024, 384000, 1 << 40      # mt3_op_render_notes
+RENDER_RELEASE_SECONDS, RENDER_DRUM_SECONDS = 0.04, 0.15
 
 
 class Mt3Error(RuntimeError):
@@ -281,6 +283,8 @@ SIGNATURES = {
     "mt3_op_pianoroll": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_double, C.c_int32, _P,
                                    C.c_int64, _P]),
     "mt3_op_frame_counts": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P]),
+    "mt3_op_render_notes": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P,
+                                      C.c_int64, _P, _P]),
 }
 
 _lib = None

@@ -639,6 +639,13 @@ class InferenceModel(object):
         from . import pianoroll
         return pianoroll.pianorolls([ns], fps)[0]
 
+    @staticmethod
+    def render(ns, sample_rate: int = 16000):
+        """A transcription as audio, to listen to: a float32 CUDA tensor [n] at `sample_rate`, peak 0.9
+        (`mt3_amd.render.render([ns], sample_rate)[0]`; one timbre for every program, a noise burst per drum note)."""
+        from . import render
+        return render.render([ns], sample_rate)[0]
+
     def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None, well_formed=False):
         """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
         NoteSequence per file, all segments through the engine as one job"""

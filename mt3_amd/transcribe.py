@@ -3,7 +3,7 @@
     python -m mt3_amd.transcribe --checkpoint PATH [--model mt3|ismir2021] [--dtype float32|bfloat16]
                                  [--decoding beam1|greedy|beam|sample] [--num-beams K] [--confidences]
                                  [--temperature T] [--top-k K] [--top-p P] [--seed N]
-                                 [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]]
+                                 [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]] [--render [RATE]]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -21,6 +21,9 @@ inputs share the job (`InferenceModel(decoding="sample", temperature=, top_k=, t
 --pianoroll [FPS] also writes NAME.npy beside each NAME.mid: the transcription's piano roll, uint16 [128, frames] at FPS
 frames per second (default 62.5), each note's velocity summed into its frames (cut at 65535), drum notes silent
 (`mt3_amd.pianoroll.pianorolls`: the rolls of all inputs are rasterised in one call once the job's notes are decoded).
+--render [RATE] also writes NAME.render.wav beside each NAME.mid: the transcription as mono int16 audio at RATE Hz (default
+16000), peak 0.9, to listen to (`mt3_amd.render.render`: one timbre for every program, a noise burst per drum note; all
+inputs are rendered in one call).  It is the sound of the notes as NAME.mid holds them, times on the file's tick grid.
 """
 from __future__ import annotations
 
@@ -65,6 +68,9 @@ def plan(argv=None):
     ap.add_argument("--pianoroll", type=float, nargs="?", const=62.5, default=None, metavar="FPS",
                     help="also write NAME.npy beside each NAME.mid: the piano roll, uint16 [128, frames] at FPS frames "
                          "per second (default 62.5)")
+    ap.add_argument("--render", type=int, nargs="?", const=16000, default=None, metavar="RATE",
+                    help="also write NAME.render.wav beside each NAME.mid: the transcription as int16 audio at RATE Hz "
+                         "(default 16000)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -76,6 +82,8 @@ def plan(argv=None):
         ap.error("--num-beams must be 1 .. 8")
     if args.pianoroll is not None and not (math.isfinite(args.pianoroll) and args.pianoroll > 0):
         ap.error("--pianoroll takes a positive number of frames per second")
+    if args.render is not None and not 1 <= args.render <= 384000:
+        ap.error("--render takes a sample rate of 1 .. 384000 Hz")
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
@@ -124,6 +132,11 @@ def main(argv=None) -> int:
             from . import pianoroll
             rolls = [r.clamp(0, 65535).to("cpu").numpy().astype(np.uint16)
                      for r in pianoroll.pianorolls(sequences, args.pianoroll)]
+        audio = None
+        if args.render is not None:
+            from . import render
+            written = [midi_io.midi_bytes_to_note_sequence(midi_io.note_sequence_to_midi_bytes(ns)) for ns in sequences]
+            audio = [a.cpu().numpy() for a in render.render(written, args.render)]
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -137,7 +150,15 @@ def main(argv=None) -> int:
     for roll, path in zip(rolls or [], outputs):
         import numpy as np
         np.save(pianoroll_path(path), roll)
+    for samples, path in zip(audio or [], outputs):
+        from . import audio_io
+        with open(render_path(path), "wb") as f:
+            f.write(audio_io.samples_to_wav_data(samples, args.render))
     return 0
+
+
+def render_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".render.wav"
 
 
 def pianoroll_path(midi_path: str) -> str:
