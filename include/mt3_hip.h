@@ -1570,6 +1570,86 @@ int mt3_op_render_notes(const double* d_start, const double* d_end, const double
                         const int64_t* h_n_samples /* [n_seq] */, int32_t sample_rate, int32_t normalize, float* d_out,
                         int64_t out_capacity, float* d_peaks /* [n_seq] */, void* stream);
 
+/* --------------------------------------------------- note matching
+ * Replaces the matching inside mir_eval.transcription.precision_recall_f1_overlap as mt3/metrics.py calls it (lines 97-99,
+ * 163-166, 267-290): for each problem of a job, the size of a MAXIMUM bipartite matching between reference and estimated
+ * notes, and the matching.  The size of a maximum matching is unique, so the 'Onset', 'Onset + offset', program-aware and
+ * tolerance-sweep scores that are quotients of it are pinned; which maximum matching is returned is not.  NOT BUILT: the
+ * '+ velocity' scores (mir_eval.transcription_velocity fits a regression to the velocities of the particular matching
+ * its Hopcroft-Karp returned, so their value depends on WHICH maximum matching one holds and cannot be pinned without
+ * mir_eval itself).
+ *
+ * job      packed float64 device arrays over all notes of the job: onset, offset (seconds) and log2(pitch) -- the
+ *          logarithm is taken on the host (numpy's log2), so the cents comparison never depends on a device log2.
+ * problem  reference notes [ref0, ref0 + n_ref), estimated notes [est0, est0 + n_est) SORTED ASCENDING BY ONSET (the caller
+ *          sorts them, stably), its state at d_workspace + state0 (in int32 words), and an index into the rule table.
+ *          Note ranges may be shared between problems (the onset-only, onset + offset and sweep problems of one track
+ *          read the same notes); state ranges may not.
+ * rule     onset_tolerance, pitch_tolerance, offset_ratio (MT3_NOTE_MATCH_NO_OFFSET: no offset test),
+ *          offset_min_tolerance, strict.
+ * edge     reference note i and estimate j can be paired when all of the following hold, every operation float64 and
+ *          rounded on its own (no fused multiply-add):
+ *            D(a, b) = rint(|a - b| * 1e6) / 1e6            (numpy's around(., 6): one product, rint, one quotient)
+ *            onset    D(ref_on, est_on) <= onset_tolerance
+ *            cents    |1200 * (l2_ref - l2_est)| <= pitch_tolerance, a NaN difference counting as 0
+ *            offset   D(ref_off, est_off) <= max(offset_ratio * (ref_off - ref_on), offset_min_tolerance)
+ *          with every <= a < under `strict`; and j lies in i's window, the estimates whose onset is in
+ *          [ref_on - m, ref_on + m], m = onset_tolerance + 1e-6 (found by binary search; it contains every j that passes
+ *          the onset test).  Adjacency is never stored: the predicate is evaluated again wherever it is needed, so no
+ *          size depends on a count the host would have to wait for.
+ * state    per problem, int32 words: mate_ref [n_ref] first -- the output: the estimate (index within the problem, in
+ *          its sorted order) matched to reference i, or -1 -- then five more arrays of n_ref (window bounds, level,
+ *          cursor, parent) and two of n_est (mate_est, claim).  Problems with unsorted estimates or NaN times may give a
+ *          matching that is not maximum; the kernel still touches only its own notes and its own state.
+ * warm start  with warm_start != 0 mate_ref is read as an initial partial matching.  An entry is kept only if it lies in
+ *          the window, passes the edge rule and claims an estimate no other entry has claimed; anything else counts as
+ *          -1.  A bad warm start therefore costs matches, never memory safety.  warm_start == 0: start empty.
+ * algorithm  one workgroup of 256 lanes per problem, 64 problems per launch, launches in stream order (so at most 64
+ *          workgroups are in flight at a time): a greedy pass (compare-and-swap on the estimate's mate), then
+ *          Hopcroft-Karp phases -- a level-synchronous breadth-first search from the free references, then one lane per
+ *          free reference walking the levels depth-first with its path in the state (no per-lane stack), estimates
+ *          claimed atomically so that paths are vertex-disjoint.  A phase whose search found a free estimate and whose
+ *          walks augmented nothing repeats the walk with one lane, so every phase adds a match; there are at most
+ *          min(n_ref, n_est) + 1 phases.  Should that bound ever be passed, the problem's count is written as -1.
+ *
+ * The state-words query: the int32 words of one problem's state, 6 n_ref + 2 n_est; -1 for a negative count.
+ *
+ * The matching op: d_matched [n_problems] int32 = the size of each problem's maximum matching (0 for a problem with an
+ *   empty side, whose mate_ref is all -1).  The two host tables go to the kernel BY VALUE (64 problems per launch, at most
+ *   MT3_NOTE_MATCH_MAX_RULES rules), so they are free when the call returns; everything is enqueued on `stream`, nothing
+ *   is allocated, copied to the host or waited for.  MT3_ERR_INVALID, before any HIP call: a negative n_problems, n_notes,
+ *   workspace_words or note count, n_rules outside 0 .. MT3_NOTE_MATCH_MAX_RULES, a NULL rule table with n_rules > 0, a
+ *   tolerance that is negative or not finite (offset_ratio: or not MT3_NOTE_MATCH_NO_OFFSET), a NULL problem table or NULL
+ *   d_matched with n_problems > 0, a NULL note array with n_notes > 0, a note range outside [0, n_notes], a rule index
+ *   out of range, state ranges that overlap or are out of order (state0 must not decrease below the previous problem's
+ *   end) or end past workspace_words, NULL d_workspace with a non-empty state.  n_problems == 0 is a valid call that
+ *   does nothing.
+ */
+#define MT3_NOTE_MATCH_MAX_RULES 16
+#define MT3_NOTE_MATCH_NO_OFFSET (-1.0)
+
+typedef struct mt3_match_rule {
+  double onset_tolerance, pitch_tolerance;
+  double offset_ratio;                /* MT3_NOTE_MATCH_NO_OFFSET: onsets and pitches only */
+  double offset_min_tolerance;
+  int32_t strict;
+  int32_t reserved;
+} mt3_match_rule;
+
+typedef struct mt3_match_problem {
+  int64_t ref0, est0;                 /* first reference / estimated note, in notes */
+  int64_t state0;                     /* first word of the state in d_workspace */
+  int32_t n_ref, n_est;
+  int32_t rule;
+  int32_t reserved;
+} mt3_match_problem;
+
+int64_t mt3_note_match_state_words(int32_t n_ref, int32_t n_est);
+int mt3_op_match_notes(const double* d_onset, const double* d_offset, const double* d_log2_pitch, int64_t n_notes,
+                       int32_t n_problems, const mt3_match_problem* h_problems /* [n_problems] */, int32_t n_rules,
+                       const mt3_match_rule* h_rules /* [n_rules] */, int32_t* d_workspace, int64_t workspace_words,
+                       int32_t warm_start, int32_t* d_matched /* [n_problems] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

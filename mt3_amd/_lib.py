@@ -38,6 +38,7 @@ TIE_DROP_REDUNDANT_PROGRAMS = 1                # mt3_op_tie_prompts flags
 PIANOROLL_PITCHES, PIANOROLL_MIN_NOTE_SECONDS = 128, 0.05      # mt3_op_pianoroll
 RENDER_TILE, RENDER_MAX_SAMPLE_RATE, RENDER_MAX_SAMPLES = 1024, 384000, 1 << 40      # mt3_op_render_notes
 RENDER_RELEASE_SECONDS, RENDER_DRUM_SECONDS = 0.04, 0.15
+NOTE_MATCH_MAX_RULES, NOTE_MATCH_NO_OFFSET = 16, -1.0          # mt3_op_match_notes
 
 
 class Mt3Error(RuntimeError):
@@ -89,6 +90,16 @@ class NoteStruct(C.Structure):
     _fields_ = [("start_time", C.c_double), ("end_time", C.c_double), ("pitch", C.c_int32),
                 ("velocity", C.c_int32), ("program", C.c_int32), ("is_drum", C.c_int32),
                 ("instrument", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MatchRule(C.Structure):                  # mt3_match_rule
+    _fields_ = [(n, C.c_double) for n in ("onset_tolerance", "pitch_tolerance", "offset_ratio", "offset_min_tolerance")] + \
+               [("strict", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MatchProblem(C.Structure):               # mt3_match_problem
+    _fields_ = [("ref0", C.c_int64), ("est0", C.c_int64), ("state0", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_ref", "n_est", "rule", "reserved")]
 
 
 _P = C.c_void_p
@@ -285,6 +296,9 @@ SIGNATURES = {
     "mt3_op_frame_counts": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P]),
     "mt3_op_render_notes": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P,
                                       C.c_int64, _P, _P]),
+    "mt3_note_match_state_words": (C.c_int64, [C.c_int32, C.c_int32]),
+    "mt3_op_match_notes": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P,
+                                     _P]),
 }
 
 _lib = None

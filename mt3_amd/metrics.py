@@ -215,6 +215,227 @@ def frame_scores(ref_ns: NoteSequence, est_ns: NoteSequence, fps: float = 62.5, 
     return frame_scores_many([(ref_ns, est_ns)], fps, velocity_threshold, is_drum)[0]
 
 
+# ------------------------------------------------------------------------- note-level scores of a whole job
+# The functions above score one pair and one criterion at a time on the host.  The ones below score a JOB: every
+# matching that every pair needs is first collected (`_MatchJob.add`), then all of them go through ONE
+# `note_matching.match` call on the device (mt3_op_match_notes; the rule: include/mt3_hip.h, "note matching"), then the
+# quotients are taken from the integer counts -- the same integers the host path divides, so the values are equal, not
+# close.  There is no host fallback.
+SWEEP_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)          # mt3/metrics.py:151
+
+
+class _MatchJob:
+    """the matchings of a job: `add` returns a ticket, `run` makes the one device call, `prf(ticket)` is
+    precision_recall_f1_overlap's (P, R, F) for it"""
+
+    def __init__(self):
+        self.problems, self.sizes, self.counts = [], [], None
+
+    def add(self, ref, est, **rule):
+        """ref, est: (intervals, pitches) as `sequence_to_valued_intervals` returns them"""
+        for _, pitches in (ref, est):                     # mir_eval.transcription.validate, as precision_recall_f1_overlap
+            if pitches.size and (pitches <= 0).any():
+                raise ValueError("precision_recall_f1_overlap: pitches must be positive (mir_eval.transcription.validate)")
+        n_ref, n_est = len(ref[1]), len(est[1])
+        slot = None
+        if n_ref and n_est:                               # an empty side scores zero without a matching
+            from . import note_matching
+            slot = len(self.problems)
+            self.problems.append(note_matching.Problem(ref[0], ref[1], est[0], est[1], **rule))
+        self.sizes.append((n_ref, n_est, slot))
+        return len(self.sizes) - 1
+
+    def run(self):
+        from . import note_matching
+        self.counts = note_matching.match(self.problems).counts if self.problems else np.zeros(0, np.int64)
+
+    def prf(self, ticket):
+        n_ref, n_est, slot = self.sizes[ticket]
+        if slot is None:
+            return 0.0, 0.0, 0.0
+        m = int(self.counts[slot])
+        p, r = m / n_est, m / n_ref
+        return p, r, f_measure(p, r)
+
+
+def _valued(ns: NoteSequence, drums: Optional[bool], pitch_unit: str = "note_number"):
+    iv, pitches, _ = sequence_to_valued_intervals(ns, drums=drums)
+    return iv, (_hz(pitches) if pitch_unit == "hz" else pitches)
+
+
+def _plan_transcription(job: _MatchJob, ref, est, offsets: bool = True):
+    """the 'Onset' and (with `offsets`) 'Onset + offset' matchings of one (ref, est) pair of valued intervals -> a
+    function that returns their scores once the job has run"""
+    names = [("Onset", None)] + ([("Onset + offset", 0.2)] if offsets else [])
+    tickets = [(name, job.add(ref, est, offset_ratio=ratio)) for name, ratio in names]
+
+    def finish():
+        out = {}
+        for name, ticket in tickets:
+            out[name + " precision"], out[name + " recall"], out[name + " F1"] = job.prf(ticket)
+        return out
+    return finish
+
+
+def _plan_program_aware(job: _MatchJob, ref_ns: NoteSequence, est_ns: NoteSequence, granularity_type: str):
+    """`program_aware_note_scores` with its matchings handed to the job: the same tracks in the same order, the same
+    sums"""
+    from . import vocabularies
+    pmap = vocabularies.PROGRAM_MAP_FNS[granularity_type]
+
+    def tracks(ns):
+        out = {}
+        for n in ns.notes:
+            key = (n.program if n.is_drum else pmap(n.program), bool(n.is_drum))
+            out.setdefault(key, []).append(n)
+        return out
+    ref_t, est_t = tracks(ref_ns), tracks(est_ns)
+    planned = []
+    for key in set(ref_t) | set(est_t):
+        ref = _valued(NoteSequence(notes=ref_t.get(key, [])), None)
+        est = _valued(NoteSequence(notes=est_t.get(key, [])), None)
+        planned.append((key[1], len(ref[1]), len(est[1]), job.add(ref, est, **({"offset_ratio": None} if key[1] else {}))))
+
+    def finish():
+        sums = {True: [0.0, 0, 0.0, 0], False: [0.0, 0, 0.0, 0]}
+        for is_drum, n_ref, n_est, ticket in planned:
+            p, r, _ = job.prf(ticket)
+            acc = sums[is_drum]
+            acc[0] += p * n_est
+            acc[1] += n_est
+            acc[2] += r * n_ref
+            acc[3] += n_ref
+
+        def prf(ps, pc, rs, rc):
+            p, r = (ps / pc) if pc else 0, (rs / rc) if rc else 0
+            return p, r, f_measure(p, r)
+        d, nd = sums[True], sums[False]
+        g = granularity_type
+        out = {}
+        for name, (p, r, f) in (("Onset + offset + program", prf(d[0] + nd[0], d[1] + nd[1], d[2] + nd[2], d[3] + nd[3])),
+                                ("Drum onset", prf(*d)), ("Nondrum onset + offset + program", prf(*nd))):
+            out[f"{name} precision ({g})"], out[f"{name} recall ({g})"], out[f"{name} F1 ({g})"] = p, r, f
+        return out
+    return finish
+
+
+def _plan_sweep(job: _MatchJob, ref, est, tolerances):
+    tickets = [(tol, job.add(ref, est, onset_tolerance=tol, offset_min_tolerance=tol)) for tol in tolerances]
+
+    def finish():
+        out = {}
+        for tol, ticket in tickets:
+            p, r, f = job.prf(ticket)
+            out[f"Onset + offset precision ({tol})"], out[f"Onset + offset recall ({tol})"] = p, r
+            out[f"Onset + offset F1 ({tol})"] = f
+        return out
+    return finish
+
+
+def _run_plans(job: _MatchJob, plans) -> list:
+    job.run()
+    return [finish() for finish in plans]
+
+
+def transcription_scores_many(pairs: Sequence, pitch_unit: str = "note_number") -> list:
+    """`transcription_scores` of every (ref_ns, est_ns) pair, all their matchings in ONE device call."""
+    if pitch_unit not in ("note_number", "hz"):
+        raise ValueError("pitch_unit must be 'note_number' or 'hz'")
+    job = _MatchJob()
+    return _run_plans(job, [_plan_transcription(job, _valued(r, False, pitch_unit), _valued(e, False, pitch_unit))
+                            for r, e in pairs])
+
+
+def program_aware_note_scores_many(pairs: Sequence, granularity_type: str = "full") -> list:
+    """`program_aware_note_scores` of every (ref_ns, est_ns) pair, the matchings of all their tracks in ONE device call."""
+    job = _MatchJob()
+    return _run_plans(job, [_plan_program_aware(job, r, e, granularity_type) for r, e in pairs])
+
+
+def note_onset_tolerance_sweep_many(pairs: Sequence, tolerances=SWEEP_TOLERANCES) -> list:
+    """mt3/metrics.py:149-172 `_note_onset_tolerance_sweep` for every (ref_ns, est_ns) pair: 'Onset + offset precision
+    (tol)' / 'recall (tol)' / 'F1 (tol)' with onset_tolerance = offset_min_tolerance = tol, over the non-drum notes (the
+    reference hands it the drumless sequences), pitches as note numbers.  One device call for the job."""
+    job = _MatchJob()
+    return _run_plans(job, [_plan_sweep(job, _valued(r, False), _valued(e, False), tuple(tolerances)) for r, e in pairs])
+
+
+def matched_notes(ref_ns: NoteSequence, est_ns: NoteSequence, pitch_unit: str = "note_number", onset_tolerance=0.05,
+                  pitch_tolerance=50.0, offset_ratio: Optional[float] = 0.2, offset_min_tolerance=0.05,
+                  strict=False) -> np.ndarray:
+    """The pairs of one maximum matching over the non-drum notes, as mir_eval.transcription.match_notes returns them:
+    int64 [matched, 2] of (index into ref_ns.notes, index into est_ns.notes).  The notes of ref_ns / est_ns that appear in
+    no pair are the missed / the extra ones.  WHICH maximum matching this is, is not pinned; its size is."""
+    from . import note_matching
+    if pitch_unit not in ("note_number", "hz"):
+        raise ValueError("pitch_unit must be 'note_number' or 'hz'")
+    job = _MatchJob()
+    ticket = job.add(_valued(ref_ns, False, pitch_unit), _valued(est_ns, False, pitch_unit), onset_tolerance=onset_tolerance,
+                     pitch_tolerance=pitch_tolerance, offset_ratio=offset_ratio, offset_min_tolerance=offset_min_tolerance,
+                     strict=strict)
+    if job.sizes[ticket][2] is None:
+        return np.zeros((0, 2), np.int64)
+    pairs = note_matching.match(job.problems).pairs(0)
+    kept = [np.array([i for i, n in enumerate(ns.notes) if n.end_time != n.start_time and not n.is_drum], np.int64)
+            for ns in (ref_ns, est_ns)]
+    return np.stack([kept[0][pairs[:, 0]], kept[1][pairs[:, 1]]], axis=1)
+
+
+def transcription_metrics(pairs: Sequence, track_specs=None, frame_fps: float = 62.5,
+                          frame_velocity_threshold: int = 30) -> Dict[str, dict]:
+    """The score dictionary of mt3/metrics.py:175-392 `transcription_metrics` for a job of (ref_ns, est_ns) pairs (what the
+    reference builds from its targets and predictions before scoring), as {"scores": {key: [one value per pair]},
+    "mean": {key: mean}}.  Keys, as the reference names them:
+      whole file, drums removed:   'Onset precision|recall|F1', 'Onset + offset precision|recall|F1',
+                                   'Frame Precision|Recall|F1' (`frame_scores_many`)
+      per `note_sequences.TrackSpec`: the same under 'NAME/...', of `extract_track(ns, program, is_drum)`; a drum track
+                                   has no 'Onset + offset' keys
+      per program granularity:     `program_aware_note_scores`' nine keys, for 'flat', 'midi_class' and 'full'
+      tolerance sweep:             `note_onset_tolerance_sweep_many`'s keys
+    Pitches go to the 50-cent rule as note numbers, as the reference passes them.  ALL note matchings of the job go
+    through one `note_matching.match` call; the frame scores through one `frame_scores_many` call per value of the
+    reference's is_drum flag (all of a track's reference notes are drums).
+    NOT BUILT: the 'Onset + velocity' and 'Onset + offset + velocity' scores -- mir_eval.transcription_velocity fits a
+    regression to the velocities of the particular matching its Hopcroft-Karp returned, so their value depends on which
+    maximum matching one holds and cannot be pinned without mir_eval; 'Invalid events' / 'Dropped events', which belong to
+    the decoding, not to a pair of NoteSequences; and the reference's histograms and audio / piano-roll summaries.
+    ValueError for a pitch <= 0 (mir_eval.transcription.validate); zero-length notes are dropped before anything is
+    counted (`sequence_to_valued_intervals`)."""
+    from . import note_sequences as NS
+    from . import vocabularies
+    pairs = list(pairs)
+    job, plans, frames = _MatchJob(), [], {True: [], False: []}
+
+    def drumless(ns):
+        return NoteSequence(notes=[n for n in ns.notes if not n.is_drum], total_time=ns.total_time,
+                            ticks_per_quarter=ns.ticks_per_quarter)
+    for k, (ref_ns, est_ns) in enumerate(pairs):
+        tracks = [("", drumless(ref_ns), drumless(est_ns), True)]
+        for spec in track_specs or ():
+            tracks.append((spec.name, NS.extract_track(ref_ns, spec.program, spec.is_drum),
+                           NS.extract_track(est_ns, spec.program, spec.is_drum), not spec.is_drum))
+        for name, ref_t, est_t, offsets in tracks:
+            prefix = name + "/" if name else ""
+            ref_v, est_v = _valued(ref_t, None), _valued(est_t, None)
+            plans.append((k, prefix, _plan_transcription(job, ref_v, est_v, offsets)))
+            if not name:                                  # the sweep reads the whole file's notes: the same arrays
+                plans.append((k, "", _plan_sweep(job, ref_v, est_v, SWEEP_TOLERANCES)))
+            frames[all(n.is_drum for n in ref_t.notes)].append((k, prefix, ref_t, est_t))
+        for g in vocabularies.PROGRAM_MAP_FNS:
+            plans.append((k, "", _plan_program_aware(job, ref_ns, est_ns, g)))
+    job.run()
+    rows = [dict() for _ in pairs]
+    for k, prefix, finish in plans:
+        rows[k].update({prefix + key: v for key, v in finish().items()})
+    for is_drum, items in frames.items():
+        if items:
+            got = frame_scores_many([(r, e) for _, _, r, e in items], frame_fps, frame_velocity_threshold, is_drum)
+            for (k, prefix, _, _), sc in zip(items, got):
+                rows[k].update({prefix + key: v for key, v in sc.items()})
+    scores = {key: [row[key] for row in rows] for key in (rows[0] if rows else {})}
+    return {"scores": scores, "mean": {key: float(np.mean(v)) for key, v in scores.items()}}
+
+
 # ------------------------------------------------------------------------------- precision-mode divergence report
 def token_stream_divergence(ref_tokens: np.ndarray, est_tokens: np.ndarray, codec=None, encoding_spec=None,
                             segment_seconds: float = 2.048) -> Dict[str, float]:

@@ -36,6 +36,21 @@ class NoteSequence:
     ticks_per_quarter: int = 220
 
 
+@dataclasses.dataclass
+class TrackSpec:
+    """One track to score on its own (note_sequences.py:35-39): the notes of one (program, is_drum), named."""
+    name: str
+    program: int = 0
+    is_drum: bool = False
+
+
+def extract_track(ns: NoteSequence, program: int, is_drum: bool) -> NoteSequence:
+    """The notes of `ns` with exactly that program and drum flag, in their order (the notes are shared, not copied);
+    total_time is their latest end, 0.0 without notes (note_sequences.py:42-49)."""
+    notes = [n for n in ns.notes if n.program == program and bool(n.is_drum) == bool(is_drum)]
+    return NoteSequence(notes=notes, total_time=max((n.end_time for n in notes), default=0.0), ticks_per_quarter=220)
+
+
 @dataclasses.dataclass(frozen=True)
 class NoteEncodingSpecType:
     """Which decoder the C library runs (note_sequences.py:411-446)."""

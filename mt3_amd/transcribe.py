@@ -4,7 +4,7 @@
                                  [--decoding beam1|greedy|beam|sample] [--num-beams K] [--confidences]
                                  [--temperature T] [--top-k K] [--top-p P] [--seed N]
                                  [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]] [--render [RATE]]
-                                 IN.wav [IN2.wav ...] [-o OUT]
+                                 [--score-against DIR] IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
 engine as one job (`InferenceModel.transcribe_wavs`).  --checkpoint is handed to `InferenceModel` as it is: a t5x
@@ -24,6 +24,11 @@ frames per second (default 62.5), each note's velocity summed into its frames (c
 --render [RATE] also writes NAME.render.wav beside each NAME.mid: the transcription as mono int16 audio at RATE Hz (default
 16000), peak 0.9, to listen to (`mt3_amd.render.render`: one timbre for every program, a noise burst per drum note; all
 inputs are rendered in one call).  It is the sound of the notes as NAME.mid holds them, times on the file's tick grid.
+--score-against DIR scores the job: for each input NAME.wav it reads DIR/NAME.mid as the reference, runs
+`metrics.transcription_metrics` on all (reference, transcription) pairs once -- every note matching of the job in one
+device call -- and writes scores.json into the output directory: {"files": {NAME: {key: value}}, "mean": {key: value}}.
+The output directory is the one the MIDI files go to; inputs that would be written to several directories (no -o, inputs
+in different places) are refused with --score-against: give -o DIR.
 """
 from __future__ import annotations
 
@@ -71,6 +76,10 @@ def plan(argv=None):
     ap.add_argument("--render", type=int, nargs="?", const=16000, default=None, metavar="RATE",
                     help="also write NAME.render.wav beside each NAME.mid: the transcription as int16 audio at RATE Hz "
                          "(default 16000)")
+    ap.add_argument("--score-against", default=None, metavar="DIR",
+                    help="also write scores.json into the output directory: the transcription metrics of every input "
+                         "NAME.wav against the reference DIR/NAME.mid, and their means (all MIDI files must go to one "
+                         "directory: -o DIR for inputs in several)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -87,6 +96,10 @@ def plan(argv=None):
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
+    if args.score_against is not None:
+        for path in args.inputs:
+            if not os.path.isfile(reference_path(args.score_against, path)):
+                ap.error("--score-against: no such file: %s" % reference_path(args.score_against, path))
     out = args.output
     if out is None:
         outputs = [os.path.splitext(p)[0] + ".mid" for p in args.inputs]
@@ -98,6 +111,8 @@ def plan(argv=None):
         outputs = [os.path.join(out, os.path.splitext(os.path.basename(p))[0] + ".mid") for p in args.inputs]
     if len(set(os.path.abspath(p) for p in outputs)) != len(outputs):
         ap.error("two inputs would be written to the same output file")
+    if args.score_against is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
+        ap.error("--score-against writes one scores.json into the output directory: inputs in several directories need -o DIR")
     return args, outputs
 
 
@@ -137,6 +152,14 @@ def main(argv=None) -> int:
             from . import render
             written = [midi_io.midi_bytes_to_note_sequence(midi_io.note_sequence_to_midi_bytes(ns)) for ns in sequences]
             audio = [a.cpu().numpy() for a in render.render(written, args.render)]
+        scored = None
+        if args.score_against is not None:
+            from . import metrics
+            references = []
+            for path in args.inputs:
+                with open(reference_path(args.score_against, path), "rb") as f:
+                    references.append(midi_io.midi_bytes_to_note_sequence(f.read()))
+            scored = metrics.transcription_metrics(list(zip(references, sequences)))
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -154,7 +177,21 @@ def main(argv=None) -> int:
         from . import audio_io
         with open(render_path(path), "wb") as f:
             f.write(audio_io.samples_to_wav_data(samples, args.render))
+    if scored is not None:
+        names = [os.path.splitext(os.path.basename(p))[0] for p in args.inputs]
+        with open(scores_path(outputs), "w") as f:
+            json.dump({"files": {name: {key: values[i] for key, values in scored["scores"].items()}
+                                 for i, name in enumerate(names)}, "mean": scored["mean"]}, f, indent=1)
     return 0
+
+
+def reference_path(directory: str, wav_path: str) -> str:
+    return os.path.join(directory, os.path.splitext(os.path.basename(wav_path))[0] + ".mid")
+
+
+def scores_path(outputs) -> str:
+    """scores.json of a job: in the directory its MIDI files are written to"""
+    return os.path.join(os.path.dirname(os.path.abspath(outputs[0])), "scores.json")
 
 
 def render_path(midi_path: str) -> str:
