@@ -1650,6 +1650,214 @@ int mt3_op_match_notes(const double* d_onset, const double* d_offset, const doub
                        const mt3_match_rule* h_rules /* [n_rules] */, int32_t* d_workspace, int64_t workspace_words,
                        int32_t warm_start, int32_t* d_matched /* [n_problems] */, void* stream);
 
+/* --------------------------------------------------- target tokenizer: notes -> the id rows the model is trained on
+ * The target side of the reference's data pipeline: mt3/preprocessors.py:93-226 (tokenize_transcription_example) and
+ * mt3/tasks.py:160-180 (extract_target_sequence_with_indices with the tie token, map_midi_programs,
+ * run_length_encode_shifts, remove_redundant_state_changes(['velocity', 'program']), trim, EOS), for the segments the
+ * inference path cuts.  The rule is stated once, below (mt3t_*); mt3_notes_tokenize is that rule on host arrays and
+ * mt3_op_tokenize_notes is the kernel that compiles the same functions.  Integers only: no floating point on the device.
+ *
+ * events   of one file, prepared by the host ALREADY IN THE REFERENCE'S ORDER (mt3_amd.tokenize.pack), six int32 arrays:
+ *          step     round(time * steps_per_second), Python's round (half to even on the float64 product), not negative and
+ *                   below INT32_MAX; ascending within a file (the host's stable sort by float64 time);
+ *          pitch, program   0 .. 127 (both are taken & 127: a bad value costs tokens, never memory safety);
+ *          velbin   0 = an offset, otherwise vocabularies.velocity_to_bin (taken clamped to 0 .. velocity_count - 1);
+ *          is_drum  (read by MT3_SPEC_TIES only);   note   the index of the event's note in the caller's list.
+ * segment  step_lo, step_hi: its events are those with step_lo <= step < step_hi (two binary searches); the last segment
+ *          of a file has step_hi = INT32_MAX.
+ * row      1. tie section (MT3_SPEC_TIES only).  b = the first event with step >= step_lo; if there is none, the FIRST
+ *             event whose step equals the file's last step (the reference's frozen_state_idx: its trailing shifts do not
+ *             refresh the state index, so trailing silence keeps the state from BEFORE the last step's first event --
+ *             reproduced, not repaired); 0 for an empty file (mt3t_tie_begin).  Events 0 .. b - 1 are replayed into a
+ *             table keyed by (program, pitch): drums skipped, velbin != 0 sets, velbin == 0 clears, the last writer
+ *             wins.  The held pairs go out in ascending (program, pitch) order as program id, pitch id; then tie_id.
+ *          2. the segment's events: [shift] program velocity pitch, or [shift] velocity drum for a drum, or [shift]
+ *             velocity pitch under MT3_SPEC_NOTES.  With d = step - step_lo, shift ids come before an event exactly when d
+ *             exceeds the d of the segment's previous event (0 before the first); a d above max_shift_steps is split into
+ *             d / max_shift_steps ids of max_shift_steps and, if not zero, one of the rest (mt3t_shift_count, _value).
+ *          3. program granularity: program_map[p], keyed by the ORIGINAL program, is the program to write, or -1 to write
+ *             no program id for it (full: p; midi_class: 8 * (p / 8); flat: -1).
+ *          4. redundant state changes, over the whole row: a program id equal to the last program id before it in the
+ *             row is dropped, a velocity id likewise against the last velocity id; "none yet" matches nothing.
+ *          5. EOS (1), then the cut to `stride` ids: a row that does not fit ends without EOS and has truncated = 1.
+ * outputs  per row: ids [stride] int32, 0-padded; length (EOS included); truncated; note_of [stride] int32: at every pitch
+ *          or drum id of the EVENT part the event's `note`, -1 elsewhere (tie section included); is_onset [stride] uint8:
+ *          1 at those positions where the event's velbin is not 0, else 0.
+ * mt3_codec_tokenize_rule fills the descriptor from a codec: the id bases (token id = 3 + event index), max_shift_steps
+ *   and the map of `granularity` (MT3_GRANULARITY_*).  MT3_ERR_INVALID: null pointers, a malformed codec, a spec other
+ *   than MT3_SPEC_NOTES / MT3_SPEC_TIES, an unknown granularity, a codec without pitch, velocity (from 0), tie, program and
+ *   drum ranges or whose pitch, program or drum range is not 0 .. 127, ranges that do not fit below vocab.
+ * mt3_notes_tokenize: one row of one file on HOST arrays (n_events >= 0; the arrays may be NULL when it is 0).
+ * mt3_op_tokenize_notes: a JOB in one launch.  d_files [n_files]: each file's event range in the six device arrays and
+ *   its rows [row0, row0 + n_rows); d_rows [rows]: file, step_lo, step_hi, in ascending step_lo within a file.  One
+ *   workgroup of 256 lanes per file walks its rows in order; the held table stays in LDS and is advanced by the events
+ *   between consecutive tie-section starts (last writer by an LDS table of positions, as mt3_op_tie_prompts).  Indices read
+ *   from the two device tables are range-checked in the kernel: a file whose event range leaves [0, n_events] counts as
+ *   empty, rows outside [0, rows) or owned by another file are not written, a tie-section start that runs backwards
+ *   leaves the table as it is.  Enqueued on `stream`; nothing is allocated, copied or waited for.
+ * MT3_ERR_INVALID, before any HIP call (both entry points, where the argument exists): a null rule, table or output
+ *   pointer; a null event array with n_events > 0; n_events < 0; n_files < 1; rows < 1; stride < 2 or above 2^20; a spec
+ *   other than the two; max_shift_steps < 1; velocity_count < 1; a program_map entry outside -1 .. 127; vocab < 4 or an id
+ *   base whose range does not lie in [3, vocab). */
+enum { MT3_GRANULARITY_FULL = 0, MT3_GRANULARITY_MIDI_CLASS = 1, MT3_GRANULARITY_FLAT = 2 };
+#define MT3_TOKENIZE_PROGRAMS 128
+#define MT3_TOKENIZE_PITCHES 128
+#define MT3_TOKENIZE_MAX_STRIDE (1 << 20)
+
+typedef struct mt3_tokenize_rule {
+  int32_t spec, vocab, max_shift_steps;
+  int32_t shift_first, pitch_first, velocity_first, velocity_count, tie_id, program_first, drum_first;
+  int32_t reserved[2];
+  int32_t program_map[MT3_TOKENIZE_PROGRAMS];
+} mt3_tokenize_rule;
+
+typedef struct mt3_tokenize_file {
+  int64_t event0;                     /* first event of the file in the job's event arrays */
+  int32_t n_events;
+  int32_t row0, n_rows;               /* its rows, one per segment, in order */
+  int32_t reserved;
+} mt3_tokenize_file;
+
+typedef struct mt3_tokenize_row {
+  int32_t file, step_lo, step_hi, reserved;
+} mt3_tokenize_row;
+
+/* the first i in [0, n) with step[i] >= key, n if there is none */
+MT3_RULE_FN int32_t mt3t_lower_bound(const int32_t* step, int32_t n, int32_t key) {
+  int32_t lo = 0, hi = n < 0 ? 0 : n;
+  while (lo < hi) {                                          /* at most 32 rounds */
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (step[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+/* b of the tie section: the events before it are the ones replayed */
+MT3_RULE_FN int32_t mt3t_tie_begin(const int32_t* step, int32_t n, int32_t step_lo) {
+  if (n <= 0) return 0;
+  const int32_t b = mt3t_lower_bound(step, n, step_lo);
+  return b < n ? b : mt3t_lower_bound(step, n, step[n - 1]);
+}
+MT3_RULE_FN int32_t mt3t_index(int32_t v) { return (int32_t)((uint32_t)v & 127u); }
+MT3_RULE_FN int32_t mt3t_velbin(const mt3_tokenize_rule* r, int32_t v) {
+  return v < 0 ? 0 : (v >= r->velocity_count ? r->velocity_count - 1 : v);
+}
+/* the shift ids in front of an event at d steps from the segment's start, the event before it at `prev` */
+MT3_RULE_FN int64_t mt3t_shift_count(const mt3_tokenize_rule* r, int64_t d, int64_t prev) {
+  return d > prev ? (d + r->max_shift_steps - 1) / r->max_shift_steps : 0;
+}
+/* the value of the k-th of them */
+MT3_RULE_FN int32_t mt3t_shift_value(const mt3_tokenize_rule* r, int64_t d, int64_t k) {
+  return k < d / r->max_shift_steps ? r->max_shift_steps : (int32_t)(d % r->max_shift_steps);
+}
+/* what the op's argument checks say about a rule and a stride: NULL if fine */
+MT3_RULE_FN const char* mt3t_bad_rule(const mt3_tokenize_rule* r, int32_t stride) {
+  if (!r) return "null rule";
+  if (stride < 2 || stride > MT3_TOKENIZE_MAX_STRIDE) return "stride must be in [2, 2^20]";
+  if (r->spec != 1 /* MT3_SPEC_NOTES */ && r->spec != 2 /* MT3_SPEC_TIES */) return "spec must be MT3_SPEC_NOTES or MT3_SPEC_TIES";
+  if (r->max_shift_steps < 1) return "max_shift_steps must be at least 1";
+  if (r->velocity_count < 1) return "velocity_count must be at least 1";
+  for (int32_t p = 0; p < MT3_TOKENIZE_PROGRAMS; ++p)
+    if (r->program_map[p] < -1 || r->program_map[p] > 127) return "program_map entries must be in -1 .. 127";
+  if (r->vocab < 4) return "vocab must be at least 4";
+  {
+    const int64_t v = r->vocab;
+    if (r->shift_first < 3 || (int64_t)r->shift_first + r->max_shift_steps >= v) return "id base: the shift ids do not fit vocab";
+    if (r->pitch_first < 3 || (int64_t)r->pitch_first + MT3_TOKENIZE_PITCHES > v) return "id base: the pitch ids do not fit vocab";
+    if (r->velocity_first < 3 || (int64_t)r->velocity_first + r->velocity_count > v)
+      return "id base: the velocity ids do not fit vocab";
+    if (r->spec == 2) {
+      if (r->tie_id < 3 || r->tie_id >= v) return "id base: tie_id does not fit vocab";
+      if (r->program_first < 3 || (int64_t)r->program_first + MT3_TOKENIZE_PROGRAMS > v)
+        return "id base: the program ids do not fit vocab";
+      if (r->drum_first < 3 || (int64_t)r->drum_first + MT3_TOKENIZE_PITCHES > v) return "id base: the drum ids do not fit vocab";
+    }
+  }
+  return 0;
+}
+/* one id at position *at of a row, if it still fits; the position advances either way */
+MT3_RULE_FN void mt3t_put(int32_t stride, int64_t* at, int32_t id, int32_t note, int32_t onset, int32_t* ids,
+                          int32_t* note_of, uint8_t* is_onset) {
+  if (*at < stride) {
+    ids[*at] = id;
+    note_of[*at] = note;
+    is_onset[*at] = (uint8_t)onset;
+  }
+  ++*at;
+}
+/* EOS or the cut, the padding, length and truncated of a row whose ids end at `at` */
+MT3_RULE_FN void mt3t_finish(int32_t stride, int64_t at, int32_t* ids, int32_t* note_of, uint8_t* is_onset, int32_t* length,
+                             int32_t* truncated) {
+  if (at < stride) mt3t_put(stride, &at, 1, -1, 0, ids, note_of, is_onset);
+  else { *length = stride; *truncated = 1; return; }
+  *length = (int32_t)at;
+  *truncated = 0;
+  while (at < stride) mt3t_put(stride, &at, 0, -1, 0, ids, note_of, is_onset);
+}
+/* THE RULE: one row, serially.  The arrays are the file's own (event 0 first). */
+MT3_RULE_FN void mt3t_row(const mt3_tokenize_rule* r, const int32_t* step, const int32_t* pitch, const int32_t* program,
+                          const int32_t* velbin, const int32_t* is_drum, const int32_t* note, int32_t n_events,
+                          int32_t step_lo, int32_t step_hi, int32_t stride, int32_t* ids, int32_t* note_of,
+                          uint8_t* is_onset, int32_t* length, int32_t* truncated) {
+  const int ties = r->spec == 2 /* MT3_SPEC_TIES */;
+  int64_t at = 0, prev = 0;
+  int32_t last_program = -1, last_velocity = -1;
+  if (n_events < 0) n_events = 0;
+  if (ties) {
+    uint32_t held[MT3_TOKENIZE_PROGRAMS * MT3_TOKENIZE_PITCHES / 32];
+    const int32_t b = mt3t_tie_begin(step, n_events, step_lo);
+    for (int32_t w = 0; w < MT3_TOKENIZE_PROGRAMS * MT3_TOKENIZE_PITCHES / 32; ++w) held[w] = 0;
+    for (int32_t e = 0; e < b; ++e) {
+      if (is_drum[e]) continue;
+      const int32_t bit = mt3t_index(program[e]) * MT3_TOKENIZE_PITCHES + mt3t_index(pitch[e]);
+      if (mt3t_velbin(r, velbin[e])) held[bit >> 5] |= 1u << (bit & 31);
+      else held[bit >> 5] &= ~(1u << (bit & 31));
+    }
+    for (int32_t bit = 0; bit < MT3_TOKENIZE_PROGRAMS * MT3_TOKENIZE_PITCHES; ++bit) {
+      if (!((held[bit >> 5] >> (bit & 31)) & 1u)) continue;
+      const int32_t m = r->program_map[bit / MT3_TOKENIZE_PITCHES];
+      if (m >= 0 && m != last_program) mt3t_put(stride, &at, r->program_first + m, -1, 0, ids, note_of, is_onset);
+      if (m >= 0) last_program = m;
+      mt3t_put(stride, &at, r->pitch_first + bit % MT3_TOKENIZE_PITCHES, -1, 0, ids, note_of, is_onset);
+    }
+    mt3t_put(stride, &at, r->tie_id, -1, 0, ids, note_of, is_onset);
+  }
+  {
+    const int32_t e_lo = mt3t_lower_bound(step, n_events, step_lo);
+    const int32_t e_hi = step_hi > step_lo ? mt3t_lower_bound(step, n_events, step_hi) : e_lo;
+    for (int32_t e = e_lo; e < e_hi; ++e) {
+      const int64_t d = (int64_t)step[e] - step_lo, n_shift = mt3t_shift_count(r, d, prev);
+      const int32_t v = mt3t_velbin(r, velbin[e]), drum = ties && is_drum[e];
+      for (int64_t k = 0; k < n_shift && at < stride; ++k)
+        mt3t_put(stride, &at, r->shift_first + mt3t_shift_value(r, d, k), -1, 0, ids, note_of, is_onset);
+      if (n_shift && at >= stride) at = (int64_t)stride + 1;       /* the rest of them are past the cut */
+      prev = d;
+      if (ties && !drum) {
+        const int32_t m = r->program_map[mt3t_index(program[e])];
+        if (m >= 0 && m != last_program) mt3t_put(stride, &at, r->program_first + m, -1, 0, ids, note_of, is_onset);
+        if (m >= 0) last_program = m;
+      }
+      if (v != last_velocity) mt3t_put(stride, &at, r->velocity_first + v, -1, 0, ids, note_of, is_onset);
+      last_velocity = v;
+      mt3t_put(stride, &at, (drum ? r->drum_first : r->pitch_first) + mt3t_index(pitch[e]), note[e], v != 0, ids, note_of,
+               is_onset);
+    }
+  }
+  mt3t_finish(stride, at, ids, note_of, is_onset, length, truncated);
+}
+
+int mt3_codec_tokenize_rule(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t granularity, mt3_tokenize_rule* out);
+int mt3_notes_tokenize(const mt3_tokenize_rule* r, const int32_t* h_step, const int32_t* h_pitch, const int32_t* h_program,
+                       const int32_t* h_velbin, const int32_t* h_is_drum, const int32_t* h_note, int32_t n_events,
+                       int32_t step_lo, int32_t step_hi, int32_t stride, int32_t* h_ids /* [stride] */,
+                       int32_t* h_note_of /* [stride] */, uint8_t* h_is_onset /* [stride] */, int32_t* h_length,
+                       int32_t* h_truncated);
+int mt3_op_tokenize_notes(const mt3_tokenize_rule* r, const int32_t* d_step, const int32_t* d_pitch, const int32_t* d_program,
+                          const int32_t* d_velbin, const int32_t* d_is_drum, const int32_t* d_note, int64_t n_events,
+                          const mt3_tokenize_file* d_files, int32_t n_files, const mt3_tokenize_row* d_rows, int32_t rows,
+                          int32_t stride, int32_t* d_ids /* [rows][stride] */, int32_t* d_lengths /* [rows] */,
+                          int32_t* d_truncated /* [rows] */, int32_t* d_note_of /* [rows][stride] */,
+                          uint8_t* d_is_onset /* [rows][stride] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,9 @@ PIANOROLL_PITCHES, PIANOROLL_MIN_NOTE_SECONDS = 128, 0.05      # mt3_op_pianorol
 RENDER_TILE, RENDER_MAX_SAMPLE_RATE, RENDER_MAX_SAMPLES = 1024, 384000, 1 << 40      # mt3_op_render_notes
 RENDER_RELEASE_SECONDS, RENDER_DRUM_SECONDS = 0.04, 0.15
 NOTE_MATCH_MAX_RULES, NOTE_MATCH_NO_OFFSET = 16, -1.0          # mt3_op_match_notes
+GRANULARITY_FULL, GRANULARITY_MIDI_CLASS, GRANULARITY_FLAT = range(3)      # mt3_codec_tokenize_rule
+GRANULARITIES = {"full": GRANULARITY_FULL, "midi_class": GRANULARITY_MIDI_CLASS, "flat": GRANULARITY_FLAT}
+TOKENIZE_MAX_STRIDE = 1 << 20                  # mt3_op_tokenize_notes
 
 
 class Mt3Error(RuntimeError):
@@ -100,6 +103,20 @@ class MatchRule(C.Structure):                  # mt3_match_rule
 class MatchProblem(C.Structure):               # mt3_match_problem
     _fields_ = [("ref0", C.c_int64), ("est0", C.c_int64), ("state0", C.c_int64)] + \
                [(n, C.c_int32) for n in ("n_ref", "n_est", "rule", "reserved")]
+
+
+class TokenizeRule(C.Structure):               # mt3_tokenize_rule
+    _fields_ = [(n, C.c_int32) for n in ("spec", "vocab", "max_shift_steps", "shift_first", "pitch_first",
+                                         "velocity_first", "velocity_count", "tie_id", "program_first", "drum_first")] + \
+               [("reserved", C.c_int32 * 2), ("program_map", C.c_int32 * 128)]
+
+
+class TokenizeFile(C.Structure):               # mt3_tokenize_file
+    _fields_ = [("event0", C.c_int64)] + [(n, C.c_int32) for n in ("n_events", "row0", "n_rows", "reserved")]
+
+
+class TokenizeRow(C.Structure):                # mt3_tokenize_row
+    _fields_ = [(n, C.c_int32) for n in ("file", "step_lo", "step_hi", "reserved")]
 
 
 _P = C.c_void_p
@@ -299,6 +316,11 @@ SIGNATURES = {
     "mt3_note_match_state_words": (C.c_int64, [C.c_int32, C.c_int32]),
     "mt3_op_match_notes": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P,
                                      _P]),
+    "mt3_codec_tokenize_rule": (C.c_int, [C.POINTER(CodecDesc), C.c_int32, C.c_int32, C.c_int32, C.POINTER(TokenizeRule)]),
+    "mt3_notes_tokenize": (C.c_int, [C.POINTER(TokenizeRule), _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mt3_op_tokenize_notes": (C.c_int, [C.POINTER(TokenizeRule), _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P,
+                                        C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

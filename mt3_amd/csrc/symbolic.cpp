@@ -474,4 +474,58 @@ int mt3_notes_decode_traced(const mt3_codec* c, int32_t spec, int32_t n_segments
                            total_time, h_note_tokens);
 }
 
+// ---- the target tokenizer on the host (the rule: include/mt3_hip.h, mt3t_*; the kernel: tokenize.hip)
+int mt3_codec_tokenize_rule(const mt3_codec* c, int32_t spec, int32_t vocab, int32_t granularity, mt3_tokenize_rule* out) {
+  const std::string who = "mt3_codec_tokenize_rule: ";
+  if (!c || !out) return mt3::fail(MT3_ERR_INVALID, who + "null argument");
+  CodecTable t(c);
+  if (!t.ok) return mt3::fail(MT3_ERR_INVALID, who + "malformed codec");
+  if (spec != MT3_SPEC_NOTES && spec != MT3_SPEC_TIES)
+    return mt3::fail(MT3_ERR_INVALID, who + "spec must be MT3_SPEC_NOTES or MT3_SPEC_TIES (onsets only has no offsets to encode)");
+  if (granularity < MT3_GRANULARITY_FULL || granularity > MT3_GRANULARITY_FLAT)
+    return mt3::fail(MT3_ERR_INVALID, who + "unknown granularity");
+  int at[6] = {-1, -1, -1, -1, -1, -1};
+  for (int k = 0; k < t.n; ++k)
+    if (t.type[k] >= 0 && t.type[k] < 6) at[t.type[k]] = k;
+  for (int type : {MT3_EV_PITCH, MT3_EV_VELOCITY, MT3_EV_TIE, MT3_EV_PROGRAM, MT3_EV_DRUM})
+    if (at[type] < 0) return mt3::fail(MT3_ERR_INVALID, who + "the codec needs pitch, velocity, tie, program and drum ranges");
+  for (int type : {MT3_EV_PITCH, MT3_EV_PROGRAM, MT3_EV_DRUM})
+    if (t.lo[at[type]] != 0 || t.hi[at[type]] != 127)
+      return mt3::fail(MT3_ERR_INVALID, who + "the codec's pitch, program and drum ranges must be 0 .. 127");
+  if (t.lo[at[MT3_EV_VELOCITY]] != 0) return mt3::fail(MT3_ERR_INVALID, who + "the codec's velocity range must start at 0");
+  if (3 + static_cast<int64_t>(t.num_classes()) > vocab)
+    return mt3::fail(MT3_ERR_INVALID, who + "the codec's ranges do not fit below vocab");
+  mt3_tokenize_rule r{};
+  r.spec = spec;
+  r.vocab = vocab;
+  r.max_shift_steps = t.hi[0];
+  r.shift_first = 3 + t.start[0];
+  r.pitch_first = 3 + t.start[at[MT3_EV_PITCH]];
+  r.velocity_first = 3 + t.start[at[MT3_EV_VELOCITY]];
+  r.velocity_count = t.hi[at[MT3_EV_VELOCITY]] + 1;
+  r.tie_id = 3 + t.start[at[MT3_EV_TIE]];
+  r.program_first = 3 + t.start[at[MT3_EV_PROGRAM]];
+  r.drum_first = 3 + t.start[at[MT3_EV_DRUM]];
+  for (int p = 0; p < MT3_TOKENIZE_PROGRAMS; ++p)          // mt3/vocabularies.py:77-116, the token side of a granularity
+    r.program_map[p] = granularity == MT3_GRANULARITY_FLAT ? -1 : granularity == MT3_GRANULARITY_MIDI_CLASS ? 8 * (p / 8) : p;
+  if (const char* bad = mt3t_bad_rule(&r, 2)) return mt3::fail(MT3_ERR_INVALID, who + bad);
+  *out = r;
+  return MT3_OK;
+}
+
+int mt3_notes_tokenize(const mt3_tokenize_rule* r, const int32_t* h_step, const int32_t* h_pitch, const int32_t* h_program,
+                       const int32_t* h_velbin, const int32_t* h_is_drum, const int32_t* h_note, int32_t n_events,
+                       int32_t step_lo, int32_t step_hi, int32_t stride, int32_t* h_ids, int32_t* h_note_of,
+                       uint8_t* h_is_onset, int32_t* h_length, int32_t* h_truncated) {
+  const std::string who = "mt3_notes_tokenize: ";
+  if (const char* bad = mt3t_bad_rule(r, stride)) return mt3::fail(MT3_ERR_INVALID, who + bad);
+  if (n_events < 0) return mt3::fail(MT3_ERR_INVALID, who + "n_events must not be negative");
+  if (n_events > 0 && (!h_step || !h_pitch || !h_program || !h_velbin || !h_is_drum || !h_note))
+    return mt3::fail(MT3_ERR_INVALID, who + "null event array");
+  if (!h_ids || !h_note_of || !h_is_onset || !h_length || !h_truncated) return mt3::fail(MT3_ERR_INVALID, who + "null output");
+  mt3t_row(r, h_step, h_pitch, h_program, h_velbin, h_is_drum, h_note, n_events, step_lo, step_hi, stride, h_ids, h_note_of,
+           h_is_onset, h_length, h_truncated);
+  return MT3_OK;
+}
+
 }  // extern "C"

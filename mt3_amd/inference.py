@@ -608,6 +608,118 @@ class InferenceModel(object):
         tok = np.concatenate(tok) if tok else np.zeros((0, n), np.float64)
         return scores, [tok[i, : len(r)] for i, r in enumerate(rows)]
 
+    # ------------------------------------------------------------------ known notes against audio
+    def _num_frames(self, audio_or_num_samples, sample_rate: int = SAMPLE_RATE) -> int:
+        """the spectrogram frames `__call__` cuts audio of that many samples into (`_audio_to_frames` always pads)"""
+        n = int(audio_or_num_samples) if np.ndim(audio_or_num_samples) == 0 else int(np.shape(audio_or_num_samples)[0])
+        if int(sample_rate) != SAMPLE_RATE:
+            n = audio_io.resampled_length(n, int(sample_rate), SAMPLE_RATE)
+        return n // self.spectrogram_config.hop_width + 1
+
+    def _tokenize_kw(self):
+        return dict(stride=self.outputs_length, segment_frames=self.inputs_length,
+                    frames_per_second=self.spectrogram_config.frames_per_second, vocab_size=self.model_config.vocab_size)
+
+    def targets(self, audio_or_num_samples, ns, *, sample_rate: int = SAMPLE_RATE, granularity: str = "full"):
+        """The training targets of `ns` for this audio (a 1-d array of samples, or just their number): one int32 id row
+        per segment of `__call__`, in the form `score` takes -- the tie section, the segment's events, EOS; cut to
+        `outputs_length` ids (`tokenize.target_rows`, on the device)."""
+        from . import tokenize
+        rows = tokenize.target_rows([ns], [self._num_frames(audio_or_num_samples, sample_rate)], self.codec,
+                                    self.encoding_spec, granularity, **self._tokenize_kw())
+        ids, lengths = rows.ids.cpu().numpy(), rows.lengths.cpu().numpy()
+        return [ids[i, : lengths[i]].copy() for i in range(len(ids))]
+
+    def score_notes(self, audio, ns, *, sample_rate: int = SAMPLE_RATE, shifts=None, granularity: str = "full",
+                    return_note_scores: bool = False):
+        """How well do the notes `ns` explain `audio`?  The model's teacher-forced loss on the training targets of `ns`
+        (t5x's eval loss of one (audio, MIDI) pair) -> a dict:
+          'loss'                minus the sum of the token log-probabilities over all kept ids (EOS included), divided by
+                                their number; with shifts: a float64 array, one loss per shift
+          'segment_scores'      float64 [n_segments]: the sum of token log-probabilities of each segment (what `score`
+                                returns for `targets(audio, ns)`); with shifts: of the best shift
+          'token_accuracy'      the share of kept ids that are the model's arg-max at their position
+          'truncated_segments'  segments whose targets did not fit `outputs_length` ids (they end without EOS)
+          'best_shift'          with shifts: the shift of the lowest loss (the first of equals)
+        shifts: offsets in seconds; the notes are scored once per offset, each added to every note time (clamped at 0) --
+        all of them tokenized in one launch and scored in one engine call.  granularity: 'full', 'midi_class' or 'flat'.
+        return_note_scores: also float64 arrays aligned with `ns.notes` (of the best shift) -- 'onset_logprob' and
+        'onset_margin' of the note's onset pitch / drum id as in `transcribe_scored`, 'end_logprob' of its note-off pitch id;
+        NaN for an id that was cut or does not exist (a drum has no end).
+        Frontend and segments are those of `__call__`; the rows are built on the device (`tokenize.target_rows`) and go
+        straight to `Transformer.score_segments`.  ValueError with e4m3 K/V caches, as `score`."""
+        return self.score_notes_many([(audio, ns)], sample_rates=[sample_rate], shifts=shifts, granularity=granularity,
+                                     return_note_scores=return_note_scores)[0]
+
+    def score_notes_many(self, pairs, *, sample_rates: Optional[Sequence[int]] = None, shifts=None,
+                         granularity: str = "full", return_note_scores: bool = False) -> List[Dict[str, Any]]:
+        """`score_notes` of several (audio, NoteSequence) pairs as ONE job: one tokenizer launch and one scoring call over
+        the segments of all files (and all shifts).  Returns one dict per pair."""
+        import torch
+        from . import tokenize
+        self._refuse_e4m3("score_notes")
+        if sample_rates is None:
+            sample_rates = [SAMPLE_RATE] * len(pairs)
+        if len(sample_rates) != len(pairs):
+            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(pairs)))
+        shift_list = None if shifts is None else [float(s) for s in shifts]
+        if shift_list is not None and not shift_list:
+            raise ValueError("shifts must not be empty")
+        if not pairs:
+            return []
+        feats, n_frames = [], []
+        for (audio, _), rate in zip(pairs, sample_rates):
+            examples = self._examples(audio, rate)
+            feats.append(self._logmel_dev)
+            n_frames.append(sum(len(ex["input_times"]) for ex in examples))
+        self._logmel_dev = None
+        rows = tokenize.target_rows([ns for _, ns in pairs], n_frames, self.codec, self.encoding_spec, granularity,
+                                    shifts=shift_list, **self._tokenize_kw())
+        table = rows.rows_of_file                            # [files, shifts or 1, (first row, rows)]
+        per = table.shape[1]
+        seg0 = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])])
+        source = np.concatenate([seg0[i] + np.arange(table[i, j, 1]) for i in range(len(pairs)) for j in range(per)])
+        group = np.concatenate([np.full(table[i, j, 1], i * per + j) for i in range(len(pairs)) for j in range(per)])
+        x = torch.cat(feats, 0)
+        if per > 1 or len(source) != x.shape[0]:
+            x = x.index_select(0, torch.from_numpy(source).to(x.device))
+        width = max(int(rows.lengths.max()), 1)              # 4 bytes back: the width `score` would use
+        self._ensure_slots(len(source))
+        seq, tok, _, top = self.model.score_segments(x, rows.ids[:, :width].contiguous(), return_token_scores=True,
+                                                     return_top1=True)
+        kept = torch.arange(width, device=tok.device)[None, :] < rows.lengths[:, None]
+        at_best = ((tok == top) & kept).sum(1)
+        groups = torch.from_numpy(group).to(tok.device)
+        zeros = torch.zeros(len(pairs) * per, device=tok.device, dtype=torch.float64)
+        total = zeros.index_add(0, groups, seq.double()).cpu().numpy().reshape(len(pairs), per)
+        count = zeros.index_add(0, groups, rows.lengths.double()).cpu().numpy().reshape(len(pairs), per)
+        best = zeros.index_add(0, groups, at_best.double()).cpu().numpy().reshape(len(pairs), per)
+        cut = zeros.index_add(0, groups, rows.truncated.double()).cpu().numpy().reshape(len(pairs), per)
+        seq_host = seq.cpu().numpy().astype(np.float64)
+        out = []
+        for i, (_, ns) in enumerate(pairs):
+            loss = -total[i] / count[i]
+            j = int(np.argmin(loss))
+            first, n = int(table[i, j, 0]), int(table[i, j, 1])
+            rec = {"loss": loss if shift_list is not None else float(loss[0]), "segment_scores": seq_host[first: first + n],
+                   "token_accuracy": float(best[i, j] / count[i, j]), "truncated_segments": int(cut[i, j])}
+            if shift_list is not None:
+                rec["best_shift"] = shift_list[j]
+            if return_note_scores:
+                note_of = rows.note_of[first: first + n, :width]
+                have = (note_of >= 0) & kept[first: first + n]
+                which = note_of[have].cpu().numpy()
+                onset = rows.is_onset[first: first + n, :width][have].cpu().numpy().astype(bool)
+                logp = tok[first: first + n][have].cpu().numpy().astype(np.float64)
+                margin = (tok - top)[first: first + n][have].cpu().numpy().astype(np.float64)
+                for key in ("onset_logprob", "onset_margin", "end_logprob"):
+                    rec[key] = np.full(len(ns.notes), np.nan)
+                rec["onset_logprob"][which[onset]] = logp[onset]
+                rec["onset_margin"][which[onset]] = margin[onset]
+                rec["end_logprob"][which[~onset]] = logp[~onset]
+            out.append(rec)
+        return out
+
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
                         drums=True, prompts=None, well_formed: bool = False) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of

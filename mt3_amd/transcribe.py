@@ -80,6 +80,13 @@ def plan(argv=None):
                     help="also write scores.json into the output directory: the transcription metrics of every input "
                          "NAME.wav against the reference DIR/NAME.mid, and their means (all MIDI files must go to one "
                          "directory: -o DIR for inputs in several)")
+    ap.add_argument("--score-midi", default=None, metavar="DIR",
+                    help="also write midi_scores.json into the output directory: how well the known notes DIR/NAME.mid "
+                         "explain every input NAME.wav -- the model's teacher-forced loss on the MIDI's target tokens "
+                         "(same one-directory rule as --score-against)")
+    ap.add_argument("--score-shifts", type=_shift_list, default=None, metavar="S[,S...]",
+                    help="--score-midi: also score the MIDI moved by each of these offsets in seconds, and report the best "
+                         "(a list that starts with a minus sign is written --score-shifts=-0.1,0,0.1)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -100,6 +107,12 @@ def plan(argv=None):
         for path in args.inputs:
             if not os.path.isfile(reference_path(args.score_against, path)):
                 ap.error("--score-against: no such file: %s" % reference_path(args.score_against, path))
+    if args.score_shifts is not None and args.score_midi is None:
+        ap.error("--score-shifts needs --score-midi")
+    if args.score_midi is not None:
+        for path in args.inputs:
+            if not os.path.isfile(reference_path(args.score_midi, path)):
+                ap.error("--score-midi: no such file: %s" % reference_path(args.score_midi, path))
     out = args.output
     if out is None:
         outputs = [os.path.splitext(p)[0] + ".mid" for p in args.inputs]
@@ -113,7 +126,19 @@ def plan(argv=None):
         ap.error("two inputs would be written to the same output file")
     if args.score_against is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
         ap.error("--score-against writes one scores.json into the output directory: inputs in several directories need -o DIR")
+    if args.score_midi is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
+        ap.error("--score-midi writes one midi_scores.json into the output directory: inputs in several directories need -o DIR")
     return args, outputs
+
+
+def _shift_list(text: str):
+    try:
+        shifts = [float(v) for v in text.split(",") if v.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError("--score-shifts takes comma-separated seconds, got %r" % (text,)) from None
+    if not shifts or any(not math.isfinite(v) for v in shifts):
+        raise argparse.ArgumentTypeError("--score-shifts takes finite offsets in seconds, got %r" % (text,))
+    return shifts
 
 
 def _program_list(text: str):
@@ -160,6 +185,16 @@ def main(argv=None) -> int:
                 with open(reference_path(args.score_against, path), "rb") as f:
                     references.append(midi_io.midi_bytes_to_note_sequence(f.read()))
             scored = metrics.transcription_metrics(list(zip(references, sequences)))
+        midi_scores = None
+        if args.score_midi is not None:
+            from . import audio_io
+            pairs, rates = [], []
+            for path in args.inputs:
+                samples, rate = audio_io.read_wav(path)
+                with open(reference_path(args.score_midi, path), "rb") as f:
+                    pairs.append((samples, midi_io.midi_bytes_to_note_sequence(f.read())))
+                rates.append(rate)
+            midi_scores = model.score_notes_many(pairs, sample_rates=rates, shifts=args.score_shifts)
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -182,7 +217,21 @@ def main(argv=None) -> int:
         with open(scores_path(outputs), "w") as f:
             json.dump({"files": {name: {key: values[i] for key, values in scored["scores"].items()}
                                  for i, name in enumerate(names)}, "mean": scored["mean"]}, f, indent=1)
+    if midi_scores is not None:
+        with open(midi_scores_path(outputs), "w") as f:
+            json.dump([midi_score_record(path, sc) for path, sc in zip(args.inputs, midi_scores)], f, indent=1)
     return 0
+
+
+def midi_scores_path(outputs) -> str:
+    """midi_scores.json of a job: beside scores.json"""
+    return os.path.join(os.path.dirname(os.path.abspath(outputs[0])), "midi_scores.json")
+
+
+def midi_score_record(audio_path: str, scores) -> dict:
+    """one JSON-ready record of `InferenceModel.score_notes`: arrays as lists"""
+    plain = (lambda v: v.tolist() if hasattr(v, "tolist") else v)
+    return dict({"audio": audio_path}, **{k: plain(v) for k, v in scores.items()})
 
 
 def reference_path(directory: str, wav_path: str) -> str:
