@@ -889,6 +889,31 @@ int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs /* [n_segment
                               int32_t* d_top1_ids /* [n, length] or NULL */, float* d_top1_scores /* [n, length] or NULL */,
                               void* stream);
 
+/* Scoring of CANDIDATES: `per` target rows against every segment, the segment encoded ONCE -- the table of an offset
+ * search (the same notes under `per` time shifts) without `per` encoder passes per segment.
+ * d_inputs [n_segments, T, input_depth] f32 (log-mel); d_targets [n_segments * per, length] int32: row s * per + j is
+ * candidate j of segment s.  The outputs are those of mt3_engine_score_segments, one row per target row:
+ * d_sequence_scores [n_segments * per]; d_token_scores, d_top1_ids, d_top1_scores [n_segments * per, length] or NULL.
+ * Work: the encoder chunks of mt3_engine_score_segments over the n_segments segments (at most max_batch each; in bf16 a
+ * short last chunk padded to a pass of min(8, max_batch) rows, exactly as there); per chunk of n segments the prefill
+ * of mt3_engine_score over its n * per rows, in pieces that fit the score workspace.  Row i of the chunk reads the
+ * cross-K/V cache at row i / per (a divisor in the cross-attention launch; the kernel is the one
+ * mt3_op_score_attention runs); embedding, self-attention, dense tiles and reductions are launched as they are there.
+ * Contract: the outputs are BIT-IDENTICAL to mt3_engine_score_segments on the job with every segment repeated `per`
+ * times (row s * per + j of its inputs = segment s) wherever that function gives a segment the same bits in any batch:
+ * f32 always; bf16 when every encoder pass of BOTH calls holds 8 or more segments (see mt3_engine_encode) -- the tiles
+ * of the prefill do not depend on the batch or the piece, so only the encoder can tell the two jobs apart.
+ * State: as mt3_engine_score_segments -- the engine is left encoded with the last pass of the n_segments segments; the
+ * decode state is not touched.  MT3_STATUS_SCORE_CHUNKS reports the prefill pieces of the whole call and
+ * MT3_STATUS_SCORE_ENCODER_PASSES its encoder passes (ceil(n_segments / max_batch), whatever `per` is).
+ * MT3_ERR_INVALID, before any device work: everything mt3_engine_score_segments refuses; per < 1; n_segments * per
+ * above INT32_MAX. */
+int mt3_engine_score_candidates(mt3_engine* e, const float* d_inputs /* [n_segments, T, input_depth] log-mel */,
+                                int32_t n_segments, int32_t per, int32_t length,
+                                const int32_t* d_targets /* [n_segments * per, length] */,
+                                float* d_sequence_scores /* [n_segments * per] */, float* d_token_scores /* or NULL */,
+                                int32_t* d_top1_ids /* or NULL */, float* d_top1_scores /* or NULL */, void* stream);
+
 /* Engine facts a caller cannot see from results alone (a negative return is an mt3_status).
  * GRAPH_FALLBACKS: decode calls so far whose step graph could not be captured/instantiated and that therefore
  * ran as direct launches (same ids, slower) -- the fallback is counted, never silent;
@@ -907,7 +932,8 @@ enum { MT3_STATUS_GRAPH_FALLBACKS = 0, MT3_STATUS_LAST_DECODE_USED_GRAPH = 1, MT
        MT3_STATUS_PROMPTS = 13 /* prompts set by mt3_engine_set_prompts (0: none) */,
        MT3_STATUS_TOKEN_GRAMMAR = 14 /* 1: a grammar is set by mt3_engine_set_token_grammar (0: none) */,
        MT3_STATUS_SAMPLING = 15 /* 1: sampling is set by mt3_engine_set_sampling (0: none) */,
-       MT3_STATUS_NOTE_GRAMMAR = 16 /* 1: a note grammar is set by mt3_engine_set_note_grammar (0: none) */ };
+       MT3_STATUS_NOTE_GRAMMAR = 16 /* 1: a note grammar is set by mt3_engine_set_note_grammar (0: none) */,
+       MT3_STATUS_SCORE_ENCODER_PASSES = 17 /* encoder passes of the most recent mt3_engine_score_segments / mt3_engine_score_candidates */ };
 int mt3_engine_status(const mt3_engine* e, int32_t what);
 
 /* GenericTokenVocabulary._decode_tf (mt3/vocabularies.py:241-271): -1 from the
@@ -1857,6 +1883,35 @@ int mt3_op_tokenize_notes(const mt3_tokenize_rule* r, const int32_t* d_step, con
                           int32_t stride, int32_t* d_ids /* [rows][stride] */, int32_t* d_lengths /* [rows] */,
                           int32_t* d_truncated /* [rows] */, int32_t* d_note_of /* [rows][stride] */,
                           uint8_t* d_is_onset /* [rows][stride] */, void* stream);
+
+/* ---- shift paths: the best time shift per segment of every file of a job (alignment of known notes to audio).
+ * d_scores [total_segments][K] f32: the log-probability of segment s under shift j of the grid, as
+ * mt3_engine_score_candidates writes its sequence scores with per = K.  h_files [n_files][2] int32: (first segment,
+ * segments S) of each file, in increasing order and without overlap.  h_grid [K] float64: the shifts in seconds,
+ * finite and strictly increasing, 1 <= K <= MT3_ALIGN_MAX_SHIFTS.  smoothness: lambda >= 0 (finite), in log-probability
+ * per second of jump between neighbouring segments.  max_jump >= 0: the largest jump allowed, INFINITY: any.
+ * THE RULE, per file, all in float64 (numpy statement: mt3_amd/alignment.py, best_paths_reference):
+ *   c[s][j] = -(double)score[s][j];   D[0][j] = c[0][j];
+ *   D[s][j] = c[s][j] + min over k with |g_j - g_k| <= max_jump of (D[s-1][k] + lambda * |g_j - g_k|),
+ * the LOWEST k on equal values; the path ends at the lowest j of minimal D[S-1][j] and is read back through the stored k.
+ * Every difference, product and sum is rounded once, in the order written (no fused multiply-add), so the device
+ * result is numpy's bit for bit.  The scores must be finite (with NaN or infinite scores the path is still a row of
+ * indices in [0, K), but which one is not stated).
+ * d_path [total_segments] int32: the shift index of every segment that belongs to a file (the others are not written);
+ * d_total [n_files] float64: D[S-1] at the path's end = minus the path's log-probability plus its jump penalties.
+ * d_backptr: total_segments * K bytes of scratch (the stored k of every (segment, shift)), so the number of segments of
+ * a file is not bounded by LDS.  Work: one workgroup of 64 lanes per file, lane j owns shift j, the row D[s-1][.] in
+ * LDS; 64 files per launch (their table and the grid ride in the kernel arguments), the launches one after the other on
+ * `stream`.  Microseconds for a job: the kernel exists so that the table never leaves the device, not for speed.
+ * MT3_ERR_INVALID, before any device work: a NULL pointer; K outside 1 .. 64; a grid that is not finite and strictly
+ * increasing; lambda or max_jump negative or NaN, lambda infinite; total_segments or n_files < 0; S < 1; a segment range
+ * outside [0, total_segments], overlapping the one before it or out of order.  n_files == 0 is MT3_OK and does
+ * nothing. */
+#define MT3_ALIGN_MAX_SHIFTS 64
+int mt3_op_align_paths(const float* d_scores /* [total_segments][K] */, int32_t total_segments, int32_t K,
+                       const int32_t* h_files /* [n_files][2] */, int32_t n_files, const double* h_grid /* [K] */,
+                       double smoothness, double max_jump, uint8_t* d_backptr /* [total_segments * K] */,
+                       int32_t* d_path /* [total_segments] */, double* d_total /* [n_files] */, void* stream);
 
 #ifdef __cplusplus
 }

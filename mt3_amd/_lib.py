@@ -26,7 +26,7 @@ DEBUG_SKIP_SELF_ATTN, DEBUG_SKIP_CROSS_ATTN = 1, 2
 (STATUS_GRAPH_FALLBACKS, STATUS_LAST_DECODE_USED_GRAPH, STATUS_RESIDUAL_SPLIT, STATUS_KV_FP8, STATUS_Q_FOLD,
  STATUS_DENSE_FP8, STATUS_QKV_FOLD, STATUS_LAST_DECODE_GROUPS, STATUS_PARTITION_FALLBACKS,
  STATUS_LAST_DECODE_COMPACTIONS, STATUS_LAST_DECODE_FORKS, STATUS_SCORE_CHUNKS, STATUS_TOKEN_MASKS,
- STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR, STATUS_SAMPLING, STATUS_NOTE_GRAMMAR) = range(17)
+ STATUS_PROMPTS, STATUS_TOKEN_GRAMMAR, STATUS_SAMPLING, STATUS_NOTE_GRAMMAR, STATUS_SCORE_ENCODER_PASSES) = range(18)
 SAMPLING_MAX_TOP_K, SAMPLING_MAX_VOCAB = 256, 2048      # mt3_engine_set_sampling
 (MT3_PCM_U8, MT3_PCM_S16, MT3_PCM_S24, MT3_PCM_S32, MT3_PCM_F32, MT3_PCM_F64) = range(6)     # mt3_pcm_decode formats
 PCM_MAX_CHANNELS = 7
@@ -42,6 +42,7 @@ NOTE_MATCH_MAX_RULES, NOTE_MATCH_NO_OFFSET = 16, -1.0          # mt3_op_match_no
 GRANULARITY_FULL, GRANULARITY_MIDI_CLASS, GRANULARITY_FLAT = range(3)      # mt3_codec_tokenize_rule
 GRANULARITIES = {"full": GRANULARITY_FULL, "midi_class": GRANULARITY_MIDI_CLASS, "flat": GRANULARITY_FLAT}
 TOKENIZE_MAX_STRIDE = 1 << 20                  # mt3_op_tokenize_notes
+ALIGN_MAX_SHIFTS = 64                          # mt3_op_align_paths
 
 
 class Mt3Error(RuntimeError):
@@ -195,6 +196,7 @@ SIGNATURES = {
     "mt3_engine_decode_forced": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_engine_score": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_score_segments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mt3_engine_score_candidates": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_set_token_masks": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     "mt3_engine_set_prompts": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "mt3_engine_set_token_grammar": (C.c_int, [_P, C.POINTER(TokenGrammar)]),
@@ -321,6 +323,7 @@ SIGNATURES = {
                                      C.c_int32, _P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mt3_op_tokenize_notes": (C.c_int, [C.POINTER(TokenizeRule), _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P,
                                         C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mt3_op_align_paths": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_double, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -375,6 +375,7 @@ struct mt3_engine {
   int score_Lp = 0;              // rows per segment: max_decode_len rounded up to 64
   int score_chunk_req = 0;       // mt3_debug_engine_set_score_chunk (0: the workspace default)
   int score_chunks = 0;          // chunks of the most recent score call
+  int score_passes = 0;          // encoder passes of the most recent mt3_engine_score_segments / _score_candidates
   bool score_planes = false;     // f32 engine (x6): the plane copies of the decoder's matrices and of logits_w exist
   float* sc_y = nullptr;         // [rows][emb] f32 residual rows
   void* sc_y_ct = nullptr;       // bf16: compute-type copy [rows][emb] ...
@@ -2760,10 +2761,11 @@ static int ensure_score_planes(mt3_engine* e, hipStream_t s) {
   return MT3_OK;
 }
 
-// The prefill and the reduction of `batch` segments whose cross-K/V sit in cache rows row0 .. row0 + batch - 1 of the
-// last encoder pass; the caller arrays start at the first of them.  d_top1_ids / d_top1_scores (either): the reduction
-// is launch_score_stats instead of launch_score_reduce (same token and sequence scores)
-static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0, const int32_t* d_targets,
+// The prefill and the reduction of `batch` rows whose cross-K/V sit in cache rows row0 .. of the last encoder pass, `per`
+// consecutive rows on each cache row (row i reads cache row row0 + i / per; per = 1: one row each); the caller arrays
+// start at the first of them.  d_top1_ids / d_top1_scores (either): the reduction is launch_score_stats instead of
+// launch_score_reduce (same token and sequence scores)
+static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0, int32_t per, const int32_t* d_targets,
                       const int32_t* d_decoder_inputs, const float* d_weights, float* d_sequence_scores,
                       float* d_token_scores, int32_t* d_top1_ids, float* d_top1_scores, float* d_logits, hipStream_t s) {
   const mt3_engine_config& c = e->cfg;
@@ -2810,13 +2812,17 @@ static int score_impl(mt3_engine* e, int32_t batch, int32_t length, int32_t row0
       MT3_TRY(resid_gemm(e, L.wo, e->sc_attn, R, false, s));
       MT3_TRY(normed_gemm(e, R, L.wq_x, e->sc_q, hd, MT3_EPI_STORE, false, s));
       {
-        // the cross K/V cache of the encoded batch: [2][cur_batch][H][T][64]; the chunk's segments start at row row0 + seg0
+        // the cross K/V cache of the encoded batch: [2][cur_batch][H][T][64]; the chunk's rows start at cache row
+        // row0 + seg0 / per, seg0 % per rows into its group of `per`
         const size_t head = static_cast<size_t>(T) * 64;
+        const int kv0 = row0 + seg0 / per;
         mt3k::ScoreAttnArgs a{};
         a.q = e->sc_q;
         a.q_stride = hd;
-        a.k = static_cast<const char*>(L.cross_kv) + static_cast<size_t>(row0 + seg0) * H * head * es;
-        a.v = static_cast<const char*>(L.cross_kv) + (static_cast<size_t>(e->cur_batch) + row0 + seg0) * H * head * es;
+        a.k = static_cast<const char*>(L.cross_kv) + static_cast<size_t>(kv0) * H * head * es;
+        a.v = static_cast<const char*>(L.cross_kv) + (static_cast<size_t>(e->cur_batch) + kv0) * H * head * es;
+        a.kv_share = per;
+        a.kv_b0 = seg0 % per;
         a.kv_stride = 64;
         a.kv_bstride = static_cast<long long>(H) * head;
         a.kv_hstride = static_cast<long long>(head);
@@ -2865,24 +2871,29 @@ int mt3_engine_score(mt3_engine* e, int32_t batch, int32_t length, const int32_t
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
   if (batch <= 0 || batch > e->cur_batch)
     return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score: batch must be in 1 .. the batch of the preceding encode");
-  return score_impl(e, batch, length, 0, d_targets, d_decoder_inputs, d_weights, d_sequence_scores, d_token_scores, nullptr,
+  return score_impl(e, batch, length, 0, 1, d_targets, d_decoder_inputs, d_weights, d_sequence_scores, d_token_scores, nullptr,
                     nullptr, d_logits, static_cast<hipStream_t>(stream));
 }
 
-int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t length,
-                              const int32_t* d_targets, float* d_sequence_scores, float* d_token_scores,
-                              int32_t* d_top1_ids, float* d_top1_scores, void* stream) {
-  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: null engine");
+// mt3_engine_score_segments (per = 1) and mt3_engine_score_candidates: `per` target rows on every segment's one encoder
+// pass; fn: "<function>: "
+static int score_job(mt3_engine* e, const std::string& fn, const float* d_inputs, int32_t n_segments, int32_t per,
+                     int32_t length, const int32_t* d_targets, float* d_sequence_scores, float* d_token_scores,
+                     int32_t* d_top1_ids, float* d_top1_scores, void* stream) {
+  if (!e) return mt3::fail(MT3_ERR_INVALID, fn + "null engine");
   if (!d_inputs || !d_targets || !d_sequence_scores)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: null inputs, targets or sequence scores");
-  if (n_segments < 1) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: n_segments must be >= 1");
+    return mt3::fail(MT3_ERR_INVALID, fn + "null inputs, targets or sequence scores");
+  if (n_segments < 1) return mt3::fail(MT3_ERR_INVALID, fn + "n_segments must be >= 1");
+  if (per < 1) return mt3::fail(MT3_ERR_INVALID, fn + "per must be >= 1");
+  if (static_cast<int64_t>(n_segments) * per > INT32_MAX)
+    return mt3::fail(MT3_ERR_INVALID, fn + "n_segments * per must fit int32");
   if (length < 1 || length > e->cfg.max_decode_len)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: length must be in 1 .. max_decode_len");
+    return mt3::fail(MT3_ERR_INVALID, fn + "length must be in 1 .. max_decode_len");
   if (e->kv_fp8)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: engines with e4m3 K/V caches (kv_cache_dtype MT3_FP8_E4M3) cannot score");
-  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: engine not finalized");
+    return mt3::fail(MT3_ERR_INVALID, fn + "engines with e4m3 K/V caches (kv_cache_dtype MT3_FP8_E4M3) cannot score");
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, fn + "engine not finalized");
   if (e->pending.active)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_score_segments: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+    return mt3::fail(MT3_ERR_INVALID, fn + "a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
   const mt3_engine_config& c = e->cfg;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t seg_floats = static_cast<size_t>(c.input_length) * c.input_depth;
@@ -2891,20 +2902,35 @@ int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs, int32_t n_se
   const int min_batch = c.compute_dtype == MT3_BF16 ? std::min(c.max_batch, kStageMinBatch) : 0;
   Feed feed;
   feed.n_total = n_segments;
-  int chunks = 0;
-  for (int q = 0;; ++q) {
+  int chunks = 0, passes = 0;
+  for (int q = 0;; ++q, ++passes) {
     int first, n, pad;
     if (!mt3feed::feed_claim(feed, q, c.max_batch, min_batch, &first, &n, &pad)) break;
     MT3_TRY(encode_impl(e, d_inputs + static_cast<size_t>(first - pad) * seg_floats, pad + n, nullptr, CrossDst{}, s));
     e->cur_batch = pad + n;
-    const size_t at = static_cast<size_t>(first) * length;
-    MT3_TRY(score_impl(e, n, length, pad, d_targets + at, nullptr, nullptr, d_sequence_scores + first,
+    const size_t row = static_cast<size_t>(first) * per, at = row * length;
+    MT3_TRY(score_impl(e, n * per, length, pad, per, d_targets + at, nullptr, nullptr, d_sequence_scores + row,
                        d_token_scores ? d_token_scores + at : nullptr, d_top1_ids ? d_top1_ids + at : nullptr,
                        d_top1_scores ? d_top1_scores + at : nullptr, nullptr, s));
     chunks += e->score_chunks;
   }
   e->score_chunks = chunks;
+  e->score_passes = passes;
   return MT3_OK;
+}
+
+int mt3_engine_score_segments(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t length,
+                              const int32_t* d_targets, float* d_sequence_scores, float* d_token_scores,
+                              int32_t* d_top1_ids, float* d_top1_scores, void* stream) {
+  return score_job(e, "mt3_engine_score_segments: ", d_inputs, n_segments, 1, length, d_targets, d_sequence_scores,
+                   d_token_scores, d_top1_ids, d_top1_scores, stream);
+}
+
+int mt3_engine_score_candidates(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t per, int32_t length,
+                                const int32_t* d_targets, float* d_sequence_scores, float* d_token_scores,
+                                int32_t* d_top1_ids, float* d_top1_scores, void* stream) {
+  return score_job(e, "mt3_engine_score_candidates: ", d_inputs, n_segments, per, length, d_targets, d_sequence_scores,
+                   d_token_scores, d_top1_ids, d_top1_scores, stream);
 }
 
 // ---- mt3_hip_debug.h
@@ -3165,6 +3191,7 @@ int mt3_engine_status(const mt3_engine* e, int32_t what) {
     case MT3_STATUS_LAST_DECODE_COMPACTIONS: return e->compactions;
     case MT3_STATUS_LAST_DECODE_FORKS: return e->h_pinned ? e->h_pinned[kForksPinned] : 0;
     case MT3_STATUS_SCORE_CHUNKS: return e->score_chunks;
+    case MT3_STATUS_SCORE_ENCODER_PASSES: return e->score_passes;
     case MT3_STATUS_TOKEN_MASKS: return e->tm.n;
     case MT3_STATUS_PROMPTS: return e->tp.n;
     case MT3_STATUS_TOKEN_GRAMMAR: return e->gr.on && !e->nt.on ? 1 : 0;

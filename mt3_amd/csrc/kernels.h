@@ -502,6 +502,8 @@ struct ScoreAttnArgs {
   int out_stride;
   int B, H, Lq, n_keys;   // Lq % 64 == 0; causal: n_keys = Lq; cross: n_keys = T (a multiple of 64)
   int causal;
+  // rows that share one K / V row (mt3_engine_score_candidates): batch b reads K / V batch (b + kv_b0) / kv_share
+  int kv_share = 1, kv_b0 = 0;
 };
 int launch_score_attention(int dtype, const ScoreAttnArgs& a, hipStream_t s);
 struct ScoreReduceArgs {

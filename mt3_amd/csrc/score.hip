@@ -82,8 +82,9 @@ __global__ __launch_bounds__(256) void score_attn_kernel(ScoreAttnArgs a) {
   const int fr = lane & 15, fg = lane >> 4;
   const int q0 = qb * 64 + wave * 16;             // the wave's 16 queries
   const CT* qbase = static_cast<const CT*>(a.q) + (static_cast<size_t>(b) * a.Lq) * a.q_stride + h * D;
-  const CT* kbase = static_cast<const CT*>(a.k) + static_cast<size_t>(b) * a.kv_bstride + static_cast<size_t>(h) * a.kv_hstride;
-  const CT* vbase = static_cast<const CT*>(a.v) + static_cast<size_t>(b) * a.kv_bstride + static_cast<size_t>(h) * a.kv_hstride;
+  const int kvb = (b + a.kv_b0) / a.kv_share;      // kv_share = 1, kv_b0 = 0: b
+  const CT* kbase = static_cast<const CT*>(a.k) + static_cast<size_t>(kvb) * a.kv_bstride + static_cast<size_t>(h) * a.kv_hstride;
+  const CT* vbase = static_cast<const CT*>(a.v) + static_cast<size_t>(kvb) * a.kv_bstride + static_cast<size_t>(h) * a.kv_hstride;
   const int* ktgt = a.key_tgt ? a.key_tgt + static_cast<size_t>(b) * a.Lq : nullptr;
 
   u32x4 qf[NC];
@@ -237,7 +238,8 @@ __global__ __launch_bounds__(256) void score_attn_kernel(ScoreAttnArgs a) {
 
 int launch_score_attention(int dtype, const ScoreAttnArgs& a, hipStream_t s) {
   if (!a.q || !a.k || !a.v || !a.out || a.B <= 0 || a.H <= 0 || a.Lq <= 0 || a.Lq % 64 ||
-      (a.causal ? (a.n_keys != a.Lq) : (a.n_keys <= 0 || a.n_keys % 64)))
+      (a.causal ? (a.n_keys != a.Lq) : (a.n_keys <= 0 || a.n_keys % 64)) || a.kv_share < 1 || a.kv_b0 < 0 ||
+      a.kv_b0 >= a.kv_share)
     return mt3::fail(MT3_ERR_INVALID, "score_attention: bad arguments");
   const dim3 grid(a.B * a.H * (a.Lq / 64)), block(256);
   if (dtype == MT3_BF16) hipLaunchKernelGGL(score_attn_kernel<__bf16>, grid, block, 0, s, a);

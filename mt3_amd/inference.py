@@ -720,6 +720,91 @@ class InferenceModel(object):
             out.append(rec)
         return out
 
+    def align_notes(self, audio, ns, *, max_shift: float = 0.2, step: float = 0.02, shifts=None, smoothness=None,
+                    max_jump=None, sample_rate: int = SAMPLE_RATE, granularity: str = "full", shared_encoder: bool = True,
+                    return_table: bool = False):
+        """Repair the timing of the notes `ns` against `audio`: a time shift per segment, chosen as the smooth path of the
+        highest log-probability through the (segment, shift) table, and the notes warped by it -> a dict:
+          'notes'           the warped NoteSequence (`alignment.warp_notes`: the shift is interpolated between the
+                            segments' centres and evaluated at each note time; every other field is kept)
+          'segment_shifts'  float64 [n_segments]: the path, in seconds
+          'path_score'      the path's log-probability minus its jump penalties (smoothness * |jump| per step)
+          'flat_shift', 'flat_score'  the best constant path of the same table (one global shift, the lowest of equals)
+                            and its log-probability (never above 'path_score')
+          'scores'          with return_table: float64 [n_segments, n_shifts], the table
+        The shifts are `alignment.shift_grid(max_shift, step)` or `shifts` (strictly increasing seconds, at most 64).
+        smoothness: log-probability per second of jump (default `alignment.DEFAULT_SMOOTHNESS`); max_jump: the largest
+        jump between neighbouring segments in seconds (default: any).  A grid on which a path may jump by a segment's
+        length or more is refused (ValueError).  Every segment is scored under a GLOBAL shift of the notes, so a note
+        near a jump may be counted in both neighbouring segments or in neither; the shifts are segment-granular.
+        shared_encoder: every segment is encoded once for all shifts (`Transformer.score_candidates`); False: the table
+        comes from `score_segments` on the log-mel replicated per shift, as `score_notes` gets it -- the same bits in
+        float32.  ValueError with e4m3 K/V caches, as `score_notes`."""
+        return self.align_notes_many([(audio, ns)], sample_rates=[sample_rate], max_shift=max_shift, step=step,
+                                     shifts=shifts, smoothness=smoothness, max_jump=max_jump, granularity=granularity,
+                                     shared_encoder=shared_encoder, return_table=return_table)[0]
+
+    def align_notes_many(self, pairs, *, sample_rates: Optional[Sequence[int]] = None, max_shift: float = 0.2,
+                         step: float = 0.02, shifts=None, smoothness=None, max_jump=None, granularity: str = "full",
+                         shared_encoder: bool = True, return_table: bool = False) -> List[Dict[str, Any]]:
+        """`align_notes` of several (audio, NoteSequence) pairs as ONE job: one tokenizer launch, one scoring call and one
+        path call over the segments of all files.  Returns one dict per pair."""
+        import torch
+        from . import alignment, tokenize
+        self._refuse_e4m3("align_notes")
+        if sample_rates is None:
+            sample_rates = [SAMPLE_RATE] * len(pairs)
+        if len(sample_rates) != len(pairs):
+            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(pairs)))
+        grid = alignment.shift_grid(max_shift, step) if shifts is None else np.asarray(shifts, np.float64).reshape(-1)
+        smoothness = alignment.DEFAULT_SMOOTHNESS if smoothness is None else float(smoothness)
+        seconds = self.inputs_length / self.spectrogram_config.frames_per_second
+        alignment._check([1], 1, grid, smoothness, max_jump)
+        alignment.check_jumps(grid, max_jump, seconds)
+        if not pairs:
+            return []
+        feats, n_frames = [], []
+        for (audio, _), rate in zip(pairs, sample_rates):
+            examples = self._examples(audio, rate)
+            feats.append(self._logmel_dev)
+            n_frames.append(sum(len(ex["input_times"]) for ex in examples))
+        self._logmel_dev = None
+        K = len(grid)
+        rows = tokenize.target_rows([ns for _, ns in pairs], n_frames, self.codec, self.encoding_spec, granularity,
+                                    shifts=[float(g) for g in grid], **self._tokenize_kw())
+        table = rows.rows_of_file                            # [files, K, (first row, rows)]
+        counts = [int(f.shape[0]) for f in feats]
+        # the tokenizer's rows are (file, shift, segment); the table is (file, segment, shift)
+        order = np.concatenate([(table[i, :, 0][None, :] + np.arange(counts[i])[:, None]).reshape(-1)
+                                for i in range(len(pairs))])
+        order_dev = torch.from_numpy(order).cuda()
+        x = torch.cat(feats, 0)
+        width = max(int(rows.lengths.max()), 1)
+        if shared_encoder:
+            self._ensure_slots(x.shape[0])
+            seq = self.model.score_candidates(x, rows.ids.index_select(0, order_dev)[:, :width].contiguous(), K)
+        else:
+            seg0 = np.concatenate([[0], np.cumsum(counts)])
+            source = np.concatenate([seg0[i] + np.arange(counts[i]) for i in range(len(pairs)) for _ in range(K)])
+            self._ensure_slots(len(source))
+            seq = self.model.score_segments(x.index_select(0, torch.from_numpy(source).to(x.device)),
+                                            rows.ids[:, :width].contiguous()).index_select(0, order_dev)
+        scores = seq.view(-1, K)
+        path, total = alignment.best_paths(scores, counts, grid, smoothness, max_jump)
+        flat, flat_total = alignment.best_paths(scores, counts, grid, 0.0, 0.0)      # max_jump 0: the constant paths
+        path, total, flat, flat_total = path.cpu().numpy(), total.cpu().numpy(), flat.cpu().numpy(), flat_total.cpu().numpy()
+        scores_host = scores.cpu().numpy().astype(np.float64) if return_table else None
+        out, first = [], 0
+        for i, (_, ns) in enumerate(pairs):
+            seg_shifts = grid[path[first: first + counts[i]]]
+            rec = {"notes": alignment.warp_notes(ns, seg_shifts, seconds), "segment_shifts": seg_shifts,
+                   "path_score": -float(total[i]), "flat_shift": float(grid[flat[first]]), "flat_score": -float(flat_total[i])}
+            if return_table:
+                rec["scores"] = scores_host[first: first + counts[i]]
+            out.append(rec)
+            first += counts[i]
+        return out
+
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
                         drums=True, prompts=None, well_formed: bool = False) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of

@@ -552,6 +552,21 @@ class Transformer:
         token_scores [N, length] if asked, top1_ids int32 [N, length] and top1_scores [N, length] if `return_top1`):
         the arg-max of each position's logits (lowest id on ties) and its log-probability.  Leaves the engine encoded
         with the last chunk, as a loop of `encode` calls would."""
+        return self._score_job(x, targets, None, return_token_scores, return_top1)
+
+    def score_candidates(self, x, targets, per: int, return_token_scores: bool = False, return_top1: bool = False):
+        """mt3_engine_score_candidates: `per` target rows against every segment, each segment encoded ONCE (the table of an
+        offset search; include/mt3_hip.h states the contract).  x: CUDA f32 [N, T, input_depth]; targets: int32
+        [N * per, 1 .. L], row s * per + j = candidate j of segment s.  Returns what `score_segments` returns on
+        `x.repeat_interleave(per, 0)` -- one row per target row, the same bits -- and leaves the engine as
+        `score_segments(x, ...)` would.  `status(STATUS_SCORE_ENCODER_PASSES)` reports the encoder passes of the call."""
+        per = int(per)
+        if per < 1:
+            raise ValueError("per must be at least 1, got %r" % (per,))
+        return self._score_job(x, targets, per, return_token_scores, return_top1)
+
+    def _score_job(self, x, targets, per, return_token_scores, return_top1):
+        """the shared body of `score_segments` (per None) and `score_candidates`"""
         import torch
         if self.config.kv_dtype:
             raise ValueError("scoring is not available with kv_dtype=%r (e4m3 cross caches are out of scope)"
@@ -560,20 +575,27 @@ class Transformer:
             raise ValueError(f"expected [N >= 1, {self.input_length}, {self.config.input_depth}], got {tuple(x.shape)}")
         x = x.to(device="cuda", dtype=torch.float32).contiguous()
         N = int(x.shape[0])
+        R = N * (per or 1)                                 # target rows
+        if R >= 1 << 31:
+            raise ValueError("N * per must fit int32")
         tgt = torch.as_tensor(targets)
-        if tgt.dim() != 2 or tgt.shape[0] != N or tgt.shape[1] < 1 or tgt.shape[1] > self.max_decode_length:
-            raise ValueError(f"targets must be [N={N}, 1 .. {self.max_decode_length}], got {tuple(tgt.shape)}")
+        if tgt.dim() != 2 or tgt.shape[0] != R or tgt.shape[1] < 1 or tgt.shape[1] > self.max_decode_length:
+            rows = f"N={N}" if per is None else f"N * per = {R}"
+            raise ValueError(f"targets must be [{rows}, 1 .. {self.max_decode_length}], got {tuple(tgt.shape)}")
         n = int(tgt.shape[1])
         tgt = tgt.to(device="cuda", dtype=torch.int32).contiguous()
         if int(tgt.min()) < 0 or int(tgt.max()) >= self.config.vocab_size:
             raise ValueError("target ids must lie in [0, vocab_size)")
-        seq = torch.empty((N,), device="cuda", dtype=torch.float32)
-        tok = torch.empty((N, n), device="cuda", dtype=torch.float32) if return_token_scores else None
-        top_id = torch.empty((N, n), device="cuda", dtype=torch.int32) if return_top1 else None
-        top_sc = torch.empty((N, n), device="cuda", dtype=torch.float32) if return_top1 else None
+        seq = torch.empty((R,), device="cuda", dtype=torch.float32)
+        tok = torch.empty((R, n), device="cuda", dtype=torch.float32) if return_token_scores else None
+        top_id = torch.empty((R, n), device="cuda", dtype=torch.int32) if return_top1 else None
+        top_sc = torch.empty((R, n), device="cuda", dtype=torch.float32) if return_top1 else None
         ptr = (lambda t: t.data_ptr() if t is not None else None)
-        _lib.check(self._lib.mt3_engine_score_segments(self._h, x.data_ptr(), N, n, tgt.data_ptr(), ptr(seq), ptr(tok),
-                                                       ptr(top_id), ptr(top_sc), torch.cuda.current_stream().cuda_stream))
+        out = (tgt.data_ptr(), ptr(seq), ptr(tok), ptr(top_id), ptr(top_sc), torch.cuda.current_stream().cuda_stream)
+        if per is None:
+            _lib.check(self._lib.mt3_engine_score_segments(self._h, x.data_ptr(), N, n, *out))
+        else:
+            _lib.check(self._lib.mt3_engine_score_candidates(self._h, x.data_ptr(), N, per, n, *out))
         torch.cuda.current_stream().synchronize()          # the converted inputs must outlive the work the call enqueued
         last = N - (N - 1) // self.max_batch * self.max_batch          # segments of the last chunk
         pad8 = self.config.dtype == "bfloat16" and N > self.max_batch  # (bf16: encoded in a pass of at least 8 rows)

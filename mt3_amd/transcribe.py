@@ -4,7 +4,9 @@
                                  [--decoding beam1|greedy|beam|sample] [--num-beams K] [--confidences]
                                  [--temperature T] [--top-k K] [--top-p P] [--seed N]
                                  [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]] [--render [RATE]]
-                                 [--score-against DIR] IN.wav [IN2.wav ...] [-o OUT]
+                                 [--score-against DIR] [--score-midi DIR [--score-shifts S,...]]
+                                 [--align-midi DIR [--align-max-shift S] [--align-step S] [--align-smoothness L]]
+                                 IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
 engine as one job (`InferenceModel.transcribe_wavs`).  --checkpoint is handed to `InferenceModel` as it is: a t5x
@@ -29,6 +31,12 @@ inputs are rendered in one call).  It is the sound of the notes as NAME.mid hold
 device call -- and writes scores.json into the output directory: {"files": {NAME: {key: value}}, "mean": {key: value}}.
 The output directory is the one the MIDI files go to; inputs that would be written to several directories (no -o, inputs
 in different places) are refused with --score-against: give -o DIR.
+--align-midi DIR repairs the timing of known notes: for each input NAME.wav it reads DIR/NAME.mid, finds a time shift per
+segment of the audio (`InferenceModel.align_notes_many`: all inputs as one job; shifts of -S .. S seconds from
+--align-max-shift, default 0.2, in steps of --align-step, default 0.02; --align-smoothness: log-probability per second
+of jump between neighbouring segments) and writes the moved notes as NAME.aligned.mid beside NAME.mid, and one
+alignment.json into the output directory: a list with one record per input, in input order -- "audio", "segment_shifts",
+"path_score", "flat_shift", "flat_score" (same one-directory rule as --score-against).
 """
 from __future__ import annotations
 
@@ -87,6 +95,16 @@ def plan(argv=None):
     ap.add_argument("--score-shifts", type=_shift_list, default=None, metavar="S[,S...]",
                     help="--score-midi: also score the MIDI moved by each of these offsets in seconds, and report the best "
                          "(a list that starts with a minus sign is written --score-shifts=-0.1,0,0.1)")
+    ap.add_argument("--align-midi", default=None, metavar="DIR",
+                    help="also write NAME.aligned.mid beside each NAME.mid and alignment.json into the output directory: "
+                         "the known notes DIR/NAME.mid moved by a time shift per segment so that they explain NAME.wav "
+                         "best (same one-directory rule as --score-against)")
+    ap.add_argument("--align-max-shift", type=float, default=None, metavar="S",
+                    help="--align-midi: shifts of -S .. S seconds are tried (default 0.2)")
+    ap.add_argument("--align-step", type=float, default=None, metavar="S", help="--align-midi: the step of the shifts "
+                    "in seconds (default 0.02)")
+    ap.add_argument("--align-smoothness", type=float, default=None, metavar="L",
+                    help="--align-midi: log-probability a path pays per second of jump between neighbouring segments")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -113,6 +131,23 @@ def plan(argv=None):
         for path in args.inputs:
             if not os.path.isfile(reference_path(args.score_midi, path)):
                 ap.error("--score-midi: no such file: %s" % reference_path(args.score_midi, path))
+    if args.align_midi is None:
+        for name in ("align_max_shift", "align_step", "align_smoothness"):
+            if getattr(args, name) is not None:
+                ap.error("--%s needs --align-midi" % name.replace("_", "-"))
+    else:
+        for path in args.inputs:
+            if not os.path.isfile(reference_path(args.align_midi, path)):
+                ap.error("--align-midi: no such file: %s" % reference_path(args.align_midi, path))
+        max_shift = 0.2 if args.align_max_shift is None else args.align_max_shift
+        step = 0.02 if args.align_step is None else args.align_step
+        if not (math.isfinite(max_shift) and max_shift >= 0 and math.isfinite(step) and step > 0):
+            ap.error("--align-max-shift takes seconds >= 0 and --align-step seconds > 0")
+        if 2 * math.floor(max_shift / step + 1e-9) + 1 > 64:
+            ap.error("--align-max-shift / --align-step: at most 64 shifts fit (a larger step, or a smaller maximum)")
+        if args.align_smoothness is not None and not (math.isfinite(args.align_smoothness) and args.align_smoothness >= 0):
+            ap.error("--align-smoothness takes a finite number >= 0")
+        args.align_max_shift, args.align_step = max_shift, step
     out = args.output
     if out is None:
         outputs = [os.path.splitext(p)[0] + ".mid" for p in args.inputs]
@@ -128,6 +163,8 @@ def plan(argv=None):
         ap.error("--score-against writes one scores.json into the output directory: inputs in several directories need -o DIR")
     if args.score_midi is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
         ap.error("--score-midi writes one midi_scores.json into the output directory: inputs in several directories need -o DIR")
+    if args.align_midi is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
+        ap.error("--align-midi writes one alignment.json into the output directory: inputs in several directories need -o DIR")
     return args, outputs
 
 
@@ -195,6 +232,17 @@ def main(argv=None) -> int:
                     pairs.append((samples, midi_io.midi_bytes_to_note_sequence(f.read())))
                 rates.append(rate)
             midi_scores = model.score_notes_many(pairs, sample_rates=rates, shifts=args.score_shifts)
+        aligned = None
+        if args.align_midi is not None:
+            from . import audio_io
+            pairs, rates = [], []
+            for path in args.inputs:
+                samples, rate = audio_io.read_wav(path)
+                with open(reference_path(args.align_midi, path), "rb") as f:
+                    pairs.append((samples, midi_io.midi_bytes_to_note_sequence(f.read())))
+                rates.append(rate)
+            aligned = model.align_notes_many(pairs, sample_rates=rates, max_shift=args.align_max_shift,
+                                             step=args.align_step, smoothness=args.align_smoothness)
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -220,7 +268,28 @@ def main(argv=None) -> int:
     if midi_scores is not None:
         with open(midi_scores_path(outputs), "w") as f:
             json.dump([midi_score_record(path, sc) for path, sc in zip(args.inputs, midi_scores)], f, indent=1)
+    if aligned is not None:
+        for rec, path in zip(aligned, outputs):
+            midi_io.note_sequence_to_midi_file(rec["notes"], aligned_path(path))
+        with open(alignment_path(outputs), "w") as f:
+            json.dump([alignment_record(path, rec) for path, rec in zip(args.inputs, aligned)], f, indent=1)
     return 0
+
+
+def aligned_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".aligned.mid"
+
+
+def alignment_path(outputs) -> str:
+    """alignment.json of a job: beside scores.json"""
+    return os.path.join(os.path.dirname(os.path.abspath(outputs[0])), "alignment.json")
+
+
+def alignment_record(audio_path: str, rec) -> dict:
+    """one JSON-ready record of `InferenceModel.align_notes`: the path and its scores (the notes go to NAME.aligned.mid)"""
+    return {"audio": audio_path, "segment_shifts": [float(v) for v in rec["segment_shifts"]],
+            "path_score": float(rec["path_score"]), "flat_shift": float(rec["flat_shift"]),
+            "flat_score": float(rec["flat_score"])}
 
 
 def midi_scores_path(outputs) -> str:
