@@ -119,6 +119,59 @@ __device__ __forceinline__ void unpack_chunk<float>(const u32x4& c, float* out) 
   for (int i = 0; i < 4; ++i) out[i] = v[i];
 }
 
+__device__ __forceinline__ int wave_scan_max(int x, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o);
+    if (lane >= o) x = max(x, y);
+  }
+  return x;
+}
+
+__device__ __forceinline__ int wave_scan_add(int x, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
+// Exclusive scans over a workgroup of kWaves waves: *before = the lanes before this one, *total = all of them.  `s` is
+// kWaves words of LDS that nobody else touches between the barrier before the call and the next barrier after it.
+template <int kWaves>
+__device__ __forceinline__ void block_scan_max(int x, int* s, int* before, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int inc = wave_scan_max(x, lane);
+  int b = __shfl_up(inc, 1);
+  if (lane == 0) b = 0;
+  if (lane == 63) s[wave] = inc;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    if (w < wave) b = max(b, s[w]);
+    t = max(t, s[w]);
+  }
+  *before = b, *total = t;
+}
+
+template <int kWaves>
+__device__ __forceinline__ void block_scan_add(int x, int* s, int* before, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int inc = wave_scan_add(x, lane);
+  int b = inc - x;
+  if (lane == 63) s[wave] = inc;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    if (w < wave) b += s[w];
+    t += s[w];
+  }
+  *before = b, *total = t;
+}
+
 // bijective XCD-aware block remap (8 XCDs; block b is dispatched to XCD b % 8): gives every
 // XCD a contiguous run of logical ids so that neighbouring tiles share that XCD's L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -30,6 +30,7 @@
 #include <string>
 
 #include "common.h"
+#include "device.h"
 #include "mt3_hip.h"
 
 #pragma clang fp contract(off)          // int(x * fps) is ONE rounded product, as Python evaluates it
@@ -90,22 +91,13 @@ __global__ __launch_bounds__(kThreads) void edges_kernel(RollTable t, const doub
   if (f1 < F) (void)__hip_atomic_fetch_add(row + f1, -v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ int wave_scan_add(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
 // grid (128 pitch rows, rolls): the row's int32 edges -> the float32 of their running sums, in place
 __global__ __launch_bounds__(kThreads) void scan_kernel(RollTable t, int32_t* out) {
   __shared__ int s_sum[2][kWaves];
   const int r = blockIdx.y;
   const int32_t F = t.width[r];
   if (F == 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int32_t* row = out + t.cell0[r] + static_cast<int64_t>(blockIdx.x) * F;
   const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
   int carry = 0, set = 0;                            // uniform over the workgroup
@@ -121,16 +113,9 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(RollTable t, int32_t* ou
       for (int j = 0; j < kPerLane; ++j) x[j] = at + j < F ? row[at + j] : 0;
     }
     x[1] += x[0], x[2] += x[1], x[3] += x[2];
-    const int inc = wave_scan_add(x[3], lane);
-    if (lane == 63) s_sum[set][wave] = inc;
-    __syncthreads();
-    int before = carry + inc - x[3], total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int s = s_sum[set][w];
-      if (w < wave) before += s;
-      total += s;
-    }
+    int before, total;                               // the set of the tile before may still be read: this one is the other
+    mt3k::block_scan_add<kWaves>(x[3], s_sum[set], &before, &total);
+    before += carry;
     carry += total;
     if (whole) {
       int4 v;

@@ -30,6 +30,7 @@
 #include <string>
 
 #include "common.h"
+#include "device.h"
 #include "mt3_hip.h"
 
 namespace {
@@ -44,24 +45,6 @@ constexpr int kMaxWords = MT3_NOTE_MAX_PROGRAMS * MT3_NOTE_ROW_WORDS;
 __device__ __forceinline__ int wave_min(int x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o));
-  return x;
-}
-
-__device__ __forceinline__ int wave_scan_max(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x = max(x, y);
-  }
-  return x;
-}
-
-__device__ __forceinline__ int wave_scan_add(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
   return x;
 }
 
@@ -110,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void tie_prompts_kernel(mt3_note_grammar 
     }
     // ---- the wave's part, then the four waves through LDS
     const int w_end = wave_min(end), w_tie = wave_min(tie);
-    const int inc_p = wave_scan_max(run_p, lane), inc_v = wave_scan_max(run_v, lane);
+    const int inc_p = mt3k::wave_scan_max(run_p, lane), inc_v = mt3k::wave_scan_max(run_v, lane);
     int before_p = __shfl_up(inc_p, 1), before_v = __shfl_up(inc_v, 1);          // the lanes before this one
     if (lane == 0) before_p = 0, before_v = 0;
     if (lane == 63) s_prog[wave] = inc_p, s_vel[wave] = inc_v;
@@ -166,16 +149,9 @@ __global__ __launch_bounds__(kThreads) void tie_prompts_kernel(mt3_note_grammar 
   if (tid < R)
     for (int w = 0; w < RW; ++w) mine += __popc(s_held[tid * RW + w]);
   const int packed = (mine << 8) | (mine ? 1 : 0);
-  const int inc = wave_scan_add(packed, lane);
-  if (lane == 63) s_sum[wave] = inc;
   if (tid == 0) s_tie_at = 0;                                  // nothing kept: the bare tie_id
-  __syncthreads();
-  int excl = inc - packed, total = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) excl += s_sum[w];
-    total += s_sum[w];
-  }
+  int excl, total;
+  mt3k::block_scan_add<kWaves>(packed, s_sum, &excl, &total);  // (its barrier publishes s_tie_at too)
   const int pairs = total >> 8, kept = min(pairs, cap);
   const bool drop = (flags & MT3_TIE_DROP_REDUNDANT_PROGRAMS) != 0;
   int32_t* out = prompts + static_cast<size_t>(blockIdx.x) * (2 * static_cast<size_t>(cap) + 1);

@@ -29,6 +29,7 @@
 #include <string>
 
 #include "common.h"
+#include "device.h"
 #include "mt3_hip.h"
 
 namespace {
@@ -39,57 +40,6 @@ constexpr int kPairs = MT3_TOKENIZE_PROGRAMS * MT3_TOKENIZE_PITCHES;
 constexpr int kRowWords = MT3_TOKENIZE_PITCHES / 32;
 constexpr int kWords = kPairs / 32;
 static_assert(MT3_TOKENIZE_PROGRAMS <= kThreads, "a lane per program row");
-
-__device__ __forceinline__ int wave_scan_max(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x = max(x, y);
-  }
-  return x;
-}
-
-__device__ __forceinline__ int wave_scan_add(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// Exclusive scans over the workgroup: *before = the lanes before this one, *total = all of them.  `s` is kWaves words of
-// LDS that nobody else touches between the barrier before the call and the next barrier after it.
-__device__ __forceinline__ void block_scan_max(int x, int* s, int* before, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int inc = wave_scan_max(x, lane);
-  int b = __shfl_up(inc, 1);
-  if (lane == 0) b = 0;
-  if (lane == 63) s[wave] = inc;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) b = max(b, s[w]);
-    t = max(t, s[w]);
-  }
-  *before = b, *total = t;
-}
-
-__device__ __forceinline__ void block_scan_add(int x, int* s, int* before, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int inc = wave_scan_add(x, lane);
-  int b = inc - x;
-  if (lane == 63) s[wave] = inc;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) b += s[w];
-    t += s[w];
-  }
-  *before = b, *total = t;
-}
 
 __global__ __launch_bounds__(kThreads) void tokenize_kernel(
     mt3_tokenize_rule r, const int32_t* __restrict__ d_step, const int32_t* __restrict__ d_pitch,
@@ -166,9 +116,9 @@ __global__ __launch_bounds__(kThreads) void tokenize_kernel(
         mapped = r.program_map[tid];
       }
       int seen, seen_all, off, total;
-      block_scan_max(mine && mapped >= 0 ? ((tid + 1) << 8) | mapped : 0, s_max, &seen, &seen_all);
+      mt3k::block_scan_max<kWaves>(mine && mapped >= 0 ? ((tid + 1) << 8) | mapped : 0, s_max, &seen, &seen_all);
       const int opens = mine && mapped >= 0 && (seen ? (seen & 0xff) : -1) != mapped;
-      block_scan_add(mine + opens, s_add, &off, &total);
+      mt3k::block_scan_add<kWaves>(mine + opens, s_add, &off, &total);
       if (mine) {
         int64_t at = off;
         if (opens) mt3t_put(stride, &at, r.program_first + mapped, -1, 0, ids, note_of, is_onset);
@@ -207,9 +157,9 @@ __global__ __launch_bounds__(kThreads) void tokenize_kernel(
         has_velocity = e == e_lo || v != mt3t_velbin(&r, velbin[e - 1]);
       }
       int seen, seen_all, off, total;
-      block_scan_max(mapped >= 0 ? ((tid + 1) << 8) | mapped : 0, s_max, &seen, &seen_all);
+      mt3k::block_scan_max<kWaves>(mapped >= 0 ? ((tid + 1) << 8) | mapped : 0, s_max, &seen, &seen_all);
       const int has_program = mapped >= 0 && (seen ? (seen & 0xff) : last_program) != mapped;
-      block_scan_add(active ? n_shift + has_program + has_velocity + 1 : 0, s_add, &off, &total);
+      mt3k::block_scan_add<kWaves>(active ? n_shift + has_program + has_velocity + 1 : 0, s_add, &off, &total);
       if (active) {
         int64_t at = base + off;
         for (int k = 0; k < n_shift && at < stride; ++k)

@@ -27,6 +27,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from . import note_arrays
 from .note_sequences import NoteSequence
 
 N_DECIMALS = 6          # mir_eval.transcription: precision the onset / offset distances are rounded to
@@ -35,9 +36,9 @@ N_DECIMALS = 6          # mir_eval.transcription: precision the onset / offset d
 def sequence_to_valued_intervals(ns: NoteSequence, drums: Optional[bool] = None):
     """note_seq.sequences_lib.sequence_to_valued_intervals as mt3/metrics.py uses it: (intervals [n, 2], note numbers,
     velocities), zero-length notes dropped (mir_eval rejects them).  `drums`: None = every note, else filter."""
-    notes = [n for n in ns.notes if n.end_time != n.start_time and (drums is None or bool(n.is_drum) == drums)]
-    iv = np.array([[n.start_time, n.end_time] for n in notes], np.float64).reshape(-1, 2)
-    return iv, np.array([n.pitch for n in notes], np.float64), np.array([n.velocity for n in notes], np.int64)
+    start, end, pitch, velocity, is_drum = note_arrays.fields(ns)
+    keep = (end != start) & (True if drums is None else (is_drum != 0) == drums)
+    return np.stack([start[keep], end[keep]], axis=1), pitch[keep].astype(np.float64), velocity[keep]
 
 
 def _hit_pairs(ref_iv, ref_pitch, est_iv, est_pitch, onset_tolerance, pitch_tolerance, offset_ratio,

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib
 from . import event_codec
+from . import note_arrays
 from . import note_sequences
 
 
@@ -63,8 +64,7 @@ def decode_token_rows(codec, encoding_spec, rows, start_times, lengths=None):
         eos = rows == -1
         lengths = np.where(eos.any(1), eos.argmax(1), rows.shape[1])
     lengths = np.asarray(lengths, np.int64)
-    offs = np.zeros(len(rows) + 1, np.int64)
-    np.cumsum(lengths, out=offs[1:])
+    offs = note_arrays.offsets(lengths)
     flat = rows[np.arange(rows.shape[1])[None, :] < lengths[:, None]]
     return _decode(codec, encoding_spec.spec_id, flat, offs, start_times)
 
@@ -86,9 +86,7 @@ def _run_full(codec, spec_id, tokens_list, start_times, max_times, trace):
     onset and end token ((-1, -1): none); None otherwise"""
     n = len(tokens_list)
     toks = [np.asarray(t, np.int32).reshape(-1) for t in tokens_list]
-    offs = np.zeros(n + 1, np.int64)
-    if n:
-        np.cumsum([t.size for t in toks], out=offs[1:])
+    offs = note_arrays.offsets([t.size for t in toks])
     flat = np.concatenate(toks) if n and offs[-1] else np.zeros(1, np.int32)
     rec, inv, drop, total, flat_idx = _decode_full(codec, spec_id, flat, offs, start_times, max_times, trace)
     if flat_idx is None:

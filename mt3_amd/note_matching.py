@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, note_arrays
 
 RULE_DTYPE = np.dtype([("onset_tolerance", "<f8"), ("pitch_tolerance", "<f8"), ("offset_ratio", "<f8"),
                        ("offset_min_tolerance", "<f8"), ("strict", "<i4"), ("reserved", "<i4")])       # mt3_match_rule
@@ -151,16 +151,14 @@ def match(problems: Sequence[Problem], warm_start: Optional[Sequence] = None, pa
     packed = pack(problems) if packed is None else packed
     n = len(packed.problems)
     if warm_start is not None:
-        workspace = torch.from_numpy(warm_words(packed, warm_start)).cuda()
+        workspace = note_arrays.to_device(warm_words(packed, warm_start))
     else:
         workspace = torch.empty(packed.workspace_words, device="cuda", dtype=torch.int32)
     if n == 0:
         return Matching(np.zeros(0, np.int64), workspace, packed)
     n_notes = packed.notes.shape[1]
-    notes = torch.from_numpy(packed.notes).cuda()        # the one upload
+    notes, ptr = note_arrays.upload(packed.notes, n_notes, ("<f8",) * 3)        # the one upload
     counts = torch.empty(n, device="cuda", dtype=torch.int32)
-    base = notes.data_ptr()
-    ptr = [base, base + 8 * n_notes, base + 16 * n_notes] if n_notes else [None] * 3
     _lib.check(_lib.load().mt3_op_match_notes(*ptr, n_notes, n, packed.problems.ctypes.data, len(packed.rules),
                                               packed.rules.ctypes.data, workspace.data_ptr() if workspace.numel() else None,
                                               packed.workspace_words, 1 if warm_start is not None else 0,

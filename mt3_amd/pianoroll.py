@@ -7,28 +7,17 @@ counts of a job from one count call and one copy of 24 bytes per pair back to th
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, note_arrays
 
 PITCHES = _lib.PIANOROLL_PITCHES
 MIN_NOTE_SECONDS = _lib.PIANOROLL_MIN_NOTE_SECONDS
 DEFAULT_FPS = 62.5                      # mt3/metrics.py: frame_fps
 DEFAULT_VELOCITY_THRESHOLD = 30         # mt3/metrics.py: frame_velocity_threshold
-
-
-def _fields(seq):
-    """(start, end, pitch, velocity, is_drum) arrays of one NoteSequence, or of a record array with those field names
-    (metrics_utils.NOTE_DTYPE: what metrics_utils.decode_token_rows returns)"""
-    if isinstance(seq, np.ndarray):
-        return (seq["start_time"].astype(np.float64), seq["end_time"].astype(np.float64), seq["pitch"].astype(np.int64),
-                seq["velocity"].astype(np.int64), seq["is_drum"].astype(np.int64))
-    notes = seq.notes
-    return (np.array([n.start_time for n in notes], np.float64), np.array([n.end_time for n in notes], np.float64),
-            np.array([n.pitch for n in notes], np.int64), np.array([n.velocity for n in notes], np.int64),
-            np.array([bool(n.is_drum) for n in notes], np.int64))
+LAYOUT = ("<f8", "<f8", "<i4", "<i4", "<i4")      # the types of the columns that _pack lays out
 
 
 def roll_width(start: np.ndarray, end: np.ndarray, drum: np.ndarray, fps: float, is_drum: bool) -> int:
@@ -46,29 +35,19 @@ def _pack(sequences, fps: float, is_drum: bool):
     fps = float(fps)
     if not np.isfinite(fps) or fps <= 0:
         raise ValueError("fps must be finite and positive, got %r" % (fps,))
-    parts = [_fields(s) for s in sequences]
-    offs = np.zeros(len(parts) + 1, np.int64)
-    if parts:
-        np.cumsum([len(p[0]) for p in parts], out=offs[1:])
+    parts = [note_arrays.fields(s) for s in sequences]
+    offs = note_arrays.offsets([len(p[0]) for p in parts])
     widths = np.zeros(len(parts), np.int32)
     for i, (start, end, pitch, velocity, drum) in enumerate(parts):
-        if len(start) == 0:
-            continue
-        if (pitch < 0).any() or (pitch >= PITCHES).any():
-            raise ValueError("sequence %d: a piano roll has pitches 0 .. 127, got %d" % (i, pitch[(pitch < 0) | (pitch >= PITCHES)][0]))
-        if not (np.isfinite(start).all() and np.isfinite(end).all()) or (start < 0).any() or (end < 0).any():
-            raise ValueError("sequence %d: note times must be finite and not negative" % i)
+        note_arrays.check_range("sequence %d: a piano roll has pitches 0 .. 127" % i, pitch)
+        note_arrays.check_times(start, end, not_negative=True, prefix="sequence %d: " % i)
         if (np.abs(velocity) >= 2 ** 31).any():
             raise ValueError("sequence %d: velocities must fit int32" % i)
         w = roll_width(start, end, drum, fps, is_drum)
         if w >= 2 ** 31:
             raise ValueError("sequence %d: %d frames do not fit a roll" % (i, w))
         widths[i] = w
-    n = int(offs[-1])
-    cat = (lambda k, dt: np.concatenate([p[k] for p in parts]).astype(dt) if n else np.zeros(0, dt))
-    packed = np.concatenate([cat(0, "<f8").view(np.uint8), cat(1, "<f8").view(np.uint8), cat(2, "<i4").view(np.uint8),
-                             cat(3, "<i4").view(np.uint8), cat(4, "<i4").view(np.uint8)])
-    return packed, n, offs, widths
+    return note_arrays.pack([[p[k] for p in parts] for k in range(5)], LAYOUT), int(offs[-1]), offs, widths
 
 
 def _rasterise(sequences, fps: float, is_drum: bool):
@@ -76,20 +55,16 @@ def _rasterise(sequences, fps: float, is_drum: bool):
     buffer[128 * col[i] : 128 * (col[i] + width[i])] as [128, width[i]]"""
     import torch
     packed, n, offs, widths = _pack(sequences, fps, is_drum)
-    cols = np.zeros(len(widths), np.int64)
-    if len(widths):
-        np.cumsum(widths[:-1], out=cols[1:])
-    total = PITCHES * int(widths.sum(dtype=np.int64))
+    cols = note_arrays.offsets(widths)
+    total = PITCHES * int(cols[-1])
     out = torch.empty(total, device="cuda", dtype=torch.float32)
     if total == 0:
-        return out, cols, widths
-    notes = torch.from_numpy(packed).cuda()            # the one upload
-    base = notes.data_ptr()
-    ptr = [base, base + 8 * n, base + 16 * n, base + 20 * n, base + 24 * n] if n else [None] * 5
+        return out, cols[:-1], widths
+    notes, ptr = note_arrays.upload(packed, n, LAYOUT)             # the one upload
     _lib.check(_lib.load().mt3_op_pianoroll(*ptr, n, len(widths), offs.ctypes.data, cols.ctypes.data, widths.ctypes.data,
                                             float(fps), 1 if is_drum else 0, out.data_ptr(), total,
                                             torch.cuda.current_stream().cuda_stream))
-    return out, cols, widths
+    return out, cols[:-1], widths
 
 
 def _views(out, cols, widths) -> list:

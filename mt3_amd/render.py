@@ -15,14 +15,14 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
-from .pianoroll import _fields
+from . import _lib, note_arrays
 
 TILE = _lib.RENDER_TILE                           # samples per workgroup of the render kernel
 MAX_SAMPLE_RATE = _lib.RENDER_MAX_SAMPLE_RATE
 RELEASE_SECONDS = _lib.RENDER_RELEASE_SECONDS
 DRUM_SECONDS = _lib.RENDER_DRUM_SECONDS
 DEFAULT_SAMPLE_RATE = 16000
+LAYOUT = ("<f8", "<f8", "<f8", "<i4", "<i4", "<i4")   # the types of the columns that _pack lays out
 
 
 def _rate(sample_rate) -> int:
@@ -48,23 +48,18 @@ def _pack(sequences, sample_rate: int, lengths):
     """the job's notes, each sequence's sorted by (start, end, pitch, velocity, is_drum), as one byte buffer (start f64 |
     end f64 | reach f64 | pitch i32 | velocity i32 | is_drum i32, each [n]; reach = the running maximum of the sounding
     instants within the sequence) and the host tables: note offsets int64 [n_seq + 1], lengths int64 [n_seq]"""
-    parts = [_fields(s) for s in sequences]
+    parts = [note_arrays.fields(s) for s in sequences]
     if lengths is not None:
         lengths = [int(v) for v in lengths]
         if len(lengths) != len(parts):
             raise ValueError("%d lengths for %d sequences" % (len(lengths), len(parts)))
-    offs = np.zeros(len(parts) + 1, np.int64)
-    if parts:
-        np.cumsum([len(p[0]) for p in parts], out=offs[1:])
+    offs = note_arrays.offsets([len(p[0]) for p in parts])
     n_samples = np.zeros(len(parts), np.int64)
     cols = [[] for _ in range(6)]
     for i, (start, end, pitch, velocity, drum) in enumerate(parts):
-        if (pitch < 0).any() or (pitch > 127).any():
-            raise ValueError("sequence %d: pitches are 0 .. 127, got %d" % (i, pitch[(pitch < 0) | (pitch > 127)][0]))
-        if (velocity < 0).any() or (velocity > 127).any():
-            raise ValueError("sequence %d: velocities are 0 .. 127, got %d" % (i, velocity[(velocity < 0) | (velocity > 127)][0]))
-        if not (np.isfinite(start).all() and np.isfinite(end).all()) or (start < 0).any() or (end < 0).any():
-            raise ValueError("sequence %d: note times must be finite and not negative" % i)
+        note_arrays.check_range("sequence %d: pitches are 0 .. 127" % i, pitch)
+        note_arrays.check_range("sequence %d: velocities are 0 .. 127" % i, velocity)
+        note_arrays.check_times(start, end, not_negative=True, prefix="sequence %d: " % i)
         if (end < start).any():
             raise ValueError("sequence %d: a note ends before it starts" % i)
         n = render_length(start, end, drum, sample_rate) if lengths is None else lengths[i]
@@ -77,9 +72,7 @@ def _pack(sequences, sample_rate: int, lengths):
         reach = np.maximum.accumulate(sounding_instants(start, end, drum)) if len(start) else start
         for c, a in zip(cols, (start, end, reach, pitch, velocity, drum)):
             c.append(a)
-    cat = (lambda k, dt: np.concatenate(cols[k]).astype(dt).view(np.uint8) if offs[-1] else np.zeros(0, np.uint8))
-    packed = np.concatenate([cat(0, "<f8"), cat(1, "<f8"), cat(2, "<f8"), cat(3, "<i4"), cat(4, "<i4"), cat(5, "<i4")])
-    return packed, int(offs[-1]), offs, n_samples
+    return note_arrays.pack(cols, LAYOUT), int(offs[-1]), offs, n_samples
 
 
 def render(sequences: Sequence, sample_rate: int = DEFAULT_SAMPLE_RATE, lengths: Optional[Sequence[int]] = None,
@@ -97,15 +90,12 @@ def render(sequences: Sequence, sample_rate: int = DEFAULT_SAMPLE_RATE, lengths:
     if not sequences:
         return []
     packed, n, offs, n_samples = _pack(sequences, sample_rate, lengths)
-    first = np.zeros(len(n_samples), np.int64)
-    np.cumsum(n_samples[:-1], out=first[1:])
-    total = int(n_samples.sum())
+    first = note_arrays.offsets(n_samples)
+    total = int(first[-1])
     out = torch.empty(total, device="cuda", dtype=torch.float32)
     if total:
         peaks = torch.empty(len(n_samples), device="cuda", dtype=torch.float32)
-        notes = torch.from_numpy(packed).cuda()            # the one upload
-        base = notes.data_ptr()
-        ptr = [base, base + 8 * n, base + 16 * n, base + 24 * n, base + 28 * n, base + 32 * n] if n else [None] * 6
+        notes, ptr = note_arrays.upload(packed, n, LAYOUT)         # the one upload
         _lib.check(_lib.load().mt3_op_render_notes(*ptr, n, len(n_samples), offs.ctypes.data, first.ctypes.data,
                                                    n_samples.ctypes.data, sample_rate, 1 if normalize else 0,
                                                    out.data_ptr(), total, peaks.data_ptr(),

@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import note_arrays
 from . import note_sequences
 from . import run_length_encoding
 from . import vocabularies
@@ -88,19 +89,12 @@ def pack(sequences: Sequence[note_sequences.NoteSequence], codec, spec, shifts: 
     sps = float(codec.steps_per_second)
     chunks, event0 = [], [0]
     for ns in sequences:
-        notes = ns.notes
-        n = len(notes)
-        start = np.fromiter((x.start_time for x in notes), np.float64, n)
-        end = np.fromiter((x.end_time for x in notes), np.float64, n)
-        pitch = np.fromiter((x.pitch for x in notes), np.int64, n)
-        velocity = np.fromiter((x.velocity for x in notes), np.int64, n)
-        program = np.fromiter((x.program for x in notes), np.int64, n) if ties else np.zeros(n, np.int64)
-        drum = np.fromiter((bool(x.is_drum) for x in notes), np.bool_, n) if ties else np.zeros(n, np.bool_)
-        if n and not (np.isfinite(start).all() and np.isfinite(end).all()):
-            raise ValueError("note times must be finite")
-        if n and (pitch.min() < 0 or pitch.max() > 127 or program.min() < 0 or program.max() > 127 or
-                  velocity.min() < 0 or velocity.max() > vocabularies.MAX_MIDI_VELOCITY):
-            raise ValueError("pitches, programs and velocities must be in 0 .. 127")
+        start, end, pitch, velocity, drum, program = note_arrays.fields(ns, program=True)
+        drum = drum != 0
+        if not ties:                                                    # the notes spec: program 0, drums not told apart
+            program, drum = np.zeros_like(program), np.zeros_like(drum)
+        note_arrays.check_times(start, end)
+        note_arrays.check_range("pitches, programs and velocities must be in 0 .. 127", pitch, program, velocity, got=False)
         order = np.lexsort((pitch, program, drum))                      # stable, like sorted(): last key first
         off = order[~drum[order]]
         who = np.concatenate([off, order])
@@ -185,16 +179,13 @@ def run(job: Job) -> TargetRows:
     is_onset = torch.empty((n_rows, stride), device="cuda", dtype=torch.uint8)
     lengths, truncated = torch.empty(n_rows, **dev), torch.empty(n_rows, **dev)
     if n_rows:
-        events = torch.from_numpy(job.packed.events).cuda()
-        files = torch.from_numpy(job.files.view(np.uint8)).cuda()
-        rows = torch.from_numpy(job.rows.view(np.uint8)).cuda()
-        ptr = [events.data_ptr() + 4 * n_ev * i for i in range(6)] if n_ev else [None] * 6
+        events, ptr = note_arrays.upload(job.packed.events, n_ev, ("<i4",) * 6)
+        files = note_arrays.to_device(job.files.view(np.uint8))
+        rows = note_arrays.to_device(job.rows.view(np.uint8))
         _lib.check(_lib.load().mt3_op_tokenize_notes(
             C.byref(job.rule), *ptr, n_ev, files.data_ptr(), len(job.files), rows.data_ptr(), n_rows, stride,
             ids.data_ptr(), lengths.data_ptr(), truncated.data_ptr(), note_of.data_ptr(), is_onset.data_ptr(),
             torch.cuda.current_stream().cuda_stream))
-        for t in (events, files, rows):
-            t.record_stream(torch.cuda.current_stream())
     return TargetRows(ids, lengths, truncated, note_of, is_onset, job.rows_of_file)
 
 
