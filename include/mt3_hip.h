@@ -1913,6 +1913,70 @@ int mt3_op_align_paths(const float* d_scores /* [total_segments][K] */, int32_t 
                        double smoothness, double max_jump, uint8_t* d_backptr /* [total_segments * K] */,
                        int32_t* d_path /* [total_segments] */, double* d_total /* [n_files] */, void* stream);
 
+/* ---- note consensus: n transcriptions of a file -> one transcription, and for every note the voters that have it.
+ * VOTERS  a file has V voters, 1 <= V <= MT3_CONSENSUS_MAX_VOTERS; a voter is one transcription, numbered 0 .. V - 1, and
+ *   may have no notes.
+ * KEY     key = is_drum << 14 | program << 7 | pitch (int32; the host packs it, and zeroes the program field when
+ *   instruments are not to split a vote).  The kernel compares keys and copies them; it never takes one apart.
+ * ORDER   the notes of a file, from all its voters together, lie SORTED by (key, onset, offset, velocity, voter): a total
+ *   order up to exact duplicates, so the result does not depend on the order the caller held the notes in.  The host
+ *   sorts (numpy's lexsort); the op takes sorted columns.
+ * CLUSTERS  single linkage on onsets within a key.  Note i of the sorted file starts a cluster when it is the file's
+ *   first note, or key[i] != key[i-1], or onset[i] - onset[i-1] > tolerance: ONE float64 difference, rounded once, and
+ *   one comparison.  A cluster is therefore a contiguous run [a, b) of m = b - a members.  Rounding is monotone, so these
+ *   runs are the connected components of "same key and |onset difference| <= tolerance" over ALL pairs.  Limit: repeated
+ *   notes of one key closer than the tolerance chain into one cluster; `members` > `votes` shows such a chain.
+ * PER CLUSTER  votes = the number of distinct voters among the members (the population count of a 64-bit mask; a voter
+ *   number is taken modulo 64), members = m; the cluster is KEPT when votes >= the file's min_votes (1 .. V).
+ * THE EMITTED NOTE of a kept cluster is made of member values alone -- no arithmetic, so nothing rounds:
+ *   key       the cluster's;
+ *   onset     of the member at position a + (m - 1) / 2: the run is sorted by onset, so this is the lower median;
+ *   offset    the member offset of rank (m - 1) / 2 under the order (offset, position);
+ *   velocity  the member velocity of rank (m - 1) / 2 under the order (velocity, position).
+ *   Every member has offset >= onset, so the k-th smallest offset is >= the k-th smallest onset: an emitted note never
+ *   ends before it starts.
+ * OUTPUTS (device)  the kept notes of each file compacted in the sorted order, (key, onset), from the position where the
+ *   file's input starts (so each output column has n_notes entries; those past a file's count are not written), with
+ *   their votes and members; d_counts [n_files]: the kept notes of each file (0 for a file without notes);
+ *   d_note_votes [n_notes]: for every input note of a file, in the sorted order, the votes of its cluster, kept or not.
+ * WORK  one workgroup of MT3_CONSENSUS_TILE lanes per file, 64 files per launch (their table rides in the kernel
+ *   arguments), the launches one after the other on `stream`.  The workgroup walks its file in tiles of
+ *   MT3_CONSENSUS_TILE notes, the scan state carried from tile to tile, so a file's length is not bounded by LDS:
+ *     1. head flags, and their running sum: each note's cluster number and each cluster's start;
+ *     2. per cluster head: the voter mask over its members, votes, kept; a running sum of the kept flags places it;
+ *     3. per note: the ranks of its offset and velocity among its cluster's members; the member of the wanted rank (for
+ *        the onset: position) writes that field of the emitted note.  Every output word has exactly one writer.
+ *   The loops over members are O(m) per note, and m is about V in real input; a degenerate file whose notes all fall
+ *   into one cluster costs O(n^2): slow, but finite.  No atomics, no floating-point arithmetic but the one difference:
+ *   the same input gives the same bits on every run, and they are numpy's (mt3_amd/consensus.py, consensus_reference).
+ * d_scratch: int32 words, at least MT3_CONSENSUS_SCRATCH_WORDS(n_notes) = 4 * n_notes (cluster number of every note;
+ *   start, votes and output place of every cluster).
+ * SAFETY  every index is derived from the file table, which is checked below before any device work.  Columns that are
+ *   not sorted as required (or hold NaN) give unspecified notes, but cluster runs are built from positions alone, so no
+ *   read or write leaves the file's own ranges.
+ * MT3_ERR_INVALID, before any device work: NULL note columns with n_notes > 0, NULL outputs, NULL scratch, a NULL file
+ *   table with n_files > 0; n_notes or n_files negative; a file's note range outside [0, n_notes], overlapping the one
+ *   before it or out of order; n_voters outside 1 .. 64; min_votes outside 1 .. n_voters; a tolerance that is negative
+ *   or not finite; scratch_words below the formula.  n_files == 0 is MT3_OK and launches nothing. */
+#define MT3_CONSENSUS_MAX_VOTERS 64
+#define MT3_CONSENSUS_TILE 256
+#define MT3_CONSENSUS_SCRATCH_WORDS(n_notes) (4 * (int64_t)(n_notes))
+
+typedef struct mt3_consensus_file {
+  int64_t first;                      /* the file's first note in the columns; its output starts there too */
+  int32_t n_notes;
+  int32_t n_voters;                   /* 1 .. MT3_CONSENSUS_MAX_VOTERS */
+  int32_t min_votes;                  /* 1 .. n_voters */
+  int32_t reserved;
+} mt3_consensus_file;
+
+int mt3_op_note_consensus(const double* d_onset, const double* d_offset, const int32_t* d_key, const int32_t* d_velocity,
+                          const int32_t* d_voter, int64_t n_notes, const mt3_consensus_file* h_files /* [n_files] */,
+                          int32_t n_files, double tolerance, double* d_out_onset, double* d_out_offset,
+                          int32_t* d_out_key, int32_t* d_out_velocity, int32_t* d_out_votes, int32_t* d_out_members,
+                          int32_t* d_note_votes /* [n_notes] */, int32_t* d_counts /* [n_files] */, int32_t* d_scratch,
+                          int64_t scratch_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

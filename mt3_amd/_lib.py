@@ -43,6 +43,7 @@ GRANULARITY_FULL, GRANULARITY_MIDI_CLASS, GRANULARITY_FLAT = range(3)      # mt3
 GRANULARITIES = {"full": GRANULARITY_FULL, "midi_class": GRANULARITY_MIDI_CLASS, "flat": GRANULARITY_FLAT}
 TOKENIZE_MAX_STRIDE = 1 << 20                  # mt3_op_tokenize_notes
 ALIGN_MAX_SHIFTS = 64                          # mt3_op_align_paths
+CONSENSUS_MAX_VOTERS, CONSENSUS_TILE, CONSENSUS_SCRATCH_WORDS_PER_NOTE = 64, 256, 4      # mt3_op_note_consensus
 
 
 class Mt3Error(RuntimeError):
@@ -118,6 +119,10 @@ class TokenizeFile(C.Structure):               # mt3_tokenize_file
 
 class TokenizeRow(C.Structure):                # mt3_tokenize_row
     _fields_ = [(n, C.c_int32) for n in ("file", "step_lo", "step_hi", "reserved")]
+
+
+class ConsensusFile(C.Structure):              # mt3_consensus_file
+    _fields_ = [("first", C.c_int64)] + [(n, C.c_int32) for n in ("n_notes", "n_voters", "min_votes", "reserved")]
 
 
 _P = C.c_void_p
@@ -324,6 +329,8 @@ SIGNATURES = {
     "mt3_op_tokenize_notes": (C.c_int, [C.POINTER(TokenizeRule), _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, _P,
                                         C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mt3_op_align_paths": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "mt3_op_note_consensus": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P,
+                                        _P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

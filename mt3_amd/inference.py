@@ -490,6 +490,20 @@ class InferenceModel(object):
             self.decoding, self.sampling = was
         return out
 
+    def consensus(self, audio, num_samples: int = 8, sample_rate: int = SAMPLE_RATE, *, tolerance: float = 0.05,
+                  min_votes: Optional[int] = None, return_votes: bool = False, **kw):
+        """The notes that `min_votes` of `num_samples` sampled transcriptions agree on (self-consistency):
+        `sample(audio, num_samples, sample_rate, **kw)`, then `consensus.consensus` of those voters on the device -- notes
+        of one pitch, program and drum flag whose onsets lie within `tolerance` seconds form a cluster; a cluster that
+        min_votes voters (default: a strict majority, num_samples // 2 + 1) take part in becomes one note with the
+        cluster's median onset, offset and velocity.  -> the NoteSequence; with return_votes (NoteSequence, the
+        `consensus.Consensus` record with votes, members and every sample's per-note votes, the samples).  The seeds and
+        the ValueErrors are `sample`'s; the model's own decoding and sampling parameters are left as they were."""
+        from . import consensus
+        samples = self.sample(audio, num_samples, sample_rate, **kw)
+        result = consensus.consensus([samples], tolerance=tolerance, min_votes=min_votes)[0]
+        return (result.notes, result, samples) if return_votes else result.notes
+
     def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample

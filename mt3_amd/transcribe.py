@@ -6,6 +6,7 @@
                                  [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]] [--render [RATE]]
                                  [--score-against DIR] [--score-midi DIR [--score-shifts S,...]]
                                  [--align-midi DIR [--align-max-shift S] [--align-step S] [--align-smoothness L]]
+                                 [--consensus N [--consensus-min-votes M] [--consensus-tolerance S]]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -37,6 +38,13 @@ segment of the audio (`InferenceModel.align_notes_many`: all inputs as one job; 
 of jump between neighbouring segments) and writes the moved notes as NAME.aligned.mid beside NAME.mid, and one
 alignment.json into the output directory: a list with one record per input, in input order -- "audio", "segment_shifts",
 "path_score", "flat_shift", "flat_score" (same one-directory rule as --score-against).
+--consensus N writes as NAME.mid the notes that N sampled transcriptions of the input agree on
+(`InferenceModel.consensus`: N draws with the sampling parameters of --temperature / --top-k / --top-p and seeds --seed ..
+--seed + N - 1, voted on the device; a note is kept when --consensus-min-votes of them have it, default a strict
+majority; onsets within --consensus-tolerance seconds, default 0.05, are one note), and NAME.votes.json beside it:
+{"n_voters": N, "min_votes": M, "notes": [...]}, one record per note of NAME.mid in the NoteSequence's order with its
+start_time, end_time, pitch, program, is_drum, votes and members.  Each input is a job of its own (N decodes).  Not with
+--decoding beam, and not together with --confidences.
 """
 from __future__ import annotations
 
@@ -105,6 +113,13 @@ def plan(argv=None):
                     "in seconds (default 0.02)")
     ap.add_argument("--align-smoothness", type=float, default=None, metavar="L",
                     help="--align-midi: log-probability a path pays per second of jump between neighbouring segments")
+    ap.add_argument("--consensus", type=int, default=None, metavar="N",
+                    help="write the notes N sampled transcriptions agree on (1 .. 64) as NAME.mid, and NAME.votes.json "
+                         "beside it: every note's votes and members")
+    ap.add_argument("--consensus-min-votes", type=int, default=None, metavar="M",
+                    help="--consensus: the samples that must have a note for it to be kept (1 .. N; default N // 2 + 1)")
+    ap.add_argument("--consensus-tolerance", type=float, default=None, metavar="S",
+                    help="--consensus: seconds between neighbouring onsets of one note's cluster (default 0.05)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -118,6 +133,21 @@ def plan(argv=None):
         ap.error("--pianoroll takes a positive number of frames per second")
     if args.render is not None and not 1 <= args.render <= 384000:
         ap.error("--render takes a sample rate of 1 .. 384000 Hz")
+    if args.consensus is None:
+        for name in ("consensus_min_votes", "consensus_tolerance"):
+            if getattr(args, name) is not None:
+                ap.error("--%s needs --consensus" % name.replace("_", "-"))
+    else:
+        if not 1 <= args.consensus <= 64:
+            ap.error("--consensus takes 1 .. 64 samples")
+        if args.consensus_min_votes is not None and not 1 <= args.consensus_min_votes <= args.consensus:
+            ap.error("--consensus-min-votes must be 1 .. %d (--consensus)" % args.consensus)
+        if args.consensus_tolerance is None:
+            args.consensus_tolerance = 0.05
+        if not (math.isfinite(args.consensus_tolerance) and args.consensus_tolerance >= 0):
+            ap.error("--consensus-tolerance takes seconds >= 0")
+        if args.confidences:
+            ap.error("--consensus and --confidences do not go together")
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
@@ -195,7 +225,17 @@ def main(argv=None) -> int:
         model = inference.InferenceModel(args.checkpoint, args.model, dtype=args.dtype, decoding=args.decoding,
                                          num_beams=args.num_beams, temperature=args.temperature, top_k=args.top_k,
                                          top_p=args.top_p, seed=args.seed)
-        if args.confidences:
+        votes = None
+        if args.consensus is not None:
+            from . import audio_io
+            voted = []
+            for path in args.inputs:
+                samples, rate = audio_io.read_wav(path)
+                voted.append(model.consensus(samples, args.consensus, rate, tolerance=args.consensus_tolerance,
+                                             min_votes=args.consensus_min_votes, return_votes=True,
+                                             programs=args.programs, drums=args.drums, well_formed=args.well_formed))
+            sequences, scores, votes = [ns for ns, _, _ in voted], None, [rec for _, rec, _ in voted]
+        elif args.confidences:
             scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums,
                                                   well_formed=args.well_formed)
                       for path in args.inputs]
@@ -253,6 +293,9 @@ def main(argv=None) -> int:
     for ns, sc, path in zip(sequences, scores or [], outputs):
         with open(confidence_path(path), "w") as f:
             json.dump(confidence_records(ns, sc), f, indent=1)
+    for rec, path in zip(votes or [], outputs):
+        with open(votes_path(path), "w") as f:
+            json.dump(votes_record(rec), f, indent=1)
     for roll, path in zip(rolls or [], outputs):
         import numpy as np
         np.save(pianoroll_path(path), roll)
@@ -274,6 +317,18 @@ def main(argv=None) -> int:
         with open(alignment_path(outputs), "w") as f:
             json.dump([alignment_record(path, rec) for path, rec in zip(args.inputs, aligned)], f, indent=1)
     return 0
+
+
+def votes_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".votes.json"
+
+
+def votes_record(rec) -> dict:
+    """the JSON-ready form of one `consensus.Consensus`: the notes in the NoteSequence's order with their votes"""
+    return {"n_voters": rec.n_voters, "min_votes": rec.min_votes,
+            "notes": [{"start_time": n.start_time, "end_time": n.end_time, "pitch": n.pitch, "program": n.program,
+                       "is_drum": bool(n.is_drum), "votes": int(v), "members": int(m)}
+                      for n, v, m in zip(rec.notes.notes, rec.votes, rec.members)]}
 
 
 def aligned_path(midi_path: str) -> str:
