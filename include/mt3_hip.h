@@ -405,6 +405,30 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
                                 int32_t num_steps, int32_t flags, int32_t* d_ids, int32_t* d_all_ids /* NULL ok */,
                                 float* d_scores /* NULL ok */, mt3_transcribe_stats* h_stats, void* stream);
 
+/* Several DRAWS of every segment in one job, each segment encoded once (n sampled transcriptions of one recording are the
+ * use): mt3_engine_transcribe on a job of n_segments * per draws, draw d = s * per + j being sample j of segment s.
+ * d_inputs [n_segments, T, input_depth] f32 holds every segment ONCE; d_ids [n_segments * per, L] int32: row s * per + j is
+ * draw j of segment s.  "Segment i" of every per-segment table -- token masks, prompts, sampling streams, sampling seeds
+ * (mt3_engine_set_sampling_seeds: what tells the draws of a segment apart) and the synthetic EOS schedule -- means DRAW i:
+ * the tables cover n_segments * per entries.  Without sampling the `per` draws of a segment are equal; that is legal.
+ * Contract: d_ids is BIT-IDENTICAL to mt3_engine_transcribe on the inputs with each segment `per` times in a row and the
+ * same tables set, under the encoder-reproducibility condition mt3_engine_encode documents (f32: always; bf16: every
+ * encoder pass of 8 or more segments -- the staging passes are padded to 8 as in mt3_engine_transcribe).
+ * Schedule: mt3_engine_transcribe's greedy path with min(n_segments * per, max_batch) slots.  As in
+ * mt3_engine_transcribe_beams EVERY draw reaches its slot through the staging ring: the slots start finished and empty,
+ * an encoder pass covers up to 64 segments (a short last pass is padded with the segments before it), and the `per` draws
+ * of a segment copy the same staged entry into their cache rows.
+ * flags: MT3_DECODE_NO_GRAPH, MT3_DECODE_SINGLE_STREAM.  MT3_ERR_INVALID, before any device work: any other flag bit
+ * (MT3_DECODE_BEAM1 included: beam-1 does not sample), per < 1, n_segments * per above INT32_MAX / L, and the argument
+ * errors of mt3_engine_transcribe (NULL d_inputs or d_ids, n_segments < 1, num_steps outside 1 .. L, more than 16 decoder
+ * layers, a decode in flight, a per-segment table or EOS schedule shorter than n_segments * per).
+ * h_stats (may be NULL) as for mt3_engine_transcribe: slots as above, refills = n_segments * per - slots, encoder_chunks =
+ * ALL encoder passes = ceil(n_segments / 64) (ceil(n_segments / max_batch) below 64 slots).  The call BLOCKS until every
+ * draw is done. */
+int mt3_engine_transcribe_draws(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t per, int32_t num_steps,
+                                int32_t flags, int32_t* d_ids /* [n_segments * per][L] */, mt3_transcribe_stats* h_stats,
+                                void* stream);
+
 /* Constrained decoding: per-segment token masks (allowed instruments are the use: mt3_codec_token_mask).  What a logit
  * mask ahead of t5x decoding.beam_search does [from memory: t5x is not at hand, as for the beam search above]:
  *   mask     a bit set over the vocabulary, words = ceil(vocab / 32) uint32: bit i % 32 of word i / 32 set = token i allowed.
@@ -804,6 +828,16 @@ uint32_t mt3_sampling_bits(uint64_t seed, uint64_t stream, int32_t t, int32_t id
 float mt3_sampling_gumbel(uint32_t bits);
 int mt3_engine_set_sampling(mt3_engine* e, const mt3_sampling* s /* NULL clears */,
                             const uint64_t* h_seg_stream /* [n_segments] or NULL */, int32_t n_segments);
+/* Per-segment seeds: where this table is set, the Philox key of segment i (row i of mt3_engine_decode, segment i of
+ * mt3_engine_transcribe, draw i of mt3_engine_transcribe_draws -- indexed exactly as h_seg_stream is) is h_seg_seed[i] in
+ * place of mt3_sampling.seed; everything else of the rule above stays.  Two draws of one segment can therefore sit in one
+ * job: same stream, different seeds.  A synchronous setup call like its neighbours; NULL clears the table, and so does
+ * mt3_engine_set_sampling(e, NULL, ...).  A sampled step graph captured with the table never serves a job without it, or
+ * the reverse; a sampled step without the table runs the kernels and gives the bits it gave before the table existed.
+ * MT3_ERR_INVALID, before any device work: n_segments < 1 with h_seg_seed; an engine that is not finalized; a decode in
+ * flight; a table while sampling is not set.  The decode / transcribe calls return MT3_ERR_INVALID before any device work
+ * for more rows, segments or draws than n_segments. */
+int mt3_engine_set_sampling_seeds(mt3_engine* e, const uint64_t* h_seg_seed /* [n_segments] or NULL */, int32_t n_segments);
 
 /* Teacher-forced cached decode: Transformer.decode (mt3/network.py:303-361) on GIVEN decoder inputs, driven one
  * token per call through the same cached step (layers.py:246-314) the autoregressive loop uses -- the input of
@@ -1165,6 +1199,16 @@ int mt3_op_token_steps_notes(float* d_logits, const float* d_ss, int32_t n_ss, i
                              const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
                              const mt3_note_grammar* h_notes, int32_t* h_state, const mt3_sampling* h_sampling,
                              const uint64_t* h_row_stream, int32_t* h_note, uint32_t* h_held);
+/* mt3_op_token_steps_notes with per-row Philox keys (mt3_engine_set_sampling_seeds states the rule): h_row_seed (HOST,
+ * [rows], may be NULL) gives the key of each row in place of h_sampling->seed; it is read only with h_sampling.  With
+ * NULL the call is the _notes driver, bit for bit. */
+int mt3_op_token_steps_seeded(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows, int32_t vocab,
+                              int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids, int32_t* h_done,
+                              void* stream, const uint32_t* d_masks, int32_t n_masks, const int32_t* d_row_mask,
+                              const int32_t* d_prompts, int32_t stride, const int32_t* d_row_prompt,
+                              const mt3_note_grammar* h_notes, int32_t* h_state, const mt3_sampling* h_sampling,
+                              const uint64_t* h_row_stream, int32_t* h_note, uint32_t* h_held,
+                              const uint64_t* h_row_seed);
 int mt3_op_beam_search_notes(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
                              int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
                              const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
@@ -1263,6 +1307,16 @@ int mt3_op_slot_refill(const mt3_slot_state_view* st, const mt3_input_row_view* 
                        int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids, int32_t ids_stride,
                        int32_t* d_out_ids, int32_t rows, int32_t n_new, int32_t first_seg,
                        const mt3_staged_cross_view* x, int32_t* h_plan, void* stream);
+/* mt3_op_slot_refill as mt3_engine_transcribe_draws issues it: `per` consecutive DRAWS share one staged entry.  first_seg
+ * and x->src_entry0 count draws; x keeps its layout, its src_batch is the number of staged ENTRIES (the encoder pass's
+ * real batch, the plane stride of the chunk), and src_entry0 + n_new <= src_batch * per.  The i-th restarted slot takes
+ * the staged cross K/V (and e4m3 scale rows, where x has them) of entry (src_entry0 + i) / per -- a run may start in the
+ * middle of an entry's draws -- and restarts on draw first_seg + i.  per = 1 is mt3_op_slot_refill, byte for byte;
+ * per < 1 is MT3_ERR_INVALID. */
+int mt3_op_slot_refill_draws(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f,
+                             int32_t beam_rows, int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids,
+                             int32_t ids_stride, int32_t* d_out_ids, int32_t rows, int32_t n_new, int32_t first_seg,
+                             const mt3_staged_cross_view* x, int32_t per, int32_t* h_plan, void* stream);
 /* The refill of mt3_engine_transcribe_beams over b->elems elements: every finished element (first slot done) with
  * slot_seg >= 0 has its k decodes walked back from the history into d_out_all[seg] [k][L] / d_out_scores[seg] [k]
  * (increasing score; optional) and the best into d_out_ids[seg] [L]; the first n_new restart (live = [0, -1e7, ...],

@@ -198,6 +198,8 @@ SIGNATURES = {
     "mt3_engine_transcribe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(TranscribeStats), _P]),
     "mt3_engine_transcribe_beams": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                               C.POINTER(TranscribeStats), _P]),
+    "mt3_engine_transcribe_draws": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                              C.POINTER(TranscribeStats), _P]),
     "mt3_engine_decode_forced": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mt3_engine_score": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "mt3_engine_score_segments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
@@ -217,6 +219,7 @@ SIGNATURES = {
     "mt3_token_grammar_advance": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
     "mt3_token_grammar_allowed": (C.c_int32, [C.POINTER(TokenGrammar), C.c_int32, C.c_int32]),
     "mt3_engine_set_sampling": (C.c_int, [_P, C.POINTER(Sampling), _P, C.c_int32]),
+    "mt3_engine_set_sampling_seeds": (C.c_int, [_P, _P, C.c_int32]),
     "mt3_sampling_bits": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "mt3_sampling_gumbel": (C.c_float, [C.c_uint32]),
     "mt3_engine_status": (C.c_int, [_P, C.c_int32]),
@@ -282,6 +285,9 @@ SIGNATURES = {
     "mt3_op_token_steps_notes": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
                                            C.POINTER(NoteGrammar), _P, C.POINTER(Sampling), _P, _P, _P]),
+    "mt3_op_token_steps_seeded": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P,
+                                            C.POINTER(NoteGrammar), _P, C.POINTER(Sampling), _P, _P, _P, _P]),
     "mt3_op_beam_search_notes": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.c_int32, _P,
@@ -293,6 +299,9 @@ SIGNATURES = {
                                       _P]),
     "mt3_op_slot_refill": (C.c_int, [C.POINTER(SlotStateView), C.POINTER(InputRowView), _P, C.c_int32, _P, _P, _P,
                                      C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(StagedCrossView), _P, _P]),
+    "mt3_op_slot_refill_draws": (C.c_int, [C.POINTER(SlotStateView), C.POINTER(InputRowView), _P, C.c_int32, _P, _P, _P,
+                                           C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(StagedCrossView),
+                                           C.c_int32, _P, _P]),
     "mt3_op_beam_refill": (C.c_int, [C.POINTER(BeamKView), C.POINTER(SlotStateView), C.POINTER(InputRowView), C.c_int32,
                                      C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(StagedCrossView), _P, _P]),
     "mt3_op_beam_stream_init": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),

@@ -600,7 +600,9 @@ __device__ __forceinline__ unsigned long long cand_key(float v, int i) {
 // Every branch on the slot's state (done, inside its prompt, at its scheduled EOS) is block-uniform.
 // NOTES = true: the note rule on top of the grammar (a.nt; argmax_step_kernel's NOTES form says how); NOTES = false compiles
 // from the statements the kernel had before the note rule existed.
-template <bool NOTES>
+// SEEDS = true: the Philox key of a slot is its segment's entry of sa.seed (a table indexed as sa.stream is; no row: the
+// parameters' seed); SEEDS = false compiles from the statements the kernel had before the seed table existed.
+template <bool NOTES, bool SEEDS>
 __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
   const ArgmaxStepArgs& a = sa.a;
   const SlotState& st = a.st;
@@ -641,6 +643,11 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
   const mt3_sampling sp = *sa.params;
   const uint64_t* srow = sa.stream.rows ? seg_table_row(sa.stream, seg) : nullptr;
   const uint64_t stream = srow ? *srow : static_cast<uint64_t>(static_cast<int64_t>(sa.seg0) + seg);
+  uint64_t seed = sp.seed;
+  if (SEEDS) {
+    const uint64_t* krow = seg_table_row(sa.seed, seg);
+    if (krow) seed = *krow;
+  }
   if (ls.ss) {                                           // the folded logits projection, as the greedy kernel applies it
     if (wave == 0) {
       float p = lane < ls.n_ss ? ls.ss[static_cast<size_t>(b) * ls.n_ss + lane] : 0.f;
@@ -748,7 +755,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(SampleStepArgs sa) {
     for (int u = 0; u < kPer; ++u) {
       if (!keep[u]) continue;
       const int i = tid + u * 256;
-      const float v = z[u] + mt3s_gumbel(mt3s_bits(sp.seed, stream, t, i));
+      const float v = z[u] + mt3s_gumbel(mt3s_bits(seed, stream, t, i));
       if (cand_better(v, i, bv, bi)) {
         bv = v;
         bi = i;
@@ -827,8 +834,15 @@ int launch_sample_step(const SampleStepArgs& sa, hipStream_t s) {
                                       "note states and a valid descriptor");
   if (sa.stream.rows && sa.stream.stride != 1)
     return mt3::fail(MT3_ERR_INVALID, "sample_step: the stream table holds one entry per row");
-  if (a.nt.on) hipLaunchKernelGGL(sample_step_kernel<true>, dim3(a.B), dim3(256), 0, s, sa);
-  else hipLaunchKernelGGL(sample_step_kernel<false>, dim3(a.B), dim3(256), 0, s, sa);
+  if (sa.seed.rows && sa.seed.stride != 1)
+    return mt3::fail(MT3_ERR_INVALID, "sample_step: the seed table holds one entry per row");
+  if (sa.seed.rows) {
+    if (a.nt.on) hipLaunchKernelGGL((sample_step_kernel<true, true>), dim3(a.B), dim3(256), 0, s, sa);
+    else hipLaunchKernelGGL((sample_step_kernel<false, true>), dim3(a.B), dim3(256), 0, s, sa);
+  } else {
+    if (a.nt.on) hipLaunchKernelGGL((sample_step_kernel<true, false>), dim3(a.B), dim3(256), 0, s, sa);
+    else hipLaunchKernelGGL((sample_step_kernel<false, false>), dim3(a.B), dim3(256), 0, s, sa);
+  }
   MT3_HIP_CHECK(hipGetLastError());
   return MT3_OK;
 }
@@ -947,6 +961,8 @@ int launch_compact(const CompactArgs& c, hipStream_t s) {
 //   slot   block i: id row of slot plan[i] -> the caller's row of the segment it decoded (beam-1: the finished
 //          hypothesis, as beam1_finalize_kernel would leave it); i < n_new: restart on segment first_seg + i
 // (unit > 1: plan and cross copy are over ELEMENTS of `unit` slots each -- beam groups, keyed on the element's first slot)
+// (StagedCross::per > 1, mt3_engine_transcribe_draws: first_seg, src_entry0 and src_batch count DRAWS, `per` of which share
+// one staged entry -- restarted slot i copies entry (src_entry0 + i) / per of a chunk whose planes are src_batch / per apart)
 __global__ __launch_bounds__(64) void refill_plan_kernel(const int* __restrict__ done, int* __restrict__ plan,
                                                           int* __restrict__ n_done, int rows, int n_new, int unit) {
   const int lane = threadIdx.x;
@@ -977,12 +993,12 @@ __global__ __launch_bounds__(256) void refill_cross_kernel(StagedCross x, const 
   size_t bytes;
   if (what < 2) {
     bytes = x.row_bytes;
-    src = x.src[l] + (static_cast<size_t>(what) * x.src_batch + x.src_entry0 + i) * bytes;
+    src = x.src[l] + (static_cast<size_t>(what) * (x.src_batch / x.per) + (x.src_entry0 + i) / x.per) * bytes;
     dst = x.dst[l] + static_cast<size_t>(what) * x.dst_batch * bytes;
   } else {
     if (!x.src_sc[l]) return;
     bytes = x.sc_bytes;
-    src = x.src_sc[l] + static_cast<size_t>(x.src_entry0 + i) * bytes;
+    src = x.src_sc[l] + static_cast<size_t>((x.src_entry0 + i) / x.per) * bytes;
     dst = x.dst_sc[l];
   }
   u32x4* d4[kBeamMaxK];
@@ -1045,7 +1061,7 @@ __global__ __launch_bounds__(128) void refill_slot_kernel(RefillArgs a) {
 
 static bool bad_staged_cross(const StagedCross& x, int n_new) {   // a copy of n_new staged segments that cannot be right
   return x.n_layers <= 0 || x.n_layers > kRefillMaxLayers || x.row_bytes % 16 || x.sc_bytes % 16 || x.src_batch <= 0 ||
-         x.dst_batch <= 0 || x.src_entry0 < 0 || x.src_entry0 + n_new > x.src_batch;
+         x.dst_batch <= 0 || x.src_entry0 < 0 || x.src_entry0 + n_new > x.src_batch || x.per < 1 || x.src_batch % x.per;
 }
 
 // the plan (refill_plan_kernel) and the copy of the first n_new staged segments of `x` into the slots it names
@@ -2064,7 +2080,8 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
                               const int32_t* d_row_prompt = nullptr, const mt3_token_grammar* h_grammar = nullptr,
                               int32_t* h_state = nullptr, const mt3_sampling* h_sampling = nullptr,
                               const uint64_t* h_row_stream = nullptr, const mt3_note_grammar* h_notes = nullptr,
-                              int32_t* h_note = nullptr, uint32_t* h_held = nullptr) {
+                              int32_t* h_note = nullptr, uint32_t* h_held = nullptr,
+                              const uint64_t* h_row_seed = nullptr) {
   if (h_notes) h_grammar = &h_notes->g;             // the note rule's grammar is the grammar
   if (!d_logits || !d_ids || !h_done) return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
   if ((mode != 0 && mode != 1) || rows <= 0 || rows > 4096 || vocab < 2 || num_steps <= 0 || num_steps > 4096 ||
@@ -2124,16 +2141,19 @@ static int token_steps_driver(const std::string& who, bool masked, float* d_logi
   Scratch sm;
   mt3k::SampleStepArgs sa{};
   if (h_sampling) {
-    MT3_OP_TRY(sm.alloc(Scratch::piece(sizeof(mt3_sampling)) + Scratch::piece(n * 8) + Scratch::piece(n * 4), s));
+    MT3_OP_TRY(sm.alloc(Scratch::piece(sizeof(mt3_sampling)) + 2 * Scratch::piece(n * 8) + Scratch::piece(n * 4), s));
     mt3_sampling* d_sp = sm.take<mt3_sampling>(1);
     uint64_t* d_stream = sm.take<uint64_t>(n);
-    int* d_row = sm.take<int>(n);                              // row i's stream is entry i of the table
+    uint64_t* d_seed = sm.take<uint64_t>(n);
+    int* d_row = sm.take<int>(n);                              // row i's stream (and seed) is entry i of its table
     MT3_HIP_CHECK(hipMemcpyAsync(d_sp, h_sampling, sizeof(mt3_sampling), hipMemcpyHostToDevice, s));
     if (h_row_stream) MT3_HIP_CHECK(hipMemcpyAsync(d_stream, h_row_stream, n * 8, hipMemcpyHostToDevice, s));
+    if (h_row_seed) MT3_HIP_CHECK(hipMemcpyAsync(d_seed, h_row_seed, n * 8, hipMemcpyHostToDevice, s));
     MT3_OP_TRY(mt3k::launch_iota(d_row, rows, s));
     MT3_HIP_CHECK(hipStreamSynchronize(s));                    // the host arrays are the caller's
     sa.params = d_sp;
     if (h_row_stream) sa.stream = mt3k::SampleStream{d_stream, d_row, nullptr, 1};
+    if (h_row_seed) sa.seed = mt3k::SampleStream{d_seed, d_row, nullptr, 1};
   }
   for (int t = 0; t < num_steps; ++t) {
     a.logits = d_logits + static_cast<size_t>(t) * n * vocab;
@@ -2227,6 +2247,18 @@ extern "C" int mt3_op_token_steps_notes(float* d_logits, const float* d_ss, int3
                             d_row_prompt, nullptr, h_state, h_sampling, h_row_stream, h_notes, h_note, h_held);
 }
 
+extern "C" int mt3_op_token_steps_seeded(float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t rows,
+                                         int32_t vocab, int32_t num_steps, int32_t mode, int32_t max_len, int32_t* d_ids,
+                                         int32_t* h_done, void* stream, const uint32_t* d_masks, int32_t n_masks,
+                                         const int32_t* d_row_mask, const int32_t* d_prompts, int32_t stride,
+                                         const int32_t* d_row_prompt, const mt3_note_grammar* h_notes, int32_t* h_state,
+                                         const mt3_sampling* h_sampling, const uint64_t* h_row_stream, int32_t* h_note,
+                                         uint32_t* h_held, const uint64_t* h_row_seed) {
+  return token_steps_driver("mt3_op_token_steps_seeded", d_masks != nullptr, d_logits, d_ss, n_ss, dim, rows, vocab,
+                            num_steps, mode, max_len, d_ids, h_done, stream, d_masks, n_masks, d_row_mask, d_prompts, stride,
+                            d_row_prompt, nullptr, h_state, h_sampling, h_row_stream, h_notes, h_note, h_held, h_row_seed);
+}
+
 extern "C" int mt3_op_beam_search_notes(const float* d_logits, const float* d_ss, int32_t n_ss, int32_t dim, int32_t elems,
                                         int32_t k, int32_t vocab, int32_t num_steps, int32_t max_len, const float* d_table,
                                         const float* d_pos, int32_t dim_e, int32_t* d_ids, int32_t* d_all_ids,
@@ -2306,17 +2338,20 @@ bool bad_written_row(const mt3k::InputRow& r) {
 }
 
 // MT3_OK and `out` filled, or what is wrong with a staged-cross view of n_new segments (unused when n_new == 0)
-int staged_cross_of(const mt3_staged_cross_view* v, int n_new, const char* who, mt3k::StagedCross* out) {
+// (per > 1, mt3_op_slot_refill_draws: the view's src_batch counts staged ENTRIES, its src_entry0 draws)
+int staged_cross_of(const mt3_staged_cross_view* v, int n_new, const char* who, mt3k::StagedCross* out, int per = 1) {
   *out = mt3k::StagedCross{};
+  out->per = per;
   if (n_new <= 0) return MT3_OK;
   const std::string w(who);
   if (!v || !v->src || !v->dst) return mt3::fail(MT3_ERR_INVALID, w + ": segments to hand out need a staging chunk");
   if (v->n_layers <= 0 || v->n_layers > mt3k::kRefillMaxLayers || v->row_bytes == 0 || v->row_bytes % 16 ||
       v->sc_bytes % 16 || v->src_batch <= 0 || v->dst_batch <= 0 || v->src_entry0 < 0 ||
-      static_cast<long long>(v->src_entry0) + n_new > v->src_batch)
+      static_cast<long long>(v->src_entry0) + n_new > static_cast<long long>(v->src_batch) * per ||
+      static_cast<long long>(v->src_batch) * per > 0x7fffffffLL)
     return mt3::fail(MT3_ERR_INVALID, w + ": bad staging chunk");
   out->n_layers = v->n_layers;
-  out->src_batch = v->src_batch;
+  out->src_batch = v->src_batch * per;
   out->src_entry0 = v->src_entry0;
   out->dst_batch = v->dst_batch;
   out->row_bytes = v->row_bytes;
@@ -2390,25 +2425,28 @@ extern "C" int mt3_op_slot_compact(const mt3_slot_state_view* st, const mt3_inpu
   return MT3_OK;
 }
 
-extern "C" int mt3_op_slot_refill(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f,
-                                  int32_t beam_rows, int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids,
-                                  int32_t ids_stride, int32_t* d_out_ids, int32_t rows, int32_t n_new, int32_t first_seg,
-                                  const mt3_staged_cross_view* x, int32_t* h_plan, void* stream) {
+// shared body of mt3_op_slot_refill (per = 1) and mt3_op_slot_refill_draws
+static int slot_refill_driver(const std::string& who, const mt3_slot_state_view* st, const mt3_input_row_view* in,
+                              float* d_beam_f, int32_t beam_rows, int32_t* d_beam_len, int32_t* d_beam_len_row,
+                              int32_t* d_ids, int32_t ids_stride, int32_t* d_out_ids, int32_t rows, int32_t n_new,
+                              int32_t first_seg, const mt3_staged_cross_view* x, int32_t per, int32_t* h_plan,
+                              void* stream) {
   if (!st || !in || !st->done || !st->slot_row || !st->slot_seg || !st->step || !st->cur_tok || !st->n_done || !d_ids ||
       !d_out_ids)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: null argument");
+    return mt3::fail(MT3_ERR_INVALID, who + ": null argument");
+  if (per < 1) return mt3::fail(MT3_ERR_INVALID, who + ": per must be at least 1");
   if (rows <= 0 || rows > kOpMaxSlots || n_new < 0 || n_new > rows || ids_stride <= 0 || first_seg < 0)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: 1 .. 65536 rows, 0 <= n_new <= rows, ids_stride > 0, "
+    return mt3::fail(MT3_ERR_INVALID, who + ": 1 .. 65536 rows, 0 <= n_new <= rows, ids_stride > 0, "
                                       "first_seg >= 0");
   if (d_beam_f ? (!d_beam_len || !d_beam_len_row || beam_rows < rows) : (d_beam_len || d_beam_len_row))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: the beam state is f (two arrays beam_rows >= rows apart), "
+    return mt3::fail(MT3_ERR_INVALID, who + ": the beam state is f (two arrays beam_rows >= rows apart), "
                                       "len and len_row, together");
   mt3k::RefillArgs a{};
   a.in = input_row_of(*in);
   if (bad_written_row(a.in))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_op_slot_refill: the input row needs y, its tables, dim % 16 == 0, y_ss with "
+    return mt3::fail(MT3_ERR_INVALID, who + ": the input row needs y, its tables, dim % 16 == 0, y_ss with "
                                       "y_ct, and ew / pw / q_n % 4 == 0 with q_out");
-  MT3_OP_TRY(staged_cross_of(x, n_new, "mt3_op_slot_refill", &a.x));
+  MT3_OP_TRY(staged_cross_of(x, n_new, who.c_str(), &a.x, per));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n = static_cast<size_t>(rows);
   Scratch m;
@@ -2426,6 +2464,23 @@ extern "C" int mt3_op_slot_refill(const mt3_slot_state_view* st, const mt3_input
   if (h_plan) MT3_HIP_CHECK(hipMemcpyAsync(h_plan, a.plan, (n + 1) * 4, hipMemcpyDeviceToHost, s));
   MT3_HIP_CHECK(hipStreamSynchronize(s));
   return MT3_OK;
+}
+
+extern "C" int mt3_op_slot_refill(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f,
+                                  int32_t beam_rows, int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids,
+                                  int32_t ids_stride, int32_t* d_out_ids, int32_t rows, int32_t n_new, int32_t first_seg,
+                                  const mt3_staged_cross_view* x, int32_t* h_plan, void* stream) {
+  return slot_refill_driver("mt3_op_slot_refill", st, in, d_beam_f, beam_rows, d_beam_len, d_beam_len_row, d_ids, ids_stride,
+                            d_out_ids, rows, n_new, first_seg, x, 1, h_plan, stream);
+}
+
+extern "C" int mt3_op_slot_refill_draws(const mt3_slot_state_view* st, const mt3_input_row_view* in, float* d_beam_f,
+                                        int32_t beam_rows, int32_t* d_beam_len, int32_t* d_beam_len_row, int32_t* d_ids,
+                                        int32_t ids_stride, int32_t* d_out_ids, int32_t rows, int32_t n_new,
+                                        int32_t first_seg, const mt3_staged_cross_view* x, int32_t per, int32_t* h_plan,
+                                        void* stream) {
+  return slot_refill_driver("mt3_op_slot_refill_draws", st, in, d_beam_f, beam_rows, d_beam_len, d_beam_len_row, d_ids,
+                            ids_stride, d_out_ids, rows, n_new, first_seg, x, per, h_plan, stream);
 }
 
 extern "C" int mt3_op_beam_refill(const mt3_beam_k_view* b, const mt3_slot_state_view* st, const mt3_input_row_view* in,

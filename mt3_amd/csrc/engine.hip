@@ -302,6 +302,10 @@ struct mt3_engine {
   bool samp_on = false;
   bool samp_seen = false, samp_table = false;   // sampling has been set before, and then with a stream table: the sampled
                                  // step graphs hold whether there is one
+  SegTableHost<uint64_t> sseed;  // per-segment Philox keys (mt3_engine_set_sampling_seeds): a table like sstream, indexed as it
+                                 // is (not set: every segment's key is the parameters' seed)
+  bool seed_table = false;       // the form the sampled step graphs hold (there may be some as soon as sampling has been set,
+                                 // captured without a seed table: false is the true state of a new engine)
   int* gram = nullptr;           // [max_batch] per slot: the packed grammar state (SlotState::gram); with a grammar set it
                                  // travels with the slot and is reset with it, without one no launch is handed it
   // In-flight batching (mt3_engine_transcribe): slot_seg maps a slot to the SEGMENT it is decoding (-1: none); a
@@ -975,7 +979,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
     if (skip & kVarSample) {
       // the stream table is indexed as the masks are; without one the stream is the row / segment index itself
       mt3k::SampleStepArgs sa{a, e->samp, e->sstream.n ? seg_view(e->sstream, crow0, nullptr) : mt3k::SampleStream{},
-                              static_cast<int>(crow0)};
+                              static_cast<int>(crow0),
+                              e->sseed.n ? seg_view(e->sseed, crow0, nullptr) : mt3k::SampleStream{}};
       return mt3k::launch_sample_step(sa, s);
     }
     return mt3k::launch_argmax_step(a, s);
@@ -2050,11 +2055,12 @@ static int seg_tables_fit(const mt3_engine* e, const char* who, int n, int need,
 }
 
 // Temperature sampling against a greedy-path job of `n` rows / segments (the beam calls, teacher forcing and scoring ignore
-// it): beam-1 does not sample, and a stream table must cover the job.  MT3_OK and *var |= kVarSample where it is set.
+// it): beam-1 does not sample, and a stream table and a seed table must cover the job.  MT3_OK and *var |= kVarSample where it is set.
 static int sampling_fits(const mt3_engine* e, const char* who, int n, bool beam1, int* var) {
   if (!e->samp_on) return MT3_OK;
   if (beam1) return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": MT3_DECODE_BEAM1 does not sample (clear sampling first)");
   MT3_TRY(fits(e->sstream, who, n, 0, 0, "the sampling streams'", ": a sampling stream is out of range"));
+  MT3_TRY(fits(e->sseed, who, n, 0, 0, "the sampling seeds'", ": a sampling seed is out of range"));
   *var |= kVarSample;
   return MT3_OK;
 }
@@ -2281,7 +2287,8 @@ static float2* stage_chunk_scale(const mt3_engine* e, int l, int chunk) {
 }
 
 // the staged run `rg` (sequence number -> ring chunk) and the caches of a `dst_batch`-row decode it is copied into
-static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_batch, mt3k::StagedCross* x) {
+// (per > 1, mt3_engine_transcribe_draws: the run counts draws, `per` of which share one staged entry)
+static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_batch, mt3k::StagedCross* x, int per = 1) {
   const mt3_engine_config& c = e->cfg;
   x->n_layers = c.num_decoder_layers;
   x->row_bytes = static_cast<size_t>(c.num_heads) * c.input_length * 64 * e->kv_esize;
@@ -2295,11 +2302,12 @@ static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_
   x->src_batch = rg.batch;
   x->src_entry0 = rg.entry0;
   x->dst_batch = dst_batch;
+  x->per = per;
 }
 
 // the refill launches of one run of staged segments for row group `r` (rg == nullptr: finished slots only hand their
 // ids over -- the queue is empty)
-static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRange* rg, int32_t* d_out) {
+static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRange* rg, int32_t* d_out, int per) {
   const mt3_engine_config& c = e->cfg;
   const size_t r0 = static_cast<size_t>(r.row0);
   mt3k::RefillArgs a{};
@@ -2315,7 +2323,7 @@ static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRan
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
-    fill_staged_cross(e, *rg, r.batch, &a.x);
+    fill_staged_cross(e, *rg, r.batch, &a.x, per);
   }
   return mt3k::launch_refill(a, r.s);
 }
@@ -2353,10 +2361,13 @@ static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* 
 // bo != nullptr (mt3_engine_transcribe_beams): the unit of refill is an ELEMENT of bo->k slots -- the snapshot, the
 // watchdog and `refillable` count slots, the feed counts segments = elements -- the group starts with every element
 // finished and takes its first segments off the feed before its first step, and it is never compacted.
-static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out, int kPoll, const BeamOut* bo = nullptr) {
+// draws_per > 0 (mt3_engine_transcribe_draws): the greedy path on a feed that counts DRAWS, draws_per of which share one
+// staged entry; as in the beam job the group starts with every slot finished and empty.
+static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out, int kPoll, const BeamOut* bo = nullptr,
+                            int draws_per = 0) {
   const int unit = bo ? bo->k : 1;
   auto refill = [&](int cur_rows, const FeedRange* rg) {
-    return bo ? refill_beam_group(e, r, rg, d_out, *bo) : refill_group(e, r, cur_rows, rg, d_out);
+    return bo ? refill_beam_group(e, r, rg, d_out, *bo) : refill_group(e, r, cur_rows, rg, d_out, draws_per ? draws_per : 1);
   };
   int cur = r.rows;
   hipGraphExec_t exec = nullptr;
@@ -2381,7 +2392,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
   const long stall_limit = static_cast<long>(r.num_steps) + 4L * kPoll + 64;
   long last_progress = 0;
   int seen_fin = 0;
-  if (bo) {
+  if (bo || draws_per) {
     // every element is finished and empty: the first refill comes before the first step interval
     int n_fin = r.rows;
     bool dry = false;
@@ -2470,8 +2481,10 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
   return MT3_OK;
 }
 
-// the producer side of the feed (calling thread, caller's stream)
-static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStream_t s, bool skip_encoder) {
+// the producer side of the feed (calling thread, caller's stream).  per > 1 (mt3_engine_transcribe_draws): the feed counts
+// draws, `per` of every segment: a claim is one of up to stage_cap * per draws, so that `first`, `n` and `pad` are multiples
+// of `per` and the pass encodes the (pad + n) / per segments from (first - pad) / per on, each ONCE.
+static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStream_t s, bool skip_encoder, int per = 1) {
   const mt3_engine_config& c = e->cfg;
   const size_t seg_floats = static_cast<size_t>(c.input_length) * c.input_depth;
   const int min_batch = e->stage_cap < kStageMinBatch ? e->stage_cap : kStageMinBatch;
@@ -2480,7 +2493,11 @@ static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStre
   int rc = MT3_OK;
   for (int q = 0; rc == MT3_OK; ++q) {
     int first, n, pad;
-    if (!mt3feed::feed_claim(f, q, e->stage_cap, min_batch, &first, &n, &pad)) break;
+    // (in draws, never above the job: stage_cap * per itself may not fit an int)
+    const long long total = f.n_total;
+    const int cap = static_cast<int>(std::min(static_cast<long long>(e->stage_cap) * per, total));
+    const int least = static_cast<int>(std::min(static_cast<long long>(min_batch) * per, total));
+    if (!mt3feed::feed_claim(f, q, cap, least, &first, &n, &pad)) break;
     for (int l = 0; l < c.num_decoder_layers; ++l) {
       kv[l] = stage_chunk_base(e, l, q);
       sc[l] = stage_chunk_scale(e, l, q);
@@ -2490,7 +2507,8 @@ static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStre
     dst.scale = e->kv_fp8 ? sc.data() : nullptr;
     // (skip_encoder: mt3_debug_engine_transcribe's differential timing -- the chunk goes on offer with whatever the staging
     // ring holds; under an imposed EOS schedule the decode does exactly the same work)
-    if (!skip_encoder) rc = encode_impl(e, d_inputs + static_cast<size_t>(first - pad) * seg_floats, pad + n, nullptr, dst, s);
+    if (!skip_encoder)
+      rc = encode_impl(e, d_inputs + static_cast<size_t>((first - pad) / per) * seg_floats, (pad + n) / per, nullptr, dst, s);
     if (rc == MT3_OK && wait_stream(e, kMaxGroups, s) != hipSuccess) rc = mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe: encoder pass failed");
     if (rc != MT3_OK) break;
     mt3feed::feed_publish(f, q, first, n, pad);
@@ -2508,20 +2526,25 @@ struct StreamCounts {
 // workers while the calling thread encodes segments [next_seg, n_segments) into the staging ring (segments below next_seg
 // sit in the caches already); then the groups' outcomes are folded into one.  The device-side start of the slots is the
 // entry point's, enqueued on j.s before this and closed with part_begin.
+// draws_per > 0 (mt3_engine_transcribe_draws): n_segments and next_seg count draws, draws_per of every segment of d_inputs.
 static int run_stream_job(mt3_engine* e, const std::string& who, const GroupJob& j, const float* d_inputs, int n_segments,
-                          int next_seg, int32_t* d_ids, int poll, const BeamOut* bo, bool skip_encoder, StreamCounts* n) {
+                          int next_seg, int32_t* d_ids, int poll, const BeamOut* bo, bool skip_encoder, StreamCounts* n,
+                          int draws_per = 0) {
   Feed feed;
   feed.n_total = n_segments;
   feed.next_seg = next_seg;
   feed.finished = next_seg == n_segments;
   PendingDecode& p = begin_job(e);
   int rc = MT3_OK;
-  if (!post_groups(e, j, [e, &feed, d_ids, poll, bo](GroupRun& r) { return run_group_stream(e, r, feed, d_ids, poll, bo); },
+  if (!post_groups(e, j,
+                   [e, &feed, d_ids, poll, bo, draws_per](GroupRun& r) {
+                     return run_group_stream(e, r, feed, d_ids, poll, bo, draws_per);
+                   },
                    &feed)) {
     feed_fail(feed);
     rc = mt3::fail(MT3_ERR_HIP, who + ": could not start a row group's worker thread");
   } else if (!feed.finished) {
-    rc = produce_chunks(e, feed, d_inputs, j.s, skip_encoder);
+    rc = produce_chunks(e, feed, d_inputs, j.s, skip_encoder, draws_per ? draws_per : 1);
   }
   const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
   for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
@@ -2688,6 +2711,73 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
   st.used_graph = e->last_used_graph;
   if (h_stats) *h_stats = st;
   return MT3_OK;
+}
+
+// mt3_engine_transcribe_draws: mt3_engine_transcribe's greedy path on a job of D = n_segments * per draws in
+// S = min(D, max_batch) slots, every segment encoded ONCE.  As in the beam job EVERY draw, the first S included, reaches its
+// slot through the staging ring: the groups start with every slot finished and empty and the feed -- which counts draws --
+// starts at 0; `per` consecutive draws copy the same staged entry (StagedCross::per).
+int mt3_engine_transcribe_draws(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t per, int32_t num_steps,
+                                int32_t flags, int32_t* d_ids, mt3_transcribe_stats* h_stats, void* stream) {
+  const std::string fn = "mt3_engine_transcribe_draws: ";
+  if (!e) return mt3::fail(MT3_ERR_INVALID, fn + "null engine");
+  const mt3_engine_config& c = e->cfg;
+  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM))
+    return mt3::fail(MT3_ERR_INVALID, fn + "flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM (beam-1 does not sample)");
+  if (!d_inputs || !d_ids || n_segments <= 0) return mt3::fail(MT3_ERR_INVALID, fn + "null buffer or no segments");
+  if (per < 1) return mt3::fail(MT3_ERR_INVALID, fn + "per must be at least 1");
+  if (num_steps <= 0 || num_steps > c.max_decode_len) return mt3::fail(MT3_ERR_INVALID, fn + "num_steps out of range");
+  const int L = c.max_decode_len;
+  if (static_cast<long long>(n_segments) * per > INT32_MAX / L)
+    return mt3::fail(MT3_ERR_INVALID, fn + "n_segments * per exceeds INT32_MAX / max_decode_len");
+  if (c.num_decoder_layers > mt3k::kRefillMaxLayers) return mt3::fail(MT3_ERR_INVALID, fn + "at most 16 decoder layers");
+  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, fn + "engine not finalized");
+  if (e->pending.active)
+    return mt3::fail(MT3_ERR_INVALID, fn + "a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+  const int D = n_segments * per, S = D < c.max_batch ? D : c.max_batch;
+  if (e->eos_on && D > e->eos_cap)
+    return mt3::fail(MT3_ERR_INVALID, fn + "the synthetic EOS schedule is shorter than n_segments * per");
+  int seg_var = 0;
+  MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe_draws", D, 2, num_steps, &seg_var));
+  MT3_TRY(sampling_fits(e, "mt3_engine_transcribe_draws", D, false, &seg_var));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MT3_TRY(ensure_stage(e));
+  const int groups = stream_groups_for(c, flags, S, 1, 0);
+  if (ensure_group_streams(e, groups) != MT3_OK)
+    return mt3::fail(MT3_ERR_HIP, fn + "could not create the row groups' streams");
+
+  // ---- every slot finished and empty, slot i on cache row i; valid (BOS) input rows so that the dense launches of empty
+  // slots read numbers; a group's counter of finished slots = its slots
+  MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, static_cast<size_t>(D) * L * 4, s));
+  MT3_TRY(reset_slots(e, S, false, true, s));
+  MT3_TRY(embed_bos(e, S, s));
+  MT3_TRY(mt3k::launch_iota(e->slot_row, S, s));
+  MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->done), 1, static_cast<size_t>(S), s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->slot_seg, 0xFF, static_cast<size_t>(S) * 4, s));   // -1: no segment
+  for (int g = 0; g < groups; ++g) {
+    int r0, rn;
+    chain_rows(S, groups, g, &r0, &rn);
+    MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->n_done + g), rn, 1, s));
+  }
+  e->cur_batch = S;
+  e->stream_max_len = num_steps;
+  const int variant = kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | seg_var;
+  MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
+  const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
+  StreamCounts n{};
+  const int rc = run_stream_job(e, "mt3_engine_transcribe_draws", j, d_inputs, D, 0, d_ids, kStreamPollSteps, nullptr, false, &n, per);
+  mt3_transcribe_stats st{};
+  st.slots = S;
+  st.groups = groups;
+  st.steps_run = n.most;
+  st.polls = n.polls;
+  st.refills = n.refills - S;
+  st.starved_polls = n.starved;
+  st.encoder_chunks = n.produced;
+  st.compactions = e->compactions;
+  st.used_graph = e->last_used_graph;
+  if (h_stats) *h_stats = st;
+  return rc;
 }
 
 int mt3_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t* d_ids,
@@ -3113,6 +3203,47 @@ int mt3_engine_set_note_grammar(mt3_engine* e, const mt3_note_grammar* n) {
   return MT3_OK;
 }
 
+// The sampled step graphs hold whether the Philox keys come from a seed table: the other form and they go.  Unlike the
+// streams' samp_seen there is no "never set" state: a sampled step may have been captured, without a table, before the
+// seeds setter was ever called.  table == false takes the table out of use.
+static int seed_table_form(mt3_engine* e, bool table) {
+  if (!table) e->sseed.n = 0;
+  if (e->seed_table != table) {
+    MT3_HIP_CHECK(hipDeviceSynchronize());
+    drop_step_graphs(e);
+  }
+  e->seed_table = table;
+  return MT3_OK;
+}
+
+int mt3_engine_set_sampling_seeds(mt3_engine* e, const uint64_t* h_seg_seed, int32_t n_segments) {
+  const std::string fn = "mt3_engine_set_sampling_seeds: ";
+  if (!e) return mt3::fail(MT3_ERR_INVALID, fn + "null engine");
+  if (h_seg_seed && n_segments < 1) return mt3::fail(MT3_ERR_INVALID, fn + "n_segments must be positive");
+  if (h_seg_seed && e->finalized && !e->pending.active && !e->samp_on)
+    return mt3::fail(MT3_ERR_INVALID, fn + "sampling is not set (mt3_engine_set_sampling comes first)");
+  // a per-segment table of one entry per row behind the identity index, as the streams are; the shared body refuses an
+  // engine that is not finalized or has a decode in flight before it touches the device
+  const bool table = h_seg_seed != nullptr;
+  std::vector<int32_t> ident(table ? static_cast<size_t>(n_segments) : 0);
+  for (size_t i = 0; i < ident.size(); ++i) ident[i] = static_cast<int32_t>(i);
+  const int rc = set_seg_table(e, e->sseed, fn, "seed", h_seg_seed, table ? n_segments : 0, 1, nullptr,
+                               table ? ident.data() : nullptr, n_segments, [](const uint64_t*, int* stat) {
+                                 *stat = 0;
+                                 return static_cast<const char*>(nullptr);
+                               });
+  if (rc != MT3_OK) {
+    // a copy that failed has left the table out of use (a refusal leaves it as it was): the graphs that hold it go too
+    if (!e->sseed.n && e->seed_table) {
+      const std::string why = mt3_last_error();
+      (void)seed_table_form(e, false);
+      return mt3::fail(rc, why);
+    }
+    return rc;
+  }
+  return seed_table_form(e, table);
+}
+
 int mt3_engine_set_sampling(mt3_engine* e, const mt3_sampling* sp, const uint64_t* h_seg_stream, int32_t n_segments) {
   const std::string fn = "mt3_engine_set_sampling: ";
   if (!e) return mt3::fail(MT3_ERR_INVALID, fn + "null engine");
@@ -3134,7 +3265,7 @@ int mt3_engine_set_sampling(mt3_engine* e, const mt3_sampling* sp, const uint64_
                         }));
   if (!sp) {
     e->samp_on = false;
-    return MT3_OK;
+    return seed_table_form(e, false);        // clearing sampling clears the per-segment seeds too
   }
   e->samp_on = false;             // (a failed copy leaves sampling off, not half set)
   // a setup call: nothing a caller enqueued earlier may still read the parameters this call replaces

@@ -328,13 +328,16 @@ int launch_argmax_step(const ArgmaxStepArgs& a, hipStream_t s);
 // argmax_step_kernel's place in the step.  The parameters are read from DEVICE memory, so that a captured step serves
 // every seed.  The noise stream of a slot is that of its segment: the entry of `stream`, a per-segment table of one
 // uint64 per row indexed as the masks are, or -- no table -- seg0 + the segment index the masks would be indexed by.
-// vocab <= MT3_SAMPLING_MAX_VOCAB: the row lives in registers, eight values per thread.
+// vocab <= MT3_SAMPLING_MAX_VOCAB: the row lives in registers, eight values per thread.  The Philox key of a slot is the
+// parameters' seed, or -- `seed`, a second table of one uint64 per row indexed exactly as `stream` is
+// (mt3_engine_set_sampling_seeds) -- its segment's entry: several draws of one segment can then sit in one job.
 using SampleStream = SegTable<uint64_t>;
 struct SampleStepArgs {
   ArgmaxStepArgs a;
   const mt3_sampling* params;   // device
   SampleStream stream;          // rows == nullptr: stream = seg0 + segment
   int seg0;
+  SampleStream seed;            // rows == nullptr: the key is params->seed (the instantiations that do not mention it run)
 };
 int launch_sample_step(const SampleStepArgs& a, hipStream_t s);
 // Compaction of the live slots of one row group to the front of the group (row retirement): the per-slot state that
@@ -370,7 +373,11 @@ int launch_compact(const CompactArgs& c, hipStream_t s);
 constexpr int kRefillMaxLayers = 16;
 // The staged cross-attention K/V of a run of segments and the caches they are copied into: per decoder layer, staging
 // chunk [2][src_batch][row_bytes] (the run starts at entry src_entry0) -> cache [2][dst_batch][row_bytes]; with e4m3
-// caches also the scale rows [src_batch][sc_bytes] -> [dst_batch][sc_bytes] (src_sc[l] == nullptr: none)
+// caches also the scale rows [src_batch][sc_bytes] -> [dst_batch][sc_bytes] (src_sc[l] == nullptr: none).
+// per > 1 (mt3_engine_transcribe_draws): `per` consecutive restarted slots share one staged entry -- src_batch and
+// src_entry0 count DRAWS, the i-th restarted slot copies entry (src_entry0 + i) / per and the chunk's planes are
+// src_batch / per entries apart (src_batch % per == 0; the run may start in the middle of an entry's draws).  per = 1:
+// one entry per slot, the copy it always was.
 struct StagedCross {
   int n_layers;
   const char* src[kRefillMaxLayers];
@@ -379,6 +386,7 @@ struct StagedCross {
   char* dst_sc[kRefillMaxLayers];
   int src_batch, src_entry0, dst_batch;
   size_t row_bytes, sc_bytes;
+  int per;
 };
 struct RefillArgs {
   SlotState st;         // n_done is decremented by the number of slots refilled

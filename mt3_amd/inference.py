@@ -86,7 +86,8 @@ class InferenceModel(object):
         probability top_p (0 .. 1); 0 turns either off, both on is an error.  The draw of a segment depends on `seed`, the
         segment's index within its own file and its logits only: a file's notes are the same alone, in any
         `transcribe_many` / `transcribe_wavs` job and on either schedule (f32; bf16 logits depend on the rows of a launch).
-        `sample(audio, num_samples=n)` draws n transcriptions with seeds seed .. seed + n - 1.
+        `sample(audio, num_samples=n)` draws n transcriptions with seeds seed .. seed + n - 1, as ONE engine job in which
+        every segment is encoded once (Transformer.transcribe(draws=n)).
         cap / drop_redundant_programs: for well_formed="tied" (`__call__`) -- the most (program, pitch) pairs a tie
         section carried from one segment into the next may declare, and whether it repeats a program id that does not
         change (True, the default, is the form MT3's targets have after remove_redundant_state_changes)."""
@@ -115,6 +116,7 @@ class InferenceModel(object):
             raise ValueError("decoding must be 'beam1', 'greedy', 'beam' or 'sample', got %r" % (decoding,))
         self.sampling = sampling.SamplingParams(float(temperature), int(top_k), float(top_p), int(seed)).check()
         self._job_streams = None                 # per-segment noise streams of the job in flight (None: the segment index)
+        self._job_draws = None                   # `sample` / `sample_many` in flight as one job: the draws of every segment
         if int(cap) < 0:
             raise ValueError("cap must not be negative, got %r" % (cap,))
         self.cap = int(cap)
@@ -316,11 +318,14 @@ class InferenceModel(object):
             if self.decoding == "sample" and self.model is not None:
                 self.model.clear_sampling()
 
-    def _set_masks(self, lo: int, hi: int):
-        """before an engine call on segments [lo, hi) of the job: their masks and prompts on the engine that will run it"""
+    def _set_masks(self, lo: int, hi: int, per: int = 0):
+        """before an engine call on segments [lo, hi) of the job: their masks and prompts on the engine that will run it.
+        per > 0 (Transformer.transcribe(draws=per)): the tables of the job's draws -- every segment's mask index, prompt
+        and stream `per` times in a row, and draw j of every segment under the seed (seed + j) mod 2^64."""
+        rep = max(int(per), 1)
         if self._job_masks is not None:
             masks, seg = self._job_masks
-            self.model.set_token_masks(masks, None if seg is None else seg[lo:hi])
+            self.model.set_token_masks(masks, None if seg is None else np.repeat(np.asarray(seg[lo:hi]), rep))
         if self._job_prompts is not None:
             rows, index = [], []
             for p in self._job_prompts[lo:hi]:
@@ -330,7 +335,7 @@ class InferenceModel(object):
                 if p not in rows:
                     rows.append(p)
                 index.append(rows.index(p))
-            self.model.set_prompts(rows, index if rows else None)
+            self.model.set_prompts(rows, list(np.repeat(np.asarray(index, np.int32), rep)) if rows else None)
         if isinstance(self._job_grammar, _lib.NoteGrammar):
             self.model.set_note_grammar(self._job_grammar)
         elif self._job_grammar is not None:
@@ -338,7 +343,11 @@ class InferenceModel(object):
         if self.decoding == "sample":
             # the stream of a segment is its index within its own file, whatever else the job or the engine call holds
             streams = self._job_streams[lo:hi] if self._job_streams is not None else np.arange(lo, hi)
-            self.model.set_sampling(self.sampling, np.asarray(streams, dtype=np.uint64))
+            streams = np.repeat(np.asarray(streams, dtype=np.uint64), rep)
+            seeds = None
+            if per:
+                seeds = np.tile(np.array([(self.sampling.seed + j) % (1 << 64) for j in range(rep)], dtype=np.uint64), hi - lo)
+            self.model.set_sampling(self.sampling, streams, seeds)
 
     # ------------------------------------------------------------------ model call
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
@@ -357,6 +366,13 @@ class InferenceModel(object):
         beam1 = self.decoding == "beam1"
         if self.decoding == "beam":
             return self._predict_ids_beam(x)
+        if self.schedule == "refill" and self.early_exit and self._job_draws:
+            # ONE engine call for all draws of the job's segments, each segment encoded once; row s * per + j = draw j
+            per, n = int(self._job_draws), int(x.shape[0])
+            self._ensure_slots(n * per)
+            self.rows_per_engine_call = [n * per]
+            self._set_masks(0, n, per)
+            return self.model.transcribe(x, draws=per)
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: finished rows restart on the job's next segments
             self._ensure_slots(x.shape[0])
@@ -471,14 +487,32 @@ class InferenceModel(object):
                                well_formed):
             return self._transcribe_examples(examples)
 
-    def sample(self, audio, num_samples: int = 1, sample_rate: int = SAMPLE_RATE, **kw):
-        """`num_samples` transcriptions of the same audio, drawn with seeds seed .. seed + num_samples - 1 of the model's
-        sampling parameters (decoding='sample' for the length of the call, whatever the model's own decoding is) -> a list
-        of NoteSequences.  kw: the keywords of `__call__` (programs, drums, prompts, well_formed)."""
+    def _draws_in_one_job(self, well_formed) -> bool:
+        """whether `sample` runs its draws as one engine job: the refill schedule, and not well_formed="tied" (whose
+        wavefront carries one tie chain per decode)"""
+        tied = isinstance(well_formed, str) and well_formed == "tied"
+        return self.schedule == "refill" and self.early_exit and not tied
+
+    def _check_sample(self, num_samples):
         if int(num_samples) < 1:
             raise ValueError("num_samples must be at least 1, got %r" % (num_samples,))
         if self.decoding == "beam":
             raise ValueError("sample() draws on the greedy path: not for a model with decoding='beam'")
+
+    def sample(self, audio, num_samples: int = 1, sample_rate: int = SAMPLE_RATE, **kw):
+        """`num_samples` transcriptions of the same audio, drawn with seeds seed .. seed + num_samples - 1 of the model's
+        sampling parameters (decoding='sample' for the length of the call, whatever the model's own decoding is) -> a list
+        of NoteSequences, sample j equal note for note to a model with seed + j called on the audio.  kw: the keywords of
+        `__call__` (programs, drums, prompts, well_formed).
+        The samples are ONE engine job (Transformer.transcribe(draws=num_samples)): the frontend and the encoder run once,
+        draw j of every segment decodes under the seed (seed + j) mod 2^64 in a slot of its own, and the engine is sized
+        to min(segments * num_samples, max_slots).  well_formed="tied" keeps a loop of num_samples decodes: its wavefront
+        carries one tie chain per decode (so does schedule='batch' / early_exit=False, which have no in-flight job)."""
+        self._check_sample(num_samples)
+        if self._draws_in_one_job(kw.get("well_formed", False)):
+            prompts = kw.pop("prompts", None)
+            return self._sample_files([functools.partial(self._examples, audio, sample_rate)], int(num_samples),
+                                      prompts=None if prompts is None else [prompts], **kw)[0]
         was = (self.decoding, self.sampling)
         out = []
         try:
@@ -488,6 +522,62 @@ class InferenceModel(object):
                 out.append(self(audio, sample_rate, **kw))
         finally:
             self.decoding, self.sampling = was
+        return out
+
+    def sample_many(self, audios: Sequence[Any], num_samples: int = 1, sample_rates: Optional[Sequence[int]] = None,
+                    **kw) -> List[List[Any]]:
+        """`sample` of several files as ONE job: one list of `num_samples` NoteSequences per file, each equal to
+        `sample(audio, num_samples)` of that file.  sample_rates and kw as for `transcribe_many` (programs / drums /
+        prompts: one entry per file where they differ).  well_formed="tied": num_samples `transcribe_many` jobs."""
+        self._check_sample(num_samples)
+        if sample_rates is None:
+            sample_rates = [SAMPLE_RATE] * len(audios)
+        if len(sample_rates) != len(audios):
+            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
+        if self._draws_in_one_job(kw.get("well_formed", False)):
+            return self._sample_files([functools.partial(self._examples, audio, sr)
+                                       for audio, sr in zip(audios, sample_rates)], int(num_samples), **kw)
+        was = (self.decoding, self.sampling)
+        runs = []
+        try:
+            self.decoding = "sample"
+            for i in range(int(num_samples)):
+                self.sampling = dataclasses.replace(was[1], seed=(was[1].seed + i) % (1 << 64))
+                runs.append(self.transcribe_many(audios, sample_rates, **kw))
+        finally:
+            self.decoding, self.sampling = was
+        return [[run[f] for run in runs] for f in range(len(audios))]
+
+    def _sample_files(self, make_examples, num_samples: int, programs=None, drums=True, prompts=None, well_formed=False):
+        """make_examples as for `_transcribe_files` -> per file the list of its `num_samples` sampled NoteSequences: all
+        draws of all segments through the engine as one job (row s * num_samples + j of the job = draw j of segment s)"""
+        per_file, feats, job_prompts = self._job_examples(make_examples, prompts)
+        if not per_file:
+            return []
+        was = self.decoding
+        self._job_streams = np.concatenate([np.arange(len(ex)) for ex in per_file])
+        self._job_draws = int(num_samples)
+        try:
+            self.decoding = "sample"
+            with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts,
+                                   well_formed):
+                tokens = self.predict_tokens({"encoder_input_tokens": feats})
+        finally:
+            self._job_streams = None
+            self._job_draws = None
+            self.decoding = was
+        out, at, results, n = [], 0, [], int(num_samples)
+        for examples in per_file:
+            draws = []
+            for j in range(n):
+                rows = tokens[at * n + j:(at + len(examples)) * n:n]
+                preds = [self.postprocess(t, ex) for t, ex in zip(rows, examples)]
+                results.append(metrics_utils.event_predictions_to_ns(preds, codec=self.codec,
+                                                                     encoding_spec=self.encoding_spec))
+                draws.append(results[-1]["est_ns"])
+            at += len(examples)
+            out.append(draws)
+        self._count_events(results)
         return out
 
     def consensus(self, audio, num_samples: int = 8, sample_rate: int = SAMPLE_RATE, *, tolerance: float = 0.05,
@@ -503,6 +593,15 @@ class InferenceModel(object):
         samples = self.sample(audio, num_samples, sample_rate, **kw)
         result = consensus.consensus([samples], tolerance=tolerance, min_votes=min_votes)[0]
         return (result.notes, result, samples) if return_votes else result.notes
+
+    def consensus_many(self, audios: Sequence[Any], num_samples: int = 8, sample_rates: Optional[Sequence[int]] = None, *,
+                       tolerance: float = 0.05, min_votes: Optional[int] = None, return_votes: bool = False, **kw):
+        """`consensus` of several files: `sample_many(audios, num_samples, sample_rates, **kw)` -- ONE engine job -- then one
+        vote per file, all in one `consensus.consensus` call.  -> per file what `consensus` returns for it."""
+        from . import consensus
+        samples = self.sample_many(audios, num_samples, sample_rates, **kw)
+        results = consensus.consensus(samples, tolerance=tolerance, min_votes=min_votes)
+        return [(r.notes, r, s) if return_votes else r.notes for r, s in zip(results, samples)]
 
     def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
@@ -857,9 +956,10 @@ class InferenceModel(object):
         from . import render
         return render.render([ns], sample_rate)[0]
 
-    def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None, well_formed=False):
-        """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
-        NoteSequence per file, all segments through the engine as one job"""
+    def _job_examples(self, make_examples, prompts):
+        """the files of a job: make_examples (one call per file that returns its examples and leaves its log-mel in
+        _logmel_dev) and `prompts` (None, or one `__call__`-style sequence or None per file) -> (examples per file, the
+        job's log-mel [segments, T, depth] on the device, the job's per-segment prompts or None)"""
         import torch
         per_file, feats = [], []
         for make in make_examples:
@@ -867,7 +967,7 @@ class InferenceModel(object):
             feats.append(self._logmel_dev)
         self._logmel_dev = None
         if not per_file:
-            return []
+            return [], None, None
         job_prompts = None
         if prompts is not None:
             if len(prompts) != len(per_file):
@@ -876,11 +976,19 @@ class InferenceModel(object):
             for p, ex in zip(prompts, per_file):
                 rows += self._segment_prompts(p, len(ex)) or [None] * len(ex)
             job_prompts = rows if any(r is not None for r in rows) else None
+        return per_file, torch.cat(feats, 0), job_prompts
+
+    def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None, well_formed=False):
+        """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
+        NoteSequence per file, all segments through the engine as one job"""
+        per_file, feats, job_prompts = self._job_examples(make_examples, prompts)
+        if not per_file:
+            return []
         self._job_streams = np.concatenate([np.arange(len(ex)) for ex in per_file])
         try:
             with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts,
                                    well_formed):
-                tokens = self.predict_tokens({"encoder_input_tokens": torch.cat(feats, 0)})
+                tokens = self.predict_tokens({"encoder_input_tokens": feats})
         finally:
             self._job_streams = None
         out, at, results = [], 0, []

@@ -267,7 +267,7 @@ class Transformer:
     def transcribe(self, encoder_input_tokens, num_steps: Optional[int] = None, beam1: bool = False,
                    use_graph: bool = True, single_stream: bool = False, debug_poll_steps: int = 0,
                    debug_row_groups: int = 0, debug_skip_encoder_passes: bool = False,
-                   num_beams: Optional[int] = None, return_all: bool = False):
+                   num_beams: Optional[int] = None, return_all: bool = False, draws: Optional[int] = None):
         """mt3_engine_transcribe: encode + decode of ANY number of segments through the engine's `max_batch` decode slots
         with in-flight batching -- a slot whose segment has finished restarts on the next one (the reference's loop over
         `.batch(8)` calls of predict_batch_with_aux, NB:295-301, without its batch-synchronous wait for the longest row).
@@ -276,7 +276,11 @@ class Transformer:
         num_beams = k (1 .. 8): mt3_engine_transcribe_beams -- the k-beam search of `decode_beams` with in-flight batching
         of max_batch // k elements of k slots each (each segment is passed once).  Returns the ids [N, L] of the best
         decode, or with `return_all` all k decodes [N, k, L] and their scores [N, k] in increasing order of score:
-        bit-identical to encode(x, num_beams=k) + decode_beams(k, early_exit=True) of each segment."""
+        bit-identical to encode(x, num_beams=k) + decode_beams(k, early_exit=True) of each segment.
+        draws = per (>= 1): mt3_engine_transcribe_draws -- `per` decodes of every segment in ONE job, each segment encoded
+        once.  Returns ids [N * per, L], row s * per + j = draw j of segment s; "segment i" of every per-segment table
+        (masks, prompts, sampling streams and seeds, the EOS schedule) means draw i.  Bit-identical to
+        transcribe(x.repeat_interleave(per, 0)) under the same tables.  Not with num_beams, beam1 or the debug_* schedule."""
         import torch
         x = encoder_input_tokens
         if x.dim() != 3 or x.shape[1] != self.input_length or x.shape[2] != self.config.input_depth:
@@ -287,8 +291,8 @@ class Transformer:
             k = int(num_beams)
             if k < 1 or k > min(_lib.MAX_BEAMS, self.max_batch):
                 raise ValueError(f"num_beams must be 1 .. {min(_lib.MAX_BEAMS, self.max_batch)}, got {num_beams}")
-            if beam1 or debug_poll_steps or debug_row_groups or debug_skip_encoder_passes:
-                raise ValueError("num_beams goes with neither beam1 nor the debug_* schedule parameters")
+            if beam1 or debug_poll_steps or debug_row_groups or debug_skip_encoder_passes or draws is not None:
+                raise ValueError("num_beams goes with neither beam1, draws nor the debug_* schedule parameters")
             ids = torch.empty((N, L), device="cuda", dtype=torch.int32)
             all_ids = torch.empty((N, k, L), device="cuda", dtype=torch.int32) if return_all else None
             scores = torch.empty((N, k), device="cuda", dtype=torch.float32) if return_all else None
@@ -306,6 +310,23 @@ class Transformer:
             return (all_ids, scores) if return_all else ids
         if return_all:
             raise ValueError("return_all needs num_beams")
+        if draws is not None:
+            per = int(draws)
+            if per < 1:
+                raise ValueError(f"draws must be at least 1, got {draws}")
+            if beam1 or debug_poll_steps or debug_row_groups or debug_skip_encoder_passes:
+                raise ValueError("draws goes with neither beam1 nor the debug_* schedule parameters")
+            ids = torch.empty((N * per, L), device="cuda", dtype=torch.int32)
+            flags = (0 if use_graph else _lib.DECODE_NO_GRAPH) | (_lib.DECODE_SINGLE_STREAM if single_stream else 0)
+            st = _lib.TranscribeStats()
+            _lib.check(self._lib.mt3_engine_transcribe_draws(self._h, x.data_ptr(), N, per, num_steps or L, flags,
+                                                             ids.data_ptr(), C.byref(st),
+                                                             torch.cuda.current_stream().cuda_stream))
+            self._batch = int(st.slots)
+            self.transcribe_stats = {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
+            self.last_transcribe_stats = self.transcribe_stats
+            self.steps_run = st.steps_run
+            return ids
         ids = torch.empty((N, L), device="cuda", dtype=torch.int32)
         flags = (0 if use_graph else _lib.DECODE_NO_GRAPH) | (_lib.DECODE_BEAM1 if beam1 else 0) | \
             (_lib.DECODE_SINGLE_STREAM if single_stream else 0)
@@ -437,21 +458,30 @@ class Transformer:
             held.data_ptr() if held is not None else None, torch.cuda.current_stream().cuda_stream))
         return (prompts, counts, held) if return_held else (prompts, counts)
 
-    def set_sampling(self, params=None, seg_stream=None, **kw):
+    def set_sampling(self, params=None, seg_stream=None, seg_seed=None, **kw):
         """mt3_engine_set_sampling: every later decode / transcribe call (greedy path; not beam1) DRAWS its free tokens --
         t5x temperature_sample -- until `clear_sampling`.  params: a `sampling.SamplingParams`, or its fields as keywords
         (temperature=1.0, top_k=0, top_p=0.0, seed=0).  seg_stream: the uint64 noise stream of each batch row / segment of
         the job (None: row / segment i draws from stream i); a segment's sample depends on (seed, stream) and its logits
-        only, not on the slot, the batch or the schedule.  top_k=1 is greedy.  decode_beams, transcribe(num_beams=...),
+        only, not on the slot, the batch or the schedule.  seg_seed (mt3_engine_set_sampling_seeds): the uint64 Philox key
+        of each batch row / segment / draw in place of params.seed (None: params.seed everywhere) -- what tells the draws
+        of one segment in `transcribe(draws=per)` apart.  The sampled step graphs hold whether there is a seed table: a
+        call that sets one after a call that set none (or the reverse) waits for the device and drops the captured step
+        graphs, so alternating the two forms costs a recapture at each switch.  top_k=1 is greedy.  decode_beams, transcribe(num_beams=...),
         decode_forced, score and score_segments ignore it."""
         from . import sampling
         p = (params if params is not None else sampling.SamplingParams(**kw)).check()
         st = p.struct()
         if seg_stream is None:
             _lib.check(self._lib.mt3_engine_set_sampling(self._h, C.byref(st), None, 0))
-            return
-        ss = np.ascontiguousarray(np.asarray(seg_stream).astype(np.uint64)).reshape(-1)
-        _lib.check(self._lib.mt3_engine_set_sampling(self._h, C.byref(st), ss.ctypes.data, int(ss.size)))
+        else:
+            ss = np.ascontiguousarray(np.asarray(seg_stream).astype(np.uint64)).reshape(-1)
+            _lib.check(self._lib.mt3_engine_set_sampling(self._h, C.byref(st), ss.ctypes.data, int(ss.size)))
+        if seg_seed is None:
+            _lib.check(self._lib.mt3_engine_set_sampling_seeds(self._h, None, 0))
+        else:
+            sd = np.ascontiguousarray(np.asarray(seg_seed).astype(np.uint64)).reshape(-1)
+            _lib.check(self._lib.mt3_engine_set_sampling_seeds(self._h, sd.ctypes.data, int(sd.size)))
 
     def clear_sampling(self):
         _lib.check(self._lib.mt3_engine_set_sampling(self._h, None, None, 0))

@@ -5,6 +5,7 @@ decodes with it.
   philox_bits(seed, stream, t, id)   word 0 of Philox4x32-10, key (seed lo, seed hi), counter (stream lo, stream hi, t, id)
   gumbel(bits)                       u = ((bits >> 9) + 0.5) * 2^-23 (exact in f32), g = -log(-log(u)) in float64
   pick(logits, t, stream, params)    one free pick, in float64 after the f32-exact u, with its decision margins
+                                     (seed=: the segment's own key where a per-segment seed table is set)
 
 The kernel computes z = x / temperature, z + g and the softmax masses in f32; `pick` computes them in float64 and reports
 how far every decision it took was from going the other way, so that a caller can compare ids only where the margin is
@@ -80,9 +81,11 @@ def gumbel(bits):
     return -np.log(-np.log(uniform(bits)))
 
 
-def pick(logits, t: int, stream: int, params: SamplingParams, allowed: Optional[np.ndarray] = None):
+def pick(logits, t: int, stream: int, params: SamplingParams, allowed: Optional[np.ndarray] = None,
+         seed: Optional[int] = None):
     """One free pick from a row of logits (as the token kernel reads them: after the row scale) at position t of the
-    segment with noise stream `stream`; allowed: bool [vocab], what the mask and the grammar leave (None: everything).
+    segment with noise stream `stream`; allowed: bool [vocab], what the mask and the grammar leave (None: everything);
+    seed: the segment's own Philox key (mt3_engine_set_sampling_seeds; None: params.seed).
     Returns (token id, margins):
       'pick'      gap between the best and the second best z + g of the kept set (inf: one candidate kept)
       'boundary'  top_k: gap in z between the last kept candidate and the first one left out (inf: nothing left out, or
@@ -118,7 +121,7 @@ def pick(logits, t: int, stream: int, params: SamplingParams, allowed: Optional[
         margins["mass"] = float(min(near))
     ids, z = ids[:keep], z[:keep]
     margins["kept"] = ids
-    s = z + gumbel(philox_bits(params.seed, stream, t, ids))
+    s = z + gumbel(philox_bits(params.seed if seed is None else seed, stream, t, ids))
     best = np.lexsort((ids, -s))                           # larger first, lower id on ties
     if keep > 1:
         margins["pick"] = float(s[best[0]] - s[best[1]])

@@ -39,11 +39,12 @@ of jump between neighbouring segments) and writes the moved notes as NAME.aligne
 alignment.json into the output directory: a list with one record per input, in input order -- "audio", "segment_shifts",
 "path_score", "flat_shift", "flat_score" (same one-directory rule as --score-against).
 --consensus N writes as NAME.mid the notes that N sampled transcriptions of the input agree on
-(`InferenceModel.consensus`: N draws with the sampling parameters of --temperature / --top-k / --top-p and seeds --seed ..
---seed + N - 1, voted on the device; a note is kept when --consensus-min-votes of them have it, default a strict
-majority; onsets within --consensus-tolerance seconds, default 0.05, are one note), and NAME.votes.json beside it:
+(`InferenceModel.consensus_many`: N draws with the sampling parameters of --temperature / --top-k / --top-p and seeds
+--seed .. --seed + N - 1, all input files and all their draws as ONE engine job in which every segment is encoded once,
+voted on the device; a note is kept when --consensus-min-votes of them have it, default a strict majority; onsets within
+--consensus-tolerance seconds, default 0.05, are one note), and NAME.votes.json beside it:
 {"n_voters": N, "min_votes": M, "notes": [...]}, one record per note of NAME.mid in the NoteSequence's order with its
-start_time, end_time, pitch, program, is_drum, votes and members.  Each input is a job of its own (N decodes).  Not with
+start_time, end_time, pitch, program, is_drum, votes and members.  (--well-formed-tied keeps N decodes per job.)  Not with
 --decoding beam, and not together with --confidences.
 """
 from __future__ import annotations
@@ -228,12 +229,12 @@ def main(argv=None) -> int:
         votes = None
         if args.consensus is not None:
             from . import audio_io
-            voted = []
-            for path in args.inputs:
-                samples, rate = audio_io.read_wav(path)
-                voted.append(model.consensus(samples, args.consensus, rate, tolerance=args.consensus_tolerance,
-                                             min_votes=args.consensus_min_votes, return_votes=True,
-                                             programs=args.programs, drums=args.drums, well_formed=args.well_formed))
+            # every input file's N draws as ONE engine job (well_formed="tied" keeps its loop of N decodes)
+            decoded = [audio_io.read_wav(path) for path in args.inputs]
+            voted = model.consensus_many([s for s, _ in decoded], args.consensus, [r for _, r in decoded],
+                                         tolerance=args.consensus_tolerance, min_votes=args.consensus_min_votes,
+                                         return_votes=True, programs=args.programs, drums=args.drums,
+                                         well_formed=args.well_formed)
             sequences, scores, votes = [ns for ns, _, _ in voted], None, [rec for _, rec, _ in voted]
         elif args.confidences:
             scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums,
