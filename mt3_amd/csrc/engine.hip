@@ -1592,7 +1592,7 @@ static int row_groups_for(const mt3_engine_config& c, int batch, bool early_exit
   return batch >= 128 ? 2 : 1;
 }
 
-// Row groups of a streaming job (mt3_engine_transcribe, mt3_engine_transcribe_beams) over `units` units of `unit` slots:
+// Row groups of a streaming job (mt3_engine_transcribe, _transcribe_beams, _transcribe_draws) over `units` units of `unit` slots:
 // in-flight batching keeps every group's rows full, so the rule of the canonical full-length schedule applies, not the
 // ragged one's; a group holds whole units and at least 16 slots (groups_override > 0: mt3_debug_engine_transcribe's choice)
 static int stream_groups_for(const mt3_engine_config& c, int flags, int units, int unit, int groups_override) {
@@ -1875,7 +1875,8 @@ using mt3feed::feed_pop;
 using mt3feed::feed_release;
 using mt3feed::feed_wait;
 
-// ---- the scaffold every row-group job shares (mt3_engine_decode, _decode_beams, _transcribe, _transcribe_beams)
+// ---- the scaffold every row-group job shares (mt3_engine_decode, _decode_beams, _transcribe, _transcribe_beams,
+// _transcribe_draws)
 // A job deals `units` units of `unit` slots each to `groups` row groups: greedy and beam-1 jobs have unit = 1, k-beam jobs
 // unit = k, so that every group boundary is an element boundary.
 struct GroupJob {
@@ -1885,6 +1886,20 @@ struct GroupJob {
   hipStream_t s;              // the caller's stream
   float* d_first_logits;      // (GroupRun: the caller's-stream schedule only)
   float* d_step_logits;
+};
+
+// What tells the three streaming entry points apart (run_stream_job; the k-beam job is the one whose variant has kVarBeams)
+struct StreamJob {
+  const char* who;            // the entry point's name
+  int unit;                   // slots per element: k in the beam job, else 1
+  int per;                    // feed entries per encoded segment: the draws of each in mt3_engine_transcribe_draws, else 1
+  bool from_ring;             // every entry, the first ones included, reaches its slots through the staging ring: the groups
+                              // start with every slot finished and empty (false: the first ones sit in the caches already)
+  int32_t* d_ids;             // the caller's outputs, rows by feed entry ...
+  int32_t* d_all_ids;         // ... and what only the beam job has (each may be nullptr)
+  float* d_scores;
+  int poll;                   // steps between refill polls
+  bool skip_encoder;          // mt3_debug_engine_transcribe's differential timing (produce_chunks)
 };
 
 // Starts a job: the step-graph cache is trimmed (no worker is running here) and e->pending is the job's
@@ -1950,20 +1965,34 @@ static bool post_groups(mt3_engine* e, const GroupJob& j, const GroupLoop& loop,
   return true;
 }
 
-// Joins the decode that is in flight: waits for its workers, then (on the caller's stream) the beam-1 finalisation
-// and the copy of the ids.  Every group thread has waited for its stream, so the caller's stream needs no event.
-static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
+// Joins the job in flight, entry point `who`'s: waits for its workers and folds what the groups left in e->pending into one
+// outcome -- the first failed group's error, *most = the steps of the group that ran longest, and the engine's record of
+// the most recent job (compactions, last_groups, last_used_graph)
+static int join_groups(mt3_engine* e, const std::string& who, int* most) {
   PendingDecode& p = e->pending;
-  if (!p.active) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_wait: no decode in flight");
   for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
   p.active = false;
   e->compactions = e->compactions_now.exchange(0);
-  int most = 0;
+  e->last_groups = p.groups;
+  e->last_used_graph = 1;
+  *most = 0;
+  int rc = MT3_OK;
   for (int g = 0; g < p.groups; ++g) {
-    if (p.rcs[g] != MT3_OK)
-      return mt3::fail(p.rcs[g], "mt3_engine_decode (row group " + std::to_string(g) + "): " + p.errs[g]);
-    most = p.ran[g] > most ? p.ran[g] : most;
+    if (rc == MT3_OK && p.rcs[g] != MT3_OK)
+      rc = mt3::fail(p.rcs[g], who + " (row group " + std::to_string(g) + "): " + p.errs[g]);
+    *most = p.ran[g] > *most ? p.ran[g] : *most;
+    if (!p.used_graph[g]) e->last_used_graph = 0;
   }
+  return rc;
+}
+
+// Joins the decode that is in flight, then (on the caller's stream) the beam-1 finalisation and the copy of the ids.
+// Every group thread has waited for its stream, so the caller's stream needs no event.
+static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
+  PendingDecode& p = e->pending;
+  if (!p.active) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_wait: no decode in flight");
+  int most = 0;
+  MT3_TRY(join_groups(e, "mt3_engine_decode", &most));
   const int L = e->cfg.max_decode_len;
   if (p.beams) {
     // k-beam search: the results are walked back from the history straight into the caller's buffers
@@ -1974,21 +2003,17 @@ static int decode_finish(mt3_engine* e, int32_t* h_steps_run) {
     if (p.beam1) MT3_TRY(mt3k::launch_beam1_finalize(e->ids, L, e->beam_len_row, p.batch, p.s));
     MT3_HIP_CHECK(hipMemcpyAsync(p.d_ids, e->ids, static_cast<size_t>(p.batch) * L * 4, hipMemcpyDeviceToDevice, p.s));
   }
-  e->last_groups = p.groups;
-  e->last_used_graph = 1;
-  for (int g = 0; g < p.groups; ++g)
-    if (!p.used_graph[g]) e->last_used_graph = 0;
   if (h_steps_run) *h_steps_run = most;
   return MT3_OK;
 }
 
 // ---- the start of a job, on the caller's stream
-// Position 0 and BOS (= 0) for slots [0, n); `counters`: nothing finished (done flags, the groups' counters of finished
-// slots), `ids`: zeroed id rows -- mt3_engine_transcribe_beams starts every slot FINISHED (launch_beam_stream_init) and
-// the k-beam jobs keep their ids in the history
 // the grammar state a slot starts in at position 0 (no grammar set: 0, which nothing reads)
 static int grammar_initial(const mt3_engine* e) { return e->gr.on ? mt3g_initial(&e->gr.g) : 0; }
 
+// Position 0 and BOS (= 0) for slots [0, n); `counters`: nothing finished (done flags, the groups' counters of finished
+// slots), `ids`: zeroed id rows -- the jobs that start from the ring start every slot FINISHED (start_empty) and the
+// k-beam jobs keep their ids in the history
 static int reset_slots(mt3_engine* e, int n, bool counters, bool ids, hipStream_t s) {
   MT3_HIP_CHECK(hipMemsetAsync(e->step, 0, static_cast<size_t>(n) * 4, s));
   if (counters) MT3_HIP_CHECK(hipMemsetAsync(e->n_done, 0, 4 * kMaxChains, s));
@@ -2065,28 +2090,90 @@ static int sampling_fits(const mt3_engine* e, const char* who, int n, bool beam1
   return MT3_OK;
 }
 
+// ---- the preconditions the job entry points share, each refused as MT3_ERR_INVALID in the name of the entry point `who`
+static int invalid(const char* who, const char* what) { return mt3::fail(MT3_ERR_INVALID, std::string(who) + ": " + what); }
+
+// ready: finalized, and no job in flight
+static int engine_ready(const mt3_engine* e, const char* who) {
+  if (!e || !e->finalized) return invalid(who, "engine not finalized");
+  if (e->pending.active) return invalid(who, "a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
+  return MT3_OK;
+}
+
+static int steps_fit(const mt3_engine* e, const char* who, int num_steps) {
+  if (num_steps <= 0 || num_steps > e->cfg.max_decode_len) return invalid(who, "num_steps out of range");
+  return MT3_OK;
+}
+
+// what the beam step takes: 1 .. 8 beams that fit the engine, 2k candidates in a vocabulary of at most 2048 ids, and no
+// more layers than a cache-row copy holds
+static int beams_fit(const mt3_engine* e, const char* who, int k) {
+  const mt3_engine_config& c = e->cfg;
+  if (k < 1 || k > mt3k::kBeamMaxK) return invalid(who, "num_beams must be 1 .. 8");
+  if (k > c.max_batch) return invalid(who, "num_beams exceeds max_batch");
+  if (c.vocab_size > 2048 || c.vocab_size < 2 * k) return invalid(who, "the beam step needs 2 * num_beams <= vocab <= 2048");
+  if (c.num_decoder_layers > mt3k::kRefillMaxLayers) return invalid(who, "more than 16 decoder layers");
+  return MT3_OK;
+}
+
+// what a greedy-path streaming job of n feed entries takes: no more layers than a refill holds, and a synthetic EOS
+// schedule (where one is set) with an entry for each
+static int stream_fits(const mt3_engine* e, const char* who, int n) {
+  if (e->cfg.num_decoder_layers > mt3k::kRefillMaxLayers) return invalid(who, "at most 16 decoder layers");
+  if (e->eos_on && n > e->eos_cap) return invalid(who, "the synthetic EOS schedule is shorter than the job");
+  return MT3_OK;
+}
+
+// The ending the two decodes share, for job j -- one group so far, its slots started on j.s.  Row groups on streams of
+// their own where the slots, the flags and the engine's options allow it (caller_stream_only: the call needs what lives on
+// the caller's stream), each group a whole number of units; else the one group on the caller's stream, on the calling
+// thread -- or with MT3_DECODE_ASYNC on worker 0, if there is one to be had.  Then the job is joined (decode_finish), or
+// with MT3_DECODE_ASYNC left to mt3_engine_decode_wait.
+static int run_decode_job(mt3_engine* e, GroupJob j, int flags, bool caller_stream_only, int32_t* h_steps_run) {
+  const mt3_engine_config& c = e->cfg;
+  const bool async = (flags & MT3_DECODE_ASYNC) != 0;
+  const GroupLoop loop = [e](GroupRun& r) { return run_group(e, r); };
+  int groups = row_groups_for(c, j.units * j.unit, j.early);
+  if (groups > j.units) groups = 1;
+  if (groups > 1 && !caller_stream_only && !(flags & MT3_DECODE_SINGLE_STREAM) && c.decode_chains <= 1 &&
+      !(c.options & MT3_OPT_NO_ROW_GROUPS)) {
+    if (ensure_group_streams(e, groups) == MT3_OK) {
+      MT3_HIP_CHECK(hipEventRecord(e->part_begin, j.s));
+      j.groups = groups;
+      j.own_streams = true;
+    } else {
+      ++e->part_failed;                           // the masked streams could not be created: single stream, recorded
+    }
+  }
+  if (j.own_streams || async) {
+    post_groups(e, j, loop, nullptr);
+  } else {
+    e->pending.active = true;
+    run_one_group(e, j, 0, loop);
+  }
+  return async ? MT3_OK : decode_finish(e, h_steps_run);
+}
+
 // shared body of mt3_engine_decode / mt3_engine_decode_forced
 static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t debug_skip,
                        const int32_t* d_forced, float* d_step_logits, int32_t* d_ids, float* d_first_logits,
                        int32_t* h_steps_run, void* stream) {
-  if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode: engine not finalized");
-  if (e->pending.active)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
-  if (batch <= 0 || batch != e->cur_batch)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode: batch must equal the batch of the preceding encode");
+  const char* who = "mt3_engine_decode";
+  MT3_TRY(engine_ready(e, who));
+  if (batch <= 0 || batch != e->cur_batch) return invalid(who, "batch must equal the batch of the preceding encode");
   const mt3_engine_config& c = e->cfg;
-  if (num_steps <= 0 || num_steps > c.max_decode_len || !d_ids)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode: num_steps out of range or null ids");
+  MT3_TRY(steps_fit(e, who, num_steps));
+  if (!d_ids) return invalid(who, "null ids");
   if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_EARLY_EXIT | MT3_DECODE_BEAM1 | MT3_DECODE_SINGLE_STREAM |
                 MT3_DECODE_ASYNC | MT3_DECODE_CHAINS(0xF)))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode: unknown flag bit");
+    return invalid(who, "unknown flag bit");
   const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0, early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
   const bool async = (flags & MT3_DECODE_ASYNC) != 0;
   if (d_forced && (beam1 || early || async))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_forced: not combinable with BEAM1 / EARLY_EXIT / ASYNC");
+    return invalid("mt3_engine_decode_forced", "not combinable with BEAM1 / EARLY_EXIT / ASYNC");
   int seg_var = 0;                                       // teacher forcing ignores token masks and prompts
-  if (!d_forced) MT3_TRY(seg_tables_fit(e, "mt3_engine_decode", batch, 2, num_steps, &seg_var));
-  if (!d_forced) MT3_TRY(sampling_fits(e, "mt3_engine_decode", batch, beam1, &seg_var));
+  if (!d_forced) MT3_TRY(seg_tables_fit(e, who, batch, 2, num_steps, &seg_var));
+  if (!d_forced) MT3_TRY(sampling_fits(e, who, batch, beam1, &seg_var));
   hipStream_t s = static_cast<hipStream_t>(stream);
   MT3_TRY(reset_slots(e, batch, true, true, s));
   if (d_forced)    // engine-owned copy: the step graph holds ITS address, whatever buffer the caller passes
@@ -2110,25 +2197,8 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   p.s = s;
   const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
   const int req_chains = (flags >> 8) & 0xF;
-  GroupJob j{batch, 1, 1, variant, num_steps, early, use_graph, false, s, d_first_logits, d_step_logits};
-  const GroupLoop loop = [e](GroupRun& r) { return run_group(e, r); };
-
-  // ---- the row-group schedule (see mt3_engine::part_stream): batches of >= 128 rows, unless the caller asked for
-  // one stream / graph chains, or wants per-step logits (those live on the caller's stream)
-  int groups = row_groups_for(c, batch, early);
-  if (groups > 1 && !(flags & MT3_DECODE_SINGLE_STREAM) && req_chains == 0 && e->cfg.decode_chains <= 1 &&
-      !(c.options & MT3_OPT_NO_ROW_GROUPS) && debug_skip == 0 && !d_forced && !d_step_logits && !d_first_logits) {
-    if (ensure_group_streams(e, groups) == MT3_OK) {
-      MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-      j.groups = groups;
-      j.own_streams = true;
-      post_groups(e, j, loop, nullptr);
-      if (async) return MT3_OK;
-      return decode_finish(e, h_steps_run);
-    }
-    ++e->part_failed;                             // the masked streams could not be created: single stream, recorded
-  }
-  p.groups = 1;
+  const GroupJob j{batch, 1, 1, variant, num_steps, early, use_graph, false, s, d_first_logits, d_step_logits};
+  // (graph chains come from the flags or the engine's decode_chains, and either keeps the job off the row groups)
   const int chains = chains_for(e, batch, req_chains);
   if (chains > 1) {
     // the step graph with `chains` parallel branches (r1's schedule, kept for comparison): inline on the caller's stream
@@ -2160,14 +2230,10 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
     if (async) return MT3_OK;
     return decode_finish(e, h_steps_run);
   }
-  // one group = the whole batch, on the caller's stream (MT3_DECODE_ASYNC: driven by worker 0, if there is one to be had)
-  if (async) {
-    post_groups(e, j, loop, nullptr);
-    return MT3_OK;
-  }
-  p.active = true;
-  run_one_group(e, j, 0, loop);
-  return decode_finish(e, h_steps_run);
+  // the row-group schedule (see mt3_engine::part_stream) unless the caller asked for graph chains, or for what lives on
+  // the caller's stream: skipped kernels, teacher forcing, logits
+  return run_decode_job(e, j, flags, req_chains != 0 || debug_skip != 0 || d_forced || d_step_logits || d_first_logits,
+                        h_steps_run);
 }
 
 // ----------------------------------------------------------------------------------------------- k-beam search
@@ -2189,37 +2255,39 @@ static int ensure_beam_state(mt3_engine* e) {
   return dmalloc(e, reinterpret_cast<void**>(&e->bk_live), Bm * 4);     // last: it marks the set as complete
 }
 
-static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t num_steps, int32_t flags, int32_t* d_ids,
-                             int32_t* d_all_ids, float* d_scores, int32_t* h_steps_run, hipStream_t s) {
-  if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: engine not finalized");
-  if (e->pending.active)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
-  const mt3_engine_config& c = e->cfg;
-  if (k < 1 || k > mt3k::kBeamMaxK) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: num_beams must be 1 .. 8");
-  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_EARLY_EXIT | MT3_DECODE_SINGLE_STREAM))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: flags other than NO_GRAPH / EARLY_EXIT / SINGLE_STREAM");
-  if (batch <= 0 || static_cast<int64_t>(batch) * k > c.max_batch)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: batch * num_beams must be 1 .. max_batch");
-  if (batch * k != e->cur_batch)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: the preceding encode must hold each of the batch's "
-                                      "segments num_beams times in a row (batch * num_beams rows)");
-  if (num_steps <= 0 || num_steps > c.max_decode_len || !d_ids)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: num_steps out of range or null ids");
-  if (c.vocab_size > 2048 || c.vocab_size < 2 * k)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: the beam step needs 2 * num_beams <= vocab <= 2048");
-  if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_decode_beams: more than 16 decoder layers");
-  int seg_var = 0;
-  MT3_TRY(seg_tables_fit(e, "mt3_engine_decode_beams", batch, 2 * k, num_steps, &seg_var));
+// The start the two k-beam entry points share, on stream s: the beam state allocated, `slots` slots at position 0 on BOS
+// (`counters`: as reset_slots) with no fork counted yet, then the entry point's own `init` of its beams, then the loop
+// bound (the brevity penalty of num_steps + 1, as reset_beam1_state)
+static int start_beams(mt3_engine* e, int slots, bool counters, int num_steps, hipStream_t s, const std::function<int()>& init) {
   MT3_TRY(ensure_beam_state(e));
-  const int slots = batch * k;
-  const bool early = (flags & MT3_DECODE_EARLY_EXIT) != 0;
-  MT3_TRY(reset_slots(e, slots, true, false, s));
+  MT3_TRY(reset_slots(e, slots, counters, false, s));
   MT3_HIP_CHECK(hipMemsetAsync(e->bk_forks, 0, 4, s));
   MT3_TRY(embed_bos(e, slots, s));
-  MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
-  MT3_TRY(mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s));
-  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
+  MT3_TRY(init());
+  return mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s);
+}
+
+static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t num_steps, int32_t flags, int32_t* d_ids,
+                             int32_t* d_all_ids, float* d_scores, int32_t* h_steps_run, hipStream_t s) {
+  const char* who = "mt3_engine_decode_beams";
+  MT3_TRY(engine_ready(e, who));
+  MT3_TRY(beams_fit(e, who, k));
+  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_EARLY_EXIT | MT3_DECODE_SINGLE_STREAM))
+    return invalid(who, "flags other than NO_GRAPH / EARLY_EXIT / SINGLE_STREAM");
+  if (batch <= 0 || static_cast<int64_t>(batch) * k > e->cfg.max_batch)
+    return invalid(who, "batch * num_beams must be 1 .. max_batch");
+  if (batch * k != e->cur_batch)
+    return invalid(who, "the preceding encode must hold each of the batch's segments num_beams times in a row "
+                        "(batch * num_beams rows)");
+  MT3_TRY(steps_fit(e, who, num_steps));
+  if (!d_ids) return invalid(who, "null ids");
+  int seg_var = 0;
+  MT3_TRY(seg_tables_fit(e, who, batch, 2 * k, num_steps, &seg_var));
+  const int slots = batch * k;
+  MT3_TRY(start_beams(e, slots, true, num_steps, s, [&] {
+    MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
+    return mt3k::launch_beam_init(e->bk_live, e->bk_fin_score, e->bk_fin_step, e->bk_fin_beam, slots, k, s);
+  }));
   const int variant = kVarRetire | kVarBeams | (k << kVarBeamsShift) | seg_var;
   PendingDecode& p = begin_job(e);
   p.beams = k;
@@ -2229,35 +2297,18 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   p.d_all_ids = d_all_ids;
   p.d_scores = d_scores;
   p.s = s;
-  GroupJob j{batch, k, 1, variant, num_steps, early, !(flags & MT3_DECODE_NO_GRAPH), false, s, nullptr, nullptr};
-  const GroupLoop loop = [e](GroupRun& r) { return run_group(e, r); };
-  // the row-group rule of mt3_engine_decode on batch * k slots (a group holds whole elements)
-  int groups = row_groups_for(c, slots, early);
-  if (groups > batch) groups = 1;
-  if (groups > 1 && !(flags & MT3_DECODE_SINGLE_STREAM) && c.decode_chains <= 1 && !(c.options & MT3_OPT_NO_ROW_GROUPS)) {
-    if (ensure_group_streams(e, groups) == MT3_OK) {
-      MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-      j.groups = groups;
-      j.own_streams = true;
-    } else {
-      ++e->part_failed;
-    }
-  }
-  if (j.own_streams) {
-    post_groups(e, j, loop, nullptr);
-  } else {            // one group = every slot, on the caller's stream and the calling thread
-    p.active = true;
-    run_one_group(e, j, 0, loop);
-  }
-  MT3_TRY(decode_finish(e, h_steps_run));
+  const GroupJob j{batch, k, 1, variant, num_steps, (flags & MT3_DECODE_EARLY_EXIT) != 0, !(flags & MT3_DECODE_NO_GRAPH), false,
+                   s, nullptr, nullptr};
+  MT3_TRY(run_decode_job(e, j, flags, false, h_steps_run));
   MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));    // complete on return: the fork count is in host memory
   return MT3_OK;
 }
 
 // ------------------------------------------------------------------------------------------- in-flight batching
-// mt3_engine_transcribe, mt3_engine_transcribe_beams (mt3_hip.h): the engine's max_batch decode slots stay full while
-// there are segments left.  The queue between the encoder passes (producer: the calling thread, produce_chunks) and the
-// row groups (consumers: run_group_stream) is csrc/feed.h; run_stream_job runs the two sides of one job.
+// mt3_engine_transcribe, _transcribe_beams, _transcribe_draws (mt3_hip.h): the engine's max_batch decode slots stay full
+// while there are segments left.  The queue between the encoder passes (producer: the calling thread, produce_chunks) and
+// the row groups (consumers: run_group_stream) is csrc/feed.h; run_stream_job runs the two sides of one job, and
+// stream_call is the body the three entry points share behind their argument checks.
 static int ensure_stage(mt3_engine* e) {
   if (e->stage_cap) return MT3_OK;
   const mt3_engine_config& c = e->cfg;
@@ -2288,7 +2339,7 @@ static float2* stage_chunk_scale(const mt3_engine* e, int l, int chunk) {
 
 // the staged run `rg` (sequence number -> ring chunk) and the caches of a `dst_batch`-row decode it is copied into
 // (per > 1, mt3_engine_transcribe_draws: the run counts draws, `per` of which share one staged entry)
-static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_batch, mt3k::StagedCross* x, int per = 1) {
+static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_batch, mt3k::StagedCross* x, int per) {
   const mt3_engine_config& c = e->cfg;
   x->n_layers = c.num_decoder_layers;
   x->row_bytes = static_cast<size_t>(c.num_heads) * c.input_length * 64 * e->kv_esize;
@@ -2307,7 +2358,7 @@ static void fill_staged_cross(const mt3_engine* e, const FeedRange& rg, int dst_
 
 // the refill launches of one run of staged segments for row group `r` (rg == nullptr: finished slots only hand their
 // ids over -- the queue is empty)
-static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRange* rg, int32_t* d_out, int per) {
+static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRange* rg, const StreamJob& sj) {
   const mt3_engine_config& c = e->cfg;
   const size_t r0 = static_cast<size_t>(r.row0);
   mt3k::RefillArgs a{};
@@ -2316,58 +2367,51 @@ static int refill_group(mt3_engine* e, const GroupRun& r, int cur, const FeedRan
   if (r.variant & kVarBeam) a.beam = beam1_state(e, r.row0, 0);
   a.ids = e->ids;
   a.ids_stride = c.max_decode_len;
-  a.out_ids = d_out;
+  a.out_ids = sj.d_ids;
   a.plan = e->refill_plan + r0 + r.slot;
   a.rows = cur;
   a.gram0 = grammar_initial(e);
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
-    fill_staged_cross(e, *rg, r.batch, &a.x, per);
+    fill_staged_cross(e, *rg, r.batch, &a.x, sj.per);
   }
   return mt3k::launch_refill(a, r.s);
 }
 
-// where the decodes of mt3_engine_transcribe_beams go (the caller's buffers, rows by segment)
-struct BeamOut {
-  int k;
-  int32_t* all_ids;
-  float* scores;
-};
-
-// the beam counterpart of refill_group: finished ELEMENTS of row group `r` hand their k decodes over and restart on the
-// run `rg` of staged segments (rg == nullptr: hand-over only)
-static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* rg, int32_t* d_out, const BeamOut& bo) {
+// the beam counterpart of refill_group: finished ELEMENTS of row group `r` hand their k decodes over (the caller's
+// buffers, rows by segment) and restart on the run `rg` of staged segments (rg == nullptr: hand-over only)
+static int refill_beam_group(mt3_engine* e, const GroupRun& r, const FeedRange* rg, const StreamJob& sj) {
   const mt3_engine_config& c = e->cfg;
   mt3k::BeamRefillArgs a{};
-  a.b = beam_args(e, r.row0, r.rows, bo.k, r.slot);
+  a.b = beam_args(e, r.row0, r.rows, sj.unit, r.slot);
   a.plan = e->refill_plan + r.row0 + r.slot;
   a.L = c.max_decode_len;
   a.num_steps = r.num_steps;
-  a.out_ids = d_out;
-  a.out_all = bo.all_ids;
-  a.out_scores = bo.scores;
+  a.out_ids = sj.d_ids;
+  a.out_all = sj.d_all_ids;
+  a.out_scores = sj.d_scores;
   a.gram0 = grammar_initial(e);
   if (rg) {
     a.n_new = rg->n;
     a.first_seg = rg->first_seg;
-    fill_staged_cross(e, *rg, r.batch, &a.x);
+    fill_staged_cross(e, *rg, r.batch, &a.x, sj.per);
   }
   return mt3k::launch_beam_refill(a, r.s);
 }
 
 // One row group's loop of mt3_engine_transcribe: as run_group, but a finished slot restarts on the next staged segment
 // at the poll, and the loop ends when the queue is empty for good and every slot of the group has finished.
-// bo != nullptr (mt3_engine_transcribe_beams): the unit of refill is an ELEMENT of bo->k slots -- the snapshot, the
-// watchdog and `refillable` count slots, the feed counts segments = elements -- the group starts with every element
-// finished and takes its first segments off the feed before its first step, and it is never compacted.
-// draws_per > 0 (mt3_engine_transcribe_draws): the greedy path on a feed that counts DRAWS, draws_per of which share one
-// staged entry; as in the beam job the group starts with every slot finished and empty.
-static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out, int kPoll, const BeamOut* bo = nullptr,
-                            int draws_per = 0) {
-  const int unit = bo ? bo->k : 1;
+// The beam job (mt3_engine_transcribe_beams): the unit of refill is an ELEMENT of sj.unit slots -- the snapshot, the
+// watchdog and `refillable` count slots, the feed counts segments = elements -- and the group is never compacted.
+// sj.from_ring (the beam job and mt3_engine_transcribe_draws, whose feed counts DRAWS, sj.per of which share one staged
+// entry): the group starts with every slot finished and empty and takes its first entries off the feed before its first
+// step.
+static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, const StreamJob& sj) {
+  const bool beams = (r.variant & kVarBeams) != 0;
+  const int unit = sj.unit, kPoll = sj.poll;
   auto refill = [&](int cur_rows, const FeedRange* rg) {
-    return bo ? refill_beam_group(e, r, rg, d_out, *bo) : refill_group(e, r, cur_rows, rg, d_out, draws_per ? draws_per : 1);
+    return beams ? refill_beam_group(e, r, rg, sj) : refill_group(e, r, cur_rows, rg, sj);
   };
   int cur = r.rows;
   hipGraphExec_t exec = nullptr;
@@ -2392,7 +2436,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
   const long stall_limit = static_cast<long>(r.num_steps) + 4L * kPoll + 64;
   long last_progress = 0;
   int seen_fin = 0;
-  if (bo || draws_per) {
+  if (sj.from_ring) {
     // every element is finished and empty: the first refill comes before the first step interval
     int n_fin = r.rows;
     bool dry = false;
@@ -2451,7 +2495,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
         const int live = r.rows - n_fin;
         int want = (live + 31) & ~31;
         if (want > r.rows) want = r.rows;
-        const bool compact = !bo && live > 0 && want < cur;    // beam groups stay where they are (run_group)
+        const bool compact = !beams && live > 0 && want < cur;    // beam groups stay where they are (run_group)
         // (the hand-over runs on the device's own done flags, directly in front of a compaction or of the exit: no slot
         // that finished after the snapshot can be dropped with its ids still in the engine)
         if ((n_fin - (r.rows - cur) > 0 && n_fin != flushed_at) || compact || live <= 0) {
@@ -2481,11 +2525,12 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, int32_t* d_out,
   return MT3_OK;
 }
 
-// the producer side of the feed (calling thread, caller's stream).  per > 1 (mt3_engine_transcribe_draws): the feed counts
+// the producer side of the feed (calling thread, caller's stream).  sj.per > 1 (mt3_engine_transcribe_draws): the feed counts
 // draws, `per` of every segment: a claim is one of up to stage_cap * per draws, so that `first`, `n` and `pad` are multiples
 // of `per` and the pass encodes the (pad + n) / per segments from (first - pad) / per on, each ONCE.
-static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStream_t s, bool skip_encoder, int per = 1) {
+static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStream_t s, const StreamJob& sj) {
   const mt3_engine_config& c = e->cfg;
+  const int per = sj.per;
   const size_t seg_floats = static_cast<size_t>(c.input_length) * c.input_depth;
   const int min_batch = e->stage_cap < kStageMinBatch ? e->stage_cap : kStageMinBatch;
   std::vector<void*> kv(c.num_decoder_layers);
@@ -2507,7 +2552,7 @@ static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStre
     dst.scale = e->kv_fp8 ? sc.data() : nullptr;
     // (skip_encoder: mt3_debug_engine_transcribe's differential timing -- the chunk goes on offer with whatever the staging
     // ring holds; under an imposed EOS schedule the decode does exactly the same work)
-    if (!skip_encoder)
+    if (!sj.skip_encoder)
       rc = encode_impl(e, d_inputs + static_cast<size_t>((first - pad) / per) * seg_floats, (pad + n) / per, nullptr, dst, s);
     if (rc == MT3_OK && wait_stream(e, kMaxGroups, s) != hipSuccess) rc = mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe: encoder pass failed");
     if (rc != MT3_OK) break;
@@ -2517,115 +2562,152 @@ static int produce_chunks(mt3_engine* e, Feed& f, const float* d_inputs, hipStre
   return rc;
 }
 
-// what a streaming job did: the longest group's steps and the feed's counters
-struct StreamCounts {
-  int most, polls, refills, starved, produced;
-};
-
-// The streaming job j of entry point `who`, from its posting to its end: the row groups run run_group_stream on their
-// workers while the calling thread encodes segments [next_seg, n_segments) into the staging ring (segments below next_seg
-// sit in the caches already); then the groups' outcomes are folded into one.  The device-side start of the slots is the
-// entry point's, enqueued on j.s before this and closed with part_begin.
-// draws_per > 0 (mt3_engine_transcribe_draws): n_segments and next_seg count draws, draws_per of every segment of d_inputs.
-static int run_stream_job(mt3_engine* e, const std::string& who, const GroupJob& j, const float* d_inputs, int n_segments,
-                          int next_seg, int32_t* d_ids, int poll, const BeamOut* bo, bool skip_encoder, StreamCounts* n,
-                          int draws_per = 0) {
-  Feed feed;
-  feed.n_total = n_segments;
-  feed.next_seg = next_seg;
-  feed.finished = next_seg == n_segments;
-  PendingDecode& p = begin_job(e);
-  int rc = MT3_OK;
-  if (!post_groups(e, j,
-                   [e, &feed, d_ids, poll, bo, draws_per](GroupRun& r) {
-                     return run_group_stream(e, r, feed, d_ids, poll, bo, draws_per);
-                   },
-                   &feed)) {
-    feed_fail(feed);
-    rc = mt3::fail(MT3_ERR_HIP, who + ": could not start a row group's worker thread");
-  } else if (!feed.finished) {
-    rc = produce_chunks(e, feed, d_inputs, j.s, skip_encoder, draws_per ? draws_per : 1);
-  }
-  const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
-  for (int g = 0; g < p.posted; ++g) worker_wait(e, g);
-  p.active = false;
-  e->compactions = e->compactions_now.exchange(0);
-  e->last_groups = j.groups;
-  e->last_used_graph = 1;
-  n->most = 0;
-  for (int g = 0; g < p.posted; ++g) {
-    if (rc == MT3_OK && p.rcs[g] != MT3_OK)
-      rc = mt3::fail(p.rcs[g], who + " (row group " + std::to_string(g) + "): " + p.errs[g]);
-    n->most = p.ran[g] > n->most ? p.ran[g] : n->most;
-    if (!p.used_graph[g]) e->last_used_graph = 0;
-  }
-  n->polls = feed.polls;
-  n->refills = feed.refills;
-  n->starved = feed.starved;
-  n->produced = feed.produced;
-  if (rc != MT3_OK && !producer_err.empty()) return mt3::fail(rc, producer_err);
-  return rc;
+// what a streaming job did, in slots: the feed's counters and the longest group's steps; `initial` of the feed's refills
+// were the first fill of the slots (a job that starts from the ring), which the caller did not ask about
+static mt3_transcribe_stats stream_stats(const mt3_engine* e, const GroupJob& j, const Feed& f, int most, int initial) {
+  mt3_transcribe_stats st{};
+  st.slots = j.units * j.unit;
+  st.groups = j.groups;
+  st.steps_run = most;
+  st.polls = f.polls;
+  st.refills = (f.refills - initial) * j.unit;
+  st.starved_polls = f.starved;
+  st.encoder_chunks = f.produced;
+  st.compactions = e->compactions;              // (beam groups are never compacted: 0)
+  st.used_graph = e->last_used_graph;
+  return st;
 }
 
-// poll_steps / groups_override: 0 = the product's choice (mt3_debug_engine_transcribe sets them for A/B runs)
-static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_steps, int32_t flags,
-                           int32_t* d_ids, mt3_transcribe_stats* h_stats, void* stream, int poll_steps, int groups_override,
-                           bool skip_encoder = false) {
-  if (!e || !e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: engine not finalized");
-  if (e->pending.active)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
-  const mt3_engine_config& c = e->cfg;
-  if (!d_inputs || !d_ids || n_segments <= 0) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: null buffer or no segments");
-  if (num_steps <= 0 || num_steps > c.max_decode_len) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: num_steps out of range");
-  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_BEAM1 | MT3_DECODE_SINGLE_STREAM))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_BEAM1 | MT3_DECODE_SINGLE_STREAM");
-  if (c.num_decoder_layers > mt3k::kRefillMaxLayers) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: at most 16 decoder layers");
-  if (e->eos_on && n_segments > e->eos_cap)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: the synthetic EOS schedule is shorter than n_segments");
-  int seg_var = 0;
-  MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe", n_segments, 2, num_steps, &seg_var));
-  MT3_TRY(sampling_fits(e, "mt3_engine_transcribe", n_segments, (flags & MT3_DECODE_BEAM1) != 0, &seg_var));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = c.max_decode_len, S = n_segments < c.max_batch ? n_segments : c.max_batch;
-  const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
-  if (n_segments > S) MT3_TRY(ensure_stage(e));
-  const int groups = stream_groups_for(c, flags, S, 1, groups_override);
-  const int poll = poll_steps > 0 ? poll_steps : kStreamPollSteps;
-  if (ensure_group_streams(e, groups) != MT3_OK)
-    return mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe: could not create the row groups' streams");
+// The streaming job sj / j over n feed entries, from its posting to its end: the row groups run run_group_stream on their
+// workers while the calling thread encodes what is not in the caches yet into the staging ring (everything if
+// sj.from_ring, else the entries from j.units on); then the groups are joined and *st says what ran.  The device-side
+// start of the slots is enqueued on j.s before this and closed with part_begin.
+static int run_stream_job(mt3_engine* e, const StreamJob& sj, const GroupJob& j, const float* d_inputs, int n,
+                          mt3_transcribe_stats* st) {
+  Feed feed;
+  feed.n_total = n;
+  feed.next_seg = sj.from_ring ? 0 : j.units;
+  feed.finished = feed.next_seg == n;
+  begin_job(e);
+  int rc = MT3_OK;
+  if (!post_groups(e, j, [e, &feed, &sj](GroupRun& r) { return run_group_stream(e, r, feed, sj); }, &feed)) {
+    feed_fail(feed);
+    rc = mt3::fail(MT3_ERR_HIP, std::string(sj.who) + ": could not start a row group's worker thread");
+  } else if (!feed.finished) {
+    rc = produce_chunks(e, feed, d_inputs, j.s, sj);
+  }
+  const std::string producer_err = rc != MT3_OK ? mt3_last_error() : "";
+  int most = 0;
+  const int joined = join_groups(e, sj.who, &most);
+  *st = stream_stats(e, j, feed, most, sj.from_ring ? j.units : 0);
+  return rc != MT3_OK ? mt3::fail(rc, producer_err) : joined;      // the producer's message wins over a group's
+}
 
-  // ---- the first S segments go straight into the caches, slot i starts on segment i
+// ---- the two starts of a streaming job's slots, on the caller's stream
+// mt3_engine_transcribe's direct first pass: the first j.units of the n segments go straight into the caches, slot i
+// starts on segment i
+static int start_direct(mt3_engine* e, const StreamJob& sj, const GroupJob& j, const float* d_inputs, int n) {
+  const int S = j.units;
+  hipStream_t s = j.s;
   MT3_TRY(encode_impl(e, d_inputs, S, nullptr, CrossDst{}, s));
-  e->cur_batch = S;
-  MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, static_cast<size_t>(n_segments) * L * 4, s));
+  MT3_HIP_CHECK(hipMemsetAsync(sj.d_ids, 0, static_cast<size_t>(n) * e->cfg.max_decode_len * 4, s));
   MT3_TRY(reset_slots(e, S, true, true, s));
   MT3_TRY(embed_bos(e, S, s));
   MT3_TRY(mt3k::launch_iota(e->slot_row, S, s));
   MT3_TRY(mt3k::launch_iota(e->slot_seg, S, s));
-  if (beam1) MT3_TRY(reset_beam1_state(e, num_steps, s));
+  if (j.variant & kVarBeam) MT3_TRY(reset_beam1_state(e, j.num_steps, s));
+  return MT3_OK;
+}
+
+// a job that starts from the ring: every slot finished and empty, with a valid (BOS) input row so that the dense launches
+// of empty slots read numbers, and every group's counter of finished slots = its slots.  The beam job's form is one
+// launch behind the beam start; the greedy form (mt3_engine_transcribe_draws; slot i on cache row i) is memsets.
+static int start_empty(mt3_engine* e, const StreamJob& sj, const GroupJob& j, int n) {
+  const int slots = j.units * j.unit;
+  hipStream_t s = j.s;
+  mt3k::GroupSlots gs{};
+  for (int g = 0; g < j.groups; ++g) {
+    int u0, un;
+    chain_rows(j.units, j.groups, g, &u0, &un);
+    gs.n[g] = un * j.unit;
+  }
+  if (j.variant & kVarBeams)
+    return start_beams(e, slots, false, j.num_steps, s, [&] {
+      return mt3k::launch_beam_stream_init(e->done, e->slot_seg, e->bk_fork_src, e->slot_row, e->n_done, slots, j.groups, gs, s);
+    });
+  MT3_HIP_CHECK(hipMemsetAsync(sj.d_ids, 0, static_cast<size_t>(n) * e->cfg.max_decode_len * 4, s));
+  MT3_TRY(reset_slots(e, slots, false, true, s));
+  MT3_TRY(embed_bos(e, slots, s));
+  MT3_TRY(mt3k::launch_iota(e->slot_row, slots, s));
+  MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->done), 1, static_cast<size_t>(slots), s));
+  MT3_HIP_CHECK(hipMemsetAsync(e->slot_seg, 0xFF, static_cast<size_t>(slots) * 4, s));   // -1: no segment
+  for (int g = 0; g < j.groups; ++g)
+    MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->n_done + g), gs.n[g], 1, s));
+  return MT3_OK;
+}
+
+// The body the three streaming entry points share behind their argument checks: job sj over n feed entries (segments;
+// draws) in units = min(n, max_batch / sj.unit) units of slots.  `variant`: the entry point's bits of the step variant;
+// groups_override: stream_groups_for.  h_stats (may be nullptr) is written as mt3_hip.h says: by the beam job only when
+// it succeeds, by the other two also for a job that failed once it was running.
+static int stream_call(mt3_engine* e, const StreamJob& sj, const float* d_inputs, int n, int num_steps, int flags, int variant,
+                       int groups_override, mt3_transcribe_stats* h_stats, hipStream_t s) {
+  const mt3_engine_config& c = e->cfg;
+  const bool beams = (variant & kVarBeams) != 0;
+  const int units = n < c.max_batch / sj.unit ? n : c.max_batch / sj.unit;
+  if (sj.from_ring || n > units) MT3_TRY(ensure_stage(e));
+  const int groups = stream_groups_for(c, flags, units, sj.unit, groups_override);
+  if (ensure_group_streams(e, groups) != MT3_OK)
+    return mt3::fail(MT3_ERR_HIP, std::string(sj.who) + ": could not create the row groups' streams");
+  const GroupJob j{units, sj.unit, groups, variant | kVarRetire | kVarStream, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH),
+                   true, s, nullptr, nullptr};
+  MT3_TRY(sj.from_ring ? start_empty(e, sj, j, n) : start_direct(e, sj, j, d_inputs, n));
+  e->cur_batch = units * sj.unit;
   e->stream_max_len = num_steps;
-  const int variant = (beam1 ? kVarBeam : 0) | kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | seg_var;
   MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-  const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
-  StreamCounts n{};
-  const int rc = run_stream_job(e, "mt3_engine_transcribe", j, d_inputs, n_segments, S, d_ids, poll, nullptr, skip_encoder, &n);
   mt3_transcribe_stats st{};
-  st.slots = S;
-  st.groups = groups;
-  st.steps_run = n.most;
-  st.polls = n.polls;
-  st.refills = n.refills;
-  st.starved_polls = n.starved;
-  st.encoder_chunks = n.produced;
-  st.compactions = e->compactions;
-  st.used_graph = e->last_used_graph;
+  const int rc = run_stream_job(e, sj, j, d_inputs, n, &st);
+  if (beams) {
+    MT3_TRY(rc);
+    // every group thread has waited for its stream: the fork count of the job is final
+    MT3_HIP_CHECK(hipMemcpyAsync(e->h_pinned + kForksPinned, e->bk_forks, 4, hipMemcpyDeviceToHost, s));
+    MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
+  }
   if (h_stats) *h_stats = st;
   return rc;
 }
 
+// flags within `allowed`, buffers, a job, steps in range: the arguments every streaming entry point takes
+static int stream_args_fit(const mt3_engine* e, const char* who, int flags, int allowed, const float* d_inputs,
+                           const int32_t* d_ids, int n_segments, int num_steps) {
+  if (flags & ~allowed)
+    return invalid(who, allowed & MT3_DECODE_BEAM1 ? "flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_BEAM1 | MT3_DECODE_SINGLE_STREAM"
+                                                   : "flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM");
+  if (!d_inputs || !d_ids || n_segments <= 0) return invalid(who, "null buffer or no segments");
+  return steps_fit(e, who, num_steps);
+}
+constexpr int kStreamFlags = MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM;
+
+// poll_steps / groups_override: 0 = the product's choice (mt3_debug_engine_transcribe sets them for A/B runs)
+static int transcribe_impl(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_steps, int32_t flags,
+                           int32_t* d_ids, mt3_transcribe_stats* h_stats, void* stream, int poll_steps, int groups_override,
+                           bool skip_encoder) {
+  const char* who = "mt3_engine_transcribe";
+  MT3_TRY(engine_ready(e, who));
+  MT3_TRY(stream_args_fit(e, who, flags, kStreamFlags | MT3_DECODE_BEAM1, d_inputs, d_ids, n_segments, num_steps));
+  MT3_TRY(stream_fits(e, who, n_segments));
+  const bool beam1 = (flags & MT3_DECODE_BEAM1) != 0;
+  int seg_var = 0;
+  MT3_TRY(seg_tables_fit(e, who, n_segments, 2, num_steps, &seg_var));
+  MT3_TRY(sampling_fits(e, who, n_segments, beam1, &seg_var));
+  const StreamJob sj{who, 1, 1, false, d_ids, nullptr, nullptr, poll_steps > 0 ? poll_steps : kStreamPollSteps, skip_encoder};
+  return stream_call(e, sj, d_inputs, n_segments, num_steps, flags, (beam1 ? kVarBeam : 0) | (e->eos_on ? kVarEos : 0) | seg_var,
+                     groups_override, h_stats, static_cast<hipStream_t>(stream));
+}
+
 int mt3_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_steps, int32_t flags,
                           int32_t* d_ids, mt3_transcribe_stats* h_stats, void* stream) {
-  return transcribe_impl(e, d_inputs, n_segments, num_steps, flags, d_ids, h_stats, stream, 0, 0);
+  return transcribe_impl(e, d_inputs, n_segments, num_steps, flags, d_ids, h_stats, stream, 0, 0, false);
 }
 
 int mt3_debug_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_steps, int32_t flags,
@@ -2644,73 +2726,18 @@ int mt3_debug_engine_transcribe(mt3_engine* e, const float* d_inputs, int32_t n_
 int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t num_beams,
                                 int32_t num_steps, int32_t flags, int32_t* d_ids, int32_t* d_all_ids, float* d_scores,
                                 mt3_transcribe_stats* h_stats, void* stream) {
-  if (!e) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: null engine");
-  const mt3_engine_config& c = e->cfg;
+  const char* who = "mt3_engine_transcribe_beams";
   const int k = num_beams;
-  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM))
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM");
-  if (k < 1 || k > mt3k::kBeamMaxK) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: num_beams must be 1 .. 8");
-  if (k > c.max_batch) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: num_beams exceeds max_batch");
-  if (c.vocab_size > 2048 || c.vocab_size < 2 * k)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the beam step needs 2 * num_beams <= vocab <= 2048");
-  if (c.num_decoder_layers > mt3k::kRefillMaxLayers)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: more than 16 decoder layers");
-  if (!d_inputs || !d_ids || n_segments < 1)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: null buffer or no segments");
-  if (num_steps < 1 || num_steps > c.max_decode_len)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: num_steps out of range");
-  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: engine not finalized");
-  if (e->pending.active)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
-  if (e->eos_on)
-    return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe_beams: the synthetic EOS schedule drives the greedy / beam-1 token kernel only");
+  if (!e) return invalid(who, "null engine");
+  MT3_TRY(stream_args_fit(e, who, flags, kStreamFlags, d_inputs, d_ids, n_segments, num_steps));
+  MT3_TRY(beams_fit(e, who, k));
+  MT3_TRY(engine_ready(e, who));
+  if (e->eos_on) return invalid(who, "the synthetic EOS schedule drives the greedy / beam-1 token kernel only");
   int seg_var = 0;
-  MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe_beams", n_segments, 2 * k, num_steps, &seg_var));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  MT3_TRY(ensure_beam_state(e));
-  MT3_TRY(ensure_stage(e));
-  const int E = n_segments < c.max_batch / k ? n_segments : c.max_batch / k, slots = E * k;
-  const int groups = stream_groups_for(c, flags, E, k, 0);
-  if (ensure_group_streams(e, groups) != MT3_OK)
-    return mt3::fail(MT3_ERR_HIP, "mt3_engine_transcribe_beams: could not create the row groups' streams");
-
-  // ---- every slot finished and empty; valid (BOS) input rows so that the dense launches of empty slots read numbers
-  MT3_TRY(reset_slots(e, slots, false, false, s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->bk_forks, 0, 4, s));
-  MT3_TRY(embed_bos(e, slots, s));
-  {
-    mt3k::GroupSlots gs{};
-    for (int g = 0; g < groups; ++g) {
-      int e0, en;
-      chain_rows(E, groups, g, &e0, &en);
-      gs.n[g] = en * k;
-    }
-    MT3_TRY(mt3k::launch_beam_stream_init(e->done, e->slot_seg, e->bk_fork_src, e->slot_row, e->n_done, slots, groups, gs, s));
-  }
-  MT3_TRY(mt3k::launch_set_float(e->beam_cfg, brevity_penalty(num_steps + 1), s));   // the loop bound, as reset_beam1_state
-  e->cur_batch = slots;
-  e->stream_max_len = num_steps;
-  const int variant = kVarRetire | kVarStream | kVarBeams | (k << kVarBeamsShift) | seg_var;
-  MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-  const GroupJob j{E, k, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
-  const BeamOut bo{k, d_all_ids, d_scores};
-  StreamCounts n{};
-  MT3_TRY(run_stream_job(e, "mt3_engine_transcribe_beams", j, d_inputs, n_segments, 0, d_ids, kStreamPollSteps, &bo, false, &n));
-  // every group thread has waited for its stream: the fork count of the job is final
-  MT3_HIP_CHECK(hipMemcpyAsync(e->h_pinned + kForksPinned, e->bk_forks, 4, hipMemcpyDeviceToHost, s));
-  MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
-  mt3_transcribe_stats st{};
-  st.slots = slots;
-  st.groups = groups;
-  st.steps_run = n.most;
-  st.polls = n.polls;
-  st.refills = (n.refills - E) * k;
-  st.starved_polls = n.starved;
-  st.encoder_chunks = n.produced;
-  st.compactions = 0;
-  st.used_graph = e->last_used_graph;
-  if (h_stats) *h_stats = st;
-  return MT3_OK;
+  MT3_TRY(seg_tables_fit(e, who, n_segments, 2 * k, num_steps, &seg_var));
+  const StreamJob sj{who, k, 1, true, d_ids, d_all_ids, d_scores, kStreamPollSteps, false};
+  return stream_call(e, sj, d_inputs, n_segments, num_steps, flags, kVarBeams | (k << kVarBeamsShift) | seg_var, 0, h_stats,
+                     static_cast<hipStream_t>(stream));
 }
 
 // mt3_engine_transcribe_draws: mt3_engine_transcribe's greedy path on a job of D = n_segments * per draws in
@@ -2719,65 +2746,21 @@ int mt3_engine_transcribe_beams(mt3_engine* e, const float* d_inputs, int32_t n_
 // starts at 0; `per` consecutive draws copy the same staged entry (StagedCross::per).
 int mt3_engine_transcribe_draws(mt3_engine* e, const float* d_inputs, int32_t n_segments, int32_t per, int32_t num_steps,
                                 int32_t flags, int32_t* d_ids, mt3_transcribe_stats* h_stats, void* stream) {
-  const std::string fn = "mt3_engine_transcribe_draws: ";
-  if (!e) return mt3::fail(MT3_ERR_INVALID, fn + "null engine");
-  const mt3_engine_config& c = e->cfg;
-  if (flags & ~(MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM))
-    return mt3::fail(MT3_ERR_INVALID, fn + "flags are MT3_DECODE_NO_GRAPH | MT3_DECODE_SINGLE_STREAM (beam-1 does not sample)");
-  if (!d_inputs || !d_ids || n_segments <= 0) return mt3::fail(MT3_ERR_INVALID, fn + "null buffer or no segments");
-  if (per < 1) return mt3::fail(MT3_ERR_INVALID, fn + "per must be at least 1");
-  if (num_steps <= 0 || num_steps > c.max_decode_len) return mt3::fail(MT3_ERR_INVALID, fn + "num_steps out of range");
-  const int L = c.max_decode_len;
-  if (static_cast<long long>(n_segments) * per > INT32_MAX / L)
-    return mt3::fail(MT3_ERR_INVALID, fn + "n_segments * per exceeds INT32_MAX / max_decode_len");
-  if (c.num_decoder_layers > mt3k::kRefillMaxLayers) return mt3::fail(MT3_ERR_INVALID, fn + "at most 16 decoder layers");
-  if (!e->finalized) return mt3::fail(MT3_ERR_INVALID, fn + "engine not finalized");
-  if (e->pending.active)
-    return mt3::fail(MT3_ERR_INVALID, fn + "a decode is in flight (MT3_DECODE_ASYNC): call mt3_engine_decode_wait first");
-  const int D = n_segments * per, S = D < c.max_batch ? D : c.max_batch;
-  if (e->eos_on && D > e->eos_cap)
-    return mt3::fail(MT3_ERR_INVALID, fn + "the synthetic EOS schedule is shorter than n_segments * per");
+  const char* who = "mt3_engine_transcribe_draws";
+  if (!e) return invalid(who, "null engine");
+  MT3_TRY(stream_args_fit(e, who, flags, kStreamFlags, d_inputs, d_ids, n_segments, num_steps));   // (beam-1 does not sample)
+  if (per < 1) return invalid(who, "per must be at least 1");
+  if (static_cast<long long>(n_segments) * per > INT32_MAX / e->cfg.max_decode_len)
+    return invalid(who, "n_segments * per exceeds INT32_MAX / max_decode_len");
+  const int D = n_segments * per;
+  MT3_TRY(stream_fits(e, who, D));
+  MT3_TRY(engine_ready(e, who));
   int seg_var = 0;
-  MT3_TRY(seg_tables_fit(e, "mt3_engine_transcribe_draws", D, 2, num_steps, &seg_var));
-  MT3_TRY(sampling_fits(e, "mt3_engine_transcribe_draws", D, false, &seg_var));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  MT3_TRY(ensure_stage(e));
-  const int groups = stream_groups_for(c, flags, S, 1, 0);
-  if (ensure_group_streams(e, groups) != MT3_OK)
-    return mt3::fail(MT3_ERR_HIP, fn + "could not create the row groups' streams");
-
-  // ---- every slot finished and empty, slot i on cache row i; valid (BOS) input rows so that the dense launches of empty
-  // slots read numbers; a group's counter of finished slots = its slots
-  MT3_HIP_CHECK(hipMemsetAsync(d_ids, 0, static_cast<size_t>(D) * L * 4, s));
-  MT3_TRY(reset_slots(e, S, false, true, s));
-  MT3_TRY(embed_bos(e, S, s));
-  MT3_TRY(mt3k::launch_iota(e->slot_row, S, s));
-  MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->done), 1, static_cast<size_t>(S), s));
-  MT3_HIP_CHECK(hipMemsetAsync(e->slot_seg, 0xFF, static_cast<size_t>(S) * 4, s));   // -1: no segment
-  for (int g = 0; g < groups; ++g) {
-    int r0, rn;
-    chain_rows(S, groups, g, &r0, &rn);
-    MT3_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->n_done + g), rn, 1, s));
-  }
-  e->cur_batch = S;
-  e->stream_max_len = num_steps;
-  const int variant = kVarRetire | kVarStream | (e->eos_on ? kVarEos : 0) | seg_var;
-  MT3_HIP_CHECK(hipEventRecord(e->part_begin, s));
-  const GroupJob j{S, 1, groups, variant, num_steps, true, !(flags & MT3_DECODE_NO_GRAPH), true, s, nullptr, nullptr};
-  StreamCounts n{};
-  const int rc = run_stream_job(e, "mt3_engine_transcribe_draws", j, d_inputs, D, 0, d_ids, kStreamPollSteps, nullptr, false, &n, per);
-  mt3_transcribe_stats st{};
-  st.slots = S;
-  st.groups = groups;
-  st.steps_run = n.most;
-  st.polls = n.polls;
-  st.refills = n.refills - S;
-  st.starved_polls = n.starved;
-  st.encoder_chunks = n.produced;
-  st.compactions = e->compactions;
-  st.used_graph = e->last_used_graph;
-  if (h_stats) *h_stats = st;
-  return rc;
+  MT3_TRY(seg_tables_fit(e, who, D, 2, num_steps, &seg_var));
+  MT3_TRY(sampling_fits(e, who, D, false, &seg_var));
+  const StreamJob sj{who, 1, per, true, d_ids, nullptr, nullptr, kStreamPollSteps, false};
+  return stream_call(e, sj, d_inputs, D, num_steps, flags, (e->eos_on ? kVarEos : 0) | seg_var, 0, h_stats,
+                     static_cast<hipStream_t>(stream));
 }
 
 int mt3_engine_decode(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t flags, int32_t* d_ids,
