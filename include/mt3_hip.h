@@ -2031,6 +2031,69 @@ int mt3_op_note_consensus(const double* d_onset, const double* d_offset, const i
                           int32_t* d_note_votes /* [n_notes] */, int32_t* d_counts /* [n_files] */, int32_t* d_scratch,
                           int64_t scratch_words, void* stream);
 
+/* ---- note preparation: known notes as the reference prepares them before tokenizing.  Two modes over the same skeleton;
+ * a job that wants both calls twice.  The host statement, event by event: mt3_amd/note_sequences.py.
+ * MT3_NOTE_PREP_SUSTAIN  note_seq.apply_sustain_control_changes [from memory: parity unpinned against note_seq]: a note
+ *   whose key goes up while its instrument's sustain pedal (controller 64, down from value 64 on) is down lasts until the
+ *   pedal goes up, or until the same pitch of that instrument is struck again under the pedal.
+ *   KEY    key = instrument << 7 | pitch (int32; the kernel reads the instrument as key >> 7).
+ *   PEDAL  the controller-64 events of a file lie SORTED by (instrument, time, ON before OFF) as
+ *     inst_state = instrument << 1 | (1 for OFF: value < 64).  ped(g, t): the state after g's last event with time <= t,
+ *     up when there is none; rel(g, t): the time of g's first OFF with time > t, or none.
+ *   t_last  the largest time among the file's note starts, note ends and controller-64 events, 0 for an empty file.
+ *   RULE   for note i (start s, end e, instrument g) let j be the FIRST later note of its key, in the order
+ *     (start, pos), with ped(g, s_j) down.
+ *       cut   if ped(g, e) is down and s_j < rel(g, e) (or there is no rel), or ped(g, e) is up and s_j <= e:
+ *             the new end is s_j, and the note is DELETED when s_j == s;
+ *       hold  else, if ped(g, e) is down: the new end is rel(g, e), or t_last when there is none;
+ *       else  the end stays.
+ *     total_time: t_last if any note was held to t_last; else the largest of the old value and every rel a note was held to.
+ * MT3_NOTE_PREP_TRIM  mt3 trim_overlapping_notes (mt3/note_sequences.py:52-69).  key = is_drum << 14 | program << 7 |
+ *   pitch; j is the NEXT note of the key in the order (start, pos); the new end is s_j if e > s_j, else e; the note is
+ *   deleted unless s < the new end.  total_time stays.  The pedal arguments are not read.
+ * ORDER   a file's notes lie SORTED by (key, start, pos), pos = the note's position in the caller's own order, 0 .. n - 1,
+ *   each once.  The host sorts; the op takes sorted columns.
+ * OUTPUTS (device)  the surviving notes of each file in the CALLER'S order, compacted from the position where the file's
+ *   input starts: d_out_end the new end, d_out_src the note's pos (entries past a file's count are not written);
+ *   d_counts [n_files] the survivors, d_total_time [n_files] the new total_time.  No end is computed: each is a note
+ *   start, a pedal time, t_last or the old end, so the result equals the host statement bit for bit.
+ * WORK  one workgroup of MT3_NOTE_PREP_TILE lanes per file, 64 files per launch (their table rides in the kernel
+ *   arguments), the launches one after the other on `stream`; tiles of MT3_NOTE_PREP_TILE items, scan state carried from
+ *   tile to tile: (0, sustain) a reversed max-scan over the pedal events -> the next OFF at or after each, so that rel is a
+ *   binary search and one read however long a held pedal's run of ON values is; (1) a reversed max-scan over the notes
+ *   flagged ped(g, start) (trim: all) -> j, the case analysis, new end and keep flag into scratch at pos; (2) a sum-scan of
+ *   the keep flags over the caller's order compacts.  No atomics.
+ * d_scratch: int32 words, 8-byte aligned, at least MT3_NOTE_PREP_SCRATCH_WORDS(n_notes, n_pedal) = 3 * n_notes + n_pedal
+ *   (n_pedal counts 0 in trim mode).
+ * SAFETY  every index comes from the file table, checked below, from the scans or from a binary search over the file's own
+ *   range; a pos outside 0 .. n - 1 is not written.  Columns that are not as required give unspecified notes, but no read or
+ *   write leaves the file's own ranges.
+ * MT3_ERR_INVALID, before any device work: an unknown mode; n_notes, n_pedal or n_files negative; NULL note columns with
+ *   n_notes > 0, NULL pedal columns with n_pedal > 0 (sustain), NULL outputs, NULL or misaligned scratch, a NULL file table
+ *   with n_files > 0; a file's note or pedal range outside its column, overlapping the one before it or out of order; a
+ *   t_last or total_time that is not finite; scratch_words below the formula.  n_files == 0 is MT3_OK and launches
+ *   nothing. */
+#define MT3_NOTE_PREP_SUSTAIN 0
+#define MT3_NOTE_PREP_TRIM 1
+#define MT3_NOTE_PREP_TILE 256
+#define MT3_NOTE_PREP_SCRATCH_WORDS(n_notes, n_pedal) (3 * (int64_t)(n_notes) + (int64_t)(n_pedal))
+
+typedef struct mt3_note_prep_file {
+  int64_t first;                      /* the file's first note in the columns; its output starts there too */
+  int64_t pedal_first;                /* the file's first pedal event in the pedal columns */
+  int32_t n_notes;
+  int32_t n_pedal;
+  double t_last;
+  double total_time;
+} mt3_note_prep_file;
+
+int mt3_op_prepare_notes(int32_t mode, const double* d_start, const double* d_end, const int32_t* d_key,
+                         const int32_t* d_pos, int64_t n_notes, const double* d_pedal_time,
+                         const int32_t* d_pedal_inst_state, int64_t n_pedal,
+                         const mt3_note_prep_file* h_files /* [n_files] */, int32_t n_files, double* d_out_end,
+                         int32_t* d_out_src, int32_t* d_counts /* [n_files] */, double* d_total_time /* [n_files] */,
+                         int32_t* d_scratch, int64_t scratch_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ GRANULARITIES = {"full": GRANULARITY_FULL, "midi_class": GRANULARITY_MIDI_CLASS,
 TOKENIZE_MAX_STRIDE = 1 << 20                  # mt3_op_tokenize_notes
 ALIGN_MAX_SHIFTS = 64                          # mt3_op_align_paths
 CONSENSUS_MAX_VOTERS, CONSENSUS_TILE, CONSENSUS_SCRATCH_WORDS_PER_NOTE = 64, 256, 4      # mt3_op_note_consensus
+NOTE_PREP_SUSTAIN, NOTE_PREP_TRIM, NOTE_PREP_TILE = 0, 1, 256                              # mt3_op_prepare_notes
 
 
 class Mt3Error(RuntimeError):
@@ -123,6 +124,11 @@ class TokenizeRow(C.Structure):                # mt3_tokenize_row
 
 class ConsensusFile(C.Structure):              # mt3_consensus_file
     _fields_ = [("first", C.c_int64)] + [(n, C.c_int32) for n in ("n_notes", "n_voters", "min_votes", "reserved")]
+
+
+class NotePrepFile(C.Structure):               # mt3_note_prep_file
+    _fields_ = [("first", C.c_int64), ("pedal_first", C.c_int64), ("n_notes", C.c_int32), ("n_pedal", C.c_int32),
+                ("t_last", C.c_double), ("total_time", C.c_double)]
 
 
 _P = C.c_void_p
@@ -340,6 +346,8 @@ SIGNATURES = {
     "mt3_op_align_paths": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_double, _P, _P, _P, _P]),
     "mt3_op_note_consensus": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P,
                                         _P, _P, _P, C.c_int64, _P]),
+    "mt3_op_prepare_notes": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, _P,
+                                       _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

@@ -733,11 +733,23 @@ class InferenceModel(object):
         return dict(stride=self.outputs_length, segment_frames=self.inputs_length,
                     frames_per_second=self.spectrogram_config.frames_per_second, vocab_size=self.model_config.vocab_size)
 
-    def targets(self, audio_or_num_samples, ns, *, sample_rate: int = SAMPLE_RATE, granularity: str = "full"):
+    @staticmethod
+    def _sustained(sequences, sustain: bool):
+        """sustain: the job's sequences with their sustain pedals applied on the device (`note_prep.prepare`: what the
+        reference tokenizes for piano, mt3/preprocessors.py:154), the control changes cleared; else the sequences as given"""
+        if not sustain:
+            return list(sequences)
+        from . import note_prep
+        return note_prep.prepare(sequences, sustain=True)
+
+    def targets(self, audio_or_num_samples, ns, *, sample_rate: int = SAMPLE_RATE, granularity: str = "full",
+                sustain: bool = False):
         """The training targets of `ns` for this audio (a 1-d array of samples, or just their number): one int32 id row
         per segment of `__call__`, in the form `score` takes -- the tie section, the segment's events, EOS; cut to
-        `outputs_length` ids (`tokenize.target_rows`, on the device)."""
+        `outputs_length` ids (`tokenize.target_rows`, on the device).  sustain: the sustain pedal of `ns.control_changes`
+        is applied to the notes first (`note_prep.prepare`), as the reference does for piano."""
         from . import tokenize
+        ns, = self._sustained([ns], sustain)
         rows = tokenize.target_rows([ns], [self._num_frames(audio_or_num_samples, sample_rate)], self.codec,
                                     self.encoding_spec, granularity, **self._tokenize_kw())
         ids, lengths = rows.ids.cpu().numpy(), rows.lengths.cpu().numpy()
@@ -759,15 +771,20 @@ class InferenceModel(object):
         return_note_scores: also float64 arrays aligned with `ns.notes` (of the best shift) -- 'onset_logprob' and
         'onset_margin' of the note's onset pitch / drum id as in `transcribe_scored`, 'end_logprob' of its note-off pitch id;
         NaN for an id that was cut or does not exist (a drum has no end).
+        Under the sustain pedal of `ns.control_changes`: `score_notes_many([(audio, ns)], sustain=True)[0]`.
         Frontend and segments are those of `__call__`; the rows are built on the device (`tokenize.target_rows`) and go
         straight to `Transformer.score_segments`.  ValueError with e4m3 K/V caches, as `score`."""
         return self.score_notes_many([(audio, ns)], sample_rates=[sample_rate], shifts=shifts, granularity=granularity,
                                      return_note_scores=return_note_scores)[0]
 
     def score_notes_many(self, pairs, *, sample_rates: Optional[Sequence[int]] = None, shifts=None,
-                         granularity: str = "full", return_note_scores: bool = False) -> List[Dict[str, Any]]:
+                         granularity: str = "full", return_note_scores: bool = False,
+                         sustain: bool = False) -> List[Dict[str, Any]]:
         """`score_notes` of several (audio, NoteSequence) pairs as ONE job: one tokenizer launch and one scoring call over
-        the segments of all files (and all shifts).  Returns one dict per pair."""
+        the segments of all files (and all shifts).  Returns one dict per pair.  sustain: score the notes as they sound
+        under the sustain pedal of each `ns.control_changes` (`note_prep.prepare`, one device call for the job) -- the
+        targets a piano model was trained on; the per-note arrays are then aligned with the notes that survive it
+        (`note_prep.prepare([ns])[0].notes`)."""
         import torch
         from . import tokenize
         self._refuse_e4m3("score_notes")
@@ -780,6 +797,7 @@ class InferenceModel(object):
             raise ValueError("shifts must not be empty")
         if not pairs:
             return []
+        pairs = list(zip([audio for audio, _ in pairs], self._sustained([ns for _, ns in pairs], sustain)))
         feats, n_frames = [], []
         for (audio, _), rate in zip(pairs, sample_rates):
             examples = self._examples(audio, rate)
@@ -835,7 +853,7 @@ class InferenceModel(object):
 
     def align_notes(self, audio, ns, *, max_shift: float = 0.2, step: float = 0.02, shifts=None, smoothness=None,
                     max_jump=None, sample_rate: int = SAMPLE_RATE, granularity: str = "full", shared_encoder: bool = True,
-                    return_table: bool = False):
+                    return_table: bool = False, sustain: bool = False):
         """Repair the timing of the notes `ns` against `audio`: a time shift per segment, chosen as the smooth path of the
         highest log-probability through the (segment, shift) table, and the notes warped by it -> a dict:
           'notes'           the warped NoteSequence (`alignment.warp_notes`: the shift is interpolated between the
@@ -852,14 +870,16 @@ class InferenceModel(object):
         near a jump may be counted in both neighbouring segments or in neither; the shifts are segment-granular.
         shared_encoder: every segment is encoded once for all shifts (`Transformer.score_candidates`); False: the table
         comes from `score_segments` on the log-mel replicated per shift, as `score_notes` gets it -- the same bits in
-        float32.  ValueError with e4m3 K/V caches, as `score_notes`."""
+        float32.  sustain: the sustain pedal of `ns.control_changes` is applied first (`note_prep.prepare`): the sustained
+        notes are aligned, and 'notes' are the sustained notes, warped.  ValueError with e4m3 K/V caches, as `score_notes`."""
         return self.align_notes_many([(audio, ns)], sample_rates=[sample_rate], max_shift=max_shift, step=step,
                                      shifts=shifts, smoothness=smoothness, max_jump=max_jump, granularity=granularity,
-                                     shared_encoder=shared_encoder, return_table=return_table)[0]
+                                     shared_encoder=shared_encoder, return_table=return_table, sustain=sustain)[0]
 
     def align_notes_many(self, pairs, *, sample_rates: Optional[Sequence[int]] = None, max_shift: float = 0.2,
                          step: float = 0.02, shifts=None, smoothness=None, max_jump=None, granularity: str = "full",
-                         shared_encoder: bool = True, return_table: bool = False) -> List[Dict[str, Any]]:
+                         shared_encoder: bool = True, return_table: bool = False,
+                         sustain: bool = False) -> List[Dict[str, Any]]:
         """`align_notes` of several (audio, NoteSequence) pairs as ONE job: one tokenizer launch, one scoring call and one
         path call over the segments of all files.  Returns one dict per pair."""
         import torch
@@ -876,6 +896,7 @@ class InferenceModel(object):
         alignment.check_jumps(grid, max_jump, seconds)
         if not pairs:
             return []
+        pairs = list(zip([audio for audio, _ in pairs], self._sustained([ns for _, ns in pairs], sustain)))
         feats, n_frames = [], []
         for (audio, _), rate in zip(pairs, sample_rates):
             examples = self._examples(audio, rate)

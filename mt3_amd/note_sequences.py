@@ -8,6 +8,7 @@ state machine itself (note_sequences.py:262-408) lives in libmt3hip.so
 """
 from __future__ import annotations
 
+import copy
 import dataclasses
 from typing import List
 
@@ -30,10 +31,20 @@ class Note:
 
 
 @dataclasses.dataclass
+class ControlChange:
+    """One MIDI controller event (note_seq's NoteSequence.ControlChange, the fields the sustain rule reads)."""
+    time: float = 0.0
+    control_number: int = 0
+    control_value: int = 0
+    instrument: int = 0
+
+
+@dataclasses.dataclass
 class NoteSequence:
     notes: List[Note] = dataclasses.field(default_factory=list)
     total_time: float = 0.0
     ticks_per_quarter: int = 220
+    control_changes: List[ControlChange] = dataclasses.field(default_factory=list)      # the last field: see DESIGN 6p
 
 
 @dataclasses.dataclass
@@ -49,6 +60,91 @@ def extract_track(ns: NoteSequence, program: int, is_drum: bool) -> NoteSequence
     total_time is their latest end, 0.0 without notes (note_sequences.py:42-49)."""
     notes = [n for n in ns.notes if n.program == program and bool(n.is_drum) == bool(is_drum)]
     return NoteSequence(notes=notes, total_time=max((n.end_time for n in notes), default=0.0), ticks_per_quarter=220)
+
+
+def trim_overlapping_notes(ns: NoteSequence) -> NoteSequence:
+    """Trim overlapping notes of one (pitch, program, is_drum), dropping zero-length notes (note_sequences.py:52-69).  A new
+    sequence; `ns` is not touched."""
+    ns_trimmed = copy.deepcopy(ns)
+    channels = set((note.pitch, note.program, note.is_drum) for note in ns_trimmed.notes)
+    for pitch, program, is_drum in channels:
+        notes = [note for note in ns_trimmed.notes
+                 if note.pitch == pitch and note.program == program and note.is_drum == is_drum]
+        sorted_notes = sorted(notes, key=lambda note: note.start_time)
+        for i in range(1, len(sorted_notes)):
+            if sorted_notes[i - 1].end_time > sorted_notes[i].start_time:
+                sorted_notes[i - 1].end_time = sorted_notes[i].start_time
+    ns_trimmed.notes = [note for note in ns_trimmed.notes if note.start_time < note.end_time]
+    return ns_trimmed
+
+
+def validate_note_sequence(ns: NoteSequence) -> None:
+    """Raise ValueError if `ns` contains invalid notes (note_sequences.py:87-94)."""
+    for note in ns.notes:
+        if note.start_time >= note.end_time:
+            raise ValueError("note has start time >= end time: %f >= %f" % (note.start_time, note.end_time))
+        if note.velocity == 0:
+            raise ValueError("note has zero velocity")
+
+
+SUSTAIN_CONTROL_NUMBER = 64
+_SUS_ON, _SUS_OFF, _NOTE_ON, _NOTE_OFF = range(4)
+
+
+def apply_sustain_control_changes(ns: NoteSequence, sustain_control_number: int = SUSTAIN_CONTROL_NUMBER) -> NoteSequence:
+    """The notes of `ns` as they sound under its sustain pedal (controller 64, down from value 64 on): a note whose key goes
+    up while its instrument's pedal is down lasts until the pedal goes up, or until the same pitch is struck again under the
+    pedal.  note_seq.apply_sustain_control_changes, event by event [from memory: parity unpinned against note_seq].  A new
+    sequence, its control changes kept; `ns` is not touched.  The yardstick of mt3_op_prepare_notes: DESIGN 6p."""
+    out = copy.deepcopy(ns)
+    events = [(n.start_time, _NOTE_ON, n) for n in out.notes] + [(n.end_time, _NOTE_OFF, n) for n in out.notes]
+    events += [(cc.time, _SUS_ON if cc.control_value >= 64 else _SUS_OFF, cc) for cc in out.control_changes
+               if cc.control_number == sustain_control_number]
+    events.sort(key=lambda e: (e[0], e[1]))                  # stable: the order above breaks ties
+    active, sus, removed, time = {}, {}, set(), 0
+    for time, kind, value in events:
+        inst = value.instrument
+        notes = active.setdefault(inst, [])
+        if kind == _SUS_ON:
+            sus[inst] = True
+        elif kind == _SUS_OFF:
+            sus[inst] = False
+            still = []
+            for note in notes:
+                if note.end_time < time:
+                    note.end_time = time
+                    out.total_time = max(out.total_time, time)
+                else:
+                    still.append(note)
+            active[inst] = still
+        elif kind == _NOTE_ON:
+            if sus.get(inst, False):
+                still = []
+                for note in notes:
+                    if note.pitch == value.pitch:
+                        note.end_time = time
+                        if note.start_time == note.end_time:
+                            removed.add(id(note))
+                    else:
+                        still.append(note)
+                active[inst] = notes = still
+            notes.append(value)
+        elif not sus.get(inst, False):                       # _NOTE_OFF
+            active[inst] = [note for note in notes if note is not value]
+    for notes in active.values():
+        for note in notes:
+            note.end_time = time
+            out.total_time = time
+    out.notes = [note for note in out.notes if id(note) not in removed]
+    return out
+
+
+def sustain_reference(ns: NoteSequence) -> NoteSequence:
+    """What the reference tokenizes and stores for evaluation (preprocessors.py:154-160): the sustained notes, the control
+    changes cleared."""
+    out = apply_sustain_control_changes(ns)
+    out.control_changes = []
+    return out
 
 
 @dataclasses.dataclass(frozen=True)

@@ -7,6 +7,7 @@
                                  [--score-against DIR] [--score-midi DIR [--score-shifts S,...]]
                                  [--align-midi DIR [--align-max-shift S] [--align-step S] [--align-smoothness L]]
                                  [--consensus N [--consensus-min-votes M] [--consensus-tolerance S]]
+                                 [--sustain] [--trim-overlaps]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -46,6 +47,10 @@ voted on the device; a note is kept when --consensus-min-votes of them have it, 
 {"n_voters": N, "min_votes": M, "notes": [...]}, one record per note of NAME.mid in the NoteSequence's order with its
 start_time, end_time, pitch, program, is_drum, votes and members.  (--well-formed-tied keeps N decodes per job.)  Not with
 --decoding beam, and not together with --confidences.
+--sustain and --trim-overlaps prepare the MIDI files read for --score-against, --score-midi and --align-midi the way the
+reference prepares its targets (`mt3_amd.note_prep.prepare`, on the device, all files of an option as one job): --sustain
+applies each file's sustain pedal (controller 64) to its notes' ends -- what a piano model such as ismir2021 was trained
+on; --trim-overlaps then trims overlapping notes of one pitch and program and drops the empty ones.
 """
 from __future__ import annotations
 
@@ -121,6 +126,12 @@ def plan(argv=None):
                     help="--consensus: the samples that must have a note for it to be kept (1 .. N; default N // 2 + 1)")
     ap.add_argument("--consensus-tolerance", type=float, default=None, metavar="S",
                     help="--consensus: seconds between neighbouring onsets of one note's cluster (default 0.05)")
+    ap.add_argument("--sustain", action="store_true",
+                    help="--score-against / --score-midi / --align-midi: apply the sustain pedal (controller 64) of each "
+                         "MIDI file read to its notes' ends")
+    ap.add_argument("--trim-overlaps", action="store_true",
+                    help="--score-against / --score-midi / --align-midi: trim overlapping notes of one pitch and program "
+                         "in each MIDI file read, and drop the empty ones")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -149,6 +160,9 @@ def plan(argv=None):
             ap.error("--consensus-tolerance takes seconds >= 0")
         if args.confidences:
             ap.error("--consensus and --confidences do not go together")
+    if (args.sustain or args.trim_overlaps) and args.score_against is None and args.score_midi is None and \
+            args.align_midi is None:
+        ap.error("--sustain and --trim-overlaps need --score-against, --score-midi or --align-midi")
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
@@ -258,29 +272,24 @@ def main(argv=None) -> int:
         scored = None
         if args.score_against is not None:
             from . import metrics
-            references = []
-            for path in args.inputs:
-                with open(reference_path(args.score_against, path), "rb") as f:
-                    references.append(midi_io.midi_bytes_to_note_sequence(f.read()))
+            references = known_notes(args.score_against, args)
             scored = metrics.transcription_metrics(list(zip(references, sequences)))
         midi_scores = None
         if args.score_midi is not None:
             from . import audio_io
             pairs, rates = [], []
-            for path in args.inputs:
+            for path, ns in zip(args.inputs, known_notes(args.score_midi, args)):
                 samples, rate = audio_io.read_wav(path)
-                with open(reference_path(args.score_midi, path), "rb") as f:
-                    pairs.append((samples, midi_io.midi_bytes_to_note_sequence(f.read())))
+                pairs.append((samples, ns))
                 rates.append(rate)
             midi_scores = model.score_notes_many(pairs, sample_rates=rates, shifts=args.score_shifts)
         aligned = None
         if args.align_midi is not None:
             from . import audio_io
             pairs, rates = [], []
-            for path in args.inputs:
+            for path, ns in zip(args.inputs, known_notes(args.align_midi, args)):
                 samples, rate = audio_io.read_wav(path)
-                with open(reference_path(args.align_midi, path), "rb") as f:
-                    pairs.append((samples, midi_io.midi_bytes_to_note_sequence(f.read())))
+                pairs.append((samples, ns))
                 rates.append(rate)
             aligned = model.align_notes_many(pairs, sample_rates=rates, max_shift=args.align_max_shift,
                                              step=args.align_step, smoothness=args.align_smoothness)
@@ -318,6 +327,19 @@ def main(argv=None) -> int:
         with open(alignment_path(outputs), "w") as f:
             json.dump([alignment_record(path, rec) for path, rec in zip(args.inputs, aligned)], f, indent=1)
     return 0
+
+
+def known_notes(directory: str, args) -> list:
+    """DIR/NAME.mid of every input as a NoteSequence, prepared as --sustain / --trim-overlaps ask: one device job"""
+    from . import midi_io
+    sequences = []
+    for path in args.inputs:
+        with open(reference_path(directory, path), "rb") as f:
+            sequences.append(midi_io.midi_bytes_to_note_sequence(f.read()))
+    if args.sustain or args.trim_overlaps:
+        from . import note_prep
+        sequences = note_prep.prepare(sequences, sustain=args.sustain, trim=args.trim_overlaps)
+    return sequences
 
 
 def votes_path(midi_path: str) -> str:
