@@ -42,13 +42,27 @@ constexpr int kMagStride = 1028;
 constexpr int kMaxBandWeights = 2048;       // >= sum of band lengths (1934 for the reference's mel matrix)
 // logf(1e-5f) as numpy's float32 evaluates it (spectral_ops.safe_log's floor), and ln 2
 constexpr float kLogFloor = -11.512925148010254f, kLn2 = 0.6931471805599453f;
+// ln 2 in two pieces: the upper one has 16 significant bits, so its product with a binary exponent is exact
+constexpr float kLn2Hi = 6.9313812256e-01f, kLn2Lo = 9.0580006145e-06f;
 
-// safe_log of a mel value: v_log_f32 (log2, 1 ulp) * ln 2 instead of logf's expansion; denormal inputs (which the
-// instruction would flush) are clamped
+// safe_log of a mel value on v_log_f32 (log2, 1 ulp) instead of logf's expansion; denormal inputs (which the
+// instruction would flush) are clamped.  The instruction's ulp is one of ITS result: taken of the whole value it costs
+// 1.3e-6 in the log at int16 scale (log2 near 20), as much as the FFT's own error there.  So it is taken of the
+// mantissa f in [sqrt 1/2, sqrt 2) alone, |log2 f| <= 1/2 and off by 3e-8 at most, and the exponent comes in as
+// e * ln 2 in two pieces: ln m = e ln2_hi + (e ln2_lo + log2 f * ln 2), within 0.6 ulp of the result at any scale.
+// Only called for frames whose spectrum is finite (spectrum_not_finite below): fmaxf would read a NaN mel value as the
+// clamp constant.
 __device__ __forceinline__ float safe_log_fast(float m) {
   // (a positive DENORMAL mel -- below 1.2e-38, i.e. numerical dust of a silent frame -- is read as the smallest
   // normal number: v_log_f32 would flush it to zero)
-  const float l = __builtin_amdgcn_logf(fmaxf(m, 1.17549435e-38f)) * kLn2;
+  const float x = fmaxf(m, 1.17549435e-38f);
+  float f = __builtin_amdgcn_frexp_mantf(x);                     // [1/2, 1)
+  int e = __builtin_amdgcn_frexp_expf(x);
+  const bool low = f < 0.70710678f;
+  f = low ? f + f : f;
+  e = low ? e - 1 : e;
+  const float ef = static_cast<float>(e);
+  const float l = __builtin_fmaf(ef, kLn2Hi, __builtin_fmaf(ef, kLn2Lo, __builtin_amdgcn_logf(f) * kLn2));
   return m <= 0.f ? kLogFloor : l;
 }
 
@@ -56,6 +70,24 @@ template <int I>
 __device__ __forceinline__ void mel_group(const int* k0, const float* wpad, int lane, const float* mag, float* dst) {
   const int j = lane + 64 * I;
   dst[j] = safe_log_fast(mt3fe::mel_bin_padded<mt3fe::kGroupMaxBand[I]>(k0, wpad + mt3fe::group_base(I), j, mag));
+}
+
+// Whether one of the frame's magnitudes |X[0 .. 1023]| is NaN or Inf, the same answer in all lanes of the wave.  A NaN or
+// an Inf among the frame's 2048 samples reaches every bin of the FFT, and the reference's DENSE mel product (NaN * 0 =
+// Inf * 0 = NaN under every zero weight, spectral_ops.py:58-73) then has NaN in all 512 mel bins, the two empty columns
+// included, which safe_log keeps (NaN <= 0 is false, log NaN = NaN).  The band-sparse product cannot do that, so the
+// kernel writes the NaN row of such a frame itself.  The test reads the wave's own `mag` once more (after the barrier
+// that follows untangle_mag), 16 bins per lane as bit patterns, and leaves the arithmetic of a finite frame untouched.
+__device__ __forceinline__ bool spectrum_not_finite(const float* mag, int lane) {
+  unsigned top = 0;                                              // largest |bits|: exponent all ones = NaN or Inf
+#pragma unroll
+  for (int q = 0; q < mt3fe::kHalf / 256; ++q) {
+    const float4 v = *reinterpret_cast<const float4*>(mag + 4 * lane + 256 * q);
+    const unsigned a = max(__float_as_uint(v.x) & 0x7fffffffu, __float_as_uint(v.y) & 0x7fffffffu);
+    const unsigned b = max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu);
+    top = max(top, max(a, b));
+  }
+  return __ballot(top >= 0x7f800000u) != 0;
 }
 
 // The 4 waves of a workgroup work on different frames and only meet at the initial staging barrier;
@@ -145,7 +177,13 @@ __global__ __launch_bounds__(kWaves * 64) void logmel_kernel(FrontendDev t, cons
     wave_lds_sync();
     const int f = f0 + fl;
     float* dst = out + (static_cast<size_t>(seg) * frames_per_segment + f) * kMelBins;
-    if (f < n) {                                                 // spectral_ops.safe_log(mel)
+    if (f >= n) {
+#pragma unroll
+      for (int i = 0; i < kMelBins / 64; ++i) dst[lane + 64 * i] = 0.f;
+    } else {                                                     // spectral_ops.safe_log(mel)
+      // (the test's LDS reads and vote run beside the mel sums instead of in front of them; a frame that fails it has
+      // its row written twice, each lane over its own stores)
+      const bool odd = spectrum_not_finite(mag, lane);
       mel_group<0>(s_k0, s_w, lane, mag, dst);
       mel_group<1>(s_k0, s_w, lane, mag, dst);
       mel_group<2>(s_k0, s_w, lane, mag, dst);
@@ -154,9 +192,10 @@ __global__ __launch_bounds__(kWaves * 64) void logmel_kernel(FrontendDev t, cons
       mel_group<5>(s_k0, s_w, lane, mag, dst);
       mel_group<6>(s_k0, s_w, lane, mag, dst);
       mel_group<7>(s_k0, s_w, lane, mag, dst);
-    } else {
+      if (odd) {
 #pragma unroll
-      for (int i = 0; i < kMelBins / 64; ++i) dst[lane + 64 * i] = 0.f;
+        for (int i = 0; i < kMelBins / 64; ++i) dst[lane + 64 * i] = __builtin_nanf("");
+      }
     }
     // the next round's stage_a overwrites xchg: every lane's zlin reads happened before the
     // barrier that precedes the mel step, and mag is only rewritten after the next 4 barriers.

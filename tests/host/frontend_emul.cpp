@@ -62,14 +62,18 @@ extern "C" int emul_logmel(const float* audio, int n_frames, int frames_per_segm
       for (int l = 0; l < 64; ++l) mt3fe::untangle_mag(lc[l], l, z[l], xchg.data(), mag.data());
       const int f = f0 + fl;
       float* dst = out + static_cast<size_t>(f) * 512;
+      bool odd = false;                                      // the kernel's spectrum_not_finite: |X[0 .. 1023]| has a NaN or an Inf
+      for (int k = 0; k < mt3fe::kHalf; ++k) odd = odd || !std::isfinite(mag[k]);
       for (int l = 0; l < 64; ++l)
         for (int i = 0; i < 8; ++i) {
           const int j = l + 64 * i;
-          if (f < n_frames) {
+          if (f >= n_frames) {
+            dst[j] = 0.f;
+          } else if (odd) {
+            dst[j] = NAN;                                    // the whole row, as the reference's dense mel product gives
+          } else {
             const float m = padded_bin(i, T.k0.data(), WP.data(), j, mag.data());
             dst[j] = logf(m <= 0.f ? 1e-5f : m);
-          } else {
-            dst[j] = 0.f;
           }
         }
     }
