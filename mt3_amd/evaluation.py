@@ -28,9 +28,8 @@ REDUCED_MODES = {
 
 def file_notes_and_tokens(model, audio) -> Tuple[Any, np.ndarray]:
     """`InferenceModel.__call__` (NB:283-308) that also hands back the token rows: (NoteSequence, int32 [segments, 1024])"""
-    examples = model.preprocess(model.audio_to_dataset(audio), host_inputs=False)
-    batch, model._logmel_dev = {"encoder_input_tokens": model._logmel_dev}, None
-    tokens = model.predict_tokens(batch)
+    examples, logmel = model._examples(audio, 16000)
+    tokens = model.predict_tokens({"encoder_input_tokens": logmel})
     preds = [model.postprocess(t, ex) for t, ex in zip(tokens, examples)]
     ns = metrics_utils.event_predictions_to_ns(preds, codec=model.codec, encoding_spec=model.encoding_spec)["est_ns"]
     return ns, tokens

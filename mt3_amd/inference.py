@@ -18,7 +18,9 @@ stays the reference's 8 as an ATTRIBUTE (`input_shapes`, NB:190), but the engine
 runs mt3_engine_transcribe: a 10-minute file is ONE engine call whose finished rows are
 refilled with the file's next segments, not 37 batch-synchronous calls of 8 rows
 (`schedule="batch"` keeps the reference's loop for comparison); the log-mel stays on
-the device between `preprocess` and `predict_tokens`.  Decoding
+the device between the frontend and `predict_tokens` (`_examples` returns it beside the examples).  What a call sets
+on the engine -- masks, prompts, grammar, sampling -- is one `_Job` value, built in `_job`, passed down to
+`_predict_ids` and cleared by `_engine_job`; the model object holds nothing about a call in flight.  Decoding
 defaults to `decoding="beam1"`: the selection rule of t5x beam search with one beam and
 alpha 0.6, which is what the reference's predict_batch_with_aux runs (SURVEY.md A.5);
 `decoding="greedy"` stops a row at its first arg-max EOS.
@@ -55,6 +57,21 @@ def trim_eos(tokens: Sequence[int]) -> np.ndarray:
     if vocabularies.DECODED_EOS_ID in tokens:
         tokens = tokens[: np.argmax(tokens == vocabularies.DECODED_EOS_ID)]
     return tokens
+
+
+@dataclasses.dataclass(frozen=True)
+class _Job:
+    """What one decode job sets on the engine (`InferenceModel._job` builds it from the public keywords): a value that
+    is passed from the transcribing method down to `_predict_ids`, never kept on the model."""
+    decoding: str                                # the decoding rule of this job; the model's own unless `sample*` asks
+    sampling: sampling.SamplingParams            # ... and its sampling parameters (decoding == "sample")
+    masks: Optional[np.ndarray] = None           # constrained: uint32 [n_masks, words]
+    mask_index: Optional[np.ndarray] = None      # ... and the mask of every segment (None: mask 0 everywhere)
+    prompts: Optional[List[Any]] = None          # prompted: one id list or None per segment
+    grammar: Any = None                          # well-formed: a _lib.TokenGrammar or _lib.NoteGrammar
+    tied: bool = False                           # well_formed="tied": a wavefront over segment indices
+    streams: Optional[np.ndarray] = None         # the noise stream of every segment (None: its index in the engine call)
+    draws: Optional[int] = None                  # `sample` / `sample_many` as one job: the draws of every segment
 
 
 class InferenceModel(object):
@@ -115,14 +132,10 @@ class InferenceModel(object):
         if decoding not in ("beam1", "greedy", "beam", "sample"):
             raise ValueError("decoding must be 'beam1', 'greedy', 'beam' or 'sample', got %r" % (decoding,))
         self.sampling = sampling.SamplingParams(float(temperature), int(top_k), float(top_p), int(seed)).check()
-        self._job_streams = None                 # per-segment noise streams of the job in flight (None: the segment index)
-        self._job_draws = None                   # `sample` / `sample_many` in flight as one job: the draws of every segment
         if int(cap) < 0:
             raise ValueError("cap must not be negative, got %r" % (cap,))
         self.cap = int(cap)
         self.drop_redundant_programs = bool(drop_redundant_programs)
-        self._job_tied = False                   # the call in flight is well_formed="tied": a wavefront over segment indices
-        self._tie_overflows = 0
         if decoding == "beam" and not 1 <= int(num_beams) <= min(8, self.max_slots):
             raise ValueError("num_beams must be 1 .. 8 (and <= max_slots), got %r" % (num_beams,))
         self.decoding = decoding
@@ -140,9 +153,6 @@ class InferenceModel(object):
             "vocab_size": vocabularies.num_embeddings(self.vocabulary), "dtype": dtype,
             "input_depth": spectrograms.input_depth(self.spectrogram_config)})
         self._params = None
-        self._job_masks = None                   # (masks, per-segment index or None) of the constrained call in flight
-        self._job_prompts = None                 # per-segment prompts (id list or None) of the prompted call in flight
-        self._job_grammar = None                 # the event grammar of the well-formed call in flight
         self.last_event_counts = None            # invalid_events / dropped_events of the most recent transcribing call
         self.model = network.Transformer(self.model_config, input_length=self.inputs_length,
                                          max_decode_length=self.outputs_length, max_batch=self.batch_size)
@@ -261,74 +271,86 @@ class InferenceModel(object):
         rows += [None] * (n_segments - len(rows))
         return rows if any(r is not None for r in rows) else None
 
+    def _max_steps(self) -> int:
+        """a segment's length in steps of the codec: 204 for `mt3`, 409 for `ismir2021`"""
+        cfg = self.spectrogram_config
+        return int(math.floor(self.inputs_length * cfg.hop_width / cfg.sample_rate * self.codec.steps_per_second))
+
     def token_grammar(self):
         """the event grammar of this model's codec, spec and segment length (`vocabularies.token_grammar`): max_steps is
         the segment's length in steps, 204 for `mt3` and 409 for `ismir2021`"""
-        cfg = self.spectrogram_config
-        max_steps = int(math.floor(self.inputs_length * cfg.hop_width / cfg.sample_rate * self.codec.steps_per_second))
-        return vocabularies.token_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, max_steps)
+        return vocabularies.token_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, self._max_steps())
 
     def note_grammar(self):
         """the note grammar of this model's codec, spec and segment length (`vocabularies.note_grammar`); ValueError for a
         spec without a tie section"""
-        cfg = self.spectrogram_config
-        max_steps = int(math.floor(self.inputs_length * cfg.hop_width / cfg.sample_rate * self.codec.steps_per_second))
-        return vocabularies.note_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, max_steps)
+        return vocabularies.note_grammar(self.codec, self.model_config.vocab_size, self.encoding_spec, self._max_steps())
 
-    @contextlib.contextmanager
-    def _constrained(self, job, prompts=None, well_formed=False):
-        """the engine calls of `_predict_ids` inside run under `job` (`_token_masks`), `prompts` (`_segment_prompts` of
-        the whole job) and, with well_formed, the model's event grammar (True) or note grammar ("notes"); all are cleared
-        on the way out, also on error"""
+    def _job(self, segments_per_file, many: bool, *, programs=None, drums=True, prompts=None, well_formed=False,
+             **rule) -> _Job:
+        """The job of one transcribing call, from its public keywords and the segments of its files.  many: the `_many` /
+        `wavs` forms -- programs / drums may hold one entry per file, prompts holds one sequence per file, and a segment's
+        noise stream is its index within its own file; else one file, one constraint, one prompt sequence.  rule: `draws`,
+        and the `decoding` / `sampling` of this job where they are not the model's.  Everything is checked here, before
+        anything is set on the engine."""
         if isinstance(well_formed, str) and well_formed not in ("notes", "tied"):
             raise ValueError('well_formed is False, True, "notes" or "tied", got %r' % (well_formed,))
         tied = isinstance(well_formed, str) and well_formed == "tied"
+        masks = self._token_masks(programs, drums, segments_per_file if many else None)
+        rows = None
+        if prompts is not None:
+            per_file = prompts if many else [prompts]
+            if len(per_file) != len(segments_per_file):
+                raise ValueError("prompts has %d entries for %d files" % (len(per_file), len(segments_per_file)))
+            rows = []
+            for p, n in zip(per_file, segments_per_file):
+                rows += self._segment_prompts(p, n) or [None] * n
+            rows = rows if any(r is not None for r in rows) else None
         if tied:
-            if prompts is not None:
+            if rows is not None:
                 raise ValueError('well_formed="tied" writes every segment\'s prompt itself: not together with prompts=')
             if 2 * self.cap + 1 >= self.outputs_length:
                 raise ValueError('well_formed="tied": a tie section of cap = %d pairs (%d ids) leaves no room in a decode '
                                  "of %d steps" % (self.cap, 2 * self.cap + 1, self.outputs_length))
-        self._job_masks = job
-        self._job_prompts = prompts
-        self._tie_overflows = 0
+        if well_formed == "notes" or tied:
+            grammar = self.note_grammar()
+        else:
+            grammar = self.token_grammar() if well_formed else None
+        streams = np.concatenate([np.arange(n) for n in segments_per_file]) if many else None
+        return _Job(rule.pop("decoding", None) or self.decoding, rule.pop("sampling", None) or self.sampling,
+                    *(masks or (None, None)), prompts=rows, grammar=grammar, tied=tied, streams=streams, **rule)
+
+    @contextlib.contextmanager
+    def _engine_job(self, job: _Job):
+        """the engine calls of `job` run inside; what the job set on the engine is cleared on the way out, also on error"""
         try:
-            if well_formed == "notes" or tied:
-                self._job_grammar = self.note_grammar()
-                self._job_tied = tied
-            else:
-                self._job_grammar = self.token_grammar() if well_formed else None
             yield
         finally:
-            self._job_masks = None
-            self._job_prompts = None
-            if self._job_tied and self.model is not None:
-                self.model.set_prompts(None)
-            self._job_tied = False
-            if self._job_grammar is not None and self.model is not None:
-                if isinstance(self._job_grammar, _lib.NoteGrammar):
+            if self.model is not None:
+                if job.tied:
+                    self.model.set_prompts(None)
+                if isinstance(job.grammar, _lib.NoteGrammar):
                     self.model.clear_note_grammar()
-                else:
+                elif job.grammar is not None:
                     self.model.clear_token_grammar()
-            self._job_grammar = None
-            if job is not None and self.model is not None:
-                self.model.clear_token_masks()
-            if prompts is not None and self.model is not None:
-                self.model.set_prompts(None)
-            if self.decoding == "sample" and self.model is not None:
-                self.model.clear_sampling()
+                if job.masks is not None:
+                    self.model.clear_token_masks()
+                if job.prompts is not None:
+                    self.model.set_prompts(None)
+                if job.decoding == "sample":
+                    self.model.clear_sampling()
 
-    def _set_masks(self, lo: int, hi: int, per: int = 0):
-        """before an engine call on segments [lo, hi) of the job: their masks and prompts on the engine that will run it.
+    def _set_masks(self, job: _Job, lo: int, hi: int, per: int = 0):
+        """before an engine call on segments [lo, hi) of `job`: their masks and prompts on the engine that will run it.
         per > 0 (Transformer.transcribe(draws=per)): the tables of the job's draws -- every segment's mask index, prompt
         and stream `per` times in a row, and draw j of every segment under the seed (seed + j) mod 2^64."""
         rep = max(int(per), 1)
-        if self._job_masks is not None:
-            masks, seg = self._job_masks
-            self.model.set_token_masks(masks, None if seg is None else np.repeat(np.asarray(seg[lo:hi]), rep))
-        if self._job_prompts is not None:
+        if job.masks is not None:
+            seg = job.mask_index
+            self.model.set_token_masks(job.masks, None if seg is None else np.repeat(np.asarray(seg[lo:hi]), rep))
+        if job.prompts is not None:
             rows, index = [], []
-            for p in self._job_prompts[lo:hi]:
+            for p in job.prompts[lo:hi]:
                 if p is None:
                     index.append(-1)
                     continue
@@ -336,18 +358,18 @@ class InferenceModel(object):
                     rows.append(p)
                 index.append(rows.index(p))
             self.model.set_prompts(rows, list(np.repeat(np.asarray(index, np.int32), rep)) if rows else None)
-        if isinstance(self._job_grammar, _lib.NoteGrammar):
-            self.model.set_note_grammar(self._job_grammar)
-        elif self._job_grammar is not None:
-            self.model.set_token_grammar(self._job_grammar)
-        if self.decoding == "sample":
+        if isinstance(job.grammar, _lib.NoteGrammar):
+            self.model.set_note_grammar(job.grammar)
+        elif job.grammar is not None:
+            self.model.set_token_grammar(job.grammar)
+        if job.decoding == "sample":
             # the stream of a segment is its index within its own file, whatever else the job or the engine call holds
-            streams = self._job_streams[lo:hi] if self._job_streams is not None else np.arange(lo, hi)
+            streams = job.streams[lo:hi] if job.streams is not None else np.arange(lo, hi)
             streams = np.repeat(np.asarray(streams, dtype=np.uint64), rep)
             seeds = None
             if per:
-                seeds = np.tile(np.array([(self.sampling.seed + j) % (1 << 64) for j in range(rep)], dtype=np.uint64), hi - lo)
-            self.model.set_sampling(self.sampling, streams, seeds)
+                seeds = np.tile(np.array([(job.sampling.seed + j) % (1 << 64) for j in range(rep)], dtype=np.uint64), hi - lo)
+            self.model.set_sampling(job.sampling, streams, seeds)
 
     # ------------------------------------------------------------------ model call
     def predict_tokens(self, batch: Dict[str, Any], seed: int = 0) -> np.ndarray:
@@ -355,82 +377,78 @@ class InferenceModel(object):
         with -1 from EOS on and -2 for invalid ids (vocabulary.decode_tf)."""
         return self.vocabulary.decode_tf(self._predict_ids(batch)).cpu().numpy()
 
-    def _predict_ids(self, batch: Dict[str, Any]):
-        """the engine's side of `predict_tokens`: the raw vocabulary ids, int32 CUDA [B, 1024]"""
+    def _predict_ids(self, batch: Dict[str, Any], job: Optional[_Job] = None, overflows: Optional[list] = None):
+        """the engine's side of `predict_tokens`: the raw vocabulary ids, int32 CUDA [B, 1024].  Every decode reaches the
+        engine through here.  job: what to set on the engine for it (None: nothing but the model's own decoding rule);
+        whoever built the job clears it (`_engine_job`).  overflows: a list that a tied job appends its count to."""
         import torch
         x = batch["encoder_input_tokens"]
         x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, np.float32))
         x = x.cuda()
-        if self._job_tied:
-            return self._predict_ids_tied(x)
-        beam1 = self.decoding == "beam1"
-        if self.decoding == "beam":
-            return self._predict_ids_beam(x)
-        if self.schedule == "refill" and self.early_exit and self._job_draws:
+        job = job if job is not None else _Job(self.decoding, self.sampling)
+        if job.tied:
+            return self._predict_ids_tied(x, job, overflows)
+        beam1 = job.decoding == "beam1"
+        if job.decoding == "beam":
+            return self._predict_ids_beam(x, job)
+        if self.schedule == "refill" and self.early_exit and job.draws:
             # ONE engine call for all draws of the job's segments, each segment encoded once; row s * per + j = draw j
-            per, n = int(self._job_draws), int(x.shape[0])
+            per, n = int(job.draws), int(x.shape[0])
             self._ensure_slots(n * per)
             self.rows_per_engine_call = [n * per]
-            self._set_masks(0, n, per)
+            self._set_masks(job, 0, n, per)
             return self.model.transcribe(x, draws=per)
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: finished rows restart on the job's next segments
             self._ensure_slots(x.shape[0])
             self.rows_per_engine_call = [int(x.shape[0])]
-            self._set_masks(0, int(x.shape[0]))
+            self._set_masks(job, 0, int(x.shape[0]))
             return self.model.transcribe(x, beam1=beam1)
         out = []
         step = min(self.batch_size, self.model.max_batch)
         self.rows_per_engine_call = []
         for s in range(0, x.shape[0], step):
             self.model.encode(x[s:s + step])
-            self._set_masks(s, s + step)
+            self._set_masks(job, s, s + step)
             out.append(self.model.decode(early_exit=self.early_exit, beam1=beam1))
             self.rows_per_engine_call.append(int(min(step, x.shape[0] - s)))
         return torch.cat(out, 0)
 
-    def _predict_ids_tied(self, x):
+    def _predict_ids_tied(self, x, job: _Job, overflows: Optional[list]):
         """well_formed="tied": the job as a wavefront.  Pass j decodes segment j of every file that has one through
-        `_predict_ids` -- the job's masks, streams and decoding rule sliced to the pass's rows -- with segment 0 forced to
-        the bare `tie` and segment j + 1 forced to `Transformer.tie_prompts` of the file's row from pass j."""
+        `_predict_ids` -- a job of its own: this one's masks, streams and decoding rule sliced to the pass's rows -- with
+        segment 0 forced to the bare `tie` and segment j + 1 forced to `Transformer.tie_prompts` of the file's row from
+        pass j."""
         import torch
         N = int(x.shape[0])
-        seg = np.asarray(self._job_streams if self._job_streams is not None else np.arange(N), np.int64)
-        job = (self._job_masks, self._job_streams)
-        grammar = self._job_grammar
+        seg = np.asarray(job.streams if job.streams is not None else np.arange(N), np.int64)
         ids = torch.empty((N, self.outputs_length), device=x.device, dtype=torch.int32)
         carried = {}                             # job row of segment j -> the prompt of the file's segment j + 1
-        bare = [int(grammar.g.tie_id)]
-        calls = []
-        self._job_tied = False                   # the passes themselves take the plain path
-        try:
-            for j in range(int(seg.max()) + 1 if N else 0):
-                rows = np.flatnonzero(seg == j)
-                if job[0] is not None:
-                    masks, index = job[0]
-                    self._job_masks = (masks, None if index is None else np.asarray(index)[rows])
-                self._job_streams = seg[rows]
-                self._job_prompts = [bare if j == 0 else carried[r - 1] for r in rows]
-                at = torch.from_numpy(rows).to(x.device)
-                out = self._predict_ids({"encoder_input_tokens": x.index_select(0, at)})
-                ids.index_copy_(0, at, out)
-                calls += self.rows_per_engine_call
-                go_on = [i for i, r in enumerate(rows) if r + 1 < N and seg[r + 1] == j + 1]
-                if not go_on:
-                    continue
-                src = out if len(go_on) == len(rows) else out.index_select(0, torch.tensor(go_on, device=x.device))
-                prompts, counts = self.model.tie_prompts(src, grammar, self.cap, self.drop_redundant_programs)
-                prompts, counts = prompts.cpu().numpy(), counts.cpu().numpy()
-                self._tie_overflows += int((counts > self.cap).sum())
-                carried = {int(rows[i]): ties.prompt_ids(p) for i, p in zip(go_on, prompts)}
-        finally:
-            self._job_tied = True
-            self._job_masks, self._job_streams = job
-            self._job_prompts = None
+        bare = [int(job.grammar.g.tie_id)]
+        calls, over = [], 0
+        for j in range(int(seg.max()) + 1 if N else 0):
+            rows = np.flatnonzero(seg == j)
+            one = dataclasses.replace(                                           # the pass itself takes the plain path
+                job, tied=False, streams=seg[rows], prompts=[bare if j == 0 else carried[r - 1] for r in rows],
+                mask_index=None if job.mask_index is None else np.asarray(job.mask_index)[rows])
+            at = torch.from_numpy(rows).to(x.device)
+            out = self._predict_ids({"encoder_input_tokens": x.index_select(0, at)}, one)
+            ids.index_copy_(0, at, out)
+            calls += self.rows_per_engine_call
+            go_on = [i for i, r in enumerate(rows) if r + 1 < N and seg[r + 1] == j + 1]
+            if not go_on:
+                continue
+            src = out if len(go_on) == len(rows) else out.index_select(0, torch.tensor(go_on, device=x.device))
+            prompts, counts = self.model.tie_prompts(src, job.grammar, self.cap, self.drop_redundant_programs)
+            prompts, counts = prompts.cpu().numpy(), counts.cpu().numpy()
+            over += int((counts > self.cap).sum())
+            carried = {int(rows[i]): ties.prompt_ids(p) for i, p in zip(go_on, prompts)}
         self.rows_per_engine_call = calls
+        if overflows is not None:
+            overflows.append(over)
         return ids
 
-    def _predict_ids_beam(self, x):
+    def _predict_ids_beam(self, x, job: _Job):
         """decoding='beam', k engine rows (beams) per segment: one in-flight batched call (schedule='refill'), or
         batch-synchronous chunks of max_slots // k segments (schedule='batch')"""
         import torch
@@ -440,14 +458,14 @@ class InferenceModel(object):
         if self.schedule == "refill" and self.early_exit:
             # ONE engine call for the whole job: a closed element restarts on the job's next segment
             self.rows_per_engine_call = [int(x.shape[0]) * k]
-            self._set_masks(0, int(x.shape[0]))
+            self._set_masks(job, 0, int(x.shape[0]))
             return self.model.transcribe(x, num_beams=k)
         chunk = max(1, min(chunk, self.model.max_batch // k))
         out = []
         self.rows_per_engine_call = []
         for s in range(0, x.shape[0], chunk):
             self.model.encode(x[s:s + chunk], num_beams=k)
-            self._set_masks(s, s + chunk)
+            self._set_masks(job, s, s + chunk)
             ids, _ = self.model.decode_beams(k, early_exit=self.early_exit)
             out.append(ids)
             self.rows_per_engine_call.append(int(min(chunk, x.shape[0] - s)) * k)
@@ -482,10 +500,45 @@ class InferenceModel(object):
         ValueError with prompts=, for a spec without a tie section, or when 2 * cap + 1 >= the decode length.
         `last_event_counts` holds the note decoder's invalid_events / dropped_events of the most recent call and
         tie_overflows, the segments whose held set exceeded `cap` on its way into the next (0 unless "tied")."""
-        examples = self._examples(audio, sample_rate)
-        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
-                               well_formed):
-            return self._transcribe_examples(examples)
+        return self._transcribe([functools.partial(self._examples, audio, sample_rate)], False,
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))[0]
+
+    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, **rule):
+        """The one path from files to notes.  make_examples: one call per file that returns (its examples, its log-mel on
+        the device); many and kw (programs, drums, prompts, well_formed) as `_job` reads them; rule: `_job`'s -- with
+        draws=n the segments' n draws run as one job (row s * n + j of the job = draw j of segment s).  -> per file its
+        NoteSequence; with draws the list of its n NoteSequences; with scored (one file) the pair (NoteSequence, scores).
+        All segments go through the engine as one job, and the job's tables are cleared on the way out."""
+        import torch
+        files = [make() for make in make_examples]
+        if not files:
+            return []
+        per_file = [examples for examples, _ in files]
+        job = self._job([len(examples) for examples in per_file], many, **kw, **rule)
+        # the frontend kernel has already written the feature converter's form of every segment -- [T, 512] rows, 0.0
+        # after a short last segment's frames (mt3/models.py:48-98 via models.convert_features) -- and it is still on the
+        # device: no host round trip between the frontend and the engine
+        x = files[0][1] if len(files) == 1 else torch.cat([logmel for _, logmel in files], 0)
+        del files
+        to_ns = metrics_utils.event_predictions_to_ns_traced if scored else metrics_utils.event_predictions_to_ns
+        n, overflows = int(job.draws or 1), []
+        with self._engine_job(job):
+            ids = self._predict_ids({"encoder_input_tokens": x}, job, overflows)
+            tokens = self.vocabulary.decode_tf(ids).cpu().numpy()
+            out, at, results = [], 0, []
+            for examples in per_file:
+                runs = []
+                for j in range(n):
+                    rows = tokens[at * n + j:(at + len(examples)) * n:n]
+                    preds = [self.postprocess(t, ex) for t, ex in zip(rows, examples)]
+                    results.append(to_ns(preds, codec=self.codec, encoding_spec=self.encoding_spec))
+                    runs.append(results[-1]["est_ns"])
+                at += len(examples)
+                out.append(runs if job.draws else runs[0])
+            self._count_events(results, sum(overflows))
+            if scored:
+                out = [(out[0], self._note_scores(x, ids, results[0]["note_tokens"]))]
+        return out
 
     def _draws_in_one_job(self, well_formed) -> bool:
         """whether `sample` runs its draws as one engine job: the refill schedule, and not well_formed="tied" (whose
@@ -501,7 +554,7 @@ class InferenceModel(object):
 
     def sample(self, audio, num_samples: int = 1, sample_rate: int = SAMPLE_RATE, **kw):
         """`num_samples` transcriptions of the same audio, drawn with seeds seed .. seed + num_samples - 1 of the model's
-        sampling parameters (decoding='sample' for the length of the call, whatever the model's own decoding is) -> a list
+        sampling parameters (the job's decoding is 'sample', whatever the model's own decoding is) -> a list
         of NoteSequences, sample j equal note for note to a model with seed + j called on the audio.  kw: the keywords of
         `__call__` (programs, drums, prompts, well_formed).
         The samples are ONE engine job (Transformer.transcribe(draws=num_samples)): the frontend and the encoder run once,
@@ -509,20 +562,16 @@ class InferenceModel(object):
         to min(segments * num_samples, max_slots).  well_formed="tied" keeps a loop of num_samples decodes: its wavefront
         carries one tie chain per decode (so does schedule='batch' / early_exit=False, which have no in-flight job)."""
         self._check_sample(num_samples)
+        make = [functools.partial(self._examples, audio, sample_rate)]
         if self._draws_in_one_job(kw.get("well_formed", False)):
-            prompts = kw.pop("prompts", None)
-            return self._sample_files([functools.partial(self._examples, audio, sample_rate)], int(num_samples),
-                                      prompts=None if prompts is None else [prompts], **kw)[0]
-        was = (self.decoding, self.sampling)
-        out = []
-        try:
-            self.decoding = "sample"
-            for i in range(int(num_samples)):
-                self.sampling = dataclasses.replace(was[1], seed=(was[1].seed + i) % (1 << 64))
-                out.append(self(audio, sample_rate, **kw))
-        finally:
-            self.decoding, self.sampling = was
-        return out
+            return self._transcribe(make, False, kw, decoding="sample", draws=int(num_samples))[0]
+        return self._sample_loop(lambda **rule: self._transcribe(make, False, kw, **rule)[0], num_samples)
+
+    def _sample_loop(self, run, num_samples):
+        """where the draws are no single engine job: run(decoding=, sampling=) once per sample, sample j under the
+        model's sampling parameters with the seed (seed + j) mod 2^64 -> the list of what the runs return"""
+        return [run(decoding="sample", sampling=dataclasses.replace(self.sampling, seed=(self.sampling.seed + j) % (1 << 64)))
+                for j in range(int(num_samples))]
 
     def sample_many(self, audios: Sequence[Any], num_samples: int = 1, sample_rates: Optional[Sequence[int]] = None,
                     **kw) -> List[List[Any]]:
@@ -530,55 +579,20 @@ class InferenceModel(object):
         `sample(audio, num_samples)` of that file.  sample_rates and kw as for `transcribe_many` (programs / drums /
         prompts: one entry per file where they differ).  well_formed="tied": num_samples `transcribe_many` jobs."""
         self._check_sample(num_samples)
-        if sample_rates is None:
-            sample_rates = [SAMPLE_RATE] * len(audios)
-        if len(sample_rates) != len(audios):
-            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
+        make = [functools.partial(self._examples, audio, sr) for audio, sr in zip(audios, self._rates(sample_rates, len(audios)))]
         if self._draws_in_one_job(kw.get("well_formed", False)):
-            return self._sample_files([functools.partial(self._examples, audio, sr)
-                                       for audio, sr in zip(audios, sample_rates)], int(num_samples), **kw)
-        was = (self.decoding, self.sampling)
-        runs = []
-        try:
-            self.decoding = "sample"
-            for i in range(int(num_samples)):
-                self.sampling = dataclasses.replace(was[1], seed=(was[1].seed + i) % (1 << 64))
-                runs.append(self.transcribe_many(audios, sample_rates, **kw))
-        finally:
-            self.decoding, self.sampling = was
+            return self._transcribe(make, True, kw, decoding="sample", draws=int(num_samples))
+        runs = self._sample_loop(lambda **rule: self._transcribe(make, True, kw, **rule), num_samples)
         return [[run[f] for run in runs] for f in range(len(audios))]
 
-    def _sample_files(self, make_examples, num_samples: int, programs=None, drums=True, prompts=None, well_formed=False):
-        """make_examples as for `_transcribe_files` -> per file the list of its `num_samples` sampled NoteSequences: all
-        draws of all segments through the engine as one job (row s * num_samples + j of the job = draw j of segment s)"""
-        per_file, feats, job_prompts = self._job_examples(make_examples, prompts)
-        if not per_file:
-            return []
-        was = self.decoding
-        self._job_streams = np.concatenate([np.arange(len(ex)) for ex in per_file])
-        self._job_draws = int(num_samples)
-        try:
-            self.decoding = "sample"
-            with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts,
-                                   well_formed):
-                tokens = self.predict_tokens({"encoder_input_tokens": feats})
-        finally:
-            self._job_streams = None
-            self._job_draws = None
-            self.decoding = was
-        out, at, results, n = [], 0, [], int(num_samples)
-        for examples in per_file:
-            draws = []
-            for j in range(n):
-                rows = tokens[at * n + j:(at + len(examples)) * n:n]
-                preds = [self.postprocess(t, ex) for t, ex in zip(rows, examples)]
-                results.append(metrics_utils.event_predictions_to_ns(preds, codec=self.codec,
-                                                                     encoding_spec=self.encoding_spec))
-                draws.append(results[-1]["est_ns"])
-            at += len(examples)
-            out.append(draws)
-        self._count_events(results)
-        return out
+    @staticmethod
+    def _rates(sample_rates, n: int):
+        """the `sample_rates` keyword of the many-file methods for n files: one rate per file, 16 kHz where None"""
+        if sample_rates is None:
+            return [SAMPLE_RATE] * n
+        if len(sample_rates) != n:
+            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), n))
+        return sample_rates
 
     def consensus(self, audio, num_samples: int = 8, sample_rate: int = SAMPLE_RATE, *, tolerance: float = 0.05,
                   min_votes: Optional[int] = None, return_votes: bool = False, **kw):
@@ -607,37 +621,14 @@ class InferenceModel(object):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
-        examples = self._wav_examples(wav_data)
-        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
-                               well_formed):
-            return self._transcribe_examples(examples)
+        return self._transcribe([functools.partial(self._wav_examples, wav_data)], False,
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))[0]
 
-    def _transcribe_examples(self, examples, scored: bool = False):
-        """the examples of one file, their log-mel in _logmel_dev -> NoteSequence (scored: and the notes' scores)"""
-        # the frontend kernel has already written the feature converter's form of every segment -- [T, 512] rows, 0.0
-        # after a short last segment's frames (mt3/models.py:48-98 via models.convert_features) -- and it is still on the
-        # device: no host round trip between preprocess and predict_tokens
-        batch, self._logmel_dev = {"encoder_input_tokens": self._logmel_dev}, None
-        if not scored:
-            tokens = self.predict_tokens(batch)
-            predictions = [self.postprocess(t, ex) for t, ex in zip(tokens, examples)]
-            result = metrics_utils.event_predictions_to_ns(predictions, codec=self.codec,
-                                                           encoding_spec=self.encoding_spec)
-            self._count_events([result])
-            return result["est_ns"]
-        ids = self._predict_ids(batch)
-        tokens = self.vocabulary.decode_tf(ids).cpu().numpy()
-        predictions = [self.postprocess(t, ex) for t, ex in zip(tokens, examples)]
-        result = metrics_utils.event_predictions_to_ns_traced(predictions, codec=self.codec,
-                                                              encoding_spec=self.encoding_spec)
-        self._count_events([result])
-        return result["est_ns"], self._note_scores(batch["encoder_input_tokens"], ids, result["note_tokens"])
-
-    def _count_events(self, results):
-        """the note decoder's counts of the call that just ended, summed over its files"""
+    def _count_events(self, results, tie_overflows: int):
+        """the note decoder's counts of the call that just ended, summed over its files, and its wavefront's overflows"""
         self.last_event_counts = {"invalid_events": int(sum(r["est_invalid_events"] for r in results)),
                                   "dropped_events": int(sum(r["est_dropped_events"] for r in results)),
-                                  "tie_overflows": int(self._tie_overflows)}
+                                  "tie_overflows": int(tie_overflows)}
 
     def transcribe_scored(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True,
                           prompts=None, well_formed: bool = False):
@@ -655,16 +646,15 @@ class InferenceModel(object):
         scores stay the unconstrained model's log-probabilities (scoring ignores token masks).  With prompts the prompt's
         tokens are scored like any other decoded token (scoring ignores prompts)."""
         self._refuse_e4m3("transcribe_scored")
-        examples = self._examples(audio, sample_rate)
-        with self._constrained(self._token_masks(programs, drums), self._segment_prompts(prompts, len(examples)),
-                               well_formed):
-            return self._transcribe_examples(examples, scored=True)
+        return self._transcribe([functools.partial(self._examples, audio, sample_rate)], False,
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
+                                scored=True)[0]
 
     def transcribe_wav_scored(self, wav_data, *, programs=None, drums: bool = True, well_formed: bool = False):
         """The file-level form of `transcribe_scored`: `transcribe_wav` plus the notes' confidences."""
         self._refuse_e4m3("transcribe_wav_scored")
-        with self._constrained(self._token_masks(programs, drums), None, well_formed):
-            return self._transcribe_examples(self._wav_examples(wav_data), scored=True)
+        return self._transcribe([functools.partial(self._wav_examples, wav_data)], False,
+                                dict(programs=programs, drums=drums, well_formed=well_formed), scored=True)[0]
 
     def _refuse_e4m3(self, who):
         if self.model_config.kv_dtype:
@@ -696,11 +686,8 @@ class InferenceModel(object):
         most 1024).  Returns float64 [n_segments] sequence scores, with return_token_scores also a list of float64
         per-token scores (one array of len(targets[i]) per segment).  sample_rate: as for `__call__`."""
         import torch
-        if self.model_config.kv_dtype:
-            raise ValueError("score() is not available with kv_dtype=%r: e4m3 K/V caches cannot score"
-                             % (self.model_config.kv_dtype,))
-        examples = self._examples(audio, sample_rate)
-        x, self._logmel_dev = self._logmel_dev, None
+        self._refuse_e4m3("score")
+        examples, x = self._examples(audio, sample_rate)
         if len(targets) != len(examples):
             raise ValueError("targets has %d rows; the audio has %d segments" % (len(targets), len(examples)))
         rows = [np.asarray(t, np.int32).reshape(-1)[: self.outputs_length] for t in targets]
@@ -741,6 +728,17 @@ class InferenceModel(object):
             return list(sequences)
         from . import note_prep
         return note_prep.prepare(sequences, sustain=True)
+
+    def _paired_examples(self, pairs, sample_rates, sustain: bool):
+        """the (audio, NoteSequence) pairs of a job -> (the pairs with the notes under the sustain pedal if asked, each
+        file's log-mel on the device, each file's frame count)"""
+        pairs = list(zip([audio for audio, _ in pairs], self._sustained([ns for _, ns in pairs], sustain)))
+        feats, n_frames = [], []
+        for (audio, _), rate in zip(pairs, sample_rates):
+            examples, logmel = self._examples(audio, rate)
+            feats.append(logmel)
+            n_frames.append(sum(len(ex["input_times"]) for ex in examples))
+        return pairs, feats, n_frames
 
     def targets(self, audio_or_num_samples, ns, *, sample_rate: int = SAMPLE_RATE, granularity: str = "full",
                 sustain: bool = False):
@@ -788,22 +786,13 @@ class InferenceModel(object):
         import torch
         from . import tokenize
         self._refuse_e4m3("score_notes")
-        if sample_rates is None:
-            sample_rates = [SAMPLE_RATE] * len(pairs)
-        if len(sample_rates) != len(pairs):
-            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(pairs)))
+        sample_rates = self._rates(sample_rates, len(pairs))
         shift_list = None if shifts is None else [float(s) for s in shifts]
         if shift_list is not None and not shift_list:
             raise ValueError("shifts must not be empty")
         if not pairs:
             return []
-        pairs = list(zip([audio for audio, _ in pairs], self._sustained([ns for _, ns in pairs], sustain)))
-        feats, n_frames = [], []
-        for (audio, _), rate in zip(pairs, sample_rates):
-            examples = self._examples(audio, rate)
-            feats.append(self._logmel_dev)
-            n_frames.append(sum(len(ex["input_times"]) for ex in examples))
-        self._logmel_dev = None
+        pairs, feats, n_frames = self._paired_examples(pairs, sample_rates, sustain)
         rows = tokenize.target_rows([ns for _, ns in pairs], n_frames, self.codec, self.encoding_spec, granularity,
                                     shifts=shift_list, **self._tokenize_kw())
         table = rows.rows_of_file                            # [files, shifts or 1, (first row, rows)]
@@ -885,10 +874,7 @@ class InferenceModel(object):
         import torch
         from . import alignment, tokenize
         self._refuse_e4m3("align_notes")
-        if sample_rates is None:
-            sample_rates = [SAMPLE_RATE] * len(pairs)
-        if len(sample_rates) != len(pairs):
-            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(pairs)))
+        sample_rates = self._rates(sample_rates, len(pairs))
         grid = alignment.shift_grid(max_shift, step) if shifts is None else np.asarray(shifts, np.float64).reshape(-1)
         smoothness = alignment.DEFAULT_SMOOTHNESS if smoothness is None else float(smoothness)
         seconds = self.inputs_length / self.spectrogram_config.frames_per_second
@@ -896,13 +882,7 @@ class InferenceModel(object):
         alignment.check_jumps(grid, max_jump, seconds)
         if not pairs:
             return []
-        pairs = list(zip([audio for audio, _ in pairs], self._sustained([ns for _, ns in pairs], sustain)))
-        feats, n_frames = [], []
-        for (audio, _), rate in zip(pairs, sample_rates):
-            examples = self._examples(audio, rate)
-            feats.append(self._logmel_dev)
-            n_frames.append(sum(len(ex["input_times"]) for ex in examples))
-        self._logmel_dev = None
+        pairs, feats, n_frames = self._paired_examples(pairs, sample_rates, sustain)
         K = len(grid)
         rows = tokenize.target_rows([ns for _, ns in pairs], n_frames, self.codec, self.encoding_spec, granularity,
                                     shifts=[float(g) for g in grid], **self._tokenize_kw())
@@ -949,19 +929,16 @@ class InferenceModel(object):
         as for `__call__`.  programs / drums: as for `__call__`, or one entry per file (programs=[[0], [33]]): every segment
         of a file carries its file's mask, so one job holds files with different instruments.  prompts: one `__call__`-style
         sequence (or None) per file."""
-        if sample_rates is None:
-            sample_rates = [SAMPLE_RATE] * len(audios)
-        if len(sample_rates) != len(audios):
-            raise ValueError("sample_rates has %d entries for %d files" % (len(sample_rates), len(audios)))
-        return self._transcribe_files([functools.partial(self._examples, audio, sr)
-                                       for audio, sr in zip(audios, sample_rates)], programs, drums, prompts, well_formed)
+        return self._transcribe([functools.partial(self._examples, audio, sr)
+                                 for audio, sr in zip(audios, self._rates(sample_rates, len(audios)))], True,
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))
 
     def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None,
                         well_formed: bool = False) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
         `self.transcribe_wav(wav)`.  programs / drums / prompts: as for `transcribe_many`."""
-        return self._transcribe_files([functools.partial(self._wav_examples, wav) for wav in wavs], programs, drums, prompts,
-                                      well_formed)
+        return self._transcribe([functools.partial(self._wav_examples, wav) for wav in wavs], True,
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))
 
     @staticmethod
     def pianoroll(ns, fps: float = 62.5):
@@ -977,55 +954,11 @@ class InferenceModel(object):
         from . import render
         return render.render([ns], sample_rate)[0]
 
-    def _job_examples(self, make_examples, prompts):
-        """the files of a job: make_examples (one call per file that returns its examples and leaves its log-mel in
-        _logmel_dev) and `prompts` (None, or one `__call__`-style sequence or None per file) -> (examples per file, the
-        job's log-mel [segments, T, depth] on the device, the job's per-segment prompts or None)"""
-        import torch
-        per_file, feats = [], []
-        for make in make_examples:
-            per_file.append(make())
-            feats.append(self._logmel_dev)
-        self._logmel_dev = None
-        if not per_file:
-            return [], None, None
-        job_prompts = None
-        if prompts is not None:
-            if len(prompts) != len(per_file):
-                raise ValueError("prompts has %d entries for %d files" % (len(prompts), len(per_file)))
-            rows = []
-            for p, ex in zip(prompts, per_file):
-                rows += self._segment_prompts(p, len(ex)) or [None] * len(ex)
-            job_prompts = rows if any(r is not None for r in rows) else None
-        return per_file, torch.cat(feats, 0), job_prompts
-
-    def _transcribe_files(self, make_examples, programs=None, drums=True, prompts=None, well_formed=False):
-        """make_examples: one call per file that returns its examples and leaves its log-mel in _logmel_dev -> one
-        NoteSequence per file, all segments through the engine as one job"""
-        per_file, feats, job_prompts = self._job_examples(make_examples, prompts)
-        if not per_file:
-            return []
-        self._job_streams = np.concatenate([np.arange(len(ex)) for ex in per_file])
-        try:
-            with self._constrained(self._token_masks(programs, drums, [len(ex) for ex in per_file]), job_prompts,
-                                   well_formed):
-                tokens = self.predict_tokens({"encoder_input_tokens": feats})
-        finally:
-            self._job_streams = None
-        out, at, results = [], 0, []
-        for examples in per_file:
-            preds = [self.postprocess(t, ex) for t, ex in zip(tokens[at:at + len(examples)], examples)]
-            at += len(examples)
-            results.append(metrics_utils.event_predictions_to_ns(preds, codec=self.codec, encoding_spec=self.encoding_spec))
-            out.append(results[-1]["est_ns"])
-        self._count_events(results)
-        return out
-
     # ------------------------------------------------------------------ host preprocessing
     def _examples(self, audio, sample_rate: int):
-        """audio at `sample_rate` -> the examples of `preprocess(..., host_inputs=False)`, log-mel left in _logmel_dev"""
+        """audio at `sample_rate` -> (the examples of `preprocess` without host 'inputs', their log-mel on the device)"""
         if int(sample_rate) == SAMPLE_RATE:
-            return self.preprocess(self.audio_to_dataset(audio), host_inputs=False)
+            return self._dataset_examples(self.audio_to_dataset(audio))
         if int(sample_rate) != sample_rate or sample_rate < 1:
             raise ValueError("sample_rate must be a positive integer, got %r" % (sample_rate,))
         return self._device_examples(audio, int(sample_rate))
@@ -1055,13 +988,13 @@ class InferenceModel(object):
 
     def _segment_device_audio(self, n_out: int, fill):
         """n_out 16 kHz samples that fill(capacity) puts at the head of a zero-padded device buffer of `capacity` samples
-        -> examples: the buffer is the frontend's [n_segments, T*hop] layout"""
+        -> (examples, log-mel): the buffer is the frontend's [n_segments, T*hop] layout"""
         hop, T = self.spectrogram_config.hop_width, self.inputs_length
         n_frames = n_out // hop + 1
         times = np.arange(n_frames) / self.spectrogram_config.frames_per_second
         counts = self._segment_counts(n_frames)
         audio_dev = fill(len(counts) * T * hop)
-        return self._spectrogram_examples(audio_dev.view(len(counts), T * hop), counts, times, False, None)
+        return self._spectrogram_examples(audio_dev.view(len(counts), T * hop), counts, times, None)
 
     def audio_to_dataset(self, audio):
         frames, frame_times = self._audio_to_frames(audio)
@@ -1077,11 +1010,19 @@ class InferenceModel(object):
         times = np.arange(num_frames) / self.spectrogram_config.frames_per_second
         return frames, times
 
-    def preprocess(self, ds, host_inputs: bool = True) -> List[Dict[str, Any]]:
+    def preprocess(self, ds) -> List[Dict[str, Any]]:
         """split_tokens_to_inputs_length + add_dummy_targets + compute_spectrograms
-        (preprocessors.py:53-57,613-618), batched over all segments in one kernel launch.
-        host_inputs=False (what `__call__` / `transcribe_many` pass): the log-mel is left on the device only -- the examples'
-        'inputs' are None -- because the engine reads it there and nothing on that path looks at the host copy."""
+        (preprocessors.py:53-57,613-618), batched over all segments in one kernel launch.  The examples carry host
+        arrays, as the reference's preprocess returns them; the transcribing methods take `_examples`, whose log-mel
+        stays on the device, because the engine reads it there and nothing on that path looks at a host copy."""
+        examples, logmel = self._dataset_examples(ds)
+        logmel = logmel.cpu().numpy()
+        for s, ex in enumerate(examples):
+            ex["inputs"] = logmel[s, : len(ex["input_times"])]
+        return examples
+
+    def _dataset_examples(self, ds):
+        """`preprocess` up to the frontend launch -> (examples with 'inputs' None, their log-mel on the device)"""
         import torch
         frames, times = ds["inputs"], ds["input_times"]
         T, hop = self.inputs_length, self.spectrogram_config.hop_width
@@ -1090,27 +1031,23 @@ class InferenceModel(object):
         for s in range(len(counts)):
             chunk = frames[s * T:(s + 1) * T]
             audio[s, : chunk.size] = chunk.reshape(-1)
-        return self._spectrogram_examples(torch.from_numpy(audio).cuda(), counts, times, host_inputs, audio)
+        return self._spectrogram_examples(torch.from_numpy(audio).cuda(), counts, times, audio)
 
     def _segment_counts(self, n_frames: int) -> List[int]:
         """frames of each `inputs_length`-frame segment (split_tokens_to_inputs_length; the last one may be short)"""
         T = self.inputs_length
         return [min(T, n_frames - s) for s in range(0, n_frames, T)]
 
-    def _spectrogram_examples(self, audio_dev, counts, times, host_inputs: bool, audio_host):
-        """The tail of `preprocess`: one frontend launch over the [n_segments, T*hop] device samples, then the examples.
+    def _spectrogram_examples(self, audio_dev, counts, times, audio_host):
+        """One frontend launch over the [n_segments, T*hop] device samples -> (the examples, 'inputs' None, and their
+        log-mel [n_segments, T, depth] on the device).  The pair is the caller's: nothing is kept on the model.
         audio_host: the same samples on the host for 'raw_inputs' (None: not kept)."""
         T, hop = self.inputs_length, self.spectrogram_config.hop_width
-        n_seg = len(counts)
-        logmel_dev = spectrograms.compute_spectrogram_batch(audio_dev, counts, self.spectrogram_config)
-        # host_inputs=False: the device tensor is kept for the predict_tokens call that follows (and dropped by it);
-        # otherwise the examples carry host arrays, as the reference's preprocess returns them, and nothing stays pinned
-        self._logmel_dev = None if host_inputs else logmel_dev
-        logmel = logmel_dev.cpu().numpy() if host_inputs else None
-        return [{"inputs": logmel[s, : counts[s]] if host_inputs else None, "input_times": times[s * T:(s + 1) * T],
+        logmel = spectrograms.compute_spectrogram_batch(audio_dev, counts, self.spectrogram_config)
+        return [{"inputs": None, "input_times": times[s * T:(s + 1) * T],
                  "raw_inputs": None if audio_host is None else audio_host[s, : counts[s] * hop],
                  "targets": np.zeros((0,), np.int32)}
-                for s in range(n_seg)]
+                for s in range(len(counts))], logmel
 
     def postprocess(self, tokens, example):
         tokens = self._trim_eos(tokens)

@@ -37,8 +37,7 @@ def _program_tokens():
 def _second_voice_token(m, audio):
     """the token j of the module docstring, from the unmodified fixture's greedy decode of `audio`"""
     t0, t33 = _program_tokens()
-    m._examples(audio, 16000)
-    x, m._logmel_dev = m._logmel_dev, None
+    _, x = m._examples(audio, 16000)
     ids = m._predict_ids({"encoder_input_tokens": x})
     h = ids.cpu().numpy()
     n = int(max(np.flatnonzero(r == 1)[0] if (r == 1).any() else len(r) - 1 for r in h)) + 1

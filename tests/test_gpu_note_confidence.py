@@ -31,8 +31,7 @@ def trained():
 
 def _id_rows(m, audio):
     """the decoded id rows of `audio`, each up to and including its EOS: InferenceModel.score's targets"""
-    m._examples(audio, 16000)
-    x, m._logmel_dev = m._logmel_dev, None
+    _, x = m._examples(audio, 16000)
     rows = []
     for row in m._predict_ids({"encoder_input_tokens": x}).cpu().numpy():
         eos = np.flatnonzero(row == 1)
@@ -72,8 +71,7 @@ def test_scored_transcription(wav, trained, decoding):
         x_rows = np.zeros((len(rows), max(len(r) for r in rows)), np.int32)
         for i, r in enumerate(rows):
             x_rows[i, : len(r)] = r
-        m._examples(wav, 16000)
-        x, m._logmel_dev = m._logmel_dev, None
+        _, x = m._examples(wav, 16000)
         _, top_id, _ = m.model.score_segments(x, x_rows, return_top1=True)
         top_id = top_id.cpu().numpy()
         agree = np.array([top_id[s, p] == x_rows[s, p] for s, p in tr[:, 0].tolist()])

@@ -251,8 +251,7 @@ def _tuples(ns):
 
 
 def _tokens_and_times(m, make_examples):
-    examples = make_examples()
-    x, m._logmel_dev = m._logmel_dev, None
+    examples, x = make_examples()
     return x.cpu().numpy(), m.predict_tokens({"encoder_input_tokens": x}), [ex["input_times"] for ex in examples]
 
 

@@ -345,8 +345,7 @@ def test_inference_model_prompts_on_the_trained_fixture():
     audio = synthetic.synth_music(3 * 2.048 - 0.3, seed=13, device="cpu")[1]
     m = inference.InferenceModel(checkpoints.load_compact_npz(CKPT), "mt3", dtype="float32", decoding="greedy")
     plain = m(audio)
-    m._examples(audio, 16000)
-    x, m._logmel_dev = m._logmel_dev, None
+    _, x = m._examples(audio, 16000)
     ids = m._predict_ids({"encoder_input_tokens": x}).cpu().numpy()
     lead = [int(t) for t in ids[0, :min(5, _eos_at(ids[0], ids.shape[1]))]]
     assert lead and min(lead) >= 2
@@ -355,7 +354,7 @@ def test_inference_model_prompts_on_the_trained_fixture():
     tie = vocabularies.tie_section_prompt(m.codec, [])
     seen = {}
     keep = m._predict_ids
-    m._predict_ids = lambda batch: seen.setdefault("ids", keep(batch))
+    m._predict_ids = lambda batch, *a, **kw: seen.setdefault("ids", keep(batch, *a, **kw))
     try:
         m(audio, prompts=[tie, None, tie], programs=[0])                      # composes with programs=
     finally:

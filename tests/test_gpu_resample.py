@@ -143,8 +143,7 @@ def _tuples(ns):
 
 
 def _tokens_and_times(m, audio, sr):
-    examples = m._examples(audio, sr)
-    x, m._logmel_dev = m._logmel_dev, None
+    examples, x = m._examples(audio, sr)
     logmel = x.cpu().numpy()
     return logmel, m.predict_tokens({"encoder_input_tokens": x}), [ex["input_times"] for ex in examples]
 
@@ -181,8 +180,7 @@ def test_native_rate_transcription_on_the_trained_fixture():
     assert [_tuples(ns) for ns in many] == [_tuples(m(y16)), n44, n48]
     # teacher-forced scores of the same token rows
     rng = np.random.default_rng(5)
-    n_seg = len(m._examples(y44, 44100))
-    m._logmel_dev = None
+    n_seg = len(m._examples(y44, 44100)[0])
     targets = [np.concatenate([rng.integers(3, 1300, int(rng.integers(5, 60))), [1]]).astype(np.int32) for _ in range(n_seg)]
     s_a, t_a = m.score(y44, targets, True, sample_rate=44100)
     s_b, t_b = m.score(audio_io.resample(y44, 44100), targets, True)

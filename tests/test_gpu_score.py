@@ -174,8 +174,7 @@ def test_score_batch_and_inference_model_end_to_end():
     trained = checkpoints.load_compact_npz(CKPT)
     _, wav = synthetic.synth_music(3 * 2.048 + 0.5, seed=13, device="cpu")
     m = inference.InferenceModel(trained, "mt3", dtype="float32")
-    examples = m.preprocess(m.audio_to_dataset(wav), host_inputs=False)
-    x, m._logmel_dev = m._logmel_dev, None
+    examples, x = m._examples(wav, 16000)
     net = network.Transformer(m.model_config, input_length=T, max_decode_length=L, max_batch=8)
     net.load_params(trained)
     net.encode(x)
