@@ -2094,6 +2094,69 @@ int mt3_op_prepare_notes(int32_t mode, const double* d_start, const double* d_en
                          int32_t* d_out_src, int32_t* d_counts /* [n_files] */, double* d_total_time /* [n_files] */,
                          int32_t* d_scratch, int64_t scratch_words, void* stream);
 
+/* ---- note velocities: from the float32 log-mel [n_rows, n_mel] the frontend has written on the device.  Nothing is
+ * measured from the samples and no transcendental function runs on the device: every step is a gather, a float64 add in
+ * a stated order, one float64 division, a max, a rank selection or a comparison with a host-built table, so the result
+ * equals the numpy statement bit for bit (mt3_amd/velocity.py, levels_reference / velocities_reference).  Two ops over
+ * one file table; a job calls the first, then the second on its levels.
+ * FILES   file f owns the log-mel rows row0 .. row0 + n_frames - 1 (n_frames: its valid frames; the zero rows of a short
+ *   last segment and the neighbouring files' rows are never read) and the notes first .. first + n_notes - 1, the
+ *   n_pitched pitched ones first, then the drums: the file's two GROUPS.  The host sorts; the ops take sorted columns.
+ * NOTES   frame = floor(onset * frames per second), computed on the host in float64, int32; key = the pitch, or
+ *   MT3_VELOCITY_KEYS - 1 = 128 for a drum.
+ * TABLE   CSR over the 129 keys: bin_first int32 [130], bins int32 [n_bins]; row k lists the mel bins whose values make
+ *   key k's level, duplicates allowed (mt3_amd/velocity.py, harmonic_bins: per pitch the strongest mel bin of each of its
+ *   first harmonics; the drum row: every 8th bin).  The host copy is what is checked; the device copy holds the same
+ *   values and is what the kernel reads -- it still treats an offset outside [0, n_bins] as an empty row and a bin outside
+ *   [0, n_mel) as NaN, so a device copy that differs gives other levels, never a read outside the buffers.
+ * mt3_op_note_levels  THE LEVEL of a note (frame t, key k) of file f: over the frames g = t .. t + window - 1 cut to
+ *   [0, n_frames), s(g) = (the float64 sum of logmel[row0 + g][b] over the bins b of row k, added left to right in table
+ *   order) / their count; the level is the largest s(g), frames whose s is NaN skipped (fmax).  d_level is NaN -- the note
+ *   is UNMEASURED -- when t is outside [0, n_frames), row k is empty, k is outside 0 .. 128, or every s was NaN.
+ *   WORK  a note's window frames are spread over 8 neighbouring lanes of a wave (lane j: frames t + j, t + j + 8, ...),
+ *   each lane gathers its frame's bins from one row, and the 8 lanes reduce the max with three cross-lane moves; 32 notes
+ *   per workgroup, the grid follows the notes, 64 files per launch (their table rides in the kernel arguments).
+ * mt3_op_level_velocities  per (file, group), n = its measured notes: THE ANCHOR is the member level of ascending rank
+ *   floor(quantile * (n - 1)) (float64), NaN for n = 0.  d = level - anchor (float64);
+ *   velocity = 1 + #{i in 0 .. 125 : d >= d_th[i]}, d_th ASCENDING (th[v] = gamma * ln((v - 0.5) / anchor_velocity) for
+ *   v = 2 .. 127, built on the host).  An unmeasured note keeps d_velocity_in.  d_anchor, d_measured: [n_files][2].
+ *   WORK  one workgroup of 256 lanes per (file, group); the rank by a radix select on the order-preserving 64-bit image
+ *   of the level, 8 passes of 8 bits: a 256-bin histogram in LDS by integer atomics over a strided loop (a group of any
+ *   size), a sum-scan over the bins; then a binary search in d_th per note.  Integer counts: the same input gives the same
+ *   bits on every run.  No atomics on global memory.
+ * SAFETY  every index comes from the file table and the host table, checked below, or is guarded in the kernel; note
+ *   columns of any content give unspecified levels, but no read or write leaves the file's own rows and notes.
+ * MT3_ERR_INVALID, before any device work: window outside 1 .. 64; n_mel outside 1 .. 4096; n_rows, n_notes, n_files or
+ *   n_bins negative; a NULL file table with n_files > 0; a file's note range outside [0, n_notes], overlapping the one
+ *   before it or out of order; n_pitched outside 0 .. n_notes; a file's rows outside [0, n_rows]; a NULL table; a
+ *   bin_first that does not rise from 0 to n_bins; a bin outside [0, n_mel); NULL columns with n_notes > 0, a NULL
+ *   log-mel with n_rows > 0, NULL thresholds or outputs; quantile outside [0, 1] (NaN included).  n_files == 0 is MT3_OK
+ *   and launches nothing. */
+#define MT3_VELOCITY_KEYS 129
+#define MT3_VELOCITY_THRESHOLDS 126
+#define MT3_VELOCITY_MAX_WINDOW 64
+#define MT3_VELOCITY_MAX_MEL 4096
+
+typedef struct mt3_velocity_file {
+  int64_t first;                      /* the file's first note in the columns */
+  int64_t row0;                       /* the file's first row in the log-mel */
+  int32_t n_notes;
+  int32_t n_pitched;                  /* group 0: notes first .. first + n_pitched - 1; group 1 (drums): the rest */
+  int32_t n_frames;                   /* the file's valid rows */
+  int32_t reserved;
+} mt3_velocity_file;
+
+int mt3_op_note_levels(const float* d_logmel, int64_t n_rows, int32_t n_mel,
+                       const mt3_velocity_file* h_files /* [n_files] */, int32_t n_files, const int32_t* d_frame,
+                       const int32_t* d_key, int64_t n_notes, const int32_t* h_bin_first /* [130] */,
+                       const int32_t* h_bins /* [n_bins] */, const int32_t* d_bin_first, const int32_t* d_bins,
+                       int32_t n_bins, int32_t window, double* d_level /* [n_notes] */, void* stream);
+
+int mt3_op_level_velocities(const double* d_level, int64_t n_notes, const mt3_velocity_file* h_files /* [n_files] */,
+                            int32_t n_files, double quantile, const double* d_th /* [126] */,
+                            const int32_t* d_velocity_in, int32_t* d_velocity, double* d_anchor /* [n_files][2] */,
+                            int32_t* d_measured /* [n_files][2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ TOKENIZE_MAX_STRIDE = 1 << 20                  # mt3_op_tokenize_notes
 ALIGN_MAX_SHIFTS = 64                          # mt3_op_align_paths
 CONSENSUS_MAX_VOTERS, CONSENSUS_TILE, CONSENSUS_SCRATCH_WORDS_PER_NOTE = 64, 256, 4      # mt3_op_note_consensus
 NOTE_PREP_SUSTAIN, NOTE_PREP_TRIM, NOTE_PREP_TILE = 0, 1, 256                              # mt3_op_prepare_notes
+VELOCITY_KEYS, VELOCITY_THRESHOLDS, VELOCITY_MAX_WINDOW, VELOCITY_MAX_MEL = 129, 126, 64, 4096   # mt3_op_note_levels
 
 
 class Mt3Error(RuntimeError):
@@ -129,6 +130,11 @@ class ConsensusFile(C.Structure):              # mt3_consensus_file
 class NotePrepFile(C.Structure):               # mt3_note_prep_file
     _fields_ = [("first", C.c_int64), ("pedal_first", C.c_int64), ("n_notes", C.c_int32), ("n_pedal", C.c_int32),
                 ("t_last", C.c_double), ("total_time", C.c_double)]
+
+
+class VelocityFile(C.Structure):               # mt3_velocity_file
+    _fields_ = [("first", C.c_int64), ("row0", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_notes", "n_pitched", "n_frames", "reserved")]
 
 
 _P = C.c_void_p
@@ -348,6 +354,9 @@ SIGNATURES = {
                                         _P, _P, _P, C.c_int64, _P]),
     "mt3_op_prepare_notes": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, _P,
                                        _P, _P, C.c_int64, _P]),
+    "mt3_op_note_levels": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32,
+                                     C.c_int32, _P, _P]),
+    "mt3_op_level_velocities": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

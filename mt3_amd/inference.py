@@ -42,6 +42,7 @@ from . import _lib
 from . import audio_io
 from . import metrics_utils
 from . import network
+from . import note_arrays
 from . import note_sequences
 from . import sampling
 from . import spectrograms
@@ -119,6 +120,7 @@ class InferenceModel(object):
         else:
             raise ValueError("unknown model_type: %s" % model_type)
 
+        self.num_velocity_bins = num_velocity_bins      # 1: every decoded note has the same velocity (see `velocities=`)
         self.batch_size = batch_size             # the reference's 8 (NB:190): what input_shapes reports
         if schedule is None:
             schedule = "batch" if decoding == "beam" else "refill"
@@ -472,7 +474,7 @@ class InferenceModel(object):
         return torch.cat(out, 0)
 
     def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True, prompts=None,
-                 well_formed: bool = False):
+                 well_formed: bool = False, velocities=None):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
         notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`.
@@ -499,17 +501,27 @@ class InferenceModel(object):
         segments one after another.  A tie section declares at most `cap` pairs (the model's keyword; default 64).
         ValueError with prompts=, for a spec without a tie section, or when 2 * cap + 1 >= the decode length.
         `last_event_counts` holds the note decoder's invalid_events / dropped_events of the most recent call and
-        tie_overflows, the segments whose held set exceeded `cap` on its way into the next (0 unless "tied")."""
+        tie_overflows, the segments whose held set exceeded `cap` on its way into the next (0 unless "tied").
+        velocities (`__call__`, `transcribe_many`, `transcribe_wav`, `transcribe_wavs`; default None: off, and every bit
+        stays where it is): note velocities from the log-mel this job's decode has just read, still on the device
+        (`velocity.estimate`) -- the one-velocity-bin codec gives every note the same velocity (127); with
+        True, or a dict of `estimate`'s keywords (window, harmonics, gamma, quantile, anchor_velocity), each note's
+        velocity is its level at the onset relative to the file's median note.  Nothing else of the notes changes.  ValueError for a model whose
+        codec has more than one velocity bin (ismir2021): it decodes them.  For known notes: `note_velocities`."""
         return self._transcribe([functools.partial(self._examples, audio, sample_rate)], False,
-                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))[0]
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
+                                velocities=velocities)[0]
 
-    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, **rule):
+    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, velocities=None, **rule):
         """The one path from files to notes.  make_examples: one call per file that returns (its examples, its log-mel on
         the device); many and kw (programs, drums, prompts, well_formed) as `_job` reads them; rule: `_job`'s -- with
         draws=n the segments' n draws run as one job (row s * n + j of the job = draw j of segment s).  -> per file its
         NoteSequence; with draws the list of its n NoteSequences; with scored (one file) the pair (NoteSequence, scores).
-        All segments go through the engine as one job, and the job's tables are cleared on the way out."""
+        All segments go through the engine as one job, and the job's tables are cleared on the way out.  velocities (not
+        with draws): the keywords of `velocity.estimate`, run on the job's log-mel after the decode, while it is still on
+        the device."""
         import torch
+        velocities = self._velocity_keywords(velocities)
         files = [make() for make in make_examples]
         if not files:
             return []
@@ -536,9 +548,32 @@ class InferenceModel(object):
                 at += len(examples)
                 out.append(runs if job.draws else runs[0])
             self._count_events(results, sum(overflows))
+            if velocities is not None:
+                from . import velocity
+                # each file's rows of x beside its frame count: a short last segment's zero rows are not the file's
+                at = note_arrays.offsets([len(examples) for examples in per_file])
+                out = velocity.estimate(
+                    [(x[at[f]: at[f + 1]], sum(len(ex["input_times"]) for ex in examples))
+                     for f, examples in enumerate(per_file)], out,
+                    frames_per_second=self.spectrogram_config.frames_per_second, **velocities)
             if scored:
                 out = [(out[0], self._note_scores(x, ids, results[0]["note_tokens"]))]
         return out
+
+    def _velocity_keywords(self, velocities):
+        """the `velocities=` keyword of the transcribing methods -> `velocity.estimate`'s keywords, or None for off"""
+        if velocities is None or velocities is False:
+            return None
+        if self.num_velocity_bins > 1:
+            raise ValueError("velocities= is for a codec with one velocity bin: this model decodes its %d velocity bins"
+                             % self.num_velocity_bins)
+        if velocities is True:
+            return {}
+        unknown = set(velocities) - {"window", "harmonics", "gamma", "quantile", "anchor_velocity"}
+        if unknown:
+            raise ValueError("velocities= takes window, harmonics, gamma, quantile, anchor_velocity, got %s"
+                             % ", ".join(sorted(map(repr, unknown))))
+        return dict(velocities)
 
     def _draws_in_one_job(self, well_formed) -> bool:
         """whether `sample` runs its draws as one engine job: the refill schedule, and not well_formed="tied" (whose
@@ -617,12 +652,14 @@ class InferenceModel(object):
         results = consensus.consensus(samples, tolerance=tolerance, min_votes=min_votes)
         return [(r.notes, r, s) if return_votes else r.notes for r, s in zip(results, samples)]
 
-    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False):
+    def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False,
+                       velocities=None):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
         return self._transcribe([functools.partial(self._wav_examples, wav_data)], False,
-                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))[0]
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
+                                velocities=velocities)[0]
 
     def _count_events(self, results, tie_overflows: int):
         """the note decoder's counts of the call that just ended, summed over its files, and its wavefront's overflows"""
@@ -920,7 +957,7 @@ class InferenceModel(object):
         return out
 
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
-                        drums=True, prompts=None, well_formed: bool = False) -> List[Any]:
+                        drums=True, prompts=None, well_formed: bool = False, velocities=None) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
@@ -928,17 +965,37 @@ class InferenceModel(object):
         NoteSequence per file, each identical to `self(audio)`.  sample_rates: one rate per file (default: all 16 kHz),
         as for `__call__`.  programs / drums: as for `__call__`, or one entry per file (programs=[[0], [33]]): every segment
         of a file carries its file's mask, so one job holds files with different instruments.  prompts: one `__call__`-style
-        sequence (or None) per file."""
+        sequence (or None) per file.  velocities: as for `__call__`, one `velocity.estimate` call for the job; every file's
+        notes are ranked against its own anchor."""
         return self._transcribe([functools.partial(self._examples, audio, sr)
                                  for audio, sr in zip(audios, self._rates(sample_rates, len(audios)))], True,
-                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
+                                velocities=velocities)
 
     def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None,
-                        well_formed: bool = False) -> List[Any]:
+                        well_formed: bool = False, velocities=None) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
-        `self.transcribe_wav(wav)`.  programs / drums / prompts: as for `transcribe_many`."""
+        `self.transcribe_wav(wav)`.  programs / drums / prompts / velocities: as for `transcribe_many`."""
         return self._transcribe([functools.partial(self._wav_examples, wav) for wav in wavs], True,
-                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed))
+                                dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
+                                velocities=velocities)
+
+    def note_velocities(self, audio, ns, *, sample_rate: int = SAMPLE_RATE, **kw):
+        """Known notes `ns` with velocities estimated from `audio`: `note_velocities_many([(audio, ns)])[0]`; with
+        return_levels the pair (NoteSequence, its record)."""
+        out = self.note_velocities_many([(audio, ns)], sample_rates=[sample_rate], **kw)
+        return (out[0][0], out[1][0]) if kw.get("return_levels") else out[0]
+
+    def note_velocities_many(self, pairs, *, sample_rates: Optional[Sequence[int]] = None, **kw):
+        """(audio, NoteSequence) pairs as one job: the frontend of `__call__` on each audio, then one `velocity.estimate`
+        call on the log-mels, which stay on the device -> per pair a new NoteSequence, the notes of `ns` with the velocity
+        their level at the onset gives them (a note outside the audio keeps its own).  kw: `estimate`'s keywords (window,
+        harmonics, gamma, quantile, anchor_velocity, return_levels).  Any model type: the notes are given, not decoded."""
+        from . import velocity
+        pairs = list(pairs)
+        _, feats, n_frames = self._paired_examples(pairs, self._rates(sample_rates, len(pairs)), False)
+        return velocity.estimate(list(zip(feats, n_frames)), [ns for _, ns in pairs],
+                                 frames_per_second=self.spectrogram_config.frames_per_second, **kw)
 
     @staticmethod
     def pianoroll(ns, fps: float = 62.5):

@@ -8,6 +8,7 @@
                                  [--align-midi DIR [--align-max-shift S] [--align-step S] [--align-smoothness L]]
                                  [--consensus N [--consensus-min-votes M] [--consensus-tolerance S]]
                                  [--sustain] [--trim-overlaps]
+                                 [--velocities [--velocity-gamma G] [--velocity-anchor V]]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -51,6 +52,11 @@ start_time, end_time, pitch, program, is_drum, votes and members.  (--well-forme
 reference prepares its targets (`mt3_amd.note_prep.prepare`, on the device, all files of an option as one job): --sustain
 applies each file's sustain pedal (controller 64) to its notes' ends -- what a piano model such as ismir2021 was trained
 on; --trim-overlaps then trims overlapping notes of one pitch and program and drops the empty ones.
+--velocities gives every note a velocity estimated from the log-mel the decode has just read (`InferenceModel(...,
+velocities=)`, `mt3_amd.velocity.estimate`: the note's level at its onset against the file's median note, which gets
+--velocity-anchor, default 80; amplitude ~ (velocity / 127)^G with --velocity-gamma G, default 2.0) before NAME.mid,
+--render and --pianoroll are written; the mt3 model alone gives every note the same velocity, 127.  With --consensus or
+--confidences the estimate runs on the finished notes (`InferenceModel.note_velocities_many`).  Not with --model ismir2021.
 """
 from __future__ import annotations
 
@@ -132,6 +138,14 @@ def plan(argv=None):
     ap.add_argument("--trim-overlaps", action="store_true",
                     help="--score-against / --score-midi / --align-midi: trim overlapping notes of one pitch and program "
                          "in each MIDI file read, and drop the empty ones")
+    ap.add_argument("--velocities", action="store_true",
+                    help="estimate every note's velocity from the log-mel at its onset, relative to the file's median note "
+                         "(the mt3 model gives every note the same velocity); applied before NAME.mid, --render and --pianoroll "
+                         "are written")
+    ap.add_argument("--velocity-gamma", type=float, default=None, metavar="G",
+                    help="--velocities: amplitude ~ (velocity / 127)^G (default 2.0; 1.0 is what --render plays)")
+    ap.add_argument("--velocity-anchor", type=float, default=None, metavar="V",
+                    help="--velocities: the velocity of the file's median note (default 80)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -160,6 +174,17 @@ def plan(argv=None):
             ap.error("--consensus-tolerance takes seconds >= 0")
         if args.confidences:
             ap.error("--consensus and --confidences do not go together")
+    if not args.velocities:
+        for name in ("velocity_gamma", "velocity_anchor"):
+            if getattr(args, name) is not None:
+                ap.error("--%s needs --velocities" % name.replace("_", "-"))
+    else:
+        if args.model != "mt3":
+            ap.error("--velocities is for --model mt3: ismir2021 decodes its velocities")
+        for name in ("velocity_gamma", "velocity_anchor"):
+            v = getattr(args, name)
+            if v is not None and not (math.isfinite(v) and v > 0):
+                ap.error("--%s takes a finite number > 0" % name.replace("_", "-"))
     if (args.sustain or args.trim_overlaps) and args.score_against is None and args.score_midi is None and \
             args.align_midi is None:
         ap.error("--sustain and --trim-overlaps need --score-against, --score-midi or --align-midi")
@@ -241,6 +266,7 @@ def main(argv=None) -> int:
                                          num_beams=args.num_beams, temperature=args.temperature, top_k=args.top_k,
                                          top_p=args.top_p, seed=args.seed)
         votes = None
+        velocities = velocity_keywords(args)
         if args.consensus is not None:
             from . import audio_io
             # every input file's N draws as ONE engine job (well_formed="tied" keeps its loop of N decodes)
@@ -250,14 +276,22 @@ def main(argv=None) -> int:
                                          return_votes=True, programs=args.programs, drums=args.drums,
                                          well_formed=args.well_formed)
             sequences, scores, votes = [ns for ns, _, _ in voted], None, [rec for _, rec, _ in voted]
+            if velocities is not None:
+                sequences = model.note_velocities_many(list(zip([s for s, _ in decoded], sequences)),
+                                                       sample_rates=[r for _, r in decoded], **velocities)
         elif args.confidences:
             scored = [model.transcribe_wav_scored(path, programs=args.programs, drums=args.drums,
                                                   well_formed=args.well_formed)
                       for path in args.inputs]
             sequences, scores = [ns for ns, _ in scored], [sc for _, sc in scored]
+            if velocities is not None:
+                from . import audio_io
+                decoded = [audio_io.read_wav(path) for path in args.inputs]
+                sequences = model.note_velocities_many(list(zip([s for s, _ in decoded], sequences)),
+                                                       sample_rates=[r for _, r in decoded], **velocities)
         else:
             sequences, scores = model.transcribe_wavs(args.inputs, programs=args.programs, drums=args.drums,
-                                                      well_formed=args.well_formed), None
+                                                      well_formed=args.well_formed, velocities=velocities), None
         rolls = None
         if args.pianoroll is not None:
             import numpy as np
@@ -327,6 +361,14 @@ def main(argv=None) -> int:
         with open(alignment_path(outputs), "w") as f:
             json.dump([alignment_record(path, rec) for path, rec in zip(args.inputs, aligned)], f, indent=1)
     return 0
+
+
+def velocity_keywords(args):
+    """--velocities [--velocity-gamma G --velocity-anchor V] -> the `velocities=` keyword of the model: None, or a dict"""
+    if not args.velocities:
+        return None
+    named = {"gamma": args.velocity_gamma, "anchor_velocity": args.velocity_anchor}
+    return {k: v for k, v in named.items() if v is not None}
 
 
 def known_notes(directory: str, args) -> list:
