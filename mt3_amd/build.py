@@ -39,7 +39,7 @@ def _stale(out: str, deps) -> bool:
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs.append(os.path.join(ROOT, "include", "mt3_hip.h"))
+    hs += [os.path.join(ROOT, "include", f) for f in ("mt3_hip.h", "mt3_hip_debug.h")]
     return hs
 
 

@@ -109,7 +109,8 @@ struct LayerDev {
   float2* cross_scale = nullptr;   // [B][H][T]
 };
 
-// Variant bits of one decode step (index of a captured step graph): 1 / 2 = mt3_debug_engine_decode's skipped kernels,
+// Variant bits of one decode step (part of the key of its captured graph, GroupGraph): 1 / 2 = mt3_debug_engine_decode's
+// skipped kernels (no self-attention / no cross-attention: differential profiling only),
 // 4 = beam-1 token selection, 8 = teacher forcing, 16 = row retirement (finished slots cost nothing, the slot map is
 // in use), 32 = the synthetic EOS schedule (mt3_debug_engine_set_eos_schedule)
 // 64 = in-flight batching (mt3_engine_transcribe: finished slots restart on new segments, the slot -> segment map is in use)
@@ -124,13 +125,13 @@ struct LayerDev {
 // 2048 = the note rule (mt3_engine_set_note_grammar; always with 512): the step ends with the NOTES token / sample / beam
 // kernel, so steps with the note rule never share a captured graph with other steps
 constexpr int kVarBeam = 4, kVarForced = 8, kVarRetire = 16, kVarEos = 32, kVarStream = 64, kVarMask = 128,
-              kVarPrompt = 256, kVarGrammar = 512, kVarSample = 1024, kVarNotes = 2048, kNumVariants = 4096;
-// not a step variant of its own (never an index into graph_exec): set in GroupRun::variant when the decode runs as SEVERAL
-// row groups, so that a step knows it runs beside other groups' launches (GemmArgs::concurrent) and the group-graph cache
-// keeps such steps apart from a lone stream's steps of the same shape
+              kVarPrompt = 256, kVarGrammar = 512, kVarSample = 1024, kVarNotes = 2048;
+// not a rule of the step itself: set in GroupRun::variant when the decode runs as SEVERAL row groups, so that a step
+// knows it runs beside other groups' launches (GemmArgs::concurrent) and the step-graph cache keeps such steps apart
+// from a lone stream's steps of the same shape
 constexpr int kVarBeside = 4096;
-// not an index into graph_exec either: a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the
-// number of beams rides in bits kVarBeamsShift .. +3 so that the group-graph cache keeps different k apart
+// a step of mt3_engine_decode_beams (always with kVarRetire's slot -> row map); the number of beams rides in bits
+// kVarBeamsShift .. +3 so that the step-graph cache keeps different k apart
 constexpr int kVarBeams = 8192, kVarBeamsShift = 14;
 constexpr int kMaxGroups = 4;
 // staging ring of mt3_engine_transcribe: cross-attention K/V of segments that wait for a slot, kStageChunks chunks of up
@@ -154,9 +155,9 @@ struct Worker {
   bool has_job = false, quit = false;
 };
 
-// a captured decode step of rows [row0, row0 + rows) of a `batch`-row decode
+// a captured decode step of rows [row0, row0 + rows) of a `batch`-row decode, dealt to `chains` parallel branches
 struct GroupGraph {
-  int variant, batch, row0, rows, slot, max_len;
+  int variant, batch, row0, rows, slot, max_len, chains;
   hipGraph_t graph;
   hipGraphExec_t exec;
 };
@@ -326,7 +327,7 @@ struct mt3_engine {
   int* cs_perm = nullptr;        // [max_batch + kMaxChains]: rows + 1 entries per group
   int compactions = 0;           // compactions of the most recent decode (all groups; written at the end of the decode)
   std::atomic<int> compactions_now{0};
-  // step graphs of single row groups (the single-stream schedule is the group [0, batch))
+  // every captured step graph: one per row group and shape (the single-stream schedule is the group [0, batch))
   std::vector<GroupGraph> group_graphs;
   std::mutex graph_mu;
   Worker* workers[kMaxGroups] = {};
@@ -365,13 +366,11 @@ struct mt3_engine {
   int last_groups = 1;           // row groups of the most recent decode
 
   int cur_batch = 0;             // batch of the last encode
-  hipStream_t cap_stream[8] = {};     // one capture stream per chain (kMaxChains)
+  // step graphs are captured on engine-owned streams (the caller's may be the legacy default stream, which cannot be
+  // captured), under graph_mu: a row group's on cap_stream[its slot], a step of several chains on one stream per chain,
+  // forked from and joined to cap_stream[0] through cap_event (group_graph)
+  hipStream_t cap_stream[8] = {};     // kMaxChains
   hipEvent_t cap_event[8] = {};
-  // one captured decode step per (batch, variant); variant bits: 1 = no self-attention, 2 = no
-  // cross-attention (differential profiling only), 4 = beam-1 token selection, 8 = teacher forcing
-  hipGraphExec_t graph_exec[kNumVariants][9] = {};   // [variant][chains]: the step graph with `chains` parallel branches
-  hipGraph_t graph[kNumVariants][9] = {};
-  int graph_batch = 0;
 
   // Teacher-forced scoring (mt3_engine_score): a workspace of score_cap segments x score_Lp rows, allocated by the first
   // call (and grown by mt3_debug_engine_set_score_chunk); an engine that never scores keeps its device bytes
@@ -909,7 +908,8 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   float* y_ss = in.y_ss;
   // this step belongs to one of several row groups / graph chains (GemmArgs::concurrent: every residual add and the
   // GEGLU launch).  Under row retirement rows < B_total also holds for a LONE stream after a compaction, hence the
-  // explicit bit
+  // explicit bit.  Graph chains never carry the bit (kVarBeside is set only for a job of several row groups,
+  // run_one_group, and a chains job is one group), so under row retirement they take the lone stream's tiles: meant so.
   GemmExtra ex;
   ex.concurrent = ((skip & kVarBeside) || (!retire && rows < B_total)) ? 1 : 0;
   char* qkv_d = static_cast<char*>(e->qkv_d) + static_cast<size_t>(row0) * 3 * hd * es;
@@ -1097,17 +1097,27 @@ int enqueue_chain_op(mt3_engine* e, int row0, int rows, int B_total, int skip, i
   }
 }
 
-int enqueue_chain_step(mt3_engine* e, int row0, int rows, int B_total, int skip, hipStream_t s, int done_slot = 0) {
-  for (int op = 0, n = chain_num_ops(e); op < n; ++op)
-    MT3_TRY(enqueue_chain_op(e, row0, rows, B_total, skip, op, s, done_slot));
-  return MT3_OK;
-}
-
 // rows of chain k when `B` rows are dealt to `n` chains
 inline void chain_rows(int B, int n, int k, int* row0, int* rows) {
   const int q = B / n, r = B % n;
   *row0 = k * q + (k < r ? k : r);
   *rows = q + (k < r ? 1 : 0);
+}
+
+// chain k of the step of slots [row0, row0 + rows) of a B_total-row decode that is dealt to `chains` chains, on stream s
+int enqueue_chain_step(mt3_engine* e, int row0, int rows, int B_total, int skip, int chains, int k, hipStream_t s,
+                       int done_slot) {
+  int r0, n;
+  chain_rows(rows, chains, k, &r0, &n);
+  for (int op = 0, ops = chain_num_ops(e); op < ops; ++op)
+    MT3_TRY(enqueue_chain_op(e, row0 + r0, n, B_total, skip, op, s, done_slot));
+  return MT3_OK;
+}
+
+// the whole step on ONE stream, chains back to back: the direct launch, and what the capture of a one-chain step records
+int enqueue_step(mt3_engine* e, int row0, int rows, int B_total, int skip, int chains, hipStream_t s, int done_slot) {
+  for (int k = 0; k < chains; ++k) MT3_TRY(enqueue_chain_step(e, row0, rows, B_total, skip, chains, k, s, done_slot));
+  return MT3_OK;
 }
 
 int chains_for(const mt3_engine* e, int B, int requested) {
@@ -1117,78 +1127,12 @@ int chains_for(const mt3_engine* e, int B, int requested) {
   return n;
 }
 
-// direct (un-captured) launch of one whole step on one stream: chains back to back
-int enqueue_decode_step(mt3_engine* e, int B, int skip, int n, hipStream_t s) {
-  for (int k = 0; k < n; ++k) {
-    int row0, rows;
-    chain_rows(B, n, k, &row0, &rows);
-    MT3_TRY(enqueue_chain_step(e, row0, rows, B, skip, s));
-  }
-  return MT3_OK;
-}
-
-void drop_graph(mt3_engine* e) {
-  for (int v = 0; v < kNumVariants; ++v)
-    for (int n = 0; n < 9; ++n) {
-      if (e->graph_exec[v][n]) (void)hipGraphExecDestroy(e->graph_exec[v][n]);
-      if (e->graph[v][n]) (void)hipGraphDestroy(e->graph[v][n]);
-      e->graph_exec[v][n] = nullptr;
-      e->graph[v][n] = nullptr;
-    }
-  e->graph_batch = 0;
-}
-
-// capture one decode step for batch B (on the engine's private stream: the caller's stream may be
-// the legacy default stream, which cannot be captured)
-int ensure_graph(mt3_engine* e, int B, int skip, int n) {
-  if (e->graph_batch != B) drop_graph(e);
-  if (e->graph_exec[skip][n]) return MT3_OK;
-  for (int k = 0; k < n; ++k) {
-    if (!e->cap_stream[k]) MT3_HIP_CHECK(hipStreamCreateWithFlags(&e->cap_stream[k], hipStreamNonBlocking));
-    if (!e->cap_event[k]) MT3_HIP_CHECK(hipEventCreateWithFlags(&e->cap_event[k], hipEventDisableTiming));
-  }
-  hipStream_t origin = e->cap_stream[0];
-  MT3_HIP_CHECK(hipStreamBeginCapture(origin, hipStreamCaptureModeThreadLocal));
-  int rc = MT3_OK;
-  hipError_t he = hipSuccess;
-  // fork: every other chain's stream joins the capture by waiting on an event of the origin
-  if (n > 1) he = hipEventRecord(e->cap_event[0], origin);
-  for (int k = 1; k < n && he == hipSuccess; ++k) he = hipStreamWaitEvent(e->cap_stream[k], e->cap_event[0], 0);
-  for (int k = 0; k < n && he == hipSuccess && rc == MT3_OK; ++k) {
-    int row0, rows;
-    chain_rows(B, n, k, &row0, &rows);
-    rc = enqueue_chain_step(e, row0, rows, B, skip, e->cap_stream[k]);
-  }
-  // join
-  for (int k = 1; k < n && he == hipSuccess && rc == MT3_OK; ++k) {
-    he = hipEventRecord(e->cap_event[k], e->cap_stream[k]);
-    if (he == hipSuccess) he = hipStreamWaitEvent(origin, e->cap_event[k], 0);
-  }
-  hipGraph_t g = nullptr;
-  const hipError_t end = hipStreamEndCapture(origin, &g);
-  if (rc != MT3_OK || he != hipSuccess || end != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    if (rc != MT3_OK) return rc;
-    return mt3::fail(MT3_ERR_HIP, std::string("decode graph capture: ") +
-                                      hipGetErrorString(he != hipSuccess ? he : end));
-  }
-  e->graph[skip][n] = g;
-  MT3_HIP_CHECK(hipGraphInstantiate(&e->graph_exec[skip][n], g, nullptr, nullptr, 0));
-  e->graph_batch = B;
-  return MT3_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 static void workers_stop(mt3_engine* e);
 static void drop_group_graphs(mt3_engine* e);
-// every captured step graph: what a setup call does when a graph may hold an address or a constant it replaces
-static void drop_step_graphs(mt3_engine* e) {
-  drop_graph(e);
-  drop_group_graphs(e);
-}
 
 int mt3_engine_create(const mt3_engine_config* cfg, mt3_engine** out) {
   if (!cfg || !out) return mt3::fail(MT3_ERR_INVALID, "mt3_engine_create: null argument");
@@ -1236,7 +1180,7 @@ int mt3_engine_create(const mt3_engine_config* cfg, mt3_engine** out) {
 void mt3_engine_destroy(mt3_engine* e) {
   if (!e) return;
   workers_stop(e);                 // joins a decode that is still in flight
-  drop_step_graphs(e);
+  drop_group_graphs(e);
   for (int k = 0; k < kMaxChains; ++k) {
     if (e->cap_stream[k]) (void)hipStreamDestroy(e->cap_stream[k]);
     if (e->cap_event[k]) (void)hipEventDestroy(e->cap_event[k]);
@@ -1667,43 +1611,13 @@ static void workers_stop(mt3_engine* e) {
   }
 }
 
+// every captured step graph: what a setup call does when a graph may hold an address or a constant it replaces
 static void drop_group_graphs(mt3_engine* e) {
   for (GroupGraph& g : e->group_graphs) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (g.graph) (void)hipGraphDestroy(g.graph);
   }
   e->group_graphs.clear();
-}
-
-// The captured step of slots [row0, row0 + rows) (nullptr: capture failed, the caller launches directly).  Captured on
-// an engine-owned stream in thread-local mode -- several group threads may be here at once, the cache is guarded.
-static hipGraphExec_t group_graph(mt3_engine* e, int variant, int batch, int row0, int rows, int slot) {
-  std::lock_guard<std::mutex> lk(e->graph_mu);
-  const int max_len = (variant & kVarStream) ? e->stream_max_len : 0;      // baked into the step's token kernel
-  for (const GroupGraph& g : e->group_graphs)
-    if (g.variant == variant && g.batch == batch && g.row0 == row0 && g.rows == rows && g.slot == slot &&
-        g.max_len == max_len)
-      return g.exec;
-  if (!e->cap_stream[slot] && hipStreamCreateWithFlags(&e->cap_stream[slot], hipStreamNonBlocking) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  hipStream_t cs = e->cap_stream[slot];
-  if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  const int rc = enqueue_chain_step(e, row0, rows, batch, variant, cs, slot);
-  hipGraph_t g = nullptr;
-  hipGraphExec_t x = nullptr;
-  const hipError_t end = hipStreamEndCapture(cs, &g);
-  if (rc != MT3_OK || end != hipSuccess || hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  e->group_graphs.push_back(GroupGraph{variant, batch, row0, rows, slot, max_len, g, x});
-  return x;
 }
 
 // One row group's decode loop: slots [row0, row0 + rows) of a `batch`-row decode on stream `s` (the single-stream
@@ -1716,7 +1630,52 @@ struct GroupRun {
   float* d_step_logits;
   int ran;
   bool used_graph;
+  int chains = 1;             // graph chains of every step (GroupJob::chains)
 };
+
+// The captured step of the first `rows` slots of group r (nullptr: capture failed, the caller launches directly).
+// Captured on engine-owned streams in thread-local mode -- several group threads may be here at once, so graph_mu is held
+// throughout: it guards the cache and the capture streams.  A step of one chain is captured on the group's own stream.
+// A step of several is the only graph here with parallel branches: chain k is captured on cap_stream[k], which joins the
+// capture by waiting for an event of the origin (cap_stream[0]) and is joined back to it through an event of its own.
+static hipGraphExec_t group_graph(mt3_engine* e, const GroupRun& r, int rows) {
+  std::lock_guard<std::mutex> lk(e->graph_mu);
+  const int max_len = (r.variant & kVarStream) ? e->stream_max_len : 0;    // baked into the step's token kernel
+  for (const GroupGraph& g : e->group_graphs)
+    if (g.variant == r.variant && g.batch == r.batch && g.row0 == r.row0 && g.rows == rows && g.slot == r.slot &&
+        g.max_len == max_len && g.chains == r.chains)
+      return g.exec;
+  const int n = r.chains;
+  hipStream_t* cs = e->cap_stream + (n > 1 ? 0 : r.slot);
+  hipError_t he = hipSuccess;
+  for (int k = 0; k < n && he == hipSuccess; ++k) {
+    if (!cs[k]) he = hipStreamCreateWithFlags(&cs[k], hipStreamNonBlocking);
+    if (n > 1 && !e->cap_event[k] && he == hipSuccess) he = hipEventCreateWithFlags(&e->cap_event[k], hipEventDisableTiming);
+  }
+  if (he != hipSuccess || hipStreamBeginCapture(cs[0], hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  int rc = MT3_OK;
+  if (n > 1) he = hipEventRecord(e->cap_event[0], cs[0]);                                        // fork
+  for (int k = 1; k < n && he == hipSuccess; ++k) he = hipStreamWaitEvent(cs[k], e->cap_event[0], 0);
+  for (int k = 0; k < n && he == hipSuccess && rc == MT3_OK; ++k)
+    rc = enqueue_chain_step(e, r.row0, rows, r.batch, r.variant, n, k, cs[k], r.slot);
+  for (int k = 1; k < n && he == hipSuccess && rc == MT3_OK; ++k) {                              // join
+    he = hipEventRecord(e->cap_event[k], cs[k]);
+    if (he == hipSuccess) he = hipStreamWaitEvent(cs[0], e->cap_event[k], 0);
+  }
+  hipGraph_t g = nullptr;
+  hipGraphExec_t x = nullptr;
+  const hipError_t end = hipStreamEndCapture(cs[0], &g);       // (fails, and ends the capture, if a chain was left unjoined)
+  if (rc != MT3_OK || he != hipSuccess || end != hipSuccess || hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  e->group_graphs.push_back(GroupGraph{r.variant, r.batch, r.row0, rows, r.slot, max_len, n, g, x});
+  return x;
+}
 
 // ---- sleeping waits (mt3_engine::wait_ev)
 static hipEvent_t wait_event(mt3_engine* e, int slot, int which) {
@@ -1809,7 +1768,7 @@ static int run_group(mt3_engine* e, GroupRun& r) {
   Throttle throttle{e, wslot, r.s};
   for (int t = 0; t < r.num_steps; ++t) {
     if (r.use_graph && exec_rows != cur) {
-      exec = group_graph(e, r.variant, r.batch, r.row0, cur, r.slot);
+      exec = group_graph(e, r, cur);
       exec_rows = cur;
       if (!exec) {                               // direct launches give the same ids; the fallback is RECORDED
         r.use_graph = r.used_graph = false;
@@ -1817,7 +1776,7 @@ static int run_group(mt3_engine* e, GroupRun& r) {
       }
     }
     if (r.use_graph) MT3_HIP_CHECK(hipGraphLaunch(exec, r.s));
-    else MT3_TRY(enqueue_chain_step(e, r.row0, cur, r.batch, r.variant, r.s, r.slot));
+    else MT3_TRY(enqueue_step(e, r.row0, cur, r.batch, r.variant, r.chains, r.s, r.slot));
     ++r.ran;
     if (whole && t == 0 && r.d_first_logits)
       MT3_HIP_CHECK(hipMemcpyAsync(r.d_first_logits, e->logits, static_cast<size_t>(r.batch) * c.vocab_size * 4,
@@ -1832,7 +1791,9 @@ static int run_group(mt3_engine* e, GroupRun& r) {
       MT3_HIP_CHECK(wait_stream(e, wslot, r.s));
       const int live = r.rows - e->h_pinned[r.slot];
       if (live <= 0) break;
-      if (retire && !(r.variant & kVarBeams)) {    // beam groups stay where they are (their rows are k-slot units)
+      // beam groups stay where they are (their rows are k-slot units), and so do graph chains (the deal of the rows is
+      // part of the captured step)
+      if (retire && !(r.variant & kVarBeams) && r.chains == 1) {
         int want = (live + 31) & ~31;
         if (want > r.rows) want = r.rows;
         if (want < cur) {                        // the live rows fit fewer GEMM row tiles: move them to the front
@@ -1886,6 +1847,8 @@ struct GroupJob {
   hipStream_t s;              // the caller's stream
   float* d_first_logits;      // (GroupRun: the caller's-stream schedule only)
   float* d_step_logits;
+  int chains = 1;             // graph chains: every step of the one group on the caller's stream deals its rows to `chains`
+                              // parallel branches of its graph (chains_for; launched directly they run back to back)
 };
 
 // What tells the three streaming entry points apart (run_stream_job; the k-beam job is the one whose variant has kVarBeams)
@@ -1902,7 +1865,8 @@ struct StreamJob {
   bool skip_encoder;          // mt3_debug_engine_transcribe's differential timing (produce_chunks)
 };
 
-// Starts a job: the step-graph cache is trimmed (no worker is running here) and e->pending is the job's
+// Starts a job: the step-graph cache is trimmed (no worker is running here; the bound covers every kind of step graph,
+// those of graph chains included) and e->pending is the job's
 static PendingDecode& begin_job(mt3_engine* e) {
   if (e->group_graphs.size() > 96) drop_group_graphs(e);
   e->pending = PendingDecode();
@@ -1920,6 +1884,7 @@ static int run_one_group(mt3_engine* e, const GroupJob& j, int g, const GroupLoo
   r.rows *= j.unit;
   r.batch = j.units * j.unit;
   r.variant = j.variant | (j.groups > 1 ? kVarBeside : 0);
+  r.chains = j.chains;
   r.num_steps = j.num_steps;
   r.slot = g;
   r.early = j.early;
@@ -2135,8 +2100,7 @@ static int run_decode_job(mt3_engine* e, GroupJob j, int flags, bool caller_stre
   const GroupLoop loop = [e](GroupRun& r) { return run_group(e, r); };
   int groups = row_groups_for(c, j.units * j.unit, j.early);
   if (groups > j.units) groups = 1;
-  if (groups > 1 && !caller_stream_only && !(flags & MT3_DECODE_SINGLE_STREAM) && c.decode_chains <= 1 &&
-      !(c.options & MT3_OPT_NO_ROW_GROUPS)) {
+  if (groups > 1 && !caller_stream_only && !(flags & MT3_DECODE_SINGLE_STREAM) && !(c.options & MT3_OPT_NO_ROW_GROUPS)) {
     if (ensure_group_streams(e, groups) == MT3_OK) {
       MT3_HIP_CHECK(hipEventRecord(e->part_begin, j.s));
       j.groups = groups;
@@ -2196,43 +2160,13 @@ static int decode_impl(mt3_engine* e, int32_t batch, int32_t num_steps, int32_t 
   p.d_ids = d_ids;
   p.s = s;
   const bool use_graph = !(flags & MT3_DECODE_NO_GRAPH);
-  const int req_chains = (flags >> 8) & 0xF;
-  const GroupJob j{batch, 1, 1, variant, num_steps, early, use_graph, false, s, d_first_logits, d_step_logits};
-  // (graph chains come from the flags or the engine's decode_chains, and either keeps the job off the row groups)
-  const int chains = chains_for(e, batch, req_chains);
-  if (chains > 1) {
-    // the step graph with `chains` parallel branches (r1's schedule, kept for comparison): inline on the caller's stream
-    bool graph = use_graph;
-    if (graph && ensure_graph(e, batch, variant, chains) != MT3_OK) {
-      graph = false;
-      ++e->graph_fallbacks;
-    }
-    p.used_graph[0] = graph;
-    int ran = 0;
-    for (int t = 0; t < num_steps; ++t) {
-      if (graph) MT3_HIP_CHECK(hipGraphLaunch(e->graph_exec[variant][chains], s));
-      else MT3_TRY(enqueue_decode_step(e, batch, variant, chains, s));
-      ++ran;
-      if (t == 0 && d_first_logits)
-        MT3_HIP_CHECK(hipMemcpyAsync(d_first_logits, e->logits, static_cast<size_t>(batch) * c.vocab_size * 4,
-                                     hipMemcpyDeviceToDevice, s));
-      if (d_step_logits)
-        MT3_HIP_CHECK(hipMemcpyAsync(d_step_logits + static_cast<size_t>(t) * batch * c.vocab_size, e->logits,
-                                     static_cast<size_t>(batch) * c.vocab_size * 4, hipMemcpyDeviceToDevice, s));
-      if (early && (t % 32 == 31)) {
-        MT3_HIP_CHECK(hipMemcpyAsync(e->h_pinned, e->n_done, 4, hipMemcpyDeviceToHost, s));
-        MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));
-        if (e->h_pinned[0] >= batch) break;
-      }
-    }
-    p.ran[0] = ran;
-    p.active = true;
-    if (async) return MT3_OK;
-    return decode_finish(e, h_steps_run);
-  }
-  // the row-group schedule (see mt3_engine::part_stream) unless the caller asked for graph chains, or for what lives on
-  // the caller's stream: skipped kernels, teacher forcing, logits
-  return run_decode_job(e, j, flags, req_chains != 0 || debug_skip != 0 || d_forced || d_step_logits || d_first_logits,
+  // Graph chains come from the flags or the engine's decode_chains.  The row-group schedule (see mt3_engine::part_stream)
+  // unless the caller asked for chains (one chain included) or gets them, or for what lives on the caller's stream:
+  // skipped kernels, teacher forcing, logits
+  const int req_chains = (flags >> 8) & 0xF, chains = chains_for(e, batch, req_chains);
+  const GroupJob j{batch, 1, 1, variant, num_steps, early, use_graph, false, s, d_first_logits, d_step_logits, chains};
+  return run_decode_job(e, j, flags,
+                        req_chains != 0 || chains > 1 || debug_skip != 0 || d_forced || d_step_logits || d_first_logits,
                         h_steps_run);
 }
 
@@ -2299,7 +2233,8 @@ static int decode_beams_impl(mt3_engine* e, int32_t batch, int32_t k, int32_t nu
   p.s = s;
   const GroupJob j{batch, k, 1, variant, num_steps, (flags & MT3_DECODE_EARLY_EXIT) != 0, !(flags & MT3_DECODE_NO_GRAPH), false,
                    s, nullptr, nullptr};
-  MT3_TRY(run_decode_job(e, j, flags, false, h_steps_run));
+  // (an engine configured for graph chains keeps every decode on the caller's stream, this one too -- in one chain)
+  MT3_TRY(run_decode_job(e, j, flags, e->cfg.decode_chains > 1, h_steps_run));
   MT3_HIP_CHECK(wait_stream(e, kMaxGroups, s));    // complete on return: the fork count is in host memory
   return MT3_OK;
 }
@@ -2457,7 +2392,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, const StreamJob
     if (t - last_progress > stall_limit)
       return mt3::fail(MT3_ERR_INVALID, "mt3_engine_transcribe: a row group made no progress for num_steps + 4 polls");
     if (r.use_graph && exec_rows != cur) {
-      exec = group_graph(e, r.variant, r.batch, r.row0, cur, r.slot);
+      exec = group_graph(e, r, cur);
       exec_rows = cur;
       if (!exec) {
         r.use_graph = r.used_graph = false;
@@ -2465,7 +2400,7 @@ static int run_group_stream(mt3_engine* e, GroupRun& r, Feed& f, const StreamJob
       }
     }
     if (r.use_graph) MT3_HIP_CHECK(hipGraphLaunch(exec, r.s));
-    else MT3_TRY(enqueue_chain_step(e, r.row0, cur, r.batch, r.variant, r.s, r.slot));
+    else MT3_TRY(enqueue_step(e, r.row0, cur, r.batch, r.variant, r.chains, r.s, r.slot));
     ++r.ran;
     if (t % kPoll != kPoll - 1) continue;
     // ---- the previous interval's snapshot
@@ -3068,7 +3003,7 @@ static int set_seg_table(mt3_engine* e, SegTableHost<T>& tb, const std::string& 
   bool stale = tb.rows && ((n_seg > 0) != tb.seg_on || stride != tb.stride);
   MT3_TRY(grow(e, &tb.rows, &tb.rows_cap, n_elems, &stale));
   MT3_TRY(grow(e, &tb.seg, &tb.seg_cap, n_seg, &stale));
-  if (stale) drop_step_graphs(e);
+  if (stale) drop_group_graphs(e);
   tb.n = 0;                       // (a failed copy leaves the table out of use, not half set)
   MT3_HIP_CHECK(hipMemcpy(tb.rows, h_rows, n_elems * sizeof(T), hipMemcpyHostToDevice));
   if (n_seg) MT3_HIP_CHECK(hipMemcpy(tb.seg, h_seg, n_seg * 4, hipMemcpyHostToDevice));
@@ -3094,7 +3029,7 @@ int mt3_debug_engine_set_eos_schedule(mt3_engine* e, const int32_t* h_lengths, i
   // address, so they go)
   bool stale = false;
   MT3_TRY(grow(e, &e->eos_at, &e->eos_cap, static_cast<size_t>(n), &stale));
-  if (stale) drop_step_graphs(e);
+  if (stale) drop_group_graphs(e);
   std::vector<int32_t> h(static_cast<size_t>(e->eos_cap), 0x7fffffff);       // rows / segments past n: never
   for (int i = 0; i < n; ++i) {
     if (h_lengths[i] < 1) return mt3::fail(MT3_ERR_INVALID, "mt3_debug_engine_set_eos_schedule: lengths must be >= 1");
@@ -3144,7 +3079,7 @@ int mt3_engine_set_token_grammar(mt3_engine* e, const mt3_token_grammar* g) {
   // the grammar's step graphs hold the descriptor by value: another one and they go
   if (e->gr_seen && std::memcmp(&e->gr.g, g, sizeof(*g)) != 0) {
     MT3_HIP_CHECK(hipDeviceSynchronize());
-    drop_step_graphs(e);
+    drop_group_graphs(e);
   }
   e->gr.g = *g;
   e->gr.on = 1;
@@ -3172,7 +3107,7 @@ int mt3_engine_set_note_grammar(mt3_engine* e, const mt3_note_grammar* n) {
   }
   // the step graphs hold the descriptor and the state pointers by value: setting, changing or clearing drops them
   MT3_HIP_CHECK(hipDeviceSynchronize());
-  drop_step_graphs(e);
+  drop_group_graphs(e);
   if (!n) {
     e->nt.on = 0;
     e->gr.on = 0;
@@ -3193,7 +3128,7 @@ static int seed_table_form(mt3_engine* e, bool table) {
   if (!table) e->sseed.n = 0;
   if (e->seed_table != table) {
     MT3_HIP_CHECK(hipDeviceSynchronize());
-    drop_step_graphs(e);
+    drop_group_graphs(e);
   }
   e->seed_table = table;
   return MT3_OK;
@@ -3254,7 +3189,7 @@ int mt3_engine_set_sampling(mt3_engine* e, const mt3_sampling* sp, const uint64_
   // a setup call: nothing a caller enqueued earlier may still read the parameters this call replaces
   MT3_HIP_CHECK(hipDeviceSynchronize());
   // the sampled step graphs hold whether the streams come from a table: the other form and they go
-  if (e->samp_seen && e->samp_table != table) drop_step_graphs(e);
+  if (e->samp_seen && e->samp_table != table) drop_group_graphs(e);
   e->samp_seen = true;
   e->samp_table = table;
   if (!e->samp) MT3_TRY(dmalloc(e, reinterpret_cast<void**>(&e->samp), sizeof(mt3_sampling)));
