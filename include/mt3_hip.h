@@ -2157,6 +2157,85 @@ int mt3_op_level_velocities(const double* d_level, int64_t n_notes, const mt3_ve
                             const int32_t* d_velocity_in, int32_t* d_velocity, double* d_anchor /* [n_files][2] */,
                             int32_t* d_measured /* [n_files][2] */, void* stream);
 
+/* ---- beats: the beats of every file of a job from its own onsets, and the notes of a job on the beats' grid.  The
+ * dynamic-programming beat tracker of Ellis (2007) restated in integers: after the host has packed the onset frames no
+ * float is left, so any summation order and integer atomics give the same bits as the numpy statement
+ * (mt3_amd/beats.py, track_reference).
+ * THE RULE, per file of F = n_frames frames at MT3_BEATS_FPS frames per second:
+ *   FRAMES    d_frames holds one int32 per note, f = floor(start_time * fps + 0.5), in any order; F = max f + 1.  A frame
+ *     outside [0, F) is skipped.  F == 0: no beats, period 0.
+ *   ENVELOPE  n[t] = the onsets in frame t, at most 255;  E[t] = n[t-1] + 2 n[t] + n[t+1] for t in 0 .. F-1, zeros outside;
+ *     peak = max E;  S[t] = (E[t] << 16) / peak.  peak == 0: no beats, period 0.
+ *   PERIOD    A[l] = sum over t of E[t] * E[t + l] (int64) for l in MT3_BEATS_LAG_MIN .. MT3_BEATS_LAG_MAX; p = the LOWEST l
+ *     of maximal A[l] * W[l], W = d_prior [176] int64 (a tempo prior, <= 2^16; F < 2^20 keeps the product below 2^63).
+ *     Every product 0: no beats, period 0.
+ *   PATH      lo = (p + 1) / 2, hi = 2 p, pen[l] = d_penalties[(p - LAG_MIN) * MT3_BEATS_PEN_STRIDE + l - lo] for l in lo .. hi:
+ *       best(t) = max over l in lo .. hi with t - l >= 0 of (C[t - l] - pen[l]), the LOWEST l on equal values;
+ *       C[t] = S[t] + max(best(t), 0);  back[t] = that l, or 0 when best(t) <= 0 or no l is admissible.
+ *   BEATS     the path ends at the LOWEST t of maximal C[t] among the last p frames (all of them when F <= p) and is read
+ *     back through `back` until back[t] == 0; the beats are those frames in ascending order, score = C[end].
+ * Both tables are built by the host in float64 and rounded there (mt3_amd/beats.py: prior_table, penalty_table); penalties
+ * must be >= 0 and below 2^40.
+ * h_files [n_files]: per file its notes in d_frames (first, n_notes), its n_frames, frame0 = where its rows start in the
+ * per-frame scratch and beat0 = where its beats start in d_beats, which gives it MT3_BEATS_CAPACITY(n_frames) slots (steps
+ * of a path are >= 13 frames).  The three kinds of range each lie in increasing order and without overlap.
+ * d_rows: 2 * total_frames int32 of scratch (the op zeroes what it needs), d_back: total_frames uint16 of scratch.
+ * d_period, d_n_beats [n_files] int32, d_score [n_files] int64, d_beats [total_beats] int32: a file's n_beats beat frames
+ * from its beat0 on, the rest of its slots is not written.
+ * Work: one workgroup of 256 lanes per file, 32 files per launch (their table rides in the kernel arguments), the launches
+ * one after the other on `stream`; the layout is described in mt3_amd/csrc/beats.hip.
+ * MT3_ERR_INVALID, before any device work: a NULL pointer that the job needs; a negative count; tables that do not hold
+ * 176 and 176 * 301 entries; n_frames outside 0 .. 2^20 - 1; a note, frame or beat range outside its array, overlapping
+ * the one before it or out of order.  n_files == 0 is MT3_OK and does nothing.
+ *
+ * mt3_op_snap_notes: every note time of a job on the grid of `subdivisions` steps per beat, in float64, every operation
+ * rounded once (no fused multiply-add), so the result is numpy's bit for bit (mt3_amd/beats.py, snap_reference).  Per
+ * file: its beat frames (strictly ascending int32, n_beats of them from beat0 on in d_beat_frames), b = frame / fps.  With
+ * fewer than 2 beats the times are copied.  For a time t: i = the last beat at or before t, kept within 0 .. n_beats - 2
+ * (the grid of the first / last interval continues outside the beats); d = b[i+1] - b[i];
+ * k = ceil(((t - b[i]) / d) * subdivisions - 0.5): the nearest step, the lower one on a tie;
+ * point(i, k) = b[i+1] when k == subdivisions, else b[i] + (k / subdivisions) * d.  out_start = point of the start,
+ * out_end = point of the end, or, when that would not exceed out_start, point(i, k + 1) of the START: one grid step.
+ * MT3_ERR_INVALID, before any device work: a NULL pointer that the job needs; a negative count; subdivisions outside
+ * 1 .. MT3_BEATS_MAX_SUBDIVISIONS; a note or beat range outside its array, overlapping the one before it or out of
+ * order.  n_files == 0 is MT3_OK and does nothing. */
+#define MT3_BEATS_FPS 100
+#define MT3_BEATS_LAG_MIN 25
+#define MT3_BEATS_LAG_MAX 200
+#define MT3_BEATS_PEN_STRIDE 301
+#define MT3_BEATS_MAX_FRAMES (1 << 20)
+#define MT3_BEATS_TILE 1024
+#define MT3_BEATS_MAX_SUBDIVISIONS 48
+#define MT3_BEATS_CAPACITY(n_frames) ((int64_t)(n_frames) / 13 + 2)
+
+typedef struct mt3_beats_file {
+  int64_t first;                      /* the file's first note in d_frames */
+  int64_t frame0;                     /* the file's first word in each per-frame scratch row */
+  int64_t beat0;                      /* the file's first slot in d_beats */
+  int32_t n_notes;
+  int32_t n_frames;
+} mt3_beats_file;
+
+typedef struct mt3_snap_file {
+  int64_t first;                      /* the file's first note in the columns */
+  int64_t beat0;                      /* the file's first beat in d_beat_frames */
+  int32_t n_notes;
+  int32_t n_beats;
+} mt3_snap_file;
+
+int mt3_op_track_beats(const int32_t* d_frames /* [n_notes] */, int64_t n_notes,
+                       const mt3_beats_file* h_files /* [n_files] */, int32_t n_files, const int64_t* d_prior /* [176] */,
+                       int32_t n_prior, const int64_t* d_penalties /* [176][301] */, int32_t n_penalties,
+                       int32_t* d_rows /* [2][total_frames] */, uint16_t* d_back /* [total_frames] */, int64_t total_frames,
+                       int32_t* d_period /* [n_files] */, int32_t* d_n_beats /* [n_files] */,
+                       int32_t* d_beats /* [total_beats] */, int64_t total_beats, int64_t* d_score /* [n_files] */,
+                       void* stream);
+
+int mt3_op_snap_notes(const double* d_start /* [n_notes] */, const double* d_end /* [n_notes] */, int64_t n_notes,
+                      const int32_t* d_beat_frames /* [n_beat_frames] */, int64_t n_beat_frames,
+                      const mt3_snap_file* h_files /* [n_files] */, int32_t n_files, int32_t subdivisions,
+                      double* d_out_start /* [n_notes] */, double* d_out_end /* [n_notes] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

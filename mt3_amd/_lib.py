@@ -46,6 +46,8 @@ ALIGN_MAX_SHIFTS = 64                          # mt3_op_align_paths
 CONSENSUS_MAX_VOTERS, CONSENSUS_TILE, CONSENSUS_SCRATCH_WORDS_PER_NOTE = 64, 256, 4      # mt3_op_note_consensus
 NOTE_PREP_SUSTAIN, NOTE_PREP_TRIM, NOTE_PREP_TILE = 0, 1, 256                              # mt3_op_prepare_notes
 VELOCITY_KEYS, VELOCITY_THRESHOLDS, VELOCITY_MAX_WINDOW, VELOCITY_MAX_MEL = 129, 126, 64, 4096   # mt3_op_note_levels
+BEATS_FPS, BEATS_LAG_MIN, BEATS_LAG_MAX, BEATS_PEN_STRIDE = 100, 25, 200, 301                    # mt3_op_track_beats
+BEATS_MAX_FRAMES, BEATS_TILE, BEATS_MAX_SUBDIVISIONS = 1 << 20, 1024, 48
 
 
 class Mt3Error(RuntimeError):
@@ -135,6 +137,15 @@ class NotePrepFile(C.Structure):               # mt3_note_prep_file
 class VelocityFile(C.Structure):               # mt3_velocity_file
     _fields_ = [("first", C.c_int64), ("row0", C.c_int64)] + \
                [(n, C.c_int32) for n in ("n_notes", "n_pitched", "n_frames", "reserved")]
+
+
+class BeatsFile(C.Structure):                  # mt3_beats_file
+    _fields_ = [("first", C.c_int64), ("frame0", C.c_int64), ("beat0", C.c_int64), ("n_notes", C.c_int32),
+                ("n_frames", C.c_int32)]
+
+
+class SnapFile(C.Structure):                   # mt3_snap_file
+    _fields_ = [("first", C.c_int64), ("beat0", C.c_int64), ("n_notes", C.c_int32), ("n_beats", C.c_int32)]
 
 
 _P = C.c_void_p
@@ -357,6 +368,9 @@ SIGNATURES = {
     "mt3_op_note_levels": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32,
                                      C.c_int32, _P, _P]),
     "mt3_op_level_velocities": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "mt3_op_track_beats": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, _P, _P,
+                                     _P, C.c_int64, _P, _P]),
+    "mt3_op_snap_notes": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
 }
 
 _lib = None

@@ -474,7 +474,7 @@ class InferenceModel(object):
         return torch.cat(out, 0)
 
     def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True, prompts=None,
-                 well_formed: bool = False, velocities=None):
+                 well_formed: bool = False, velocities=None, beats=False):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
         notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`.
@@ -507,12 +507,18 @@ class InferenceModel(object):
         (`velocity.estimate`) -- the one-velocity-bin codec gives every note the same velocity (127); with
         True, or a dict of `estimate`'s keywords (window, harmonics, gamma, quantile, anchor_velocity), each note's
         velocity is its level at the onset relative to the file's median note.  Nothing else of the notes changes.  ValueError for a model whose
-        codec has more than one velocity bin (ismir2021): it decodes them.  For known notes: `note_velocities`."""
+        codec has more than one velocity bin (ismir2021): it decodes them.  For known notes: `note_velocities`.
+        beats (the same four methods; default False: off, and nothing changes): with True, or a dict of `beats.track`'s
+        keywords (prior_bpm, tightness, width), the job's notes go through the beat tracker on the device (one
+        `mt3_amd.beats.track` call for all files) and every returned NoteSequence carries the attribute
+        `beats`, its file's `mt3_amd.beats.Beats` (times, period, qpm, score).  The notes themselves do not change;
+        `midi_io.note_sequence_to_midi_bytes(ns, beats=ns.beats.times)` writes them with the tempo map.  For known notes:
+        `InferenceModel.beats`."""
         return self._transcribe([functools.partial(self._examples, audio, sample_rate)], False,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities)[0]
+                                velocities=velocities, beats=beats)[0]
 
-    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, velocities=None, **rule):
+    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, velocities=None, beats=False, **rule):
         """The one path from files to notes.  make_examples: one call per file that returns (its examples, its log-mel on
         the device); many and kw (programs, drums, prompts, well_formed) as `_job` reads them; rule: `_job`'s -- with
         draws=n the segments' n draws run as one job (row s * n + j of the job = draw j of segment s).  -> per file its
@@ -522,6 +528,9 @@ class InferenceModel(object):
         the device."""
         import torch
         velocities = self._velocity_keywords(velocities)
+        beats = self._beat_keywords(beats)
+        if beats is not None and (scored or rule.get("draws")):
+            raise ValueError("beats= is for the transcribing methods that return one NoteSequence per file")
         files = [make() for make in make_examples]
         if not files:
             return []
@@ -558,7 +567,23 @@ class InferenceModel(object):
                     frames_per_second=self.spectrogram_config.frames_per_second, **velocities)
             if scored:
                 out = [(out[0], self._note_scores(x, ids, results[0]["note_tokens"]))]
+        if beats is not None:
+            from . import beats as beat_tracking
+            for ns, found in zip(out, beat_tracking.track(out, **beats)):
+                ns.beats = found
         return out
+
+    @staticmethod
+    def _beat_keywords(beats):
+        """the `beats=` keyword of the transcribing methods -> `beats.track`'s keywords, or None for off"""
+        if beats is None or beats is False:
+            return None
+        if beats is True:
+            return {}
+        unknown = set(beats) - {"prior_bpm", "tightness", "width"}
+        if unknown:
+            raise ValueError("beats= takes prior_bpm, tightness, width, got %s" % ", ".join(sorted(map(repr, unknown))))
+        return dict(beats)
 
     def _velocity_keywords(self, velocities):
         """the `velocities=` keyword of the transcribing methods -> `velocity.estimate`'s keywords, or None for off"""
@@ -653,13 +678,13 @@ class InferenceModel(object):
         return [(r.notes, r, s) if return_votes else r.notes for r, s in zip(results, samples)]
 
     def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False,
-                       velocities=None):
+                       velocities=None, beats=False):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
         return self._transcribe([functools.partial(self._wav_examples, wav_data)], False,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities)[0]
+                                velocities=velocities, beats=beats)[0]
 
     def _count_events(self, results, tie_overflows: int):
         """the note decoder's counts of the call that just ended, summed over its files, and its wavefront's overflows"""
@@ -957,7 +982,7 @@ class InferenceModel(object):
         return out
 
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
-                        drums=True, prompts=None, well_formed: bool = False, velocities=None) -> List[Any]:
+                        drums=True, prompts=None, well_formed: bool = False, velocities=None, beats=False) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
@@ -970,15 +995,15 @@ class InferenceModel(object):
         return self._transcribe([functools.partial(self._examples, audio, sr)
                                  for audio, sr in zip(audios, self._rates(sample_rates, len(audios)))], True,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities)
+                                velocities=velocities, beats=beats)
 
     def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None,
-                        well_formed: bool = False, velocities=None) -> List[Any]:
+                        well_formed: bool = False, velocities=None, beats=False) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
         `self.transcribe_wav(wav)`.  programs / drums / prompts / velocities: as for `transcribe_many`."""
         return self._transcribe([functools.partial(self._wav_examples, wav) for wav in wavs], True,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities)
+                                velocities=velocities, beats=beats)
 
     def note_velocities(self, audio, ns, *, sample_rate: int = SAMPLE_RATE, **kw):
         """Known notes `ns` with velocities estimated from `audio`: `note_velocities_many([(audio, ns)])[0]`; with
@@ -996,6 +1021,13 @@ class InferenceModel(object):
         _, feats, n_frames = self._paired_examples(pairs, self._rates(sample_rates, len(pairs)), False)
         return velocity.estimate(list(zip(feats, n_frames)), [ns for _, ns in pairs],
                                  frames_per_second=self.spectrogram_config.frames_per_second, **kw)
+
+    @staticmethod
+    def beats(ns, **kw):
+        """The beats of a transcription: `mt3_amd.beats.track([ns], **kw)[0]`, a `Beats` (times in seconds, period in
+        10 ms frames, qpm, score), found on the device from the notes' own onsets."""
+        from . import beats
+        return beats.track([ns], **kw)[0]
 
     @staticmethod
     def pianoroll(ns, fps: float = 62.5):

@@ -8,11 +8,22 @@ one tempo of 120 qpm at tick 0, tick = round(time * resolution * qpm / 60), one 
 Controller events (`NoteSequence.control_changes`: the sustain pedal of piano files) are written onto the channel their
 instrument's notes use, and read back; the reader numbers instruments 9 (channel 9) or 0 (every other channel), so the
 pedal of any non-drum channel holds the notes of all of them: right for piano files, a stated limit otherwise.
+TEMPO MAPS.  With `beats=` (ascending times in seconds, at least two: `mt3_amd.beats.track(...)[i].times`) the writer puts
+beat i on tick (m + i) * resolution -- every beat is one quarter note -- and a set-tempo event of
+round(1e6 * (b[i+1] - b[i])) microseconds per quarter on every beat but the last, after which the last tempo holds.  A
+time t in interval i is tick round((m + i + (t - b[i]) / (b[i+1] - b[i])) * resolution); before the first beat the first
+interval is extended backwards over m = `preroll(beats)[0]` whole beats, the fewest that put tick 0 at or before time 0.
+Tick 0 is therefore time b[0] - m * (b[1] - b[0]) <= 0, and a file read back runs later than its source by minus that.
+The reader keeps every set-tempo event with its tick (on equal ticks the last one read) and converts ticks to seconds
+through the map; `midi_bytes_to_beats` returns the quarter-note ticks' times.  The tempo field is a whole number of
+microseconds, so a written interval is off by at most 0.5 us; beats on the tracker's 10 ms frames are written exactly.
 """
 from __future__ import annotations
 
+import bisect
+import math
 import struct
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 from .note_sequences import ControlChange, Note, NoteSequence
 
@@ -39,11 +50,47 @@ def _track(events: List[Tuple[int, int, bytes]]) -> bytes:
     return b"MTrk" + struct.pack(">I", len(data)) + bytes(data)
 
 
-def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM) -> bytes:
+def _tempo_event(tick: int, microseconds: int) -> Tuple[int, int, bytes]:
+    return (tick, 0, b"\xff\x51\x03" + struct.pack(">I", microseconds)[1:])
+
+
+def _check_beats(beats) -> List[float]:
+    b = [float(t) for t in beats]
+    if len(b) < 2 or not all(math.isfinite(t) for t in b) or any(t1 <= t0 for t0, t1 in zip(b, b[1:])):
+        raise ValueError("beats must be at least two finite, strictly ascending times")
+    if any(not 1 <= int(round(1e6 * (t1 - t0))) < 1 << 24 for t0, t1 in zip(b, b[1:])):
+        raise ValueError("a beat interval must be 1 us .. 16.7 s: the tempo field has 24 bits")
+    return b
+
+
+def preroll(beats) -> Tuple[int, float]:
+    """(m, t0) of a tempo map written from `beats`: the whole beats inserted before the first one, and the time of tick 0,
+    b[0] - m * (b[1] - b[0]) <= 0"""
+    b = _check_beats(beats)
+    m = max(int(math.ceil(b[0] / (b[1] - b[0]))), 0)
+    while b[0] - m * (b[1] - b[0]) > 0:                      # (the quotient was rounded down across a whole number)
+        m += 1
+    return m, b[0] - m * (b[1] - b[0])
+
+
+def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM, beats: Optional[Sequence[float]] = None) -> bytes:
     res = ns.ticks_per_quarter or 220
-    to_tick = lambda t: int(round(t * res * qpm / 60.0))  # noqa: E731
-    tempo = int(round(60_000_000 / qpm))
-    tracks = [_track([(0, 0, b"\xff\x51\x03" + struct.pack(">I", tempo)[1:])])]
+    if beats is None:
+        to_tick = lambda t: int(round(t * res * qpm / 60.0))  # noqa: E731
+        tempo = int(round(60_000_000 / qpm))
+        tracks = [_track([_tempo_event(0, tempo)])]
+    else:
+        b = _check_beats(beats)
+        m = preroll(b)[0]
+
+        def to_tick(t):
+            i = min(max(bisect.bisect_right(b, t) - 1, 0), len(b) - 2)
+            return max(int(round((m + i + (t - b[i]) / (b[i + 1] - b[i])) * res)), 0)
+
+        conductor = [_tempo_event((m + i) * res, int(round(1e6 * (b[i + 1] - b[i])))) for i in range(len(b) - 1)]
+        if m:
+            conductor.append(_tempo_event(0, int(round(1e6 * (b[1] - b[0])))))
+        tracks = [_track(conductor)]
     groups: Dict[Tuple[int, int, bool], List[Note]] = {}
     for n in ns.notes:
         groups.setdefault((n.instrument, n.program, bool(n.is_drum)), []).append(n)
@@ -68,20 +115,38 @@ def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM) -> b
     return header + b"".join(tracks)
 
 
-def note_sequence_to_midi_file(ns: NoteSequence, path: str, qpm: float = DEFAULT_QPM) -> None:
+def note_sequence_to_midi_file(ns: NoteSequence, path: str, qpm: float = DEFAULT_QPM,
+                               beats: Optional[Sequence[float]] = None) -> None:
     with open(path, "wb") as f:
-        f.write(note_sequence_to_midi_bytes(ns, qpm))
+        f.write(note_sequence_to_midi_bytes(ns, qpm, beats))
 
 
 sequence_proto_to_midi_file = note_sequence_to_midi_file       # note_seq's name for it
 
 
-def midi_bytes_to_note_sequence(data: bytes) -> NoteSequence:
-    """Minimal SMF reader (note on/off, program change, controllers, one tempo; SysEx skipped) -- enough to round-trip the
-    writer and to read a piano file's pedal.  control_changes come in (tick, file) order."""
+class _TempoMap:
+    """ticks -> seconds through a file's set-tempo events; 500000 us per quarter until the first one"""
+
+    def __init__(self, events: List[Tuple[int, int]], res: int):
+        self.res, self.ticks, self.tempos, self.seconds = res, [0], [500000], [0.0]
+        for tick, tempo in sorted(events, key=lambda e: e[0]):       # stable: on equal ticks the last one read holds
+            if tick == self.ticks[-1]:
+                self.tempos[-1] = tempo
+            else:
+                self.seconds.append(self(tick))
+                self.ticks.append(tick)
+                self.tempos.append(tempo)
+
+    def __call__(self, tick: int) -> float:
+        k = bisect.bisect_right(self.ticks, tick) - 1
+        return self.seconds[k] + (tick - self.ticks[k]) * self.tempos[k] / 1e6 / self.res
+
+
+def _parse(data: bytes):
+    """-> (resolution, notes, controllers, tempo events, the last event's tick), everything in ticks"""
     assert data[:4] == b"MThd"
     _, fmt, ntrk, res = struct.unpack(">IHHH", data[4:14])
-    pos, tempo = 14, 500000
+    pos, tempos, last_tick = 14, [], 0
     raw, raw_cc = [], []
     for _ in range(ntrk):
         assert data[pos:pos + 4] == b"MTrk"
@@ -103,7 +168,9 @@ def midi_bytes_to_note_sequence(data: bytes) -> NoteSequence:
             if status == 0xFF:
                 kind, ln2 = body[i], body[i + 1]
                 if kind == 0x51:
-                    tempo = int.from_bytes(body[i + 2:i + 5], "big")
+                    tempos.append((tick, int.from_bytes(body[i + 2:i + 5], "big")))
+                if kind != 0x2F:
+                    last_tick = max(last_tick, tick)
                 i += 2 + ln2
                 continue
             if status in (0xF0, 0xF7):                       # SysEx: a VLQ length, then that many bytes
@@ -117,6 +184,7 @@ def midi_bytes_to_note_sequence(data: bytes) -> NoteSequence:
                 i += ln2
                 continue
             hi, ch = status & 0xF0, status & 0x0F
+            last_tick = max(last_tick, tick)
             if hi == 0xC0:
                 program[ch] = body[i]
                 i += 1
@@ -133,7 +201,14 @@ def midi_bytes_to_note_sequence(data: bytes) -> NoteSequence:
                 i += 2
             else:
                 i += 2 if hi not in (0xD0,) else 1
-    sec = lambda t: t * tempo / 1e6 / res  # noqa: E731
+    return res, raw, raw_cc, tempos, last_tick
+
+
+def midi_bytes_to_note_sequence(data: bytes) -> NoteSequence:
+    """Minimal SMF reader (note on/off, program change, controllers, the tempo map; SysEx skipped) -- enough to round-trip
+    the writer and to read a piano file's pedal.  control_changes come in (tick, file) order."""
+    res, raw, raw_cc, tempos, _ = _parse(data)
+    sec = _TempoMap(tempos, res)
     ns = NoteSequence(ticks_per_quarter=res)
     for t0, t1, pitch, vel, prog, drum in sorted(raw):
         ns.notes.append(Note(sec(t0), sec(t1), pitch, vel, prog, drum, 9 if drum else 0))
@@ -141,3 +216,11 @@ def midi_bytes_to_note_sequence(data: bytes) -> NoteSequence:
     for tick, number, value, inst in sorted(raw_cc, key=lambda c: c[0]):
         ns.control_changes.append(ControlChange(sec(tick), number, value, inst))
     return ns
+
+
+def midi_bytes_to_beats(data: bytes) -> List[float]:
+    """The times in seconds of a file's quarter-note ticks, 0, resolution, 2 * resolution, ..., up to its last event (the
+    End-of-Track events apart): the beats of a file written with `beats=`, the inserted ones (`preroll`) included."""
+    res, _, _, tempos, last_tick = _parse(data)
+    sec = _TempoMap(tempos, res)
+    return [sec(tick) for tick in range(0, last_tick + 1, res)]

@@ -9,6 +9,7 @@
                                  [--consensus N [--consensus-min-votes M] [--consensus-tolerance S]]
                                  [--sustain] [--trim-overlaps]
                                  [--velocities [--velocity-gamma G] [--velocity-anchor V]]
+                                 [--beats [--beats-prior-bpm B] [--quantize SUBDIV]]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -57,6 +58,12 @@ velocities=)`, `mt3_amd.velocity.estimate`: the note's level at its onset agains
 --velocity-anchor, default 80; amplitude ~ (velocity / 127)^G with --velocity-gamma G, default 2.0) before NAME.mid,
 --render and --pianoroll are written; the mt3 model alone gives every note the same velocity, 127.  With --consensus or
 --confidences the estimate runs on the finished notes (`InferenceModel.note_velocities_many`).  Not with --model ismir2021.
+--beats finds the beats of every input from its transcription's own onsets (`mt3_amd.beats.track`: all inputs as one job
+on the device; one tempo per file, found under a prior centred on --beats-prior-bpm, default 120) and writes NAME.mid
+with the tempo map -- a set-tempo event on every beat, every beat one quarter note, so the file plays as performed and
+opens on the grid of a notation editor -- and NAME.beats.json beside it: {"qpm", "period_frames", "beats": [seconds]}.
+An input in which no beat is found keeps the constant 120 qpm.  --quantize SUBDIV first moves the notes onto the grid of
+SUBDIV steps per beat (1 .. 48; `mt3_amd.beats.snap`), before NAME.mid, --render and --pianoroll are written.
 """
 from __future__ import annotations
 
@@ -146,6 +153,13 @@ def plan(argv=None):
                     help="--velocities: amplitude ~ (velocity / 127)^G (default 2.0; 1.0 is what --render plays)")
     ap.add_argument("--velocity-anchor", type=float, default=None, metavar="V",
                     help="--velocities: the velocity of the file's median note (default 80)")
+    ap.add_argument("--beats", action="store_true",
+                    help="find each input's beats from its notes and write NAME.mid with the tempo map (every beat a quarter "
+                         "note), and NAME.beats.json beside it")
+    ap.add_argument("--beats-prior-bpm", type=float, default=None, metavar="B",
+                    help="--beats: the centre of the tempo prior in beats per minute (default 120)")
+    ap.add_argument("--quantize", type=int, default=None, metavar="SUBDIV",
+                    help="--beats: move the notes onto the grid of SUBDIV steps per beat (1 .. 48) first")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -185,6 +199,15 @@ def plan(argv=None):
             v = getattr(args, name)
             if v is not None and not (math.isfinite(v) and v > 0):
                 ap.error("--%s takes a finite number > 0" % name.replace("_", "-"))
+    if not args.beats:
+        for name in ("beats_prior_bpm", "quantize"):
+            if getattr(args, name) is not None:
+                ap.error("--%s needs --beats" % name.replace("_", "-"))
+    else:
+        if args.beats_prior_bpm is not None and not (math.isfinite(args.beats_prior_bpm) and args.beats_prior_bpm > 0):
+            ap.error("--beats-prior-bpm takes a finite number > 0")
+        if args.quantize is not None and not 1 <= args.quantize <= 48:
+            ap.error("--quantize takes 1 .. 48 steps per beat")
     if (args.sustain or args.trim_overlaps) and args.score_against is None and args.score_midi is None and \
             args.align_midi is None:
         ap.error("--sustain and --trim-overlaps need --score-against, --score-midi or --align-midi")
@@ -292,6 +315,13 @@ def main(argv=None) -> int:
         else:
             sequences, scores = model.transcribe_wavs(args.inputs, programs=args.programs, drums=args.drums,
                                                       well_formed=args.well_formed, velocities=velocities), None
+        found = None
+        if args.beats:
+            from . import beats
+            # all inputs as one job, on the finished notes (whichever branch above made them)
+            found = beats.track(sequences, **({} if args.beats_prior_bpm is None else {"prior_bpm": args.beats_prior_bpm}))
+            if args.quantize is not None:
+                sequences = beats.snap(sequences, found, args.quantize)
         rolls = None
         if args.pianoroll is not None:
             import numpy as np
@@ -302,6 +332,7 @@ def main(argv=None) -> int:
         if args.render is not None:
             from . import render
             written = [midi_io.midi_bytes_to_note_sequence(midi_io.note_sequence_to_midi_bytes(ns)) for ns in sequences]
+            # (with --beats the file's ticks follow the tempo map; the render keeps the constant grid's rounding)
             audio = [a.cpu().numpy() for a in render.render(written, args.render)]
         scored = None
         if args.score_against is not None:
@@ -330,10 +361,14 @@ def main(argv=None) -> int:
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
-    for ns, path in zip(sequences, outputs):
+    for i, (ns, path) in enumerate(zip(sequences, outputs)):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        midi_io.note_sequence_to_midi_file(ns, path)
+        mapped = found is not None and len(found[i].times) >= 2
+        midi_io.note_sequence_to_midi_file(ns, path, beats=found[i].times if mapped else None)
         print("%s: %d notes" % (path, len(ns.notes)))
+    for rec, path in zip(found or [], outputs):
+        with open(beats_path(path), "w") as f:
+            json.dump(beats_record(rec), f, indent=1)
     for ns, sc, path in zip(sequences, scores or [], outputs):
         with open(confidence_path(path), "w") as f:
             json.dump(confidence_records(ns, sc), f, indent=1)
@@ -382,6 +417,15 @@ def known_notes(directory: str, args) -> list:
         from . import note_prep
         sequences = note_prep.prepare(sequences, sustain=args.sustain, trim=args.trim_overlaps)
     return sequences
+
+
+def beats_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".beats.json"
+
+
+def beats_record(rec) -> dict:
+    """the JSON-ready form of one `beats.Beats`"""
+    return {"qpm": float(rec.qpm), "period_frames": int(rec.period), "beats": [float(t) for t in rec.times]}
 
 
 def votes_path(midi_path: str) -> str:
