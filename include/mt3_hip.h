@@ -2236,6 +2236,116 @@ int mt3_op_snap_notes(const double* d_start /* [n_notes] */, const double* d_end
                       const mt3_snap_file* h_files /* [n_files] */, int32_t n_files, int32_t subdivisions,
                       double* d_out_start /* [n_notes] */, double* d_out_end /* [n_notes] */, void* stream);
 
+/* ---- score-to-audio synchronisation: chroma features of a recording (from the log-mel the frontend has written) and of
+ * a score (from its notes), and the dynamic-time-warping path between the two.  Integer or fixed-order arithmetic
+ * throughout, so each op equals its numpy statement bit for bit (mt3_amd/sync.py: logmel_chroma_reference,
+ * note_chroma_reference, paths_reference).  Three ops over ONE file table; a job calls the two chroma ops, then the path op
+ * on their outputs.  Max-log chroma is this project's own feature; it claims parity with no library.
+ * FILES   h_files [n_files] is what is checked; d_files is the same records on the device and what the kernels read (the
+ *   one upload of a job carries it), so each op is ONE launch (the path op), or one launch per kernel, whatever n_files is.
+ *   A device copy that differs from the checked one is the caller's error, as a wrong pointer is.  File f owns the log-mel
+ *   rows row0 .. row0 + n_frames - 1, the notes first .. first + n_notes - 1, the audio features a0 .. a0 + n - 1 of d_a, the
+ *   score features s0 .. s0 + m - 1 of d_s, the path slots path0 .. path0 + MT3_SYNC_PATH_CAPACITY(n, m) - 1 and the
+ *   workspace words work0 .. work0 + mt3s_workspace_words(n, m) - 1.  Each kind of range lies in increasing order and
+ *   without overlap.  An op checks and reads only the fields it names.
+ * mt3_op_logmel_chroma  (row0, n_frames, a0, n; n == ceil(n_frames / pool))  d_a [total_a][12] uint8.  d_bins int8
+ *   [n_mel]: each mel bin's pitch class 0 .. 11, anything else: unused (the host builds it: mt3_amd/sync.py, chroma_bins).
+ *   Feature frame i of a file covers its rows i * pool .. min((i + 1) * pool, n_frames) - 1:
+ *     v[c] = the largest log-mel value at the bins of class c over those rows, NaN values skipped; a class with no bin or
+ *            nothing but NaN is UNMEASURED;  mx = the largest measured v[c];
+ *     q[c] = clamp(floor(((v[c] - mx) + range) * scale)) in float32, each of the three operations rounded on its own
+ *            (no fused multiply-add), scale = (float)(255.0 / (double)range) from the host; clamp(t) = 255 for t >= 255,
+ *            (int)t for 0 <= t < 255, else 0 (NaN among them); an unmeasured class gives 0.
+ *     The frame is SILENT, twelve zeros, unless mx >= floor (nothing measured: silent).  No transcendental function runs.
+ *   WORK  a wave per feature frame, four to a workgroup, the grid over the job's feature frames (a frame finds its file
+ *   by binary search in d_files).  A lane reads 16 bytes of each row (four bins; 64 lanes: 1 KiB, contiguous) when n_mel
+ *   is a multiple of 4 and the log-mel is 16-byte aligned, else single floats 256 bytes per wave; it folds the rows per
+ *   bin, then its bins into twelve registers, and six xor moves per class reduce across the wave.  Lanes 0 .. 11 store.
+ * mt3_op_note_chroma  (first, n_notes, s0, m)  d_s [total_s][12] uint8.  Note columns (int32): d_j0, d_j1, d_pitch; the
+ *   host computes j0 = floor(start * fps), j1 = max(j0 + 1, floor(end * fps)) in float64 and m = the largest j1 of the file
+ *   (0 without notes).  For h < n_harmonics the note adds h_weights[h] (0 .. 255) to class (pitch + MT3_SYNC_OFFSETS[h])
+ *   mod 12 over the frames j0 .. j1 - 1;  s[j][c] = min(255, sum).  A note with pitch outside 0 .. 127, j0 outside [0, m)
+ *   or j1 outside (j0, m] adds nothing.
+ *   WORK  the piano roll's idiom: the op zeroes 12 * total_s int32 words of d_scratch (file f's twelve rows of m words
+ *   from 12 * s0 on), a lane per note makes two return-less integer atomic adds per harmonic (+w at j0, -w at j1 < m),
+ *   one workgroup per (file, class) add-scans its row and stores the clipped bytes.  Integer sums: any order, same bits.
+ * mt3_op_sync_paths  (a0, n, s0, m, path0)  cost(i, j) = sum over c of |a[i][c] - s[j][c]| (<= 3060), all int32:
+ *     D[0][0] = cost(0, 0);  D[i][j] = cost(i, j) + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) over the predecessors that
+ *     exist, the FIRST of equal values in that order;  the path runs from (n-1, m-1) back to (0, 0) along those choices.
+ *   d_path_i, d_path_j: the path in FORWARD order from path0 on, d_path_len [n_files] its length (<= n + m - 1),
+ *   d_total [n_files] = D[n-1][m-1].  n == 0 or m == 0: length 0, total 0.  n, m <= MT3_SYNC_MAX_FRAMES keeps every D below
+ *   2^31; n * m <= MT3_SYNC_MAX_CELLS bounds the workspace -- there is no band constraint.
+ *   WORK  ONE workgroup of MT3_SYNC_LANES lanes per file, the files side by side in one launch; no workgroup ever waits for
+ *   another.  The skewed column-strip form: lane l owns the MT3_SYNC_STRIP columns of strip l and keeps their row of D and
+ *   their twelve-byte score features in registers; at step t it computes row t - l of its strip (twelve absolute
+ *   differences are three sad_u8), takes the strip's left boundary from lane l - 1 (a cross-lane move inside a wave, one
+ *   LDS word between waves, one barrier per step) and stores the strip's 16 two-bit choices as ONE dword, in step order so
+ *   that a wave's stores are contiguous.  More than MT3_SYNC_LANES strips: panels of that many, the boundary column
+ *   between two panels (n int32) in the workspace.  The read-back is one lane following dependent loads, as in
+ *   mt3_op_align_paths (a move to the left inside a strip reuses the dword it holds); it fills the file's slots from the
+ *   back, and the workgroup then moves the path to the front.
+ *   d_workspace: int32 words, 4-byte aligned; a file's words are never read before they are written, so nothing needs
+ *   clearing.  mt3_sync_workspace_bytes(h_files, n_files): the bytes the files need back to back (work0 = the running
+ *   sum of mt3s_workspace_words); -1 (and mt3_last_error) for a NULL table or an n or m the path op would refuse.
+ * MT3_ERR_INVALID, before any device work: n_files negative; a NULL table (host or device) with n_files > 0; a count of a
+ *   file negative; pool outside 1 .. MT3_SYNC_MAX_POOL; n_mel outside 1 .. 4096; range not finite and > 0; floor NaN;
+ *   n != ceil(n_frames / pool); n_harmonics outside 1 .. MT3_SYNC_HARMONICS, a weight outside 0 .. 255; n or m above
+ *   MT3_SYNC_MAX_FRAMES; n * m above MT3_SYNC_MAX_CELLS; a range outside its array, overlapping the one before it or out
+ *   of order; a NULL or misaligned (4 bytes) array the job needs; a NULL or short workspace.  n_files == 0 is MT3_OK and
+ *   launches nothing. */
+#define MT3_SYNC_CLASSES 12
+#define MT3_SYNC_MAX_POOL 16
+#define MT3_SYNC_HARMONICS 6
+#define MT3_SYNC_MAX_FRAMES (1 << 18)
+#define MT3_SYNC_MAX_CELLS ((int64_t)1 << 31)
+#define MT3_SYNC_LANES 1024
+#define MT3_SYNC_STRIP 16
+#define MT3_SYNC_PATH_CAPACITY(n, m) ((n) > 0 && (m) > 0 ? (int64_t)(n) + (int64_t)(m) - 1 : (int64_t)0)
+
+typedef struct mt3_sync_file {
+  int64_t row0;                       /* the file's first row in the log-mel */
+  int64_t first;                      /* the file's first note in the note columns */
+  int64_t a0;                         /* the file's first audio feature frame in d_a */
+  int64_t s0;                         /* the file's first score feature frame in d_s */
+  int64_t path0;                      /* the file's first slot in d_path_i / d_path_j */
+  int64_t work0;                      /* the file's first int32 word in d_workspace */
+  int32_t n_frames;                   /* the file's valid log-mel rows */
+  int32_t n_notes;
+  int32_t n;                          /* audio feature frames */
+  int32_t m;                          /* score feature frames */
+} mt3_sync_file;
+
+/* the semitone offsets of the harmonics 1 .. 6 of a note: 0, 12, 19, 24, 28, 31 */
+MT3_RULE_FN int32_t mt3s_offset(int32_t h) {
+  return h == 0 ? 0 : h == 1 ? 12 : h == 2 ? 19 : h == 3 ? 24 : h == 4 ? 28 : 31;
+}
+
+/* int32 words of workspace of one file: the choices of every panel in step order, then the boundary column */
+MT3_RULE_FN int64_t mt3s_workspace_words(int32_t n, int32_t m) {
+  if (n <= 0 || m <= 0) return 0;
+  const int64_t strips = ((int64_t)m + MT3_SYNC_STRIP - 1) / MT3_SYNC_STRIP;
+  const int64_t full = strips / MT3_SYNC_LANES, rest = strips % MT3_SYNC_LANES;
+  return full * ((int64_t)n + MT3_SYNC_LANES - 1) * MT3_SYNC_LANES + (rest ? ((int64_t)n + rest - 1) * rest : 0) + n;
+}
+
+int64_t mt3_sync_workspace_bytes(const mt3_sync_file* h_files /* [n_files] */, int32_t n_files);
+
+int mt3_op_logmel_chroma(const float* d_logmel, int64_t n_rows, int32_t n_mel, const mt3_sync_file* h_files /* [n_files] */,
+                         const mt3_sync_file* d_files, int32_t n_files, const int8_t* d_bins /* [n_mel] */, int32_t pool,
+                         float range, float floor, uint8_t* d_a /* [total_a][12] */, int64_t total_a, void* stream);
+
+int mt3_op_note_chroma(const int32_t* d_j0, const int32_t* d_j1, const int32_t* d_pitch, int64_t n_notes,
+                       const mt3_sync_file* h_files /* [n_files] */, const mt3_sync_file* d_files, int32_t n_files,
+                       const int32_t* h_weights /* [n_harmonics] */, int32_t n_harmonics,
+                       int32_t* d_scratch /* [12 * total_s] */, uint8_t* d_s /* [total_s][12] */, int64_t total_s,
+                       void* stream);
+
+int mt3_op_sync_paths(const uint8_t* d_a /* [total_a][12] */, int64_t total_a, const uint8_t* d_s /* [total_s][12] */,
+                      int64_t total_s, const mt3_sync_file* h_files /* [n_files] */, const mt3_sync_file* d_files,
+                      int32_t n_files, void* d_workspace, int64_t workspace_bytes, int32_t* d_path_i, int32_t* d_path_j,
+                      int64_t total_path, int32_t* d_path_len /* [n_files] */, int32_t* d_total /* [n_files] */,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,8 @@ NOTE_PREP_SUSTAIN, NOTE_PREP_TRIM, NOTE_PREP_TILE = 0, 1, 256                   
 VELOCITY_KEYS, VELOCITY_THRESHOLDS, VELOCITY_MAX_WINDOW, VELOCITY_MAX_MEL = 129, 126, 64, 4096   # mt3_op_note_levels
 BEATS_FPS, BEATS_LAG_MIN, BEATS_LAG_MAX, BEATS_PEN_STRIDE = 100, 25, 200, 301                    # mt3_op_track_beats
 BEATS_MAX_FRAMES, BEATS_TILE, BEATS_MAX_SUBDIVISIONS = 1 << 20, 1024, 48
+SYNC_CLASSES, SYNC_MAX_POOL, SYNC_HARMONICS, SYNC_LANES, SYNC_STRIP = 12, 16, 6, 1024, 16        # mt3_op_sync_paths
+SYNC_MAX_FRAMES, SYNC_MAX_CELLS = 1 << 18, 1 << 31
 
 
 class Mt3Error(RuntimeError):
@@ -146,6 +148,11 @@ class BeatsFile(C.Structure):                  # mt3_beats_file
 
 class SnapFile(C.Structure):                   # mt3_snap_file
     _fields_ = [("first", C.c_int64), ("beat0", C.c_int64), ("n_notes", C.c_int32), ("n_beats", C.c_int32)]
+
+
+class SyncFile(C.Structure):                   # mt3_sync_file
+    _fields_ = [(n, C.c_int64) for n in ("row0", "first", "a0", "s0", "path0", "work0")] + \
+               [(n, C.c_int32) for n in ("n_frames", "n_notes", "n", "m")]
 
 
 _P = C.c_void_p
@@ -371,6 +378,12 @@ SIGNATURES = {
     "mt3_op_track_beats": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, _P, _P,
                                      _P, C.c_int64, _P, _P]),
     "mt3_op_snap_notes": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mt3_sync_workspace_bytes": (C.c_int64, [_P, C.c_int32]),
+    "mt3_op_logmel_chroma": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_float, C.c_float, _P,
+                                       C.c_int64, _P]),
+    "mt3_op_note_chroma": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, _P]),
+    "mt3_op_sync_paths": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, _P,
+                                    _P, _P]),
 }
 
 _lib = None

@@ -1022,6 +1022,26 @@ class InferenceModel(object):
         return velocity.estimate(list(zip(feats, n_frames)), [ns for _, ns in pairs],
                                  frames_per_second=self.spectrogram_config.frames_per_second, **kw)
 
+    def synchronize(self, audio, ns, *, sample_rate: int = SAMPLE_RATE, sustain: bool = False, **kw):
+        """Synchronise the SCORE `ns` (quantised, another tempo, ritardandi) to the recording `audio`:
+        `synchronize_many([(audio, ns)])[0]`, a dict with 'notes' (the NoteSequence in the recording's time), 'path',
+        'total', 'mean_cost' and 'tempo_ratio' (`sync.synchronize`).  It composes with `align_notes`: `synchronize` for
+        the tempo, then `align_notes` on its 'notes' for the last +-0.2 s."""
+        return self.synchronize_many([(audio, ns)], sample_rates=[sample_rate], sustain=sustain, **kw)[0]
+
+    def synchronize_many(self, pairs, *, sample_rates: Optional[Sequence[int]] = None, sustain: bool = False, **kw):
+        """(audio, score NoteSequence) pairs as ONE job: the frontend of `__call__` on each audio (no decode is run), then
+        one `sync.synchronize` call on the log-mels, which stay on the device: chroma of the audio, chroma of the notes and
+        the dynamic-time-warping path of every file, one workgroup per file -> one dict per pair.  kw: `sync.synchronize`'s
+        keywords (pool=5, harmonic_weights=(255,), range, floor, fmin, fmax).  sustain: the sustain pedal of
+        `ns.control_changes` is applied first (`note_prep.prepare`), as `align_notes` does; 'notes' are then the sustained
+        notes, in the recording's time.  Any model type: nothing is decoded."""
+        from . import sync
+        pairs = list(pairs)
+        pairs, feats, n_frames = self._paired_examples(pairs, self._rates(sample_rates, len(pairs)), sustain)
+        return sync.synchronize(list(zip(feats, n_frames)), [ns for _, ns in pairs],
+                                frames_per_second=self.spectrogram_config.frames_per_second, **kw)
+
     @staticmethod
     def beats(ns, **kw):
         """The beats of a transcription: `mt3_amd.beats.track([ns], **kw)[0]`, a `Beats` (times in seconds, period in

@@ -66,6 +66,16 @@ def to_device(array):
     return t
 
 
+def one_buffer(tensors):
+    """the files' float32 [rows, mel] blocks as ONE device buffer: as they lie when each starts where the one before it
+    ends (slices of one tensor: the engine's job) -- then the FIRST block, whose storage the others continue -- else one
+    torch.cat"""
+    import torch
+    if all(b.data_ptr() == a.data_ptr() + a.numel() * 4 for a, b in zip(tensors, tensors[1:])):
+        return tensors[0]
+    return torch.cat([t.reshape(-1, t.shape[-1]) for t in tensors], 0)
+
+
 def upload(packed, n, dtypes) -> tuple:
     """ONE upload of a job's columns, `n` items each, `packed` back to back as `dtypes` -> (the tensor that owns them, the
     device address of every column); no items: (None, [None] * k) and nothing is uploaded"""

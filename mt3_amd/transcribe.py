@@ -6,6 +6,7 @@
                                  [--programs P[,P...]] [--no-drums] [--pianoroll [FPS]] [--render [RATE]]
                                  [--score-against DIR] [--score-midi DIR [--score-shifts S,...]]
                                  [--align-midi DIR [--align-max-shift S] [--align-step S] [--align-smoothness L]]
+                                 [--sync-midi DIR [--sync-pool P]]
                                  [--consensus N [--consensus-min-votes M] [--consensus-tolerance S]]
                                  [--sustain] [--trim-overlaps]
                                  [--velocities [--velocity-gamma G] [--velocity-anchor V]]
@@ -41,6 +42,13 @@ segment of the audio (`InferenceModel.align_notes_many`: all inputs as one job; 
 of jump between neighbouring segments) and writes the moved notes as NAME.aligned.mid beside NAME.mid, and one
 alignment.json into the output directory: a list with one record per input, in input order -- "audio", "segment_shifts",
 "path_score", "flat_shift", "flat_score" (same one-directory rule as --score-against).
+--sync-midi DIR synchronises a score to each recording: for each input NAME.wav it reads DIR/NAME.mid (a score: quantised,
+another tempo), finds the dynamic-time-warping path between the chroma of the audio and of the notes
+(`InferenceModel.synchronize_many`: all inputs as one job on the device, no decode of its own; --sync-pool P log-mel frames
+per feature frame, 1 .. 16, default 5) and writes the notes in the recording's time as NAME.synced.mid beside NAME.mid, and
+one sync.json into the output directory: a list with one record per input, in input order -- "audio", "total",
+"mean_cost", "tempo_ratio" and "path", [audio seconds, score seconds] pairs thinned to one per second of audio (same
+one-directory rule as --score-against).  It goes with every other flag: the transcription is written as without it.
 --consensus N writes as NAME.mid the notes that N sampled transcriptions of the input agree on
 (`InferenceModel.consensus_many`: N draws with the sampling parameters of --temperature / --top-k / --top-p and seeds
 --seed .. --seed + N - 1, all input files and all their draws as ONE engine job in which every segment is encoded once,
@@ -49,7 +57,7 @@ voted on the device; a note is kept when --consensus-min-votes of them have it, 
 {"n_voters": N, "min_votes": M, "notes": [...]}, one record per note of NAME.mid in the NoteSequence's order with its
 start_time, end_time, pitch, program, is_drum, votes and members.  (--well-formed-tied keeps N decodes per job.)  Not with
 --decoding beam, and not together with --confidences.
---sustain and --trim-overlaps prepare the MIDI files read for --score-against, --score-midi and --align-midi the way the
+--sustain and --trim-overlaps prepare the MIDI files read for --score-against, --score-midi, --align-midi and --sync-midi the way the
 reference prepares its targets (`mt3_amd.note_prep.prepare`, on the device, all files of an option as one job): --sustain
 applies each file's sustain pedal (controller 64) to its notes' ends -- what a piano model such as ismir2021 was trained
 on; --trim-overlaps then trims overlapping notes of one pitch and program and drops the empty ones.
@@ -132,6 +140,12 @@ def plan(argv=None):
                     "in seconds (default 0.02)")
     ap.add_argument("--align-smoothness", type=float, default=None, metavar="L",
                     help="--align-midi: log-probability a path pays per second of jump between neighbouring segments")
+    ap.add_argument("--sync-midi", default=None, metavar="DIR",
+                    help="also write NAME.synced.mid beside each NAME.mid and sync.json into the output directory: the "
+                         "score DIR/NAME.mid moved onto the time of NAME.wav by dynamic time warping of chroma features "
+                         "(same one-directory rule as --score-against)")
+    ap.add_argument("--sync-pool", type=int, default=None, metavar="P",
+                    help="--sync-midi: log-mel frames (8 ms) per feature frame, 1 .. 16 (default 5)")
     ap.add_argument("--consensus", type=int, default=None, metavar="N",
                     help="write the notes N sampled transcriptions agree on (1 .. 64) as NAME.mid, and NAME.votes.json "
                          "beside it: every note's votes and members")
@@ -209,8 +223,8 @@ def plan(argv=None):
         if args.quantize is not None and not 1 <= args.quantize <= 48:
             ap.error("--quantize takes 1 .. 48 steps per beat")
     if (args.sustain or args.trim_overlaps) and args.score_against is None and args.score_midi is None and \
-            args.align_midi is None:
-        ap.error("--sustain and --trim-overlaps need --score-against, --score-midi or --align-midi")
+            args.align_midi is None and args.sync_midi is None:
+        ap.error("--sustain and --trim-overlaps need --score-against, --score-midi, --align-midi or --sync-midi")
     for path in args.inputs:
         if not os.path.isfile(path):
             ap.error("no such file: %s" % path)
@@ -241,6 +255,15 @@ def plan(argv=None):
         if args.align_smoothness is not None and not (math.isfinite(args.align_smoothness) and args.align_smoothness >= 0):
             ap.error("--align-smoothness takes a finite number >= 0")
         args.align_max_shift, args.align_step = max_shift, step
+    if args.sync_midi is None:
+        if args.sync_pool is not None:
+            ap.error("--sync-pool needs --sync-midi")
+    else:
+        for path in args.inputs:
+            if not os.path.isfile(reference_path(args.sync_midi, path)):
+                ap.error("--sync-midi: no such file: %s" % reference_path(args.sync_midi, path))
+        if args.sync_pool is not None and not 1 <= args.sync_pool <= 16:
+            ap.error("--sync-pool takes 1 .. 16 log-mel frames")
     out = args.output
     if out is None:
         outputs = [os.path.splitext(p)[0] + ".mid" for p in args.inputs]
@@ -258,6 +281,8 @@ def plan(argv=None):
         ap.error("--score-midi writes one midi_scores.json into the output directory: inputs in several directories need -o DIR")
     if args.align_midi is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
         ap.error("--align-midi writes one alignment.json into the output directory: inputs in several directories need -o DIR")
+    if args.sync_midi is not None and len(set(os.path.dirname(os.path.abspath(p)) for p in outputs)) != 1:
+        ap.error("--sync-midi writes one sync.json into the output directory: inputs in several directories need -o DIR")
     return args, outputs
 
 
@@ -358,6 +383,16 @@ def main(argv=None) -> int:
                 rates.append(rate)
             aligned = model.align_notes_many(pairs, sample_rates=rates, max_shift=args.align_max_shift,
                                              step=args.align_step, smoothness=args.align_smoothness)
+        synced = None
+        if args.sync_midi is not None:
+            from . import audio_io
+            pairs, rates = [], []
+            for path, ns in zip(args.inputs, known_notes(args.sync_midi, args)):
+                samples, rate = audio_io.read_wav(path)
+                pairs.append((samples, ns))
+                rates.append(rate)
+            synced = model.synchronize_many(pairs, sample_rates=rates,
+                                            **({} if args.sync_pool is None else {"pool": args.sync_pool}))
     except Exception as e:                            # a file scipy cannot read, a checkpoint that does not load, ...
         print("mt3_amd.transcribe: %s: %s" % (type(e).__name__, e), file=sys.stderr)
         return 1
@@ -395,7 +430,36 @@ def main(argv=None) -> int:
             midi_io.note_sequence_to_midi_file(rec["notes"], aligned_path(path))
         with open(alignment_path(outputs), "w") as f:
             json.dump([alignment_record(path, rec) for path, rec in zip(args.inputs, aligned)], f, indent=1)
+    if synced is not None:
+        for rec, path in zip(synced, outputs):
+            midi_io.note_sequence_to_midi_file(rec["notes"], synced_path(path))
+        with open(sync_json_path(outputs), "w") as f:
+            json.dump([sync_record(path, rec) for path, rec in zip(args.inputs, synced)], f, indent=1)
     return 0
+
+
+def synced_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".synced.mid"
+
+
+def sync_json_path(outputs) -> str:
+    """sync.json of a job: beside scores.json"""
+    return os.path.join(os.path.dirname(os.path.abspath(outputs[0])), "sync.json")
+
+
+def sync_record(audio_path: str, rec) -> dict:
+    """one JSON-ready record of `InferenceModel.synchronize`: the scores and the path thinned to one anchor per second of
+    audio (the first cell at or after each whole second, and the last cell); the notes go to NAME.synced.mid"""
+    audio, score = rec["path"]
+    keep, second = [], -1
+    for k, t in enumerate(audio):
+        if int(t) > second:
+            keep.append(k)
+            second = int(t)
+    if len(audio) and keep[-1] != len(audio) - 1:
+        keep.append(len(audio) - 1)
+    return {"audio": audio_path, "total": int(rec["total"]), "mean_cost": float(rec["mean_cost"]),
+            "tempo_ratio": float(rec["tempo_ratio"]), "path": [[float(audio[k]), float(score[k])] for k in keep]}
 
 
 def velocity_keywords(args):

@@ -156,15 +156,6 @@ def pack(sequences, n_frames, rows_per_file, frames_per_second: float) -> Packed
     return Packed(note_arrays.pack(cols, NOTE_LAYOUT), int(table["n_notes"].sum()), table, int(np.sum(rows_per_file)), src)
 
 
-def _one_buffer(tensors):
-    """the files' [rows, mel] blocks as ONE device buffer: as they lie when each starts where the one before it ends
-    (slices of one tensor: the engine's job), else one torch.cat"""
-    import torch
-    if all(b.data_ptr() == a.data_ptr() + a.numel() * 4 for a, b in zip(tensors, tensors[1:])):
-        return tensors[0]
-    return torch.cat([t.reshape(-1, t.shape[-1]) for t in tensors], 0)
-
-
 def _check_table(bin_first, bins, n_mel: int):
     if len(bin_first) != N_KEYS + 1 or bin_first[0] != 0 or (np.diff(bin_first) < 0).any() or bin_first[-1] != len(bins):
         raise ValueError("bin_first must be 130 offsets that rise from 0 to len(bins)")
@@ -221,7 +212,7 @@ def estimate(logmels, sequences, *, window: int = 8, harmonics: int = 6, gamma: 
     bin_first, bins = (np.ascontiguousarray(a, np.int32) for a in table)
     _check_table(bin_first, bins, n_mel)
     packed = pack(sequences, n_frames, [t.shape[0] * t.shape[1] for t in tensors], frames_per_second)
-    level, velocity, anchor, measured = run(packed, _one_buffer(tensors), n_mel, bin_first, bins, th, int(window),
+    level, velocity, anchor, measured = run(packed, note_arrays.one_buffer(tensors), n_mel, bin_first, bins, th, int(window),
                                             float(quantile))
     out, records = [], []
     for f, (ns, rec, src) in enumerate(zip(sequences, packed.files, packed.src)):
