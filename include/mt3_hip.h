@@ -2346,6 +2346,75 @@ int mt3_op_sync_paths(const uint8_t* d_a /* [total_a][12] */, int64_t total_a, c
                       int64_t total_path, int32_t* d_path_len /* [n_files] */, int32_t* d_total /* [n_files] */,
                       void* stream);
 
+/* ---- harmony: the key, the chord of every beat, the bar length and the downbeat phase of every file of a job, from its
+ * notes and its beat frames.  Integer arithmetic throughout, so any order of the sums and integer atomics give the bits of
+ * the numpy statement (mt3_amd/harmony.py, analyze_reference).  `/` below floors, also for a negative dividend; argmax takes
+ * the LOWEST index unless said otherwise.  The feature claims parity with no library.
+ * NOTES   three int32 columns: d_start = s, d_end = e (frames at MT3_BEATS_FPS; the host rounds, e >= s + 1) and d_key =
+ *   pitch + 256 * is_drum.  A note with s < 0 or e <= s adds nothing anywhere.  h_key is the host's copy of d_key: what is
+ *   checked.  h_beats / d_beats likewise: per file n_beats strictly ascending frames b[0 .. B-1] in 0 .. 2^20 - 1.
+ * THE RULE, per file:
+ *   INTERVALS  B < 2: no chords, beats_per_bar 0, downbeat -1, chord_score 0; the key is still found.  Else interval i is
+ *     [b[i], b[i+1]) for i < B - 1, the last [b[B-1], 2 b[B-1] - b[B-2]); len[i] its length.  A note is clipped to them.
+ *   ROLL     R[i][p] = the frames the non-drum notes of pitch p share with interval i, summed over the notes (int32: n_notes
+ *     times the longest interval stays below 2^31).  H[i][c] = sum of R[i][p] over p % 12 == c, tot[i] = sum of H[i].
+ *     low[i] = the lowest p with 4 R[i][p] >= len[i], else -1;  bass[i] = low[i] % 12, else -1.
+ *   KEY      D[c] = the sum of e - s over the non-drum notes of class c (int64);  key_score[k] = sum over c of
+ *     K[k][c] * D[c], K = d_profiles int32 [24][12] (the host builds it: harmony.py, key_profiles);  key = the lowest k of
+ *     maximal score, -1 when every D is 0.
+ *   CHORDS   MT3_HARMONY_STATES = 25 states: 0 = N, 1 + 2 r + q = the major (q = 0: r, r + 4, r + 7) or minor (q = 1: r,
+ *     r + 3, r + 7) triad on r.  E[i][k] = sum over c of w_k(c) H[i][c] + (H[i][r] if bass[i] == r), w = +2 on a chord tone,
+ *     -1 elsewhere, E[i][0] = 0;  Q[i][k] = (E[i][k] * 256) / max(tot[i], 1), -256 .. 768.
+ *       V[0][k] = Q[0][k];  V[i][k] = Q[i][k] + max(V[i-1][k], M - change_penalty), M = the largest V[i-1][.] at its lowest
+ *       index j, staying on equal values;  back[i][k] = k or j.
+ *     The path ends at the lowest k of maximal V[B-1] and is read back: chords int8 [B];  chord_score = V[B-1][end]
+ *     (|V| <= 768 B + 2^20 < 2^30: int32).
+ *   METER    change[i] = (i > 0 and chords[i] != chords[i-1]);  on[i] = min(the notes, drums too, with |s - b[i]| <=
+ *     MT3_HARMONY_ONSET_WINDOW, 255);  struck[i] = some non-drum note with |s - b[i]| <= the window has pitch low[i];
+ *     a[i] = onset_weight on[i] + change_weight change[i] + bass_weight struck[i].  For m in 2, 3, 4 with B >= 2 m and f in
+ *     0 .. m - 1: num = the sum of a[i] over i % m == f, cnt = the number of such i,
+ *       score(m, f) = (num << 16) / cnt - ((sum of a - num) << 16) / (B - cnt)   (int64)
+ *     (beats_per_bar, downbeat) = the (m, f) of maximal score, the lowest m and then f on ties; (0, -1) when no m is
+ *     admissible or no score is > 0.
+ * FILES   h_files [n_files] is what is checked, d_files the same records on the device and what the kernel reads: the
+ *   notes first .. first + n_notes - 1 and the beats beat0 .. beat0 + n_beats - 1, each kind in increasing order and
+ *   without overlap.  A file's chords lie at d_chords + beat0 (not written when n_beats < 2).
+ * OUT     d_key_scores int64 [n_files][24];  d_info int32 [n_files][4] = key, chord_score, beats_per_bar, downbeat;
+ *   d_chords int8 [n_beats].  d_workspace: MT3_HARMONY_WORKSPACE_BYTES_PER_BEAT * n_beats bytes, 2-byte aligned; nothing
+ *   in it is read before it is written, so nothing needs clearing.
+ * WORK    ONE launch: a workgroup of MT3_HARMONY_NOTE_TILE lanes per file, no workgroup waits for another; the beats go
+ *   through LDS in tiles of MT3_HARMONY_BEAT_TILE intervals (mt3_amd/csrc/harmony.hip).
+ * MT3_ERR_INVALID, before any device work: n_files, n_notes or n_beats negative; a NULL pointer that the job needs; a
+ *   table that does not hold 24 * 12 entries; change_penalty outside 0 .. MT3_HARMONY_MAX_CHANGE_PENALTY, a weight outside
+ *   0 .. MT3_HARMONY_MAX_WEIGHT; a note or beat range outside its array, overlapping the one before it or out of order; a
+ *   key whose pitch is outside 0 .. 127 or that has bits above the drum flag; beat frames that do not ascend strictly
+ *   inside 0 .. 2^20 - 1; n_notes times the longest interval at or above 2^31; a short or misaligned workspace.
+ *   n_files == 0 is MT3_OK and launches nothing. */
+#define MT3_HARMONY_STATES 25
+#define MT3_HARMONY_KEYS 24
+#define MT3_HARMONY_BEAT_TILE 32
+#define MT3_HARMONY_NOTE_TILE 256
+#define MT3_HARMONY_ONSET_WINDOW 3
+#define MT3_HARMONY_MAX_CHANGE_PENALTY (1 << 20)
+#define MT3_HARMONY_MAX_WEIGHT 255
+#define MT3_HARMONY_WORKSPACE_BYTES_PER_BEAT 27
+
+typedef struct mt3_harmony_file {
+  int64_t first;                      /* the file's first note in the note columns */
+  int64_t beat0;                      /* the file's first beat in d_beats, and its first chord in d_chords */
+  int32_t n_notes;
+  int32_t n_beats;
+} mt3_harmony_file;
+
+int mt3_op_analyze_harmony(const int32_t* d_start, const int32_t* d_end, const int32_t* d_key,
+                           const int32_t* h_key /* [n_notes] */, int64_t n_notes, const int32_t* d_beats,
+                           const int32_t* h_beats /* [n_beats] */, int64_t n_beats,
+                           const mt3_harmony_file* h_files /* [n_files] */, const mt3_harmony_file* d_files,
+                           int32_t n_files, const int32_t* d_profiles /* [24][12] */, int32_t n_profiles,
+                           int32_t change_penalty, int32_t onset_weight, int32_t change_weight, int32_t bass_weight,
+                           void* d_workspace, int64_t workspace_bytes, int64_t* d_key_scores /* [n_files][24] */,
+                           int32_t* d_info /* [n_files][4] */, int8_t* d_chords /* [n_beats] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,9 @@ BEATS_FPS, BEATS_LAG_MIN, BEATS_LAG_MAX, BEATS_PEN_STRIDE = 100, 25, 200, 301   
 BEATS_MAX_FRAMES, BEATS_TILE, BEATS_MAX_SUBDIVISIONS = 1 << 20, 1024, 48
 SYNC_CLASSES, SYNC_MAX_POOL, SYNC_HARMONICS, SYNC_LANES, SYNC_STRIP = 12, 16, 6, 1024, 16        # mt3_op_sync_paths
 SYNC_MAX_FRAMES, SYNC_MAX_CELLS = 1 << 18, 1 << 31
+HARMONY_STATES, HARMONY_KEYS, HARMONY_BEAT_TILE, HARMONY_NOTE_TILE = 25, 24, 32, 256                # mt3_op_analyze_harmony
+HARMONY_ONSET_WINDOW = 3
+HARMONY_MAX_CHANGE_PENALTY, HARMONY_MAX_WEIGHT, HARMONY_WORKSPACE_BYTES_PER_BEAT = 1 << 20, 255, 27
 
 
 class Mt3Error(RuntimeError):
@@ -153,6 +156,10 @@ class SnapFile(C.Structure):                   # mt3_snap_file
 class SyncFile(C.Structure):                   # mt3_sync_file
     _fields_ = [(n, C.c_int64) for n in ("row0", "first", "a0", "s0", "path0", "work0")] + \
                [(n, C.c_int32) for n in ("n_frames", "n_notes", "n", "m")]
+
+
+class HarmonyFile(C.Structure):                # mt3_harmony_file
+    _fields_ = [("first", C.c_int64), ("beat0", C.c_int64), ("n_notes", C.c_int32), ("n_beats", C.c_int32)]
 
 
 _P = C.c_void_p
@@ -384,6 +391,8 @@ SIGNATURES = {
     "mt3_op_note_chroma": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64, _P]),
     "mt3_op_sync_paths": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, _P,
                                     _P, _P]),
+    "mt3_op_analyze_harmony": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -29,8 +29,8 @@ steps_per_second):
 
 prior_bpm (120), the prior's width (one octave), the [1, 2, 1] smoothing and the tightness are DESIGN CHOICES, not
 measurements: they were set on synthetic metrical input (DESIGN.md section 6r holds the procedure and the numbers).
-Measure them on your music.  Limits: one period per file; half / double tempo is the prior's choice; no downbeats or time
-signature (every beat is a quarter note); no triplets beyond `subdivisions`.
+Measure them on your music.  Limits: one period per file; half / double tempo is the prior's choice; every beat is a quarter
+note (downbeats and the time signature: `mt3_amd.harmony`); no triplets beyond `subdivisions`.
 
 SNAPPING (float64, every operation rounded once, no fused multiply-add).  A file's beat times b = frame / fps; with fewer
 than 2 beats its notes stay.  For a time t: i = the last beat at or before t, kept within 0 .. n - 2 (so before the first

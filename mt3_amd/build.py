@@ -20,7 +20,7 @@ OBJ = os.path.join(ROOT, "build", "obj")
 HIP_SOURCES = ["frontend.hip", "gemm.hip", "gemm_mx8.hip", "attention.hip", "enc_attention_x6.hip", "decode_ops.hip",
                "score.hip", "engine.hip", "resample.hip", "pcm.hip", "ties.hip", "pianoroll.hip", "render.hip",
                "note_match.hip", "tokenize.hip", "align.hip", "consensus.hip", "note_prep.hip", "velocity.hip",
-               "beats.hip", "sync.hip"]
+               "beats.hip", "sync.hip", "harmony.hip"]
 CPP_SOURCES = ["errors.cpp", "symbolic.cpp", "mx8_host.cpp"]
 
 

@@ -474,7 +474,7 @@ class InferenceModel(object):
         return torch.cat(out, 0)
 
     def __call__(self, audio, sample_rate: int = SAMPLE_RATE, *, programs=None, drums: bool = True, prompts=None,
-                 well_formed: bool = False, velocities=None, beats=False):
+                 well_formed: bool = False, velocities=None, beats=False, harmony=False):
         """1-d array of samples at `sample_rate` -> NoteSequence.  At 16 kHz (the default) the samples go straight to the
         frontend; at any other rate they are resampled on the device first (`_device_examples`), which replaces the
         notebook's host `wav_data_to_samples_librosa(wav, sample_rate=16000)`.
@@ -513,12 +513,20 @@ class InferenceModel(object):
         `mt3_amd.beats.track` call for all files) and every returned NoteSequence carries the attribute
         `beats`, its file's `mt3_amd.beats.Beats` (times, period, qpm, score).  The notes themselves do not change;
         `midi_io.note_sequence_to_midi_bytes(ns, beats=ns.beats.times)` writes them with the tempo map.  For known notes:
-        `InferenceModel.beats`."""
+        `InferenceModel.beats`.
+        harmony (the same four methods; default False: off, and nothing changes): with True, or a dict of
+        `harmony.analyze`'s keywords (change_penalty, onset_weight, change_weight, bass_weight), the beats are tracked
+        (it implies beats=True; a dict given as beats= still sets the tracker's keywords) and the job's notes and beats go
+        through one `mt3_amd.harmony.analyze` call for all files: every returned NoteSequence also carries
+        `harmony`, its file's `mt3_amd.harmony.Harmony` (key, chords per beat, beats_per_bar, downbeats, segments).
+        `midi_io.note_sequence_to_midi_bytes(ns, beats=ns.beats.times, harmony=ns.harmony)` writes the signatures and the
+        chord markers.  For known notes: `InferenceModel.harmony`."""
         return self._transcribe([functools.partial(self._examples, audio, sample_rate)], False,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities, beats=beats)[0]
+                                velocities=velocities, beats=beats, harmony=harmony)[0]
 
-    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, velocities=None, beats=False, **rule):
+    def _transcribe(self, make_examples, many: bool, kw, *, scored: bool = False, velocities=None, beats=False,
+                    harmony=False, **rule):
         """The one path from files to notes.  make_examples: one call per file that returns (its examples, its log-mel on
         the device); many and kw (programs, drums, prompts, well_formed) as `_job` reads them; rule: `_job`'s -- with
         draws=n the segments' n draws run as one job (row s * n + j of the job = draw j of segment s).  -> per file its
@@ -528,7 +536,10 @@ class InferenceModel(object):
         the device."""
         import torch
         velocities = self._velocity_keywords(velocities)
-        beats = self._beat_keywords(beats)
+        harmony = self._harmony_keywords(harmony)
+        beats = self._beat_keywords(True if harmony is not None and (beats is None or beats is False) else beats)
+        if harmony is not None and (scored or rule.get("draws")):
+            raise ValueError("harmony= is for the transcribing methods that return one NoteSequence per file")
         if beats is not None and (scored or rule.get("draws")):
             raise ValueError("beats= is for the transcribing methods that return one NoteSequence per file")
         files = [make() for make in make_examples]
@@ -571,7 +582,24 @@ class InferenceModel(object):
             from . import beats as beat_tracking
             for ns, found in zip(out, beat_tracking.track(out, **beats)):
                 ns.beats = found
+        if harmony is not None:
+            from . import harmony as harmony_analysis
+            for ns, found in zip(out, harmony_analysis.analyze(out, [ns.beats for ns in out], **harmony)):
+                ns.harmony = found
         return out
+
+    @staticmethod
+    def _harmony_keywords(harmony):
+        """the `harmony=` keyword of the transcribing methods -> `harmony.analyze`'s keywords, or None for off"""
+        if harmony is None or harmony is False:
+            return None
+        if harmony is True:
+            return {}
+        unknown = set(harmony) - {"change_penalty", "onset_weight", "change_weight", "bass_weight"}
+        if unknown:
+            raise ValueError("harmony= takes change_penalty, onset_weight, change_weight, bass_weight, got %s"
+                             % ", ".join(sorted(map(repr, unknown))))
+        return dict(harmony)
 
     @staticmethod
     def _beat_keywords(beats):
@@ -678,13 +706,13 @@ class InferenceModel(object):
         return [(r.notes, r, s) if return_votes else r.notes for r, s in zip(results, samples)]
 
     def transcribe_wav(self, wav_data, *, programs=None, drums: bool = True, prompts=None, well_formed: bool = False,
-                       velocities=None, beats=False):
+                       velocities=None, beats=False, harmony=False):
         """WAV bytes or path -> NoteSequence: the file-level form of `__call__`, equal to `self(*audio_io.read_wav(wav))`
         note for note.  The file's data chunk is uploaded as it is; the PCM decode, the channel mixdown and the resample
         to 16 kHz run on the device in one launch (`_wav_examples`)."""
         return self._transcribe([functools.partial(self._wav_examples, wav_data)], False,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities, beats=beats)[0]
+                                velocities=velocities, beats=beats, harmony=harmony)[0]
 
     def _count_events(self, results, tie_overflows: int):
         """the note decoder's counts of the call that just ended, summed over its files, and its wavefront's overflows"""
@@ -982,7 +1010,8 @@ class InferenceModel(object):
         return out
 
     def transcribe_many(self, audios: Sequence[Any], sample_rates: Optional[Sequence[int]] = None, *, programs=None,
-                        drums=True, prompts=None, well_formed: bool = False, velocities=None, beats=False) -> List[Any]:
+                        drums=True, prompts=None, well_formed: bool = False, velocities=None, beats=False,
+                        harmony=False) -> List[Any]:
         """Several files as ONE job (no counterpart in the notebook, which loops `model(audio)` over files): the segments of
         all files go through the engine's decode slots in one refilled call -- a finished slot restarts on the next
         segment, whichever file it belongs to -- and every file's tokens then become notes on their own (the note state
@@ -995,15 +1024,15 @@ class InferenceModel(object):
         return self._transcribe([functools.partial(self._examples, audio, sr)
                                  for audio, sr in zip(audios, self._rates(sample_rates, len(audios)))], True,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities, beats=beats)
+                                velocities=velocities, beats=beats, harmony=harmony)
 
     def transcribe_wavs(self, wavs: Sequence[Any], *, programs=None, drums=True, prompts=None,
-                        well_formed: bool = False, velocities=None, beats=False) -> List[Any]:
+                        well_formed: bool = False, velocities=None, beats=False, harmony=False) -> List[Any]:
         """WAV files (bytes or paths) as ONE job: the file-level form of `transcribe_many`, each NoteSequence identical to
         `self.transcribe_wav(wav)`.  programs / drums / prompts / velocities: as for `transcribe_many`."""
         return self._transcribe([functools.partial(self._wav_examples, wav) for wav in wavs], True,
                                 dict(programs=programs, drums=drums, prompts=prompts, well_formed=well_formed),
-                                velocities=velocities, beats=beats)
+                                velocities=velocities, beats=beats, harmony=harmony)
 
     def note_velocities(self, audio, ns, *, sample_rate: int = SAMPLE_RATE, **kw):
         """Known notes `ns` with velocities estimated from `audio`: `note_velocities_many([(audio, ns)])[0]`; with
@@ -1048,6 +1077,18 @@ class InferenceModel(object):
         10 ms frames, qpm, score), found on the device from the notes' own onsets."""
         from . import beats
         return beats.track([ns], **kw)[0]
+
+    @staticmethod
+    def harmony(ns, beats=None, **kw):
+        """The harmony and meter of known notes: `mt3_amd.harmony.analyze([ns], [beats], **kw)[0]`, a `Harmony` (key, chord
+        per beat, beats_per_bar, downbeats, chord segments).  beats: a `Beats` or beat frames; None: `ns.beats` when the
+        notes carry one, else they are tracked first (`InferenceModel.beats(ns)`)."""
+        from . import harmony
+        if beats is None:
+            beats = getattr(ns, "beats", None)
+        if beats is None:
+            beats = InferenceModel.beats(ns)
+        return harmony.analyze([ns], [beats], **kw)[0]
 
     @staticmethod
     def pianoroll(ns, fps: float = 62.5):

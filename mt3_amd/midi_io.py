@@ -17,6 +17,12 @@ Tick 0 is therefore time b[0] - m * (b[1] - b[0]) <= 0, and a file read back run
 The reader keeps every set-tempo event with its tick (on equal ticks the last one read) and converts ticks to seconds
 through the map; `midi_bytes_to_beats` returns the quarter-note ticks' times.  The tempo field is a whole number of
 microseconds, so a written interval is off by at most 0.5 us; beats on the tracker's 10 ms frames are written exactly.
+SIGNATURES AND CHORDS.  With `harmony=` (a `mt3_amd.harmony.Harmony` of the same beats; `beats=` is then required) the
+tempo map's track also gets a key-signature event FF 59 02 sf mi at tick 0 when a key was found, a time-signature event
+FF 58 04 nn 02 18 08 at tick 0 when a meter was found (nn quarter notes per bar), and a marker FF 06 with the chord's name
+on the beat of every chord change (`N` is written `N.C.`).  The preroll then grows by the fewest whole beats that put a
+downbeat on tick 0, so the bar lines of an editor fall on the downbeats.  `midi_bytes_to_signatures` reads the three kinds
+of event back with their times.
 """
 from __future__ import annotations
 
@@ -63,25 +69,48 @@ def _check_beats(beats) -> List[float]:
     return b
 
 
-def preroll(beats) -> Tuple[int, float]:
+def preroll(beats, harmony=None) -> Tuple[int, float]:
     """(m, t0) of a tempo map written from `beats`: the whole beats inserted before the first one, and the time of tick 0,
-    b[0] - m * (b[1] - b[0]) <= 0"""
+    b[0] - m * (b[1] - b[0]) <= 0.  With a `harmony` that has a meter, m is the smallest such number that also puts a
+    downbeat on tick 0: (m + harmony.downbeat) % harmony.beats_per_bar == 0"""
     b = _check_beats(beats)
     m = max(int(math.ceil(b[0] / (b[1] - b[0]))), 0)
     while b[0] - m * (b[1] - b[0]) > 0:                      # (the quotient was rounded down across a whole number)
         m += 1
+    if harmony is not None and harmony.beats_per_bar:
+        m += -(m + harmony.downbeat) % harmony.beats_per_bar
     return m, b[0] - m * (b[1] - b[0])
 
 
-def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM, beats: Optional[Sequence[float]] = None) -> bytes:
+def _harmony_events(harmony, n_beats: int, m: int, res: int) -> List[Tuple[int, int, bytes]]:
+    """the key signature, the time signature (both before the tempo at tick 0) and the chord markers of one `Harmony`"""
+    if len(harmony.chords) != n_beats:
+        raise ValueError("harmony has %d chords for %d beats" % (len(harmony.chords), n_beats))
+    from .harmony import chord_name
+    events = []
+    if harmony.key >= 0:
+        events.append((0, -2, b"\xff\x59\x02" + struct.pack(">bB", harmony.sharps, harmony.key % 2)))
+    if harmony.beats_per_bar:
+        events.append((0, -1, b"\xff\x58\x04" + bytes([harmony.beats_per_bar, 2, 24, 8])))
+    for i, state in enumerate(harmony.chords):
+        if i == 0 or state != harmony.chords[i - 1]:
+            name = chord_name(state, harmony.key).encode("ascii") if state else b"N.C."
+            events.append(((m + i) * res, 1, b"\xff\x06" + _vlq(len(name)) + name))
+    return events
+
+
+def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM, beats: Optional[Sequence[float]] = None,
+                                harmony=None) -> bytes:
     res = ns.ticks_per_quarter or 220
+    if harmony is not None and beats is None:
+        raise ValueError("harmony= needs the beats it was found on: pass beats= too")
     if beats is None:
         to_tick = lambda t: int(round(t * res * qpm / 60.0))  # noqa: E731
         tempo = int(round(60_000_000 / qpm))
         tracks = [_track([_tempo_event(0, tempo)])]
     else:
         b = _check_beats(beats)
-        m = preroll(b)[0]
+        m = preroll(b, harmony)[0]
 
         def to_tick(t):
             i = min(max(bisect.bisect_right(b, t) - 1, 0), len(b) - 2)
@@ -90,6 +119,8 @@ def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM, beat
         conductor = [_tempo_event((m + i) * res, int(round(1e6 * (b[i + 1] - b[i])))) for i in range(len(b) - 1)]
         if m:
             conductor.append(_tempo_event(0, int(round(1e6 * (b[1] - b[0])))))
+        if harmony is not None:
+            conductor += _harmony_events(harmony, len(b), m, res)
         tracks = [_track(conductor)]
     groups: Dict[Tuple[int, int, bool], List[Note]] = {}
     for n in ns.notes:
@@ -116,9 +147,9 @@ def note_sequence_to_midi_bytes(ns: NoteSequence, qpm: float = DEFAULT_QPM, beat
 
 
 def note_sequence_to_midi_file(ns: NoteSequence, path: str, qpm: float = DEFAULT_QPM,
-                               beats: Optional[Sequence[float]] = None) -> None:
+                               beats: Optional[Sequence[float]] = None, harmony=None) -> None:
     with open(path, "wb") as f:
-        f.write(note_sequence_to_midi_bytes(ns, qpm, beats))
+        f.write(note_sequence_to_midi_bytes(ns, qpm, beats, harmony))
 
 
 sequence_proto_to_midi_file = note_sequence_to_midi_file       # note_seq's name for it
@@ -142,8 +173,9 @@ class _TempoMap:
         return self.seconds[k] + (tick - self.ticks[k]) * self.tempos[k] / 1e6 / self.res
 
 
-def _parse(data: bytes):
-    """-> (resolution, notes, controllers, tempo events, the last event's tick), everything in ticks"""
+def _parse(data: bytes, metas: Optional[list] = None):
+    """-> (resolution, notes, controllers, tempo events, the last event's tick), everything in ticks; every key-signature,
+    time-signature and marker event is also appended to `metas` as (tick, kind, payload)"""
     assert data[:4] == b"MThd"
     _, fmt, ntrk, res = struct.unpack(">IHHH", data[4:14])
     pos, tempos, last_tick = 14, [], 0
@@ -169,6 +201,8 @@ def _parse(data: bytes):
                 kind, ln2 = body[i], body[i + 1]
                 if kind == 0x51:
                     tempos.append((tick, int.from_bytes(body[i + 2:i + 5], "big")))
+                if kind in (0x59, 0x58, 0x06) and metas is not None:
+                    metas.append((tick, kind, bytes(body[i + 2:i + 2 + ln2])))
                 if kind != 0x2F:
                     last_tick = max(last_tick, tick)
                 i += 2 + ln2
@@ -224,3 +258,22 @@ def midi_bytes_to_beats(data: bytes) -> List[float]:
     res, _, _, tempos, last_tick = _parse(data)
     sec = _TempoMap(tempos, res)
     return [sec(tick) for tick in range(0, last_tick + 1, res)]
+
+
+def midi_bytes_to_signatures(data: bytes) -> Dict[str, list]:
+    """The key signatures, time signatures and markers of a file, each in file order with its time in seconds through the
+    tempo map: {"key_signatures": [(time, sharps, mode)], "time_signatures": [(time, numerator, denominator)],
+    "markers": [(time, text)]}.  sharps is -7 .. 7, mode 0 major / 1 minor; the denominator is the note value (4: quarters).
+    Events shorter than their kind's payload are skipped."""
+    metas: list = []
+    res, _, _, tempos, _ = _parse(data, metas)
+    sec = _TempoMap(tempos, res)
+    out: Dict[str, list] = {"key_signatures": [], "time_signatures": [], "markers": []}
+    for tick, kind, payload in metas:
+        if kind == 0x59 and len(payload) >= 2:
+            out["key_signatures"].append((sec(tick), struct.unpack(">b", payload[:1])[0], payload[1]))
+        elif kind == 0x58 and len(payload) >= 2:
+            out["time_signatures"].append((sec(tick), payload[0], 1 << payload[1]))
+        elif kind == 0x06:
+            out["markers"].append((sec(tick), payload.decode("latin-1")))
+    return out

@@ -11,6 +11,7 @@
                                  [--sustain] [--trim-overlaps]
                                  [--velocities [--velocity-gamma G] [--velocity-anchor V]]
                                  [--beats [--beats-prior-bpm B] [--quantize SUBDIV]]
+                                 [--harmony [--harmony-change-penalty P]]
                                  IN.wav [IN2.wav ...] [-o OUT]
 
 Writes IN.mid beside each input, or to OUT: a file for one input, a directory for several.  All inputs go through the
@@ -72,6 +73,12 @@ with the tempo map -- a set-tempo event on every beat, every beat one quarter no
 opens on the grid of a notation editor -- and NAME.beats.json beside it: {"qpm", "period_frames", "beats": [seconds]}.
 An input in which no beat is found keeps the constant 120 qpm.  --quantize SUBDIV first moves the notes onto the grid of
 SUBDIV steps per beat (1 .. 48; `mt3_amd.beats.snap`), before NAME.mid, --render and --pianoroll are written.
+--harmony (it implies --beats) finds each input's key, the chord of every beat, the bar length and the downbeats from its
+notes and beats (`mt3_amd.harmony.analyze`: all inputs as one job on the device; --harmony-change-penalty P, 0 .. 2^20,
+default 857: what the chord path pays for a change) and writes NAME.mid with a key signature, a time signature and a marker
+per chord change in the tempo map's track, tick 0 on a downbeat, and NAME.harmony.json beside it: {"key", "key_name",
+"sharps", "beats_per_bar", "downbeat", "downbeats": [seconds], "chords": [[start, end, name]]}.  With --quantize the
+analysis reads the notes as they are written, on the grid.
 """
 from __future__ import annotations
 
@@ -174,6 +181,11 @@ def plan(argv=None):
                     help="--beats: the centre of the tempo prior in beats per minute (default 120)")
     ap.add_argument("--quantize", type=int, default=None, metavar="SUBDIV",
                     help="--beats: move the notes onto the grid of SUBDIV steps per beat (1 .. 48) first")
+    ap.add_argument("--harmony", action="store_true",
+                    help="find each input's key, chords, bar length and downbeats (implies --beats) and write NAME.mid with "
+                         "the key and time signatures and chord markers, and NAME.harmony.json beside it")
+    ap.add_argument("--harmony-change-penalty", type=int, default=None, metavar="P",
+                    help="--harmony: what the chord path pays for a change of chord, 0 .. 1048576 (default 857)")
     ap.add_argument("-o", "--output", help="output file (one input) or directory (several)")
     ap.add_argument("inputs", nargs="+", metavar="IN.wav")
     args = ap.parse_args(argv)
@@ -213,6 +225,13 @@ def plan(argv=None):
             v = getattr(args, name)
             if v is not None and not (math.isfinite(v) and v > 0):
                 ap.error("--%s takes a finite number > 0" % name.replace("_", "-"))
+    if not args.harmony:
+        if args.harmony_change_penalty is not None:
+            ap.error("--harmony-change-penalty needs --harmony")
+    else:
+        args.beats = True
+        if args.harmony_change_penalty is not None and not 0 <= args.harmony_change_penalty <= 1 << 20:
+            ap.error("--harmony-change-penalty takes 0 .. 1048576")
     if not args.beats:
         for name in ("beats_prior_bpm", "quantize"):
             if getattr(args, name) is not None:
@@ -347,6 +366,11 @@ def main(argv=None) -> int:
             found = beats.track(sequences, **({} if args.beats_prior_bpm is None else {"prior_bpm": args.beats_prior_bpm}))
             if args.quantize is not None:
                 sequences = beats.snap(sequences, found, args.quantize)
+        analyzed = None
+        if args.harmony:
+            from . import harmony
+            analyzed = harmony.analyze(sequences, found, **({} if args.harmony_change_penalty is None else
+                                                            {"change_penalty": args.harmony_change_penalty}))
         rolls = None
         if args.pianoroll is not None:
             import numpy as np
@@ -399,8 +423,12 @@ def main(argv=None) -> int:
     for i, (ns, path) in enumerate(zip(sequences, outputs)):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         mapped = found is not None and len(found[i].times) >= 2
-        midi_io.note_sequence_to_midi_file(ns, path, beats=found[i].times if mapped else None)
+        midi_io.note_sequence_to_midi_file(ns, path, beats=found[i].times if mapped else None,
+                                           harmony=analyzed[i] if mapped and analyzed is not None else None)
         print("%s: %d notes" % (path, len(ns.notes)))
+    for rec, path in zip(analyzed or [], outputs):
+        with open(harmony_path(path), "w") as f:
+            json.dump(harmony_record(rec), f, indent=1)
     for rec, path in zip(found or [], outputs):
         with open(beats_path(path), "w") as f:
             json.dump(beats_record(rec), f, indent=1)
@@ -490,6 +518,17 @@ def beats_path(midi_path: str) -> str:
 def beats_record(rec) -> dict:
     """the JSON-ready form of one `beats.Beats`"""
     return {"qpm": float(rec.qpm), "period_frames": int(rec.period), "beats": [float(t) for t in rec.times]}
+
+
+def harmony_path(midi_path: str) -> str:
+    return os.path.splitext(midi_path)[0] + ".harmony.json"
+
+
+def harmony_record(rec) -> dict:
+    """the JSON-ready form of one `harmony.Harmony`"""
+    return {"key": int(rec.key), "key_name": rec.key_name, "sharps": int(rec.sharps), "beats_per_bar": int(rec.beats_per_bar),
+            "downbeat": int(rec.downbeat), "downbeats": [float(t) for t in rec.downbeats],
+            "chords": [[float(a), float(b), name] for a, b, name in rec.segments]}
 
 
 def votes_path(midi_path: str) -> str:
